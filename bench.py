@@ -7,13 +7,19 @@ frontend kernel -> conv1 -> conv2 -> fc1 -> fc2 -> classifier -> logits (+ for N
 all-gather of the per-clip logits, the path's only exchange).  Weak scaling: every rank holds its
 own 4096 clips.  PCM is resident in HBM before the timed region.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract fields + "roofline" for the dominant kernel, measured
-with HIP events on the launch stream inside the timed region, + "cpu_baseline": the numpy oracle
-of the same workload timed on the host cores; kind "port").
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one
+timed step) with the workload's description.  --dump-outputs DIR writes the logits of the last timed
+step, as a caller of the path receives them, to DIR/logits.npy (float32; inputs are seeded, so runs
+with the same arguments see the same clips).  --full adds what the headline does not need: HIP events
+on every --profile-every-th timed step for "kernel_ms" / "roofline" of the dominant kernel, the
+correctness guard and "max_abs_dlogit" against the oracle, the self-audit legs (other arithmetics,
+PCIe-inclusive rate, rotating PCM buffers, the other BASELINE configs, sustained loop) and
+"cpu_baseline": the numpy oracle of the same workload timed on the host cores (kind "port").
 """
 import argparse
 import glob
@@ -54,12 +60,17 @@ def parse():
                          "16-bit mode that holds 1e-2 on every test clip, bf16 the lower-accuracy variant; BASELINE.md)")
     ap.add_argument("--conv-arith", default="f16x3", choices=["f32", "bf16x9", "bf16x6", "f16x3"],
                     help="arithmetic of the MFMA contractions (all float32-grade; nww_config.conv_arith; the library default is f16x3)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel profile and roofline, correctness guard and oracle check, self-audit "
+                         "legs, CPU baseline (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     ap.add_argument("--profile-every", type=int, default=4,
-                    help="HIP events around the launches of every n-th timed step (an event per launch boundary costs the "
+                    help="--full: HIP events around the launches of every n-th timed step (an event per launch boundary costs the "
                          "stream ~10 us: n = 1 slows the timed loop by ~10 %%)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the self-audit legs (other conv arithmetics, the other BASELINE configs, PCIe-inclusive rate, sustained loop); N=1 only anyway")
+                    help="--full: skip the self-audit legs (other conv arithmetics, the other BASELINE configs, PCIe-inclusive rate, sustained loop); N=1 only anyway")
     ap.add_argument("--sustain-seconds", type=float, default=6.5)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--global-batch", type=int, default=0,
@@ -71,7 +82,10 @@ def parse():
     ap.add_argument("--debug-single-gpu", action="store_true",
                     help="control-flow check of the N>1 path on a 1-GPU box: every rank uses cuda:0 and the gather "
                          "runs over gloo on host copies (never a measurement)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def _cpu_model():
@@ -264,6 +278,102 @@ def leg_roofline(cfg, fe, B, prof, act_bytes=4):
         out["peak_definition"] = "dense 16-bit MFMA peak / 3 partial products per float32 product (default arithmetic f16x3)"
     out.update({"bound": bound, "achieved": round(ach, 2), "peak": peak, "unit": unit, "frac": round(ach / peak, 4)})
     return out
+
+
+def headline_roofline(cfg, fe, B, N, arith, prof):
+    """--full fields of the headline step from the timed loop's per-launch profile: "roofline" of the dominant kernel (largest share
+    of device time in the timed region), "kernel_ms" and "stft_stage"."""
+    from nanowakeword_amd.config import head_macs
+    per = [(n.split(" [")[0], ms / max(c, 1), c, ms) for (n, ms, c) in prof if c > 0]      # " [f16x3]" marks a step's arithmetic
+    dom = max(per, key=lambda r: r[3])
+    kernel_ms = {n: round(avg, 4) for (n, avg, c, tot) in per}
+    T, n_mels = 101, fe.n_mels
+    algo = {   # algorithmic work per LAUNCH (B clips): DESIGN.md "Kernels"
+        "frontend:fe_stft_mel_db_kernel": ("hbm", B * (2 * N + 4 * n_mels * T) / 1e9, "GB/s", PEAK_HBM_GBS),
+    }
+    if cfg.model_type == "cnn":
+        H1, W1 = T // 2, n_mels // 2
+        algo["conv3x3:conv1"] = ("mfma", B * 2 * 9 * 1 * 16 * (2 * H1) * (2 * W1) / 1e12, "TFLOP/s", PEAK_F32_TFLOPS)
+        algo["conv3x3:conv2"] = ("mfma", B * 2 * 9 * 16 * 32 * (2 * (H1 // 2)) * (2 * (W1 // 2)) / 1e12, "TFLOP/s", PEAK_F32_TFLOPS)
+        algo["gemm:fc1"] = ("mfma", B * 2 * 32 * (T // 4) * (n_mels // 4) * 128 / 1e12, "TFLOP/s", PEAK_F32_TFLOPS)
+        # fused trunk: conv1 on the 2*H1 x 2*W1 positions that survive the floor pooling + conv2 on 2*H2 x 2*W2
+        algo["trunk:conv1+pool+conv2+pool"] = ("mfma", algo["conv3x3:conv1"][1] + algo["conv3x3:conv2"][1], "TFLOP/s", PEAK_F32_TFLOPS)
+        # trunk_x3: BOTH convolutions run as P bf16 partial products per float32 product on v_mfma_f32_32x32x16_bf16
+        # (trunk_b.hip), so the matrix-pipe speed of light for the algorithmic (float32-equivalent) flops is bf16_peak / P.
+        P = {"bf16x6": 6, "bf16x9": 9, "f16x3": 3}.get(arith, 6)
+        f1, f2 = algo["conv3x3:conv1"][1], algo["conv3x3:conv2"][1]
+        algo["trunk_x3:conv1+pool+conv2+pool"] = ("mfma", f1 + f2, "TFLOP/s", round(PEAK_BF16_TFLOPS / P, 1))
+    name = dom[0]
+    if name in algo:
+        bound, work, unit, peak = algo[name]
+        achieved = work / (dom[1] * 1e-3)
+    else:
+        bound, unit, peak = "mfma", "TFLOP/s", PEAK_F32_TFLOPS
+        achieved = B * 2 * head_macs(cfg) / 1e12 / (sum(r[1] for r in per if not r[0].startswith("frontend")) * 1e-3)
+    traffic = None
+    tp = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tp):
+        try:
+            tj = json.load(open(tp))
+            ent = tj.get(name)
+            if ent and ent.get("batch") == B:
+                traffic = ent["hbm_bytes_per_launch"]
+        except Exception:
+            traffic = None
+    roofline = {"kernel": name, "bound": bound, "achieved": round(achieved, 3), "peak": peak, "unit": unit,
+                "frac": round(achieved / peak, 4), "traffic": traffic,
+                "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this kernel at this batch "
+                                  "(tools/collect_profiles.py), not measured in this run" if traffic is not None else None,
+                "avg_launch_ms": round(dom[1], 4), "launches": dom[2]}
+    if name.startswith("trunk_x3"):
+        P = {"bf16x6": 6, "bf16x9": 9, "f16x3": 3}.get(arith, 6)
+        f1, f2 = algo["conv3x3:conv1"][1], algo["conv3x3:conv2"][1]
+        roofline["peak_definition"] = (f"dense bf16 / f16 MFMA peak ({PEAK_BF16_TFLOPS:.0f} TFLOP/s) / {P} partial products per float32 product: "
+                                       "both convolutions are issued as split-operand 16-bit MFMAs")
+        # rounds 2-3 priced conv1 at the f32-MFMA rate (it ran there in round 2); kept only so that rounds compare
+        peak_r2 = (f1 + f2) / (f1 / PEAK_F32_TFLOPS + f2 / (PEAK_BF16_TFLOPS / P))
+        roofline["frac_round2_definition"] = round(achieved / peak_r2, 4)
+        roofline["note"] = ("peaks assume the 2.4 GHz boost clock; with all 256 CUs busy this kernel runs power-limited at "
+                            "1.9-2.0 GHz (tools/ubench/trunk_trace.hip, DESIGN.md 4.10)")
+        # back-to-back bf16 MFMAs with toggling operands on all 256 CUs sustain 5.63e10 wave-instructions per second of the
+        # nominal 7.68e10 (1.85 GHz at the package's power limit; tools/ubench/power_mix.hip mode 4, DESIGN 4.10)
+        roofline["frac_of_sustained_matrix_rate"] = round(achieved / peak / (5.63 / 7.68), 4)
+        # how busy the two pipes the kernel is limited by actually are, from the committed PMC pass of this kernel at this batch
+        # (profiles/traffic.json) and the live launch time: with the two-term arithmetic the matrix pipe is no longer the only
+        # limiter - the launch takes about the SUM of its matrix time and its VALU time (DESIGN.md 2)
+        try:
+            ent = json.load(open(tp)).get(name) or {}
+            if ent.get("batch") == B and ent.get("sq_insts_mfma"):
+                cyc = 1024 * dom[1] * 1e-3 * 2.4e9
+                roofline["mfma_busy_frac_at_2.4GHz"] = round(ent["sq_insts_mfma"] * 32 / cyc, 4)
+                roofline["valu_issue_frac_at_2.4GHz"] = round(ent["sq_insts_valu"] * 4 / cyc, 4)
+                roofline["pipe_counters_source"] = "SQ_INSTS_MFMA x 32 clocks, SQ_INSTS_VALU x 4 clocks (profiles/traffic.json) / (1024 SIMDs x avg_launch_ms x 2.4 GHz)"
+        except Exception:
+            pass
+        roofline["vs_f32_mfma_peak"] = round(achieved / PEAK_F32_TFLOPS, 3)      # the float32 products per second against the chip's float32 matrix peak
+    fe_row = [r for r in per if r[0].startswith("frontend")]
+    extra = {}
+    if fe_row:
+        fe_ms = fe_row[0][1]
+        fe_gbs = B * (2 * N + 4 * n_mels * T) / 1e9 / (fe_ms * 1e-3)
+        extra["stft_stage"] = {"bound": "hbm", "achieved": round(fe_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                               "frac": round(fe_gbs / PEAK_HBM_GBS, 4),
+                               "f32_tflops": round(B * 1.27e6 / 1e12 / (fe_ms * 1e-3), 2),
+                               "clips_per_s_stage": round(B / (fe_ms * 1e-3), 0), "avg_launch_ms": round(fe_ms, 4)}
+        # The stage's BINDING roofline is VALU issue, not HBM: SQ_INSTS_VALU wave-instructions (rocprofv3 --pmc pass of this
+        # kernel at this batch, profiles/traffic.json) x 4 clocks each / (1024 SIMDs x the live launch time x 2.4 GHz)
+        try:
+            ent = json.load(open(os.path.join(ROOT, "profiles", "traffic.json"))).get("frontend:fe_stft_mel_db_kernel", {})
+            if ent.get("batch") == B and ent.get("sq_insts_valu"):
+                n_simd, clk = 1024, 2.4e9
+                extra["stft_stage"]["valu_issue_frac"] = round(ent["sq_insts_valu"] * 4 / (n_simd * fe_ms * 1e-3 * clk), 4)
+                extra["stft_stage"]["valu_issue_source"] = (f"SQ_INSTS_VALU {ent['sq_insts_valu']:.4g} per launch (profiles/traffic.json, rocprofv3 --pmc) "
+                                                            "x 4 clocks / (1024 SIMDs x avg_launch_ms x 2.4 GHz)")
+                extra["stft_stage"]["binding"] = "valu_issue"
+                extra["stft_stage"]["binding_frac"] = extra["stft_stage"]["valu_issue_frac"]      # the stage's fraction of its REAL roof
+        except Exception:
+            pass
+    return {"roofline": roofline, "kernel_ms": kernel_ms, **extra}
 
 
 def config_legs(torch, dev):
@@ -480,7 +590,7 @@ def main():
     a = parse()
     import torch
     import torch.distributed as dist
-    from nanowakeword_amd.config import FrontendConfig, HeadConfig, head_macs
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
     from nanowakeword_amd.session import HipModel, torchaudio_tables
     from nanowakeword_amd.synth import synth_pcm, synth_state_dict
 
@@ -522,8 +632,8 @@ def main():
     pcm = torch.from_numpy(pcm_host).to(dev)               # resident in HBM before timing
     # The timed loop re-reads ONE 131 MB batch (as in rounds 1-5: comparable), which fits the 256 MiB Infinity Cache - said on the line;
     # the `pcm_rotation` leg times the same step walking THREE copies of the batch (same clips, distinct addresses: 393 MB), so that the
-    # frontend's reads come from HBM every step
-    pcm_ring = [pcm] + ([pcm.clone() for _ in range(2)] if world == 1 else [pcm, pcm])
+    # frontend's reads come from HBM every step (--full)
+    pcm_ring = [pcm] + ([pcm.clone() for _ in range(2)] if world == 1 and a.full else [pcm, pcm])
     logits = torch.empty(B, dtype=torch.float32, device=dev)
     gdev = torch.device("cpu") if a.debug_single_gpu else dev
     gathered = torch.empty(B * world, dtype=torch.float32, device=gdev) if world > 1 else None
@@ -583,7 +693,8 @@ def main():
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize(dev)
-    model.set_profiling(max(1, a.profile_every))
+    if a.full:
+        model.set_profiling(max(1, a.profile_every))
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -597,130 +708,49 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    prof = model.get_profile()
-    model.set_profiling(False)
+    prof = None
+    if a.full:
+        prof = model.get_profile()
+        model.set_profiling(False)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=gdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # ---- correctness guard on the timed buffers (cheap): finite, and first clips == small-batch run
-    lg = logits.cpu().numpy()
-    if world > 1:       # every rank's shard must sit at its slot of the gathered vector(s), and every rank must hold the same vector
-        for gbuf in (gathered2 if gathered2 else [gathered]):
-            gv = gbuf.cpu().numpy()
-            assert np.array_equal(gv[rank * B:(rank + 1) * B], lg), "all-gather placed a shard wrongly"
-            chk = torch.tensor([float(np.float64(gv.astype(np.float64).sum()))], dtype=torch.float64, device=gdev)
-            lo, hi = chk.clone(), chk.clone()
-            dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-            assert float(lo.item()) == float(hi.item()), "ranks hold different gathered vectors"
-    assert np.isfinite(lg).all()
-    l8, _ = model.forward_pcm(pcm_host[:8])
-    assert np.array_equal(l8, lg[:8]), "batch-size dependence in the timed path"
-    # the headline configuration's own max |dlogit| against the oracle (checker only; 16 clips of the timed batch, CPU, outside the timed region)
-    max_dlogit = None
-    if rank == 0:
-        import oracle
-        nchk = 16
-        lm = oracle.frontend_logmel(pcm_host[:nchk], window, fb)
-        if cfg.model_type != "e2e_dnn":
-            lm = lm.transpose(0, 2, 1)
-        ref = oracle.model_forward(np.ascontiguousarray(lm), sd, cfg).ravel()
-        max_dlogit = float(np.abs(lg[:nchk] - ref).max())
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: this rank's logits at N = 1, the gathered vector at N > 1
+        last = gathered2[(step_no[0] - 1) & 1] if gathered2 else (gathered if world > 1 else logits)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "logits.npy"), last.cpu().numpy().astype(np.float32))
+
+    max_dlogit = lg = None
+    if a.full:
+        # ---- correctness guard on the timed buffers (cheap): finite, and first clips == small-batch run
+        lg = logits.cpu().numpy()
+        if world > 1:       # every rank's shard must sit at its slot of the gathered vector(s), and every rank must hold the same vector
+            for gbuf in (gathered2 if gathered2 else [gathered]):
+                gv = gbuf.cpu().numpy()
+                assert np.array_equal(gv[rank * B:(rank + 1) * B], lg), "all-gather placed a shard wrongly"
+                chk = torch.tensor([float(np.float64(gv.astype(np.float64).sum()))], dtype=torch.float64, device=gdev)
+                lo, hi = chk.clone(), chk.clone()
+                dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+                assert float(lo.item()) == float(hi.item()), "ranks hold different gathered vectors"
+        assert np.isfinite(lg).all()
+        l8, _ = model.forward_pcm(pcm_host[:8])
+        assert np.array_equal(l8, lg[:8]), "batch-size dependence in the timed path"
+        # the headline configuration's own max |dlogit| against the oracle (checker only; 16 clips of the timed batch, CPU, outside the timed region)
+        if rank == 0:
+            import oracle
+            nchk = 16
+            lm = oracle.frontend_logmel(pcm_host[:nchk], window, fb)
+            if cfg.model_type != "e2e_dnn":
+                lm = lm.transpose(0, 2, 1)
+            ref = oracle.model_forward(np.ascontiguousarray(lm), sd, cfg).ravel()
+            max_dlogit = float(np.abs(lg[:nchk] - ref).max())
 
     if rank == 0:
         ms_step = dt / a.steps * 1e3
         value = B * world * a.steps / dt
-        # ---- roofline of the dominant kernel (largest share of device time in the timed region)
-        per = [(n.split(" [")[0], ms / max(c, 1), c, ms) for (n, ms, c) in prof if c > 0]      # " [f16x3]" marks a step's arithmetic
-        dom = max(per, key=lambda r: r[3])
-        kernel_ms = {n: round(avg, 4) for (n, avg, c, tot) in per}
-        T, n_mels = 101, fe.n_mels
-        algo = {   # algorithmic work per LAUNCH (B clips): DESIGN.md "Kernels"
-            "frontend:fe_stft_mel_db_kernel": ("hbm", B * (2 * N + 4 * n_mels * T) / 1e9, "GB/s", PEAK_HBM_GBS),
-        }
-        if cfg.model_type == "cnn":
-            H1, W1 = T // 2, n_mels // 2
-            algo["conv3x3:conv1"] = ("mfma", B * 2 * 9 * 1 * 16 * (2 * H1) * (2 * W1) / 1e12, "TFLOP/s", PEAK_F32_TFLOPS)
-            algo["conv3x3:conv2"] = ("mfma", B * 2 * 9 * 16 * 32 * (2 * (H1 // 2)) * (2 * (W1 // 2)) / 1e12, "TFLOP/s", PEAK_F32_TFLOPS)
-            algo["gemm:fc1"] = ("mfma", B * 2 * 32 * (T // 4) * (n_mels // 4) * 128 / 1e12, "TFLOP/s", PEAK_F32_TFLOPS)
-            # fused trunk: conv1 on the 2*H1 x 2*W1 positions that survive the floor pooling + conv2 on 2*H2 x 2*W2
-            algo["trunk:conv1+pool+conv2+pool"] = ("mfma", algo["conv3x3:conv1"][1] + algo["conv3x3:conv2"][1], "TFLOP/s", PEAK_F32_TFLOPS)
-            # trunk_x3: BOTH convolutions run as P bf16 partial products per float32 product on v_mfma_f32_32x32x16_bf16
-            # (trunk_b.hip), so the matrix-pipe speed of light for the algorithmic (float32-equivalent) flops is bf16_peak / P.
-            P = {"bf16x6": 6, "bf16x9": 9, "f16x3": 3}.get(arith, 6)
-            f1, f2 = algo["conv3x3:conv1"][1], algo["conv3x3:conv2"][1]
-            algo["trunk_x3:conv1+pool+conv2+pool"] = ("mfma", f1 + f2, "TFLOP/s", round(PEAK_BF16_TFLOPS / P, 1))
-        name = dom[0]
-        if name in algo:
-            bound, work, unit, peak = algo[name]
-            achieved = work / (dom[1] * 1e-3)
-        else:
-            bound, unit, peak = "mfma", "TFLOP/s", PEAK_F32_TFLOPS
-            achieved = B * 2 * head_macs(cfg) / 1e12 / (sum(r[1] for r in per if not r[0].startswith("frontend")) * 1e-3)
-        traffic = None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tp):
-            try:
-                tj = json.load(open(tp))
-                ent = tj.get(name)
-                if ent and ent.get("batch") == B:
-                    traffic = ent["hbm_bytes_per_launch"]
-            except Exception:
-                traffic = None
-        roofline = {"kernel": name, "bound": bound, "achieved": round(achieved, 3), "peak": peak, "unit": unit,
-                    "frac": round(achieved / peak, 4), "traffic": traffic,
-                    "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this kernel at this batch "
-                                      "(tools/collect_profiles.py), not measured in this run" if traffic is not None else None,
-                    "avg_launch_ms": round(dom[1], 4), "launches": dom[2]}
-        if name.startswith("trunk_x3"):
-            P = {"bf16x6": 6, "bf16x9": 9, "f16x3": 3}.get(arith, 6)
-            f1, f2 = algo["conv3x3:conv1"][1], algo["conv3x3:conv2"][1]
-            roofline["peak_definition"] = (f"dense bf16 / f16 MFMA peak ({PEAK_BF16_TFLOPS:.0f} TFLOP/s) / {P} partial products per float32 product: "
-                                           "both convolutions are issued as split-operand 16-bit MFMAs")
-            # rounds 2-3 priced conv1 at the f32-MFMA rate (it ran there in round 2); kept only so that rounds compare
-            peak_r2 = (f1 + f2) / (f1 / PEAK_F32_TFLOPS + f2 / (PEAK_BF16_TFLOPS / P))
-            roofline["frac_round2_definition"] = round(achieved / peak_r2, 4)
-            roofline["note"] = ("peaks assume the 2.4 GHz boost clock; with all 256 CUs busy this kernel runs power-limited at "
-                                "1.9-2.0 GHz (tools/ubench/trunk_trace.hip, DESIGN.md 4.10)")
-            # back-to-back bf16 MFMAs with toggling operands on all 256 CUs sustain 5.63e10 wave-instructions per second of the
-            # nominal 7.68e10 (1.85 GHz at the package's power limit; tools/ubench/power_mix.hip mode 4)
-            roofline["frac_of_sustained_matrix_rate"] = round(achieved / peak / (5.63 / 7.68), 4)
-            # how busy the two pipes the kernel is limited by actually are, from the committed PMC pass of this kernel at this batch
-            # (profiles/traffic.json) and the live launch time: with the two-term arithmetic the matrix pipe is no longer the only
-            # limiter - the launch takes about the SUM of its matrix time and its VALU time
-            try:
-                ent = json.load(open(tp)).get(name) or {}
-                if ent.get("batch") == B and ent.get("sq_insts_mfma"):
-                    cyc = 1024 * dom[1] * 1e-3 * 2.4e9
-                    roofline["mfma_busy_frac_at_2.4GHz"] = round(ent["sq_insts_mfma"] * 32 / cyc, 4)
-                    roofline["valu_issue_frac_at_2.4GHz"] = round(ent["sq_insts_valu"] * 4 / cyc, 4)
-                    roofline["pipe_counters_source"] = "SQ_INSTS_MFMA x 32 clocks, SQ_INSTS_VALU x 4 clocks (profiles/traffic.json) / (1024 SIMDs x avg_launch_ms x 2.4 GHz)"
-            except Exception:
-                pass
-            roofline["vs_f32_mfma_peak"] = round(achieved / PEAK_F32_TFLOPS, 3)      # the float32 products per second against the chip's float32 matrix peak
-        fe_row = [r for r in per if r[0].startswith("frontend")]
-        extra = {}
-        if fe_row:
-            fe_ms = fe_row[0][1]
-            fe_gbs = B * (2 * N + 4 * n_mels * T) / 1e9 / (fe_ms * 1e-3)
-            extra["stft_stage"] = {"bound": "hbm", "achieved": round(fe_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                   "frac": round(fe_gbs / PEAK_HBM_GBS, 4),
-                                   "f32_tflops": round(B * 1.27e6 / 1e12 / (fe_ms * 1e-3), 2),
-                                   "clips_per_s_stage": round(B / (fe_ms * 1e-3), 0), "avg_launch_ms": round(fe_ms, 4)}
-            # The stage's BINDING roofline is VALU issue, not HBM: SQ_INSTS_VALU wave-instructions (rocprofv3 --pmc pass of this
-            # kernel at this batch, profiles/traffic.json) x 4 clocks each / (1024 SIMDs x the live launch time x 2.4 GHz)
-            try:
-                ent = json.load(open(os.path.join(ROOT, "profiles", "traffic.json"))).get("frontend:fe_stft_mel_db_kernel", {})
-                if ent.get("batch") == B and ent.get("sq_insts_valu"):
-                    n_simd, clk = 1024, 2.4e9
-                    extra["stft_stage"]["valu_issue_frac"] = round(ent["sq_insts_valu"] * 4 / (n_simd * fe_ms * 1e-3 * clk), 4)
-                    extra["stft_stage"]["valu_issue_source"] = (f"SQ_INSTS_VALU {ent['sq_insts_valu']:.4g} per launch (profiles/traffic.json, rocprofv3 --pmc) "
-                                                                "x 4 clocks / (1024 SIMDs x avg_launch_ms x 2.4 GHz)")
-                    extra["stft_stage"]["binding"] = "valu_issue"
-                    extra["stft_stage"]["binding_frac"] = extra["stft_stage"]["valu_issue_frac"]      # the stage's fraction of its REAL roof
-            except Exception:
-                pass
         out = {
             "metric": "clips/sec (1 s @16 kHz PCM->logits)", "value": round(value, 1), "unit": "clips/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 4),
@@ -734,16 +764,15 @@ def main():
                                       "bf16x6": "float32 operands split exactly into 3 bf16 terms, the 6 partial products >= 2^-23 of a product on v_mfma_f32_32x32x16_bf16, f32 accumulate (float32-grade: DESIGN.md 4.2)",
                                       "f16x3": "float32 operands, scaled by plan-time powers of two, split into 2 binary16 terms (22-23 of 24 significant bits), the 3 partial products >= 2^-22 of a product on v_mfma_f32_32x32x16_f16, f32 accumulate (float32-MFMA accuracy against float64: DESIGN.md 2)"}[arith],
                        "parallelism": f"batch-split x{world}" + (f" + RCCL all-gather of logits ({gather_via}" + (", on a side stream, two steps in flight)" if gather_via == "capi" else ")") if world > 1 else "")},
-            "max_abs_dlogit": max_dlogit,      # the timed logits of the first 16 clips against the oracle (north_star: <= 1e-4)
-            "max_abs_dlogit_note": "16 clips of the timed batch, PCM -> logit, against oracle/ (numpy float32 restatement of the reference); checker only, outside the timed region",
             "gather_via": gather_via,          # "capi" = RCCL all-gather inside the C-ABI on the kernels' stream; "none" at N = 1
-            "roofline": roofline,
-            "kernel_ms": kernel_ms,
         }
         if world > 1 and a.gather == "capi" and gather_via != "capi":
             out["gather_fallback"] = "the C-ABI communicator could not be created: torch.distributed all_gather_into_tensor was timed instead"
-        out.update(extra)
-        extras = world == 1 and not a.no_extras
+        if a.full:
+            out["max_abs_dlogit"] = max_dlogit      # the timed logits of the first 16 clips against the oracle (north_star: <= 1e-4)
+            out["max_abs_dlogit_note"] = "16 clips of the timed batch, PCM -> logit, against oracle/ (numpy float32 restatement of the reference); checker only, outside the timed region"
+            out.update(headline_roofline(cfg, fe, B, N, arith, prof))
+        extras = a.full and world == 1 and not a.no_extras
         if extras:
             # the same step over three rotating copies of the batch (393 MB > the Infinity Cache): PCM really comes from HBM
             t_pre = time.perf_counter()                         # (the clocks fell while the checker ran on the CPU: the same ramp as in front of the headline loop)
@@ -760,7 +789,7 @@ def main():
                                    "buffers": 3, "note": "never the headline: the headline re-reads one batch, as every round did"}
             out.update(audit_legs(a, torch, dev, cfg, fe, sd, window, fb, pcm_host, B, N, lg))
             out["configs"] = config_legs(torch, dev)
-        if not a.no_cpu_baseline and world == 1:           # reported at N = 1 only (rank 0, the GPU box's host cores)
+        if a.full and not a.no_cpu_baseline and world == 1:   # reported at N = 1 only (rank 0, the GPU box's host cores)
             out["cpu_baseline"] = cpu_baseline(cfg, sd, window, fb, a.cpu_seconds)
         if extras:                                         # last: the GPU is busy for the final >= 6 s of the run
             out["sustained"] = sustained_leg(a, torch, dev, model, pcm, logits, B, N)

@@ -1,11 +1,12 @@
 #!/bin/bash
 # PMC passes over the wave-private frontend kernel (fe2_wave_kernel): instruction mix, stall breakdown, LDS.
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-fe2_pmc}
 mkdir -p $OUT
 run() {  # name, counters...
   n=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$n -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$n.log 2>&1
+  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$n -o p -- python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$n.log 2>&1
   python - <<PY
 import csv
 from collections import defaultdict
