@@ -45,6 +45,7 @@ hipError_t launch_ffn_x3_pack(const float* W1, const float* b1, const float* W2,
 // the prologue Linear's weights W [D][KP] -> ceil(D/32) tiles of KP/16 x 2 fragments (two binary16 terms of W x ws), ffn_x3_pro_tile_bytes(KP) apart
 __host__ __device__ inline size_t ffn_x3_pro_tile_bytes(int KP) { return ((size_t)(KP / 16) * 2 * 1024 + 4095) & ~(size_t)4095; }
 bool ffn_x3_pro_supported(int D, int KP);
+bool ffn_x3_epi_supported(int D, int T);          // the LayerNorm + time-sum epilogue (FfnArgs::msum) for clips of T rows
 hipError_t launch_ffn_x3_pro_pack(const float* W, void* out, int D, int KP, float ws, hipStream_t s);
 // finish of the epilogue instances: out [B][D] = (sum over the clip's tile segments of msum) / (m_scale T)
 size_t ffn_x3_msum_bytes(int M, int D);

@@ -784,6 +784,8 @@ size_t ffn_x3_packed_bytes(int D) { return (size_t)(D / 8) * ffn_x3_block_bytes(
 bool ffn_x3_supported(int D, bool h2) { return D == 32 || D == 64 || D == 96 || D == 128 || D == 144 || (h2 && (D == 192 || D == 256)); }
 // prologue / epilogue instances are compiled for the BASELINE width only (d_model 144; K = 64 log-mel bins or K = d_model)
 bool ffn_x3_pro_supported(int D, int KP) { return D == 144 && (KP == 64 || KP == 144); }
+// the epilogue's clips are at least one 32-row tile long (a tile touches at most two clips)
+bool ffn_x3_epi_supported(int D, int T) { return D == 144 && T >= 32; }
 
 hipError_t launch_ffn_x3_pack(const float* W1, const float* b1, const float* W2, void* out, int D, hipStream_t s, float sw1, float sw2, int perm) {
     const size_t total = (size_t)(D / 8) * (D / 16 + 2 * ((D + 31) / 32)) * 64;
@@ -803,7 +805,7 @@ size_t ffn_x3_msum_bytes(int M, int D) { return (size_t)((M + 127) / 128) * 4 * 
 
 hipError_t launch_ffn_x3_mean_finish(const float* msum, float* out, int B, int T, int D, float m_scale, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if (T < 32 || !(m_scale > 0.0f)) return hipErrorInvalidValue;
+    if (!ffn_x3_epi_supported(D, T) || !(m_scale > 0.0f)) return hipErrorInvalidValue;
     const size_t total = (size_t)B * D;
     hipLaunchKernelGGL(ffn_mean_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, msum, out, B, T, D, 1.0 / ((double)m_scale * (double)T));
     return hipGetLastError();
@@ -814,8 +816,8 @@ hipError_t launch_ffn_x3(const FfnArgs& a, int D, hipStream_t s) {
     const dim3 grid((a.M + 127) / 128);
     const bool epi = a.msum != nullptr;
     if (a.pro_k > 0 || epi) {                                  // round-6 instances: d_model 144, two-term form
-        if (D != 144 || !(a.h2_x > 0.0f) || (a.pro_k > 0 && (!ffn_x3_pro_supported(D, a.pro_k) || !a.px || !a.ppacked || !a.pb)) ||
-            (epi && (a.T < 32 || !(a.m_scale > 0.0f) || !a.ln2_w || !a.ln2_b)) || (a.pro_k == 64 && a.pro_res)) return hipErrorInvalidValue;
+        if (!(a.h2_x > 0.0f) || (a.pro_k > 0 && (!ffn_x3_pro_supported(D, a.pro_k) || !a.px || !a.ppacked || !a.pb)) ||
+            (epi && (!ffn_x3_epi_supported(D, a.T) || !(a.m_scale > 0.0f) || !a.ln2_w || !a.ln2_b)) || (a.pro_k == 64 && a.pro_res)) return hipErrorInvalidValue;
         if (a.pro_k == 64) {
             if (epi) hipLaunchKernelGGL((ffn_x3_kernel<9, true, 4, false, true>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((ffn_x3_kernel<9, true, 4, false, false>), grid, dim3(256), 0, s, a);

@@ -183,7 +183,6 @@ hipError_t launch_transpose3x3(const float* w, float* out, int nfilters, hipStre
 hipError_t launch_transpose_planes(const float* in, float* out, int B, int R, int C, hipStream_t s);
 // rnn_x3.hip: gates = 3 (GRU) / 4 (LSTM), H in {32, 64, 128}
 bool rnn_x3_usable(const GruArgs& a);
-bool rnn_x3_enabled(const GruArgs& a);   // ... and not switched off (NWW_GRU16 = 0)
 hipError_t launch_rnn_x3(const GruArgs& a, int gates, hipStream_t s);
 // rnn_stream.hip: 128 < H <= 256 (H % 4 == 0), two-term form, W_hh streamed from L2 each step
 bool rnn_stream_usable(const GruArgs& a);

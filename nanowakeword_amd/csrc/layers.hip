@@ -1626,19 +1626,13 @@ static hipError_t launch_rnn_wide(const GruArgs& a, int gates, hipStream_t s) {
     return hipGetLastError();
 }
 
-bool rnn_x3_enabled(const GruArgs& a) {
-    static const int use16 = 1;
-    return use16 && rnn_x3_usable(a);
-}
-
 hipError_t launch_lstm(const GruArgs& a, hipStream_t s) {
     if (a.w_packed) return launch_rnn_stream(a, 4, s);
     if (a.ldw) return launch_rnn_wide(a, 4, s);                      // padded weights: the any-width kernel (planned for H % 4 != 0 or H > 256)
     if (a.H % 4 != 0 || a.H > 256) return hipErrorInvalidValue;      // a wave per 32 hidden units, 512 threads
-    static const int use16 = 1;
-    if (rnn_x3_enabled(a)) return launch_rnn_x3(a, 4, s);
+    if (rnn_x3_usable(a)) return launch_rnn_x3(a, 4, s);
     if (a.xg2) return hipErrorInvalidValue;                           // only rnn_x3 folds the opposite direction's step
-    if (use16 && (a.H == 32 || a.H == 64 || a.H == 128) && (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0) {
+    if ((a.H == 32 || a.H == 64 || a.H == 128) && (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0) {
         const size_t lds16 = (size_t)16 * (a.H + 4) * sizeof(float);
         const dim3 grid((a.B + 15) / 16);
         switch (a.H) {
@@ -1662,10 +1656,9 @@ hipError_t launch_gru(const GruArgs& a, hipStream_t s) {
     if (a.w_packed) return launch_rnn_stream(a, 3, s);
     if (a.ldw) return launch_rnn_wide(a, 3, s);
     if (a.H % 4 != 0 || a.H > 256) return hipErrorInvalidValue;      // a wave per 32 hidden units, 512 threads
-    static const int use16 = 1;
-    if (rnn_x3_enabled(a)) return launch_rnn_x3(a, 3, s);
+    if (rnn_x3_usable(a)) return launch_rnn_x3(a, 3, s);
     if (a.xg2) return hipErrorInvalidValue;                           // only rnn_x3 folds the opposite direction's step
-    if (use16 && (a.H == 32 || a.H == 64 || a.H == 128) && (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0) {
+    if ((a.H == 32 || a.H == 64 || a.H == 128) && (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0) {
         const size_t lds16 = (size_t)16 * (a.H + 4) * sizeof(float);
         const dim3 grid((a.B + 15) / 16);
         switch (a.H) {

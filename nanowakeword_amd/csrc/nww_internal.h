@@ -166,6 +166,15 @@ int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipSt
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
 void nww_build_spec(nww_handle* h);            // nww_plan.hip
 
+// The run-time knobs, read from the environment on the first call (nww_plan.hip).  Each selection knob defaults to the
+// specialised kernel; setting it picks a general one.
+struct Knobs {
+    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, mha_mfma, bc_front, bc_chain, tail;
+    int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
+    int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2
+};
+const Knobs& nww_knobs();
+
 #define fail nww_fail
 #define HIP_TRY(h, expr)                                                                             \
     do {                                                                                             \

@@ -11,6 +11,20 @@
 #define h2d_small nww_h2d_small
 #define copy_out nww_copy_out
 
+const Knobs& nww_knobs() {
+    static const Knobs k = [] {
+        auto env = [](const char* name, int d) { const char* e = getenv(name); return e ? atoi(e) : d; };
+        Knobs r;
+        r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
+        r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
+        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
+        r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
+        r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
+        return r;
+    }();
+    return k;
+}
+
 // ------------------------------------------------------------------------------------------ spec
 namespace {
 using Shape = std::vector<int64_t>;
@@ -195,8 +209,7 @@ double f16_layer_bound(const std::vector<float>& w, int Cout, int K, const std::
 // how far above the typical magnitude a worst-case bound may lie: 2^16 leaves typical values 22+ significant bits in two binary16 terms.
 // NWW_F16_RANGE_LOG2 (A/B and test knob): a larger exponent lets deeper stages take the two-term kernels at reduced precision of small values
 inline double f16_range_factor() {
-    static const double f = [] { const char* e = getenv("NWW_F16_RANGE_LOG2"); return std::ldexp(1.0, e ? atoi(e) : 16); }();
-    return f;
+    return std::ldexp(1.0, nww_knobs().f16_range_log2);
 }
 struct F16Range {
     double bound = 0.0, typ = 0.0;
@@ -231,7 +244,7 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
     // small square ones, (144,144) 0.23 / 0.18, whose single padded column tile wastes the wide kernel.  Long-K layers
     // get a fine split-K.  The choice depends on (N, K) only, so batch invariance is kept.
     // NWW_GEMM_X3 = 0: never, 2: every shape with N, K >= 32, 3: the round-1 rule (K >= 4096 only).
-    static const int x3_mode = [] { const char* e = getenv("NWW_GEMM_X3"); return e ? atoi(e) : 1; }();
+    const int x3_mode = nww_knobs().gemm_x3;
     const bool small_square = N <= 160 && K > 64 && K <= 160;
     const bool use_x3 = p.h->conv_products != 0 &&
                         (x3_mode == 2 ? (N >= 32 && K >= 32)
@@ -307,8 +320,7 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
 bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int rows_per_clip, int N, int K, const float* W,
                 const float* bias, int epi, int res_id = 99, float rscale = 1.f, const float* ln_w = nullptr,
                 const float* ln_b = nullptr, int qkv_T = 0, int qkv_dh = 0) {
-    static const int enabled = [] { const char* e = getenv("NWW_LIN_X3"); return e ? atoi(e) : 1; }();
-    if (!enabled || p.h->conv_products != 6 || !lin_x3_supported(K, N, true)) return false;
+    if (!nww_knobs().lin_x3 || p.h->conv_products != 6 || !lin_x3_supported(K, N, true)) return false;
     const int parts = epi == 2 ? 2 : 1;
     // under NWW_ARITH_F16X3: two binary16 terms per operand, the input rows scaled per row in the kernel (LinArgs::h2: no bound on the
     // tensor needed); conv_arith = bf16x6 keeps the three-term bf16 form
@@ -358,8 +370,7 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
                F16Range in_range = F16Range{}, F16Range* out_range = nullptr) {
     if (out_range) *out_range = F16Range{};
     const double in_bound = in_range.ok() ? in_range.bound : 0.0;
-    static const int enabled = [] { const char* e = getenv("NWW_TRUNK"); return e ? atoi(e) : 1; }();
-    if (!enabled || C1 != 16 || C2 != 32 || H < 4 || W < 4 || trunk_fits(C1, H, W) == 0) return false;
+    if (!nww_knobs().trunk || C1 != 16 || C2 != 32 || H < 4 || W < 4 || trunk_fits(C1, H, W) == 0) return false;
     p.need(out_id, (size_t)C2 * (H / 4) * (W / 4));
     const int max_grid = p.h->cu_count;
     // both convolutions on the bf16 matrix cores by exact operand splitting (trunk_b.hip) or on the float32 MFMA (nww_config.conv_arith)
@@ -428,8 +439,7 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
                    F16Range in_range = F16Range{}, F16Range* out_range = nullptr, int scratch_id = -1) {
     if (out_range) *out_range = F16Range{};
     const double in_bound = in_range.ok() ? in_range.bound : 0.0;
-    static const int enabled = [] { const char* e = getenv("NWW_CONV_MFMA"); return e ? atoi(e) : 1; }();
-    static const int x3_enabled = [] { const char* e = getenv("NWW_CONV3_X3"); return e ? atoi(e) : 1; }();
+    const int enabled = nww_knobs().conv_mfma, x3_enabled = nww_knobs().conv3_x3;
     // 64 input channels (a fourth CRNN stage): conv3_x3's wide instance - two-term arithmetic on a bounded input only
     bool wide = Cin == 64 && enabled && x3_enabled && pool && avg_ow == 0 && !avg_y && p.h->conv_products == 6 && p.h->f16 && in_bound > 0.0 &&
                 Cout % 32 == 0 && conv3_x3_wide_fits(Cin, H, W, Cout);
@@ -440,9 +450,8 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
     // more than 32 input channels without a usable bound (the worst-case bound of a fourth stage is usually too loose for two terms): the
     // 32-channel three-term instance once per 32 input channels - every pass but the last leaves raw, un-pooled sums in a scratch buffer, the
     // next one starts its accumulators from them (k-split; the planes of such stages are a few hundred pixels)
-    static const int ksplit_on = 1;
     if (!wide && Cin > 32) {
-        if (!ksplit_on || !enabled || !x3_enabled || Cin % 32 != 0 || Cin > 256 || !pool || avg_ow > 0 || avg_y || p.h->conv_products != 6 || scratch_id < 0 ||
+        if (!enabled || !x3_enabled || Cin % 32 != 0 || Cin > 256 || !pool || avg_ow > 0 || avg_y || p.h->conv_products != 6 || scratch_id < 0 ||
             Cout % 32 != 0) return false;
         const bool whole = conv3_x3_fits(H, W, Cout, 0, 1) && conv3_x3_fits(H, W, Cout, 0, 0);
         const int sh = whole ? 0 : conv3_x3_strip_rows(H, W, Cout);          // larger planes: in strips of rows
@@ -530,12 +539,9 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
 // conv1 groups and 16-column conv2 tiles waste 28 % on a 101-wide plane and nothing on a 64-wide one, conv3's 2 x 16 tiles 22 %
 // against 4 %, and the frontend's frames-major output is its fast path.  Needs the split-operand kernels (default arithmetic).
 bool e2e_transposed_ok(PlanCtx& p, int n_mels, int frames) {
-    static const int on = 1;
-    static const int trunk_on = [] { const char* e = getenv("NWW_TRUNK"); return e ? atoi(e) : 1; }();
-    static const int mfma_on = [] { const char* e = getenv("NWW_CONV_MFMA"); return e ? atoi(e) : 1; }();
-    static const int c3_on = [] { const char* e = getenv("NWW_CONV3_X3"); return e ? atoi(e) : 1; }();
+    const Knobs& k = nww_knobs();
     const int H = frames, W = n_mels;
-    return on && trunk_on && mfma_on && c3_on && p.h->conv_products == 6 && H >= 16 && W >= 4 && trunk_b_pick_strips(H, W) > 0 &&
+    return k.trunk && k.conv_mfma && k.conv3_x3 && p.h->conv_products == 6 && H >= 16 && W >= 4 && trunk_b_pick_strips(H, W) > 0 &&
            conv_mfma_lds_bytes(32, H / 4, W / 4) <= 160 * 1024 && conv3_x3_fits(H / 4, W / 4, 64, 4, 0);
 }
 
@@ -547,13 +553,11 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
     p.need(last_id, (size_t)2 * H);
     // the recurrent product follows the handle's arithmetic switch; NWW_ARITH_F16X3: two binary16 terms (|h| <= 1 bounds the one
     // operand, W_hh's scale comes from the weights)
-    static const int rnn_h2 = 1;
-    const int products = (p.h->f16 && rnn_h2) ? 3 : p.h->conv_products;
+    const int products = p.h->f16 ? 3 : p.h->conv_products;
     GruArgs probe; probe.H = H; probe.products = products;
     probe.w_hh = p.W(prefix + ".weight_hh_l" + std::to_string(layers - 1));       // the pointer the fused launch will really get (alignment test)
-    static const int gru16_on = 1;
-    const bool streamed = gru16_on && rnn_stream_usable(probe);      // 128 < H <= 256: W_hh streamed from L2 (rnn_stream.hip)
-    bool x3 = probe.w_hh != nullptr && (rnn_x3_enabled(probe) || streamed);
+    const bool streamed = rnn_stream_usable(probe);      // 128 < H <= 256: W_hh streamed from L2 (rnn_stream.hip)
+    bool x3 = probe.w_hh != nullptr && (rnn_x3_usable(probe) || streamed);
     if (x3 && H != 32 && H != 64 && H != 128) {              // zero-padded / streamed instances: two-term form only, so the last layer's W_hh must scale
         const float* wl = probe.w_hh;
         if (!(f16_wscale(f16_fetch(p.h, wl, (size_t)G * H * H)) > 0.0f)) x3 = false;
@@ -570,10 +574,8 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
         // GRU head, first layer fed by the head's own input features (<= 64 per frame), two-term arithmetic: the forward direction's input
         // projection is computed inside the recurrence kernel - x_t W_ih^T on the matrix pipe beside h W_hh^T - instead of a GEMM that
         // writes T x 3H gate pre-activations per clip to HBM for the recurrence to read back (635 MB each way at B = 4096, T = 101, H = 128).
-        // NWW_RNN_FUSE_IH = 0 keeps the separate projection.
-        static const int fuse_env = 1;
         const float* wih_f = p.W(prefix + ".weight_ih_l" + std::to_string(l));
-        const float wi_scale = (fuse_env && fold && l == 0 && in_id == -1 && G == 3 && products == 3 && (cur_I == 32 || cur_I == 64) && (H == 32 || H == 64 || H == 128) &&
+        const float wi_scale = (fold && l == 0 && in_id == -1 && G == 3 && products == 3 && (cur_I == 32 || cur_I == 64) && (H == 32 || H == 64 || H == 128) &&
                                 wih_f && (reinterpret_cast<uintptr_t>(wih_f) & 15) == 0)
                                    ? f16_wscale(f16_fetch(p.h, wih_f, (size_t)G * H * cur_I)) : 0.0f;
         const float* whh_fwd = p.W(prefix + ".weight_hh_l" + std::to_string(l));
@@ -751,9 +753,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         case NWW_HEAD_DNN: {                      // Net: architectures.py:110-126
             // Everything behind layer1 runs inside the tail's launch (layers.hip: TailArgs::ln0_w) when the widths allow: LayerNorm1 on
             // layer1's split-K partials, the blocks' Linear + LayerNorm, last_layer, classifier - two launches per forward instead of six
-            static const int tail_on = [] { const char* e = getenv("NWW_TAIL"); return e ? atoi(e) : 1; }();
-            static const int body_on = 1;
-            if (tail_on && body_on && L <= 256 && nb <= 4 && tail_supported(L, E)) {
+            if (nww_knobs().tail && L <= 256 && nb <= 4 && tail_supported(L, E)) {
                 add_gemm(p, "layer1", -1, 0, 1, L, T * F, p.W("model.layer1.weight"), p.W("model.layer1.bias"), ACT_NONE, nullptr, nullptr, 99, 1.f, nullptr, false, true, F16_FEATURES, true);
                 p.dnn_body = true;
                 p.dnn_ln0_w = p.W("model.layernorm1.weight"); p.dnn_ln0_b = p.W("model.layernorm1.bias");
@@ -805,9 +805,8 @@ extern "C" int nww_finalize(nww_handle* h) {
                 add_conv(p, "conv2", 0, 1, 16, 32, T / 2, F / 2, p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, 1);
             }
             // fc1's split-K partials are reduced by the classifier tail itself when that is the fused kernel
-            static const int tail_on = [] { const char* e = getenv("NWW_TAIL"); return e ? atoi(e) : 1; }();
             add_gemm(p, "fc1", 1, 0, 1, 128, 32 * H2 * W2, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, nullptr, nullptr, 99, 1.f,
-                     &h->trunk_blocked, tail_on && tail_supported(128, E), false, a2_bound);
+                     &h->trunk_blocked, nww_knobs().tail && tail_supported(128, E), false, a2_bound);
             set_tail(p, "fc2", 0, 128, p.W("model.fc2.weight"), p.W("model.fc2.bias"));
             break;
         }
@@ -955,9 +954,9 @@ extern "C" int nww_finalize(nww_handle* h) {
             // init conv (+BN+act+pool) writes [B][H1][W1][32]; each block: one depthwise kernel emits d = dw3x3(x) and
             // xs = x at the strided centres, then two MFMA GEMMs over M = B*Ho*Wo pixels:
             //   R = BN_s(xs . Wsc^T) ;  out = act(BN_1(d . Wpw^T)) + R      (activation BEFORE the residual add, :646-647)
-            static const int ic_mfma = [] { const char* e = getenv("NWW_CONV_MFMA"); return e ? atoi(e) : 1; }();
+            const int ic_mfma = nww_knobs().conv_mfma;
             // init conv fused with block1's depthwise (trunk.hip: the 32-channel planes never reach HBM)
-            static const int bc_front = [] { const char* e = getenv("NWW_BC_FRONT"); return e ? atoi(e) : 1; }();
+            const int bc_front = nww_knobs().bc_front;
             const bool front_fused = ic_mfma && bc_front && conv1_pool_nhwc_mfma_fits(T, F) && conv1_pool_dw_rows(T, F, 2) > 0;
             // nww_config.act_dtype = NWW_ACT_DTYPE_BF16 / _F16: every activation tensor between the kernels of this head is stored in 16
             // bits (arithmetic and accumulation stay float32); implemented on the fused front + split-operand block path only.
@@ -1020,10 +1019,9 @@ extern "C" int nww_finalize(nww_handle* h) {
                 void* fpack = nullptr;
                 int fprod = p.h->conv_products;
                 // under NWW_ARITH_F16X3 (BN present): two binary16 terms per operand, features clamped to +-NWW_F16_FEATURE_BOUND as in the
-                // CNN trunk; NWW_BC_FRONT_H2 = 0 keeps the three-term bf16 form
-                static const int front_h2_on = 1;
+                // CNN trunk
                 float fin = 0.0f, fws = 1.0f;
-                if (front_h2_on && p.h->f16 && fprod == 6 && a0 && bc_front != 2) {
+                if (p.h->f16 && fprod == 6 && a0 && bc_front != 2) {
                     fin = f16_scale(F16_FEATURES.bound); fws = f16_wscale(f16_fetch(p.h, w0, 32 * 9));
                     if (fin > 0.0f && fws > 0.0f) fprod = 3;
                 }
@@ -1071,7 +1069,6 @@ extern "C" int nww_finalize(nww_handle* h) {
             // already there - written by the fused front kernel or by the previous block's chained kernel (bc_chain.hip)
             int dwb = 2, xsb = 3;
             bool have_dx = front_fused;
-            static const int chain_on = [] { const char* e = getenv("NWW_BC_CHAIN"); return e ? atoi(e) : 1; }();
             for (int i = 1; i <= 3; ++i) {
                 const std::string q = "model.block" + std::to_string(i);
                 const int ci = ch[i - 1], co = ch[i], sh = st[i - 1][0], sw = st[i - 1][1];
@@ -1092,22 +1089,20 @@ extern "C" int nww_finalize(nww_handle* h) {
                     const int rows = ho * wo;
                     p.need(outb, (size_t)rows * co);
                     // both products from split operands on the bf16 matrix cores (dual_x3.hip) under the same arithmetic switch
-                    static const int dual_x3 = 1;
                     void* packed = nullptr;
                     // float32 activations under NWW_ARITH_F16X3: two binary16 terms per operand, the activation rows scaled per pixel in
-                    // the kernel (DualArgs::h2) - no tensor bound needed; NWW_BC_DUAL_H2 = 0 keeps the three-term bf16 form
-                    static const int dual_h2_on = 1;
-                    const bool dual_h2 = dual_h2_on && p.h->f16 && !act_bf16;
+                    // the kernel (DualArgs::h2) - no tensor bound needed
+                    const bool dual_h2 = p.h->f16 && !act_bf16;
                     // blocks 1 and 2 chained with the next block's depthwise (bc_chain.hip; two-term weights in every storage mode)
-                    const bool will_chain = chain_on && i < 3 && have_dx && bc_chain_supported(ci, ho, wo) &&
-                                            (act_f16 || dual_h2 || (act16 == NWW_ACT_DTYPE_BF16 && dual_h2_on && p.h->f16));
+                    const bool will_chain = nww_knobs().bc_chain && i < 3 && have_dx && bc_chain_supported(ci, ho, wo) &&
+                                            (act_f16 || dual_h2 || (act16 == NWW_ACT_DTYPE_BF16 && p.h->f16));
                     if (dual_h2 || (will_chain && !act_f16)) {
                         dps[i].pw_ws = f16_wscale(f16_fetch(p.h, wpw, (size_t)co * ci)); dps[i].sc_ws = f16_wscale(f16_fetch(p.h, wsc, (size_t)co * ci));
                         if (!(dps[i].pw_ws > 0.f && dps[i].sc_ws > 0.f)) return fail(h, NWW_ERR_INVALID, "block %d: non-finite weights", i);
                         dps[i].pw_un = 1.0f / dps[i].pw_ws; dps[i].sc_un = 1.0f / dps[i].sc_ws;
                     }
                     const int terms = act_f16 || dual_h2 || will_chain ? 2 : 3;
-                    if (dual_x3 && p.h->conv_products == 6 && dual_x3_supported(ci, co) &&
+                    if (p.h->conv_products == 6 && dual_x3_supported(ci, co) &&
                         hipMalloc(&packed, dual_x3_packed_bytes(ci, co, terms)) == hipSuccess) {
                         if (launch_dual_x3_pack(wpw, wsc, a1, b1, as, bs, packed, ci, co, p.h->own_stream, terms, dps[i]) == hipSuccess) {
                             p.h->packed_weights.push_back(packed);
@@ -1140,8 +1135,7 @@ extern "C" int nww_finalize(nww_handle* h) {
                                 continue;
                             }
                             // the last block feeds only the global average pool: averaged in the same launch, its output never reaches HBM
-                            static const int mean_fused_on = 1;
-                            const bool fuse_mean = mean_fused_on && i == 3 && ci == 128 && dual_x3_mean_supported(rows);
+                            const bool fuse_mean = i == 3 && ci == 128 && dual_x3_mean_supported(rows);
                             if (fuse_mean) { mean_fused = true; p.need(5, 256); }
                             const float out_mul = fuse_mean ? 1.0f : s_h[i];
                             p.add(std::string(gather ? "dual_x3(xs gathered):" : "dual_x3:") + q + ".pointwise+bn+act + shortcut+bn" + (fuse_mean ? " + global_avg_pool" : "") + suffix, [=](Run& r) {
@@ -1188,101 +1182,120 @@ extern "C" int nww_finalize(nww_handle* h) {
             p.need(hb, (size_t)T * D);
             // round 6: the row-local Linears next to a feed-forward module run INSIDE its launch (FfnArgs::px: input_proj in front of the first
             // block's ff1, conv2 + residual in front of every ff2), and the last block's LayerNorm + time average behind its ff2
-            // (FfnArgs::msum); NWW_FFN_FUSED = 0 and the other arithmetics keep the separate launches
+            // (FfnArgs::msum); NWW_FFN_FUSED = 0 and the other arithmetics keep the separate launches.
+            // A feed-forward step takes one of four forms, richest first: prologue + epilogue, prologue, plain ffn_x3, unfused (LayerNorm +
+            // two GEMMs).  pro: 0 none, 1 input_proj (x = the head input), 2 conv_module.conv2 + residual (x = the depthwise output in t3);
+            // epi: the block's final LayerNorm + mean over time.
+            struct FfnForm {
+                int pro = 0;
+                bool epi = false, fused = false, h2 = false;
+                float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f, pws = 0.0f, mscale = 0.0f;
+            };
             for (int i = 0; i < nb; ++i) {
                 const std::string q = "model.conformer_blocks." + std::to_string(i);
-                // pro: 0 none, 1 input_proj (x = the head input), 2 conv_module.conv2 + residual (x = the depthwise output in t3); epi: the block's
-                // final LayerNorm + mean over time.  With pro / epi the step is planned only if it can be fused that way (false: nothing planned).
-                auto ffn = [&](const std::string& ff, int pro, bool epi) -> bool {
-                    const float *lw = p.W(q + ff + ".layer_norm.weight"), *lb = p.W(q + ff + ".layer_norm.bias");
+                const float* pro_w[3] = {nullptr, p.W("model.input_proj.weight"), p.W(q + ".conv_module.conv2.weight")};
+                const float* pro_b[3] = {nullptr, p.W("model.input_proj.bias"), p.W(q + ".conv_module.conv2.bias")};
+                const int pro_k[3] = {0, F, D};
+                const float *l2w = p.W(q + ".layer_norm.weight"), *l2b = p.W(q + ".layer_norm.bias");
+                // the richest feasible form with at most the requested prologue / epilogue: plan-time scales only, nothing allocated or launched
+                auto ffn_decide = [&](const std::string& ff, int pro, bool epi) {
+                    FfnForm f;
                     // LayerNorm + linear1 + swish + linear2 + half-step residual in one kernel (ffn_x3.hip); same arithmetic
                     // switch as the split-operand GEMMs it replaces
-                    static const int fused = [] { const char* e = getenv("NWW_FFN_FUSED"); return e ? atoi(e) : 1; }();
-                    const int pro_k = pro == 1 ? F : pro == 2 ? D : 0;
-                    if ((pro || epi) && !(fused && p.h->f16 && p.h->conv_products == 6 && (!pro || ffn_x3_pro_supported(D, pro_k)) && D == 144 && (!epi || T >= 32))) return false;
-                    if (fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16)) {
-                        void* packed = nullptr;
-                        // NWW_ARITH_F16X3: both operands of both products are bounded whatever the residual stream holds -
-                        // |LayerNorm(h)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v| - so the scales need nothing but the weights
-                        float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f;
-                        if (p.h->f16) {
-                            const auto hlw = f16_fetch(p.h, lw, D), hlb = f16_fetch(p.h, lb, D);
-                            double bx = 0.0;
-                            for (int i = 0; i < D; ++i) bx = std::fmax(bx, std::sqrt((double)D) * std::fabs((double)hlw[i]) + std::fabs((double)hlb[i]));
-                            const auto w1 = f16_fetch(p.h, p.W(q + ff + ".linear1.weight"), (size_t)4 * D * D), w2 = f16_fetch(p.h, p.W(q + ff + ".linear2.weight"), (size_t)4 * D * D);
-                            const auto b1 = f16_fetch(p.h, p.W(q + ff + ".linear1.bias"), (size_t)4 * D);
-                            const double bh = f16_layer_bound(w1, 4 * D, D, b1, true, b1, b1, false, bx);
-                            fx = f16_scale(bx); fw1 = f16_wscale(w1); fh = f16_scale(bh); fw2 = f16_wscale(w2);
-                        }
-                        const bool h2 = fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f;
-                        // the prologue Linear's weights (two binary16 terms; its input rows are scaled per row in the kernel) and the epilogue's scale
-                        const float* pw = pro == 1 ? p.W("model.input_proj.weight") : pro == 2 ? p.W(q + ".conv_module.conv2.weight") : nullptr;
-                        const float* pbias = pro == 1 ? p.W("model.input_proj.bias") : pro == 2 ? p.W(q + ".conv_module.conv2.bias") : nullptr;
-                        const float *l2w = epi ? p.W(q + ".layer_norm.weight") : nullptr, *l2b = epi ? p.W(q + ".layer_norm.bias") : nullptr;
-                        float pws = 0.0f, mscale = 0.0f;
-                        void* ppk = nullptr;
-                        bool extras_ok = h2 || !(pro || epi);
-                        if (pro && extras_ok) {
-                            pws = f16_wscale(f16_fetch(p.h, pw, (size_t)D * pro_k));
-                            extras_ok = pws > 0.0f && pbias && hipMalloc(&ppk, ffn_x3_pro_tile_bytes(pro_k) * ((D + 31) / 32)) == hipSuccess &&
-                                        launch_ffn_x3_pro_pack(pw, ppk, D, pro_k, pws, p.h->own_stream) == hipSuccess;
-                        }
-                        if (epi && extras_ok) {
-                            const auto h2w = f16_fetch(p.h, l2w, D), h2b = f16_fetch(p.h, l2b, D);
-                            double by = 0.0;
-                            for (int k = 0; k < D; ++k) by = std::fmax(by, std::sqrt((double)D) * std::fabs((double)h2w[k]) + std::fabs((double)h2b[k]));
-                            mscale = by < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(by, 1e-30)) : 0.0f;      // |LayerNorm| x scale <= 2^36
-                            extras_ok = mscale > 0.0f && std::isfinite(mscale);
-                        }
-                        if (!extras_ok) {
-                            if (ppk) (void)hipFree(ppk);
-                            if (pro || epi) return false;
-                        }
-                        if (ffn_x3_supported(D, h2) && hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
-                            launch_ffn_x3_pack(p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"),
-                                               p.W(q + ff + ".linear2.weight"), packed, D, p.h->own_stream, h2 ? fw1 : 0.0f, h2 ? fw2 : 0.0f, pro ? 1 : 0) == hipSuccess) {
-                            p.h->packed_weights.push_back(packed);
-                            if (ppk) p.h->packed_weights.push_back(ppk);
-                            const float* b2 = p.W(q + ff + ".linear2.bias");
-                            const float p_un = pro ? 1.0f / pws : 1.0f;
-                            // the epilogue's exact partial sums: per 32-row tile two segments x two planes of D floats (the idle wide scratch buffer)
-                            if (epi) p.need(big, (size_t)((T + 31) / 32 + 1) * 4 * D + (size_t)16 * D);
-                            const std::string what = std::string(pro == 1 ? "input_proj+" : pro == 2 ? "conv2(pw)+res+" : "") + "ln+linear1+swish+linear2+0.5res" + (epi ? "+layernorm+time sums" : "");
-                            p.add("ffn_x3:" + q + ff + " (" + what + ")" + (h2 ? " [f16x3]" : ""), [=](Run& r) {
-                                FfnArgs a{r.buf[hb], lw, lb, static_cast<const unsigned char*>(packed), b2, r.B * T, 0.5f};
-                                if (h2) { a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2; }
-                                if (pro) {
-                                    a.px = pro == 1 ? r.x : r.buf[t3]; a.ppacked = static_cast<const unsigned char*>(ppk); a.pb = pbias;
-                                    a.pro_k = pro_k; a.pro_res = pro == 2 ? 1 : 0; a.p_un = p_un;
-                                }
-                                if (epi) { a.ln2_w = l2w; a.ln2_b = l2b; a.msum = r.buf[big]; a.T = T; a.m_scale = mscale; }
-                                return launch_ffn_x3(a, D, r.stream);
-                            });
-                            if (epi)
-                                p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
-                                    return launch_ffn_x3_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, mscale, r.stream);
-                                });
-                            return true;
-                        }
+                    if (!(nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16))) return f;
+                    // NWW_ARITH_F16X3: both operands of both products are bounded whatever the residual stream holds -
+                    // |LayerNorm(h)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v| - so the scales need nothing but the weights
+                    if (p.h->f16) {
+                        const auto hlw = f16_fetch(p.h, p.W(q + ff + ".layer_norm.weight"), D), hlb = f16_fetch(p.h, p.W(q + ff + ".layer_norm.bias"), D);
+                        double bx = 0.0;
+                        for (int k = 0; k < D; ++k) bx = std::fmax(bx, std::sqrt((double)D) * std::fabs((double)hlw[k]) + std::fabs((double)hlb[k]));
+                        const auto w1 = f16_fetch(p.h, p.W(q + ff + ".linear1.weight"), (size_t)4 * D * D), w2 = f16_fetch(p.h, p.W(q + ff + ".linear2.weight"), (size_t)4 * D * D);
+                        const auto b1 = f16_fetch(p.h, p.W(q + ff + ".linear1.bias"), (size_t)4 * D);
+                        const double bh = f16_layer_bound(w1, 4 * D, D, b1, true, b1, b1, false, bx);
+                        f.fx = f16_scale(bx); f.fw1 = f16_wscale(w1); f.fh = f16_scale(bh); f.fw2 = f16_wscale(w2);
+                    }
+                    f.h2 = f.fx > 0.0f && f.fw1 > 0.0f && f.fh > 0.0f && f.fw2 > 0.0f;
+                    f.fused = ffn_x3_supported(D, f.h2);
+                    if (!f.fused || !f.h2) return f;                   // the prologue / epilogue instances: two-term form only
+                    // the prologue Linear's weights (two binary16 terms; its input rows are scaled per row in the kernel)
+                    if (pro && ffn_x3_pro_supported(D, pro_k[pro]) && pro_b[pro]) {
+                        f.pws = f16_wscale(f16_fetch(p.h, pro_w[pro], (size_t)D * pro_k[pro]));
+                        if (f.pws > 0.0f) f.pro = pro;
+                    }
+                    if (epi && f.pro == pro && ffn_x3_epi_supported(D, T)) {
+                        const auto h2w = f16_fetch(p.h, l2w, D), h2b = f16_fetch(p.h, l2b, D);
+                        double by = 0.0;
+                        for (int k = 0; k < D; ++k) by = std::fmax(by, std::sqrt((double)D) * std::fabs((double)h2w[k]) + std::fabs((double)h2b[k]));
+                        f.mscale = by < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(by, 1e-30)) : 0.0f;      // |LayerNorm| x scale <= 2^36
+                        f.epi = f.mscale > 0.0f && std::isfinite(f.mscale);
+                    }
+                    return f;
+                };
+                // allocates, packs and plans form f; false (an allocation or a pack failed): nothing planned, nothing kept
+                auto ffn_build = [&](const std::string& ff, const FfnForm& f) -> bool {
+                    const float *lw = p.W(q + ff + ".layer_norm.weight"), *lb = p.W(q + ff + ".layer_norm.bias");
+                    if (!f.fused) {
+                        p.add("layernorm:" + q + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
+                        add_gemm(p, q + ff + ".linear1+swish", t1, big, T, 4 * D, D, p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), ACT_SILU);
+                        add_gemm(p, q + ff + ".linear2+0.5res", big, hb, T, D, 4 * D, p.W(q + ff + ".linear2.weight"), p.W(q + ff + ".linear2.bias"), ACT_NONE, nullptr, nullptr, hb, 0.5f);
+                        return true;
+                    }
+                    const int pro = f.pro, pk = pro_k[pro];
+                    void *packed = nullptr, *ppk = nullptr;
+                    if ((pro && (hipMalloc(&ppk, ffn_x3_pro_tile_bytes(pk) * ((D + 31) / 32)) != hipSuccess ||
+                                 launch_ffn_x3_pro_pack(pro_w[pro], ppk, D, pk, f.pws, p.h->own_stream) != hipSuccess)) ||
+                        hipMalloc(&packed, ffn_x3_packed_bytes(D)) != hipSuccess ||
+                        launch_ffn_x3_pack(p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), p.W(q + ff + ".linear2.weight"), packed, D,
+                                           p.h->own_stream, f.h2 ? f.fw1 : 0.0f, f.h2 ? f.fw2 : 0.0f, pro ? 1 : 0) != hipSuccess) {
                         if (packed) (void)hipFree(packed);
                         if (ppk) (void)hipFree(ppk);
-                        if (pro || epi) return false;
+                        return false;
                     }
-                    p.add("layernorm:" + q + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-                    add_gemm(p, q + ff + ".linear1+swish", t1, big, T, 4 * D, D, p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), ACT_SILU);
-                    add_gemm(p, q + ff + ".linear2+0.5res", big, hb, T, D, 4 * D, p.W(q + ff + ".linear2.weight"), p.W(q + ff + ".linear2.bias"), ACT_NONE, nullptr, nullptr, hb, 0.5f);
+                    p.h->packed_weights.push_back(packed);
+                    if (ppk) p.h->packed_weights.push_back(ppk);
+                    const float* b2 = p.W(q + ff + ".linear2.bias");
+                    const float* pbias = pro_b[pro];
+                    const float p_un = pro ? 1.0f / f.pws : 1.0f;
+                    const bool epi = f.epi;
+                    // the epilogue's exact partial sums: per 32-row tile two segments x two planes of D floats (the idle wide scratch buffer)
+                    if (epi) p.need(big, (size_t)((T + 31) / 32 + 1) * 4 * D + (size_t)16 * D);
+                    const std::string what = std::string(pro == 1 ? "input_proj+" : pro == 2 ? "conv2(pw)+res+" : "") + "ln+linear1+swish+linear2+0.5res" + (epi ? "+layernorm+time sums" : "");
+                    p.add("ffn_x3:" + q + ff + " (" + what + ")" + (f.h2 ? " [f16x3]" : ""), [=](Run& r) {
+                        FfnArgs a{r.buf[hb], lw, lb, static_cast<const unsigned char*>(packed), b2, r.B * T, 0.5f};
+                        if (f.h2) { a.h2_x = f.fx; a.h2_w1 = f.fw1; a.h2_h = f.fh; a.h2_w2 = f.fw2; }
+                        if (pro) {
+                            a.px = pro == 1 ? r.x : r.buf[t3]; a.ppacked = static_cast<const unsigned char*>(ppk); a.pb = pbias;
+                            a.pro_k = pk; a.pro_res = pro == 2 ? 1 : 0; a.p_un = p_un;
+                        }
+                        if (epi) { a.ln2_w = l2w; a.ln2_b = l2b; a.msum = r.buf[big]; a.T = T; a.m_scale = f.mscale; }
+                        return launch_ffn_x3(a, D, r.stream);
+                    });
+                    if (epi)
+                        p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
+                            return launch_ffn_x3_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, f.mscale, r.stream);
+                        });
                     return true;
                 };
-                if (!(i == 0 && ffn(".ff1", 1, false))) {
-                    if (i == 0 && !add_lin_x3(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 0))
+                // the richest form that can be built, one form down after each failed build; separate_pro plans the prologue Linear on its
+                // own when the form planned does not take it.  Returns whether the epilogue was fused.
+                auto ffn = [&](const std::string& ff, int pro, bool epi, const auto& separate_pro) {
+                    FfnForm f = ffn_decide(ff, pro, epi);
+                    if (pro && !f.pro) separate_pro();
+                    while (!ffn_build(ff, f)) {
+                        if (f.epi) f.epi = false;
+                        else if (f.pro) { f.pro = 0; separate_pro(); }
+                        else f.fused = false;
+                    }
+                    return f.epi;
+                };
+                ffn(".ff1", i == 0 ? 1 : 0, false, [&] {
+                    if (!add_lin_x3(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 0))
                         add_gemm(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
-                    ffn(".ff1", 0, false);
-                }
+                });
                 // the whole attention module (in_proj, per-head softmax(q k^T) v, out_proj, residual) in one launch per clip-resident
                 // workgroup (attn_x3.hip) under the default arithmetic at the compiled shape; NWW_ATTN_FUSED=0: the three launches below
-                static const int attn_fused = [] { const char* e = getenv("NWW_ATTN_FUSED"); return e ? atoi(e) : 1; }();
                 bool attn_done = false;
-                if (attn_fused && p.h->f16 && p.h->conv_products == 6 && attn_x3_supported(T, D, NH)) {
+                if (nww_knobs().attn_fused && p.h->f16 && p.h->conv_products == 6 && attn_x3_supported(T, D, NH)) {
                     const float *iw = p.W(q + ".attention.in_proj_weight"), *ib = p.W(q + ".attention.in_proj_bias");
                     const float *ow = p.W(q + ".attention.out_proj.weight"), *ob = p.W(q + ".attention.out_proj.bias");
                     const auto hiw = f16_fetch(p.h, iw, (size_t)3 * D * D), how = f16_fetch(p.h, ow, (size_t)D * D);
@@ -1318,18 +1331,16 @@ extern "C" int nww_finalize(nww_handle* h) {
                 }
                 if (!attn_done) {
                 // in_proj writes q, k, v head-major when the matrix-core attention consumes them: every (clip, head) block is then
-                // one contiguous run for its LDS-DMA (NWW_QKV_HEAD_MAJOR=0: nn.Linear's [B][T][3 D] rows)
-                static const int mha_mfma0 = [] { const char* e = getenv("NWW_MHA_MFMA"); return e ? atoi(e) : 1; }();
-                const bool want_hm = mha_mfma0 && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
+                // one contiguous run for its LDS-DMA
+                const int mha_mfma = nww_knobs().mha_mfma;
+                const bool want_hm = mha_mfma && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
                 bool head_major = false;
                 if (add_lin_x3(p, q + (want_hm ? ".attention.in_proj(head-major)" : ".attention.in_proj"), hb, big, T, 3 * D, D, p.W(q + ".attention.in_proj_weight"), p.W(q + ".attention.in_proj_bias"), 0,
                                99, 1.f, nullptr, nullptr, want_hm ? T : 0, want_hm ? D / NH : 0))
                     head_major = want_hm;
                 else
                     add_gemm(p, q + ".attention.in_proj", hb, big, T, 3 * D, D, p.W(q + ".attention.in_proj_weight"), p.W(q + ".attention.in_proj_bias"), ACT_NONE);
-                static const int mha_mfma = [] { const char* e = getenv("NWW_MHA_MFMA"); return e ? atoi(e) : 1; }();
-                static const int mha_h2 = 1;
-                if (mha_mfma && mha_h2 && p.h->f16 && mha_h2_supported(T, D, NH))
+                if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
                     p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0); });
                 else if (mha_mfma && mha_mfma_supported(T, D, NH))
                     p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0); });
@@ -1356,18 +1367,14 @@ extern "C" int nww_finalize(nww_handle* h) {
                     }
                 }
                 // conv2 + residual inside ff2's launch, and behind the LAST block's ff2 its LayerNorm + the sums of the time average
-                const bool want_epi = i == nb - 1;
-                bool ff2_done = ffn(".ff2", 2, want_epi);
-                if (ff2_done && want_epi) last_fused = true;
-                if (!ff2_done && want_epi) ff2_done = ffn(".ff2", 2, false);
-                if (!ff2_done) {
-                    const std::string m = q + ".conv_module";
-                    if (!add_lin_x3(p, m + ".conv2(pw)+res", t3, hb, T, D, D, p.W(m + ".conv2.weight"), p.W(m + ".conv2.bias"), 1, hb, 1.0f))
-                        add_gemm(p, m + ".conv2(pw)+res", t3, hb, T, D, D, p.W(m + ".conv2.weight"), p.W(m + ".conv2.bias"), ACT_NONE, nullptr, nullptr, hb, 1.0f);
-                    ffn(".ff2", 0, false);
-                }
+                if (ffn(".ff2", 2, i == nb - 1, [&] {
+                        const std::string m = q + ".conv_module";
+                        if (!add_lin_x3(p, m + ".conv2(pw)+res", t3, hb, T, D, D, p.W(m + ".conv2.weight"), p.W(m + ".conv2.bias"), 1, hb, 1.0f))
+                            add_gemm(p, m + ".conv2(pw)+res", t3, hb, T, D, D, p.W(m + ".conv2.weight"), p.W(m + ".conv2.bias"), ACT_NONE, nullptr, nullptr, hb, 1.0f);
+                    }))
+                    last_fused = true;
                 const float *lw = p.W(q + ".layer_norm.weight"), *lb = p.W(q + ".layer_norm.bias");
-                // the last block's LayerNorm feeds only the mean over time: one pass for both (NWW_LN_MEAN=0: two launches)
+                // the last block's LayerNorm feeds only the mean over time: one pass for both
                 if (last_fused) {
                 } else if (i == nb - 1 && D <= 256) {
                     p.add("layernorm+mean:" + q + " + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], lw, lb, r.B, T, D, r.stream); });
@@ -1382,8 +1389,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         }
     }
     // embedding Linear + Model.classifier (model.py:291-296) (+ sigmoid) -> emb [B][E], logits [B] (, probs [B])
-    static const int tail_fused = [] { const char* e = getenv("NWW_TAIL"); return e ? atoi(e) : 1; }();
-    if (tail_fused && tail_supported(p.tail_K, E)) {
+    if (nww_knobs().tail && tail_supported(p.tail_K, E)) {
         const float *We = p.tail_W, *be = p.tail_b, *W0 = p.W("classifier.0.weight"), *b0 = p.W("classifier.0.bias"),
                     *w3 = p.W("classifier.3.weight"), *b3 = p.W("classifier.3.bias");
         const int tin = p.tail_in, tK = p.tail_K;

@@ -63,7 +63,7 @@ extern "C" int nww_stream_close(nww_handle* h) {
 // NWW_STREAM_INC = 0: every hop re-scores the whole window (rounds 1-3), 1: frontend only, 2: + the fused trunk's rows, 3 (default):
 // + the third conv's rows.
 static int plan_incremental(nww_handle* h, int S, int W, int hop) {
-    static const int mode = [] { const char* e = getenv("NWW_STREAM_INC"); return e ? atoi(e) : 3; }();
+    const int mode = nww_knobs().stream_inc;
     const nww_config& c = h->cfg;
     const int T = fe_num_frames(h->fe, W), hl = h->fe.hop;
     const bool frames_major = !c.mel_major_features || h->e2e_transposed;

@@ -273,8 +273,7 @@ static int rnn_stream_width(int H) { return H <= 192 ? 192 : 256; }
 
 // 128 < H <= 256, a multiple of 4 (the xg rows' alignment), two-term form
 bool rnn_stream_usable(const GruArgs& a) {
-    static const int on = 1;
-    return on && a.products == 3 && a.H > 128 && a.H <= 256 && a.H % 4 == 0 && a.fin == 0;
+    return a.products == 3 && a.H > 128 && a.H <= 256 && a.H % 4 == 0 && a.fin == 0;
 }
 
 size_t rnn_stream_packed_bytes(int gates, int H) {
@@ -292,9 +291,8 @@ hipError_t launch_rnn_stream_pack(const float* w_hh, void* packed, int gates, in
 hipError_t launch_rnn_stream(const GruArgs& a, int gates, hipStream_t s) {
     if (!rnn_stream_usable(a) || !a.w_packed || (gates != 3 && gates != 4) || !(a.w_scale > 0.0f)) return hipErrorInvalidValue;
     const int HP = rnn_stream_width(a.H);
-    static const int force_mt = 0;
     static const int n_cu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256; return n; }();
-    const int mt = force_mt == 1 || force_mt == 2 ? force_mt : (a.B <= 16 * n_cu ? 1 : 2);
+    const int mt = a.B <= 16 * n_cu ? 1 : 2;
     const dim3 grid((a.B + 16 * mt - 1) / (16 * mt)), block(64 * (HP / 32));
     const size_t lds = (size_t)2 * 2 * 16 * mt * (HP + 16) * sizeof(uint16_t);     // two sets of two term planes
 #ifdef NWW_ABLATION

@@ -336,8 +336,7 @@ __global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(GruArgs a)
 
 // widths 32 / 64 / 128 in every arithmetic; any other multiple of 4 below 128 as a zero-padded instance of the next width (two-term form)
 static bool rnn_x3_padded(const GruArgs& a) {
-    static const int on = 1;
-    return on && a.products == 3 && a.H >= 4 && a.H < 128 && a.H % 4 == 0 && a.H != 32 && a.H != 64 && a.fin == 0;
+    return a.products == 3 && a.H >= 4 && a.H < 128 && a.H % 4 == 0 && a.H != 32 && a.H != 64 && a.fin == 0;
 }
 bool rnn_x3_usable(const GruArgs& a) {
     return (a.products == 3 || a.products == 6 || a.products == 9) && (a.H == 32 || a.H == 64 || a.H == 128 || rnn_x3_padded(a)) &&
@@ -346,58 +345,37 @@ bool rnn_x3_usable(const GruArgs& a) {
 
 hipError_t launch_rnn_x3(const GruArgs& a, int gates, hipStream_t s) {
     if (!rnn_x3_usable(a) || (gates != 3 && gates != 4)) return hipErrorInvalidValue;
+    if (gates == 3 && a.fin > 0 && (a.products != 3 || (a.fin != 32 && a.fin != 64) || !a.x_in || !a.w_ih || !a.b_ih || a.reverse))
+        return hipErrorInvalidValue;                          // fused input projection (GRU, two-term form)
     const bool pad = rnn_x3_padded(a);
     const int HP = a.H <= 32 ? 32 : a.H <= 64 ? 64 : 128;     // the instance's width
-    const dim3 grid((a.B + 15) / 16), block(HP == 128 ? 256 : 64 * (HP / 16));
+    const dim3 grid((a.B + 15) / 16);
     const size_t lds = (size_t)2 * (a.products == 3 ? 2 : 3) * 16 * (HP + 16) * sizeof(uint16_t);     // two sets of h planes
     // H = 128 in the two-term form: eight waves of 16 hidden units (two per SIMD, 144 fragment registers each) instead of four of 32 - a step's
-    // products and gate arithmetic per wave halve, and the step is a latency chain: 0.280 -> 0.243 ms (GRU head, B = 2048), 32 -> 23 us (CRNN, B = 16)
-    static const int nb1 = 1;
-    if (pad) {
-#define RNN_PAD(GV, HV) hipLaunchKernelGGL((rnn_x3_kernel<GV, HV, 3, (HV == 128 ? 2 : 1), 0, true>), grid, block, lds, s, a)
-#define RNN_PAD8(GV) hipLaunchKernelGGL((rnn_x3_kernel<GV, 128, 3, 1, 0, true>), grid, dim3(512), lds, s, a)
-        if (gates == 3) { if (HP == 32) RNN_PAD(3, 32); else if (HP == 64) RNN_PAD(3, 64); else if (nb1) RNN_PAD8(3); else RNN_PAD(3, 128); }
-        else { if (HP == 32) RNN_PAD(4, 32); else if (HP == 64) RNN_PAD(4, 64); else RNN_PAD(4, 128); }      // (the padded eight-wave LSTM would need scratch)
-#undef RNN_PAD8
-#undef RNN_PAD
-        return hipGetLastError();
+    // products and gate arithmetic per wave halve, and the step is a latency chain: 0.280 -> 0.243 ms (GRU head, B = 2048), 32 -> 23 us (CRNN, B = 16).
+    // The three-term forms and the padded LSTM (its eight-wave form would need scratch) keep four waves of 32.
+#define RNN_L(GV, HV, NPV, FV, PV)                                                                                   \
+    {                                                                                                                \
+        constexpr int NB = HV == 128 && (NPV != 3 || (GV == 4 && PV)) ? 2 : 1;                                       \
+        hipLaunchKernelGGL((rnn_x3_kernel<GV, HV, NPV, NB, FV, PV>), grid, dim3(64 * (HV / (16 * NB))), lds, s, a);   \
     }
-#define RNN_GO(GV, HV)                                                                                                \
-    if (a.products == 9) hipLaunchKernelGGL((rnn_x3_kernel<GV, HV, 9, (HV == 128 ? 2 : 1)>), grid, block, lds, s, a);  \
-    else if (a.products == 3) hipLaunchKernelGGL((rnn_x3_kernel<GV, HV, 3, (HV == 128 ? 2 : 1)>), grid, block, lds, s, a); \
-    else hipLaunchKernelGGL((rnn_x3_kernel<GV, HV, 6, (HV == 128 ? 2 : 1)>), grid, block, lds, s, a);
-#define RNN_H(GV)                                                                                                     \
-    switch (a.H) {                                                                                                    \
-        case 32: RNN_GO(GV, 32) break;                                                                                \
-        case 64: RNN_GO(GV, 64) break;                                                                                \
-        default: RNN_GO(GV, 128) break;                                                                               \
+#define RNN_H(GV, NPV, FV, PV)                                                                                       \
+    switch (HP) {                                                                                                    \
+        case 32: RNN_L(GV, 32, NPV, FV, PV) break;                                                                   \
+        case 64: RNN_L(GV, 64, NPV, FV, PV) break;                                                                   \
+        default: RNN_L(GV, 128, NPV, FV, PV) break;                                                                  \
     }
-    if (nb1 && a.H == 128 && a.products == 3 && !pad) {
-        const dim3 block8(512);
-        if (gates == 3 && a.fin > 0) {
-            if ((a.fin != 32 && a.fin != 64) || !a.x_in || !a.w_ih || !a.b_ih || a.reverse) return hipErrorInvalidValue;
-            if (a.fin == 32) hipLaunchKernelGGL((rnn_x3_kernel<3, 128, 3, 1, 32>), grid, block8, lds, s, a);
-            else hipLaunchKernelGGL((rnn_x3_kernel<3, 128, 3, 1, 64>), grid, block8, lds, s, a);
-        } else if (gates == 3) hipLaunchKernelGGL((rnn_x3_kernel<3, 128, 3, 1>), grid, block8, lds, s, a);
-        else hipLaunchKernelGGL((rnn_x3_kernel<4, 128, 3, 1>), grid, block8, lds, s, a);
-        return hipGetLastError();
-    }
-    if (gates == 3 && a.fin > 0) {                            // fused input projection (GRU, two-term form)
-        if (a.products != 3 || (a.fin != 32 && a.fin != 64) || !a.x_in || !a.w_ih || !a.b_ih || a.reverse) return hipErrorInvalidValue;
-#define RNN_FIN(HV, FV) hipLaunchKernelGGL((rnn_x3_kernel<3, HV, 3, (HV == 128 ? 2 : 1), FV>), grid, block, lds, s, a)
-        switch (a.H * 100 + a.fin) {
-            case 3232: RNN_FIN(32, 32); break;
-            case 3264: RNN_FIN(32, 64); break;
-            case 6432: RNN_FIN(64, 32); break;
-            case 6464: RNN_FIN(64, 64); break;
-            case 12832: RNN_FIN(128, 32); break;
-            default: RNN_FIN(128, 64); break;
-        }
-#undef RNN_FIN
-        return hipGetLastError();
-    }
-    if (gates == 3) { RNN_H(3) } else { RNN_H(4) }
+#define RNN_P(GV)                                                                                                    \
+    if (a.products == 9) RNN_H(GV, 9, 0, false)                                                                      \
+    else if (a.products == 6) RNN_H(GV, 6, 0, false)                                                                 \
+    else if (pad) RNN_H(GV, 3, 0, true)                                                                              \
+    else RNN_H(GV, 3, 0, false)
+    if (gates == 4) { RNN_P(4) }
+    else if (a.fin == 32) { RNN_H(3, 3, 32, false) }
+    else if (a.fin == 64) { RNN_H(3, 3, 64, false) }
+    else { RNN_P(3) }
+#undef RNN_P
 #undef RNN_H
-#undef RNN_GO
+#undef RNN_L
     return hipGetLastError();
 }

@@ -48,7 +48,7 @@ size_t trunk_lds_bytes(int C1, int H, int W, int S) {
     return worst * sizeof(float);
 }
 // strips per clip: the whole clip (one 8-wave workgroup per CU) whenever it fits in LDS, else the fewest strips that
-// do.  Two 4-wave workgroups per CU on half-clip strips (NWW_TRUNK_STRIPS=2) measured no better: with equal work the
+// do.  Two 4-wave workgroups per CU on half-clip strips measured no better: with equal work the
 // two stay in lock-step, so one's conv1 does not fall under the other's conv2.
 int trunk_pick_strips(int C1, int H, int W, int* wgs_per_cu) {
     const int H2 = H / 4;
@@ -402,16 +402,10 @@ hipError_t launch_cnn_trunk(const TrunkArgs& a, int C1, int C2, int max_grid, hi
 #else
     const int dbg = 0;
 #endif
-    static const int force_strips = 0;
     TrunkArgs aa = a;
     aa.dbg = dbg;
     int per_cu = 0;
     int S = trunk_pick_strips(C1, a.H, a.W, &per_cu);
-    if (force_strips > 0 && force_strips <= a.H / 4) {
-        S = force_strips;
-        const size_t l = trunk_lds_bytes(C1, a.H, a.W, S);
-        per_cu = l <= 80 * 1024 ? 2 : (l <= 160 * 1024 ? 1 : 0);
-    }
     if (S < 1 || per_cu < 1) return hipErrorInvalidValue;
     aa.strips = S;
     const size_t lds = trunk_lds_bytes(C1, a.H, a.W, S);

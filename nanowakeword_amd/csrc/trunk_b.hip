@@ -1332,17 +1332,14 @@ static hipError_t launch_cnn_trunk_b_stream(TrunkArgs aa, int products, int max_
 hipError_t launch_cnn_trunk_b(const TrunkArgs& a, int products, int max_grid, hipStream_t s) {
     if (!a.wpack || (products != 3 && products != 6 && products != 9)) return hipErrorInvalidValue;
     TrunkArgs aa = a;
-    static const int force_strips = 0;
     if (a.n_sub > 0 || a.out_ring_rows > 0) return launch_cnn_trunk_b_stream(aa, products, max_grid, s);
     int S = trunk_b_pick_strips(a.H, a.W);
     if (S < 1) return hipErrorInvalidValue;
-    if (force_strips > S && force_strips <= a.H / 4) S = force_strips;
     // a handful of clips (the interpreter's B = 1 .. 16 calls) would occupy a handful of CUs for a whole clip each: cut
     // every clip into more row strips on more CUs instead.  Seam rows are recomputed by both neighbours with the same
     // arithmetic, so the result does not depend on the strip count (bit for bit).
-    if (!force_strips)
-        for (int small_strips : {8, 6, 4})
-            if (small_strips > S && (long)a.B * small_strips * 4 <= max_grid && small_strips <= a.H / 4) { S = small_strips; break; }
+    for (int small_strips : {8, 6, 4})
+        if (small_strips > S && (long)a.B * small_strips * 4 <= max_grid && small_strips <= a.H / 4) { S = small_strips; break; }
     aa.strips = S;
     const size_t lds = trunk_b_lds_bytes(a.H, a.W, S, products);
     long want = (long)a.B * S;
