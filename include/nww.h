@@ -42,6 +42,7 @@ extern "C" {
 #define NWW_HEAD_BCRESNET 4    /* BcResNetModel           architectures.py:620-687 */
 #define NWW_HEAD_CONFORMER 5   /* ConformerModel          architectures.py:441-543 */
 #define NWW_HEAD_E2E_DNN 6     /* E2E_MelSpectrogram_CNN  architectures.py:820-889 */
+#define NWW_HEAD_TRANSFORMER 7 /* TransformerModel        architectures.py:164-206 */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1
@@ -70,6 +71,8 @@ typedef struct nww_config {
     int32_t layer_dim, n_blocks, embedding_dim, activation;
     int32_t n_crnn_channels;   /* crnn_cnn_channels (<= 4 stages)                             */
     int32_t crnn_channels[4];
+    /* d_model / n_head of the attention encoder (Conformer, Transformer): conformer_d_model / conformer_n_head for
+       NWW_HEAD_CONFORMER, transformer_d_model / transformer_n_head (model.py:200-201) for NWW_HEAD_TRANSFORMER      */
     int32_t conformer_d_model, conformer_n_head;
     /* how nww_forward_pcm feeds the head: 0 = log-mel transposed to (frames, n_mels) =
        Model(input_shape=(frames, n_mels)); 1 = (n_mels, frames) as E2E_MelSpectrogram_CNN.   */

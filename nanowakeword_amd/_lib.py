@@ -169,7 +169,11 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
     c.n_crnn_channels = len(ch)
     for i, v in enumerate(ch):
         c.crnn_channels[i] = int(v)
-    c.conformer_d_model, c.conformer_n_head = head.conformer_d_model, head.conformer_n_head
+    # the two slots carry d_model / n_head of whichever attention encoder the head has (include/nww.h)
+    if head.model_type == "transformer":
+        c.conformer_d_model, c.conformer_n_head = head.transformer_d_model, head.transformer_n_head
+    else:
+        c.conformer_d_model, c.conformer_n_head = head.conformer_d_model, head.conformer_n_head
     c.crnn_rnn_lstm = int(head.model_type == "crnn" and head.crnn_rnn_type == "lstm")
     if mel_major_features is None:
         mel_major_features = head.model_type == "e2e_dnn"

@@ -15,12 +15,14 @@ from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn")
+HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
-HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6}
+HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7}
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
+# rows of the Transformer's positional-encoding buffer (PositionalEncoding(max_len=5000), architectures.py:31)
+PE_MAX_LEN = 5000
 
 
 @dataclass
@@ -61,6 +63,8 @@ class HeadConfig:
     crnn_rnn_type: str = "gru"
     conformer_d_model: int = 144
     conformer_n_head: int = 4
+    transformer_d_model: int = 128     # model.py:200-201 config keys of the Transformer head
+    transformer_n_head: int = 4
 
     def __post_init__(self):
         self.model_type = self.model_type.lower()
@@ -174,6 +178,20 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
             s[f"{p}.conv_module.conv2.weight"] = (D, D, 1); s[f"{p}.conv_module.conv2.bias"] = (D,)
             _ln(s, f"{p}.layer_norm", D)
         _lin(s, "model.output_proj", E, D)
+    elif mt == "transformer":             # architectures.py:164-206 (TransformerModel), PositionalEncoding :26-48
+        D = cfg.transformer_d_model
+        _lin(s, "model.input_proj", D, F)
+        s["model.pos_encoder.pe"] = (PE_MAX_LEN, 1, D)
+        for i in range(nb):
+            p = f"model.transformer_encoder.layers.{i}"
+            s[f"{p}.self_attn.in_proj_weight"] = (3 * D, D)
+            s[f"{p}.self_attn.in_proj_bias"] = (3 * D,)
+            _lin(s, f"{p}.self_attn.out_proj", D, D)
+            _lin(s, f"{p}.linear1", 4 * D, D)
+            _lin(s, f"{p}.linear2", D, 4 * D)
+            _ln(s, f"{p}.norm1", D)
+            _ln(s, f"{p}.norm2", D)
+        _lin(s, "model.output_proj", E, D)
     elif mt == "e2e_dnn":                 # architectures.py:840-865 (E2E_MelSpectrogram_CNN body)
         cin = 1
         for i, c in enumerate((16, 32, 64)):
@@ -234,5 +252,11 @@ def head_macs(cfg: HeadConfig) -> int:
         m += T * F * D + D * E
         per = 2 * (2 * T * D * 4 * D) + T * 3 * D * D + 2 * T * T * D + T * D * D \
             + T * D * 2 * D + 31 * T * D + T * D * D
+        m += nb * per
+    elif mt == "transformer":
+        D = cfg.transformer_d_model
+        m += T * F * D + D * E
+        # in_proj, q k^T and (softmax) v, out_proj, linear1, linear2
+        per = T * 3 * D * D + 2 * T * T * D + T * D * D + 2 * T * D * 4 * D
         m += nb * per
     return int(m)

@@ -1,4 +1,5 @@
-// ffn_x3.h - fused Conformer feed-forward module (ffn_x3.hip): h <- h + rscale * (W2 . swish(W1 . LayerNorm(h) + b1) + b2)
+// ffn_x3.h - fused Conformer feed-forward module (ffn_x3.hip): h <- h + rscale * (W2 . swish(W1 . LayerNorm(h) + b1) + b2),
+// and the Transformer's post-norm ReLU form (launch_ffn_x3_post)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -51,3 +52,13 @@ hipError_t launch_ffn_x3_pro_pack(const float* W, void* out, int D, int KP, floa
 size_t ffn_x3_msum_bytes(int M, int D);
 hipError_t launch_ffn_x3_mean_finish(const float* msum, float* out, int B, int T, int D, float m_scale, hipStream_t s);
 hipError_t launch_ffn_x3(const FfnArgs& a, int D, hipStream_t s);
+// ---- the post-norm ReLU module of nn.TransformerEncoderLayer (norm_first = False, two-term form):
+//     h <- LayerNorm2(y + W2 . relu(W1 . y + b1) + b2),  y = LayerNorm1(h)      (ln_w / ln_b = norm1, ln2_w / ln2_b = norm2)
+// in place, or with msum != nullptr (the last layer) not stored: exact per-tile sums of the LayerNorm2-ed rows for the time mean, as the EPI
+// instances, for clips of any length T - a 32-row tile holds rows of at most ffn_x3_post_nseg(T) clips
+__host__ __device__ inline int ffn_x3_post_nseg(int T) { return (30 + T) / T + 1; }
+bool ffn_x3_post_supported(int D);
+size_t ffn_x3_post_msum_floats(int B, int T, int D);
+hipError_t launch_ffn_x3_post(const FfnArgs& a, int D, hipStream_t s);
+// out [B][D] = the time means of the LayerNorm2-ed rows from launch_ffn_x3_post's sums
+hipError_t launch_ffn_x3_post_mean_finish(const float* msum, float* out, int B, int T, int D, float m_scale, hipStream_t s);

@@ -190,9 +190,13 @@ __global__ void __launch_bounds__(256) ffn_mean_finish_kernel(const float* __res
 // accumulator layout is the module's input AND the start value of the output accumulators (h0 / (rscale ik2): the residual rides through
 // the second product, nothing is re-read at the end).  EPI (round 6): the updated rows are not stored - LayerNorm, then exact per-tile,
 // per-clip sums (FfnArgs::msum).
-template <int D16, bool H2, int KP16 = 0, bool PRES = false, bool EPI = false>
+// POST: the post-norm ReLU module of nn.TransformerEncoderLayer (norm_first = False): y = LayerNorm1(h) (ln_w, ln_b), then
+// LayerNorm2(y + W2 . relu(W1 . y + b1) + b2) (ln2_w, ln2_b) - stored in place, or with EPI summed per tile and clip segment for the time
+// mean (any T: a tile's 32 rows may span several clips, ffn_x3_post_nseg).  rscale is not used.
+template <int D16, bool H2, int KP16 = 0, bool PRES = false, bool EPI = false, bool POST = false>
 __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
     static_assert(KP16 == 0 || H2, "the prologue product exists in the two-term form only");
+    static_assert(!POST || (H2 && KP16 == 0), "the post-norm instances: two-term form, no prologue");
     constexpr int D = 16 * D16, NOB = (D + 31) / 32, NHB = D / 8;
     constexpr int NT = H2 ? 2 : 3, NP = H2 ? 3 : 6;            // terms per value, partial products per operand pair
     constexpr int W1_PART = (D16 * NT * 1024 + 4095) & ~4095, W2_PART = (NOB * 2 * NT * 1024 + 128 + 4095) & ~4095, BLK = W1_PART + W2_PART;
@@ -236,6 +240,7 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
     auto fetch_w2 = [&](int hb, unsigned char* buf) { fetch(a.packed + (size_t)hb * BLK + W1_PART, buf, std::integral_constant<int, W2_PART / 4096>{}); };
     bf16x8 xf[D16][NT];
     f32x16 yacc[NOB];
+    float ln1_mu = 0.0f, ln1_rstd = 1.0f;                      // POST: the input row's LayerNorm, applied again to the residual at the end
     if constexpr (KP16 == 0) {
     FFN_STAMP(30, 0)
     fetch_w1(0, w1b0);
@@ -267,6 +272,7 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
             for (int e = 0; e < 8; ++e) { const float d = v[kb][e] - mu; q = fmaf(d, d, q); }
         q += __shfl_xor(q, 32, 64);
         const float rstd = 1.0f / sqrtf(q / (float)D + 1e-5f);
+        if constexpr (POST) { ln1_mu = mu; ln1_rstd = rstd; }
 #pragma unroll
         for (int kb = 0; kb < D16; ++kb) {
             const float4 w0 = *reinterpret_cast<const float4*>(a.ln_w + 16 * kb + 8 * h), w1 = *reinterpret_cast<const float4*>(a.ln_w + 16 * kb + 8 * h + 4);
@@ -442,6 +448,11 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
         }
     };
     auto piece_a = [&](int e, const f32x16& acc, const float (&bias)[16]) {
+        if constexpr (POST) {                                  // ReLU: no second stage
+            va[e] = fmaxf(fmaf(acc[e], ik1, bias[e]), 0.0f);
+            asm volatile("" : "+v"(va[e]));
+            return;
+        }
         va[e] = H2 ? fmaf(acc[e], ik1, bias[e]) : acc[e] + bias[e];
         ua[e] = 1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * va[e]);
         asm volatile("" : "+v"(va[e]), "+v"(ua[e]));
@@ -467,7 +478,8 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
                 const int j = p / 3, st = p - 3 * j;
                 if (st < 2) {
                     const int e = 2 * j + st;
-                    va[e] = (va[e] * s_h) * __builtin_amdgcn_rcpf(ua[e]);
+                    if constexpr (POST) va[e] = va[e] * s_h;
+                    else va[e] = (va[e] * s_h) * __builtin_amdgcn_rcpf(ua[e]);
                     asm volatile("" : "+v"(va[e]));
                 } else {
                     nww_split2h(va[2 * j], va[2 * j + 1], th[j], tl[j]);
@@ -667,7 +679,13 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
                     yacc[ob][4 * g + 0] *= ik2; yacc[ob][4 * g + 1] *= ik2; yacc[ob][4 * g + 2] *= ik2; yacc[ob][4 * g + 3] *= ik2;
                 }
                 float4 r;
-                if constexpr (KP16 == 0) {
+                if constexpr (POST) {                          // LayerNorm1(h) again (the module's input, now in this layout) + Y + b2
+                    const float4 w = *reinterpret_cast<const float4*>(a.ln_w + m), c = *reinterpret_cast<const float4*>(a.ln_b + m);
+                    r.x = ((res[ob][g].x - ln1_mu) * ln1_rstd * w.x + c.x) + (yacc[ob][4 * g + 0] + b2.x);
+                    r.y = ((res[ob][g].y - ln1_mu) * ln1_rstd * w.y + c.y) + (yacc[ob][4 * g + 1] + b2.y);
+                    r.z = ((res[ob][g].z - ln1_mu) * ln1_rstd * w.z + c.z) + (yacc[ob][4 * g + 2] + b2.z);
+                    r.w = ((res[ob][g].w - ln1_mu) * ln1_rstd * w.w + c.w) + (yacc[ob][4 * g + 3] + b2.w);
+                } else if constexpr (KP16 == 0) {
                     r = res[ob][g];
                     r.x += a.rscale * (yacc[ob][4 * g + 0] + b2.x);
                     r.y += a.rscale * (yacc[ob][4 * g + 1] + b2.y);
@@ -679,7 +697,7 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
                     r.z = a.rscale * (yacc[ob][4 * g + 2] + b2.z);
                     r.w = a.rscale * (yacc[ob][4 * g + 3] + b2.w);
                 }
-                if constexpr (!EPI) {
+                if constexpr (!EPI && !POST) {
                     if (row_ok) *reinterpret_cast<float4*>(hrow + m) = r;
                 } else {
                     yacc[ob][4 * g + 0] = r.x; yacc[ob][4 * g + 1] = r.y; yacc[ob][4 * g + 2] = r.z; yacc[ob][4 * g + 3] = r.w;
@@ -687,11 +705,11 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
             }
         }
     FFN_STAMP(31, 1)
-    if constexpr (EPI) {
+    if constexpr (EPI || POST) {
         // ---- LayerNorm of the updated rows, then per tile and clip segment the column sums - staged through the wave's own (dead) weight
         // buffer as [32 rows][D + 4] float32 (16-byte stores conflict-free at this pitch), summed by lane = column in row order
         constexpr int GP = D + 4;
-        static_assert(32 * GP * 4 <= W1_PART, "the staging tile must fit a weight buffer");
+        static_assert(POST || 32 * GP * 4 <= W1_PART, "the staging tile must fit a weight buffer");      // (POST returned above)
         float sm = 0.0f;
 #pragma unroll
         for (int ob = 0; ob < NOB; ++ob)
@@ -708,6 +726,75 @@ __global__ void __launch_bounds__(256) ffn_x3_kernel(FfnArgs a) {
                 if (32 * ob + 8 * (r >> 2) < D) { const float d = yacc[ob][r] - mu2; q2 = fmaf(d, d, q2); }
         q2 += __shfl_xor(q2, 32, 64);
         const float rstd2 = 1.0f / sqrtf(q2 / (float)D + 1e-5f);
+        if constexpr (POST && !EPI) {                          // LayerNorm2, stored in place
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    if (32 * ob + 8 * g < D) {
+                        const int m = 32 * ob + 8 * g + 4 * h;
+                        const float4 w = *reinterpret_cast<const float4*>(a.ln2_w + m), c = *reinterpret_cast<const float4*>(a.ln2_b + m);
+                        const float4 o = make_float4((yacc[ob][4 * g + 0] - mu2) * rstd2 * w.x + c.x, (yacc[ob][4 * g + 1] - mu2) * rstd2 * w.y + c.y,
+                                                     (yacc[ob][4 * g + 2] - mu2) * rstd2 * w.z + c.z, (yacc[ob][4 * g + 3] - mu2) * rstd2 * w.w + c.w);
+                        if (row_ok) *reinterpret_cast<float4*>(hrow + m) = o;
+                    }
+            return;
+        }
+        if constexpr (POST) {
+            // LayerNorm2, then the exact per-tile sums of EPI below, for clips of any length: segment sg of the tile = its rows of clip
+            // c0 + sg (c0 = the clip of its first row), ffn_x3_post_nseg(T) segments of two planes of D floats per tile.  The staging pitch is
+            // D + 4 where that fits the wave's weight buffer, else D (the buffers are 32 D floats at least)
+            constexpr int GPP = 32 * (D + 4) * 4 <= W1_PART ? D + 4 : D;
+            static_assert(32 * GPP * 4 <= W1_PART, "the staging tile must fit a weight buffer");
+            __syncthreads();                                   // every wave has left the weight buffers
+            float* st = reinterpret_cast<float*>(wave == 0 ? w1b0 : wave == 1 ? w1b1 : wave == 2 ? w2b0 : w2b1);
+            const float sc1 = a.m_scale * (1.0f / 262144.0f);
+            const long long r0 = (long long)blockIdx.x * 128 + wave * 32;
+            const int nv = (int)max((long long)0, min((long long)32, (long long)a.M - r0));
+            const long long c0 = r0 / a.T;
+            const int nseg = ffn_x3_post_nseg(a.T);
+            constexpr int NC = (D + 63) / 64;
+            float* mrow = a.msum + (size_t)(blockIdx.x * 4 + wave) * nseg * 2 * D;      // [segment][plane][D]
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+                for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        if (32 * ob + 8 * g < D) {
+                            const int m = 32 * ob + 8 * g + 4 * h;
+                            float o[4];
+                            if (pl == 0) {
+                                const float4 w = *reinterpret_cast<const float4*>(a.ln2_w + m), c = *reinterpret_cast<const float4*>(a.ln2_b + m);
+                                const float wv[4] = {w.x, w.y, w.z, w.w}, cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    const float t = ((yacc[ob][4 * g + q] - mu2) * rstd2 * wv[q] + cv[q]) * sc1, hf = __builtin_rintf(t);
+                                    o[q] = hf;
+                                    yacc[ob][4 * g + q] = __builtin_rintf((t - hf) * 262144.0f);
+                                }
+                            } else {
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) o[q] = yacc[ob][4 * g + q];
+                            }
+                            *reinterpret_cast<float4*>(st + n * GPP + m) = make_float4(o[0], o[1], o[2], o[3]);
+                        }
+                __builtin_amdgcn_wave_barrier();               // (one wave: its LDS operations execute in order)
+                for (int sg = 0; sg < nseg; ++sg) {
+                    const long long cb = (c0 + sg) * a.T - r0;
+                    const int lo = (int)max((long long)0, min((long long)nv, cb)), hi = (int)max((long long)0, min((long long)nv, cb + a.T));
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) {
+                        float sum = 0.0f;
+                        if (lane + 64 * k < D)
+                            for (int j = lo; j < hi; ++j) sum += st[j * GPP + lane + 64 * k];
+                        if (lane + 64 * k < D) mrow[(size_t)(2 * sg + pl) * D + lane + 64 * k] = sum;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+            return;
+        }
         FFN_STAMP(31, 3)
         __syncthreads();                                       // every wave has left the weight buffers
         FFN_STAMP(31, 4)
@@ -787,6 +874,11 @@ bool ffn_x3_pro_supported(int D, int KP) { return D == 144 && (KP == 64 || KP ==
 // the epilogue's clips are at least one 32-row tile long (a tile touches at most two clips)
 bool ffn_x3_epi_supported(int D, int T) { return D == 144 && T >= 32; }
 
+bool ffn_x3_post_supported(int D) { return ffn_x3_supported(D, true); }
+size_t ffn_x3_post_msum_floats(int B, int T, int D) {
+    return ((size_t)((((long long)B * T + 127) / 128) * 4)) * ffn_x3_post_nseg(T) * 2 * D;
+}
+
 hipError_t launch_ffn_x3_pack(const float* W1, const float* b1, const float* W2, void* out, int D, hipStream_t s, float sw1, float sw2, int perm) {
     const size_t total = (size_t)(D / 8) * (D / 16 + 2 * ((D + 31) / 32)) * 64;
     hipLaunchKernelGGL(ffn_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, W1, b1, W2,
@@ -808,6 +900,57 @@ hipError_t launch_ffn_x3_mean_finish(const float* msum, float* out, int B, int T
     if (!ffn_x3_epi_supported(D, T) || !(m_scale > 0.0f)) return hipErrorInvalidValue;
     const size_t total = (size_t)B * D;
     hipLaunchKernelGGL(ffn_mean_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, msum, out, B, T, D, 1.0 / ((double)m_scale * (double)T));
+    return hipGetLastError();
+}
+
+// out [b][c] = (sum over the clip's tile segments) / (scale T), segments as ffn_x3_kernel<.., POST> writes them (ffn_x3_post_nseg per tile)
+__global__ void __launch_bounds__(256) ffn_post_mean_finish_kernel(const float* __restrict__ msum, float* __restrict__ out, int B, int T, int D,
+                                                                   int nseg, double inv) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)B * D) return;
+    const int c = (int)(idx % D);
+    const long long b = (long long)(idx / D);
+    const long long t0 = (b * T) / 32, t1 = (b * T + T - 1) / 32;
+    double hi = 0.0, lo = 0.0;                                 // integers: exact in any order
+    for (long long t = t0; t <= t1; ++t) {
+        const long long sg = b - (32 * t) / T;                 // 0 .. nseg - 1
+        const float* m = msum + ((size_t)t * nseg + sg) * 2 * D;
+        hi += (double)m[c]; lo += (double)m[D + c];
+    }
+    out[idx] = (float)((hi * 262144.0 + lo) * inv);
+}
+
+hipError_t launch_ffn_x3_post_mean_finish(const float* msum, float* out, int B, int T, int D, float m_scale, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    if (!ffn_x3_post_supported(D) || T <= 0 || !(m_scale > 0.0f)) return hipErrorInvalidValue;
+    const size_t total = (size_t)B * D;
+    hipLaunchKernelGGL(ffn_post_mean_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, msum, out, B, T, D,
+                       ffn_x3_post_nseg(T), 1.0 / ((double)m_scale * (double)T));
+    return hipGetLastError();
+}
+
+hipError_t launch_ffn_x3_post(const FfnArgs& a, int D, hipStream_t s) {
+    if (a.M <= 0) return hipSuccess;
+    const bool epi = a.msum != nullptr;
+    if (!ffn_x3_post_supported(D) || !(a.h2_x > 0.0f) || !a.ln2_w || !a.ln2_b || a.pro_k != 0 || (epi && (a.T <= 0 || a.M % a.T || !(a.m_scale > 0.0f))))
+        return hipErrorInvalidValue;
+    const dim3 grid((a.M + 127) / 128);
+#define FFN_POST(D16V)                                                                                             \
+    {                                                                                                              \
+        if (epi) hipLaunchKernelGGL((ffn_x3_kernel<D16V, true, 0, false, true, true>), grid, dim3(256), 0, s, a);   \
+        else hipLaunchKernelGGL((ffn_x3_kernel<D16V, true, 0, false, false, true>), grid, dim3(256), 0, s, a);     \
+    }
+    switch (D) {
+        case 32: FFN_POST(2) break;
+        case 64: FFN_POST(4) break;
+        case 96: FFN_POST(6) break;
+        case 128: FFN_POST(8) break;
+        case 144: FFN_POST(9) break;
+        case 192: FFN_POST(12) break;
+        case 256: FFN_POST(16) break;
+        default: return hipErrorInvalidValue;
+    }
+#undef FFN_POST
     return hipGetLastError();
 }
 

@@ -131,6 +131,8 @@ hipError_t launch_avgpool(const float* in, float* out, int BC, int H, int W, int
                           int ow, hipStream_t s);
 // y = act(x) elementwise (sigmoid for probabilities)
 hipError_t launch_unary(const float* x, float* y, size_t n, int act, hipStream_t s);
+// x [B][T][D] <- x * scale + pe[t][D] in place (the Transformer's input projection output, architectures.py:196-199; pe has >= T rows)
+hipError_t launch_scale_add_pe(float* x, const float* pe, int B, int T, int D, float scale, hipStream_t s);
 // GLU over the last axis: in [R][2D] -> out [R][D] = in[:, :D] * sigmoid(in[:, D:])
 hipError_t launch_glu(const float* in, float* out, int R, int D, hipStream_t s);
 // depthwise conv1d over time, 'same' padding, + bias, folded BN (alpha,beta), Swish: x [B][T][D] -> y [B][T][D]
@@ -146,7 +148,8 @@ bool mha_head_dim_supported(int head_dim);
 // the same from two binary16 terms per operand on v_mfma_f32_32x32x16_f16 (mha_h2.hip; NWW_ARITH_F16X3): K, V scaled by the
 // unit's own maxima, every query row by its own
 bool mha_h2_supported(int T, int D, int n_head);
-hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s, int head_major = 0);
+// exact_sub = 1: the softmax subtracts the maximum from the raw scores before scaling them (mha_h2.hip XSUB; the Transformer head)
+hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s, int head_major = 0, int exact_sub = 0);
 // [B][C][H][W] -> [B][W][C*H]  (CRNN: sequence over W, features C*H; architectures.py:272-276)
 hipError_t launch_crnn_seq(const float* in, float* out, int B, int C, int H, int W, hipStream_t s);
 // GRU recurrence for one direction. xg [B][T][3H] = x W_ih^T + b_ih (precomputed by GEMM).

@@ -1104,6 +1104,20 @@ hipError_t launch_mha_core(const float* qkv, float* out, int B, int T, int D, in
 #undef MHA_CASE
     return hipGetLastError();
 }
+__global__ void __launch_bounds__(256) scale_add_pe_kernel(float* __restrict__ x, const float* __restrict__ pe, size_t n, int T, int D, float scale) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = i / D;
+    x[i] = x[i] * scale + pe[(row % T) * D + (i - row * D)];
+}
+
+hipError_t launch_scale_add_pe(float* x, const float* pe, int B, int T, int D, float scale, hipStream_t s) {
+    const size_t n = (size_t)B * T * D;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(scale_add_pe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, pe, n, T, D, scale);
+    return hipGetLastError();
+}
+
 bool mha_head_dim_supported(int dh) { return dh >= 1 && mha_compiled_width(dh) > 0; }
 
 // ------------------------------------------------------------------------------------------ GRU recurrence

@@ -6,14 +6,15 @@
 struct LinArgs {
     const float* x; int ldx;         // [M][K] input rows
     float* out; int ldc;             // [M][N]
-    const float* res; int ldres;     // epilogue 1: out = res + rscale * (y + bias)   (res may be out)
+    const float* res; int ldres;     // epilogue 1: out = res + rscale * (y + bias)   (res may be out); epilogue 3: res = positional table
     float rscale;
     const float* ln_w; const float* ln_b;      // LayerNorm over the K input features first (epilogue 2 instances only)
     const unsigned char* packed;     // launch_lin_x3_pack output
     int M, N;                        // N = output features written (for the GLU epilogue: of the gated product)
     int nblk = 0;                    // filled by the launcher
     // epilogue 0 only, qkv_T > 0: N = 3 D outputs are stored head-major, out[which = q|k|v][clip][head][t][dh] (clip = row / qkv_T,
-    // t = row % qkv_T, head = (col % D) / qkv_dh) - every (clip, head) block of the attention kernel is then one contiguous run
+    // t = row % qkv_T, head = (col % D) / qkv_dh) - every (clip, head) block of the attention kernel is then one contiguous run.
+    // Epilogue 3: out = rscale (y + bias) + res[(row % qkv_T) ldres ..] (rows of one clip = qkv_T consecutive rows)
     int qkv_T = 0, qkv_dh = 0;
     // h2 = 1 (NWW_ARITH_F16X3): two binary16 terms per operand, three products per float32 product.  The weights are packed with
     // terms = 2 as binary16 terms of W x ws (ws a power of two putting the largest weight in [2^14, 2^15)), w_un = 1 / ws; an input row
@@ -33,5 +34,5 @@ size_t lin_x3_packed_bytes(int K, int n_out, int parts, int terms = 3);
 // terms = 3: three bf16 terms per weight; terms = 2: two binary16 terms of W x ws (LinArgs::h2)
 hipError_t launch_lin_x3_pack(const float* W, const float* bias, void* out, int K, int n_out, int parts, int gate_off, hipStream_t s,
                               int terms = 3, float ws = 1.0f);
-// epi: 0 plain, 1 residual, 2 GLU; ln: LayerNorm prologue (epi 2 only)
+// epi: 0 plain, 1 residual, 2 GLU, 3 scale + positional row (LinArgs::qkv_T rows per clip); ln: LayerNorm prologue (epi 2 only)
 hipError_t launch_lin_x3(const LinArgs& a, int K, int epi, bool ln, hipStream_t s);

@@ -108,7 +108,9 @@ __global__ void __launch_bounds__(256) lin_pack_kernel(const float* __restrict__
         reinterpret_cast<float*>(base + (size_t)parts * K16 * terms * 1024)[part * 32 + lane] = (bias && col < n_out) ? bias[part * gate_off + col] : 0.0f;
 }
 
-// EPI: 0 = out = y + bias;  1 = out = res + rscale * (y + bias);  2 = GLU, out = (ya + bias_a) * sigmoid(yb + bias_b)
+// EPI: 0 = out = y + bias;  1 = out = res + rscale * (y + bias);  2 = GLU, out = (ya + bias_a) * sigmoid(yb + bias_b);
+//      3 = out = rscale * (y + bias) + res[row % qkv_T] (the Transformer's input projection: rscale = sqrt(d_model), res = the positional
+//          table pe [>= T][D], one row per time step of the clip)
 // NWV waves per workgroup (32 rows each) share every weight block streamed through LDS
 // H2: two binary16 terms per operand with a per-row scale (LinArgs::h2); fragments are carried as 128-bit bags typed bf16x8 either way
 template <int K16, int EPI, bool LN, int NWV, bool H2 = false>
@@ -242,7 +244,7 @@ __global__ void __launch_bounds__(64 * NWV, 2) lin_x3_kernel(LinArgs a) {
                 const int b = (int)(rrj / T), t = (int)(rrj - (size_t)b * T);
                 t_orow[j] = a.out + ((size_t)b * NH * T + t) * dh;
             }
-            t_rrow[j] = EPI == 1 ? a.res + rrj * a.ldres : nullptr;
+            t_rrow[j] = EPI == 1 ? a.res + rrj * a.ldres : EPI == 3 ? a.res + (rrj % (size_t)a.qkv_T) * a.ldres : nullptr;
         }
     }
     auto block = [&](int blk, const unsigned char* wbuf) {
@@ -255,7 +257,7 @@ __global__ void __launch_bounds__(64 * NWV, 2) lin_x3_kernel(LinArgs a) {
             for (int r = 0; r < 16; ++r) acc[p][r] = 0.0f;
         // the residual values of this block's outputs travel during its products
         float4 rres[4];
-        if (EPI == 1) {
+        if (EPI == 1 || EPI == 3) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int col = 32 * blk + 4 * tq;
@@ -312,7 +314,7 @@ __global__ void __launch_bounds__(64 * NWV, 2) lin_x3_kernel(LinArgs a) {
             for (int j = 0; j < 4; ++j) {
                 const float4 y = *reinterpret_cast<const float4*>(tb + (8 * j + (lane >> 3)) * TP + 4 * tq);
                 float4 o = make_float4(y.x + b0.x, y.y + b0.y, y.z + b0.z, y.w + b0.w);
-                if (EPI == 1) {
+                if (EPI == 1 || EPI == 3) {
                     const float4 r4 = rres[j];
                     o.x = r4.x + a.rscale * o.x; o.y = r4.y + a.rscale * o.y; o.z = r4.z + a.rscale * o.z; o.w = r4.w + a.rscale * o.w;
                 }
@@ -388,7 +390,8 @@ hipError_t launch_lin_x3_pack(const float* W, const float* bias, void* out, int 
 hipError_t launch_lin_x3(const LinArgs& a0, int K, int epi, bool ln, hipStream_t s) {
     if (a0.M <= 0) return hipSuccess;
     if (!lin_x3_supported(K, a0.N, a0.h2 != 0) || (ln && epi != 2) || (a0.ldx % 4) || (a0.ldc % 4)) return hipErrorInvalidValue;
-    if (a0.qkv_T > 0 && (epi != 0 || a0.N > 1024 || a0.N % 3 || a0.qkv_dh <= 0 || (a0.N / 3) % a0.qkv_dh || a0.qkv_dh % 4 || a0.M % a0.qkv_T))
+    if (epi == 3 && (a0.qkv_T <= 0 || !a0.res || (a0.ldres % 4))) return hipErrorInvalidValue;
+    if (a0.qkv_T > 0 && epi != 3 && (epi != 0 || a0.N > 1024 || a0.N % 3 || a0.qkv_dh <= 0 || (a0.N / 3) % a0.qkv_dh || a0.qkv_dh % 4 || a0.M % a0.qkv_T))
         return hipErrorInvalidValue;
     // 16-byte row loads / stores (as the general GEMM's loaders): refuse a misaligned buffer loudly instead of faulting
     if (((reinterpret_cast<uintptr_t>(a0.x) | reinterpret_cast<uintptr_t>(a0.out) | reinterpret_cast<uintptr_t>(a0.res)) & 15) != 0) return hipErrorInvalidValue;
@@ -411,9 +414,11 @@ hipError_t launch_lin_x3(const LinArgs& a0, int K, int epi, bool ln, hipStream_t
 #define LIN_GO_H2ONLY(K16V, EPIV, LNV)                                                                             \
     if (a.h2) { LIN_GO2(K16V, EPIV, LNV, true) } else return hipErrorInvalidValue;
 #define LIN_EPI(K16V)                                                                                              \
-    if (epi == 0) { LIN_GO(K16V, 0, false) } else if (epi == 1) { LIN_GO(K16V, 1, false) } else if (ln) { LIN_GO(K16V, 2, true) } else { LIN_GO(K16V, 2, false) }
+    if (epi == 0) { LIN_GO(K16V, 0, false) } else if (epi == 1) { LIN_GO(K16V, 1, false) } else if (epi == 3) { LIN_GO(K16V, 3, false) }        \
+    else if (ln) { LIN_GO(K16V, 2, true) } else { LIN_GO(K16V, 2, false) }
 #define LIN_EPI_H2(K16V)                                                                                           \
-    if (epi == 0) { LIN_GO_H2ONLY(K16V, 0, false) } else if (epi == 1) { LIN_GO_H2ONLY(K16V, 1, false) } else if (ln) { LIN_GO_H2ONLY(K16V, 2, true) } else { LIN_GO_H2ONLY(K16V, 2, false) }
+    if (epi == 0) { LIN_GO_H2ONLY(K16V, 0, false) } else if (epi == 1) { LIN_GO_H2ONLY(K16V, 1, false) }                                    \
+    else if (epi == 3) { LIN_GO_H2ONLY(K16V, 3, false) } else if (ln) { LIN_GO_H2ONLY(K16V, 2, true) } else { LIN_GO_H2ONLY(K16V, 2, false) }
     switch (K) {
         case 32: LIN_EPI(2) break;
         case 64: LIN_EPI(4) break;

@@ -73,7 +73,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_E2E_DNN) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_TRANSFORMER) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)
@@ -88,13 +88,16 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
         return fail(nullptr, NWW_ERR_INVALID, "crnn_cnn_channels must have 1..4 stages");
     if ((c.head_type == NWW_HEAD_CRNN || c.head_type == NWW_HEAD_GRU) && c.layer_dim > 512)
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "recurrent hidden size (layer_dim = %d) must be <= 512", c.layer_dim);
-    if (c.head_type == NWW_HEAD_CONFORMER && (c.conformer_n_head <= 0 || c.conformer_d_model % c.conformer_n_head))
-        return fail(nullptr, NWW_ERR_INVALID, "conformer_d_model must be divisible by conformer_n_head");
+    // the Transformer's d_model / n_head travel in the Conformer's slots (include/nww.h)
+    const bool attn_head = c.head_type == NWW_HEAD_CONFORMER || c.head_type == NWW_HEAD_TRANSFORMER;
+    const char* attn_name = c.head_type == NWW_HEAD_TRANSFORMER ? "transformer" : "conformer";
+    if (attn_head && (c.conformer_n_head <= 0 || c.conformer_d_model % c.conformer_n_head))
+        return fail(nullptr, NWW_ERR_INVALID, "%s_d_model must be divisible by %s_n_head", attn_name, attn_name);
     if (c.act_dtype != NWW_ACT_DTYPE_F32 && c.act_dtype != NWW_ACT_DTYPE_BF16 && c.act_dtype != NWW_ACT_DTYPE_F16)
         return fail(nullptr, NWW_ERR_INVALID, "act_dtype must be NWW_ACT_DTYPE_F32, NWW_ACT_DTYPE_BF16 or NWW_ACT_DTYPE_F16");
     if (c.act_dtype != NWW_ACT_DTYPE_F32 && c.head_type != NWW_HEAD_BCRESNET)
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "act_dtype = bf16 / f16 is implemented for the BcResNet head only (BASELINE config 3)");
-    if (c.head_type == NWW_HEAD_CONFORMER && !mha_head_dim_supported(c.conformer_d_model / c.conformer_n_head))
+    if (attn_head && !mha_head_dim_supported(c.conformer_d_model / c.conformer_n_head))
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "attention head_dim %d is wider than the widest compiled kernel (128)",
                     c.conformer_d_model / c.conformer_n_head);
     int ndev = 0;

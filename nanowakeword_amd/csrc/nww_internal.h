@@ -26,6 +26,9 @@
 #include "dual_x3.h"
 #include "emb_stream.h"
 
+// rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
+// architectures.py:31)
+#define NWW_PE_MAX_LEN 5000
 
 struct HostTensor {
     std::vector<int64_t> shape;

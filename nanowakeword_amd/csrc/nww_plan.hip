@@ -124,6 +124,20 @@ void nww_build_spec(nww_handle* h) {
             s.lin("model.output_proj", E, D);
             break;
         }
+        case NWW_HEAD_TRANSFORMER: {              // TransformerModel (architectures.py:164-206); d_model / n_head in the conformer_* slots
+            const int D = c.conformer_d_model;
+            s.lin("model.input_proj", D, F);
+            s.add("model.pos_encoder.pe", {NWW_PE_MAX_LEN, 1, D});
+            for (int i = 0; i < nb; ++i) {
+                const std::string p = "model.transformer_encoder.layers." + std::to_string(i);
+                s.add(p + ".self_attn.in_proj_weight", {3 * D, D}); s.add(p + ".self_attn.in_proj_bias", {3 * D});
+                s.lin(p + ".self_attn.out_proj", D, D);
+                s.lin(p + ".linear1", 4 * D, D); s.lin(p + ".linear2", D, 4 * D);
+                s.ln(p + ".norm1", D); s.ln(p + ".norm2", D);
+            }
+            s.lin("model.output_proj", E, D);
+            break;
+        }
         case NWW_HEAD_E2E_DNN: {
             int cin = 1;
             const int ch[3] = {16, 32, 64};
@@ -316,10 +330,11 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
 }
 
 // Short-K Linear on the input-stationary split-operand kernel (lin_x3.hip); false -> the caller plans the general GEMM.
-// epi 0: out = y + b; 1: out = res + rscale (y + b); 2: LayerNorm(ln_w, ln_b) first when given, W = [2N][K], out = a * sigmoid(b)
+// epi 0: out = y + b; 1: out = res + rscale (y + b); 2: LayerNorm(ln_w, ln_b) first when given, W = [2N][K], out = a * sigmoid(b);
+// 3: out = rscale (y + b) + res_tab[(row % qkv_T) N ..] (a [>= qkv_T][N] table, the Transformer's positional encoding)
 bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int rows_per_clip, int N, int K, const float* W,
                 const float* bias, int epi, int res_id = 99, float rscale = 1.f, const float* ln_w = nullptr,
-                const float* ln_b = nullptr, int qkv_T = 0, int qkv_dh = 0) {
+                const float* ln_b = nullptr, int qkv_T = 0, int qkv_dh = 0, const float* res_tab = nullptr) {
     if (!nww_knobs().lin_x3 || p.h->conv_products != 6 || !lin_x3_supported(K, N, true)) return false;
     const int parts = epi == 2 ? 2 : 1;
     // under NWW_ARITH_F16X3: two binary16 terms per operand, the input rows scaled per row in the kernel (LinArgs::h2: no bound on the
@@ -338,7 +353,7 @@ bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int 
     p.add("lin_x3:" + name + (h2 ? " [f16x3]" : ""), [=](Run& r) {
         LinArgs a;
         a.x = src(r, in_id); a.ldx = K; a.out = dst(r, out_id); a.ldc = N;
-        a.res = res_id == 99 ? nullptr : src(r, res_id); a.ldres = N; a.rscale = rscale;
+        a.res = res_tab ? res_tab : res_id == 99 ? nullptr : src(r, res_id); a.ldres = N; a.rscale = rscale;
         a.ln_w = ln_w; a.ln_b = ln_b; a.packed = static_cast<const unsigned char*>(packed);
         a.M = r.B * rows_per_clip; a.N = N; a.qkv_T = qkv_T; a.qkv_dh = qkv_dh;
         a.h2 = h2 ? 1 : 0; a.w_un = w_un;
@@ -1384,6 +1399,103 @@ extern "C" int nww_finalize(nww_handle* h) {
                 }
             }
             if (!last_fused) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
+            set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
+            break;
+        }
+        case NWW_HEAD_TRANSFORMER: {              // TransformerModel: architectures.py:164-206, nn.TransformerEncoderLayer defaults (post-norm, ReLU)
+            const int D = c.conformer_d_model, NH = c.conformer_n_head;
+            const int hb = 0, t1 = 1, big = 3;              // h, attention output / time mean, qkv / hidden / time sums
+            if (T > NWW_PE_MAX_LEN) return fail(h, NWW_ERR_UNSUPPORTED, "transformer: %d time steps exceed the positional table (%d rows)", T, NWW_PE_MAX_LEN);
+            p.need(hb, (size_t)T * D); p.need(t1, (size_t)T * D);
+            const float* pe = p.W("model.pos_encoder.pe");
+            const float xs = std::sqrt((float)D);          // math.sqrt(d_model), applied in float32 as torch does
+            // x = input_proj(x) sqrt(D) + pe[t]: the scale and the positional row in the short-K Linear's epilogue (lin_x3 epilogue 3), its
+            // input rows scaled per row (no clamp of the features); else the general GEMM and one elementwise pass
+            if (!add_lin_x3(p, "input_proj*sqrt(d)+pe", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 3, 99, xs, nullptr, nullptr, T, 0, pe)) {
+                add_gemm(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
+                p.add("scale+pe:input_proj", [=](Run& r) { return launch_scale_add_pe(r.buf[hb], pe, r.B, T, D, xs, r.stream); });
+            }
+            bool mean_done = false;
+            for (int i = 0; i < nb; ++i) {
+                const std::string q = "model.transformer_encoder.layers." + std::to_string(i);
+                const bool last = i == nb - 1;
+                // ---- h <- h + self_attn(h): head-major in_proj, the attention core, out_proj + residual (as the Conformer's attention module)
+                const int mha_mfma = nww_knobs().mha_mfma;
+                const bool want_hm = mha_mfma && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
+                bool head_major = false;
+                if (add_lin_x3(p, q + (want_hm ? ".self_attn.in_proj(head-major)" : ".self_attn.in_proj"), hb, big, T, 3 * D, D, p.W(q + ".self_attn.in_proj_weight"),
+                               p.W(q + ".self_attn.in_proj_bias"), 0, 99, 1.f, nullptr, nullptr, want_hm ? T : 0, want_hm ? D / NH : 0))
+                    head_major = want_hm;
+                else
+                    add_gemm(p, q + ".self_attn.in_proj", hb, big, T, 3 * D, D, p.W(q + ".self_attn.in_proj_weight"), p.W(q + ".self_attn.in_proj_bias"), ACT_NONE);
+                if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
+                    p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0, 1); });
+                else if (mha_mfma && mha_mfma_supported(T, D, NH))
+                    p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0); });
+                else
+                    p.add("mha_core:" + q, [=](Run& r) { return launch_mha_core(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream); });
+                if (!add_lin_x3(p, q + ".self_attn.out_proj+res", t1, hb, T, D, D, p.W(q + ".self_attn.out_proj.weight"), p.W(q + ".self_attn.out_proj.bias"), 1, hb, 1.0f))
+                    add_gemm(p, q + ".self_attn.out_proj+res", t1, hb, T, D, D, p.W(q + ".self_attn.out_proj.weight"), p.W(q + ".self_attn.out_proj.bias"), ACT_NONE, nullptr, nullptr, hb, 1.0f);
+                // ---- h <- norm2(y + linear2(relu(linear1(y)))), y = norm1(h): one launch (ffn_x3 post-norm instance); the last layer's norm2 feeds
+                // only the time mean: exact per-tile sums instead of the store
+                const float *n1w = p.W(q + ".norm1.weight"), *n1b = p.W(q + ".norm1.bias"), *n2w = p.W(q + ".norm2.weight"), *n2b = p.W(q + ".norm2.bias");
+                const float *w1 = p.W(q + ".linear1.weight"), *b1 = p.W(q + ".linear1.bias"), *w2 = p.W(q + ".linear2.weight"), *b2 = p.W(q + ".linear2.bias");
+                bool fused = false;
+                if (nww_knobs().ffn_fused && p.h->f16 && p.h->conv_products == 6 && ffn_x3_post_supported(D)) {
+                    // |norm1(h)_i| <= sqrt(D) |w_i| + |b_i| whatever h holds; relu(v) <= |v|: the scales need nothing but the weights
+                    auto ln_bound = [&](const float* w, const float* b) {
+                        const auto hw = f16_fetch(p.h, w, D), hbv = f16_fetch(p.h, b, D);
+                        double bx = 0.0;
+                        for (int k = 0; k < D; ++k) bx = std::fmax(bx, std::sqrt((double)D) * std::fabs((double)hw[k]) + std::fabs((double)hbv[k]));
+                        return bx;
+                    };
+                    const double bx = ln_bound(n1w, n1b);
+                    const auto hw1 = f16_fetch(p.h, w1, (size_t)4 * D * D), hw2 = f16_fetch(p.h, w2, (size_t)4 * D * D), hb1 = f16_fetch(p.h, b1, (size_t)4 * D);
+                    const double bh = f16_layer_bound(hw1, 4 * D, D, hb1, true, hb1, hb1, false, bx);
+                    const float fx = f16_scale(bx), fw1 = f16_wscale(hw1), fh = f16_scale(bh), fw2 = f16_wscale(hw2);
+                    float mscale = 0.0f;
+                    if (last) {
+                        const double by = ln_bound(n2w, n2b);
+                        mscale = by < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(by, 1e-30)) : 0.0f;      // |LayerNorm| x scale <= 2^36
+                        if (!(mscale > 0.0f) || !std::isfinite(mscale)) mscale = 0.0f;
+                    }
+                    void* packed = nullptr;
+                    if (fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f && (!last || mscale > 0.0f) &&
+                        hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
+                        launch_ffn_x3_pack(w1, b1, w2, packed, D, p.h->own_stream, fw1, fw2, 0) == hipSuccess) {
+                        p.h->packed_weights.push_back(packed);
+                        if (last) p.need(big, (size_t)((T + 31) / 32 + 4) * ffn_x3_post_nseg(T) * 2 * D);
+                        p.add("ffn_x3:" + q + " (norm1+linear1+relu+linear2+res+norm2" + (last ? "+time sums" : "") + ", post-norm) [f16x3]", [=](Run& r) {
+                            FfnArgs a{r.buf[hb], n1w, n1b, static_cast<const unsigned char*>(packed), b2, r.B * T, 1.0f};
+                            a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2;
+                            a.ln2_w = n2w; a.ln2_b = n2b;
+                            if (last) { a.msum = r.buf[big]; a.T = T; a.m_scale = mscale; }
+                            return launch_ffn_x3_post(a, D, r.stream);
+                        });
+                        if (last) {
+                            p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
+                                return launch_ffn_x3_post_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, mscale, r.stream);
+                            });
+                            mean_done = true;
+                        }
+                        fused = true;
+                    } else if (packed) {
+                        (void)hipFree(packed);
+                    }
+                }
+                if (!fused) {
+                    p.add("layernorm:" + q + ".norm1", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n1w, n1b, r.B * T, D, ACT_NONE, r.stream); });
+                    add_gemm(p, q + ".linear1+relu", hb, big, T, 4 * D, D, w1, b1, ACT_RELU);
+                    add_gemm(p, q + ".linear2+res", big, hb, T, D, 4 * D, w2, b2, ACT_NONE, nullptr, nullptr, hb, 1.0f);
+                    if (last && D <= 256) {
+                        p.add("layernorm+mean:" + q + ".norm2 + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], n2w, n2b, r.B, T, D, r.stream); });
+                        mean_done = true;
+                    } else {
+                        p.add("layernorm:" + q + ".norm2", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n2w, n2b, r.B * T, D, ACT_NONE, r.stream); });
+                    }
+                }
+            }
+            if (!mean_done) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
             set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
             break;
         }

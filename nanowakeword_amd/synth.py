@@ -112,11 +112,27 @@ def _is_seq_bn(key: str) -> bool:
     return False
 
 
+def positional_encoding(max_len: int, d_model: int) -> np.ndarray:
+    """The Transformer head's sinusoidal table [max_len, 1, d_model] (PositionalEncoding, architectures.py:26-48), float32
+    as torch evaluates it: pe[t, 0, 2i] = sin(t div_i), pe[t, 0, 2i + 1] = cos(t div_i), div_i = exp(-2i ln(10000) / d_model)."""
+    position = np.arange(max_len, dtype=np.float32)[:, None]
+    div_term = np.exp(np.arange(0, d_model, 2, dtype=np.float32) * np.float32(-np.log(10000.0) / d_model)).astype(np.float32)
+    arg = (position * div_term).astype(np.float32)
+    pe = np.zeros((max_len, 1, d_model), np.float32)
+    pe[:, 0, 0::2] = np.sin(arg)
+    pe[:, 0, 1::2] = np.cos(arg[:, : d_model // 2])
+    return pe
+
+
 def synth_state_dict(cfg: HeadConfig, seed: int = SEED) -> "OrderedDict[str, np.ndarray]":
-    """Deterministic float32 weights for every key of param_spec(cfg)."""
+    """Deterministic float32 weights for every key of param_spec(cfg).  Buffers that are not learnt (the Transformer's
+    positional encoding) hold their real values, so that fuzz cases and goldens see realistic magnitudes."""
     sd = OrderedDict()
     for key, shape in param_spec(cfg).items():
-        sd[key] = _tensor_for(key, shape, seed)
+        if key == "model.pos_encoder.pe":
+            sd[key] = positional_encoding(shape[0], shape[2])
+        else:
+            sd[key] = _tensor_for(key, shape, seed)
     return sd
 
 

@@ -34,9 +34,11 @@ def state_dict_from_pt(path: str) -> dict:
             for k, v in sd.items() if not k.endswith("num_batches_tracked")}
 
 
-def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None, activation: str = "relu") -> HeadConfig:
+def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None, activation: str = "relu",
+                      n_head: Optional[int] = None) -> HeadConfig:
     """Model type / layer_dim / n_blocks / embedding_dim from key names and shapes.  ``input_shape`` is needed
-    when the weights do not determine it (DNN/CNN flatten sizes fix only T*F or (T//4)*(F//4))."""
+    when the weights do not determine it (DNN/CNN flatten sizes fix only T*F or (T//4)*(F//4)).  ``n_head``: the
+    Transformer's attention heads (transformer_n_head), which no weight shape records; default 4 as Model()'s."""
     keys = set(sd)
     shp = lambda k: tuple(np.shape(sd[k]))
     E = shp("classifier.0.weight")[1]
@@ -87,10 +89,17 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         nb = n_indexed(r"model\.conformer_blocks\.(\d+)\.layer_norm\.weight")
         cfg = HeadConfig("conformer", input_shape, n_blocks=nb, conformer_d_model=D, **kw)
         cfg.conformer_n_head = 4          # not recoverable from weights; Model()'s default (model.py:252)
+    elif "model.input_proj.weight" in keys and "model.pos_encoder.pe" in keys:
+        D, F = shp("model.input_proj.weight")
+        if input_shape is None:
+            raise ValueError("transformer: pass input_shape=(T, F)")
+        nb = n_indexed(r"model\.transformer_encoder\.layers\.(\d+)\.norm1\.weight")
+        # n_head is not recoverable from the weights: Model()'s default (model.py:201) unless the caller says otherwise
+        cfg = HeadConfig("transformer", input_shape, n_blocks=nb, transformer_d_model=D, transformer_n_head=n_head or 4, **kw)
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/e2e_dnn)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/e2e_dnn)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:
@@ -254,17 +263,31 @@ def state_dict_from_onnx(path_or_bytes):
         raise ValueError("no 'classifier.0' Gemm: not a reference Model export")
     act = _activation_after(g, cls[0].outputs[0])
     cfg = infer_head_config(sd, input_shape=input_shape, activation=act)
-    if cfg.model_type == "conformer":
+    if cfg.model_type in ("conformer", "transformer"):
         sm = [n for n in g.nodes if n.op_type == "Softmax"]
         qk = g.producer_of(sm[0].inputs[0]) if sm else None
         sc_node = g.producer_of(qk.inputs[0]) if qk is not None else None
         c = None
         if sc_node is not None and sc_node.op_type == "Mul":
             c = next((g.constant(t) for t in sc_node.inputs if g.constant(t) is not None), None)
-        if c is None:
-            raise ValueError("conformer: cannot find the attention scale (1/sqrt(head_dim)) in the graph")
-        dh = int(round(1.0 / float(np.asarray(c).ravel()[0]) ** 2))
-        cfg.conformer_n_head = cfg.conformer_d_model // dh
+        D = cfg.conformer_d_model if cfg.model_type == "conformer" else cfg.transformer_d_model
+        if c is not None:
+            n_head = D // int(round(1.0 / float(np.asarray(c).ravel()[0]) ** 2))
+        else:
+            # nn.TransformerEncoderLayer exports scaled_dot_product_attention with a scale computed from the shape at run time; the
+            # query then goes through Reshape(q, [batch, n_head, T, head_dim]), whose only constant entry is n_head
+            n_head = None
+            q = g.producer_of(sc_node.inputs[0]) if sc_node is not None and sc_node.op_type == "Mul" else None
+            shape = g.producer_of(q.inputs[1]) if q is not None and q.op_type == "Reshape" else None
+            if shape is not None and shape.op_type == "Concat" and len(shape.inputs) == 4:
+                h = g.constant(shape.inputs[1])
+                n_head = int(np.asarray(h).ravel()[0]) if h is not None else None
+            if not n_head:
+                raise ValueError(f"{cfg.model_type}: cannot find the attention scale (1/sqrt(head_dim)) or head count in the graph")
+        if cfg.model_type == "conformer":
+            cfg.conformer_n_head = n_head
+        else:
+            cfg.transformer_n_head = n_head
     if g.metadata.get("mode") == "e2e" and mode != "e2e":
         raise ValueError("ONNX metadata says mode=e2e but the graph has no mel front end")
     info = {"mode": mode, "clip_samples": clip_samples, "frontend": fe, "opset": g.opset, "producer": g.producer,

@@ -291,6 +291,7 @@ def main():
     make_round2_goldens(args.out)
     make_round4_goldens(args.out)
     make_round6_goldens(args.out)
+    make_transformer_goldens(args.out)
     print("done ->", args.out)
 
 
@@ -576,6 +577,102 @@ def make_round6_goldens(out_dir):
     np.savez_compressed(os.path.join(out_dir, "heads_r06.npz"), **heads)
 
 
+def transformer_cases():
+    """Transformer head cases of heads_transformer.npz (name, HeadConfig, outlier): widths 32 / 64 / 128 with 2 / 4 / 8 heads, one and two
+    layers, clips of 8, 16 (several clips per 32-row tile), 33 and 101 frames, d_model 48 (a width without fused instances)."""
+    from nanowakeword_amd.config import HeadConfig
+    tf = lambda shape, D=128, H=4, **kw: HeadConfig("transformer", shape, transformer_d_model=D, transformer_n_head=H, **kw)
+    return [
+        ("transformer_16x96", tf((16, 96)), False),
+        ("transformer_16x96_outlier", tf((16, 96)), True),
+        ("transformer_16x96_d64_h2_b2", tf((16, 96), 64, 2, n_blocks=2), False),
+        ("transformer_8x12_d32_h8_b2", tf((8, 12), 32, 8, n_blocks=2, embedding_dim=16), False),
+        ("transformer_33x64_d64_h4", tf((33, 64), 64, 4, embedding_dim=32), False),
+        ("transformer_33x64_d128_h8_b2", tf((33, 64), 128, 8, n_blocks=2), False),
+        ("transformer_33x64_d32_h2_silu", tf((33, 64), 32, 2, embedding_dim=16, activation="silu"), False),
+        ("transformer_16x96_d48_h4", tf((16, 96), 48, 4, embedding_dim=32), False),
+        ("transformer_101x64", tf((101, 64)), False),
+    ]
+
+
+def transformer_ref_model(Model, cfg, sd):
+    """The reference's own Model(model_type="transformer") with the synthetic weights loaded; its state_dict keys / shapes must equal
+    param_spec (model.py:199-210, architectures.py:164-206)."""
+    from nanowakeword_amd.config import param_spec
+    conf = {"activation_function": cfg.activation, "embedding_dim": cfg.embedding_dim,
+            "transformer_d_model": cfg.transformer_d_model, "transformer_n_head": cfg.transformer_n_head}
+    m = Model(conf, "g", input_shape=cfg.input_shape, model_type=cfg.model_type, layer_dim=cfg.layer_dim, n_blocks=cfg.n_blocks)
+    ref_keys = {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.endswith("num_batches_tracked")}
+    spec = dict(param_spec(cfg))
+    assert ref_keys == spec, (set(ref_keys) ^ set(spec), {k: (ref_keys[k], spec[k]) for k in set(ref_keys) & set(spec) if ref_keys[k] != spec[k]})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.eval()
+
+
+def transformer_features(name, cfg, outlier):
+    from nanowakeword_amd.synth import synth_features
+    feats = synth_features(4, cfg.input_shape)
+    if outlier:
+        feats[1, 5, :] *= np.float32(1e4)          # one loud frame: per-row operand scaling, no clamp
+    return feats
+
+
+def make_transformer_goldens(out_dir):
+    """Transformer head (own files: earlier fixtures stay byte-identical): logits and embeddings of the reference's Model on seeded synthetic
+    weights -> heads_transformer.npz, and a reference export (opset 17) with its probabilities -> onnx/transformer.onnx + expected_transformer.npz."""
+    install_stubs()
+    torch.set_num_threads(1)
+    from nanowakeword.modules.model import Model
+    from nanowakeword._export import onnx as ref_onnx
+    from nanowakeword_amd.config import HeadConfig, param_spec
+    from nanowakeword_amd.synth import synth_features, synth_state_dict, state_dict_checksum
+    fr = dict(np.load(os.path.join(out_dir, "frontend.npz"), allow_pickle=False))
+    db64 = fr["db64"]
+    heads, meta = {}, {}
+    for name, cfg, outlier in transformer_cases():
+        sd = synth_state_dict(cfg)
+        m = transformer_ref_model(Model, cfg, sd)
+        feats = transformer_features(name, cfg, outlier)
+        with torch.no_grad():
+            out = {"feats": feats, "logits_feat": m(torch.from_numpy(feats)).numpy(), "emb_feat": m.model(torch.from_numpy(feats)).numpy()}
+            if cfg.input_shape == (101, 64):
+                out["logits_pcm"] = m(torch.from_numpy(np.ascontiguousarray(db64.transpose(0, 2, 1)))).numpy()
+        out["sd_checksum"] = np.array(state_dict_checksum(sd))
+        out["ref_spec_json"] = np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))
+        meta[name] = cfg.to_dict()
+        for k, v in out.items():
+            heads[f"{name}/{k}"] = v
+        print("transformer", name, {k: getattr(v, "shape", v) for k, v in out.items()}, "logits", out["logits_feat"].ravel())
+    heads["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(out_dir, "heads_transformer.npz"), **heads)
+
+    # the reference's own export of a small Transformer (recipe of make_onnx_fixtures)
+    onnx_dir = os.path.join(out_dir, "onnx")
+    from torch.onnx._internal.torchscript_exporter import onnx_proto_utils
+    onnx_proto_utils._add_onnxscript_fn = lambda model_bytes, custom_opsets: model_bytes
+    orig_export = torch.onnx.export
+
+    def export_torchscript(*a, **k):
+        k.setdefault("dynamo", False)
+        return orig_export(*a, **k)
+    torch.onnx.export = export_torchscript
+    cfg = HeadConfig("transformer", (8, 12), n_blocks=2, embedding_dim=16, transformer_d_model=32, transformer_n_head=8)
+    sd = synth_state_dict(cfg)
+    m = transformer_ref_model(Model, cfg, sd)
+    ref_onnx.export_onnx_model(m, cfg.input_shape, {}, "transformer", onnx_dir)
+    path = os.path.join(onnx_dir, "transformer.onnx")
+    assert os.path.exists(path), "export of the transformer failed"
+    feats = synth_features(4, cfg.input_shape)
+    with torch.no_grad():
+        logits = m(torch.from_numpy(feats)).numpy()
+    arrays = {"transformer/feats": feats, "transformer/logits": logits.reshape(-1).astype(np.float32),
+              "transformer/probs": (1.0 / (1.0 + np.exp(-logits.astype(np.float64)))).reshape(-1).astype(np.float32),
+              "meta_json": np.array(json.dumps({"transformer": cfg.to_dict()}))}
+    np.savez_compressed(os.path.join(onnx_dir, "expected_transformer.npz"), **arrays)
+    torch.onnx.export = orig_export
+    print("onnx fixture transformer", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
+
+
 def make_wire_fixtures(path):
     """Messages produced by the reference's own encoders (remote_verifier.py:147-158) for tests/test_wire.py."""
     from nanowakeword.interpreter import remote_verifier as rv
@@ -725,6 +822,8 @@ if __name__ == "__main__":
         make_round4_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--r06-only":
         make_round6_goldens(os.path.join(REPO, "tests", "golden"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--transformer-only":
+        make_transformer_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--r02-only":
         make_round2_goldens(os.path.join(REPO, "tests", "golden"))
     else:
