@@ -43,6 +43,7 @@ extern "C" {
 #define NWW_HEAD_CONFORMER 5   /* ConformerModel          architectures.py:441-543 */
 #define NWW_HEAD_E2E_DNN 6     /* E2E_MelSpectrogram_CNN  architectures.py:820-889 */
 #define NWW_HEAD_TRANSFORMER 7 /* TransformerModel        architectures.py:164-206 */
+#define NWW_HEAD_TCN 8         /* TCNModel                architectures.py:290-367 */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1
@@ -69,7 +70,9 @@ typedef struct nww_config {
     int32_t head_type;         /* NWW_HEAD_*                                                  */
     int32_t in_rows, in_cols;  /* Model(input_shape=(in_rows, in_cols))                       */
     int32_t layer_dim, n_blocks, embedding_dim, activation;
-    int32_t n_crnn_channels;   /* crnn_cnn_channels (<= 4 stages)                             */
+    /* crnn_cnn_channels (<= 4 stages) for NWW_HEAD_CRNN; tcn_channels (1..4 levels, model.py:228) for NWW_HEAD_TCN, whose
+       tcn_kernel_size (>= 2) travels in layer_dim (TCNModel reads no layer_dim)                                        */
+    int32_t n_crnn_channels;
     int32_t crnn_channels[4];
     /* d_model / n_head of the attention encoder (Conformer, Transformer): conformer_d_model / conformer_n_head for
        NWW_HEAD_CONFORMER, transformer_d_model / transformer_n_head (model.py:200-201) for NWW_HEAD_TRANSFORMER      */

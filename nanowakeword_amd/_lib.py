@@ -163,9 +163,12 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
     c.in_rows, c.in_cols = head.input_shape
     c.layer_dim, c.n_blocks, c.embedding_dim = head.layer_dim, head.n_blocks, head.embedding_dim
     c.activation = ACT_CODE[head.activation]
-    ch = list(head.crnn_cnn_channels)
+    # the TCN's channel list travels in the CRNN's channel slots and its kernel size in layer_dim (include/nww.h)
+    ch = list(head.tcn_channels if head.model_type == "tcn" else head.crnn_cnn_channels)
+    if head.model_type == "tcn":
+        c.layer_dim = head.tcn_kernel_size
     if len(ch) > 4:
-        raise ValueError("crnn_cnn_channels supports at most 4 stages")
+        raise ValueError("tcn_channels supports at most 4 levels" if head.model_type == "tcn" else "crnn_cnn_channels supports at most 4 stages")
     c.n_crnn_channels = len(ch)
     for i, v in enumerate(ch):
         c.crnn_channels[i] = int(v)

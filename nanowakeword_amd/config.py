@@ -15,11 +15,11 @@ from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer")
+HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
-HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7}
+HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8}
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
 # rows of the Transformer's positional-encoding buffer (PositionalEncoding(max_len=5000), architectures.py:31)
 PE_MAX_LEN = 5000
@@ -65,6 +65,8 @@ class HeadConfig:
     conformer_n_head: int = 4
     transformer_d_model: int = 128     # model.py:200-201 config keys of the Transformer head
     transformer_n_head: int = 4
+    tcn_channels: List[int] = field(default_factory=lambda: [64, 64, 128])   # model.py:228-229 config keys of the TCN head
+    tcn_kernel_size: int = 3
 
     def __post_init__(self):
         self.model_type = self.model_type.lower()
@@ -78,6 +80,16 @@ class HeadConfig:
         # CRNNModel: 'gru' -> nn.GRU, anything else -> nn.LSTM (architectures.py:238-254); the reference's default
         # config value is "lstm" (model.py:214), BASELINE config 4 names the GRU - HeadConfig defaults to the latter
         self.crnn_rnn_type = "gru" if str(self.crnn_rnn_type).lower() == "gru" else "lstm"
+        self.tcn_channels = [int(v) for v in self.tcn_channels]
+        self.tcn_kernel_size = int(self.tcn_kernel_size)
+        if self.model_type == "tcn":
+            # nww_config carries at most 4 levels; kernel size 1 breaks the reference (its chomp out[:, :, :-0] is empty)
+            if not 1 <= len(self.tcn_channels) <= 4:
+                raise ValueError(f"tcn_channels must have 1..4 levels (got {len(self.tcn_channels)})")
+            if any(c <= 0 for c in self.tcn_channels):
+                raise ValueError(f"tcn_channels must be positive (got {self.tcn_channels})")
+            if self.tcn_kernel_size < 2:
+                raise ValueError(f"tcn_kernel_size must be >= 2 (got {self.tcn_kernel_size})")
 
     def to_dict(self):
         return asdict(self)
@@ -192,6 +204,16 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
             _ln(s, f"{p}.norm1", D)
             _ln(s, f"{p}.norm2", D)
         _lin(s, "model.output_proj", E, D)
+    elif mt == "tcn":                     # architectures.py:290-367 (TemporalBlock, TCNModel)
+        k, cin = cfg.tcn_kernel_size, F
+        for i, co in enumerate(cfg.tcn_channels):
+            p = f"model.tcn_blocks.{i}"
+            s[f"{p}.conv1.weight"] = (co, cin, k); s[f"{p}.conv1.bias"] = (co,)
+            s[f"{p}.conv2.weight"] = (co, co, k); s[f"{p}.conv2.bias"] = (co,)
+            if cin != co:                 # the 1x1 downsample exists only when the widths differ
+                s[f"{p}.downsample.weight"] = (co, cin, 1); s[f"{p}.downsample.bias"] = (co,)
+            cin = co
+        _lin(s, "model.fc", E, cin)
     elif mt == "e2e_dnn":                 # architectures.py:840-865 (E2E_MelSpectrogram_CNN body)
         cin = 1
         for i, c in enumerate((16, 32, 64)):
@@ -259,4 +281,11 @@ def head_macs(cfg: HeadConfig) -> int:
         # in_proj, q k^T and (softmax) v, out_proj, linear1, linear2
         per = T * 3 * D * D + 2 * T * T * D + T * D * D + 2 * T * D * 4 * D
         m += nb * per
+    elif mt == "tcn":
+        # the reference's full-sequence count: conv1, conv2 (and the downsample) at every step, then fc of the last step
+        k, cin = cfg.tcn_kernel_size, F
+        for co in cfg.tcn_channels:
+            m += T * k * cin * co + T * k * co * co + (T * cin * co if cin != co else 0)
+            cin = co
+        m += cin * E
     return int(m)

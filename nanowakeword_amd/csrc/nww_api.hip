@@ -73,7 +73,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_TRANSFORMER) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_TCN) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)
@@ -86,6 +86,13 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (c.n_mels <= 0 || c.n_mels > FE_MAX_MELS) return fail(nullptr, NWW_ERR_INVALID, "n_mels must be in 1..%d", FE_MAX_MELS);
     if (c.head_type == NWW_HEAD_CRNN && (c.n_crnn_channels < 1 || c.n_crnn_channels > 4))
         return fail(nullptr, NWW_ERR_INVALID, "crnn_cnn_channels must have 1..4 stages");
+    // the TCN's channel list travels in n_crnn_channels / crnn_channels and its kernel size in layer_dim (include/nww.h)
+    if (c.head_type == NWW_HEAD_TCN) {
+        if (c.n_crnn_channels < 1 || c.n_crnn_channels > 4) return fail(nullptr, NWW_ERR_INVALID, "tcn_channels must have 1..4 levels (got %d)", c.n_crnn_channels);
+        for (int i = 0; i < c.n_crnn_channels; ++i)
+            if (c.crnn_channels[i] <= 0) return fail(nullptr, NWW_ERR_INVALID, "tcn_channels[%d] = %d must be positive", i, c.crnn_channels[i]);
+        if (c.layer_dim < 2) return fail(nullptr, NWW_ERR_INVALID, "tcn_kernel_size must be >= 2 (got %d)", c.layer_dim);
+    }
     if ((c.head_type == NWW_HEAD_CRNN || c.head_type == NWW_HEAD_GRU) && c.layer_dim > 512)
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "recurrent hidden size (layer_dim = %d) must be <= 512", c.layer_dim);
     // the Transformer's d_model / n_head travel in the Conformer's slots (include/nww.h)

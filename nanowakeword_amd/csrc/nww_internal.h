@@ -25,6 +25,7 @@
 #include "attn_x3.h"
 #include "dual_x3.h"
 #include "emb_stream.h"
+#include "tcn_x3.h"
 
 // rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
 // architectures.py:31)

@@ -138,6 +138,20 @@ void nww_build_spec(nww_handle* h) {
             s.lin("model.output_proj", E, D);
             break;
         }
+        case NWW_HEAD_TCN: {                      // TCNModel (architectures.py:290-367); tcn_channels in crnn_channels, tcn_kernel_size in layer_dim
+            const int k = c.layer_dim;
+            int cin = F;
+            for (int i = 0; i < c.n_crnn_channels; ++i) {
+                const int co = c.crnn_channels[i];
+                const std::string p = "model.tcn_blocks." + std::to_string(i);
+                s.add(p + ".conv1.weight", {co, cin, k}); s.add(p + ".conv1.bias", {co});
+                s.add(p + ".conv2.weight", {co, co, k}); s.add(p + ".conv2.bias", {co});
+                if (cin != co) { s.add(p + ".downsample.weight", {co, cin, 1}); s.add(p + ".downsample.bias", {co}); }
+                cin = co;
+            }
+            s.lin("model.fc", E, cin);
+            break;
+        }
         case NWW_HEAD_E2E_DNN: {
             int cin = 1;
             const int ch[3] = {16, 32, 64};
@@ -1497,6 +1511,80 @@ extern "C" int nww_finalize(nww_handle* h) {
             }
             if (!mean_done) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
             set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
+            break;
+        }
+        case NWW_HEAD_TCN: {                      // TCNModel: architectures.py:290-367; the head reads tcn_out[:, :, T - 1] only
+            const int k = c.layer_dim, nl = c.n_crnn_channels;
+            const int* ch = c.crnn_channels;
+            const int last = 5;                                    // [B][ch[nl - 1]]: the last block's output at t = T - 1
+            p.need(last, (size_t)ch[nl - 1]);
+            auto key = [](int i, const char* part) { return "model.tcn_blocks." + std::to_string(i) + "." + part; };
+            // the whole stack in one launch over the last step's receptive-field cone (tcn_x3.hip), under the default arithmetic at the
+            // shapes it takes (widths multiples of 32 up to 256, the cone inside the LDS): two binary16 terms per operand, every row scaled
+            // by its own power of two - no bound on the features, no clamp
+            bool fused = false;
+            if (p.h->f16 && p.h->conv_products == 6) {
+                TcnArgs a;
+                a.T = T; a.F = F; a.L = nl; a.k = k;
+                for (int i = 0; i < nl; ++i) a.ch[i] = ch[i];
+                std::vector<void*> packs;
+                bool ok = tcn_x3_plan(a);
+                int cin = F;
+                for (int i = 0; ok && i < nl; ++i) {
+                    auto pack = [&](const char* part, int ci, int taps, TcnConv& cv) {
+                        const float* w = p.W(key(i, (std::string(part) + ".weight").c_str()));
+                        const float ws = f16_wscale(f16_fetch(p.h, w, (size_t)ch[i] * ci * taps));
+                        void* d = nullptr;
+                        if (!(ws > 0.0f) || hipMalloc(&d, tcn_x3_packed_bytes(ci, ch[i], taps)) != hipSuccess) return false;
+                        packs.push_back(d);
+                        if (launch_tcn_x3_pack(w, d, ci, ch[i], taps, ws, p.h->own_stream) != hipSuccess) return false;
+                        cv.packed = static_cast<const unsigned char*>(d);
+                        cv.bias = p.W(key(i, (std::string(part) + ".bias").c_str()));
+                        cv.w_un = 1.0f / ws;
+                        return true;
+                    };
+                    ok = pack("conv1", cin, k, a.c1[i]) && pack("conv2", ch[i], k, a.c2[i]) && (cin == ch[i] || pack("downsample", cin, 1, a.ds[i]));
+                    cin = ch[i];
+                }
+                if (ok) {
+                    for (void* d : packs) p.h->packed_weights.push_back(d);
+                    p.add("tcn_x3:" + std::to_string(nl) + " blocks, last " + std::to_string(a.S) + " steps of " + std::to_string(T) + " [f16x3]",
+                          [=](Run& r) {
+                              TcnArgs g = a;
+                              g.x = r.x; g.out = r.buf[last]; g.B = r.B;
+                              return launch_tcn_x3(g, r.stream);
+                          });
+                    fused = true;
+                } else {
+                    for (void* d : packs) (void)hipFree(d);
+                }
+            }
+            if (!fused) {
+                // every level over the whole sequence: causal im2col (taps x dilation, zero history), conv1 = GEMM + ReLU, conv2 = GEMM + ReLU
+                // + the residual (or the downsample's GEMM), then the second ReLU; the last row of each clip feeds the tail
+                const int col = 0, hid = 1, rsd = 4;
+                int in = -1, cin = F;
+                for (int i = 0; i < nl; ++i) {
+                    const int co = ch[i], dil = 1 << i, out = i % 2 == 0 ? 2 : 3;
+                    const std::string q = "model.tcn_blocks." + std::to_string(i);
+                    p.need(col, (size_t)T * k * (cin > co ? cin : co));
+                    p.add("im2col:" + q + ".conv1", [=](Run& r) { return launch_tcn_im2col(src(r, in), r.buf[col], r.B, T, cin, k, dil, r.stream); });
+                    add_gemm(p, q + ".conv1+relu", col, hid, T, co, cin * k, p.W(key(i, "conv1.weight")), p.W(key(i, "conv1.bias")), ACT_RELU);
+                    p.add("im2col:" + q + ".conv2", [=](Run& r) { return launch_tcn_im2col(r.buf[hid], r.buf[col], r.B, T, co, k, dil, r.stream); });
+                    int res = in;
+                    if (cin != co) {
+                        add_gemm(p, q + ".downsample", in, rsd, T, co, cin, p.W(key(i, "downsample.weight")), p.W(key(i, "downsample.bias")), ACT_NONE);
+                        res = rsd;
+                    }
+                    add_gemm(p, q + ".conv2+relu+res", col, out, T, co, co * k, p.W(key(i, "conv2.weight")), p.W(key(i, "conv2.bias")), ACT_RELU,
+                             nullptr, nullptr, res, 1.0f);
+                    p.add("unary:relu " + q, [=](Run& r) { return launch_unary(r.buf[out], r.buf[out], (size_t)r.B * T * co, ACT_RELU, r.stream); });
+                    in = out; cin = co;
+                }
+                const int fin = in, C = cin;
+                p.add("last_row:tcn_out[:, :, T - 1]", [=](Run& r) { return launch_tcn_last_row(r.buf[fin], r.buf[last], r.B, T, C, r.stream); });
+            }
+            set_tail(p, "fc", last, ch[nl - 1], p.W("model.fc.weight"), p.W("model.fc.bias"));
             break;
         }
     }

@@ -96,10 +96,19 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         nb = n_indexed(r"model\.transformer_encoder\.layers\.(\d+)\.norm1\.weight")
         # n_head is not recoverable from the weights: Model()'s default (model.py:201) unless the caller says otherwise
         cfg = HeadConfig("transformer", input_shape, n_blocks=nb, transformer_d_model=D, transformer_n_head=n_head or 4, **kw)
+    elif "model.tcn_blocks.0.conv1.weight" in keys:
+        if input_shape is None:
+            raise ValueError("tcn: the sequence length is not in the weights; pass input_shape=(T, F)")
+        nl = n_indexed(r"model\.tcn_blocks\.(\d+)\.conv1\.weight")
+        chans = [shp(f"model.tcn_blocks.{i}.conv1.weight")[0] for i in range(nl)]
+        _, F, k = shp("model.tcn_blocks.0.conv1.weight")
+        if input_shape[1] != F:
+            raise ValueError(f"input_shape F={input_shape[1]} but the TCN expects {F} features")
+        cfg = HeadConfig("tcn", input_shape, tcn_channels=chans, tcn_kernel_size=k, **kw)
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/e2e_dnn)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e2e_dnn)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:

@@ -32,6 +32,7 @@ def main():
         ("C5 conformer 64-mel B=2048/GPU", HeadConfig("conformer", (101, 64)), FrontendConfig(), 2048, 10),
         ("e2e_dnn 64-mel B=4096", HeadConfig("e2e_dnn", (64, 101)), FrontendConfig(), 4096, 20),
         ("gru 64-mel B=4096", HeadConfig("gru", (101, 64)), FrontendConfig(), 4096, 10),
+        ("tcn 64-mel B=4096", HeadConfig("tcn", (101, 64)), FrontendConfig(), 4096, 30),
         # the reference's other activations (model.py:81-87) at speed: each within 1.15 x of its ReLU row
         ("C2-gelu cnn 64-mel B=4096 activation=gelu", HeadConfig("cnn", (101, 64), activation="gelu"), FrontendConfig(), 4096, 30),
         ("C2-silu cnn 64-mel B=4096 activation=silu", HeadConfig("cnn", (101, 64), activation="silu"), FrontendConfig(), 4096, 30),

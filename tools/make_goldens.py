@@ -292,6 +292,7 @@ def main():
     make_round4_goldens(args.out)
     make_round6_goldens(args.out)
     make_transformer_goldens(args.out)
+    make_tcn_goldens(args.out)
     print("done ->", args.out)
 
 
@@ -671,6 +672,95 @@ def make_transformer_goldens(out_dir):
     np.savez_compressed(os.path.join(onnx_dir, "expected_transformer.npz"), **arrays)
     torch.onnx.export = orig_export
     print("onnx fixture transformer", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
+
+
+def tcn_cases():
+    """TCN head cases of heads_tcn.npz (name, HeadConfig, outlier): the reference defaults ([64, 64, 128], k = 3) at (16, 96), (101, 64)
+    and (98, 40), the configuration guide's [128, 128, 256, 256] with k = 4, two levels without a downsample, a clip shorter than the
+    kernel's reach, one loud frame, and the GELU classifier."""
+    from nanowakeword_amd.config import HeadConfig
+    return [
+        ("tcn_16x96", HeadConfig("tcn", (16, 96)), False),
+        ("tcn_101x64", HeadConfig("tcn", (101, 64)), False),
+        ("tcn_98x40", HeadConfig("tcn", (98, 40)), False),
+        ("tcn_16x96_guide", HeadConfig("tcn", (16, 96), tcn_channels=[128, 128, 256, 256], tcn_kernel_size=4), False),
+        ("tcn_33x64_nods", HeadConfig("tcn", (33, 64), tcn_channels=[64, 64]), False),
+        ("tcn_5x12", HeadConfig("tcn", (5, 12)), False),
+        ("tcn_16x96_outlier", HeadConfig("tcn", (16, 96)), True),
+        ("tcn_16x96_gelu", HeadConfig("tcn", (16, 96), activation="gelu"), False),
+    ]
+
+
+def tcn_ref_model(Model, cfg, sd):
+    """The reference's own Model(model_type="tcn") with the synthetic weights loaded; its state_dict keys / shapes must equal param_spec
+    (model.py:227-237, architectures.py:290-367)."""
+    from nanowakeword_amd.config import param_spec
+    conf = {"activation_function": cfg.activation, "embedding_dim": cfg.embedding_dim,
+            "tcn_channels": list(cfg.tcn_channels), "tcn_kernel_size": cfg.tcn_kernel_size}
+    m = Model(conf, "g", input_shape=cfg.input_shape, model_type=cfg.model_type, layer_dim=cfg.layer_dim, n_blocks=cfg.n_blocks)
+    ref_keys = {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.endswith("num_batches_tracked")}
+    spec = dict(param_spec(cfg))
+    assert ref_keys == spec, (set(ref_keys) ^ set(spec), {k: (ref_keys[k], spec[k]) for k in set(ref_keys) & set(spec) if ref_keys[k] != spec[k]})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.eval()
+
+
+def make_tcn_goldens(out_dir):
+    """TCN head (own files: earlier fixtures stay byte-identical): logits and embeddings of the reference's Model on seeded synthetic
+    weights -> heads_tcn.npz, and a reference export (opset 17) with its probabilities -> onnx/tcn.onnx + expected_tcn.npz."""
+    install_stubs()
+    torch.set_num_threads(1)
+    from nanowakeword.modules.model import Model
+    from nanowakeword._export import onnx as ref_onnx
+    from nanowakeword_amd.config import HeadConfig
+    from nanowakeword_amd.synth import synth_features, synth_state_dict, state_dict_checksum
+    fr = dict(np.load(os.path.join(out_dir, "frontend.npz"), allow_pickle=False))
+    db64 = fr["db64"]
+    heads, meta = {}, {}
+    for name, cfg, outlier in tcn_cases():
+        sd = synth_state_dict(cfg)
+        m = tcn_ref_model(Model, cfg, sd)
+        feats = synth_features(4, cfg.input_shape)
+        if outlier:
+            feats[1, 10, :] *= np.float32(1e4)     # one loud frame inside the last step's cone: per-row operand scaling, no clamp
+        with torch.no_grad():
+            out = {"feats": feats, "logits_feat": m(torch.from_numpy(feats)).numpy(), "emb_feat": m.model(torch.from_numpy(feats)).numpy()}
+            if cfg.input_shape == (101, 64):
+                out["logits_pcm"] = m(torch.from_numpy(np.ascontiguousarray(db64.transpose(0, 2, 1)))).numpy()
+        out["sd_checksum"] = np.array(state_dict_checksum(sd))
+        out["ref_spec_json"] = np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))
+        meta[name] = cfg.to_dict()
+        for k, v in out.items():
+            heads[f"{name}/{k}"] = v
+        print("tcn", name, {k: getattr(v, "shape", v) for k, v in out.items()}, "logits", out["logits_feat"].ravel())
+    heads["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(out_dir, "heads_tcn.npz"), **heads)
+
+    # the reference's own export of a small TCN (recipe of make_onnx_fixtures)
+    onnx_dir = os.path.join(out_dir, "onnx")
+    from torch.onnx._internal.torchscript_exporter import onnx_proto_utils
+    onnx_proto_utils._add_onnxscript_fn = lambda model_bytes, custom_opsets: model_bytes
+    orig_export = torch.onnx.export
+
+    def export_torchscript(*a, **k):
+        k.setdefault("dynamo", False)
+        return orig_export(*a, **k)
+    torch.onnx.export = export_torchscript
+    cfg = HeadConfig("tcn", (8, 12), embedding_dim=16, tcn_channels=[16, 32], tcn_kernel_size=3)
+    sd = synth_state_dict(cfg)
+    m = tcn_ref_model(Model, cfg, sd)
+    ref_onnx.export_onnx_model(m, cfg.input_shape, {}, "tcn", onnx_dir)
+    path = os.path.join(onnx_dir, "tcn.onnx")
+    assert os.path.exists(path), "export of the tcn failed"
+    feats = synth_features(4, cfg.input_shape)
+    with torch.no_grad():
+        logits = m(torch.from_numpy(feats)).numpy()
+    arrays = {"tcn/feats": feats, "tcn/logits": logits.reshape(-1).astype(np.float32),
+              "tcn/probs": (1.0 / (1.0 + np.exp(-logits.astype(np.float64)))).reshape(-1).astype(np.float32),
+              "meta_json": np.array(json.dumps({"tcn": cfg.to_dict()}))}
+    np.savez_compressed(os.path.join(onnx_dir, "expected_tcn.npz"), **arrays)
+    torch.onnx.export = orig_export
+    print("onnx fixture tcn", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
 
 
 def make_wire_fixtures(path):
