@@ -22,4 +22,5 @@ size_t attn_x3_packed_bytes(int D, int n_head);
 // in_w [3D][D], in_b [3D], out_w [D][D], out_b [D] float32 -> packed chunks (two binary16 terms of W x ws) and bc [D]
 hipError_t launch_attn_x3_pack(const float* in_w, const float* in_b, const float* out_w, const float* out_b, void* packed, float* bc,
                                int D, int n_head, float ws_in, float ws_out, hipStream_t s);
-hipError_t launch_attn_x3(const AttnArgs& a, int D, int n_head, hipStream_t s);
+// cus: the device's compute units (at most one clip-resident workgroup each)
+hipError_t launch_attn_x3(const AttnArgs& a, int D, int n_head, int cus, hipStream_t s);

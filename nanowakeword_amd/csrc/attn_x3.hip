@@ -593,11 +593,10 @@ hipError_t launch_attn_x3_pack(const float* in_w, const float* in_b, const float
     return hipGetLastError();
 }
 
-hipError_t launch_attn_x3(const AttnArgs& a0, int D, int n_head, hipStream_t s) {
+hipError_t launch_attn_x3(const AttnArgs& a0, int D, int n_head, int cus, hipStream_t s) {
     if (a0.B <= 0) return hipSuccess;
     if (!attn_x3_supported(a0.T, D, n_head)) return hipErrorInvalidValue;
     if (((reinterpret_cast<uintptr_t>(a0.h) | reinterpret_cast<uintptr_t>(a0.out) | reinterpret_cast<uintptr_t>(a0.bc)) & 15) != 0) return hipErrorInvalidValue;
-    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
     const dim3 grid(a0.B < cus ? a0.B : cus);
     AttnArgs a = a0;
     a.stagger = a0.B >= 4 * cus ? 2000 : 0;                    // (fewer clips per workgroup: the delay would not pay back)

@@ -142,14 +142,14 @@ hipError_t launch_dwconv1d_bn_swish(const float* x, const float* w /*[D][K]*/, c
 hipError_t launch_mha_core(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s);
 // the same on v_mfma_f32_32x32x2_f32 (mha_mfma.hip): T <= 128, head dim a multiple of 4 with a compiled instance
 bool mha_mfma_supported(int T, int D, int n_head);
-// head_major != 0: qkv is [q|k|v][B][n_head][T][D / n_head] (lin_x3's qkv store) instead of [B][T][3 D]
-hipError_t launch_mha_mfma(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s, int head_major = 0);
+// head_major != 0: qkv is [q|k|v][B][n_head][T][D / n_head] (lin_x3's qkv store) instead of [B][T][3 D]; cus: the device's compute units
+hipError_t launch_mha_mfma(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0);
 bool mha_head_dim_supported(int head_dim);
 // the same from two binary16 terms per operand on v_mfma_f32_32x32x16_f16 (mha_h2.hip; NWW_ARITH_F16X3): K, V scaled by the
 // unit's own maxima, every query row by its own
 bool mha_h2_supported(int T, int D, int n_head);
 // exact_sub = 1: the softmax subtracts the maximum from the raw scores before scaling them (mha_h2.hip XSUB; the Transformer head)
-hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s, int head_major = 0, int exact_sub = 0);
+hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0, int exact_sub = 0);
 // [B][C][H][W] -> [B][W][C*H]  (CRNN: sequence over W, features C*H; architectures.py:272-276)
 hipError_t launch_crnn_seq(const float* in, float* out, int B, int C, int H, int W, hipStream_t s);
 // GRU recurrence for one direction. xg [B][T][3H] = x W_ih^T + b_ih (precomputed by GEMM).
@@ -176,6 +176,7 @@ struct GruArgs {
     int fin = 0; float x_scale = 1.0f, x_clamp = 0.0f, wi_scale = 1.0f;
     // rnn_stream (128 < H <= 256, products = 3): W_hh x w_scale as two binary16 terms in MFMA fragment order (launch_rnn_stream_pack), read every step
     const void* w_packed = nullptr;
+    int cu_count = 256;    // the device's compute units (rnn_stream: 16-clip tiles up to B = 16 x cu_count, 32-clip tiles beyond)
     int dbg = 0;           // NWW_ABLATION builds only (rnn_stream: phase-skipping for timing; results are garbage)
 };
 size_t rnn_wide_weight_bytes(int gates, int H);

@@ -316,13 +316,12 @@ bool mha_h2_supported(int T, int D, int n_head) {
     }
 }
 
-hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s, int head_major, int exact_sub) {
+hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major, int exact_sub) {
     if (!mha_h2_supported(T, D, n_head)) return hipErrorInvalidValue;
     const int dh = D / n_head, units = B * n_head;
     if (units <= 0) return hipSuccess;
     const float scale = 1.0f / sqrtf((float)dh);
     const size_t lds = mha_h2_lds(dh);
-    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
     const int slots = (dh > 40 ? 1 : 2) * cus;                 // two workgroups per CU (one's staging under the other's MFMAs) where the registers allow
     const dim3 grid(units < slots ? units : slots);
 #define MHA_GO(DHV)                                                                                                \

@@ -185,14 +185,13 @@ bool mha_mfma_supported(int T, int D, int n_head) {
     }
 }
 
-hipError_t launch_mha_mfma(const float* qkv, float* out, int B, int T, int D, int n_head, hipStream_t s, int head_major) {
+hipError_t launch_mha_mfma(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major) {
     if (!mha_mfma_supported(T, D, n_head)) return hipErrorInvalidValue;
     const int dh = D / n_head, units = B * n_head;
     if (units <= 0) return hipSuccess;
     const float scale = 1.0f / sqrtf((float)dh);
     const int uw = mha_mfma_units(dh);
     const size_t lds = mha_mfma_lds(dh, uw);
-    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
     const int groups = (units + uw - 1) / uw;
     const int slots = 2 * cus;                                 // two workgroups per CU: one's row fetch under the other's MFMAs
     const dim3 grid(groups < slots ? groups : slots);

@@ -27,7 +27,6 @@ static thread_local std::string g_create_err;   // nww_create errors: per thread
 
 std::string& nww_create_err() { return g_create_err; }
 
-#undef fail
 int nww_fail(nww_handle* h, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -39,16 +38,6 @@ int nww_fail(nww_handle* h, int code, const char* fmt, ...) {
 }
 using Shape = std::vector<int64_t>;
 static size_t numel(const Shape& s) { size_t n = 1; for (auto v : s) n *= (size_t)v; return n; }
-#define fail nww_fail
-#define prof_mark nww_prof_mark
-#define prof_begin nww_prof_begin
-#define ensure_ws nww_ensure_ws
-#define run_head nww_run_head
-#define check_run nww_check_run
-#define frontend_dev nww_frontend_on_dev
-#define forward_pcm_dev nww_forward_pcm_on_dev
-#define h2d_small nww_h2d_small
-#define copy_out nww_copy_out
 
 // ------------------------------------------------------------------------------------------ create / load
 // The default is the two-term binary16 form (round 4): float32-grade against float64 in every head (tests/test_gpu_parity.py::
@@ -295,7 +284,7 @@ extern "C" int nww_reserve(nww_handle* h, int32_t B, int32_t N) {
     if (!h || B <= 0 || N < 0) return fail(h, NWW_ERR_INVALID, "nww_reserve: bad arguments");
     if (!h->finalized) return fail(h, NWW_ERR_STATE, "nww_reserve before nww_finalize");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return ensure_ws(h, B, N);
+    return nww_ensure_ws(h, B, N);
 }
 
 int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, unsigned int* done_flag,
@@ -331,16 +320,16 @@ int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float*
     }
     int id = 1;
     for (auto& st : h->plan) {
-        prof_mark(h, s, id++);
+        nww_prof_mark(h, s, id++);
         hipError_t e = st.fn(r);
         if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch '%s' failed: %s", st.name.c_str(), hipGetErrorString(e));
     }
     if (d_probs && r.need_sigmoid) {
-        prof_mark(h, s, id);
+        nww_prof_mark(h, s, id);
         hipError_t e = launch_unary(r.logits, d_probs, (size_t)B, ACT_SIGMOID, s);
         if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'sigmoid' failed: %s", hipGetErrorString(e));
     }
-    prof_mark(h, s, -1);
+    nww_prof_mark(h, s, -1);
     if (done_armed) *done_armed = r.done_armed;
     return NWW_OK;
 }
@@ -365,11 +354,11 @@ int nww_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float
 
 extern "C" int nww_frontend_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, int32_t N, float* d_logmel,
                                 int32_t frames_major, void* stream) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!d_pcm || !d_logmel) return fail(h, NWW_ERR_INVALID, "null device pointer");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return frontend_dev(h, d_pcm, B, N, d_logmel, nullptr, frames_major, stream ? (hipStream_t)stream : h->own_stream, nullptr);
+    return nww_frontend_on_dev(h, d_pcm, B, N, d_logmel, nullptr, frames_major, stream ? (hipStream_t)stream : h->own_stream, nullptr);
 }
 
 int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_logits, float* d_probs, hipStream_t s,
@@ -381,47 +370,47 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
     if (rows != c.in_rows || cols != c.in_cols)
         return fail(h, NWW_ERR_SHAPE, "frontend yields (%d,%d) features for %d samples but the head was built for input_shape=(%d,%d)",
                     rows, cols, N, c.in_rows, c.in_cols);
-    int rc = ensure_ws(h, B, N);
+    int rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
-    prof_begin(h);
-    prof_mark(h, s, 0);
+    nww_prof_begin(h);
+    nww_prof_mark(h, s, 0);
     const bool fm = !c.mel_major_features || h->e2e_transposed;
-    rc = frontend_dev(h, d_pcm, B, N, h->d_logmel, nullptr, fm ? 1 : 0, s, nullptr, row_stride);
+    rc = nww_frontend_on_dev(h, d_pcm, B, N, h->d_logmel, nullptr, fm ? 1 : 0, s, nullptr, row_stride);
     if (rc) return rc;
-    return run_head(h, h->d_logmel, B, d_logits, d_probs, s, done_flag, done_seq, done_armed, fm && c.mel_major_features);
+    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, done_flag, done_seq, done_armed, fm && c.mel_major_features);
 }
 
 extern "C" int nww_forward_pcm_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, int32_t N, float* d_logits,
                                    float* d_probs, void* stream) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!d_pcm) return fail(h, NWW_ERR_INVALID, "null device pointer");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return forward_pcm_dev(h, d_pcm, B, N, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
+    return nww_forward_pcm_on_dev(h, d_pcm, B, N, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
 }
 
 extern "C" int nww_forward_features_dev(nww_handle* h, const float* d_feats, int32_t B, float* d_logits, float* d_probs,
                                         void* stream) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!d_feats) return fail(h, NWW_ERR_INVALID, "null device pointer");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = ensure_ws(h, B, 0);
+    rc = nww_ensure_ws(h, B, 0);
     if (rc) return rc;
-    prof_begin(h);
-    return run_head(h, d_feats, B, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
+    nww_prof_begin(h);
+    return nww_run_head(h, d_feats, B, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
 }
 
 // ---- host-pointer entry points
 extern "C" int nww_frontend_ex(nww_handle* h, const int16_t* pcm, int32_t B, int32_t N, float* logmel_out,
                                float* melpower_out, int32_t* frames_out) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!pcm) return fail(h, NWW_ERR_INVALID, "Input audio must be a non-null int16 array");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int T = fe_num_frames(h->fe, N);
     if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
-    rc = ensure_ws(h, B, N);
+    rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
     const size_t n_out = (size_t)B * T * h->cfg.n_mels;
@@ -431,7 +420,7 @@ extern "C" int nww_frontend_ex(nww_handle* h, const int16_t* pcm, int32_t B, int
     } mel;
     if (melpower_out) HIP_TRY(h, hipMalloc(&mel.p, n_out * sizeof(float)));
     HIP_TRY(h, hipMemcpyAsync(h->d_pcm, pcm, (size_t)B * N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    rc = frontend_dev(h, h->d_pcm, B, N, h->d_logmel, mel.p, 0, s, frames_out);
+    rc = nww_frontend_on_dev(h, h->d_pcm, B, N, h->d_logmel, mel.p, 0, s, frames_out);
     if (rc) return rc;
     if (logmel_out) HIP_TRY(h, hipMemcpyAsync(logmel_out, h->d_logmel, n_out * sizeof(float), hipMemcpyDeviceToHost, s));
     if (melpower_out) HIP_TRY(h, hipMemcpyAsync(melpower_out, mel.p, n_out * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -524,11 +513,11 @@ int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, 
 }
 
 extern "C" int nww_forward_pcm(nww_handle* h, const int16_t* pcm, int32_t B, int32_t N, float* logits, float* probs) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!pcm) return fail(h, NWW_ERR_INVALID, "Input audio must be a non-null int16 array");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = ensure_ws(h, B, N);
+    rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
     {
@@ -542,7 +531,7 @@ extern "C" int nww_forward_pcm(nww_handle* h, const int16_t* pcm, int32_t B, int
             if (++h->done_seq == 0) ++h->done_seq;                   // 0 is the word's initial value, never a sequence number
             const unsigned int seq = h->done_seq;
             bool armed = false;
-            rc = forward_pcm_dev(h, static_cast<const int16_t*>(d_in), B, N, zl, zp, s, 0, flag, seq, &armed);
+            rc = nww_forward_pcm_on_dev(h, static_cast<const int16_t*>(d_in), B, N, zl, zp, s, 0, flag, seq, &armed);
             if (rc) return rc;
             rc = zero_copy_wait(h, s, armed, reinterpret_cast<volatile unsigned int*>(h->pin_out + PIN_BYTES - 16), seq);
             if (rc) return rc;
@@ -551,19 +540,19 @@ extern "C" int nww_forward_pcm(nww_handle* h, const int16_t* pcm, int32_t B, int
             return NWW_OK;
         }
     }
-    rc = h2d_small(h, h->d_pcm, pcm, (size_t)B * N * sizeof(int16_t), s);
+    rc = nww_h2d_small(h, h->d_pcm, pcm, (size_t)B * N * sizeof(int16_t), s);
     if (rc) return rc;
-    rc = forward_pcm_dev(h, h->d_pcm, B, N, h->d_logits, h->d_probs, s);
+    rc = nww_forward_pcm_on_dev(h, h->d_pcm, B, N, h->d_logits, h->d_probs, s);
     if (rc) return rc;
-    return copy_out(h, B, logits, probs, nullptr, s);
+    return nww_copy_out(h, B, logits, probs, nullptr, s);
 }
 
 extern "C" int nww_forward_features_ex(nww_handle* h, const float* feats, int32_t B, float* logits, float* probs, float* emb) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!feats) return fail(h, NWW_ERR_INVALID, "null feature pointer");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = ensure_ws(h, B, 0);
+    rc = nww_ensure_ws(h, B, 0);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
     if (!emb) {
@@ -573,12 +562,12 @@ extern "C" int nww_forward_features_ex(nww_handle* h, const float* feats, int32_
             if (h->pin_in_busy) { HIP_TRY(h, hipStreamSynchronize(s)); h->pin_in_busy = false; }
             std::memcpy(h->pin_in, feats, bytes);
             h->pin_in_busy = true;
-            prof_begin(h);
+            nww_prof_begin(h);
             unsigned int* flag = reinterpret_cast<unsigned int*>(zl) + (PIN_BYTES / sizeof(float) - 4);
             if (++h->done_seq == 0) ++h->done_seq;
             const unsigned int seq = h->done_seq;
             bool armed = false;
-            rc = run_head(h, static_cast<const float*>(d_in), B, zl, zp, s, flag, seq, &armed);
+            rc = nww_run_head(h, static_cast<const float*>(d_in), B, zl, zp, s, flag, seq, &armed);
             if (rc) return rc;
             rc = zero_copy_wait(h, s, armed, reinterpret_cast<volatile unsigned int*>(h->pin_out + PIN_BYTES - 16), seq);
             if (rc) return rc;
@@ -587,12 +576,12 @@ extern "C" int nww_forward_features_ex(nww_handle* h, const float* feats, int32_
             return NWW_OK;
         }
     }
-    rc = h2d_small(h, h->d_feats, feats, (size_t)B * h->cfg.in_rows * h->cfg.in_cols * sizeof(float), s);
+    rc = nww_h2d_small(h, h->d_feats, feats, (size_t)B * h->cfg.in_rows * h->cfg.in_cols * sizeof(float), s);
     if (rc) return rc;
-    prof_begin(h);
-    rc = run_head(h, h->d_feats, B, h->d_logits, h->d_probs, s);
+    nww_prof_begin(h);
+    rc = nww_run_head(h, h->d_feats, B, h->d_logits, h->d_probs, s);
     if (rc) return rc;
-    return copy_out(h, B, logits, probs, emb, s);
+    return nww_copy_out(h, B, logits, probs, emb, s);
 }
 
 extern "C" int nww_forward_features(nww_handle* h, const float* feats, int32_t B, float* logits, float* probs) {

@@ -1,14 +1,5 @@
 // nww_comm.hip - the path's only exchange: RCCL all-gather of the per-clip logits (nww_comm_*, nww_forward_pcm_gather_dev).
 #include "nww_internal.h"
-#define prof_mark nww_prof_mark
-#define prof_begin nww_prof_begin
-#define ensure_ws nww_ensure_ws
-#define run_head nww_run_head
-#define check_run nww_check_run
-#define frontend_dev nww_frontend_on_dev
-#define forward_pcm_dev nww_forward_pcm_on_dev
-#define h2d_small nww_h2d_small
-#define copy_out nww_copy_out
 #include <dlfcn.h>
 
 // ------------------------------------------------------------------------------------------ RCCL (multi-GPU gather)
@@ -151,14 +142,14 @@ extern "C" int nww_all_gather_logits(nww_handle* h, const float* d_send, float* 
 // One sharded step without a host hop: this rank's B clips -> its B logits (written at d_all_logits + rank * B), then
 // the all-gather into d_all_logits [world][B], both on `stream`.
 extern "C" int nww_forward_pcm_gather_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, int32_t N, float* d_all_logits, void* stream) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!d_pcm || !d_all_logits) return fail(h, NWW_ERR_INVALID, "null device pointer");
     if (!h->comm) return fail(h, NWW_ERR_STATE, "no communicator (nww_comm_init)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
     float* mine = d_all_logits + (size_t)h->comm_rank * B;
-    rc = forward_pcm_dev(h, d_pcm, B, N, mine, nullptr, s);
+    rc = nww_forward_pcm_on_dev(h, d_pcm, B, N, mine, nullptr, s);
     if (rc) return rc;
     return all_gather_dev(h, mine, d_all_logits, B, s);       // in place: send buffer = this rank's slot of the receive buffer
 }
@@ -171,7 +162,7 @@ extern "C" int nww_forward_pcm_gather_dev(nww_handle* h, const int16_t* d_pcm, i
 // The gathered vector of a step is valid on `stream` after nww_gather_fence(h, stream).  Mixing this with the synchronous
 // nww_forward_pcm_gather_dev on one handle needs a nww_gather_fence in between (the synchronous form does not look at the side stream).
 extern "C" int nww_forward_pcm_gather_async_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, int32_t N, float* d_all_logits, void* stream) {
-    int rc = check_run(h, B);
+    int rc = nww_check_run(h, B);
     if (rc) return rc;
     if (!d_pcm || !d_all_logits) return fail(h, NWW_ERR_INVALID, "null device pointer");
     if (!h->comm || !h->comm_stream) return fail(h, NWW_ERR_STATE, "no communicator (nww_comm_init)");
@@ -185,7 +176,7 @@ extern "C" int nww_forward_pcm_gather_async_dev(nww_handle* h, const int16_t* d_
     h->gather_buf[p] = d_all_logits;
     HIP_TRY(h, hipEventRecord(h->ev_start[p], s));
     float* mine = d_all_logits + (size_t)h->comm_rank * B;
-    rc = forward_pcm_dev(h, d_pcm, B, N, mine, nullptr, s);
+    rc = nww_forward_pcm_on_dev(h, d_pcm, B, N, mine, nullptr, s);
     if (rc) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_ready[p], s));
     HIP_TRY(h, hipStreamWaitEvent(h->comm_stream, h->ev_ready[p], 0));

@@ -1,14 +1,5 @@
 // nww_emb.hip - embedding-mode preprocessor state on the device (nww_emb_*; kernels in emb_stream.hip).
 #include "nww_internal.h"
-#define prof_mark nww_prof_mark
-#define prof_begin nww_prof_begin
-#define ensure_ws nww_ensure_ws
-#define run_head nww_run_head
-#define check_run nww_check_run
-#define frontend_dev nww_frontend_on_dev
-#define forward_pcm_dev nww_forward_pcm_on_dev
-#define h2d_small nww_h2d_small
-#define copy_out nww_copy_out
 
 // ------------------------------------------------------------------------------------------ embedding-mode state
 // C-ABI over emb_stream.hip.  Host-pointer arguments are staged through e->stage; device-pointer arguments are used
@@ -39,7 +30,7 @@ extern "C" int nww_emb_close(nww_handle* h) {
 }
 
 extern "C" int nww_emb_open(nww_handle* h, int32_t n_streams, int32_t mel_bins, int32_t emb_dim, int32_t mel_cap, int32_t feat_cap) {
-    int rc = check_run(h, n_streams);
+    int rc = nww_check_run(h, n_streams);
     if (rc) return rc;
     if (mel_bins <= 0 || emb_dim <= 0 || mel_cap < EMB_WINDOW || feat_cap <= 0)
         return fail(h, NWW_ERR_INVALID, "nww_emb_open: mel_bins, emb_dim, feat_cap must be positive and mel_cap >= 76");
@@ -55,7 +46,7 @@ extern "C" int nww_emb_open(nww_handle* h, int32_t n_streams, int32_t mel_bins, 
     if (er == hipSuccess) er = emb_reset(e, h->own_stream);
     if (er != hipSuccess) { nww_emb_close(h); return fail(h, NWW_ERR_HIP, "nww_emb_open: %s", hipGetErrorString(er)); }
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
-    return ensure_ws(h, n_streams, 0);
+    return nww_ensure_ws(h, n_streams, 0);
 }
 
 extern "C" int nww_emb_reset(nww_handle* h) {
@@ -146,14 +137,14 @@ extern "C" int nww_emb_forward(nww_handle* h, float* logits, float* probs) {
     EmbState* e = h->emb;
     const int T = h->cfg.in_rows;
     if (e->feat_len < T) return fail(h, NWW_ERR_STATE, "the feature buffer holds %d rows, the head needs %d", e->feat_len, T);
-    int rc = ensure_ws(h, e->S, 0);
+    int rc = nww_ensure_ws(h, e->S, 0);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
     HIP_TRY(h, emb_tail_features(e, T, h->d_feats, s));
-    prof_begin(h);
-    rc = run_head(h, h->d_feats, e->S, h->d_logits, probs ? h->d_probs : nullptr, s);
+    nww_prof_begin(h);
+    rc = nww_run_head(h, h->d_feats, e->S, h->d_logits, probs ? h->d_probs : nullptr, s);
     if (rc) return rc;
-    return copy_out(h, e->S, logits, probs, nullptr, s);
+    return nww_copy_out(h, e->S, logits, probs, nullptr, s);
 }
 
 // batch path (AudioFeatures._get_embeddings_batch, :231-295): mel [B][F][bins] -> windows [B][(F-76)/8+1][76][bins]

@@ -1,15 +1,6 @@
 // nww_plan.hip - Model.state_dict() spec per head and the launch plans nww_finalize builds from the loaded weights.
 #include "nww_internal.h"
 #include "bc_chain.h"
-#define prof_mark nww_prof_mark
-#define prof_begin nww_prof_begin
-#define ensure_ws nww_ensure_ws
-#define run_head nww_run_head
-#define check_run nww_check_run
-#define frontend_dev nww_frontend_on_dev
-#define forward_pcm_dev nww_forward_pcm_on_dev
-#define h2d_small nww_h2d_small
-#define copy_out nww_copy_out
 
 const Knobs& nww_knobs() {
     static const Knobs k = [] {
@@ -186,8 +177,8 @@ struct PlanCtx {
     void pop_last() { if (!h->plan.empty()) h->plan.pop_back(); }        // a step just planned is re-planned in another form
     // the head's last Linear (-> embedding), deferred so that it can be fused with the classifier into one launch
     std::string tail_name; int tail_in = 99, tail_K = 0; const float *tail_W = nullptr, *tail_b = nullptr;
-    // DNN: LayerNorm1 + blocks run inside the tail's launch (TailArgs::ln0_w)
-    bool dnn_body = false; const float *dnn_ln0_w = nullptr, *dnn_ln0_b = nullptr; int dnn_n_mid = 0; const float* dnn_mid[4][4] = {};
+    // DNN: LayerNorm1 + blocks run inside the tail's launch (TailArgs::ln0_w); mid[i]: block i's fcn_layer weight, bias, layer_norm weight, bias
+    struct DnnBody { bool on = false; const float *ln0_w = nullptr, *ln0_b = nullptr; int n_mid = 0; const float* mid[4][4] = {}; } dnn;
 };
 
 // ---- two-term binary16 arithmetic (NWW_ARITH_F16X3): plan-time bounds and power-of-two scales
@@ -226,6 +217,18 @@ double f16_layer_bound(const std::vector<float>& w, int Cout, int K, const std::
         worst = std::fmax(worst, t);
     }
     return worst;
+}
+// |LayerNorm(x)_k| <= sqrt(D) |w_k| + |b_k| whatever x holds: a bound on a LayerNorm's output from its weights alone
+double f16_ln_bound(nww_handle* h, const float* w, const float* b, int D) {
+    const auto hw = f16_fetch(h, w, D), hb = f16_fetch(h, b, D);
+    double bound = 0.0;
+    for (int k = 0; k < D; ++k) bound = std::fmax(bound, std::sqrt((double)D) * std::fabs((double)hw[k]) + std::fabs((double)hb[k]));
+    return bound;
+}
+// scale of the LayerNorm'd rows that the ffn_x3 epilogues sum exactly over time: |LayerNorm| x scale <= 2^36; 0 = no usable bound
+float f16_mean_scale(double bound) {
+    const float s = bound < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(bound, 1e-30)) : 0.0f;
+    return s > 0.0f && std::isfinite(s) ? s : 0.0f;
 }
 
 // A tensor's plan-time range: a BOUND on its magnitude (what the scale is derived from) and a rough TYPICAL magnitude.  Two binary16
@@ -374,6 +377,13 @@ bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int 
         return launch_lin_x3(a, K, epi, ln_w != nullptr, r.stream);
     });
     return true;
+}
+
+// A Linear (+ residual res_id times rscale) on the short-K kernel where it applies, else on the general GEMM with the same operands
+void add_linear(PlanCtx& p, const std::string& name, int in_id, int out_id, int rows_per_clip, int N, int K, const float* W,
+                const float* bias, int res_id = 99, float rscale = 1.f) {
+    if (!add_lin_x3(p, name, in_id, out_id, rows_per_clip, N, K, W, bias, res_id == 99 ? 0 : 1, res_id, rscale))
+        add_gemm(p, name, in_id, out_id, rows_per_clip, N, K, W, bias, ACT_NONE, nullptr, nullptr, res_id, rscale);
 }
 
 void set_tail(PlanCtx& p, const std::string& name, int in_id, int K, const float* W, const float* b) {
@@ -631,8 +641,7 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
                 // (the forward direction's input projection runs inside its recurrence: GruArgs::fin)
             } else {
                 // short-K input projections (the GRU head's 64 mel bins) on the input-stationary kernel; the rest on the general GEMM
-                if (!add_lin_x3(p, prefix + ".ih" + sfx, cur_in, xg_id, T, G * H, cur_I, wih, bih, 0))
-                    add_gemm(p, prefix + ".ih" + sfx, cur_in, xg_id, T, G * H, cur_I, wih, bih, ACT_NONE);
+                add_linear(p, prefix + ".ih" + sfx, cur_in, xg_id, T, G * H, cur_I, wih, bih);
             }
             if (fold && dir == 0) continue;                  // the forward recurrence is launched after the reverse projection
             const int in_T = T;
@@ -678,7 +687,7 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
                 a.xg = r.buf[xg_id]; a.w_hh = whh_f; a.b_hh = bhh_f;
                 a.seq_out = last ? nullptr : r.buf[seq_out]; a.ld_seq = 2 * H;
                 a.last_out = last ? r.buf[last_id] : nullptr; a.ld_last = 2 * H;
-                a.B = r.B; a.T = in_T; a.H = H; a.ldw = ldw;
+                a.B = r.B; a.T = in_T; a.H = H; a.ldw = ldw; a.cu_count = r.cu_count;
                 if (fold) {
                     a.col_off = 0; a.reverse = 0; a.steps = in_T;
                     a.xg2 = r.buf[xg_id] + (size_t)r.B * in_T * G * H; a.xg2_bstride = (size_t)G * H; a.b_hh2 = bhh; a.col_off2 = H;
@@ -693,17 +702,9 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
     }
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------------ finalize
-extern "C" int nww_finalize(nww_handle* h) {
-    if (!h) return NWW_ERR_INVALID;
-    if (h->finalized) return NWW_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const nww_config& c = h->cfg;
-    for (const auto& k : h->keys)
-        if (!h->tensors[k].loaded) return fail(h, NWW_ERR_MISSING, "Missing key(s) in state_dict: '%s'", k.c_str());
-    // ---- fold every BatchNorm (eval): alpha = w/sqrt(var+eps), beta = b - mean*alpha (PyTorch CPU kernel form)
+// ------------------------------------------------------------------------------------------ weights and frontend tables
+// every BatchNorm folded (eval): alpha = w/sqrt(var+eps), beta = b - mean*alpha (PyTorch CPU kernel form)
+void fold_batchnorms(nww_handle* h) {
     std::vector<std::string> bn_prefixes;
     for (const auto& k : h->keys) {
         const std::string sfx = ".running_var";
@@ -725,21 +726,26 @@ extern "C" int nww_finalize(nww_handle* h) {
         h->tensors[p + ".alpha"] = al;
         h->tensors[p + ".beta"] = be;
     }
-    // ---- depthwise 3x3 weights tap-major [9][C] for the channels-last kernels (BcResNet)
-    if (c.head_type == NWW_HEAD_BCRESNET)
-        for (int i = 1; i <= 3; ++i) {
-            const std::string k = "model.block" + std::to_string(i) + ".depthwise.weight";
-            const HostTensor& w = h->tensors[k];
-            const int C = (int)w.shape[0];
-            HostTensor wt;
-            wt.shape = {9, C};
-            wt.data.resize((size_t)9 * C);
-            for (int ch = 0; ch < C; ++ch)
-                for (int tap = 0; tap < 9; ++tap) wt.data[(size_t)tap * C + ch] = w.data[(size_t)ch * 9 + tap];
-            wt.loaded = true;
-            h->tensors[k + "_t"] = wt;
-        }
-    // ---- weight arena (each tensor 16-byte aligned)
+}
+
+// BcResNet: depthwise 3x3 weights tap-major [9][C] for the channels-last kernels
+void transpose_depthwise(nww_handle* h) {
+    for (int i = 1; i <= 3; ++i) {
+        const std::string k = "model.block" + std::to_string(i) + ".depthwise.weight";
+        const HostTensor& w = h->tensors[k];
+        const int C = (int)w.shape[0];
+        HostTensor wt;
+        wt.shape = {9, C};
+        wt.data.resize((size_t)9 * C);
+        for (int ch = 0; ch < C; ++ch)
+            for (int tap = 0; tap < 9; ++tap) wt.data[(size_t)tap * C + ch] = w.data[(size_t)ch * 9 + tap];
+        wt.loaded = true;
+        h->tensors[k + "_t"] = wt;
+    }
+}
+
+// every loaded tensor but the frontend's in one device arena, each 16-byte aligned
+int upload_weight_arena(nww_handle* h) {
     size_t total = 0;
     for (auto& kv : h->tensors) {
         if (!kv.second.loaded || kv.first.rfind("frontend.", 0) == 0) continue;
@@ -752,853 +758,848 @@ extern "C" int nww_finalize(nww_handle* h) {
         HIP_TRY(h, hipMemcpy(h->d_weights + kv.second.dev_off, kv.second.data.data(), kv.second.data.size() * sizeof(float),
                              hipMemcpyHostToDevice));
     }
-    // ---- frontend tables
-    {
-        std::vector<float> win, fb;
-        auto wi = h->tensors.find("frontend.window");
-        if (wi != h->tensors.end() && wi->second.loaded) win = wi->second.data; else fe_default_window(h->fe.win_length, win);
-        auto fi = h->tensors.find("frontend.mel_fb");
-        if (fi != h->tensors.end() && fi->second.loaded) fb = fi->second.data; else fe_default_melfb(h->fe, fb);
-        FeTables tb;
-        const std::string e = fe_build_tables(h->fe, win.data(), fb.data(), &tb);
-        if (!e.empty()) return fail(h, NWW_ERR_INVALID, "frontend tables: %s", e.c_str());
-        const size_t tbytes = (sizeof(FeTables) + 15) & ~(size_t)15;
-        HIP_TRY(h, hipMalloc(&h->d_tables, tbytes));
-        HIP_TRY(h, hipMemset(h->d_tables, 0, tbytes));
-        HIP_TRY(h, hipMemcpy(h->d_tables, &tb, sizeof(FeTables), hipMemcpyHostToDevice));
-        h->mel_max_taps = 0;
-        for (int j = 0; j < h->fe.n_mels; ++j) h->mel_max_taps = tb.mel_cnt[j] > h->mel_max_taps ? tb.mel_cnt[j] : h->mel_max_taps;
-        std::vector<Fe2MelPlan> plan(1);
-        const std::string e2 = fe2_build_mel_plan(h->fe, fb.data(), plan.data());
-        if (!e2.empty()) return fail(h, NWW_ERR_INVALID, "frontend mel plan: %s", e2.c_str());
-        HIP_TRY(h, hipMalloc(&h->d_melplan, sizeof(Fe2MelPlan)));
-        HIP_TRY(h, hipMemcpy(h->d_melplan, plan.data(), sizeof(Fe2MelPlan), hipMemcpyHostToDevice));
-        // (the DFT on the matrix pipe - frontend3 - was built in round 5, parity-green and slower: tools/ubench/fe3/)
+    return NWW_OK;
+}
+
+int build_frontend_tables(nww_handle* h) {
+    std::vector<float> win, fb;
+    auto wi = h->tensors.find("frontend.window");
+    if (wi != h->tensors.end() && wi->second.loaded) win = wi->second.data; else fe_default_window(h->fe.win_length, win);
+    auto fi = h->tensors.find("frontend.mel_fb");
+    if (fi != h->tensors.end() && fi->second.loaded) fb = fi->second.data; else fe_default_melfb(h->fe, fb);
+    FeTables tb;
+    const std::string e = fe_build_tables(h->fe, win.data(), fb.data(), &tb);
+    if (!e.empty()) return fail(h, NWW_ERR_INVALID, "frontend tables: %s", e.c_str());
+    const size_t tbytes = (sizeof(FeTables) + 15) & ~(size_t)15;
+    HIP_TRY(h, hipMalloc(&h->d_tables, tbytes));
+    HIP_TRY(h, hipMemset(h->d_tables, 0, tbytes));
+    HIP_TRY(h, hipMemcpy(h->d_tables, &tb, sizeof(FeTables), hipMemcpyHostToDevice));
+    h->mel_max_taps = 0;
+    for (int j = 0; j < h->fe.n_mels; ++j) h->mel_max_taps = tb.mel_cnt[j] > h->mel_max_taps ? tb.mel_cnt[j] : h->mel_max_taps;
+    std::vector<Fe2MelPlan> plan(1);
+    const std::string e2 = fe2_build_mel_plan(h->fe, fb.data(), plan.data());
+    if (!e2.empty()) return fail(h, NWW_ERR_INVALID, "frontend mel plan: %s", e2.c_str());
+    HIP_TRY(h, hipMalloc(&h->d_melplan, sizeof(Fe2MelPlan)));
+    HIP_TRY(h, hipMemcpy(h->d_melplan, plan.data(), sizeof(Fe2MelPlan), hipMemcpyHostToDevice));
+    // (the DFT on the matrix pipe - frontend3 - was built in round 5, parity-green and slower: tools/ubench/fe3/)
+    return NWW_OK;
+}
+
+// ------------------------------------------------------------------------------------------ attention modules
+// The Conformer's whole attention module (in_proj, per-head softmax(q k^T) v, out_proj, residual) in one launch per clip-resident
+// workgroup (attn_x3.hip) under the default arithmetic at the compiled shape; false: nothing planned (NWW_ATTN_FUSED = 0 among others)
+bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH) {
+    if (!(nww_knobs().attn_fused && p.h->f16 && p.h->conv_products == 6 && attn_x3_supported(T, D, NH))) return false;
+    const float *iw = p.W(q + ".attention.in_proj_weight"), *ib = p.W(q + ".attention.in_proj_bias");
+    const float *ow = p.W(q + ".attention.out_proj.weight"), *ob = p.W(q + ".attention.out_proj.bias");
+    const auto hiw = f16_fetch(p.h, iw, (size_t)3 * D * D), how = f16_fetch(p.h, ow, (size_t)D * D);
+    const float ws_in = f16_wscale(hiw), ws_out = f16_wscale(how);
+    // |raw k / v accumulator| <= 2^15 (the clip-scaled rows) x the L1 norm of the scaled weight row: powers of two that keep them below 2^15
+    auto l1max = [&](int r0) {
+        double worst = 0;
+        for (int r = r0; r < r0 + D; ++r) {
+            double t = 0;
+            for (int k = 0; k < D; ++k) t += std::fabs((double)hiw[(size_t)r * D + k]);
+            worst = std::fmax(worst, t);
+        }
+        return worst;
+    };
+    const double lk = l1max(D) * ws_in * 1.02, lv = l1max(2 * D) * ws_in * 1.02;
+    void *packed = nullptr, *bc = nullptr;
+    if (!(ws_in > 0.0f && ws_out > 0.0f && lk < 1e30 && lv < 1e30 &&
+          hipMalloc(&packed, attn_x3_packed_bytes(D, NH)) == hipSuccess && hipMalloc(&bc, (size_t)D * sizeof(float)) == hipSuccess &&
+          launch_attn_x3_pack(iw, ib, ow, ob, packed, static_cast<float*>(bc), D, NH, ws_in, ws_out, p.h->own_stream) == hipSuccess)) {
+        if (packed) (void)hipFree(packed);
+        if (bc) (void)hipFree(bc);
+        return false;
     }
-    // ---- plan
-    PlanCtx p{h};
-    const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, E = c.embedding_dim, nb = c.n_blocks, act = c.activation;
-    switch (c.head_type) {
-        case NWW_HEAD_DNN: {                      // Net: architectures.py:110-126
-            // Everything behind layer1 runs inside the tail's launch (layers.hip: TailArgs::ln0_w) when the widths allow: LayerNorm1 on
-            // layer1's split-K partials, the blocks' Linear + LayerNorm, last_layer, classifier - two launches per forward instead of six
-            if (nww_knobs().tail && L <= 256 && nb <= 4 && tail_supported(L, E)) {
-                add_gemm(p, "layer1", -1, 0, 1, L, T * F, p.W("model.layer1.weight"), p.W("model.layer1.bias"), ACT_NONE, nullptr, nullptr, 99, 1.f, nullptr, false, true, F16_FEATURES, true);
-                p.dnn_body = true;
-                p.dnn_ln0_w = p.W("model.layernorm1.weight"); p.dnn_ln0_b = p.W("model.layernorm1.bias");
-                p.dnn_n_mid = nb;
-                for (int i = 0; i < nb; ++i) {
-                    const std::string q = "model.blocks." + std::to_string(i);
-                    p.dnn_mid[i][0] = p.W(q + ".fcn_layer.weight"); p.dnn_mid[i][1] = p.W(q + ".fcn_layer.bias");
-                    p.dnn_mid[i][2] = p.W(q + ".layer_norm.weight"); p.dnn_mid[i][3] = p.W(q + ".layer_norm.bias");
-                }
-                set_tail(p, "layernorm1+blocks+last_layer", 0, L, p.W("model.last_layer.weight"), p.W("model.last_layer.bias"));
-                break;
+    p.h->packed_weights.push_back(packed);
+    p.h->packed_weights.push_back(bc);
+    const float cK = lk > 1e-30 ? (float)f16_pow2_floor(1.0 / lk) : 1.0f, cV = lv > 1e-30 ? (float)f16_pow2_floor(1.0 / lv) : 1.0f;
+    const float w_un = 1.0f / ws_in, o_un = 1.0f / (ws_out * ws_in * cV), qs = 1.0f / std::sqrt((float)(D / NH));
+    p.add("attn_x3:" + q + ".attention (in_proj+softmax(qk)v+out_proj+res) [f16x3]", [=](Run& r) {
+        AttnArgs a{r.buf[hb], r.buf[hb], static_cast<const unsigned char*>(packed), static_cast<const float*>(bc), r.B, T, w_un, cK, cV, o_un, qs};
+        return launch_attn_x3(a, D, NH, r.cu_count, r.stream);
+    });
+    return true;
+}
+
+// h <- h + out_proj(softmax(q k^T / sqrt(dh)) v), q | k | v = in_proj(h), in three launches: block q's module `module` (".attention" /
+// ".self_attn"); buffers hb (h), big (q | k | v), t1 (the heads' outputs).  exact_sub: mha_h2's softmax form (launch_mha_h2)
+void add_attention_module(PlanCtx& p, const std::string& q, const char* module, int hb, int big, int t1, int T, int D, int NH, int exact_sub) {
+    const std::string m = q + module;
+    // in_proj writes q, k, v head-major when the matrix-core attention consumes them: every (clip, head) block is then
+    // one contiguous run for its LDS-DMA
+    const int mha_mfma = nww_knobs().mha_mfma;
+    const bool want_hm = mha_mfma && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
+    const float *iw = p.W(m + ".in_proj_weight"), *ib = p.W(m + ".in_proj_bias");
+    bool head_major = false;
+    if (add_lin_x3(p, m + (want_hm ? ".in_proj(head-major)" : ".in_proj"), hb, big, T, 3 * D, D, iw, ib, 0, 99, 1.f, nullptr, nullptr,
+                   want_hm ? T : 0, want_hm ? D / NH : 0))
+        head_major = want_hm;
+    else
+        add_gemm(p, m + ".in_proj", hb, big, T, 3 * D, D, iw, ib, ACT_NONE);
+    const int hm = head_major ? 1 : 0;
+    if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
+        p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm, exact_sub); });
+    else if (mha_mfma && mha_mfma_supported(T, D, NH))
+        p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm); });
+    else
+        p.add("mha_core:" + q, [=](Run& r) { return launch_mha_core(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream); });
+    add_linear(p, m + ".out_proj+res", t1, hb, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"), hb, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------ per-head plans
+// Each plans the head's body up to its last Linear, which it leaves to plan_tail (set_tail); NWW_OK or the fail() code.
+
+int plan_dnn(PlanCtx& p) {                          // Net: architectures.py:110-126
+    const nww_config& c = p.h->cfg;
+    const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, nb = c.n_blocks, act = c.activation;
+    add_gemm(p, "layer1", -1, 0, 1, L, T * F, p.W("model.layer1.weight"), p.W("model.layer1.bias"), ACT_NONE, nullptr, nullptr, 99, 1.f, nullptr, false, true, F16_FEATURES, true);
+    // Everything behind layer1 runs inside the tail's launch (layers.hip: TailArgs::ln0_w) when the widths allow: LayerNorm1 on
+    // layer1's split-K partials, the blocks' Linear + LayerNorm, last_layer, classifier - two launches per forward instead of six
+    if (nww_knobs().tail && L <= 256 && nb <= 4 && tail_supported(L, c.embedding_dim)) {
+        p.dnn.on = true;
+        p.dnn.ln0_w = p.W("model.layernorm1.weight"); p.dnn.ln0_b = p.W("model.layernorm1.bias");
+        p.dnn.n_mid = nb;
+        for (int i = 0; i < nb; ++i) {
+            const std::string q = "model.blocks." + std::to_string(i);
+            p.dnn.mid[i][0] = p.W(q + ".fcn_layer.weight"); p.dnn.mid[i][1] = p.W(q + ".fcn_layer.bias");
+            p.dnn.mid[i][2] = p.W(q + ".layer_norm.weight"); p.dnn.mid[i][3] = p.W(q + ".layer_norm.bias");
+        }
+        set_tail(p, "layernorm1+blocks+last_layer", 0, L, p.W("model.last_layer.weight"), p.W("model.last_layer.bias"));
+        return NWW_OK;
+    }
+    const float *lw1 = p.W("model.layernorm1.weight"), *lb1 = p.W("model.layernorm1.bias");
+    p.add("layernorm:layernorm1", [=](Run& r) {
+        if (r.deferred.active && r.deferred.out_id == 0) {           // layer1 left its split-K partials: sum them here
+            r.deferred.active = false;
+            return launch_layernorm_parts(r.splitk_ws, r.deferred.parts, r.deferred.stride, r.deferred.bias, r.buf[0], lw1, lb1, r.B, L, act, r.stream);
+        }
+        return launch_layernorm(r.buf[0], r.buf[0], lw1, lb1, r.B, L, act, r.stream);
+    });
+    int cur = 0;
+    for (int i = 0; i < nb; ++i) {
+        const std::string q = "model.blocks." + std::to_string(i);
+        const int nxt = cur ^ 1;
+        add_gemm(p, q + ".fcn_layer", cur, nxt, 1, L, L, p.W(q + ".fcn_layer.weight"), p.W(q + ".fcn_layer.bias"), ACT_NONE);
+        const float *lw = p.W(q + ".layer_norm.weight"), *lb = p.W(q + ".layer_norm.bias");
+        p.add("layernorm:" + q, [=](Run& r) { return launch_layernorm(r.buf[nxt], r.buf[nxt], lw, lb, r.B, L, act, r.stream); });
+        cur = nxt;
+    }
+    set_tail(p, "last_layer", cur, L, p.W("model.last_layer.weight"), p.W("model.last_layer.bias"));
+    return NWW_OK;
+}
+
+int plan_cnn(PlanCtx& p) {                          // CNNModel: architectures.py:51-80
+    nww_handle* h = p.h;
+    const nww_config& c = h->cfg;
+    const int T = c.in_rows, F = c.in_cols, act = c.activation;
+    // trunk -> fc1 hand-over as the GEMM's own A tiles when both run on the split-operand path and the geometry allows
+    // 16-byte stores inside a 32-feature tile row
+    const int H2 = T / 4, W2 = F / 4;
+    h->trunk_blocked = (h->conv_products == 6 || h->conv_products == 9) && trunk_b_pick_strips(T, F) > 0 &&
+                       (W2 % 4) == 0 && ((H2 * W2) % 4) == 0 && ((32 * H2 * W2) % 32) == 0;
+    F16Range a2_bound;                    // NWW_ARITH_F16X3: the range of the trunk's output, fc1's operand
+    const bool fused = add_trunk(p, "conv1+pool+conv2+pool", -1, 1, 16, 32, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr,
+                                 p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, &h->trunk_blocked,
+                                 F16_FEATURES, &a2_bound);
+    if (!fused) {
+        h->trunk_blocked = false;
+        add_conv(p, "conv1", -1, 0, 1, 16, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr, act, 1);
+        add_conv(p, "conv2", 0, 1, 16, 32, T / 2, F / 2, p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, 1);
+    }
+    // fc1's split-K partials are reduced by the classifier tail itself when that is the fused kernel
+    add_gemm(p, "fc1", 1, 0, 1, 128, 32 * H2 * W2, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, nullptr, nullptr, 99, 1.f,
+             &h->trunk_blocked, nww_knobs().tail && tail_supported(128, c.embedding_dim), false, a2_bound);
+    set_tail(p, "fc2", 0, 128, p.W("model.fc2.weight"), p.W("model.fc2.bias"));
+    return NWW_OK;
+}
+
+// The E2E head on the transposed plane (e2e_transposed_ok); whatever goes wrong while it is built (a shape one of its kernels does
+// not take after all, an allocation) drops what was planned, and plan_e2e_dnn falls back to the reference's orientation
+bool plan_e2e_dnn_transposed(PlanCtx& p) {
+    nww_handle* h = p.h;
+    const int Hh = h->cfg.in_rows, Ww = h->cfg.in_cols, act = h->cfg.activation;     // (n_mels, frames)
+    if (!e2e_transposed_ok(p, Hh, Ww)) return false;
+    const size_t steps_before = h->plan.size();
+    const int Ht = Ww, Wt = Hh;       // the plane the kernels see: (frames, n_mels)
+    float* wt = nullptr;
+    const int nf[3] = {16, 32 * 16, 64 * 32};
+    if (hipMalloc(&wt, (size_t)(nf[0] + nf[1] + nf[2]) * 9 * sizeof(float)) != hipSuccess) return false;
+    h->packed_weights.push_back(wt);
+    float* wts[3] = {wt, wt + (size_t)nf[0] * 9, wt + (size_t)(nf[0] + nf[1]) * 9};
+    for (int i = 0; i < 3; ++i)
+        if (launch_transpose3x3(p.W("model.conv_block." + std::to_string(4 * i) + ".weight"), wts[i], nf[i], h->own_stream) != hipSuccess)
+            return false;
+    h->e2e_transposed = true;
+    p.need(2, (size_t)Hh * Ww);
+    p.add("transpose:mel-major features -> frames-major (skipped after the frontend)", [=](Run& r) {
+        if (r.x_frames_major) return hipSuccess;
+        const hipError_t e = launch_transpose_planes(r.x, r.buf[2], r.B, Hh, Ww, r.stream);
+        r.x = r.buf[2];
+        return e;
+    });
+    const int h3 = Ht / 4, w3 = Wt / 4;           // (25, 16): AdaptiveAvgPool2d((1,4))'s windows run along the FRAMES, here y
+    const int sw4 = h3 / 4, kw4 = h3 - 3 * sw4;
+    F16Range tbound;                              // NWW_ARITH_F16X3: the range of the trunk's output, the third conv's operand
+    const bool ok = add_trunk(p, "conv_block.0-7 (transposed plane)", -1, 1, 16, 32, Ht, Wt, wts[0], p.W("model.conv_block.0.bias"),
+                              p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), wts[1], p.W("model.conv_block.4.bias"),
+                              p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, nullptr, F16_FEATURES, &tbound) &&
+                    h->plan.back().name.rfind("trunk_x3:", 0) == 0 && h3 >= 4 &&
+                    add_conv_mfma(p, "model.conv_block.8 (transposed plane)", 1, 0, 32, 64, h3, w3, wts[2], p.W("model.conv_block.8.bias"),
+                                  p.W("model.conv_block.9.alpha"), p.W("model.conv_block.9.beta"), act, 0, kw4, sw4, 4, nullptr, 1, nullptr, tbound);
+    if (!ok) {
+        h->plan.resize(steps_before);
+        h->e2e_transposed = false;
+        return false;
+    }
+    add_gemm(p, "fc1+bn1", 0, 1, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, p.W("model.bn1.alpha"), p.W("model.bn1.beta"));
+    set_tail(p, "out", 1, 128, p.W("model.out.weight"), p.W("model.out.bias"));
+    return true;
+}
+
+int plan_e2e_dnn(PlanCtx& p) {                      // E2E_MelSpectrogram_CNN body: architectures.py:840-865,877-889
+    if (plan_e2e_dnn_transposed(p)) return NWW_OK;
+    nww_handle* h = p.h;
+    const int Hh = h->cfg.in_rows, Ww = h->cfg.in_cols, act = h->cfg.activation;     // (n_mels, frames)
+    const int ch[3] = {16, 32, 64};
+    int cin = 1, hh = Hh, ww = Ww, cur = -1;
+    int first = 0;
+    bool fused_pool = false;
+    F16Range cbound;                                  // NWW_ARITH_F16X3: range of the current stage's input (empty: unknown)
+    if (add_trunk(p, "conv_block.0-7", -1, 1, 16, 32, Hh, Ww, p.W("model.conv_block.0.weight"), p.W("model.conv_block.0.bias"),
+                  p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), p.W("model.conv_block.4.weight"),
+                  p.W("model.conv_block.4.bias"), p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, nullptr, F16_FEATURES, &cbound)) {
+        first = 2; cin = 32; hh = Hh / 4; ww = Ww / 4; cur = 1;
+    }
+    for (int i = first; i < 3; ++i) {
+        const std::string cw = "model.conv_block." + std::to_string(4 * i), bnp = "model.conv_block." + std::to_string(4 * i + 1);
+        const int out = (i % 2 == 0) ? 0 : 1;
+        if (i == 2 && ww >= 4) {
+            // conv3 + AdaptiveAvgPool2d((1,4)) in its exported AvgPool2d form, fused when the MFMA kernel applies
+            const int sw4 = ww / 4, kw4 = ww - 3 * sw4;
+            if (add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 0, kw4, sw4, 4,
+                              nullptr, 0, nullptr, cbound)) {
+                fused_pool = true; cin = ch[i]; cur = out;
+                continue;
             }
-            add_gemm(p, "layer1", -1, 0, 1, L, T * F, p.W("model.layer1.weight"), p.W("model.layer1.bias"), ACT_NONE, nullptr, nullptr, 99, 1.f, nullptr, false, true, F16_FEATURES, true);
-            {
-                const float *lw1 = p.W("model.layernorm1.weight"), *lb1 = p.W("model.layernorm1.bias");
-                p.add("layernorm:layernorm1", [=](Run& r) {
-                    if (r.deferred.active && r.deferred.out_id == 0) {           // layer1 left its split-K partials: sum them here
-                        r.deferred.active = false;
-                        return launch_layernorm_parts(r.splitk_ws, r.deferred.parts, r.deferred.stride, r.deferred.bias, r.buf[0], lw1, lb1, r.B, L, act, r.stream);
+        }
+        F16Range nb;
+        if (!add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2,
+                           0, 0, 0, nullptr, 0, nullptr, cbound, &nb))
+            add_conv(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2);
+        cbound = nb;
+        if (i < 2) { hh /= 2; ww /= 2; }
+        cin = ch[i]; cur = out;
+    }
+    if (hh < 1 || ww < 4) return fail(h, NWW_ERR_INVALID, "e2e_dnn input too small for AdaptiveAvgPool2d((1,4))");
+    // AdaptiveAvgPool2d((1,4)) in its exported AvgPool2d form (_export/onnx.py:146-152)
+    const int sh = hh / 1, kh = hh, sw = ww / 4, kw = ww - 3 * sw;
+    int fc_in = cur;                                  // buffer holding [B][256] after the pool
+    if (!fused_pool) {
+        const int pin = cur, pout = cur ^ 1;
+        p.need(pout, 256);
+        p.add("avgpool:export(1,4)", [=](Run& r) { return launch_avgpool(r.buf[pin], r.buf[pout], r.B * 64, hh, ww, kh, kw, sh, sw, 1, 4, r.stream); });
+        fc_in = pout;
+    }
+    const int fc_out = fc_in ^ 1;
+    add_gemm(p, "fc1+bn1", fc_in, fc_out, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, p.W("model.bn1.alpha"), p.W("model.bn1.beta"));
+    set_tail(p, "out", fc_out, 128, p.W("model.out.weight"), p.W("model.out.bias"));
+    return NWW_OK;
+}
+
+int plan_crnn(PlanCtx& p) {                         // CRNNModel: architectures.py:209-287
+    nww_handle* h = p.h;
+    const nww_config& c = h->cfg;
+    const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, nb = c.n_blocks, act = c.activation;
+    int cin = 1, hh = T, ww = F, cur = -1;
+    int first = 0;
+    bool seq_written = false;
+    F16Range cbound;                                  // NWW_ARITH_F16X3: range of the current stage's input (empty: unknown)
+    const size_t steps_before = h->plan.size();
+    if (c.n_crnn_channels >= 2 && c.crnn_channels[0] == 16 && c.crnn_channels[1] == 32 &&
+        add_trunk(p, "cnn.0-7", -1, 1, 16, 32, T, F, p.W("model.cnn.0.weight"), p.W("model.cnn.0.bias"), p.W("model.cnn.1.alpha"),
+                  p.W("model.cnn.1.beta"), p.W("model.cnn.4.weight"), p.W("model.cnn.4.bias"), p.W("model.cnn.5.alpha"),
+                  p.W("model.cnn.5.beta"), act, nullptr, F16_FEATURES, &cbound)) {
+        first = 2; cin = 32; hh = T / 4; ww = F / 4; cur = 1;
+    }
+    for (int i = first; i < c.n_crnn_channels; ++i) {
+        const std::string cw = "model.cnn." + std::to_string(4 * i), bnp = "model.cnn." + std::to_string(4 * i + 1);
+        const int out = (i % 2 == 0) ? 0 : 1;
+        // the last conv stage may write the recurrent layers' [W][C * H] sequence layout itself (conv3_x3.hip)
+        bool seq = i == c.n_crnn_channels - 1;
+        // the stage right behind a fused split-operand trunk may take its input from the streaming rings (nww_stream.hip)
+        bool ring = i == 2 && first == 2 && h->plan.size() == steps_before + 1 && h->plan.back().name.rfind("trunk_x3:", 0) == 0 && ((F / 4) % 4) == 0;
+        F16Range nbr;
+        const bool mf = add_conv_mfma(p, cw, cur, out, cin, c.crnn_channels[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 1, 0, 0, 0, &seq, 0, &ring, cbound, &nbr, 2);      // (scratch: the recurrent layers' xg buffer, idle until they run)
+        cbound = nbr;
+        if (!mf) {
+            ring = false;
+            seq = false;
+            add_conv(p, cw, cur, out, cin, c.crnn_channels[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 1);
+        }
+        if (ring) {
+            h->stream_conv = true; h->stream_H = T; h->stream_W = F;
+            h->stream_seq = seq && i == c.n_crnn_channels - 1;
+            h->seq_floats = (size_t)c.crnn_channels[i] * (hh / 2) * (ww / 2);
+        }
+        seq_written = seq;
+        hh /= 2; ww /= 2; cin = c.crnn_channels[i]; cur = out;
+    }
+    if (hh < 1 || ww < 1) return fail(h, NWW_ERR_INVALID, "crnn input too small for the conv stack");
+    const int seq = seq_written ? cur : cur ^ 1, C = cin, Hc = hh, Wc = ww;
+    if (!seq_written) {
+        p.need(seq, (size_t)C * Hc * Wc);
+        p.add("crnn_seq", [=](Run& r) { return launch_crnn_seq(r.buf[cur], r.buf[seq], r.B, C, Hc, Wc, r.stream); });
+    }
+    add_bigru_last(p, "model.rnn", seq, Wc, C * Hc, L, nb, 2, seq ^ 1, 3, 4, c.crnn_rnn_lstm ? 4 : 3);      // seq ^ 1: the free one of buffers 0 / 1
+    set_tail(p, "fc", 4, 2 * L, p.W("model.fc.weight"), p.W("model.fc.bias"));
+    return NWW_OK;
+}
+
+int plan_gru(PlanCtx& p) {                          // GRUModel: architectures.py:129-145
+    const nww_config& c = p.h->cfg;
+    add_bigru_last(p, "model.gru", -1, c.in_rows, c.in_cols, c.layer_dim, c.n_blocks, 2, 0, 1, 4);
+    set_tail(p, "fc", 4, 2 * c.layer_dim, p.W("model.fc.weight"), p.W("model.fc.bias"));
+    return NWW_OK;
+}
+
+int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectures.py:620-687, channels-last on the GPU
+    nww_handle* h = p.h;
+    const nww_config& c = h->cfg;
+    const int T = c.in_rows, F = c.in_cols, act = c.activation;
+    // init conv (+BN+act+pool) writes [B][H1][W1][32]; each block: one depthwise kernel emits d = dw3x3(x) and
+    // xs = x at the strided centres, then two MFMA GEMMs over M = B*Ho*Wo pixels:
+    //   R = BN_s(xs . Wsc^T) ;  out = act(BN_1(d . Wpw^T)) + R      (activation BEFORE the residual add, :646-647)
+    const int ic_mfma = nww_knobs().conv_mfma;
+    // init conv fused with block1's depthwise (trunk.hip: the 32-channel planes never reach HBM)
+    const int bc_front = nww_knobs().bc_front;
+    const bool front_fused = ic_mfma && bc_front && conv1_pool_nhwc_mfma_fits(T, F) && conv1_pool_dw_rows(T, F, 2) > 0;
+    // nww_config.act_dtype = NWW_ACT_DTYPE_BF16 / _F16: every activation tensor between the kernels of this head is stored in 16
+    // bits (arithmetic and accumulation stay float32); implemented on the fused front + split-operand block path only.
+    // binary16 (11 significant bits against bf16's 8) stores value x a power of two fixed here from a bound on the tensor
+    // (features within +-NWW_F16_FEATURE_BOUND as in the f16x3 arithmetic; the bound is not allowed to sit more than 2^16 above
+    // the tensor's typical magnitude, and the stores saturate), and a block's weights are two binary16 terms of weight x scale.
+    const int act16 = c.act_dtype;                       // NWW_ACT_DTYPE_* == ACT16_* (split_h2.h)
+    const bool act_bf16 = act16 != NWW_ACT_DTYPE_F32;    // any 16-bit storage
+    const bool act_f16 = act16 == NWW_ACT_DTYPE_F16;
+    if (act_bf16 && !(front_fused && p.h->conv_products == 6))
+        return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = bf16 / f16 needs the fused BcResNet front kernel and a split-operand conv_arith for this input shape");
+    float s_h[4] = {1.f, 1.f, 1.f, 1.f}, s_d[4] = {1.f, 1.f, 1.f, 1.f};     // scales of h_i (block i's output, h_0 = init conv) and d_i
+    DualPackScales dps[4];
+    if (act_f16) {
+        auto cap = [](F16Range r) { return f16_scale(std::fmin(r.bound, r.typ * 65536.0)); };
+        auto dw_range = [&](const float* wt, int C, F16Range in) {      // wt [9][C] tap-major
+            const auto w = f16_fetch(p.h, wt, (size_t)9 * C);
+            double worst = 0, typ = 0;
+            for (int ch = 0; ch < C; ++ch) {
+                double l1 = 0, l2 = 0;
+                for (int k = 0; k < 9; ++k) { const double v = w[(size_t)k * C + ch]; l1 += std::fabs(v); l2 += v * v; }
+                worst = std::fmax(worst, l1); typ += std::sqrt(l2);
+            }
+            return F16Range{worst * in.bound, typ / C * in.typ};
+        };
+        const auto hw0 = f16_fetch(p.h, p.W("model.init_conv.0.weight"), 32 * 9);
+        const float *pa0 = p.W("model.init_conv.1.alpha"), *pb0 = p.W("model.init_conv.1.beta");
+        const auto ha0 = f16_fetch(p.h, pa0, 32), hb0 = f16_fetch(p.h, pb0, 32);
+        F16Range rh{f16_layer_bound(hw0, 32, 9, hb0, false, ha0, hb0, pa0 != nullptr, F16_FEATURES.bound),
+                    f16_layer_typ(hw0, 32, 9, ha0, pa0 != nullptr, F16_FEATURES.typ)};
+        s_h[0] = cap(rh);
+        const int chs[4] = {32, 64, 128, 256};
+        for (int i = 1; i <= 3; ++i) {
+            const std::string q = "model.block" + std::to_string(i);
+            const int ci = chs[i - 1], co = chs[i];
+            const F16Range rd = dw_range(p.W(q + ".depthwise.weight_t"), ci, rh);
+            s_d[i] = cap(rd);
+            const float *pa1 = p.W(q + ".bn1.alpha"), *pas = p.W(q + ".shortcut.1.alpha");
+            const auto wpw = f16_fetch(p.h, p.W(q + ".pointwise.weight"), (size_t)co * ci), wsc = f16_fetch(p.h, p.W(q + ".shortcut.0.weight"), (size_t)co * ci);
+            const auto ha1 = f16_fetch(p.h, pa1, co), hb1 = f16_fetch(p.h, p.W(q + ".bn1.beta"), co);
+            const auto has = f16_fetch(p.h, pas, co), hbs = f16_fetch(p.h, p.W(q + ".shortcut.1.beta"), co);
+            dps[i].pw_ws = f16_wscale(wpw); dps[i].sc_ws = f16_wscale(wsc);
+            if (!(s_d[i] > 0.f && s_h[i - 1] > 0.f && dps[i].pw_ws > 0.f && dps[i].sc_ws > 0.f))
+                return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = f16: no finite bound on the tensors of block %d", i);
+            dps[i].pw_un = 1.0f / (dps[i].pw_ws * s_d[i]); dps[i].sc_un = 1.0f / (dps[i].sc_ws * s_h[i - 1]);
+            const F16Range rpw{f16_layer_bound(wpw, co, ci, hb1, false, ha1, hb1, pa1 != nullptr, rd.bound), f16_layer_typ(wpw, co, ci, ha1, pa1 != nullptr, rd.typ)};
+            const F16Range rsc{f16_layer_bound(wsc, co, ci, hbs, false, has, hbs, pas != nullptr, rh.bound), f16_layer_typ(wsc, co, ci, has, pas != nullptr, rh.typ)};
+            rh = F16Range{rpw.bound + rsc.bound, std::hypot(rpw.typ, rsc.typ)};
+            s_h[i] = cap(rh);
+        }
+    }
+    if (front_fused) {
+        const float *w0 = p.W("model.init_conv.0.weight"), *a0 = p.W("model.init_conv.1.alpha"), *b0 = p.W("model.init_conv.1.beta");
+        const float* dwt1 = p.W("model.block1.depthwise.weight_t");
+        const int ho1 = (T / 2 - 1) / 2 + 1, wo1 = (F / 2 - 1) / 2 + 1;
+        p.need(2, (size_t)32 * ho1 * wo1); p.need(3, (size_t)32 * ho1 * wo1);
+        const int max_grid = p.h->cu_count;
+        // the convolution from split operands on the bf16 matrix cores (trunk_b.hip) under the handle's arithmetic switch;
+        // NWW_BC_FRONT = 2 keeps the float32-MFMA kernel
+        void* fpack = nullptr;
+        int fprod = p.h->conv_products;
+        // under NWW_ARITH_F16X3 (BN present): two binary16 terms per operand, features clamped to +-NWW_F16_FEATURE_BOUND as in the
+        // CNN trunk
+        float fin = 0.0f, fws = 1.0f;
+        if (p.h->f16 && fprod == 6 && a0 && bc_front != 2) {
+            fin = f16_scale(F16_FEATURES.bound); fws = f16_wscale(f16_fetch(p.h, w0, 32 * 9));
+            if (fin > 0.0f && fws > 0.0f) fprod = 3;
+        }
+        if ((fprod == 6 || fprod == 9 || fprod == 3) && bc_front != 2 && bc_front_b_rows(T, F, 2) > 0 &&
+            hipMalloc(&fpack, bc_front_b_packed_bytes()) == hipSuccess) {
+            const hipError_t pe = fprod == 3 ? launch_bc_front_b_pack_f16(w0, static_cast<unsigned char*>(fpack), fws, p.h->own_stream)
+                                             : launch_bc_front_b_pack(w0, static_cast<unsigned char*>(fpack), p.h->own_stream);
+            if (pe == hipSuccess) p.h->packed_weights.push_back(fpack);
+            else { (void)hipFree(fpack); fpack = nullptr; }
+        }
+        const float f_un = 1.0f / (fin > 0.0f ? fin * fws : 1.0f);
+        // all folded-BN factors non-negative (the usual case: gamma > 0): max-pool commutes with BN + ReLU through the maximum alone
+        int bn_pos = 0;
+        if (a0) {
+            bn_pos = 1;
+            for (float v : f16_fetch(p.h, a0, 32)) if (!(v >= 0.0f)) bn_pos = 0;
+        }
+        if (fpack) p.h->clamps_features = true;
+        p.add(std::string(fpack ? "conv1_dw_x3" : "conv1_dw_mfma") + ":init_conv + block1.depthwise (nhwc" + (act_f16 ? ", f16 out)" : act_bf16 ? ", bf16 out)" : ")") + (fpack && fprod == 3 ? " [f16x3]" : ""), [=](Run& r) {
+            Conv1DwArgs a{src(r, -1), w0, nullptr, a0, b0, dwt1, r.buf[2], r.buf[3], r.B, T, F, act, 2, 2};
+            a.bf16_out = act16; a.d_scale = s_d[1]; a.xs_scale = s_h[0];
+            if (fpack) {
+                a.wpack = static_cast<const unsigned char*>(fpack);
+                a.f16_in = fin; a.f16_clamp = NWW_F16_FEATURE_BOUND; a.f16_unscale = f_un; a.bn_pos = bn_pos;
+                return launch_bc_front_b(a, fprod, max_grid, r.stream);
+            }
+            return launch_conv1_pool_dw_nhwc(a, max_grid, r.stream);
+        });
+    } else if (ic_mfma && conv1_pool_nhwc_mfma_fits(T, F)) {
+        const float *w0 = p.W("model.init_conv.0.weight"), *a0 = p.W("model.init_conv.1.alpha"), *b0 = p.W("model.init_conv.1.beta");
+        p.need(0, (size_t)32 * (T / 2) * (F / 2));
+        const int max_grid = p.h->cu_count;
+        p.add("conv1_mfma:init_conv(nhwc)", [=](Run& r) {
+            Conv1NhwcArgs a{src(r, -1), w0, nullptr, a0, b0, r.buf[0], r.B, T, F, act};
+            return launch_conv1_pool_nhwc_mfma(a, max_grid, r.stream);
+        });
+    } else {
+        add_conv(p, "init_conv(nhwc)", -1, 0, 1, 32, T, F, p.W("model.init_conv.0.weight"), nullptr, p.W("model.init_conv.1.alpha"), p.W("model.init_conv.1.beta"), act, 1, 1);
+    }
+    int hh = T / 2, ww = F / 2, cur = 0;
+    bool mean_fused = false;
+    const int ch[4] = {32, 64, 128, 256};
+    const int st[3][2] = {{2, 2}, {2, 2}, {2, 1}};
+    // d_i / xs_i (depthwise output and strided block input) of the coming block live in buffers dwb / xsb; have_dx: they are
+    // already there - written by the fused front kernel or by the previous block's chained kernel (bc_chain.hip)
+    int dwb = 2, xsb = 3;
+    bool have_dx = front_fused;
+    for (int i = 1; i <= 3; ++i) {
+        const std::string q = "model.block" + std::to_string(i);
+        const int ci = ch[i - 1], co = ch[i], sh = st[i - 1][0], sw = st[i - 1][1];
+        const int ho = (hh - 1) / sh + 1, wo = (ww - 1) / sw + 1;
+        int outb = 4;
+        for (int cand : {0, 1, 4})
+            if (cand != cur && cand != dwb && cand != xsb) { outb = cand; break; }
+        p.need(dwb, (size_t)ci * ho * wo); p.need(xsb, (size_t)ci * ho * wo);
+        const float* dwt = p.W(q + ".depthwise.weight_t");
+        const int hin = hh, win = ww;
+        if (!have_dx)
+            p.add("dwconv3x3_nhwc:" + q, [=](Run& r) { return launch_dwconv3x3_nhwc(r.buf[cur], dwt, r.buf[dwb], r.buf[xsb], r.B, ci, hin, win, sh, sw, r.stream); });
+        // one dual GEMM per block: shortcut and pointwise products in the same workgroup, no residual round trip
+        {
+            const float *wpw = p.W(q + ".pointwise.weight"), *a1 = p.W(q + ".bn1.alpha"), *b1 = p.W(q + ".bn1.beta");
+            const float *wsc = p.W(q + ".shortcut.0.weight"), *as = p.W(q + ".shortcut.1.alpha"), *bs = p.W(q + ".shortcut.1.beta");
+            const int rows = ho * wo;
+            p.need(outb, (size_t)rows * co);
+            // both products from split operands on the bf16 matrix cores (dual_x3.hip) under the same arithmetic switch
+            void* packed = nullptr;
+            // float32 activations under NWW_ARITH_F16X3: two binary16 terms per operand, the activation rows scaled per pixel in
+            // the kernel (DualArgs::h2) - no tensor bound needed
+            const bool dual_h2 = p.h->f16 && !act_bf16;
+            // blocks 1 and 2 chained with the next block's depthwise (bc_chain.hip; two-term weights in every storage mode)
+            const bool will_chain = nww_knobs().bc_chain && i < 3 && have_dx && bc_chain_supported(ci, ho, wo) &&
+                                    (act_f16 || dual_h2 || (act16 == NWW_ACT_DTYPE_BF16 && p.h->f16));
+            if (dual_h2 || (will_chain && !act_f16)) {
+                dps[i].pw_ws = f16_wscale(f16_fetch(p.h, wpw, (size_t)co * ci)); dps[i].sc_ws = f16_wscale(f16_fetch(p.h, wsc, (size_t)co * ci));
+                if (!(dps[i].pw_ws > 0.f && dps[i].sc_ws > 0.f)) return fail(h, NWW_ERR_INVALID, "block %d: non-finite weights", i);
+                dps[i].pw_un = 1.0f / dps[i].pw_ws; dps[i].sc_un = 1.0f / dps[i].sc_ws;
+            }
+            const int terms = act_f16 || dual_h2 || will_chain ? 2 : 3;
+            if (p.h->conv_products == 6 && dual_x3_supported(ci, co) &&
+                hipMalloc(&packed, dual_x3_packed_bytes(ci, co, terms)) == hipSuccess) {
+                if (launch_dual_x3_pack(wpw, wsc, a1, b1, as, bs, packed, ci, co, p.h->own_stream, terms, dps[i]) == hipSuccess) {
+                    p.h->packed_weights.push_back(packed);
+                    // when the block input is in HBM (every block but the one whose depthwise ran inside the fused front kernel) the
+                    // shortcut rows are gathered from it and the depthwise kernel planned just above writes no copy of them
+                    const bool gather = !have_dx;
+                    if (gather) {
+                        const float dw_mul = s_d[i] / s_h[i - 1];
+                        p.pop_last();
+                        p.add("dwconv3x3_nhwc:" + q, [=](Run& r) { return launch_dwconv3x3_nhwc(r.buf[cur], dwt, r.buf[dwb], nullptr, r.B, ci, hin, win, sh, sw, r.stream, act16, dw_mul); });
                     }
-                    return launch_layernorm(r.buf[0], r.buf[0], lw1, lb1, r.B, L, act, r.stream);
-                });
-            }
-            int cur = 0;
-            for (int i = 0; i < nb; ++i) {
-                const std::string q = "model.blocks." + std::to_string(i);
-                const int nxt = cur ^ 1;
-                add_gemm(p, q + ".fcn_layer", cur, nxt, 1, L, L, p.W(q + ".fcn_layer.weight"), p.W(q + ".fcn_layer.bias"), ACT_NONE);
-                const float *lw = p.W(q + ".layer_norm.weight"), *lb = p.W(q + ".layer_norm.bias");
-                p.add("layernorm:" + q, [=](Run& r) { return launch_layernorm(r.buf[nxt], r.buf[nxt], lw, lb, r.B, L, act, r.stream); });
-                cur = nxt;
-            }
-            set_tail(p, "last_layer", cur, L, p.W("model.last_layer.weight"), p.W("model.last_layer.bias"));
-            break;
-        }
-        case NWW_HEAD_CNN: {                      // CNNModel: architectures.py:51-80
-            // trunk -> fc1 hand-over as the GEMM's own A tiles when both run on the split-operand path and the geometry allows
-            // 16-byte stores inside a 32-feature tile row
-            const int H2 = T / 4, W2 = F / 4;
-            h->trunk_blocked = (h->conv_products == 6 || h->conv_products == 9) && trunk_b_pick_strips(T, F) > 0 &&
-                               (W2 % 4) == 0 && ((H2 * W2) % 4) == 0 && ((32 * H2 * W2) % 32) == 0;
-            F16Range a2_bound;                    // NWW_ARITH_F16X3: the range of the trunk's output, fc1's operand
-            const bool fused = add_trunk(p, "conv1+pool+conv2+pool", -1, 1, 16, 32, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr,
-                                         p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, &h->trunk_blocked,
-                                         F16_FEATURES, &a2_bound);
-            if (!fused) {
-                h->trunk_blocked = false;
-                add_conv(p, "conv1", -1, 0, 1, 16, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr, act, 1);
-                add_conv(p, "conv2", 0, 1, 16, 32, T / 2, F / 2, p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, 1);
-            }
-            // fc1's split-K partials are reduced by the classifier tail itself when that is the fused kernel
-            add_gemm(p, "fc1", 1, 0, 1, 128, 32 * H2 * W2, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, nullptr, nullptr, 99, 1.f,
-                     &h->trunk_blocked, nww_knobs().tail && tail_supported(128, E), false, a2_bound);
-            set_tail(p, "fc2", 0, 128, p.W("model.fc2.weight"), p.W("model.fc2.bias"));
-            break;
-        }
-        case NWW_HEAD_E2E_DNN: {                  // E2E_MelSpectrogram_CNN body: architectures.py:840-865,877-889
-            const int Hh = T, Ww = F;             // (n_mels, frames)
-            const int ch[3] = {16, 32, 64};
-            // the transposed plan; whatever goes wrong while it is built (a shape one of its kernels does not take after all, an
-            // allocation) drops what was planned and falls through to the reference's orientation below
-            const auto try_transposed = [&]() -> bool {
-                if (!e2e_transposed_ok(p, Hh, Ww)) return false;
-                const size_t steps_before = h->plan.size();
-                const int Ht = Ww, Wt = Hh;       // the plane the kernels see: (frames, n_mels)
-                float* wt = nullptr;
-                const int nf[3] = {16, 32 * 16, 64 * 32};
-                if (hipMalloc(&wt, (size_t)(nf[0] + nf[1] + nf[2]) * 9 * sizeof(float)) != hipSuccess) return false;
-                p.h->packed_weights.push_back(wt);
-                float* wts[3] = {wt, wt + (size_t)nf[0] * 9, wt + (size_t)(nf[0] + nf[1]) * 9};
-                for (int i = 0; i < 3; ++i)
-                    if (launch_transpose3x3(p.W("model.conv_block." + std::to_string(4 * i) + ".weight"), wts[i], nf[i], p.h->own_stream) != hipSuccess)
-                        return false;
-                h->e2e_transposed = true;
-                p.need(2, (size_t)Hh * Ww);
-                p.add("transpose:mel-major features -> frames-major (skipped after the frontend)", [=](Run& r) {
-                    if (r.x_frames_major) return hipSuccess;
-                    const hipError_t e = launch_transpose_planes(r.x, r.buf[2], r.B, Hh, Ww, r.stream);
-                    r.x = r.buf[2];
-                    return e;
-                });
-                const int h3 = Ht / 4, w3 = Wt / 4;           // (25, 16): AdaptiveAvgPool2d((1,4))'s windows run along the FRAMES, here y
-                const int sw4 = h3 / 4, kw4 = h3 - 3 * sw4;
-                F16Range tbound;                              // NWW_ARITH_F16X3: the range of the trunk's output, the third conv's operand
-                const bool ok = add_trunk(p, "conv_block.0-7 (transposed plane)", -1, 1, 16, 32, Ht, Wt, wts[0], p.W("model.conv_block.0.bias"),
-                                          p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), wts[1], p.W("model.conv_block.4.bias"),
-                                          p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, nullptr, F16_FEATURES, &tbound) &&
-                                h->plan.back().name.rfind("trunk_x3:", 0) == 0 && h3 >= 4 &&
-                                add_conv_mfma(p, "model.conv_block.8 (transposed plane)", 1, 0, 32, 64, h3, w3, wts[2], p.W("model.conv_block.8.bias"),
-                                              p.W("model.conv_block.9.alpha"), p.W("model.conv_block.9.beta"), act, 0, kw4, sw4, 4, nullptr, 1, nullptr, tbound);
-                if (!ok) {
-                    h->plan.resize(steps_before);
-                    h->e2e_transposed = false;
-                    return false;
-                }
-                add_gemm(p, "fc1+bn1", 0, 1, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, p.W("model.bn1.alpha"), p.W("model.bn1.beta"));
-                set_tail(p, "out", 1, 128, p.W("model.out.weight"), p.W("model.out.bias"));
-                return true;
-            };
-            if (try_transposed()) break;
-            int cin = 1, hh = Hh, ww = Ww, cur = -1;
-            int first = 0;
-            bool fused_pool = false;
-            F16Range cbound;                                  // NWW_ARITH_F16X3: range of the current stage's input (empty: unknown)
-            if (add_trunk(p, "conv_block.0-7", -1, 1, 16, 32, Hh, Ww, p.W("model.conv_block.0.weight"), p.W("model.conv_block.0.bias"),
-                          p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), p.W("model.conv_block.4.weight"),
-                          p.W("model.conv_block.4.bias"), p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, nullptr, F16_FEATURES, &cbound)) {
-                first = 2; cin = 32; hh = Hh / 4; ww = Ww / 4; cur = 1;
-            }
-            for (int i = first; i < 3; ++i) {
-                const std::string cw = "model.conv_block." + std::to_string(4 * i), bnp = "model.conv_block." + std::to_string(4 * i + 1);
-                const int out = (i % 2 == 0) ? 0 : 1;
-                if (i == 2 && ww >= 4) {
-                    // conv3 + AdaptiveAvgPool2d((1,4)) in its exported AvgPool2d form, fused when the MFMA kernel applies
-                    const int sw4 = ww / 4, kw4 = ww - 3 * sw4;
-                    if (add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 0, kw4, sw4, 4,
-                                      nullptr, 0, nullptr, cbound)) {
-                        fused_pool = true; cin = ch[i]; cur = out;
+                    // blocks 1 and 2 chained with the next block's depthwise (bc_chain.hip): the block's output stays in LDS, the
+                    // next block finds its d / xs rows in the other buffer pair
+                    const char* suffix = act_f16 ? " (f16 activations)" : act_bf16 ? " (bf16 activations)" : dual_h2 ? " [f16x3]" : "";
+                    if (will_chain) {
+                        const std::string qn = "model.block" + std::to_string(i + 1);
+                        const float* dwn = p.W(qn + ".depthwise.weight_t");
+                        const int sh2 = st[i][0], sw2 = st[i][1], ho2 = (ho - 1) / sh2 + 1, wo2 = (wo - 1) / sw2 + 1;
+                        const int odb = dwb == 2 ? 0 : 2, oxb = odb + 1, idb = dwb, ixb = xsb;
+                        p.need(odb, (size_t)co * ho2 * wo2); p.need(oxb, (size_t)co * ho2 * wo2);
+                        const float d_mul = s_d[i + 1], xs_mul = s_h[i];
+                        const int max_grid = p.h->cu_count;
+                        p.add("bc_chain:" + q + ".pointwise+bn+act + shortcut+bn -> " + qn + ".depthwise" + suffix, [=](Run& r) {
+                            ChainArgs a{r.buf[idb], r.buf[ixb], r.buf[odb], r.buf[oxb], static_cast<const unsigned char*>(packed), dwn,
+                                        r.B, ho, wo, sh2, sw2, ho2, wo2};
+                            a.act16 = act16; a.d_mul = d_mul; a.xs_mul = xs_mul;
+                            return launch_bc_chain(a, ci, act, max_grid, r.stream);
+                        });
+                        hh = ho; ww = wo; dwb = odb; xsb = oxb; have_dx = true;
                         continue;
                     }
-                }
-                {
-                    F16Range nb;
-                    if (!add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2,
-                                       0, 0, 0, nullptr, 0, nullptr, cbound, &nb))
-                        add_conv(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2);
-                    cbound = nb;
-                }
-                if (i < 2) { hh /= 2; ww /= 2; }
-                cin = ch[i]; cur = out;
-            }
-            if (hh < 1 || ww < 4) return fail(h, NWW_ERR_INVALID, "e2e_dnn input too small for AdaptiveAvgPool2d((1,4))");
-            // AdaptiveAvgPool2d((1,4)) in its exported AvgPool2d form (_export/onnx.py:146-152)
-            const int sh = hh / 1, kh = hh, sw = ww / 4, kw = ww - 3 * sw;
-            int fc_in = cur;                                  // buffer holding [B][256] after the pool
-            if (!fused_pool) {
-                const int pin = cur, pout = cur ^ 1;
-                p.need(pout, 256);
-                p.add("avgpool:export(1,4)", [=](Run& r) { return launch_avgpool(r.buf[pin], r.buf[pout], r.B * 64, hh, ww, kh, kw, sh, sw, 1, 4, r.stream); });
-                fc_in = pout;
-            }
-            const int fc_out = fc_in ^ 1;
-            add_gemm(p, "fc1+bn1", fc_in, fc_out, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, p.W("model.bn1.alpha"), p.W("model.bn1.beta"));
-            set_tail(p, "out", fc_out, 128, p.W("model.out.weight"), p.W("model.out.bias"));
-            break;
-        }
-        case NWW_HEAD_CRNN: {                     // CRNNModel: architectures.py:209-287
-            int cin = 1, hh = T, ww = F, cur = -1;
-            int first = 0;
-            bool seq_written = false;
-            F16Range cbound;                                  // NWW_ARITH_F16X3: range of the current stage's input (empty: unknown)
-            const size_t steps_before = h->plan.size();
-            if (c.n_crnn_channels >= 2 && c.crnn_channels[0] == 16 && c.crnn_channels[1] == 32 &&
-                add_trunk(p, "cnn.0-7", -1, 1, 16, 32, T, F, p.W("model.cnn.0.weight"), p.W("model.cnn.0.bias"), p.W("model.cnn.1.alpha"),
-                          p.W("model.cnn.1.beta"), p.W("model.cnn.4.weight"), p.W("model.cnn.4.bias"), p.W("model.cnn.5.alpha"),
-                          p.W("model.cnn.5.beta"), act, nullptr, F16_FEATURES, &cbound)) {
-                first = 2; cin = 32; hh = T / 4; ww = F / 4; cur = 1;
-            }
-            for (int i = first; i < c.n_crnn_channels; ++i) {
-                const std::string cw = "model.cnn." + std::to_string(4 * i), bnp = "model.cnn." + std::to_string(4 * i + 1);
-                const int out = (i % 2 == 0) ? 0 : 1;
-                // the last conv stage may write the recurrent layers' [W][C * H] sequence layout itself (conv3_x3.hip)
-                bool seq = i == c.n_crnn_channels - 1;
-                // the stage right behind a fused split-operand trunk may take its input from the streaming rings (nww_stream.hip)
-                bool ring = i == 2 && first == 2 && h->plan.size() == steps_before + 1 && h->plan.back().name.rfind("trunk_x3:", 0) == 0 && ((F / 4) % 4) == 0;
-                F16Range nb;
-                const bool mf = add_conv_mfma(p, cw, cur, out, cin, c.crnn_channels[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 1, 0, 0, 0, &seq, 0, &ring, cbound, &nb, 2);      // (scratch: the recurrent layers' xg buffer, idle until they run)
-                cbound = nb;
-                if (!mf) {
-                    ring = false;
-                    seq = false;
-                    add_conv(p, cw, cur, out, cin, c.crnn_channels[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 1);
-                }
-                if (ring) {
-                    h->stream_conv = true; h->stream_H = T; h->stream_W = F;
-                    h->stream_seq = seq && i == c.n_crnn_channels - 1;
-                    h->seq_floats = (size_t)c.crnn_channels[i] * (hh / 2) * (ww / 2);
-                }
-                seq_written = seq;
-                hh /= 2; ww /= 2; cin = c.crnn_channels[i]; cur = out;
-            }
-            if (hh < 1 || ww < 1) return fail(h, NWW_ERR_INVALID, "crnn input too small for the conv stack");
-            const int seq = seq_written ? cur : cur ^ 1, C = cin, Hc = hh, Wc = ww;
-            if (!seq_written) {
-                p.need(seq, (size_t)C * Hc * Wc);
-                p.add("crnn_seq", [=](Run& r) { return launch_crnn_seq(r.buf[cur], r.buf[seq], r.B, C, Hc, Wc, r.stream); });
-            }
-            add_bigru_last(p, "model.rnn", seq, Wc, C * Hc, L, nb, 2, seq ^ 1, 3, 4, c.crnn_rnn_lstm ? 4 : 3);      // seq ^ 1: the free one of buffers 0 / 1
-            set_tail(p, "fc", 4, 2 * L, p.W("model.fc.weight"), p.W("model.fc.bias"));
-            break;
-        }
-        case NWW_HEAD_GRU: {                      // GRUModel: architectures.py:129-145
-            add_bigru_last(p, "model.gru", -1, T, F, L, nb, 2, 0, 1, 4);
-            set_tail(p, "fc", 4, 2 * L, p.W("model.fc.weight"), p.W("model.fc.bias"));
-            break;
-        }
-        case NWW_HEAD_BCRESNET: {                 // BcResNetModel: architectures.py:620-687, channels-last on the GPU
-            // init conv (+BN+act+pool) writes [B][H1][W1][32]; each block: one depthwise kernel emits d = dw3x3(x) and
-            // xs = x at the strided centres, then two MFMA GEMMs over M = B*Ho*Wo pixels:
-            //   R = BN_s(xs . Wsc^T) ;  out = act(BN_1(d . Wpw^T)) + R      (activation BEFORE the residual add, :646-647)
-            const int ic_mfma = nww_knobs().conv_mfma;
-            // init conv fused with block1's depthwise (trunk.hip: the 32-channel planes never reach HBM)
-            const int bc_front = nww_knobs().bc_front;
-            const bool front_fused = ic_mfma && bc_front && conv1_pool_nhwc_mfma_fits(T, F) && conv1_pool_dw_rows(T, F, 2) > 0;
-            // nww_config.act_dtype = NWW_ACT_DTYPE_BF16 / _F16: every activation tensor between the kernels of this head is stored in 16
-            // bits (arithmetic and accumulation stay float32); implemented on the fused front + split-operand block path only.
-            // binary16 (11 significant bits against bf16's 8) stores value x a power of two fixed here from a bound on the tensor
-            // (features within +-NWW_F16_FEATURE_BOUND as in the f16x3 arithmetic; the bound is not allowed to sit more than 2^16 above
-            // the tensor's typical magnitude, and the stores saturate), and a block's weights are two binary16 terms of weight x scale.
-            const int act16 = c.act_dtype;                       // NWW_ACT_DTYPE_* == ACT16_* (split_h2.h)
-            const bool act_bf16 = act16 != NWW_ACT_DTYPE_F32;    // any 16-bit storage
-            const bool act_f16 = act16 == NWW_ACT_DTYPE_F16;
-            if (act_bf16 && !(front_fused && p.h->conv_products == 6))
-                return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = bf16 / f16 needs the fused BcResNet front kernel and a split-operand conv_arith for this input shape");
-            float s_h[4] = {1.f, 1.f, 1.f, 1.f}, s_d[4] = {1.f, 1.f, 1.f, 1.f};     // scales of h_i (block i's output, h_0 = init conv) and d_i
-            DualPackScales dps[4];
-            if (act_f16) {
-                auto cap = [](F16Range r) { return f16_scale(std::fmin(r.bound, r.typ * 65536.0)); };
-                auto dw_range = [&](const float* wt, int C, F16Range in) {      // wt [9][C] tap-major
-                    const auto w = f16_fetch(p.h, wt, (size_t)9 * C);
-                    double worst = 0, typ = 0;
-                    for (int ch = 0; ch < C; ++ch) {
-                        double l1 = 0, l2 = 0;
-                        for (int k = 0; k < 9; ++k) { const double v = w[(size_t)k * C + ch]; l1 += std::fabs(v); l2 += v * v; }
-                        worst = std::fmax(worst, l1); typ += std::sqrt(l2);
-                    }
-                    return F16Range{worst * in.bound, typ / C * in.typ};
-                };
-                const auto hw0 = f16_fetch(p.h, p.W("model.init_conv.0.weight"), 32 * 9);
-                const float *pa0 = p.W("model.init_conv.1.alpha"), *pb0 = p.W("model.init_conv.1.beta");
-                const auto ha0 = f16_fetch(p.h, pa0, 32), hb0 = f16_fetch(p.h, pb0, 32);
-                F16Range rh{f16_layer_bound(hw0, 32, 9, hb0, false, ha0, hb0, pa0 != nullptr, F16_FEATURES.bound),
-                            f16_layer_typ(hw0, 32, 9, ha0, pa0 != nullptr, F16_FEATURES.typ)};
-                s_h[0] = cap(rh);
-                const int chs[4] = {32, 64, 128, 256};
-                for (int i = 1; i <= 3; ++i) {
-                    const std::string q = "model.block" + std::to_string(i);
-                    const int ci = chs[i - 1], co = chs[i];
-                    const F16Range rd = dw_range(p.W(q + ".depthwise.weight_t"), ci, rh);
-                    s_d[i] = cap(rd);
-                    const float *pa1 = p.W(q + ".bn1.alpha"), *pas = p.W(q + ".shortcut.1.alpha");
-                    const auto wpw = f16_fetch(p.h, p.W(q + ".pointwise.weight"), (size_t)co * ci), wsc = f16_fetch(p.h, p.W(q + ".shortcut.0.weight"), (size_t)co * ci);
-                    const auto ha1 = f16_fetch(p.h, pa1, co), hb1 = f16_fetch(p.h, p.W(q + ".bn1.beta"), co);
-                    const auto has = f16_fetch(p.h, pas, co), hbs = f16_fetch(p.h, p.W(q + ".shortcut.1.beta"), co);
-                    dps[i].pw_ws = f16_wscale(wpw); dps[i].sc_ws = f16_wscale(wsc);
-                    if (!(s_d[i] > 0.f && s_h[i - 1] > 0.f && dps[i].pw_ws > 0.f && dps[i].sc_ws > 0.f))
-                        return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = f16: no finite bound on the tensors of block %d", i);
-                    dps[i].pw_un = 1.0f / (dps[i].pw_ws * s_d[i]); dps[i].sc_un = 1.0f / (dps[i].sc_ws * s_h[i - 1]);
-                    const F16Range rpw{f16_layer_bound(wpw, co, ci, hb1, false, ha1, hb1, pa1 != nullptr, rd.bound), f16_layer_typ(wpw, co, ci, ha1, pa1 != nullptr, rd.typ)};
-                    const F16Range rsc{f16_layer_bound(wsc, co, ci, hbs, false, has, hbs, pas != nullptr, rh.bound), f16_layer_typ(wsc, co, ci, has, pas != nullptr, rh.typ)};
-                    rh = F16Range{rpw.bound + rsc.bound, std::hypot(rpw.typ, rsc.typ)};
-                    s_h[i] = cap(rh);
-                }
-            }
-            if (front_fused) {
-                const float *w0 = p.W("model.init_conv.0.weight"), *a0 = p.W("model.init_conv.1.alpha"), *b0 = p.W("model.init_conv.1.beta");
-                const float* dwt1 = p.W("model.block1.depthwise.weight_t");
-                const int ho1 = (T / 2 - 1) / 2 + 1, wo1 = (F / 2 - 1) / 2 + 1;
-                p.need(2, (size_t)32 * ho1 * wo1); p.need(3, (size_t)32 * ho1 * wo1);
-                const int max_grid = p.h->cu_count;
-                // the convolution from split operands on the bf16 matrix cores (trunk_b.hip) under the handle's arithmetic switch;
-                // NWW_BC_FRONT = 2 keeps the float32-MFMA kernel
-                void* fpack = nullptr;
-                int fprod = p.h->conv_products;
-                // under NWW_ARITH_F16X3 (BN present): two binary16 terms per operand, features clamped to +-NWW_F16_FEATURE_BOUND as in the
-                // CNN trunk
-                float fin = 0.0f, fws = 1.0f;
-                if (p.h->f16 && fprod == 6 && a0 && bc_front != 2) {
-                    fin = f16_scale(F16_FEATURES.bound); fws = f16_wscale(f16_fetch(p.h, w0, 32 * 9));
-                    if (fin > 0.0f && fws > 0.0f) fprod = 3;
-                }
-                if ((fprod == 6 || fprod == 9 || fprod == 3) && bc_front != 2 && bc_front_b_rows(T, F, 2) > 0 &&
-                    hipMalloc(&fpack, bc_front_b_packed_bytes()) == hipSuccess) {
-                    const hipError_t pe = fprod == 3 ? launch_bc_front_b_pack_f16(w0, static_cast<unsigned char*>(fpack), fws, p.h->own_stream)
-                                                     : launch_bc_front_b_pack(w0, static_cast<unsigned char*>(fpack), p.h->own_stream);
-                    if (pe == hipSuccess) p.h->packed_weights.push_back(fpack);
-                    else { (void)hipFree(fpack); fpack = nullptr; }
-                }
-                const float f_un = 1.0f / (fin > 0.0f ? fin * fws : 1.0f);
-                // all folded-BN factors non-negative (the usual case: gamma > 0): max-pool commutes with BN + ReLU through the maximum alone
-                int bn_pos = 0;
-                if (a0) {
-                    bn_pos = 1;
-                    for (float v : f16_fetch(p.h, a0, 32)) if (!(v >= 0.0f)) bn_pos = 0;
-                }
-                if (fpack) p.h->clamps_features = true;
-                p.add(std::string(fpack ? "conv1_dw_x3" : "conv1_dw_mfma") + ":init_conv + block1.depthwise (nhwc" + (act_f16 ? ", f16 out)" : act_bf16 ? ", bf16 out)" : ")") + (fpack && fprod == 3 ? " [f16x3]" : ""), [=](Run& r) {
-                    Conv1DwArgs a{src(r, -1), w0, nullptr, a0, b0, dwt1, r.buf[2], r.buf[3], r.B, T, F, act, 2, 2};
-                    a.bf16_out = act16; a.d_scale = s_d[1]; a.xs_scale = s_h[0];
-                    if (fpack) {
-                        a.wpack = static_cast<const unsigned char*>(fpack);
-                        a.f16_in = fin; a.f16_clamp = NWW_F16_FEATURE_BOUND; a.f16_unscale = f_un; a.bn_pos = bn_pos;
-                        return launch_bc_front_b(a, fprod, max_grid, r.stream);
-                    }
-                    return launch_conv1_pool_dw_nhwc(a, max_grid, r.stream);
-                });
-            } else if (ic_mfma && conv1_pool_nhwc_mfma_fits(T, F)) {
-                const float *w0 = p.W("model.init_conv.0.weight"), *a0 = p.W("model.init_conv.1.alpha"), *b0 = p.W("model.init_conv.1.beta");
-                p.need(0, (size_t)32 * (T / 2) * (F / 2));
-                const int max_grid = p.h->cu_count;
-                p.add("conv1_mfma:init_conv(nhwc)", [=](Run& r) {
-                    Conv1NhwcArgs a{src(r, -1), w0, nullptr, a0, b0, r.buf[0], r.B, T, F, act};
-                    return launch_conv1_pool_nhwc_mfma(a, max_grid, r.stream);
-                });
-            } else {
-                add_conv(p, "init_conv(nhwc)", -1, 0, 1, 32, T, F, p.W("model.init_conv.0.weight"), nullptr, p.W("model.init_conv.1.alpha"), p.W("model.init_conv.1.beta"), act, 1, 1);
-            }
-            int hh = T / 2, ww = F / 2, cur = 0;
-            bool mean_fused = false;
-            const int ch[4] = {32, 64, 128, 256};
-            const int st[3][2] = {{2, 2}, {2, 2}, {2, 1}};
-            // d_i / xs_i (depthwise output and strided block input) of the coming block live in buffers dwb / xsb; have_dx: they are
-            // already there - written by the fused front kernel or by the previous block's chained kernel (bc_chain.hip)
-            int dwb = 2, xsb = 3;
-            bool have_dx = front_fused;
-            for (int i = 1; i <= 3; ++i) {
-                const std::string q = "model.block" + std::to_string(i);
-                const int ci = ch[i - 1], co = ch[i], sh = st[i - 1][0], sw = st[i - 1][1];
-                const int ho = (hh - 1) / sh + 1, wo = (ww - 1) / sw + 1;
-                int outb = 4;
-                for (int cand : {0, 1, 4})
-                    if (cand != cur && cand != dwb && cand != xsb) { outb = cand; break; }
-                const int resb = 4;
-                p.need(dwb, (size_t)ci * ho * wo); p.need(xsb, (size_t)ci * ho * wo);
-                const float* dwt = p.W(q + ".depthwise.weight_t");
-                const int hin = hh, win = ww;
-                if (!have_dx)
-                    p.add("dwconv3x3_nhwc:" + q, [=](Run& r) { return launch_dwconv3x3_nhwc(r.buf[cur], dwt, r.buf[dwb], r.buf[xsb], r.B, ci, hin, win, sh, sw, r.stream); });
-                // one dual GEMM per block: shortcut and pointwise products in the same workgroup, no residual round trip
-                {
-                    const float *wpw = p.W(q + ".pointwise.weight"), *a1 = p.W(q + ".bn1.alpha"), *b1 = p.W(q + ".bn1.beta");
-                    const float *wsc = p.W(q + ".shortcut.0.weight"), *as = p.W(q + ".shortcut.1.alpha"), *bs = p.W(q + ".shortcut.1.beta");
-                    const int rows = ho * wo;
-                    p.need(outb, (size_t)rows * co);
-                    // both products from split operands on the bf16 matrix cores (dual_x3.hip) under the same arithmetic switch
-                    void* packed = nullptr;
-                    // float32 activations under NWW_ARITH_F16X3: two binary16 terms per operand, the activation rows scaled per pixel in
-                    // the kernel (DualArgs::h2) - no tensor bound needed
-                    const bool dual_h2 = p.h->f16 && !act_bf16;
-                    // blocks 1 and 2 chained with the next block's depthwise (bc_chain.hip; two-term weights in every storage mode)
-                    const bool will_chain = nww_knobs().bc_chain && i < 3 && have_dx && bc_chain_supported(ci, ho, wo) &&
-                                            (act_f16 || dual_h2 || (act16 == NWW_ACT_DTYPE_BF16 && p.h->f16));
-                    if (dual_h2 || (will_chain && !act_f16)) {
-                        dps[i].pw_ws = f16_wscale(f16_fetch(p.h, wpw, (size_t)co * ci)); dps[i].sc_ws = f16_wscale(f16_fetch(p.h, wsc, (size_t)co * ci));
-                        if (!(dps[i].pw_ws > 0.f && dps[i].sc_ws > 0.f)) return fail(h, NWW_ERR_INVALID, "block %d: non-finite weights", i);
-                        dps[i].pw_un = 1.0f / dps[i].pw_ws; dps[i].sc_un = 1.0f / dps[i].sc_ws;
-                    }
-                    const int terms = act_f16 || dual_h2 || will_chain ? 2 : 3;
-                    if (p.h->conv_products == 6 && dual_x3_supported(ci, co) &&
-                        hipMalloc(&packed, dual_x3_packed_bytes(ci, co, terms)) == hipSuccess) {
-                        if (launch_dual_x3_pack(wpw, wsc, a1, b1, as, bs, packed, ci, co, p.h->own_stream, terms, dps[i]) == hipSuccess) {
-                            p.h->packed_weights.push_back(packed);
-                            // when the block input is in HBM (every block but the one whose depthwise ran inside the fused front kernel) the
-                            // shortcut rows are gathered from it and the depthwise kernel planned just above writes no copy of them
-                            const bool gather = !have_dx;
-                            if (gather) {
-                                const float dw_mul = s_d[i] / s_h[i - 1];
-                                p.pop_last();
-                                p.add("dwconv3x3_nhwc:" + q, [=](Run& r) { return launch_dwconv3x3_nhwc(r.buf[cur], dwt, r.buf[dwb], nullptr, r.B, ci, hin, win, sh, sw, r.stream, act16, dw_mul); });
-                            }
-                            // blocks 1 and 2 chained with the next block's depthwise (bc_chain.hip): the block's output stays in LDS, the
-                            // next block finds its d / xs rows in the other buffer pair
-                            const char* suffix = act_f16 ? " (f16 activations)" : act_bf16 ? " (bf16 activations)" : dual_h2 ? " [f16x3]" : "";
-                            if (will_chain) {
-                                const std::string qn = "model.block" + std::to_string(i + 1);
-                                const float* dwn = p.W(qn + ".depthwise.weight_t");
-                                const int sh2 = st[i][0], sw2 = st[i][1], ho2 = (ho - 1) / sh2 + 1, wo2 = (wo - 1) / sw2 + 1;
-                                const int odb = dwb == 2 ? 0 : 2, oxb = odb + 1, idb = dwb, ixb = xsb;
-                                p.need(odb, (size_t)co * ho2 * wo2); p.need(oxb, (size_t)co * ho2 * wo2);
-                                const float d_mul = s_d[i + 1], xs_mul = s_h[i];
-                                const int max_grid = p.h->cu_count;
-                                p.add("bc_chain:" + q + ".pointwise+bn+act + shortcut+bn -> " + qn + ".depthwise" + suffix, [=](Run& r) {
-                                    ChainArgs a{r.buf[idb], r.buf[ixb], r.buf[odb], r.buf[oxb], static_cast<const unsigned char*>(packed), dwn,
-                                                r.B, ho, wo, sh2, sw2, ho2, wo2};
-                                    a.act16 = act16; a.d_mul = d_mul; a.xs_mul = xs_mul;
-                                    return launch_bc_chain(a, ci, act, max_grid, r.stream);
-                                });
-                                hh = ho; ww = wo; dwb = odb; xsb = oxb; have_dx = true;
-                                continue;
-                            }
-                            // the last block feeds only the global average pool: averaged in the same launch, its output never reaches HBM
-                            const bool fuse_mean = i == 3 && ci == 128 && dual_x3_mean_supported(rows);
-                            if (fuse_mean) { mean_fused = true; p.need(5, 256); }
-                            const float out_mul = fuse_mean ? 1.0f : s_h[i];
-                            p.add(std::string(gather ? "dual_x3(xs gathered):" : "dual_x3:") + q + ".pointwise+bn+act + shortcut+bn" + (fuse_mean ? " + global_avg_pool" : "") + suffix, [=](Run& r) {
-                                DualArgs a{r.buf[dwb], r.buf[xsb], r.buf[outb], static_cast<const unsigned char*>(packed), r.B * rows, co};
-                                if (gather) { a.x = r.buf[cur]; a.H = hin; a.W = win; a.Ho = ho; a.Wo = wo; a.sh = sh; a.sw = sw; }
-                                a.act16 = act16; a.out_mul = out_mul; a.h2 = dual_h2 ? 1 : 0;
-                                if (fuse_mean) { a.mean_out = r.buf[5]; a.mean_P = rows; }
-                                return launch_dual_x3(a, ci, act, r.stream);
-                            });
-                            hh = ho; ww = wo; cur = outb; have_dx = false; dwb = 2; xsb = 3;
-                            continue;
-                        }
-                        (void)hipFree(packed);
-                    }
-                    if (act_bf16) return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = bf16 / f16: block %d has no split-operand kernel (channels %d -> %d)", i, ci, co);
-                    p.add("gemm2:" + q + ".pointwise+bn+act + shortcut+bn", [=](Run& r) {
-                        GemmArgs g;
-                        g.A = r.buf[dwb]; g.lda = ci; g.W = wpw; g.K = ci; g.alpha = a1; g.beta = b1; g.bias = nullptr; g.act = act;
-                        g.A2 = r.buf[xsb]; g.lda2 = ci; g.W2 = wsc; g.K2 = ci; g.alpha2 = as; g.beta2 = bs;
-                        g.C = r.buf[outb]; g.ldc = co; g.M = r.B * rows; g.N = co;
-                        g.res = nullptr; g.ldres = 0; g.rscale = 1.0f;
-                        return launch_gemm(g, r.stream);
+                    // the last block feeds only the global average pool: averaged in the same launch, its output never reaches HBM
+                    const bool fuse_mean = i == 3 && ci == 128 && dual_x3_mean_supported(rows);
+                    if (fuse_mean) { mean_fused = true; p.need(5, 256); }
+                    const float out_mul = fuse_mean ? 1.0f : s_h[i];
+                    p.add(std::string(gather ? "dual_x3(xs gathered):" : "dual_x3:") + q + ".pointwise+bn+act + shortcut+bn" + (fuse_mean ? " + global_avg_pool" : "") + suffix, [=](Run& r) {
+                        DualArgs a{r.buf[dwb], r.buf[xsb], r.buf[outb], static_cast<const unsigned char*>(packed), r.B * rows, co};
+                        if (gather) { a.x = r.buf[cur]; a.H = hin; a.W = win; a.Ho = ho; a.Wo = wo; a.sh = sh; a.sw = sw; }
+                        a.act16 = act16; a.out_mul = out_mul; a.h2 = dual_h2 ? 1 : 0;
+                        if (fuse_mean) { a.mean_out = r.buf[5]; a.mean_P = rows; }
+                        return launch_dual_x3(a, ci, act, r.stream);
                     });
-                    (void)resb;
+                    hh = ho; ww = wo; cur = outb; have_dx = false; dwb = 2; xsb = 3;
+                    continue;
                 }
-                hh = ho; ww = wo; cur = outb; have_dx = false; dwb = 2; xsb = 3;
+                (void)hipFree(packed);
             }
-            const int hw = hh * ww;
-            if (mean_fused) {
-                set_tail(p, "fc", 5, 256, p.W("model.fc.weight"), p.W("model.fc.bias"));
-                break;
+            if (act_bf16) return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = bf16 / f16: block %d has no split-operand kernel (channels %d -> %d)", i, ci, co);
+            p.add("gemm2:" + q + ".pointwise+bn+act + shortcut+bn", [=](Run& r) {
+                GemmArgs g;
+                g.A = r.buf[dwb]; g.lda = ci; g.W = wpw; g.K = ci; g.alpha = a1; g.beta = b1; g.bias = nullptr; g.act = act;
+                g.A2 = r.buf[xsb]; g.lda2 = ci; g.W2 = wsc; g.K2 = ci; g.alpha2 = as; g.beta2 = bs;
+                g.C = r.buf[outb]; g.ldc = co; g.M = r.B * rows; g.N = co;
+                g.res = nullptr; g.ldres = 0; g.rscale = 1.0f;
+                return launch_gemm(g, r.stream);
+            });
             }
-            p.need(2, 256);
-            const float mean_un = act_f16 ? 1.0f / s_h[3] : 1.0f;
-            p.add("mean:global_avg_pool", [=](Run& r) { return launch_mean_mid(r.buf[cur], r.buf[2], r.B, hw, 256, r.stream, act16, mean_un); });
-            set_tail(p, "fc", 2, 256, p.W("model.fc.weight"), p.W("model.fc.bias"));
-            break;
-        }
-        case NWW_HEAD_CONFORMER: {                // ConformerModel: architectures.py:441-543
-            const int D = c.conformer_d_model, NH = c.conformer_n_head;
-            const int hb = 0, t1 = 1, t3 = 2, big = 3;      // h, LN/glu/attn scratch, dwconv scratch, wide scratch
-            bool last_fused = false;
-            p.need(t1, (size_t)T * D); p.need(t3, (size_t)T * D);
-            p.need(hb, (size_t)T * D);
-            // round 6: the row-local Linears next to a feed-forward module run INSIDE its launch (FfnArgs::px: input_proj in front of the first
-            // block's ff1, conv2 + residual in front of every ff2), and the last block's LayerNorm + time average behind its ff2
-            // (FfnArgs::msum); NWW_FFN_FUSED = 0 and the other arithmetics keep the separate launches.
-            // A feed-forward step takes one of four forms, richest first: prologue + epilogue, prologue, plain ffn_x3, unfused (LayerNorm +
-            // two GEMMs).  pro: 0 none, 1 input_proj (x = the head input), 2 conv_module.conv2 + residual (x = the depthwise output in t3);
-            // epi: the block's final LayerNorm + mean over time.
-            struct FfnForm {
-                int pro = 0;
-                bool epi = false, fused = false, h2 = false;
-                float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f, pws = 0.0f, mscale = 0.0f;
-            };
-            for (int i = 0; i < nb; ++i) {
-                const std::string q = "model.conformer_blocks." + std::to_string(i);
-                const float* pro_w[3] = {nullptr, p.W("model.input_proj.weight"), p.W(q + ".conv_module.conv2.weight")};
-                const float* pro_b[3] = {nullptr, p.W("model.input_proj.bias"), p.W(q + ".conv_module.conv2.bias")};
-                const int pro_k[3] = {0, F, D};
-                const float *l2w = p.W(q + ".layer_norm.weight"), *l2b = p.W(q + ".layer_norm.bias");
-                // the richest feasible form with at most the requested prologue / epilogue: plan-time scales only, nothing allocated or launched
-                auto ffn_decide = [&](const std::string& ff, int pro, bool epi) {
-                    FfnForm f;
-                    // LayerNorm + linear1 + swish + linear2 + half-step residual in one kernel (ffn_x3.hip); same arithmetic
-                    // switch as the split-operand GEMMs it replaces
-                    if (!(nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16))) return f;
-                    // NWW_ARITH_F16X3: both operands of both products are bounded whatever the residual stream holds -
-                    // |LayerNorm(h)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v| - so the scales need nothing but the weights
-                    if (p.h->f16) {
-                        const auto hlw = f16_fetch(p.h, p.W(q + ff + ".layer_norm.weight"), D), hlb = f16_fetch(p.h, p.W(q + ff + ".layer_norm.bias"), D);
-                        double bx = 0.0;
-                        for (int k = 0; k < D; ++k) bx = std::fmax(bx, std::sqrt((double)D) * std::fabs((double)hlw[k]) + std::fabs((double)hlb[k]));
-                        const auto w1 = f16_fetch(p.h, p.W(q + ff + ".linear1.weight"), (size_t)4 * D * D), w2 = f16_fetch(p.h, p.W(q + ff + ".linear2.weight"), (size_t)4 * D * D);
-                        const auto b1 = f16_fetch(p.h, p.W(q + ff + ".linear1.bias"), (size_t)4 * D);
-                        const double bh = f16_layer_bound(w1, 4 * D, D, b1, true, b1, b1, false, bx);
-                        f.fx = f16_scale(bx); f.fw1 = f16_wscale(w1); f.fh = f16_scale(bh); f.fw2 = f16_wscale(w2);
-                    }
-                    f.h2 = f.fx > 0.0f && f.fw1 > 0.0f && f.fh > 0.0f && f.fw2 > 0.0f;
-                    f.fused = ffn_x3_supported(D, f.h2);
-                    if (!f.fused || !f.h2) return f;                   // the prologue / epilogue instances: two-term form only
-                    // the prologue Linear's weights (two binary16 terms; its input rows are scaled per row in the kernel)
-                    if (pro && ffn_x3_pro_supported(D, pro_k[pro]) && pro_b[pro]) {
-                        f.pws = f16_wscale(f16_fetch(p.h, pro_w[pro], (size_t)D * pro_k[pro]));
-                        if (f.pws > 0.0f) f.pro = pro;
-                    }
-                    if (epi && f.pro == pro && ffn_x3_epi_supported(D, T)) {
-                        const auto h2w = f16_fetch(p.h, l2w, D), h2b = f16_fetch(p.h, l2b, D);
-                        double by = 0.0;
-                        for (int k = 0; k < D; ++k) by = std::fmax(by, std::sqrt((double)D) * std::fabs((double)h2w[k]) + std::fabs((double)h2b[k]));
-                        f.mscale = by < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(by, 1e-30)) : 0.0f;      // |LayerNorm| x scale <= 2^36
-                        f.epi = f.mscale > 0.0f && std::isfinite(f.mscale);
-                    }
-                    return f;
-                };
-                // allocates, packs and plans form f; false (an allocation or a pack failed): nothing planned, nothing kept
-                auto ffn_build = [&](const std::string& ff, const FfnForm& f) -> bool {
-                    const float *lw = p.W(q + ff + ".layer_norm.weight"), *lb = p.W(q + ff + ".layer_norm.bias");
-                    if (!f.fused) {
-                        p.add("layernorm:" + q + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-                        add_gemm(p, q + ff + ".linear1+swish", t1, big, T, 4 * D, D, p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), ACT_SILU);
-                        add_gemm(p, q + ff + ".linear2+0.5res", big, hb, T, D, 4 * D, p.W(q + ff + ".linear2.weight"), p.W(q + ff + ".linear2.bias"), ACT_NONE, nullptr, nullptr, hb, 0.5f);
-                        return true;
-                    }
-                    const int pro = f.pro, pk = pro_k[pro];
-                    void *packed = nullptr, *ppk = nullptr;
-                    if ((pro && (hipMalloc(&ppk, ffn_x3_pro_tile_bytes(pk) * ((D + 31) / 32)) != hipSuccess ||
-                                 launch_ffn_x3_pro_pack(pro_w[pro], ppk, D, pk, f.pws, p.h->own_stream) != hipSuccess)) ||
-                        hipMalloc(&packed, ffn_x3_packed_bytes(D)) != hipSuccess ||
-                        launch_ffn_x3_pack(p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), p.W(q + ff + ".linear2.weight"), packed, D,
-                                           p.h->own_stream, f.h2 ? f.fw1 : 0.0f, f.h2 ? f.fw2 : 0.0f, pro ? 1 : 0) != hipSuccess) {
-                        if (packed) (void)hipFree(packed);
-                        if (ppk) (void)hipFree(ppk);
-                        return false;
-                    }
-                    p.h->packed_weights.push_back(packed);
-                    if (ppk) p.h->packed_weights.push_back(ppk);
-                    const float* b2 = p.W(q + ff + ".linear2.bias");
-                    const float* pbias = pro_b[pro];
-                    const float p_un = pro ? 1.0f / f.pws : 1.0f;
-                    const bool epi = f.epi;
-                    // the epilogue's exact partial sums: per 32-row tile two segments x two planes of D floats (the idle wide scratch buffer)
-                    if (epi) p.need(big, (size_t)((T + 31) / 32 + 1) * 4 * D + (size_t)16 * D);
-                    const std::string what = std::string(pro == 1 ? "input_proj+" : pro == 2 ? "conv2(pw)+res+" : "") + "ln+linear1+swish+linear2+0.5res" + (epi ? "+layernorm+time sums" : "");
-                    p.add("ffn_x3:" + q + ff + " (" + what + ")" + (f.h2 ? " [f16x3]" : ""), [=](Run& r) {
-                        FfnArgs a{r.buf[hb], lw, lb, static_cast<const unsigned char*>(packed), b2, r.B * T, 0.5f};
-                        if (f.h2) { a.h2_x = f.fx; a.h2_w1 = f.fw1; a.h2_h = f.fh; a.h2_w2 = f.fw2; }
-                        if (pro) {
-                            a.px = pro == 1 ? r.x : r.buf[t3]; a.ppacked = static_cast<const unsigned char*>(ppk); a.pb = pbias;
-                            a.pro_k = pk; a.pro_res = pro == 2 ? 1 : 0; a.p_un = p_un;
-                        }
-                        if (epi) { a.ln2_w = l2w; a.ln2_b = l2b; a.msum = r.buf[big]; a.T = T; a.m_scale = f.mscale; }
-                        return launch_ffn_x3(a, D, r.stream);
-                    });
-                    if (epi)
-                        p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
-                            return launch_ffn_x3_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, f.mscale, r.stream);
-                        });
-                    return true;
-                };
-                // the richest form that can be built, one form down after each failed build; separate_pro plans the prologue Linear on its
-                // own when the form planned does not take it.  Returns whether the epilogue was fused.
-                auto ffn = [&](const std::string& ff, int pro, bool epi, const auto& separate_pro) {
-                    FfnForm f = ffn_decide(ff, pro, epi);
-                    if (pro && !f.pro) separate_pro();
-                    while (!ffn_build(ff, f)) {
-                        if (f.epi) f.epi = false;
-                        else if (f.pro) { f.pro = 0; separate_pro(); }
-                        else f.fused = false;
-                    }
-                    return f.epi;
-                };
-                ffn(".ff1", i == 0 ? 1 : 0, false, [&] {
-                    if (!add_lin_x3(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 0))
-                        add_gemm(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
+        hh = ho; ww = wo; cur = outb; have_dx = false; dwb = 2; xsb = 3;
+    }
+    const int hw = hh * ww;
+    if (mean_fused) {
+        set_tail(p, "fc", 5, 256, p.W("model.fc.weight"), p.W("model.fc.bias"));
+        return NWW_OK;
+    }
+    p.need(2, 256);
+    const float mean_un = act_f16 ? 1.0f / s_h[3] : 1.0f;
+    p.add("mean:global_avg_pool", [=](Run& r) { return launch_mean_mid(r.buf[cur], r.buf[2], r.B, hw, 256, r.stream, act16, mean_un); });
+    set_tail(p, "fc", 2, 256, p.W("model.fc.weight"), p.W("model.fc.bias"));
+    return NWW_OK;
+}
+
+int plan_conformer(PlanCtx& p) {                    // ConformerModel: architectures.py:441-543
+    const nww_config& c = p.h->cfg;
+    const int T = c.in_rows, F = c.in_cols, nb = c.n_blocks;
+    const int D = c.conformer_d_model, NH = c.conformer_n_head;
+    const int hb = 0, t1 = 1, t3 = 2, big = 3;      // h, LN/glu/attn scratch, dwconv scratch, wide scratch
+    bool last_fused = false;
+    p.need(t1, (size_t)T * D); p.need(t3, (size_t)T * D);
+    p.need(hb, (size_t)T * D);
+    // round 6: the row-local Linears next to a feed-forward module run INSIDE its launch (FfnArgs::px: input_proj in front of the first
+    // block's ff1, conv2 + residual in front of every ff2), and the last block's LayerNorm + time average behind its ff2
+    // (FfnArgs::msum); NWW_FFN_FUSED = 0 and the other arithmetics keep the separate launches.
+    // A feed-forward step takes one of four forms, richest first: prologue + epilogue, prologue, plain ffn_x3, unfused (LayerNorm +
+    // two GEMMs).  pro: 0 none, 1 input_proj (x = the head input), 2 conv_module.conv2 + residual (x = the depthwise output in t3);
+    // epi: the block's final LayerNorm + mean over time.
+    struct FfnForm {
+        int pro = 0;
+        bool epi = false, fused = false, h2 = false;
+        float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f, pws = 0.0f, mscale = 0.0f;
+    };
+    for (int i = 0; i < nb; ++i) {
+        const std::string q = "model.conformer_blocks." + std::to_string(i);
+        const float* pro_w[3] = {nullptr, p.W("model.input_proj.weight"), p.W(q + ".conv_module.conv2.weight")};
+        const float* pro_b[3] = {nullptr, p.W("model.input_proj.bias"), p.W(q + ".conv_module.conv2.bias")};
+        const int pro_k[3] = {0, F, D};
+        const float *l2w = p.W(q + ".layer_norm.weight"), *l2b = p.W(q + ".layer_norm.bias");
+        // the richest feasible form with at most the requested prologue / epilogue: plan-time scales only, nothing allocated or launched
+        auto ffn_decide = [&](const std::string& ff, int pro, bool epi) {
+            FfnForm f;
+            // LayerNorm + linear1 + swish + linear2 + half-step residual in one kernel (ffn_x3.hip); same arithmetic
+            // switch as the split-operand GEMMs it replaces
+            if (!(nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16))) return f;
+            // NWW_ARITH_F16X3: both operands of both products are bounded whatever the residual stream holds -
+            // |LayerNorm(h)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v| - so the scales need nothing but the weights
+            if (p.h->f16) {
+                const double bx = f16_ln_bound(p.h, p.W(q + ff + ".layer_norm.weight"), p.W(q + ff + ".layer_norm.bias"), D);
+                const auto w1 = f16_fetch(p.h, p.W(q + ff + ".linear1.weight"), (size_t)4 * D * D), w2 = f16_fetch(p.h, p.W(q + ff + ".linear2.weight"), (size_t)4 * D * D);
+                const auto b1 = f16_fetch(p.h, p.W(q + ff + ".linear1.bias"), (size_t)4 * D);
+                const double bh = f16_layer_bound(w1, 4 * D, D, b1, true, b1, b1, false, bx);
+                f.fx = f16_scale(bx); f.fw1 = f16_wscale(w1); f.fh = f16_scale(bh); f.fw2 = f16_wscale(w2);
+            }
+            f.h2 = f.fx > 0.0f && f.fw1 > 0.0f && f.fh > 0.0f && f.fw2 > 0.0f;
+            f.fused = ffn_x3_supported(D, f.h2);
+            if (!f.fused || !f.h2) return f;                   // the prologue / epilogue instances: two-term form only
+            // the prologue Linear's weights (two binary16 terms; its input rows are scaled per row in the kernel)
+            if (pro && ffn_x3_pro_supported(D, pro_k[pro]) && pro_b[pro]) {
+                f.pws = f16_wscale(f16_fetch(p.h, pro_w[pro], (size_t)D * pro_k[pro]));
+                if (f.pws > 0.0f) f.pro = pro;
+            }
+            if (epi && f.pro == pro && ffn_x3_epi_supported(D, T)) {
+                f.mscale = f16_mean_scale(f16_ln_bound(p.h, l2w, l2b, D));
+                f.epi = f.mscale > 0.0f;
+            }
+            return f;
+        };
+        // allocates, packs and plans form f; false (an allocation or a pack failed): nothing planned, nothing kept
+        auto ffn_build = [&](const std::string& ff, const FfnForm& f) -> bool {
+            const float *lw = p.W(q + ff + ".layer_norm.weight"), *lb = p.W(q + ff + ".layer_norm.bias");
+            if (!f.fused) {
+                p.add("layernorm:" + q + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
+                add_gemm(p, q + ff + ".linear1+swish", t1, big, T, 4 * D, D, p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), ACT_SILU);
+                add_gemm(p, q + ff + ".linear2+0.5res", big, hb, T, D, 4 * D, p.W(q + ff + ".linear2.weight"), p.W(q + ff + ".linear2.bias"), ACT_NONE, nullptr, nullptr, hb, 0.5f);
+                return true;
+            }
+            const int pro = f.pro, pk = pro_k[pro];
+            void *packed = nullptr, *ppk = nullptr;
+            if ((pro && (hipMalloc(&ppk, ffn_x3_pro_tile_bytes(pk) * ((D + 31) / 32)) != hipSuccess ||
+                         launch_ffn_x3_pro_pack(pro_w[pro], ppk, D, pk, f.pws, p.h->own_stream) != hipSuccess)) ||
+                hipMalloc(&packed, ffn_x3_packed_bytes(D)) != hipSuccess ||
+                launch_ffn_x3_pack(p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), p.W(q + ff + ".linear2.weight"), packed, D,
+                                   p.h->own_stream, f.h2 ? f.fw1 : 0.0f, f.h2 ? f.fw2 : 0.0f, pro ? 1 : 0) != hipSuccess) {
+                if (packed) (void)hipFree(packed);
+                if (ppk) (void)hipFree(ppk);
+                return false;
+            }
+            p.h->packed_weights.push_back(packed);
+            if (ppk) p.h->packed_weights.push_back(ppk);
+            const float* b2 = p.W(q + ff + ".linear2.bias");
+            const float* pbias = pro_b[pro];
+            const float p_un = pro ? 1.0f / f.pws : 1.0f;
+            const bool epi = f.epi;
+            // the epilogue's exact partial sums: per 32-row tile two segments x two planes of D floats (the idle wide scratch buffer)
+            if (epi) p.need(big, (size_t)((T + 31) / 32 + 1) * 4 * D + (size_t)16 * D);
+            const std::string what = std::string(pro == 1 ? "input_proj+" : pro == 2 ? "conv2(pw)+res+" : "") + "ln+linear1+swish+linear2+0.5res" + (epi ? "+layernorm+time sums" : "");
+            p.add("ffn_x3:" + q + ff + " (" + what + ")" + (f.h2 ? " [f16x3]" : ""), [=](Run& r) {
+                FfnArgs a{r.buf[hb], lw, lb, static_cast<const unsigned char*>(packed), b2, r.B * T, 0.5f};
+                if (f.h2) { a.h2_x = f.fx; a.h2_w1 = f.fw1; a.h2_h = f.fh; a.h2_w2 = f.fw2; }
+                if (pro) {
+                    a.px = pro == 1 ? r.x : r.buf[t3]; a.ppacked = static_cast<const unsigned char*>(ppk); a.pb = pbias;
+                    a.pro_k = pk; a.pro_res = pro == 2 ? 1 : 0; a.p_un = p_un;
+                }
+                if (epi) { a.ln2_w = l2w; a.ln2_b = l2b; a.msum = r.buf[big]; a.T = T; a.m_scale = f.mscale; }
+                return launch_ffn_x3(a, D, r.stream);
+            });
+            if (epi)
+                p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
+                    return launch_ffn_x3_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, f.mscale, r.stream);
                 });
-                // the whole attention module (in_proj, per-head softmax(q k^T) v, out_proj, residual) in one launch per clip-resident
-                // workgroup (attn_x3.hip) under the default arithmetic at the compiled shape; NWW_ATTN_FUSED=0: the three launches below
-                bool attn_done = false;
-                if (nww_knobs().attn_fused && p.h->f16 && p.h->conv_products == 6 && attn_x3_supported(T, D, NH)) {
-                    const float *iw = p.W(q + ".attention.in_proj_weight"), *ib = p.W(q + ".attention.in_proj_bias");
-                    const float *ow = p.W(q + ".attention.out_proj.weight"), *ob = p.W(q + ".attention.out_proj.bias");
-                    const auto hiw = f16_fetch(p.h, iw, (size_t)3 * D * D), how = f16_fetch(p.h, ow, (size_t)D * D);
-                    const float ws_in = f16_wscale(hiw), ws_out = f16_wscale(how);
-                    // |raw k / v accumulator| <= 2^15 (the clip-scaled rows) x the L1 norm of the scaled weight row: powers of two that keep them below 2^15
-                    auto l1max = [&](int r0) {
-                        double worst = 0;
-                        for (int r = r0; r < r0 + D; ++r) {
-                            double t = 0;
-                            for (int k = 0; k < D; ++k) t += std::fabs((double)hiw[(size_t)r * D + k]);
-                            worst = std::fmax(worst, t);
-                        }
-                        return worst;
-                    };
-                    const double lk = l1max(D) * ws_in * 1.02, lv = l1max(2 * D) * ws_in * 1.02;
-                    void *packed = nullptr, *bc = nullptr;
-                    if (ws_in > 0.0f && ws_out > 0.0f && lk < 1e30 && lv < 1e30 &&
-                        hipMalloc(&packed, attn_x3_packed_bytes(D, NH)) == hipSuccess && hipMalloc(&bc, (size_t)D * sizeof(float)) == hipSuccess &&
-                        launch_attn_x3_pack(iw, ib, ow, ob, packed, static_cast<float*>(bc), D, NH, ws_in, ws_out, p.h->own_stream) == hipSuccess) {
-                        p.h->packed_weights.push_back(packed);
-                        p.h->packed_weights.push_back(bc);
-                        const float cK = lk > 1e-30 ? (float)f16_pow2_floor(1.0 / lk) : 1.0f, cV = lv > 1e-30 ? (float)f16_pow2_floor(1.0 / lv) : 1.0f;
-                        const float w_un = 1.0f / ws_in, o_un = 1.0f / (ws_out * ws_in * cV), qs = 1.0f / std::sqrt((float)(D / NH));
-                        p.add("attn_x3:" + q + ".attention (in_proj+softmax(qk)v+out_proj+res) [f16x3]", [=](Run& r) {
-                            AttnArgs a{r.buf[hb], r.buf[hb], static_cast<const unsigned char*>(packed), static_cast<const float*>(bc), r.B, T, w_un, cK, cV, o_un, qs};
-                            return launch_attn_x3(a, D, NH, r.stream);
-                        });
-                        attn_done = true;
-                    } else {
-                        if (packed) (void)hipFree(packed);
-                        if (bc) (void)hipFree(bc);
-                    }
-                }
-                if (!attn_done) {
-                // in_proj writes q, k, v head-major when the matrix-core attention consumes them: every (clip, head) block is then
-                // one contiguous run for its LDS-DMA
-                const int mha_mfma = nww_knobs().mha_mfma;
-                const bool want_hm = mha_mfma && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
-                bool head_major = false;
-                if (add_lin_x3(p, q + (want_hm ? ".attention.in_proj(head-major)" : ".attention.in_proj"), hb, big, T, 3 * D, D, p.W(q + ".attention.in_proj_weight"), p.W(q + ".attention.in_proj_bias"), 0,
-                               99, 1.f, nullptr, nullptr, want_hm ? T : 0, want_hm ? D / NH : 0))
-                    head_major = want_hm;
-                else
-                    add_gemm(p, q + ".attention.in_proj", hb, big, T, 3 * D, D, p.W(q + ".attention.in_proj_weight"), p.W(q + ".attention.in_proj_bias"), ACT_NONE);
-                if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
-                    p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0); });
-                else if (mha_mfma && mha_mfma_supported(T, D, NH))
-                    p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0); });
-                else
-                    p.add("mha_core:" + q, [=](Run& r) { return launch_mha_core(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream); });
-                if (!add_lin_x3(p, q + ".attention.out_proj+res", t1, hb, T, D, D, p.W(q + ".attention.out_proj.weight"), p.W(q + ".attention.out_proj.bias"), 1, hb, 1.0f))
-                    add_gemm(p, q + ".attention.out_proj+res", t1, hb, T, D, D, p.W(q + ".attention.out_proj.weight"), p.W(q + ".attention.out_proj.bias"), ACT_NONE, nullptr, nullptr, hb, 1.0f);
-                }
-                {
-                    const std::string m = q + ".conv_module";
-                    const float *lw = p.W(m + ".layer_norm.weight"), *lb = p.W(m + ".layer_norm.bias");
-                    const float *dw = p.W(m + ".depthwise_conv.weight"), *db = p.W(m + ".depthwise_conv.bias");
-                    const float *ba = p.W(m + ".batch_norm.alpha"), *bb = p.W(m + ".batch_norm.beta");
-                    // (the whole module as ONE clip-resident launch was built and measured: bit-identical, 0.27 ms against 0.25 for the three launches
-                    // below - tools/ubench/convmod_x3.hip)
-                    {
-                    // LayerNorm + pointwise conv1 + GLU in one launch (lin_x3.hip), else the three separate ones
-                    if (!add_lin_x3(p, m + ".layer_norm+conv1(pw)+glu", hb, t1, T, D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), 2, 99, 1.f, lw, lb)) {
-                        p.add("layernorm:" + m, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-                        add_gemm(p, m + ".conv1(pw)", t1, big, T, 2 * D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), ACT_NONE);
-                        p.add("glu:" + m, [=](Run& r) { return launch_glu(r.buf[big], r.buf[t1], r.B * T, D, r.stream); });
-                    }
-                    p.add("dwconv1d+bn+swish:" + m, [=](Run& r) { return launch_dwconv1d_bn_swish(r.buf[t1], dw, db, ba, bb, r.buf[t3], r.B, T, D, 31, r.stream); });
-                    }
-                }
-                // conv2 + residual inside ff2's launch, and behind the LAST block's ff2 its LayerNorm + the sums of the time average
-                if (ffn(".ff2", 2, i == nb - 1, [&] {
-                        const std::string m = q + ".conv_module";
-                        if (!add_lin_x3(p, m + ".conv2(pw)+res", t3, hb, T, D, D, p.W(m + ".conv2.weight"), p.W(m + ".conv2.bias"), 1, hb, 1.0f))
-                            add_gemm(p, m + ".conv2(pw)+res", t3, hb, T, D, D, p.W(m + ".conv2.weight"), p.W(m + ".conv2.bias"), ACT_NONE, nullptr, nullptr, hb, 1.0f);
-                    }))
-                    last_fused = true;
-                const float *lw = p.W(q + ".layer_norm.weight"), *lb = p.W(q + ".layer_norm.bias");
-                // the last block's LayerNorm feeds only the mean over time: one pass for both
-                if (last_fused) {
-                } else if (i == nb - 1 && D <= 256) {
-                    p.add("layernorm+mean:" + q + " + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], lw, lb, r.B, T, D, r.stream); });
-                    last_fused = true;
-                } else {
-                    p.add("layernorm:" + q, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-                }
+            return true;
+        };
+        // the richest form that can be built, one form down after each failed build; separate_pro plans the prologue Linear on its
+        // own when the form planned does not take it.  Returns whether the epilogue was fused.
+        auto ffn = [&](const std::string& ff, int pro, bool epi, const auto& separate_pro) {
+            FfnForm f = ffn_decide(ff, pro, epi);
+            if (pro && !f.pro) separate_pro();
+            while (!ffn_build(ff, f)) {
+                if (f.epi) f.epi = false;
+                else if (f.pro) { f.pro = 0; separate_pro(); }
+                else f.fused = false;
             }
-            if (!last_fused) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
-            set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
-            break;
+            return f.epi;
+        };
+        ffn(".ff1", i == 0 ? 1 : 0, false, [&] { add_linear(p, "input_proj", -1, hb, T, D, F, pro_w[1], pro_b[1]); });
+        // the attention module in one launch where attn_x3 takes it, else in three
+        if (!add_attn_x3(p, q, hb, T, D, NH)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0);
+        const std::string m = q + ".conv_module";
+        const float *lw = p.W(m + ".layer_norm.weight"), *lb = p.W(m + ".layer_norm.bias");
+        const float *dw = p.W(m + ".depthwise_conv.weight"), *db = p.W(m + ".depthwise_conv.bias");
+        const float *ba = p.W(m + ".batch_norm.alpha"), *bb = p.W(m + ".batch_norm.beta");
+        // (the whole module as ONE clip-resident launch was built and measured: bit-identical, 0.27 ms against 0.25 for the three launches
+        // below - tools/ubench/convmod_x3.hip)
+        // LayerNorm + pointwise conv1 + GLU in one launch (lin_x3.hip), else the three separate ones
+        if (!add_lin_x3(p, m + ".layer_norm+conv1(pw)+glu", hb, t1, T, D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), 2, 99, 1.f, lw, lb)) {
+            p.add("layernorm:" + m, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
+            add_gemm(p, m + ".conv1(pw)", t1, big, T, 2 * D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), ACT_NONE);
+            p.add("glu:" + m, [=](Run& r) { return launch_glu(r.buf[big], r.buf[t1], r.B * T, D, r.stream); });
         }
-        case NWW_HEAD_TRANSFORMER: {              // TransformerModel: architectures.py:164-206, nn.TransformerEncoderLayer defaults (post-norm, ReLU)
-            const int D = c.conformer_d_model, NH = c.conformer_n_head;
-            const int hb = 0, t1 = 1, big = 3;              // h, attention output / time mean, qkv / hidden / time sums
-            if (T > NWW_PE_MAX_LEN) return fail(h, NWW_ERR_UNSUPPORTED, "transformer: %d time steps exceed the positional table (%d rows)", T, NWW_PE_MAX_LEN);
-            p.need(hb, (size_t)T * D); p.need(t1, (size_t)T * D);
-            const float* pe = p.W("model.pos_encoder.pe");
-            const float xs = std::sqrt((float)D);          // math.sqrt(d_model), applied in float32 as torch does
-            // x = input_proj(x) sqrt(D) + pe[t]: the scale and the positional row in the short-K Linear's epilogue (lin_x3 epilogue 3), its
-            // input rows scaled per row (no clamp of the features); else the general GEMM and one elementwise pass
-            if (!add_lin_x3(p, "input_proj*sqrt(d)+pe", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 3, 99, xs, nullptr, nullptr, T, 0, pe)) {
-                add_gemm(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
-                p.add("scale+pe:input_proj", [=](Run& r) { return launch_scale_add_pe(r.buf[hb], pe, r.B, T, D, xs, r.stream); });
-            }
-            bool mean_done = false;
-            for (int i = 0; i < nb; ++i) {
-                const std::string q = "model.transformer_encoder.layers." + std::to_string(i);
-                const bool last = i == nb - 1;
-                // ---- h <- h + self_attn(h): head-major in_proj, the attention core, out_proj + residual (as the Conformer's attention module)
-                const int mha_mfma = nww_knobs().mha_mfma;
-                const bool want_hm = mha_mfma && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
-                bool head_major = false;
-                if (add_lin_x3(p, q + (want_hm ? ".self_attn.in_proj(head-major)" : ".self_attn.in_proj"), hb, big, T, 3 * D, D, p.W(q + ".self_attn.in_proj_weight"),
-                               p.W(q + ".self_attn.in_proj_bias"), 0, 99, 1.f, nullptr, nullptr, want_hm ? T : 0, want_hm ? D / NH : 0))
-                    head_major = want_hm;
-                else
-                    add_gemm(p, q + ".self_attn.in_proj", hb, big, T, 3 * D, D, p.W(q + ".self_attn.in_proj_weight"), p.W(q + ".self_attn.in_proj_bias"), ACT_NONE);
-                if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
-                    p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0, 1); });
-                else if (mha_mfma && mha_mfma_supported(T, D, NH))
-                    p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream, head_major ? 1 : 0); });
-                else
-                    p.add("mha_core:" + q, [=](Run& r) { return launch_mha_core(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream); });
-                if (!add_lin_x3(p, q + ".self_attn.out_proj+res", t1, hb, T, D, D, p.W(q + ".self_attn.out_proj.weight"), p.W(q + ".self_attn.out_proj.bias"), 1, hb, 1.0f))
-                    add_gemm(p, q + ".self_attn.out_proj+res", t1, hb, T, D, D, p.W(q + ".self_attn.out_proj.weight"), p.W(q + ".self_attn.out_proj.bias"), ACT_NONE, nullptr, nullptr, hb, 1.0f);
-                // ---- h <- norm2(y + linear2(relu(linear1(y)))), y = norm1(h): one launch (ffn_x3 post-norm instance); the last layer's norm2 feeds
-                // only the time mean: exact per-tile sums instead of the store
-                const float *n1w = p.W(q + ".norm1.weight"), *n1b = p.W(q + ".norm1.bias"), *n2w = p.W(q + ".norm2.weight"), *n2b = p.W(q + ".norm2.bias");
-                const float *w1 = p.W(q + ".linear1.weight"), *b1 = p.W(q + ".linear1.bias"), *w2 = p.W(q + ".linear2.weight"), *b2 = p.W(q + ".linear2.bias");
-                bool fused = false;
-                if (nww_knobs().ffn_fused && p.h->f16 && p.h->conv_products == 6 && ffn_x3_post_supported(D)) {
-                    // |norm1(h)_i| <= sqrt(D) |w_i| + |b_i| whatever h holds; relu(v) <= |v|: the scales need nothing but the weights
-                    auto ln_bound = [&](const float* w, const float* b) {
-                        const auto hw = f16_fetch(p.h, w, D), hbv = f16_fetch(p.h, b, D);
-                        double bx = 0.0;
-                        for (int k = 0; k < D; ++k) bx = std::fmax(bx, std::sqrt((double)D) * std::fabs((double)hw[k]) + std::fabs((double)hbv[k]));
-                        return bx;
-                    };
-                    const double bx = ln_bound(n1w, n1b);
-                    const auto hw1 = f16_fetch(p.h, w1, (size_t)4 * D * D), hw2 = f16_fetch(p.h, w2, (size_t)4 * D * D), hb1 = f16_fetch(p.h, b1, (size_t)4 * D);
-                    const double bh = f16_layer_bound(hw1, 4 * D, D, hb1, true, hb1, hb1, false, bx);
-                    const float fx = f16_scale(bx), fw1 = f16_wscale(hw1), fh = f16_scale(bh), fw2 = f16_wscale(hw2);
-                    float mscale = 0.0f;
-                    if (last) {
-                        const double by = ln_bound(n2w, n2b);
-                        mscale = by < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(by, 1e-30)) : 0.0f;      // |LayerNorm| x scale <= 2^36
-                        if (!(mscale > 0.0f) || !std::isfinite(mscale)) mscale = 0.0f;
-                    }
-                    void* packed = nullptr;
-                    if (fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f && (!last || mscale > 0.0f) &&
-                        hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
-                        launch_ffn_x3_pack(w1, b1, w2, packed, D, p.h->own_stream, fw1, fw2, 0) == hipSuccess) {
-                        p.h->packed_weights.push_back(packed);
-                        if (last) p.need(big, (size_t)((T + 31) / 32 + 4) * ffn_x3_post_nseg(T) * 2 * D);
-                        p.add("ffn_x3:" + q + " (norm1+linear1+relu+linear2+res+norm2" + (last ? "+time sums" : "") + ", post-norm) [f16x3]", [=](Run& r) {
-                            FfnArgs a{r.buf[hb], n1w, n1b, static_cast<const unsigned char*>(packed), b2, r.B * T, 1.0f};
-                            a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2;
-                            a.ln2_w = n2w; a.ln2_b = n2b;
-                            if (last) { a.msum = r.buf[big]; a.T = T; a.m_scale = mscale; }
-                            return launch_ffn_x3_post(a, D, r.stream);
-                        });
-                        if (last) {
-                            p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
-                                return launch_ffn_x3_post_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, mscale, r.stream);
-                            });
-                            mean_done = true;
-                        }
-                        fused = true;
-                    } else if (packed) {
-                        (void)hipFree(packed);
-                    }
-                }
-                if (!fused) {
-                    p.add("layernorm:" + q + ".norm1", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n1w, n1b, r.B * T, D, ACT_NONE, r.stream); });
-                    add_gemm(p, q + ".linear1+relu", hb, big, T, 4 * D, D, w1, b1, ACT_RELU);
-                    add_gemm(p, q + ".linear2+res", big, hb, T, D, 4 * D, w2, b2, ACT_NONE, nullptr, nullptr, hb, 1.0f);
-                    if (last && D <= 256) {
-                        p.add("layernorm+mean:" + q + ".norm2 + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], n2w, n2b, r.B, T, D, r.stream); });
-                        mean_done = true;
-                    } else {
-                        p.add("layernorm:" + q + ".norm2", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n2w, n2b, r.B * T, D, ACT_NONE, r.stream); });
-                    }
-                }
-            }
-            if (!mean_done) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
-            set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
-            break;
-        }
-        case NWW_HEAD_TCN: {                      // TCNModel: architectures.py:290-367; the head reads tcn_out[:, :, T - 1] only
-            const int k = c.layer_dim, nl = c.n_crnn_channels;
-            const int* ch = c.crnn_channels;
-            const int last = 5;                                    // [B][ch[nl - 1]]: the last block's output at t = T - 1
-            p.need(last, (size_t)ch[nl - 1]);
-            auto key = [](int i, const char* part) { return "model.tcn_blocks." + std::to_string(i) + "." + part; };
-            // the whole stack in one launch over the last step's receptive-field cone (tcn_x3.hip), under the default arithmetic at the
-            // shapes it takes (widths multiples of 32 up to 256, the cone inside the LDS): two binary16 terms per operand, every row scaled
-            // by its own power of two - no bound on the features, no clamp
-            bool fused = false;
-            if (p.h->f16 && p.h->conv_products == 6) {
-                TcnArgs a;
-                a.T = T; a.F = F; a.L = nl; a.k = k;
-                for (int i = 0; i < nl; ++i) a.ch[i] = ch[i];
-                std::vector<void*> packs;
-                bool ok = tcn_x3_plan(a);
-                int cin = F;
-                for (int i = 0; ok && i < nl; ++i) {
-                    auto pack = [&](const char* part, int ci, int taps, TcnConv& cv) {
-                        const float* w = p.W(key(i, (std::string(part) + ".weight").c_str()));
-                        const float ws = f16_wscale(f16_fetch(p.h, w, (size_t)ch[i] * ci * taps));
-                        void* d = nullptr;
-                        if (!(ws > 0.0f) || hipMalloc(&d, tcn_x3_packed_bytes(ci, ch[i], taps)) != hipSuccess) return false;
-                        packs.push_back(d);
-                        if (launch_tcn_x3_pack(w, d, ci, ch[i], taps, ws, p.h->own_stream) != hipSuccess) return false;
-                        cv.packed = static_cast<const unsigned char*>(d);
-                        cv.bias = p.W(key(i, (std::string(part) + ".bias").c_str()));
-                        cv.w_un = 1.0f / ws;
-                        return true;
-                    };
-                    ok = pack("conv1", cin, k, a.c1[i]) && pack("conv2", ch[i], k, a.c2[i]) && (cin == ch[i] || pack("downsample", cin, 1, a.ds[i]));
-                    cin = ch[i];
-                }
-                if (ok) {
-                    for (void* d : packs) p.h->packed_weights.push_back(d);
-                    p.add("tcn_x3:" + std::to_string(nl) + " blocks, last " + std::to_string(a.S) + " steps of " + std::to_string(T) + " [f16x3]",
-                          [=](Run& r) {
-                              TcnArgs g = a;
-                              g.x = r.x; g.out = r.buf[last]; g.B = r.B;
-                              return launch_tcn_x3(g, r.stream);
-                          });
-                    fused = true;
-                } else {
-                    for (void* d : packs) (void)hipFree(d);
-                }
-            }
-            if (!fused) {
-                // every level over the whole sequence: causal im2col (taps x dilation, zero history), conv1 = GEMM + ReLU, conv2 = GEMM + ReLU
-                // + the residual (or the downsample's GEMM), then the second ReLU; the last row of each clip feeds the tail
-                const int col = 0, hid = 1, rsd = 4;
-                int in = -1, cin = F;
-                for (int i = 0; i < nl; ++i) {
-                    const int co = ch[i], dil = 1 << i, out = i % 2 == 0 ? 2 : 3;
-                    const std::string q = "model.tcn_blocks." + std::to_string(i);
-                    p.need(col, (size_t)T * k * (cin > co ? cin : co));
-                    p.add("im2col:" + q + ".conv1", [=](Run& r) { return launch_tcn_im2col(src(r, in), r.buf[col], r.B, T, cin, k, dil, r.stream); });
-                    add_gemm(p, q + ".conv1+relu", col, hid, T, co, cin * k, p.W(key(i, "conv1.weight")), p.W(key(i, "conv1.bias")), ACT_RELU);
-                    p.add("im2col:" + q + ".conv2", [=](Run& r) { return launch_tcn_im2col(r.buf[hid], r.buf[col], r.B, T, co, k, dil, r.stream); });
-                    int res = in;
-                    if (cin != co) {
-                        add_gemm(p, q + ".downsample", in, rsd, T, co, cin, p.W(key(i, "downsample.weight")), p.W(key(i, "downsample.bias")), ACT_NONE);
-                        res = rsd;
-                    }
-                    add_gemm(p, q + ".conv2+relu+res", col, out, T, co, co * k, p.W(key(i, "conv2.weight")), p.W(key(i, "conv2.bias")), ACT_RELU,
-                             nullptr, nullptr, res, 1.0f);
-                    p.add("unary:relu " + q, [=](Run& r) { return launch_unary(r.buf[out], r.buf[out], (size_t)r.B * T * co, ACT_RELU, r.stream); });
-                    in = out; cin = co;
-                }
-                const int fin = in, C = cin;
-                p.add("last_row:tcn_out[:, :, T - 1]", [=](Run& r) { return launch_tcn_last_row(r.buf[fin], r.buf[last], r.B, T, C, r.stream); });
-            }
-            set_tail(p, "fc", last, ch[nl - 1], p.W("model.fc.weight"), p.W("model.fc.bias"));
-            break;
+        p.add("dwconv1d+bn+swish:" + m, [=](Run& r) { return launch_dwconv1d_bn_swish(r.buf[t1], dw, db, ba, bb, r.buf[t3], r.B, T, D, 31, r.stream); });
+        // conv2 + residual inside ff2's launch, and behind the LAST block's ff2 its LayerNorm + the sums of the time average
+        const bool epi_fused = ffn(".ff2", 2, i == nb - 1, [&] { add_linear(p, m + ".conv2(pw)+res", t3, hb, T, D, D, pro_w[2], pro_b[2], hb, 1.0f); });
+        // the last block's LayerNorm feeds only the mean over time: one pass for both
+        if (epi_fused) {
+            last_fused = true;
+        } else if (i == nb - 1 && D <= 256) {
+            p.add("layernorm+mean:" + q + " + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], l2w, l2b, r.B, T, D, r.stream); });
+            last_fused = true;
+        } else {
+            p.add("layernorm:" + q, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], l2w, l2b, r.B * T, D, ACT_NONE, r.stream); });
         }
     }
-    // embedding Linear + Model.classifier (model.py:291-296) (+ sigmoid) -> emb [B][E], logits [B] (, probs [B])
+    if (!last_fused) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
+    set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
+    return NWW_OK;
+}
+
+int plan_transformer(PlanCtx& p) {                  // TransformerModel: architectures.py:164-206, nn.TransformerEncoderLayer defaults (post-norm, ReLU)
+    nww_handle* h = p.h;
+    const nww_config& c = h->cfg;
+    const int T = c.in_rows, F = c.in_cols, nb = c.n_blocks;
+    const int D = c.conformer_d_model, NH = c.conformer_n_head;
+    const int hb = 0, t1 = 1, big = 3;              // h, attention output / time mean, qkv / hidden / time sums
+    if (T > NWW_PE_MAX_LEN) return fail(h, NWW_ERR_UNSUPPORTED, "transformer: %d time steps exceed the positional table (%d rows)", T, NWW_PE_MAX_LEN);
+    p.need(hb, (size_t)T * D); p.need(t1, (size_t)T * D);
+    const float* pe = p.W("model.pos_encoder.pe");
+    const float xs = std::sqrt((float)D);          // math.sqrt(d_model), applied in float32 as torch does
+    // x = input_proj(x) sqrt(D) + pe[t]: the scale and the positional row in the short-K Linear's epilogue (lin_x3 epilogue 3), its
+    // input rows scaled per row (no clamp of the features); else the general GEMM and one elementwise pass
+    if (!add_lin_x3(p, "input_proj*sqrt(d)+pe", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 3, 99, xs, nullptr, nullptr, T, 0, pe)) {
+        add_gemm(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
+        p.add("scale+pe:input_proj", [=](Run& r) { return launch_scale_add_pe(r.buf[hb], pe, r.B, T, D, xs, r.stream); });
+    }
+    bool mean_done = false;
+    for (int i = 0; i < nb; ++i) {
+        const std::string q = "model.transformer_encoder.layers." + std::to_string(i);
+        const bool last = i == nb - 1;
+        // ---- h <- h + self_attn(h): head-major in_proj, the attention core, out_proj + residual (as the Conformer's attention module)
+        add_attention_module(p, q, ".self_attn", hb, big, t1, T, D, NH, 1);
+        // ---- h <- norm2(y + linear2(relu(linear1(y)))), y = norm1(h): one launch (ffn_x3 post-norm instance); the last layer's norm2 feeds
+        // only the time mean: exact per-tile sums instead of the store
+        const float *n1w = p.W(q + ".norm1.weight"), *n1b = p.W(q + ".norm1.bias"), *n2w = p.W(q + ".norm2.weight"), *n2b = p.W(q + ".norm2.bias");
+        const float *w1 = p.W(q + ".linear1.weight"), *b1 = p.W(q + ".linear1.bias"), *w2 = p.W(q + ".linear2.weight"), *b2 = p.W(q + ".linear2.bias");
+        bool fused = false;
+        if (nww_knobs().ffn_fused && p.h->f16 && p.h->conv_products == 6 && ffn_x3_post_supported(D)) {
+            // |norm1(h)_i| <= sqrt(D) |w_i| + |b_i| whatever h holds; relu(v) <= |v|: the scales need nothing but the weights
+            const double bx = f16_ln_bound(p.h, n1w, n1b, D);
+            const auto hw1 = f16_fetch(p.h, w1, (size_t)4 * D * D), hw2 = f16_fetch(p.h, w2, (size_t)4 * D * D), hb1 = f16_fetch(p.h, b1, (size_t)4 * D);
+            const double bh = f16_layer_bound(hw1, 4 * D, D, hb1, true, hb1, hb1, false, bx);
+            const float fx = f16_scale(bx), fw1 = f16_wscale(hw1), fh = f16_scale(bh), fw2 = f16_wscale(hw2);
+            const float mscale = last ? f16_mean_scale(f16_ln_bound(p.h, n2w, n2b, D)) : 0.0f;
+            void* packed = nullptr;
+            if (fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f && (!last || mscale > 0.0f) &&
+                hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
+                launch_ffn_x3_pack(w1, b1, w2, packed, D, p.h->own_stream, fw1, fw2, 0) == hipSuccess) {
+                p.h->packed_weights.push_back(packed);
+                if (last) p.need(big, (size_t)((T + 31) / 32 + 4) * ffn_x3_post_nseg(T) * 2 * D);
+                p.add("ffn_x3:" + q + " (norm1+linear1+relu+linear2+res+norm2" + (last ? "+time sums" : "") + ", post-norm) [f16x3]", [=](Run& r) {
+                    FfnArgs a{r.buf[hb], n1w, n1b, static_cast<const unsigned char*>(packed), b2, r.B * T, 1.0f};
+                    a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2;
+                    a.ln2_w = n2w; a.ln2_b = n2b;
+                    if (last) { a.msum = r.buf[big]; a.T = T; a.m_scale = mscale; }
+                    return launch_ffn_x3_post(a, D, r.stream);
+                });
+                if (last) {
+                    p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
+                        return launch_ffn_x3_post_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, mscale, r.stream);
+                    });
+                    mean_done = true;
+                }
+                fused = true;
+            } else if (packed) {
+                (void)hipFree(packed);
+            }
+        }
+        if (!fused) {
+            p.add("layernorm:" + q + ".norm1", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n1w, n1b, r.B * T, D, ACT_NONE, r.stream); });
+            add_gemm(p, q + ".linear1+relu", hb, big, T, 4 * D, D, w1, b1, ACT_RELU);
+            add_gemm(p, q + ".linear2+res", big, hb, T, D, 4 * D, w2, b2, ACT_NONE, nullptr, nullptr, hb, 1.0f);
+            if (last && D <= 256) {
+                p.add("layernorm+mean:" + q + ".norm2 + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], n2w, n2b, r.B, T, D, r.stream); });
+                mean_done = true;
+            } else {
+                p.add("layernorm:" + q + ".norm2", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n2w, n2b, r.B * T, D, ACT_NONE, r.stream); });
+            }
+        }
+    }
+    if (!mean_done) p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
+    set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
+    return NWW_OK;
+}
+
+int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.py:290-367; the head reads tcn_out[:, :, T - 1] only
+    const nww_config& c = p.h->cfg;
+    const int T = c.in_rows, F = c.in_cols;
+    const int k = c.layer_dim, nl = c.n_crnn_channels;
+    const int* ch = c.crnn_channels;
+    const int last = 5;                                    // [B][ch[nl - 1]]: the last block's output at t = T - 1
+    p.need(last, (size_t)ch[nl - 1]);
+    auto key = [](int i, const char* part) { return "model.tcn_blocks." + std::to_string(i) + "." + part; };
+    // the whole stack in one launch over the last step's receptive-field cone (tcn_x3.hip), under the default arithmetic at the
+    // shapes it takes (widths multiples of 32 up to 256, the cone inside the LDS): two binary16 terms per operand, every row scaled
+    // by its own power of two - no bound on the features, no clamp
+    bool fused = false;
+    if (p.h->f16 && p.h->conv_products == 6) {
+        TcnArgs a;
+        a.T = T; a.F = F; a.L = nl; a.k = k;
+        for (int i = 0; i < nl; ++i) a.ch[i] = ch[i];
+        std::vector<void*> packs;
+        bool ok = tcn_x3_plan(a);
+        int cin = F;
+        for (int i = 0; ok && i < nl; ++i) {
+            auto pack = [&](const char* part, int ci, int taps, TcnConv& cv) {
+                const float* w = p.W(key(i, (std::string(part) + ".weight").c_str()));
+                const float ws = f16_wscale(f16_fetch(p.h, w, (size_t)ch[i] * ci * taps));
+                void* d = nullptr;
+                if (!(ws > 0.0f) || hipMalloc(&d, tcn_x3_packed_bytes(ci, ch[i], taps)) != hipSuccess) return false;
+                packs.push_back(d);
+                if (launch_tcn_x3_pack(w, d, ci, ch[i], taps, ws, p.h->own_stream) != hipSuccess) return false;
+                cv.packed = static_cast<const unsigned char*>(d);
+                cv.bias = p.W(key(i, (std::string(part) + ".bias").c_str()));
+                cv.w_un = 1.0f / ws;
+                return true;
+            };
+            ok = pack("conv1", cin, k, a.c1[i]) && pack("conv2", ch[i], k, a.c2[i]) && (cin == ch[i] || pack("downsample", cin, 1, a.ds[i]));
+            cin = ch[i];
+        }
+        if (ok) {
+            for (void* d : packs) p.h->packed_weights.push_back(d);
+            p.add("tcn_x3:" + std::to_string(nl) + " blocks, last " + std::to_string(a.S) + " steps of " + std::to_string(T) + " [f16x3]",
+                  [=](Run& r) {
+                      TcnArgs g = a;
+                      g.x = r.x; g.out = r.buf[last]; g.B = r.B;
+                      return launch_tcn_x3(g, r.stream);
+                  });
+            fused = true;
+        } else {
+            for (void* d : packs) (void)hipFree(d);
+        }
+    }
+    if (!fused) {
+        // every level over the whole sequence: causal im2col (taps x dilation, zero history), conv1 = GEMM + ReLU, conv2 = GEMM + ReLU
+        // + the residual (or the downsample's GEMM), then the second ReLU; the last row of each clip feeds the tail
+        const int col = 0, hid = 1, rsd = 4;
+        int in = -1, cin = F;
+        for (int i = 0; i < nl; ++i) {
+            const int co = ch[i], dil = 1 << i, out = i % 2 == 0 ? 2 : 3;
+            const std::string q = "model.tcn_blocks." + std::to_string(i);
+            p.need(col, (size_t)T * k * (cin > co ? cin : co));
+            p.add("im2col:" + q + ".conv1", [=](Run& r) { return launch_tcn_im2col(src(r, in), r.buf[col], r.B, T, cin, k, dil, r.stream); });
+            add_gemm(p, q + ".conv1+relu", col, hid, T, co, cin * k, p.W(key(i, "conv1.weight")), p.W(key(i, "conv1.bias")), ACT_RELU);
+            p.add("im2col:" + q + ".conv2", [=](Run& r) { return launch_tcn_im2col(r.buf[hid], r.buf[col], r.B, T, co, k, dil, r.stream); });
+            int res = in;
+            if (cin != co) {
+                add_gemm(p, q + ".downsample", in, rsd, T, co, cin, p.W(key(i, "downsample.weight")), p.W(key(i, "downsample.bias")), ACT_NONE);
+                res = rsd;
+            }
+            add_gemm(p, q + ".conv2+relu+res", col, out, T, co, co * k, p.W(key(i, "conv2.weight")), p.W(key(i, "conv2.bias")), ACT_RELU,
+                     nullptr, nullptr, res, 1.0f);
+            p.add("unary:relu " + q, [=](Run& r) { return launch_unary(r.buf[out], r.buf[out], (size_t)r.B * T * co, ACT_RELU, r.stream); });
+            in = out; cin = co;
+        }
+        const int fin = in, C = cin;
+        p.add("last_row:tcn_out[:, :, T - 1]", [=](Run& r) { return launch_tcn_last_row(r.buf[fin], r.buf[last], r.B, T, C, r.stream); });
+    }
+    set_tail(p, "fc", last, ch[nl - 1], p.W("model.fc.weight"), p.W("model.fc.bias"));
+    return NWW_OK;
+}
+
+// the head's last Linear (-> embedding) + Model.classifier (model.py:291-296) (+ sigmoid) -> emb [B][E], logits [B] (, probs [B])
+void plan_tail(PlanCtx& p) {
+    const int E = p.h->cfg.embedding_dim, act = p.h->cfg.activation;
     if (nww_knobs().tail && tail_supported(p.tail_K, E)) {
         const float *We = p.tail_W, *be = p.tail_b, *W0 = p.W("classifier.0.weight"), *b0 = p.W("classifier.0.bias"),
                     *w3 = p.W("classifier.3.weight"), *b3 = p.W("classifier.3.bias");
         const int tin = p.tail_in, tK = p.tail_K;
-        const PlanCtx pc = p;                                   // (the DNN body's pointers, by value)
+        const PlanCtx::DnnBody dnn = p.dnn;
         p.add("tail:" + p.tail_name + "+classifier", [=](Run& r) {
             TailArgs t{src(r, tin), tK, We, be, E, W0, b0, w3, b3, r.emb, r.logits, r.probs, r.B, act};
-            if (pc.dnn_body) {
-                t.ln0_w = pc.dnn_ln0_w; t.ln0_b = pc.dnn_ln0_b; t.n_mid = pc.dnn_n_mid;
-                for (int i = 0; i < pc.dnn_n_mid; ++i) { t.mid_W[i] = pc.dnn_mid[i][0]; t.mid_b[i] = pc.dnn_mid[i][1]; t.mid_lnw[i] = pc.dnn_mid[i][2]; t.mid_lnb[i] = pc.dnn_mid[i][3]; }
+            if (dnn.on) {
+                t.ln0_w = dnn.ln0_w; t.ln0_b = dnn.ln0_b; t.n_mid = dnn.n_mid;
+                for (int i = 0; i < dnn.n_mid; ++i) { t.mid_W[i] = dnn.mid[i][0]; t.mid_b[i] = dnn.mid[i][1]; t.mid_lnw[i] = dnn.mid[i][2]; t.mid_lnb[i] = dnn.mid[i][3]; }
             }
             if (r.deferred.active && r.deferred.out_id == tin) {
                 t.parts = r.splitk_ws; t.nparts = r.deferred.parts; t.part_stride = r.deferred.stride;
@@ -1614,10 +1615,39 @@ extern "C" int nww_finalize(nww_handle* h) {
         add_gemm(p, "classifier.0", -2, -3, 1, E / 2, E, p.W("classifier.0.weight"), p.W("classifier.0.bias"), act);
         add_gemm(p, "classifier.3", -3, -4, 1, 1, E / 2, p.W("classifier.3.weight"), p.W("classifier.3.bias"), ACT_NONE);
     }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ finalize
+extern "C" int nww_finalize(nww_handle* h) {
+    if (!h) return NWW_ERR_INVALID;
+    if (h->finalized) return NWW_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (const auto& k : h->keys)
+        if (!h->tensors[k].loaded) return fail(h, NWW_ERR_MISSING, "Missing key(s) in state_dict: '%s'", k.c_str());
+    fold_batchnorms(h);
+    if (h->cfg.head_type == NWW_HEAD_BCRESNET) transpose_depthwise(h);
+    int rc = upload_weight_arena(h);
+    if (rc == NWW_OK) rc = build_frontend_tables(h);
+    if (rc != NWW_OK) return rc;
+    PlanCtx p{h};
+    switch (h->cfg.head_type) {
+        case NWW_HEAD_DNN: rc = plan_dnn(p); break;
+        case NWW_HEAD_CNN: rc = plan_cnn(p); break;
+        case NWW_HEAD_E2E_DNN: rc = plan_e2e_dnn(p); break;
+        case NWW_HEAD_CRNN: rc = plan_crnn(p); break;
+        case NWW_HEAD_GRU: rc = plan_gru(p); break;
+        case NWW_HEAD_BCRESNET: rc = plan_bcresnet(p); break;
+        case NWW_HEAD_CONFORMER: rc = plan_conformer(p); break;
+        case NWW_HEAD_TRANSFORMER: rc = plan_transformer(p); break;
+        case NWW_HEAD_TCN: rc = plan_tcn(p); break;
+    }
+    if (rc != NWW_OK) return rc;
+    plan_tail(p);
     // the plan-time weight packings above were enqueued on own_stream; a forward may arrive on any caller stream
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
     if (!h->plan_error.empty()) return fail(h, NWW_ERR_HIP, "%s", h->plan_error.c_str());
     h->finalized = true;
     return NWW_OK;
 }
-

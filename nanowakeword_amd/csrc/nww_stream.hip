@@ -1,14 +1,5 @@
 // nww_stream.hip - batched streaming: S lock-step device rings, one score per stream and hop (nww_stream_*).
 #include "nww_internal.h"
-#define prof_mark nww_prof_mark
-#define prof_begin nww_prof_begin
-#define ensure_ws nww_ensure_ws
-#define run_head nww_run_head
-#define check_run nww_check_run
-#define frontend_dev nww_frontend_on_dev
-#define forward_pcm_dev nww_forward_pcm_on_dev
-#define h2d_small nww_h2d_small
-#define copy_out nww_copy_out
 
 // ------------------------------------------------------------------------------------------ streaming
 __global__ void __launch_bounds__(256)
@@ -119,7 +110,7 @@ static int plan_incremental(nww_handle* h, int S, int W, int hop) {
 }
 
 extern "C" int nww_stream_open(nww_handle* h, int32_t S, int32_t W, int32_t hop) {
-    int rc = check_run(h, S);
+    int rc = nww_check_run(h, S);
     if (rc) return rc;
     if (W <= 0 || hop <= 0 || hop > W || (W % 8) || (hop % 8))
         return fail(h, NWW_ERR_INVALID, "window and hop must be positive multiples of 8 samples with hop <= window");
@@ -136,7 +127,7 @@ extern "C" int nww_stream_open(nww_handle* h, int32_t S, int32_t W, int32_t hop)
     h->ring_S = S; h->ring_W = W; h->ring_hop = hop; h->ring_pos = 0; h->ring_filled = 0;
     rc = plan_incremental(h, S, W, hop);
     if (rc) return rc;
-    return ensure_ws(h, S, W);
+    return nww_ensure_ws(h, S, W);
 }
 
 extern "C" int nww_stream_reset(nww_handle* h) {
@@ -155,10 +146,10 @@ extern "C" int64_t nww_stream_filled(const nww_handle* h) { return h ? h->ring_f
 static int stream_hop_incremental(nww_handle* h, float* d_logits, float* d_probs, hipStream_t s) {
     const nww_config& c = h->cfg;
     const int S = h->ring_S, W = h->ring_W, T = fe_num_frames(h->fe, W), k = h->lm_shift;
-    int rc = ensure_ws(h, S, W);
+    int rc = nww_ensure_ws(h, S, W);
     if (rc) return rc;
-    prof_begin(h);
-    prof_mark(h, s, 0);
+    nww_prof_begin(h);
+    nww_prof_mark(h, s, 0);
     Fe2Sub sub;
     sub.ring_rows = h->lm_rows; sub.row0 = h->lm_pos; sub.out_clip_stride = (size_t)2 * h->lm_rows * c.n_mels;
     if (h->primed) {
@@ -167,20 +158,20 @@ static int stream_hop_incremental(nww_handle* h, float* d_logits, float* d_probs
         sub.t0[sub.nr] = T - h->fe_edge_r - k; sub.t1[sub.nr] = T - h->fe_edge_r; ++sub.nr;
         if (h->fe_edge_r > 0) { sub.t0[sub.nr] = T - h->fe_edge_r; sub.t1[sub.nr] = T; ++sub.nr; }
     }
-    rc = frontend_dev(h, h->d_ring + h->ring_pos, S, W, h->d_lm_ring, nullptr, 1, s, nullptr, (size_t)2 * W, &sub);
+    rc = nww_frontend_on_dev(h, h->d_ring + h->ring_pos, S, W, h->d_lm_ring, nullptr, 1, s, nullptr, (size_t)2 * W, &sub);
     if (rc) return rc;
     const float* win = h->d_lm_ring + (size_t)h->lm_pos * c.n_mels;          // rows [lm_pos, lm_pos + T) of every stream's ring: its window
     const bool conv_inc = h->inc_conv && h->x_stride_ok;
     if (h->x_stride_ok) {
         h->sr.on = true; h->sr.x_stride = sub.out_clip_stride; h->sr.mode = conv_inc ? (h->primed ? 2 : 1) : 0;
-        rc = run_head(h, win, S, d_logits, d_probs, s, nullptr, 0, nullptr, false);
+        rc = nww_run_head(h, win, S, d_logits, d_probs, s, nullptr, 0, nullptr, false);
     } else {
         const int n4 = T * c.n_mels / 4;
         const size_t total = (size_t)S * n4;
         hipLaunchKernelGGL(stream_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(win),
                            reinterpret_cast<float4*>(h->d_logmel), S, n4, sub.out_clip_stride / 4);
         HIP_TRY(h, hipGetLastError());
-        rc = run_head(h, h->d_logmel, S, d_logits, d_probs, s, nullptr, 0, nullptr, c.mel_major_features != 0);
+        rc = nww_run_head(h, h->d_logmel, S, d_logits, d_probs, s, nullptr, 0, nullptr, c.mel_major_features != 0);
     }
     if (rc) return rc;
     h->lm_pos = (h->lm_pos + k) % h->lm_rows;
@@ -208,7 +199,7 @@ static int stream_push_dev(nww_handle* h, const int16_t* d_chunk, float* d_logit
         if (rc) h->primed = false;            // the rings may hold a half-finished hop: the next hop computes its window whole
         return rc;
     }
-    return forward_pcm_dev(h, h->d_ring + h->ring_pos, S, W, d_logits, d_probs, s, (size_t)2 * W);
+    return nww_forward_pcm_on_dev(h, h->d_ring + h->ring_pos, S, W, d_logits, d_probs, s, (size_t)2 * W);
 }
 extern "C" int nww_stream_push_dev(nww_handle* h, const int16_t* d_chunk, float* d_logits, float* d_probs, void* stream) {
     if (!h || !h->d_ring) return fail(h, NWW_ERR_STATE, "no open stream batch (nww_stream_open)");
@@ -223,9 +214,9 @@ extern "C" int nww_stream_push(nww_handle* h, const int16_t* chunk, float* logit
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = h->own_stream;
     const int S = h->ring_S;
-    { int rcs = h2d_small(h, h->d_chunk, chunk, (size_t)S * h->ring_hop * sizeof(int16_t), s); if (rcs) return rcs; }
+    { int rcs = nww_h2d_small(h, h->d_chunk, chunk, (size_t)S * h->ring_hop * sizeof(int16_t), s); if (rcs) return rcs; }
     int rc = stream_push_dev(h, h->d_chunk, h->d_logits, h->d_probs, s);
     if (rc) return rc;
-    return copy_out(h, S, logits, probs, nullptr, s);
+    return nww_copy_out(h, S, logits, probs, nullptr, s);
 }
 

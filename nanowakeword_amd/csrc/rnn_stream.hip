@@ -291,8 +291,7 @@ hipError_t launch_rnn_stream_pack(const float* w_hh, void* packed, int gates, in
 hipError_t launch_rnn_stream(const GruArgs& a, int gates, hipStream_t s) {
     if (!rnn_stream_usable(a) || !a.w_packed || (gates != 3 && gates != 4) || !(a.w_scale > 0.0f)) return hipErrorInvalidValue;
     const int HP = rnn_stream_width(a.H);
-    static const int n_cu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256; return n; }();
-    const int mt = a.B <= 16 * n_cu ? 1 : 2;
+    const int mt = a.B <= 16 * a.cu_count ? 1 : 2;
     const dim3 grid((a.B + 16 * mt - 1) / (16 * mt)), block(64 * (HP / 32));
     const size_t lds = (size_t)2 * 2 * 16 * mt * (HP + 16) * sizeof(uint16_t);     // two sets of two term planes
 #ifdef NWW_ABLATION

@@ -22,15 +22,16 @@ int main(int argc, char** argv) {
     hipMemcpy(dib, ib.data(), ib.size() * 4, hipMemcpyHostToDevice); hipMemcpy(dow, ow.data(), ow.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(dob, ob.data(), ob.size() * 4, hipMemcpyHostToDevice);
     hipStream_t s; hipStreamCreate(&s);
+    int dev = 0, cus = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const float ws_in = 65536.0f, ws_out = 65536.0f;                       // |w| <= 0.1 -> <= 6554 < 2^15
     launch_attn_x3_pack(diw, dib, dow, dob, packed, dbc, D, NH, ws_in, ws_out, s);
     const float cK = 1.0f / 32.0f, cV = 1.0f / 32.0f;                     // L1 <= 144 x 0.1 x 65536 < 2^20 ... (timing only)
     AttnArgs a{dh, dout, (const unsigned char*)packed, dbc, B, T, 1.0f / ws_in, cK * 0x1p-15f, cV * 0x1p-15f, 1.0f / (ws_out * ws_in * cV * 0x1p-15f), 1.0f / 6.0f};
-    for (int i = 0; i < 3; ++i) launch_attn_x3(a, D, NH, s);
+    for (int i = 0; i < 3; ++i) launch_attn_x3(a, D, NH, cus, s);
     hipStreamSynchronize(s);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, s);
-    for (int i = 0; i < 10; ++i) launch_attn_x3(a, D, NH, s);
+    for (int i = 0; i < 10; ++i) launch_attn_x3(a, D, NH, cus, s);
     hipEventRecord(e1, s); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("attn_x3 B=%d T=%d: %.4f ms per launch (%s)\n", B, T, ms / 10, hipGetErrorString(hipGetLastError()));

@@ -14,11 +14,12 @@ int main(int argc, char** argv) {
     hipMalloc(&dq, qkv.size() * 4); hipMalloc(&dout, (size_t)B * T * D * 4);
     hipMemcpy(dq, qkv.data(), qkv.size() * 4, hipMemcpyHostToDevice);
     hipStream_t s; hipStreamCreate(&s);
-    for (int i = 0; i < 3; ++i) launch_mha_h2(dq, dout, B, T, D, NH, s, 1);
+    int dev = 0, cus = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    for (int i = 0; i < 3; ++i) launch_mha_h2(dq, dout, B, T, D, NH, cus, s, 1);
     hipStreamSynchronize(s);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, s);
-    for (int i = 0; i < 10; ++i) launch_mha_h2(dq, dout, B, T, D, NH, s, 1);
+    for (int i = 0; i < 10; ++i) launch_mha_h2(dq, dout, B, T, D, NH, cus, s, 1);
     hipEventRecord(e1, s); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("mha_h2 B=%d T=%d D=%d heads=%d: %.4f ms per launch (%s)\n", B, T, D, NH, ms / 10, hipGetErrorString(hipGetLastError()));
