@@ -220,6 +220,10 @@ struct TailArgs {
     int n_mid = 0;
     const float *mid_W[4] = {nullptr, nullptr, nullptr, nullptr}, *mid_b[4] = {nullptr, nullptr, nullptr, nullptr};
     const float *mid_lnw[4] = {nullptr, nullptr, nullptr, nullptr}, *mid_lnb[4] = {nullptr, nullptr, nullptr, nullptr};
+    int cu_count = 256;    // the device's compute units: the grid of the large-batch kernel's persistent workgroups
 };
 bool tail_supported(int Kin, int E);
+// true when launch_classifier_tail runs the large-batch kernel (persistent workgroups, weights in LDS) on this shape; nparts > 0: x arrives
+// as that many split-K partials.  add_gemm defers its reduce to the tail by the SAME predicate.
+bool tail_batch_runs(int B, int Kin, int E, bool dnn_body, int nparts);
 hipError_t launch_classifier_tail(const TailArgs& a, hipStream_t s);

@@ -1847,14 +1847,215 @@ __global__ void __launch_bounds__(256) classifier_tail_kernel(TailArgs a) {
 
 bool tail_supported(int Kin, int E) { return Kin >= 1 && Kin <= 512 && E >= 2 && E <= 256 && (E % 2) == 0; }
 
+// ------------------------------------------------------------------------------------------ classifier tail, large batches
+// The same arithmetic as classifier_tail_kernel for B > TAIL_CT4_MAX: persistent workgroups over 8-clip tiles, several resident per CU.
+// We / be / W0 / b0 / w3 are staged into LDS once per workgroup (the small-batch kernel fetches every weight fragment from L1 / L2 in
+// the middle of its fmaf chains); the next tile's input - plain x rows or the producer's split-K partials - is requested before this
+// tile's dot products and summed after them, so the partials are paid for once, at bandwidth.  Thread (c = t % 8, g = t / 8) computes
+// outputs g, g + 32, .. of clip c, each ONE fmaf chain in ascending k from 0.0f with the bias added behind it; the partials are added
+// in ascending z from parts[0] with gemm_splitk_reduce_kernel's epilogue: tile shape, grid and batch position do not reach the bits.
+// Row pitches of p floats with p / 4 odd: the 8 (tile) or 4 consecutive (weight) rows that one ds_read_b128 lane group
+// ({0-3, 12-15, 20-27}, ..) touches start 4 banks apart modulo 64 - conflict-free in tools/lds_conflicts.py's model.
+// The DNN body (ln0_w, mid_*) stays on classifier_tail_kernel.
+constexpr int TB_CT = 8, TB_NG = 256 / TB_CT;
+constexpr int TAIL_CT4_MAX = 1024;                             // up to here the four-clip latency kernel (launch_classifier_tail)
+constexpr size_t TB_LDS_MAX = 96 * 1024;                       // Kin = 256, E = 64 (the recurrent heads: 87 KB) is the largest shape taken
+constexpr int TB_WG_PER_CU = 2;                                // where two fit the CU's 160 KB
+
+__host__ __device__ inline int tb_pitch(int n) { const int p = ((n + 3) & ~3) + 4; return ((p >> 2) & 1) ? p : p + 4; }
+static size_t tb_lds_bytes(int Kin, int E) {
+    const int Hd = E / 2, h4 = (Hd + 3) & ~3;
+    return sizeof(float) * ((size_t)(E + TB_CT) * tb_pitch(Kin) + (size_t)(Hd + TB_CT) * tb_pitch(E) + E + 2 * h4 + TB_CT * (Hd + 1));
+}
+
+bool tail_batch_runs(int B, int Kin, int E, bool dnn_body, int nparts) {
+    return B > TAIL_CT4_MAX && !dnn_body && tail_supported(Kin, E) && (Kin % 4) == 0 && (E % 4) == 0 &&
+           (nparts == 0 || (nparts <= 16 && Kin <= 128)) &&    // partials: one 16-byte element x 16 chunks per thread and tile in registers
+           tb_lds_bytes(Kin, E) <= TB_LDS_MAX;
+}
+
+// NB of the n4 16-byte pieces of a [rows][4 K4] matrix per thread, global -> registers -> LDS rows of `pitch` floats.  Loads AND stores
+// are unconditional with the piece index clamped (a piece beyond the end stores the last piece again, the same bytes): behind a
+// bounds test hipcc sinks every load into its store's branch, and the round trips run one after the other
+template <int NB>
+__device__ __forceinline__ void tb_load(const float* __restrict__ src, int i0, int n4, f32x4 (&v)[NB]) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) v[j] = reinterpret_cast<const f32x4*>(src)[min(i0 + 256 * j, n4 - 1)];
+}
+template <int NB>
+__device__ __forceinline__ void tb_store(float* dstp, int i0, int n4, int K4, int pitch, const f32x4 (&v)[NB]) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int i = min(i0 + 256 * j, n4 - 1), r = i / K4;
+        *reinterpret_cast<f32x4*>(dstp + r * pitch + 4 * (i - r * K4)) = v[j];
+    }
+}
+
+// outputs e0 = g, g + R NG, .. of one clip, R at a time: R fmaf chains (ascending k) sharing the x fragment, everything from LDS
+template <int R, class F>
+__device__ __forceinline__ void tb_layer(const float* xr, const float* Ws, int pW, int N, int K, int g, F&& out) {
+    for (int e0 = g; e0 < N; e0 += R * TB_NG) {
+        const float* wr[R];
+        float acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { wr[r] = Ws + min(e0 + r * TB_NG, N - 1) * pW; acc[r] = 0.0f; }
+#pragma unroll 4
+        for (int k = 0; k < K; k += 4) {
+            const float4 x = *reinterpret_cast<const float4*>(xr + k);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float4 w = *reinterpret_cast<const float4*>(wr[r] + k);
+                acc[r] = fmaf(x.x, w.x, acc[r]); acc[r] = fmaf(x.y, w.y, acc[r]); acc[r] = fmaf(x.z, w.z, acc[r]); acc[r] = fmaf(x.w, w.w, acc[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (e0 + r * TB_NG < N) out(e0 + r * TB_NG, acc[r]);
+    }
+}
+template <class F>
+__device__ __forceinline__ void tb_layer_any(const float* xr, const float* Ws, int pW, int N, int K, int g, F&& out) {
+    const int per = (N + TB_NG - 1) / TB_NG;                    // outputs per thread (uniform)
+    if (per >= 3) tb_layer<4>(xr, Ws, pW, N, K, g, out);
+    else if (per == 2) tb_layer<2>(xr, Ws, pW, N, K, g, out);
+    else tb_layer<1>(xr, Ws, pW, N, K, g, out);
+}
+
+template <int ACT, bool PARTS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) classifier_tail_batch_kernel(TailArgs a) {
+    constexpr int CT = TB_CT, NPF = PARTS ? 16 : 4;            // 16-byte pieces a thread holds for the next tile
+    extern __shared__ __attribute__((aligned(16))) float tsm[];
+    const int Kin = a.Kin, E = a.E, Hd = E / 2, K4 = Kin / 4, E4 = E / 4;
+    const int pK = tb_pitch(Kin), pE = tb_pitch(E), ldh = Hd + 1, h4 = (Hd + 3) & ~3;
+    float* Wes = tsm;                     // [E][pK]
+    float* W0s = Wes + E * pK;            // [Hd][pE]
+    float* xs = W0s + Hd * pE;            // [CT][pK]
+    float* es = xs + CT * pK;             // [CT][pE]
+    float* bes = es + CT * pE;            // [E]
+    float* b0s = bes + E;                 // [Hd]
+    float* w3s = b0s + h4;                // [Hd]
+    float* hs = w3s + h4;                 // [CT][ldh]
+    const int tid = threadIdx.x, n4 = CT * K4;                  // 16-byte pieces of a tile's input
+    const int B = a.B, step = gridDim.x * CT;
+    // this thread's pieces of a tile: piece i = tid + 256 j -> clip slot i / K4, columns 4 (i % K4) ..; the same for every tile
+    int pc[PARTS ? 1 : 4], pq[PARTS ? 1 : 4];
+#pragma unroll
+    for (int j = 0; j < (PARTS ? 1 : 4); ++j) { const int i = min(tid + 256 * j, n4 - 1); pc[j] = i / K4; pq[j] = i - pc[j] * K4; }
+    f32x4 pf[NPF];
+    auto request = [&](int b0) {                                // unconditional loads, indices clamped
+        if (PARTS) {
+            const size_t o = (size_t)min(b0 + pc[0], B - 1) * Kin + 4 * pq[0];
+#pragma unroll
+            for (int z = 0; z < 16; ++z) pf[z] = *reinterpret_cast<const f32x4*>(a.parts + (size_t)min(z, a.nparts - 1) * a.part_stride + o);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pf[j] = *reinterpret_cast<const f32x4*>(a.x + (size_t)min(b0 + pc[j], B - 1) * Kin + 4 * pq[j]);
+        }
+    };
+    int b0 = blockIdx.x * CT;
+    // every load of the prologue is issued before the first wait: the small vectors, the first tile's input, the weights
+    const float bev = a.be ? a.be[min(tid, E - 1)] : 0.0f, b0v = a.b0[min(tid, Hd - 1)], w3v = a.w3[min(tid, Hd - 1)], b3 = a.b3[0];
+    // the producer's epilogue operands of this thread's four columns: loaded whether present or not (an absent one reads the partials
+    // instead and is ignored below) - a conditionally loaded register is waited for at the join, in front of the loads that follow
+    float ib[4] = {0.f, 0.f, 0.f, 0.f}, ia[4] = {0.f, 0.f, 0.f, 0.f}, ie[4] = {0.f, 0.f, 0.f, 0.f};
+    if (PARTS) {
+        const float *pb = a.in_bias ? a.in_bias : a.parts, *pa = a.in_alpha ? a.in_alpha : a.parts, *pe = a.in_alpha ? a.in_beta : a.parts;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const int k = 4 * pq[0] + i; ib[i] = pb[k]; ia[i] = pa[k]; ie[i] = pe[k]; }
+    }
+    request(b0);
+    {
+        f32x4 wv[8], uv[4];
+        tb_load(a.We, tid, E * K4, wv);
+        tb_load(a.W0, tid, Hd * E4, uv);
+        // one statement that needs every weight piece (and the tile's first and last): all of the above is in flight before the first wait
+        asm volatile("" : "+v"(wv[0]), "+v"(wv[1]), "+v"(wv[2]), "+v"(wv[3]), "+v"(wv[4]), "+v"(wv[5]), "+v"(wv[6]), "+v"(wv[7]),
+                          "+v"(uv[0]), "+v"(uv[1]), "+v"(uv[2]), "+v"(uv[3]), "+v"(pf[0]), "+v"(pf[NPF - 1]));
+        tb_store(Wes, tid, E * K4, K4, pK, wv);
+        tb_store(W0s, tid, Hd * E4, E4, pE, uv);
+        for (int i0 = tid + 8 * 256; i0 < E * K4; i0 += 8 * 256) { f32x4 v[8]; tb_load(a.We, i0, E * K4, v); tb_store(Wes, i0, E * K4, K4, pK, v); }   // larger shapes
+        for (int i0 = tid + 4 * 256; i0 < Hd * E4; i0 += 4 * 256) { f32x4 v[4]; tb_load(a.W0, i0, Hd * E4, v); tb_store(W0s, i0, Hd * E4, E4, pE, v); }
+    }
+    if (tid < E) bes[tid] = bev;                               // E <= 256, Hd <= 128: one element per thread
+    if (tid < Hd) { b0s[tid] = b0v; w3s[tid] = w3v; }
+    for (; b0 < B; b0 += step) {
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));                            // lane coordinates from an opaque copy: nothing of the body is hoisted
+        const int c = t % CT, g = t / CT;                      // clip slot, output group
+        // ---- the tile's input rows -> xs (requested one tile ago)
+        if (PARTS) {
+            float v[4] = {pf[0].x, pf[0].y, pf[0].z, pf[0].w};
+#pragma unroll
+            for (int z = 1; z < 16; ++z)
+                if (z < a.nparts) { v[0] += pf[z].x; v[1] += pf[z].y; v[2] += pf[z].z; v[3] += pf[z].w; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float u = v[i] + (a.in_bias ? ib[i] : 0.0f);
+                if (a.in_alpha) u = u * ia[i] + ie[i];
+                v[i] = act_apply(u, a.in_act);
+                if (b0 + pc[0] >= B) v[i] = 0.0f;
+            }
+            if (t < n4) *reinterpret_cast<f32x4*>(xs + pc[0] * pK + 4 * pq[0]) = f32x4{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (t + 256 * j < n4) *reinterpret_cast<f32x4*>(xs + pc[j] * pK + 4 * pq[j]) = b0 + pc[j] < B ? pf[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if (b0 + step < B) request(b0 + step);                 // (uniform) in flight under the dot products below
+        __syncthreads();
+        tb_layer_any(xs + c * pK, Wes, pK, E, Kin, g, [&](int e, float acc) { es[c * pE + e] = acc + bes[e]; });
+        __syncthreads();
+        for (int i = t; i < CT * E4; i += 256) {               // the embedding tile leaves as 16-byte stores
+            const int cc = i / E4, q = i - cc * E4;
+            if (b0 + cc < B) *reinterpret_cast<float4*>(a.emb + (size_t)(b0 + cc) * E + 4 * q) = *reinterpret_cast<const float4*>(es + cc * pE + 4 * q);
+        }
+        tb_layer_any(es + c * pE, W0s, pE, Hd, E, g, [&](int j, float acc) { hs[c * ldh + j] = act_ct<ACT>(acc + b0s[j]); });
+        __syncthreads();
+        if (t < CT && b0 + t < B) {
+            const float* hr = hs + t * ldh;
+            float acc = 0.0f;
+            for (int j = 0; j < Hd; ++j) acc = fmaf(hr[j], w3s[j], acc);
+            const float l = acc + b3;
+            a.logits[b0 + t] = l;
+            if (a.probs) a.probs[b0 + t] = 1.0f / (1.0f + expf(-l));
+        }
+        // no barrier here: xs, es and hs are next written behind one, two and three of the next tile's barriers
+    }
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 hipError_t launch_classifier_tail(const TailArgs& a, hipStream_t s) {
     if (!tail_supported(a.Kin, a.E)) return hipErrorInvalidValue;
     if (a.ln0_w && (a.Kin > 256 || a.n_mid < 0 || a.n_mid > 4)) return hipErrorInvalidValue;
+    // large batches: the persistent LDS-weight kernel.  Measured at B = 4096 (CNN head, the same box): reduce 0.0076 +
+    // tail 0.0167 ms -> 0.0121 ms in this one launch (0.0141 with one workgroup per CU, 0.0162 before every prologue load was in flight at once).
+    // A shape it does not take (weights beyond TB_LDS_MAX, the DNN body, an operand that is not 16-byte aligned) goes on below; that kernel
+    // sums deferred partials as well, so the producer's decision (add_gemm, the same tail_batch_runs) never depends on the pointers.
+    if (tail_batch_runs(a.B, a.Kin, a.E, a.ln0_w != nullptr, a.parts ? a.nparts : 0) && !a.done_flag && (!a.parts || a.nparts >= 1) && aligned16(a.We) && aligned16(a.W0) &&
+        aligned16(a.emb) && aligned16(a.parts ? a.parts : a.x) && (a.part_stride % 4) == 0) {
+        const size_t lds = tb_lds_bytes(a.Kin, a.E);
+        int grid = (a.B + TB_CT - 1) / TB_CT;
+        const int wgs = (int)std::min<size_t>(TB_WG_PER_CU, (160 * 1024) / lds);
+        if (grid > a.cu_count * wgs) grid = a.cu_count * wgs;
+#define TAILB_CALL(A)                                                                                                       \
+    {                                                                                                                       \
+        const void* f = a.parts ? reinterpret_cast<const void*>(classifier_tail_batch_kernel<A, true>)                      \
+                                : reinterpret_cast<const void*>(classifier_tail_batch_kernel<A, false>);                    \
+        const hipError_t ea = nww_allow_lds(f, lds);                                                                        \
+        if (ea != hipSuccess) return ea;                                                                                    \
+        if (a.parts) hipLaunchKernelGGL((classifier_tail_batch_kernel<A, true>), dim3(grid), dim3(256), lds, s, a);         \
+        else hipLaunchKernelGGL((classifier_tail_batch_kernel<A, false>), dim3(grid), dim3(256), lds, s, a);                \
+    }
+        NWW_DISPATCH_ACT(a.act, TAILB_CALL)
+#undef TAILB_CALL
+        return hipGetLastError();
+    }
     const size_t lds = (size_t)16 * ((a.ln0_w ? 2 : 1) * (((a.Kin + 3) & ~3) + 4) + (((a.E + 3) & ~3) + 4) + (a.E / 2 + 1)) * sizeof(float);
-    // small batches: four clips per workgroup (64 threads per clip instead of 16; measured at B = 32 / 1024 / 4096: DNN body + tail
-    // 0.035 -> 0.021 ms, CRNN tail 0.0255 -> 0.022, CNN tail 0.020 -> 0.029).  B = 5 .. 16 keep ONE 16-clip workgroup: the
+    // small batches: four clips per workgroup (64 threads per clip instead of 16; measured at B = 32 / 1024: DNN body + tail
+    // 0.035 -> 0.021 ms, CRNN tail 0.0255 -> 0.022).  B = 5 .. 16 keep ONE 16-clip workgroup: the
     // completion word of the interpreter's zero-copy calls is written by a launch of a single workgroup only
-    static const int ct4_max = 1024;
+    static const int ct4_max = TAIL_CT4_MAX;
     const bool small = a.B <= 4 || (a.B > 16 && a.B <= ct4_max);
     const int ct = small ? 4 : 16;
     int grid = (a.B + ct - 1) / ct;

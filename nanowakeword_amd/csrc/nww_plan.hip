@@ -267,6 +267,7 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
               int res_id = 99, float rscale = 1.f, bool* a_blocked_inout = nullptr, bool feeds_tail = false, bool feeds_ln = false,
               F16Range a_range = F16Range{}, bool a_bound_assumed = false) {
     const double a_bound = a_range.ok() ? a_range.bound : 0.0;
+    const int tail_E = p.h->cfg.embedding_dim;
     if (out_id >= 0) p.need(out_id, (size_t)rows_per_clip * N);
     // Contractions run on the bf16 matrix cores by exact operand splitting (gemm_x3.hip) where that kernel wins -
     // measured per shape on the Conformer / GRU / CNN heads at full batch (ms, split-operand vs float32 MFMA):
@@ -327,10 +328,11 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
         // only the MFMA kernels leave split-K partials; the VALU fallback (K % 4 != 0 or an A pointer that is not 16-byte aligned)
         // writes C itself, so nothing may be deferred to the consumer then
         const bool partials = g.splitk > 1 && g.splitk_ws && gemm_writes_partials(g);
-        // a handful of clips (the interpreter's calls): the fused tail sums the partials itself, in the same order - one
-        // dependent launch less (B = 1: 62 -> 58 us back-to-back).  Larger batches keep the reduce launch: the tail's few
-        // workgroups read the 16 partials slower than the full-grid reduce does (B = 4096: 0.028 vs 0.019 + 0.007 ms).
-        if (feeds_tail && g.M <= 8 && partials && !g.res) {
+        // the fused tail sums the partials itself, in the reduce kernel's order: one dependent launch and the round trip of this layer's
+        // output less.  A handful of clips (the interpreter's calls; B = 1: 62 -> 58 us back-to-back) on the latency kernel, large batches
+        // where the persistent tail runs (tail_batch_runs, the predicate launch_classifier_tail itself uses; B = 4096: reduce + tail
+        // 0.0076 + 0.0167 -> 0.0121 ms).  In between the reduce launch stays: the latency kernel's few workgroups read the partials slower.
+        if (feeds_tail && partials && !g.res && (g.M <= 8 || tail_batch_runs(g.M, N, tail_E, false, g.splitk))) {
             g.defer_reduce = true;
             r.deferred.active = true; r.deferred.out_id = out_id; r.deferred.parts = g.splitk; r.deferred.stride = (size_t)g.M * N;
             r.deferred.bias = bias; r.deferred.alpha = alpha; r.deferred.beta = beta; r.deferred.act = act;
@@ -1595,8 +1597,11 @@ void plan_tail(PlanCtx& p) {
                     *w3 = p.W("classifier.3.weight"), *b3 = p.W("classifier.3.bias");
         const int tin = p.tail_in, tK = p.tail_K;
         const PlanCtx::DnnBody dnn = p.dnn;
-        p.add("tail:" + p.tail_name + "+classifier", [=](Run& r) {
+        // the step's name says which kernel large batches get (the shape part of tail_batch_runs; small batches always the latency kernel)
+        const bool batch_kernel = tail_batch_runs(1 << 20, tK, E, dnn.on, 0);
+        p.add("tail:" + p.tail_name + "+classifier" + (batch_kernel ? " (large batches: persistent, weights in LDS)" : ""), [=](Run& r) {
             TailArgs t{src(r, tin), tK, We, be, E, W0, b0, w3, b3, r.emb, r.logits, r.probs, r.B, act};
+            t.cu_count = r.cu_count;
             if (dnn.on) {
                 t.ln0_w = dnn.ln0_w; t.ln0_b = dnn.ln0_b; t.n_mid = dnn.n_mid;
                 for (int i = 0; i < dnn.n_mid; ++i) { t.mid_W[i] = dnn.mid[i][0]; t.mid_b[i] = dnn.mid[i][1]; t.mid_lnw[i] = dnn.mid[i][2]; t.mid_lnb[i] = dnn.mid[i][3]; }

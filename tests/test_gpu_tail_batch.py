@@ -1,0 +1,60 @@
+"""The large-batch classifier tail (persistent workgroups, weights in LDS, split-K partials summed in the tail) against the
+small-batch kernels it must equal bit for bit (run with -m gpu).
+
+For the CNN head (the tail receives fc1's split-K partials) and the GRU head (plain x rows): logits AND embeddings of the first
+B clips of one clip set at B in {17, 1024, 1025, 4096, 4099} equal those of the same clips pushed through in batches of 8 (the
+deferred-reduce small path) and of 1.  A CNN head whose tail weights exceed the kernel's LDS budget (embedding_dim 256) keeps the
+earlier kernel at every batch size: its plan step says so, and the results agree in the same way."""
+import numpy as np
+import pytest
+
+from nanowakeword_amd.config import FrontendConfig, HeadConfig
+from nanowakeword_amd.synth import synth_features, synth_state_dict
+
+pytestmark = pytest.mark.gpu
+SIZES = (17, 1024, 1025, 4096, 4099)
+NOTE = "(large batches: persistent, weights in LDS)"
+
+
+@pytest.fixture(scope="module")
+def HipModel():
+    from nanowakeword_amd.session import HipModel
+    return HipModel
+
+
+def _in_batches(m, x, n):
+    lg, pr, em = [], [], []
+    for i in range(0, len(x), n):
+        l, p, e = m.forward_features(x[i:i + n], return_embedding=True)
+        lg.append(l.copy()); pr.append(p.copy()); em.append(e.copy())
+    return np.concatenate(lg), np.concatenate(pr), np.concatenate(em)
+
+
+def _check(HipModel, cfg, sizes, want_batch_kernel):
+    sd = synth_state_dict(cfg)
+    m = HipModel(cfg, FrontendConfig(), state_dict=sd)
+    tail = [s for s in m.describe_plan().strip().split("\n") if "tail:" in s]
+    assert len(tail) == 1, tail
+    assert (NOTE in tail[0]) == want_batch_kernel, tail
+    x = synth_features(max(sizes), cfg.input_shape, seed=11)
+    l8, p8, e8 = _in_batches(m, x, 8)
+    l1, p1, e1 = _in_batches(m, x, 1)
+    assert np.isfinite(l8).all() and np.ptp(l8) > 0.0 and np.ptp(e8) > 0.0
+    assert np.array_equal(l8, l1) and np.array_equal(p8, p1) and np.array_equal(e8, e1)
+    for B in sizes:
+        lg, pr, em = m.forward_features(x[:B], return_embedding=True)
+        assert lg.shape == (B,) and em.shape == (B, cfg.embedding_dim)
+        assert np.array_equal(lg, l8[:B]), (B, int((lg != l8[:B]).sum()))
+        assert np.array_equal(em, e8[:B]), (B, int((em != e8[:B]).sum()))
+        assert np.array_equal(pr, p8[:B]), B
+    m.close()
+
+
+@pytest.mark.parametrize("head", ["cnn", "gru"])
+def test_large_batch_tail_equals_small_batches(HipModel, head):
+    _check(HipModel, HeadConfig(head, (101, 64)), SIZES, True)
+
+
+def test_tail_weights_beyond_lds_budget_fall_back(HipModel):
+    # We = [256][128] floats = 128 KB: beyond what the large-batch kernel stages; the earlier kernel runs, deferred partials included
+    _check(HipModel, HeadConfig("cnn", (101, 64), embedding_dim=256), (1025, 4099), False)
