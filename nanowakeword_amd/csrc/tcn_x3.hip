@@ -269,7 +269,9 @@ bool tcn_x3_plan(TcnArgs& a) {
     a.ld = cmax + 4;                                           // rows 4 banks apart: the 16-byte B-operand reads of 8 lanes are conflict-free
     a.S = a.T < tcn_receptive_field(a.L, a.k) ? a.T : tcn_receptive_field(a.L, a.k);
     // the widest level decides the instance: four output blocks per tile and wave group (up to 128 channels, 1..3 tiles, 4..12
-    // waves) or eight (up to 256 channels, one tile of four waves)
+    // waves) or eight (up to 256 channels, one tile of four waves).  With cmax <= 128 three tiles always fit (ld <= 132:
+    // tcn_lds_bytes(3, 132) = 153216 <= TCN_LDS_MAX), so the loop below settles on RT = 3 for every S <= 96 and refuses a longer
+    // cone: RT = 1 / 2 of instance <1> are kept by the kernel and the launcher but no plan reaches them
     const int max_rt = cmax <= 128 ? 3 : 1;
     a.RT = 0;
     for (int rt = max_rt; rt >= 1; --rt)

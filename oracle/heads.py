@@ -155,7 +155,7 @@ def mha(x, sd, prefix, n_head):
     dh = D // n_head
     qkv = x @ sd[prefix + ".in_proj_weight"].T + sd[prefix + ".in_proj_bias"]
     q, k, v = (qkv[..., i * D:(i + 1) * D].reshape(B, T, n_head, dh).transpose(0, 2, 1, 3) for i in range(3))
-    q = q * F32(1.0 / np.sqrt(dh))                              # torch scales q before QK^T
+    q = q * q.dtype.type(1.0 / np.sqrt(dh))                     # torch scales q before QK^T (the scale in x's own precision)
     s = q @ k.transpose(0, 1, 3, 2)
     s = s - s.max(-1, keepdims=True)
     p = np.exp(s)

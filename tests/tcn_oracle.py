@@ -42,6 +42,24 @@ def receptive_field(cfg):
     return 1 + 2 * (cfg.tcn_kernel_size - 1) * (2 ** len(cfg.tcn_channels) - 1)
 
 
+def fused_plan(cfg):
+    """The fused kernel's launch plan restated (tcn_x3_plan in tcn_x3.hip): None where the stack goes to the im2col + GEMM fallback,
+    else S (cone rows kept per clip), RT (32-row tiles per workgroup), NC (clips per workgroup) and the instance (1: widths <= 128,
+    2: <= 256).  Tests assert the plan's own text; this is for the batch sizes and clips they pick around NC."""
+    T, F = cfg.input_shape
+    L, k = len(cfg.tcn_channels), cfg.tcn_kernel_size
+    if not 1 <= L <= 4 or k < 2 or T < 1 or F < 1 or any(c <= 0 or c % 32 or c > 256 for c in cfg.tcn_channels):
+        return None
+    cmax = max([(F + 15) // 16 * 16] + list(cfg.tcn_channels))
+    if cmax > 256:
+        return None
+    S, ld = min(T, receptive_field(cfg)), cmax + 4
+    for rt in range(3 if cmax <= 128 else 1, 0, -1):
+        if 32 * rt >= S and 3 * 32 * rt * (ld + 1) * 4 <= 160 * 1024:
+            return {"S": S, "RT": rt, "NC": 32 * rt // S, "instance": 1 if cmax <= 128 else 2}
+    return None
+
+
 def tcn_head(x, sd, cfg, dtype=F32):
     """features [B, T, F] -> embedding [B, E] = fc(tcn_out[:, :, T - 1])."""
     last = tcn_sequence(x, sd, cfg, dtype)[:, -1]

@@ -11,6 +11,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
 
+# picked for what its 30 draws cover, from a listing made without a GPU (fuzz_heads.draw_new_head + tcn_oracle.fused_plan): 14 Transformer
+# and 16 TCN cases, all 16 on the fused kernel, 6 of them with a cone longer than 32 rows
+NEW_HEADS_SEED = 18
+
 
 def test_fuzz_frontend_bounded():
     import fuzz_frontend
@@ -24,6 +28,20 @@ def test_fuzz_heads_bounded():
     lines = []
     worst, ran = fuzz_heads.run(n_cases=28, seed=4, log=lines.append)
     assert ran >= 14 and worst <= 1e-4, "\n".join(lines)
+
+
+def test_fuzz_new_heads_bounded():
+    """The Transformer and TCN kinds on a seed of their own (the default kinds' 28 cases above stay the cases they have always been):
+    1e-4 against the restatements - absolute for the Transformer, relative to max(1, |logit|) for the TCN, which normalises nothing - and
+    floors on what the seed's cases exercise (listed without a GPU when the seed was picked): both kinds, the fused TCN kernel, cones of
+    more than one 32-row tile."""
+    import fuzz_heads
+    lines, stats = [], {}
+    worst, ran = fuzz_heads.run(n_cases=30, seed=NEW_HEADS_SEED, kinds=("transformer", "tcn"), log=lines.append, stats=stats)
+    text = "\n".join(lines + [str(stats)])
+    assert worst <= 1e-4, text
+    assert stats["ran_transformer"] >= 10 and stats["ran_tcn"] >= 10 and ran == stats["ran_transformer"] + stats["ran_tcn"], text
+    assert stats["tcn_fused"] >= 8 and stats["tcn_fused_long_cone"] >= 3 and stats["refused"] <= 2, text
 
 
 @pytest.mark.parametrize("head", ["cnn", "dnn", "crnn"])

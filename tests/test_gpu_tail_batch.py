@@ -1,7 +1,8 @@
 """The large-batch classifier tail (persistent workgroups, weights in LDS, split-K partials summed in the tail) against the
 small-batch kernels it must equal bit for bit (run with -m gpu).
 
-For the CNN head (the tail receives fc1's split-K partials) and the GRU head (plain x rows): logits AND embeddings of the first
+For the CNN head (the tail receives fc1's split-K partials), the GRU head (plain x rows) and the Transformer / TCN heads (plain rows
+too, K = 128, from mean_finish / tcn_x3, whose grids depend on B): logits AND embeddings of the first
 B clips of one clip set at B in {17, 1024, 1025, 4096, 4099} equal those of the same clips pushed through in batches of 8 (the
 deferred-reduce small path) and of 1.  A CNN head whose tail weights exceed the kernel's LDS budget (embedding_dim 256) keeps the
 earlier kernel at every batch size: its plan step says so, and the results agree in the same way."""
@@ -50,7 +51,7 @@ def _check(HipModel, cfg, sizes, want_batch_kernel):
     m.close()
 
 
-@pytest.mark.parametrize("head", ["cnn", "gru"])
+@pytest.mark.parametrize("head", ["cnn", "gru", "transformer", "tcn"])
 def test_large_batch_tail_equals_small_batches(HipModel, head):
     _check(HipModel, HeadConfig(head, (101, 64)), SIZES, True)
 

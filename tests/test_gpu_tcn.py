@@ -1,6 +1,7 @@
 """TCN head on the HIP path (run with -m gpu): reference goldens, ragged batches, the PCM composite, ONNX / .pt ingestion through the
 session and the interpreter, the one-launch plan at the reference defaults, the generic fallback, batch invariance, the unclamped loud
-frame and the receptive-field cone."""
+frame and the receptive-field cone; every instance of the fused kernel (cones across 32-row tiles, tap counts, depths, widths, the
+degenerate clip lengths) against the float64 restatement."""
 import json
 import os
 
@@ -11,7 +12,7 @@ import oracle
 from nanowakeword_amd.config import FrontendConfig, HeadConfig
 from nanowakeword_amd.synth import synth_features, synth_state_dict
 from parity import logit_bounds
-from tcn_oracle import receptive_field, tcn_head, tcn_model
+from tcn_oracle import fused_plan, receptive_field, tcn_head, tcn_model
 
 pytestmark = pytest.mark.gpu
 
@@ -237,4 +238,99 @@ def test_cone_only():
     b, _ = m.forward_features(y)
     assert np.array_equal(a, b)
     assert _close(a, tcn_model(x, synth_state_dict(cfg), cfg))
+    m.close()
+
+
+# (T, F, channels, k): every family of tcn_x3's launch plan (tcn_x3_plan: S = min(T, R) cone rows per clip, NC = 32 RT / S clips per
+# workgroup, instance <1> for widths <= 128 and <2> up to 256, where the input's padded width counts as a width)
+_FUSED = [
+    # the cone spans two or three 32-row tiles: dilated taps reach across tile boundaries
+    (101, 64, [64, 64, 128], 4), (101, 64, [64, 64, 128], 5), (101, 64, [64, 64, 128, 128], 3), (101, 64, [128, 128, 128, 128], 4),
+    (91, 64, [128, 128, 128, 128], 4),                       # T == R exactly
+    (60, 64, [128, 128, 128, 128], 4),                       # T < R: S = 60
+    (64, 40, [32, 64, 64, 128], 3),
+    # taps and depth
+    (16, 96, [64], 8), (50, 40, [32, 96], 6), (20, 41, [64, 64, 128, 128], 2),
+    # widths: narrowing downsamples, instance <2> (by the channels, and by the input width alone), identity residuals under a wider input
+    (40, 100, [128, 64, 32], 3), (16, 200, [160, 224], 2), (33, 200, [64, 64], 3), (16, 96, [96, 192, 256], 2), (30, 33, [32, 32], 3),
+    # degenerate: one step (96 clips per workgroup), two steps
+    (1, 96, [64, 64, 128], 3), (2, 12, [32], 2),
+]
+
+
+def _float64(fx, sd, cfg):
+    """(logits, embedding) of the float64 restatement, the stack evaluated once"""
+    e = tcn_head(fx, sd, cfg, dtype=np.float64)
+    w = {k: np.asarray(v, np.float64) for k, v in sd.items() if k.startswith("classifier.")}
+    h = oracle.heads.act(oracle.heads.linear(e, w["classifier.0.weight"], w["classifier.0.bias"]), cfg.activation)
+    return oracle.heads.linear(h, w["classifier.3.weight"], w["classifier.3.bias"]).ravel(), e
+
+
+def _fused_id(c):
+    return "%dx%d-%s-k%d" % (c[0], c[1], "_".join(map(str, c[2])), c[3])
+
+
+@pytest.mark.parametrize("T,F,ch,k", _FUSED, ids=[_fused_id(c) for c in _FUSED])
+def test_fused_instances_against_float64(T, F, ch, k):
+    """Each case must plan onto tcn_x3 (a case that lands on the fallback fails) and agree, logits and embeddings, with the float64
+    restatement and with the im2col + GEMM fallback (conv_arith = bf16x9) at batch sizes around the workgroup's clip count; a clip's
+    logit does not depend on the batch it travels in, at the workgroup seams (clips NC - 1, NC) in particular."""
+    cfg = HeadConfig("tcn", (T, F), tcn_channels=ch, tcn_kernel_size=k)
+    S = min(T, receptive_field(cfg))
+    fp = fused_plan(cfg)
+    assert fp is not None and fp["S"] == S, (fp, S)
+    NC = fp["NC"]
+    fused, generic = _model(cfg), _model(cfg, conv_arith="bf16x9")
+    text = fused.describe_plan()
+    assert "tcn_x3:" in text and f"last {S} steps of {T}" in text and "im2col:" not in text, text
+    assert "tcn_x3:" not in generic.describe_plan() and "im2col:" in generic.describe_plan(), generic.describe_plan()
+    sd = synth_state_dict(cfg)
+    worst = 0.0
+    for B in ((1, 95, 96, 97, 300) if T == 1 else (1, NC + 1, 70, 300)):
+        fx = synth_features(B, cfg.input_shape, seed=B)
+        lg, _, emb = fused.forward_features(fx, return_embedding=True)
+        ref, e_ref = _float64(fx, sd, cfg)
+        worst = max(worst, float((np.abs(lg - ref) / np.maximum(1.0, np.abs(ref))).max()))
+        assert np.isfinite(lg).all()
+        assert _close(lg, ref), (B, float(np.abs(lg - ref).max()), float(np.abs(ref).max()))
+        assert np.abs(emb - e_ref).max() <= EMB_RTOL * max(1.0, np.abs(e_ref).max()), (B, float(np.abs(emb - e_ref).max()))
+        lb, _ = generic.forward_features(fx)
+        assert _close(lg, lb), (B, float(np.abs(lg - lb).max()))
+        for i in sorted({0, NC - 1, NC, B - 1}):
+            if 0 <= i < B:
+                alone, _ = fused.forward_features(np.ascontiguousarray(fx[i:i + 1]))
+                assert alone[0] == lg[i], (B, i, alone[0], lg[i])
+    print(_fused_id((T, F, ch, k)), "S", S, "NC", NC, "instance", fp["instance"], "max |dlogit| / max(1, |logit|) vs float64: %.2e" % worst)
+    fused.close(); generic.close()
+
+
+def test_long_cone_reads_exactly_its_rows():
+    """A cone of 91 rows (three 32-row tiles): rows older than it are never read (1e30 there leaves every logit bit-identical), and the
+    rows inside it ARE read - its first row and its last, changed one at a time, change every clip's logit as the float64 restatement says
+    they must (a kernel that reads a shorter cone than the plan states passes the first half alone)."""
+    T = 101
+    cfg = HeadConfig("tcn", (T, 64), tcn_channels=[128, 128, 128, 128], tcn_kernel_size=4)
+    R = receptive_field(cfg)
+    assert R == 91
+    m = _model(cfg)
+    assert "tcn_x3:" in m.describe_plan() and f"last {R} steps" in m.describe_plan()
+    sd = synth_state_dict(cfg)
+    x = synth_features(70, cfg.input_shape, seed=3)
+    a, _ = m.forward_features(x)
+    assert _close(a, tcn_model(x, sd, cfg, dtype=np.float64))
+    y = x.copy()
+    y[:, : T - R] = 1e30
+    b, _ = m.forward_features(y)
+    assert np.array_equal(a, b)
+    base = tcn_model(x, sd, cfg, dtype=np.float64).ravel()
+    # the oldest row reaches the last step through the oldest tap of all eight convs only: + 3000 there moves every logit by >= 0.028
+    # in float64 (+ 300 on the newest row: >= 6), ten times the tolerance and more, so a kernel that drops the row cannot pass
+    for row, amp in ((T - R, 3000.0), (T - 1, 300.0)):
+        z = x.copy()
+        z[:, row] += np.float32(amp)
+        want = tcn_model(z, sd, cfg, dtype=np.float64).ravel()
+        assert np.all(np.abs(want - base) > 10 * LOGIT_ATOL), (row, np.abs(want - base).min())     # the row matters in exact arithmetic
+        c, _ = m.forward_features(z)
+        assert np.all(c != a), (row, int((c == a).sum()))
+        assert _close(c, want), (row, float(np.abs(c - want).max()))
     m.close()

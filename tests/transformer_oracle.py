@@ -28,3 +28,25 @@ def transformer_model(x, sd, cfg, dtype=F32):
     sd = {k: np.asarray(v, dtype=dtype) for k, v in sd.items()}
     h = act(linear(e, sd["classifier.0.weight"], sd["classifier.0.bias"]), cfg.activation)
     return linear(h, sd["classifier.3.weight"], sd["classifier.3.bias"]).astype(dtype)
+
+
+def top_two_score_gaps(x, sd, cfg):
+    """float64: per block, the smallest gap between the two largest scaled scores q.k / sqrt(dh) of any (clip, head, query), relative
+    to max(1, the row's largest |score|) - how far the softmax rows are from a tie in their argmax, in units of the scores' own
+    rounding (a one-hot softmax flips on a near-tie in any float32 arithmetic)."""
+    f8 = np.float64
+    w = {k: np.asarray(v, f8) for k, v in sd.items()}
+    D, nh, T = cfg.transformer_d_model, cfg.transformer_n_head, x.shape[1]
+    h = linear(np.asarray(x, f8), w["model.input_proj.weight"], w["model.input_proj.bias"]) * np.sqrt(f8(D)) + w["model.pos_encoder.pe"][:T, 0][None]
+    gaps = []
+    for i in range(cfg.n_blocks):
+        p = f"model.transformer_encoder.layers.{i}"
+        qkv = h @ w[p + ".self_attn.in_proj_weight"].T + w[p + ".self_attn.in_proj_bias"]
+        q, k = (qkv[..., j * D:(j + 1) * D].reshape(len(x), T, nh, D // nh).transpose(0, 2, 1, 3) for j in range(2))
+        s = np.sort(q @ k.transpose(0, 1, 3, 2) / np.sqrt(f8(D // nh)), axis=-1)
+        top = np.maximum(1.0, np.maximum(np.abs(s[..., 0]), np.abs(s[..., -1])))
+        gaps.append(float(((s[..., -1] - s[..., -2]) / top).min()) if T > 1 else float("inf"))
+        h = layer_norm(h + mha(h, w, p + ".self_attn", nh), w[p + ".norm1.weight"], w[p + ".norm1.bias"])
+        f = linear(np.maximum(linear(h, w[p + ".linear1.weight"], w[p + ".linear1.bias"]), 0), w[p + ".linear2.weight"], w[p + ".linear2.bias"])
+        h = layer_norm(h + f, w[p + ".norm2.weight"], w[p + ".norm2.bias"])
+    return gaps

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Random head shapes against the oracle (features in, logits out): a wider net than the parametrised GPU tests for the
 shape-dependent kernel choices (lin_x3 / ffn_x3 / mha_mfma widths and tails, conv3_x3 fits / strips / k-split passes, padded recurrent
-widths, BcResNet strips, trunk strips).
+widths, BcResNet strips, trunk strips).  Kinds "transformer" and "tcn" (not in the default set: name them) are scored against the
+restatements beside the tests; a TCN case relative to max(1, |logit|) - the head normalises nothing - and each logs whether the fused
+kernel planned.
 usage: python tools/fuzz_heads.py [n_cases] [seed] [kinds, comma-separated] [act_dtype]   (needs an MI355X)
 With act_dtype = f16 / bf16 (BcResNet only) the pass mark is 3e-2 / 2e-1 instead of 1e-4: on random features and planes of a few pixels
 the 16-bit modes are noisier than on log-mel clips (round 4: worst of 80 / 60 cases 1.7e-2 / 9.5e-2; float32 storage 3.6e-5 of 250)."""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))           # transformer_oracle / tcn_oracle: the restatements of the two newest heads
 import numpy as np
 import oracle
 from nanowakeword_amd.config import FrontendConfig, HeadConfig
@@ -14,10 +18,29 @@ from nanowakeword_amd.session import HipModel
 from nanowakeword_amd.synth import synth_features, synth_state_dict
 
 
-def run(n_cases=40, seed=0, log=print, kinds=("conformer", "crnn", "bcresnet", "cnn", "e2e_dnn", "dnn", "gru"), act_dtype=None, tol=1e-4):
-    """-> (worst |dlogit|, cases that ran)"""
+def draw_new_head(kind, rng, act):
+    """a HeadConfig of kind "transformer" / "tcn" from rng (no GPU needed: a seed's cases can be listed beforehand)"""
+    if kind == "transformer":
+        # every width with a post-norm ffn_x3 and head dims of mha_h2's exact-subtraction form; (48, 4) and (144, 8) fall back (no fused
+        # feed-forward / head dim 18); T > 128: mha_core around the fused rest
+        d, nh = [(32, 4), (32, 8), (64, 4), (64, 16), (96, 4), (128, 4), (128, 4), (128, 8), (144, 4), (192, 4), (256, 4), (256, 8), (48, 4), (144, 8)][rng.integers(0, 14)]
+        return HeadConfig("transformer", (int(rng.integers(1, 201)), int(rng.choice([32, 40, 64]))), embedding_dim=16, activation=act,
+                          transformer_d_model=d, transformer_n_head=nh, n_blocks=int(rng.integers(1, 4)))
+    # 1 .. 4 levels of multiples of 32 (two draws in three stay at <= 128: the instance whose cone may span three 32-row tiles), k 2 .. 6
+    top = 4 if rng.integers(0, 3) else 8
+    chans = [32 * int(rng.integers(1, top + 1)) for _ in range(int(rng.integers(1, 5)))]
+    return HeadConfig("tcn", (int(rng.integers(1, 121)), int(rng.choice([12, 32, 40, 41, 64, 96, 200]))), embedding_dim=16, activation=act,
+                      tcn_channels=chans, tcn_kernel_size=int(rng.integers(2, 7)))
+
+
+def run(n_cases=40, seed=0, log=print, kinds=("conformer", "crnn", "bcresnet", "cnn", "e2e_dnn", "dnn", "gru"), act_dtype=None, tol=1e-4, stats=None):
+    """-> (worst |dlogit|, cases that ran); stats (a dict, optional) receives per-kind counts: ran, refused, and for the TCN how many cases
+    planned the fused kernel and how many of those kept a cone of more than 32 rows"""
     rng = np.random.default_rng(seed)
     worst, ran = 0.0, 0
+    stats = {} if stats is None else stats
+    for key in ("ran_transformer", "ran_tcn", "refused", "tcn_fused", "tcn_fused_long_cone"):
+        stats[key] = 0
     for case in range(n_cases):
         kind = rng.choice(list(kinds))
         act = str(rng.choice(["relu", "gelu", "silu"]))
@@ -40,6 +63,8 @@ def run(n_cases=40, seed=0, log=print, kinds=("conformer", "crnn", "bcresnet", "
         elif kind == "dnn":                                 # any flattened size (K % 4 != 0 included), tiny to default widths
             cfg = HeadConfig("dnn", (int(rng.integers(4, 110)), int(rng.choice([32, 40, 41, 63, 64, 96]))), activation=act,
                              layer_dim=int(rng.choice([8, 20, 32, 128])), n_blocks=int(rng.integers(0, 3)), embedding_dim=int(rng.choice([8, 16, 64])))
+        elif kind in ("transformer", "tcn"):
+            cfg = draw_new_head(kind, rng, act)
         elif kind == "gru":
             cfg = HeadConfig("gru", (int(rng.integers(4, 110)), int(rng.choice([32, 40, 64, 96]))), embedding_dim=16, activation=act,
                              layer_dim=int(rng.choice([20, 32, 48, 64, 96, 100, 128, 160])), n_blocks=int(rng.integers(1, 3)))
@@ -52,14 +77,34 @@ def run(n_cases=40, seed=0, log=print, kinds=("conformer", "crnn", "bcresnet", "
                          act_dtype=act_dtype if kind == "bcresnet" else None)
         except (NotImplementedError, ValueError) as e:
             log(f"case {case}: {kind} {cfg.input_shape} refused at create: {str(e)[:80]}")
+            stats["refused"] += 1
             continue
         x = synth_features(B, cfg.input_shape, seed=case)
         lg, _ = m.forward_features(x)
-        ref = oracle.model_forward(x, sd, cfg).ravel()
-        err = float(np.abs(lg - ref).max())
+        note = ""
+        if kind == "transformer":
+            from transformer_oracle import transformer_model
+            ref = transformer_model(x, sd, cfg).ravel()
+            err = float(np.abs(lg - ref).max())
+            plan = m.describe_plan()
+            note = (f" d={cfg.transformer_d_model}/{cfg.transformer_n_head} blocks={cfg.n_blocks} "
+                    f"{'mha_h2' if 'mha_h2:' in plan else 'mha_core' if 'mha_core:' in plan else 'mha_mfma'} {'ffn_x3' if 'ffn_x3:' in plan else 'ffn fallback'}")
+            stats["ran_transformer"] += 1
+        elif kind == "tcn":
+            from tcn_oracle import receptive_field, tcn_model
+            ref = tcn_model(x, sd, cfg).ravel()
+            err = float((np.abs(lg - ref) / np.maximum(1.0, np.abs(ref))).max())
+            fused, S = "tcn_x3:" in m.describe_plan(), min(cfg.input_shape[0], receptive_field(cfg))
+            note = f" ch={cfg.tcn_channels} k={cfg.tcn_kernel_size} S={S} {'tcn_x3' if fused else 'fallback'} (relative)"
+            stats["ran_tcn"] += 1
+            stats["tcn_fused"] += fused
+            stats["tcn_fused_long_cone"] += fused and S > 32
+        else:
+            ref = oracle.model_forward(x, sd, cfg).ravel()
+            err = float(np.abs(lg - ref).max())
         worst, ran = max(worst, err), ran + 1
         flag = "" if err <= tol else "   <-- FAIL"
-        log(f"case {case}: {kind} {cfg.input_shape} B={B} act={act} max|dlogit| {err:.2e}{flag}")
+        log(f"case {case}: {kind} {cfg.input_shape} B={B} act={act}{note} max|dlogit| {err:.2e}{flag}")
         m.close()
     return worst, ran
 
