@@ -1,4 +1,4 @@
-"""Oracle heads: numpy float32 restatement of the in-scope classifier heads.
+"""Oracle heads: numpy float32 restatement of every in-scope classifier head (table ``_NETS``).
 
 Each function cites the reference module it follows (nanowakeword/modules/
 architectures.py, nanowakeword/modules/model.py).  Weights come in as a dict
@@ -73,6 +73,20 @@ def conv2d(x, w, b=None, stride=(1, 1), pad=(1, 1), groups=1):
     if b is not None:
         y = y + b.reshape(1, -1, 1, 1)
     return np.ascontiguousarray(y.astype(x.dtype))
+
+
+def causal_conv(x, w, b, dil):
+    """nn.Conv1d with padding (k - 1) dil and the right end chopped (TemporalBlock, architectures.py:290-331), time-major:
+    x [B,T,Cin], w [O,Cin,k], b [O] -> y [B,T,O], y[t] = b + sum_j w[:, :, j] x[t - (k - 1 - j) dil] with zero history."""
+    B, T, _ = x.shape
+    k = w.shape[2]
+    y = np.zeros((B, T, w.shape[0]), x.dtype) + b
+    for j in range(k):
+        s = (k - 1 - j) * dil
+        if s >= T:
+            continue
+        y[:, s:] += x[:, : T - s] @ w[:, :, j].T
+    return y
 
 
 def maxpool2(x):
@@ -277,8 +291,48 @@ def net_e2e_cnn_body(x, sd, cfg):
     return linear(h, sd["model.out.weight"], sd["model.out.bias"])
 
 
-_NETS = {"dnn": net_dnn, "cnn": net_cnn, "crnn": net_crnn, "gru": net_gru,
-         "bcresnet": net_bcresnet, "conformer": net_conformer, "e2e_dnn": net_e2e_cnn_body}
+def transformer_input(x, sd, cfg):
+    """TransformerModel up to the encoder (architectures.py:164-206): input_proj * sqrt(d_model) (the factor in x's own precision)
+    + pe[t] over the batch (PositionalEncoding, :41-48)."""
+    h = linear(x, sd["model.input_proj.weight"], sd["model.input_proj.bias"]) * x.dtype.type(np.sqrt(cfg.transformer_d_model))
+    return h + sd["model.pos_encoder.pe"][:x.shape[1], 0][None]
+
+
+def transformer_layer(h, sd, p, n_head):
+    """nn.TransformerEncoderLayer(batch_first=True) at torch's defaults: post-norm, ReLU, layer_norm_eps 1e-5."""
+    h = layer_norm(h + mha(h, sd, p + ".self_attn", n_head), sd[p + ".norm1.weight"], sd[p + ".norm1.bias"])
+    f = linear(np.maximum(linear(h, sd[p + ".linear1.weight"], sd[p + ".linear1.bias"]), 0), sd[p + ".linear2.weight"], sd[p + ".linear2.bias"])
+    return layer_norm(h + f, sd[p + ".norm2.weight"], sd[p + ".norm2.bias"])
+
+
+def net_transformer(x, sd, cfg):
+    """TransformerModel (architectures.py:164-206); no final norm, mean over time."""
+    h = transformer_input(x, sd, cfg)
+    for i in range(cfg.n_blocks):
+        h = transformer_layer(h, sd, f"model.transformer_encoder.layers.{i}", cfg.transformer_n_head)
+    return linear(h.mean(axis=1), sd["model.output_proj.weight"], sd["model.output_proj.bias"])
+
+
+def net_tcn(x, sd, cfg):
+    """TCNModel / TemporalBlock (architectures.py:290-367): level i is relu(relu(conv2(relu(conv1(x)))) + res) at dilation 2^i,
+    res = x or the 1x1 downsample where the widths differ; fc of the last time step."""
+    h = x
+    for i in range(len(cfg.tcn_channels)):
+        p = f"model.tcn_blocks.{i}"
+        o = np.maximum(causal_conv(h, sd[p + ".conv1.weight"], sd[p + ".conv1.bias"], 2 ** i), 0)
+        o = np.maximum(causal_conv(o, sd[p + ".conv2.weight"], sd[p + ".conv2.bias"], 2 ** i), 0)
+        res = causal_conv(h, sd[p + ".downsample.weight"], sd[p + ".downsample.bias"], 1) if p + ".downsample.weight" in sd else h
+        h = np.maximum(o + res, 0).astype(x.dtype)
+    return linear(h[:, -1], sd["model.fc.weight"], sd["model.fc.bias"])
+
+
+def tcn_receptive_field(cfg):
+    """Time steps the TCN's last step depends on: 1 + 2 (k - 1) (2^L - 1)."""
+    return 1 + 2 * (cfg.tcn_kernel_size - 1) * (2 ** len(cfg.tcn_channels) - 1)
+
+
+_NETS = {"dnn": net_dnn, "cnn": net_cnn, "crnn": net_crnn, "gru": net_gru, "bcresnet": net_bcresnet, "conformer": net_conformer,
+         "e2e_dnn": net_e2e_cnn_body, "transformer": net_transformer, "tcn": net_tcn}
 
 
 def head_forward(x, sd, cfg, dtype=F32):
@@ -289,9 +343,12 @@ def head_forward(x, sd, cfg, dtype=F32):
     return _NETS[cfg.model_type](x, sd, cfg).astype(dtype)
 
 
+def classify(e, sd, cfg, dtype=F32):
+    """Model.classifier (model.py:291-296): embedding [B,E] -> logits [B,1]."""
+    w0, b0, w3, b3 = (np.asarray(sd[k], dtype=dtype) for k in ("classifier.0.weight", "classifier.0.bias", "classifier.3.weight", "classifier.3.bias"))
+    return linear(act(linear(e, w0, b0), cfg.activation), w3, b3).astype(dtype)
+
+
 def model_forward(x, sd, cfg, dtype=F32):
-    """Model.forward (model.py:562-571): embedding -> classifier MLP (model.py:291-296) -> logits [B,1]."""
-    sd = {k: np.asarray(v, dtype=dtype) for k, v in sd.items()}
-    e = head_forward(x, sd, cfg, dtype)
-    h = act(linear(e, sd["classifier.0.weight"], sd["classifier.0.bias"]), cfg.activation)
-    return linear(h, sd["classifier.3.weight"], sd["classifier.3.bias"]).astype(dtype)
+    """Model.forward (model.py:562-571): embedding -> classifier MLP -> logits [B,1]."""
+    return classify(head_forward(x, sd, cfg, dtype), sd, cfg, dtype)

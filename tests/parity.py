@@ -28,8 +28,14 @@ and for PCM->logit, |d logit| <= 1e-4 on every broadband, silent and real-speech
 <= 2e-5); the three synthetic tonal clips (sine x2, chirp), whose logits the reference itself
 only determines to ~1e-3, get 1e-4 + 4 x the head's measured float32 noise scale on tonal input (logit_bounds).
 """
+import json
+import os
+
 import numpy as np
 
+import oracle
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DB_ATOL = 1e-4
 MEL_FRAME_REL = 3e-6
 COND_REL_FLOOR = 1e-4
@@ -97,3 +103,35 @@ def logit_bounds(names, logits_ref, logits_f32_other, logits_exact_frontend):
                     np.abs(logits_f32_other - logits_exact_frontend)[t].max())
         b[t] += 4.0 * noise
     return b
+
+
+def assert_pcm_logits_vs_reference(m, cfg, sd, g, pcm, rp, n_mels=64, center=True, names=None, extra=None, what=""):
+    """The PCM composite against the reference: m.forward_pcm(pcm) within logit_bounds of the reference's logits rp, per clip.
+    The bound's noise term comes from the oracle head on the oracle's log-mel, float32 and with a float64 frontend (g: the frontend
+    goldens' window and filterbanks; names default to its clips').  extra(lx), optional, is a per-clip allowance on top, given the
+    exact-frontend oracle logits.  -> (lp, pp, err, bound) for the caller's further assertions."""
+    names = g["names"] if names is None else names
+    fb = g["fb64"] if n_mels == 64 else g["fb40"]
+    lm32 = oracle.frontend_logmel(pcm, g["window"], fb, center=center)
+    lm64 = oracle.frontend_logmel(pcm, g["window"], fb, center=center, dtype=np.float64).astype(np.float32)
+    if cfg.model_type != "e2e_dnn":
+        lm32, lm64 = lm32.transpose(0, 2, 1), lm64.transpose(0, 2, 1)
+    l32 = oracle.model_forward(np.ascontiguousarray(lm32), sd, cfg).ravel()
+    lx = oracle.model_forward(np.ascontiguousarray(lm64), sd, cfg).ravel()
+    bound = logit_bounds(names, rp, l32, lx)
+    if extra is not None:
+        bound = bound + extra(lx)
+    lp, pp = m.forward_pcm(pcm)
+    err = np.abs(lp - rp)
+    assert np.all(err <= bound), (what, [f"{n}: {e:.2e} > {b:.2e}" for n, e, b in zip(names, err, bound) if e > b])
+    return lp, pp, err, bound
+
+
+def load_head_goldens(filename):
+    """A per-head golden file (tests/golden/heads_<head>.npz) -> (arrays, {case name: HeadConfig fields})."""
+    d = dict(np.load(os.path.join(GOLDEN, filename), allow_pickle=False))
+    return d, json.loads(str(d["meta_json"]))
+
+
+def head_golden_names(filename):
+    return sorted(load_head_goldens(filename)[1])

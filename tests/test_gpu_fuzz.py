@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
 
-# picked for what its 30 draws cover, from a listing made without a GPU (fuzz_heads.draw_new_head + tcn_oracle.fused_plan): 14 Transformer
+# picked for what its 30 draws cover, from a listing made without a GPU (fuzz_heads.draw_new_head + test_gpu_tcn.fused_plan): 14 Transformer
 # and 16 TCN cases, all 16 on the fused kernel, 6 of them with a cone longer than 32 rows
 NEW_HEADS_SEED = 18
 

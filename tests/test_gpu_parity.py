@@ -6,9 +6,7 @@ import oracle
 from conftest import head_case_names
 from nanowakeword_amd.config import FrontendConfig, HeadConfig
 from nanowakeword_amd.synth import synth_features, synth_pcm, synth_state_dict
-from parity import assert_frontend_amplitude, assert_frontend_close, frontend_errors, logit_bounds
-from tcn_oracle import tcn_model
-from transformer_oracle import transformer_model
+from parity import assert_frontend_amplitude, assert_frontend_close, assert_pcm_logits_vs_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -121,18 +119,7 @@ def test_head_vs_oracle_and_golden(hip, golden_heads, golden_frontend, name):
         assert np.abs(lg - lo).max() <= FEAT_LOGIT_ATOL, (name, B, np.abs(lg - lo).max())
     # (ii) PCM -> logits through the fused frontend, vs the reference composite
     if f"{name}/logits_pcm" in d:
-        rp = d[f"{name}/logits_pcm"].ravel()
-        lp, pp = m.forward_pcm(g["pcm"])
-        fb = g["fb64"] if n_mels == 64 else g["fb40"]
-        lm32 = oracle.frontend_logmel(g["pcm"], g["window"], fb, center=center)
-        lm64 = oracle.frontend_logmel(g["pcm"], g["window"], fb, center=center, dtype=np.float64).astype(np.float32)
-        if cfg.model_type != "e2e_dnn":
-            lm32, lm64 = lm32.transpose(0, 2, 1), lm64.transpose(0, 2, 1)
-        l32 = oracle.model_forward(np.ascontiguousarray(lm32), sd, cfg).ravel()
-        lx = oracle.model_forward(np.ascontiguousarray(lm64), sd, cfg).ravel()
-        bound = logit_bounds(g["names"], rp, l32, lx)
-        err = np.abs(lp - rp)
-        assert np.all(err <= bound), (name, [f"{n}: {e:.2e} > {b:.2e}" for n, e, b in zip(g["names"], err, bound) if e > b])
+        lp, pp, err, _ = assert_pcm_logits_vs_reference(m, cfg, sd, g, g["pcm"], d[f"{name}/logits_pcm"].ravel(), n_mels, center, what=name)
         print(f"{name}: max |dlogit| vs reference = {err.max():.2e} (broadband/speech clips: "
               f"{err[[i for i, n in enumerate(g['names']) if not str(n).startswith(('sine', 'chirp'))]].max():.2e})")
         assert np.abs(pp - oracle.sigmoid(lp)).max() <= 1e-6
@@ -367,21 +354,12 @@ _F64_HEADS = (("cnn", (101, 64), {}), ("dnn", (98, 40), {}), ("crnn", (101, 64),
               ("tcn", (101, 64), {"tcn_channels": [64, 64, 128, 128]}))          # a 61-step cone: two 32-row tiles
 
 
-def _float64_logits(feats, sd, cfg):
-    """The same network in float64: the oracle package's heads, and the two restatements that live beside the tests."""
-    if cfg.model_type == "transformer":
-        return transformer_model(feats, sd, cfg, dtype=np.float64).ravel()
-    if cfg.model_type == "tcn":
-        return tcn_model(feats, sd, cfg, dtype=np.float64).ravel()
-    return oracle.model_forward(feats, sd, cfg, dtype=np.float64).ravel()
-
-
 # the TCN contract of test_gpu_tcn.py (LOGIT_ATOL + LOGIT_ULPS |ref|): two float32 ulps of the logit on top of the 1e-4 bar
 TCN_LOGIT_ULPS = 2.4e-7
 
 
 def _arith_errors_vs_float64(HipModel, cfg, sd, feats, modes=("f32", "bf16x9", "bf16x6", "f16x3"), tcn_contract=False):
-    ref = _float64_logits(feats, sd, cfg)
+    ref = oracle.model_forward(feats, sd, cfg, dtype=np.float64).ravel()              # the same network in float64
     err = {}
     for mode in modes:
         m = HipModel(cfg, FrontendConfig(n_mels=cfg.input_shape[1]), state_dict=sd, conv_arith=mode)

@@ -11,27 +11,18 @@ import pytest
 import oracle
 from nanowakeword_amd.config import FrontendConfig, HeadConfig
 from nanowakeword_amd.synth import synth_features, synth_state_dict
-from parity import logit_bounds
-from transformer_oracle import top_two_score_gaps, transformer_head, transformer_model
+from oracle.heads import transformer_input, transformer_layer
+from parity import GOLDEN, assert_pcm_logits_vs_reference, head_golden_names, load_head_goldens
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 LOGIT_ATOL = 1e-4
 EMB_RTOL = 1e-4
 
 
-def _cfg(meta):
-    m = dict(meta)
-    m["input_shape"] = tuple(m["input_shape"])
-    return HeadConfig(**m)
-
-
 @pytest.fixture(scope="module")
 def golden():
-    d = dict(np.load(os.path.join(GOLDEN, "heads_transformer.npz"), allow_pickle=False))
-    return d, json.loads(str(d["meta_json"]))
+    return load_head_goldens("heads_transformer.npz")
 
 
 def _model(cfg, **kw):
@@ -39,15 +30,10 @@ def _model(cfg, **kw):
     return HipModel(cfg, FrontendConfig(), state_dict=synth_state_dict(cfg), **kw)
 
 
-def _golden_names():
-    d = np.load(os.path.join(GOLDEN, "heads_transformer.npz"), allow_pickle=False)
-    return sorted(json.loads(str(d["meta_json"])))
-
-
-@pytest.mark.parametrize("name", _golden_names())
+@pytest.mark.parametrize("name", head_golden_names("heads_transformer.npz"))
 def test_features_vs_reference(golden, name):
     d, meta = golden
-    cfg = _cfg(meta[name])
+    cfg = HeadConfig(**meta[name])
     m = _model(cfg)
     assert m.feature_clamp == 0.0, m.describe_plan()
     feats = d[f"{name}/feats"]
@@ -61,7 +47,7 @@ def test_features_vs_reference(golden, name):
     for B in (1, 3, 33, 70):
         fx = synth_features(B, cfg.input_shape, seed=B)
         lg, _ = m.forward_features(fx)
-        lo = transformer_model(fx, sd, cfg).ravel()
+        lo = oracle.model_forward(fx, sd, cfg).ravel()
         assert np.abs(lg - lo).max() <= LOGIT_ATOL, (name, B, np.abs(lg - lo).max())
     m.close()
 
@@ -71,18 +57,10 @@ def test_pcm_vs_reference(golden, golden_frontend):
     d, meta = golden
     g = golden_frontend
     name = "transformer_101x64"
-    cfg = _cfg(meta[name])
+    cfg = HeadConfig(**meta[name])
     sd = synth_state_dict(cfg)
     m = HipModel(cfg, FrontendConfig(), state_dict=sd, window=g["window"], mel_fb=g["fb64"])
-    rp = d[f"{name}/logits_pcm"].ravel()
-    lp, pp = m.forward_pcm(g["pcm"])
-    lm32 = oracle.frontend_logmel(g["pcm"], g["window"], g["fb64"], center=True).transpose(0, 2, 1)
-    lm64 = oracle.frontend_logmel(g["pcm"], g["window"], g["fb64"], center=True, dtype=np.float64).astype(np.float32).transpose(0, 2, 1)
-    l32 = transformer_model(np.ascontiguousarray(lm32), sd, cfg).ravel()
-    lx = transformer_model(np.ascontiguousarray(lm64), sd, cfg).ravel()
-    bound = logit_bounds(g["names"], rp, l32, lx)
-    err = np.abs(lp - rp)
-    assert np.all(err <= bound), [f"{n}: {e:.2e} > {b:.2e}" for n, e, b in zip(g["names"], err, bound) if e > b]
+    lp, pp, _, _ = assert_pcm_logits_vs_reference(m, cfg, sd, g, g["pcm"], d[f"{name}/logits_pcm"].ravel(), what=name)
     assert np.abs(pp - oracle.sigmoid(lp)).max() <= 1e-6
     m.close()
 
@@ -96,7 +74,7 @@ def test_onnx_and_pt_through_the_session(tmp_path):
     s = load_session(os.path.join(GOLDEN, "onnx", "transformer.onnx"))
     assert np.abs(s.run(None, {"input": feats})[0].reshape(-1) - want).max() <= 1e-5
     # a .pt of the same weights -> bundle (n_head given: the weights do not record it) -> session
-    cfg = _cfg(json.loads(str(e["meta_json"]))["transformer"])
+    cfg = HeadConfig(**json.loads(str(e["meta_json"]))["transformer"])
     pt = str(tmp_path / "transformer.pt")
     torch.save({k: torch.from_numpy(v) for k, v in synth_state_dict(cfg).items()}, pt)
     sd = state_dict_from_pt(pt)
@@ -130,8 +108,8 @@ def test_fallback_width_matches_restatement():
     sd = synth_state_dict(cfg)
     fx = synth_features(37, cfg.input_shape, seed=5)
     lg, _, emb = m.forward_features(fx, return_embedding=True)
-    e_or = transformer_head(fx, sd, cfg)
-    assert np.abs(lg - transformer_model(fx, sd, cfg).ravel()).max() <= LOGIT_ATOL
+    e_or = oracle.head_forward(fx, sd, cfg)
+    assert np.abs(lg - oracle.model_forward(fx, sd, cfg).ravel()).max() <= LOGIT_ATOL
     assert np.abs(emb - e_or).max() <= EMB_RTOL * max(1.0, np.abs(e_or).max())
     m.close()
     # 12 input features: no short-K instance - the general GEMM, then the scale and the positional rows in one elementwise pass
@@ -139,7 +117,7 @@ def test_fallback_width_matches_restatement():
     m = _model(cfg)
     assert "gemm:input_proj" in m.describe_plan() and "scale+pe:" in m.describe_plan()
     fx = synth_features(9, cfg.input_shape, seed=6)
-    assert np.abs(m.forward_features(fx)[0] - transformer_model(fx, synth_state_dict(cfg), cfg).ravel()).max() <= LOGIT_ATOL
+    assert np.abs(m.forward_features(fx)[0] - oracle.model_forward(fx, synth_state_dict(cfg), cfg).ravel()).max() <= LOGIT_ATOL
     m.close()
 
 
@@ -152,7 +130,7 @@ def test_batch_invariance(shape, B):
     for i in (0, B - 1):
         alone, _ = m.forward_features(np.ascontiguousarray(x[i:i + 1]))
         assert alone[0] == full[i], (shape, i, alone[0], full[i])
-    ref = transformer_model(x[:8], synth_state_dict(cfg), cfg).ravel()
+    ref = oracle.model_forward(x[:8], synth_state_dict(cfg), cfg).ravel()
     assert np.abs(full[:8] - ref).max() <= LOGIT_ATOL
     m.close()
 
@@ -166,14 +144,6 @@ def test_create_validates_heads():
 
 
 FFN_WIDTHS = (32, 64, 96, 128, 144, 192, 256)             # the post-norm ffn_x3 instances (ffn_x3_post_supported)
-
-
-def _float64(fx, sd, cfg):
-    """(logits, embedding) of the float64 restatement, the encoder evaluated once"""
-    e = transformer_head(fx, sd, cfg, dtype=np.float64)
-    w = {k: np.asarray(v, np.float64) for k, v in sd.items() if k.startswith("classifier.")}
-    h = oracle.heads.act(oracle.heads.linear(e, w["classifier.0.weight"], w["classifier.0.bias"]), cfg.activation)
-    return oracle.heads.linear(h, w["classifier.3.weight"], w["classifier.3.bias"]).ravel(), e
 
 
 def _check_against_float64(cfg, attn, ffn_fused, batches=(1, 3, 33, 70)):
@@ -193,7 +163,8 @@ def _check_against_float64(cfg, attn, ffn_fused, batches=(1, 3, 33, 70)):
     for B in batches:
         fx = synth_features(B, cfg.input_shape, seed=B)
         lg, _, emb = m.forward_features(fx, return_embedding=True)
-        ref, e_ref = _float64(fx, sd, cfg)
+        e_ref = oracle.head_forward(fx, sd, cfg, dtype=np.float64)                  # the encoder evaluated once
+        ref = oracle.classify(e_ref, sd, cfg, dtype=np.float64).ravel()
         assert np.isfinite(lg).all()
         worst = max(worst, float(np.abs(lg - ref).max()))
         assert np.abs(lg - ref).max() <= LOGIT_ATOL, (B, float(np.abs(lg - ref).max()), text)
@@ -231,6 +202,26 @@ def test_beyond_the_attention_kernels(T, D, heads, attn):
     print("T", T, "D", D, "heads", heads, "max |dlogit| vs float64: %.2e" % worst)
 
 
+def top_two_score_gaps(x, sd, cfg):
+    """float64: per block, the smallest gap between the two largest scaled scores q.k / sqrt(dh) of any (clip, head, query), relative
+    to max(1, the row's largest |score|) - how far the softmax rows are from a tie in their argmax, in units of the scores' own
+    rounding (a one-hot softmax flips on a near-tie in any float32 arithmetic)."""
+    f8 = np.float64
+    w = {k: np.asarray(v, f8) for k, v in sd.items()}
+    D, nh, T = cfg.transformer_d_model, cfg.transformer_n_head, x.shape[1]
+    h = transformer_input(np.asarray(x, f8), w, cfg)
+    gaps = []
+    for i in range(cfg.n_blocks):
+        p = f"model.transformer_encoder.layers.{i}"
+        qkv = h @ w[p + ".self_attn.in_proj_weight"].T + w[p + ".self_attn.in_proj_bias"]
+        q, k = (qkv[..., j * D:(j + 1) * D].reshape(len(x), T, nh, D // nh).transpose(0, 2, 1, 3) for j in range(2))
+        s = np.sort(q @ k.transpose(0, 1, 3, 2) / np.sqrt(f8(D // nh)), axis=-1)
+        top = np.maximum(1.0, np.maximum(np.abs(s[..., 0]), np.abs(s[..., -1])))
+        gaps.append(float(((s[..., -1] - s[..., -2]) / top).min()) if T > 1 else float("inf"))
+        h = transformer_layer(h, w, p, nh)
+    return gaps
+
+
 def _peaked(sd, cfg, s):
     """the q and k rows of every in_proj x s: raw scores x s^2"""
     D = cfg.transformer_d_model
@@ -260,9 +251,9 @@ def test_peaked_softmax(s, loud_row):
         x[1, 7] *= np.float32(1e4)
     else:
         assert min(top_two_score_gaps(x, sd, cfg)) >= 1e-4
-    ref = transformer_model(x, sd, cfg, dtype=np.float64).ravel()
+    ref = oracle.model_forward(x, sd, cfg, dtype=np.float64).ravel()
     tol = LOGIT_ATOL * np.maximum(1.0, np.abs(ref))
-    assert np.all(np.abs(transformer_model(x, sd, cfg).ravel() - ref) <= 0.1 * tol)
+    assert np.all(np.abs(oracle.model_forward(x, sd, cfg).ravel() - ref) <= 0.1 * tol)
     from nanowakeword_amd.session import HipModel
     m = HipModel(cfg, FrontendConfig(), state_dict=sd)
     assert m.feature_clamp == 0.0 and "mha_h2:" in m.describe_plan() and "post-norm" in m.describe_plan(), m.describe_plan()
@@ -285,6 +276,6 @@ def test_batch_invariance_many_clips_per_tile():
     for i in (0, 6, 7, B - 1):
         alone, _ = m.forward_features(np.ascontiguousarray(x[i:i + 1]))
         assert alone[0] == full[i], (i, alone[0], full[i])
-    ref = transformer_model(x[:40], synth_state_dict(cfg), cfg, dtype=np.float64).ravel()
+    ref = oracle.model_forward(x[:40], synth_state_dict(cfg), cfg, dtype=np.float64).ravel()
     assert np.abs(full[:40] - ref).max() <= LOGIT_ATOL
     m.close()

@@ -13,7 +13,7 @@ import oracle
 from conftest import head_case_names_r02, head_case_names_r04, head_case_names_r06
 from nanowakeword_amd.config import FrontendConfig, HeadConfig
 from nanowakeword_amd.synth import synth_features, synth_pcm, synth_state_dict
-from parity import logit_bounds
+from parity import assert_pcm_logits_vs_reference
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,14 +36,8 @@ def test_round2_heads_vs_reference(HipModel, golden_heads_r02, golden_frontend, 
     m = HipModel(cfg, fe, state_dict=sd, window=g["window"], mel_fb=g["fb64"] if n_mels == 64 else g["fb40"])
     if cfg.model_type == "e2e_dnn":
         # clip length 24 000 / 32 000: general export-form average pool (a17), through the PCM entry point
-        pcm = d[f"{name}/pcm"]
-        lp, pp = m.forward_pcm(pcm)
-        rp = d[f"{name}/logits_pcm"].ravel()
-        lm32 = oracle.frontend_logmel(pcm, g["window"], g["fb64"])
-        lm64 = oracle.frontend_logmel(pcm, g["window"], g["fb64"], dtype=np.float64).astype(np.float32)
-        bound = logit_bounds(["noise0", "noise1", "speechlike0", "speechlike1", "loud0", "zeros0"], rp,
-                             oracle.model_forward(lm32, sd, cfg).ravel(), oracle.model_forward(lm64, sd, cfg).ravel())
-        assert np.all(np.abs(lp - rp) <= bound), (name, np.abs(lp - rp), bound)
+        _, pp, _, bound = assert_pcm_logits_vs_reference(m, cfg, sd, g, d[f"{name}/pcm"], d[f"{name}/logits_pcm"].ravel(), what=name,
+                                                         names=["noise0", "noise1", "speechlike0", "speechlike1", "loud0", "zeros0"])
         assert np.all(np.abs(pp - d[f"{name}/probs_pcm_export"].ravel()) <= bound)
         m.close()
         return
@@ -58,13 +52,7 @@ def test_round2_heads_vs_reference(HipModel, golden_heads_r02, golden_frontend, 
         lg, _ = m.forward_features(fx)
         assert np.abs(lg - oracle.model_forward(fx, sd, cfg).ravel()).max() <= 1e-4, (name, B)
     if f"{name}/logits_pcm" in d:
-        rp = d[f"{name}/logits_pcm"].ravel()
-        lp, _ = m.forward_pcm(g["pcm"])
-        lm32 = oracle.frontend_logmel(g["pcm"], g["window"], g["fb64"]).transpose(0, 2, 1)
-        lm64 = oracle.frontend_logmel(g["pcm"], g["window"], g["fb64"], dtype=np.float64).astype(np.float32).transpose(0, 2, 1)
-        bound = logit_bounds(g["names"], rp, oracle.model_forward(np.ascontiguousarray(lm32), sd, cfg).ravel(),
-                             oracle.model_forward(np.ascontiguousarray(lm64), sd, cfg).ravel())
-        assert np.all(np.abs(lp - rp) <= bound), (name, np.abs(lp - rp), bound)
+        assert_pcm_logits_vs_reference(m, cfg, sd, g, g["pcm"], d[f"{name}/logits_pcm"].ravel(), what=name)
     m.close()
 
 
@@ -595,15 +583,7 @@ def test_round4_heads_vs_reference(HipModel, golden_heads_r04, golden_frontend, 
         l1, _ = m.forward_features(fx[:1])
         assert l1[0] == lg[0], (name, B, "batch dependence")
     if f"{name}/logits_pcm" in d and cfg.input_shape in ((101, 64), (98, 40)):
-        lp, _ = m.forward_pcm(g["pcm"])
-        rp = d[f"{name}/logits_pcm"].ravel()
-        center = n_mels == 64
-        fb = g["fb64"] if center else g["fb40"]
-        lm32 = oracle.frontend_logmel(g["pcm"], g["window"], fb, n_mels=n_mels, center=center).transpose(0, 2, 1)
-        lm64 = oracle.frontend_logmel(g["pcm"], g["window"], fb, n_mels=n_mels, center=center, dtype=np.float64).astype(np.float32).transpose(0, 2, 1)
-        bound = logit_bounds([str(n) for n in g["names"]], rp, oracle.model_forward(np.ascontiguousarray(lm32), sd, cfg).ravel(),
-                             oracle.model_forward(np.ascontiguousarray(lm64), sd, cfg).ravel())
-        assert np.all(np.abs(lp - rp) <= bound), (name, np.abs(lp - rp), bound)
+        assert_pcm_logits_vs_reference(m, cfg, sd, g, g["pcm"], d[f"{name}/logits_pcm"].ravel(), n_mels, center=n_mels == 64, what=name)
     m.close()
 
 
@@ -773,11 +753,5 @@ def test_round6_heads_vs_reference(HipModel, golden_heads_r06, golden_frontend, 
         l1, _ = m.forward_features(fx[:1])
         assert l1[0] == lg[0], (name, B, "batch dependence")
     if f"{name}/logits_pcm" in d:
-        lp, _ = m.forward_pcm(g["pcm"])
-        rp = d[f"{name}/logits_pcm"].ravel()
-        lm32 = oracle.frontend_logmel(g["pcm"], g["window"], g["fb64"]).transpose(0, 2, 1)
-        lm64 = oracle.frontend_logmel(g["pcm"], g["window"], g["fb64"], dtype=np.float64).astype(np.float32).transpose(0, 2, 1)
-        bound = logit_bounds([str(n) for n in g["names"]], rp, oracle.model_forward(np.ascontiguousarray(lm32), sd, cfg).ravel(),
-                             oracle.model_forward(np.ascontiguousarray(lm64), sd, cfg).ravel())
-        assert np.all(np.abs(lp - rp) <= bound), (name, np.abs(lp - rp), bound)
+        assert_pcm_logits_vs_reference(m, cfg, sd, g, g["pcm"], d[f"{name}/logits_pcm"].ravel(), what=name)
     m.close()

@@ -7,24 +7,17 @@ import re
 import numpy as np
 import pytest
 
+import oracle
 from nanowakeword_amd.config import HEAD_CODE, FrontendConfig, HeadConfig, head_macs, param_spec
 from nanowakeword_amd.synth import state_dict_checksum, synth_features, synth_state_dict
-from tcn_oracle import receptive_field, tcn_head, tcn_model
+from parity import GOLDEN, load_head_goldens
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    d = dict(np.load(os.path.join(GOLDEN, "heads_tcn.npz"), allow_pickle=False))
-    return d, json.loads(str(d["meta_json"]))
-
-
-def _cfg(meta):
-    m = dict(meta)
-    m["input_shape"] = tuple(m["input_shape"])
-    return HeadConfig(**m)
+    return load_head_goldens("heads_tcn.npz")
 
 
 def test_head_code_matches_header():
@@ -53,7 +46,7 @@ def test_config_rejects_what_the_reference_or_the_abi_cannot_take():
 def test_param_spec_equals_reference_state_dict(golden):
     d, meta = golden
     for name, m in meta.items():
-        cfg = _cfg(m)
+        cfg = HeadConfig(**m)
         ref = [(k, tuple(s)) for k, s in json.loads(str(d[f"{name}/ref_spec_json"])) if not k.endswith("num_batches_tracked")]
         assert sorted(ref) == sorted(param_spec(cfg).items()), name
     # the downsample exists only where the widths differ: (101, 64) block 0 has none, (16, 96) block 0 has one
@@ -102,15 +95,15 @@ def test_restatement_matches_reference_golden(golden):
     assert {"tcn_16x96", "tcn_101x64", "tcn_98x40", "tcn_16x96_guide", "tcn_33x64_nods", "tcn_5x12", "tcn_16x96_outlier",
             "tcn_16x96_gelu"} <= set(meta)
     for name, m in meta.items():
-        cfg = _cfg(m)
+        cfg = HeadConfig(**m)
         sd = synth_state_dict(cfg)
         assert state_dict_checksum(sd) == str(d[f"{name}/sd_checksum"]), name
         feats = d[f"{name}/feats"]
-        emb = tcn_head(feats, sd, cfg)
+        emb = oracle.head_forward(feats, sd, cfg)
         ref_e = d[f"{name}/emb_feat"]
         assert np.abs(emb - ref_e).max() <= 1e-5 * max(1.0, np.abs(ref_e).max()), (name, np.abs(emb - ref_e).max())
         ref = d[f"{name}/logits_feat"]
-        lg = tcn_model(feats, sd, cfg)
+        lg = oracle.model_forward(feats, sd, cfg)
         assert np.all(np.abs(lg - ref) <= 1e-5 * np.maximum(1.0, np.abs(ref))), (name, np.abs(lg - ref).max())
     # the outlier case differs from its plain twin in exactly the clip with the loud frame
     a, b = d["tcn_16x96/logits_feat"].ravel(), d["tcn_16x96_outlier/logits_feat"].ravel()
@@ -121,15 +114,15 @@ def test_restatement_matches_reference_golden(golden):
 def test_restatement_reads_only_the_cone():
     """The head depends on the last 1 + 2 (k - 1) (2^L - 1) steps only (29 at the defaults, 91 for the guide's stack)."""
     cfg = HeadConfig("tcn", (101, 64))
-    assert receptive_field(cfg) == 29
-    assert receptive_field(HeadConfig("tcn", (16, 96), tcn_channels=[128, 128, 256, 256], tcn_kernel_size=4)) == 91
+    assert oracle.tcn_receptive_field(cfg) == 29
+    assert oracle.tcn_receptive_field(HeadConfig("tcn", (16, 96), tcn_channels=[128, 128, 256, 256], tcn_kernel_size=4)) == 91
     sd = synth_state_dict(cfg)
     x = synth_features(3, cfg.input_shape, seed=4)
     y = x.copy()
     y[:, : 101 - 29] = 1e3
-    assert np.array_equal(tcn_model(x, sd, cfg), tcn_model(y, sd, cfg))
+    assert np.array_equal(oracle.model_forward(x, sd, cfg), oracle.model_forward(y, sd, cfg))
     y[:, 101 - 29] += 1.0
-    assert not np.array_equal(tcn_model(x, sd, cfg), tcn_model(y, sd, cfg))
+    assert not np.array_equal(oracle.model_forward(x, sd, cfg), oracle.model_forward(y, sd, cfg))
 
 
 def test_pt_ingestion(tmp_path):
@@ -151,11 +144,11 @@ def test_pt_ingestion(tmp_path):
 def test_onnx_ingestion():
     from nanowakeword_amd.weights import state_dict_from_onnx
     e = dict(np.load(os.path.join(GOLDEN, "onnx", "expected_tcn.npz"), allow_pickle=False))
-    want = _cfg(json.loads(str(e["meta_json"]))["tcn"])
+    want = HeadConfig(**json.loads(str(e["meta_json"]))["tcn"])
     cfg, sd, info = state_dict_from_onnx(os.path.join(GOLDEN, "onnx", "tcn.onnx"))
     assert info["mode"] == "features" and info["input_ndim"] == 3
     assert cfg == want and cfg.tcn_channels == [16, 32]
     ref = synth_state_dict(want)
     assert set(sd) == set(ref) and all(np.array_equal(sd[k], ref[k]) for k in ref)
-    lg = tcn_model(e["tcn/feats"], sd, cfg).ravel()
+    lg = oracle.model_forward(e["tcn/feats"], sd, cfg).ravel()
     assert np.abs(lg - e["tcn/logits"]).max() <= 1e-5

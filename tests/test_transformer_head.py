@@ -7,24 +7,17 @@ import re
 import numpy as np
 import pytest
 
+import oracle
 from nanowakeword_amd.config import HEAD_CODE, FrontendConfig, HeadConfig, head_macs, param_spec
 from nanowakeword_amd.synth import positional_encoding, state_dict_checksum, synth_state_dict
-from transformer_oracle import transformer_head, transformer_model
+from parity import GOLDEN, load_head_goldens
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    d = dict(np.load(os.path.join(GOLDEN, "heads_transformer.npz"), allow_pickle=False))
-    return d, json.loads(str(d["meta_json"]))
-
-
-def _cfg(meta):
-    m = dict(meta)
-    m["input_shape"] = tuple(m["input_shape"])
-    return HeadConfig(**m)
+    return load_head_goldens("heads_transformer.npz")
 
 
 def test_head_code_matches_header():
@@ -41,7 +34,7 @@ def test_head_code_matches_header():
 def test_param_spec_equals_reference_state_dict(golden):
     d, meta = golden
     for name, m in meta.items():
-        cfg = _cfg(m)
+        cfg = HeadConfig(**m)
         ref = [(k, tuple(s)) for k, s in json.loads(str(d[f"{name}/ref_spec_json"])) if not k.endswith("num_batches_tracked")]
         assert sorted(ref) == sorted(param_spec(cfg).items()), name
         assert param_spec(cfg)["model.pos_encoder.pe"] == (5000, 1, cfg.transformer_d_model)
@@ -79,14 +72,14 @@ def test_synth_pe_is_the_sinusoidal_table():
 def test_restatement_matches_reference_golden(golden):
     d, meta = golden
     for name, m in meta.items():
-        cfg = _cfg(m)
+        cfg = HeadConfig(**m)
         sd = synth_state_dict(cfg)
         assert state_dict_checksum(sd) == str(d[f"{name}/sd_checksum"]), name
         feats = d[f"{name}/feats"]
-        emb = transformer_head(feats, sd, cfg)
+        emb = oracle.head_forward(feats, sd, cfg)
         ref_e = d[f"{name}/emb_feat"]
         assert np.abs(emb - ref_e).max() <= 1e-5 * max(1.0, np.abs(ref_e).max()), (name, np.abs(emb - ref_e).max())
-        lg = transformer_model(feats, sd, cfg)
+        lg = oracle.model_forward(feats, sd, cfg)
         assert np.abs(lg - d[f"{name}/logits_feat"]).max() <= 1e-5, (name, np.abs(lg - d[f"{name}/logits_feat"]).max())
     # the outlier case differs from its plain twin in exactly the clip with the loud frame
     a, b = d["transformer_16x96/logits_feat"].ravel(), d["transformer_16x96_outlier/logits_feat"].ravel()
@@ -114,11 +107,11 @@ def test_pt_ingestion(tmp_path):
 def test_onnx_ingestion():
     from nanowakeword_amd.weights import state_dict_from_onnx
     e = dict(np.load(os.path.join(GOLDEN, "onnx", "expected_transformer.npz"), allow_pickle=False))
-    want = _cfg(json.loads(str(e["meta_json"]))["transformer"])
+    want = HeadConfig(**json.loads(str(e["meta_json"]))["transformer"])
     cfg, sd, info = state_dict_from_onnx(os.path.join(GOLDEN, "onnx", "transformer.onnx"))
     assert info["mode"] == "features" and info["input_ndim"] == 3
     assert cfg == want and cfg.transformer_n_head == 8
     ref = synth_state_dict(want)
     assert set(sd) == set(ref) and all(np.array_equal(sd[k], ref[k]) for k in ref)
-    lg = transformer_model(e["transformer/feats"], sd, cfg).ravel()
+    lg = oracle.model_forward(e["transformer/feats"], sd, cfg).ravel()
     assert np.abs(lg - e["transformer/logits"]).max() <= 1e-5
