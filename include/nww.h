@@ -44,6 +44,7 @@ extern "C" {
 #define NWW_HEAD_E2E_DNN 6     /* E2E_MelSpectrogram_CNN  architectures.py:820-889 */
 #define NWW_HEAD_TRANSFORMER 7 /* TransformerModel        architectures.py:164-206 */
 #define NWW_HEAD_TCN 8         /* TCNModel                architectures.py:290-367 */
+#define NWW_HEAD_E_BRANCHFORMER 9 /* EBranchformerModel   architectures.py:546-616 */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1
@@ -74,8 +75,9 @@ typedef struct nww_config {
        tcn_kernel_size (>= 2) travels in layer_dim (TCNModel reads no layer_dim)                                        */
     int32_t n_crnn_channels;
     int32_t crnn_channels[4];
-    /* d_model / n_head of the attention encoder (Conformer, Transformer): conformer_d_model / conformer_n_head for
-       NWW_HEAD_CONFORMER, transformer_d_model / transformer_n_head (model.py:200-201) for NWW_HEAD_TRANSFORMER      */
+    /* d_model / n_head of the attention encoder (Conformer, Transformer, E-Branchformer): conformer_d_model / conformer_n_head
+       for NWW_HEAD_CONFORMER, transformer_d_model / transformer_n_head (model.py:200-201) for NWW_HEAD_TRANSFORMER,
+       branchformer_d_model / branchformer_n_head (model.py:263-274) for NWW_HEAD_E_BRANCHFORMER                          */
     int32_t conformer_d_model, conformer_n_head;
     /* how nww_forward_pcm feeds the head: 0 = log-mel transposed to (frames, n_mels) =
        Model(input_shape=(frames, n_mels)); 1 = (n_mels, frames) as E2E_MelSpectrogram_CNN.   */

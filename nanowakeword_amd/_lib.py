@@ -175,6 +175,8 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
     # the two slots carry d_model / n_head of whichever attention encoder the head has (include/nww.h)
     if head.model_type == "transformer":
         c.conformer_d_model, c.conformer_n_head = head.transformer_d_model, head.transformer_n_head
+    elif head.model_type == "e_branchformer":
+        c.conformer_d_model, c.conformer_n_head = head.branchformer_d_model, head.branchformer_n_head
     else:
         c.conformer_d_model, c.conformer_n_head = head.conformer_d_model, head.conformer_n_head
     c.crnn_rnn_lstm = int(head.model_type == "crnn" and head.crnn_rnn_type == "lstm")

@@ -15,11 +15,12 @@ from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn")
+HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn", "e_branchformer")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
-HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8}
+HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8,
+             "e_branchformer": 9}
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
 # rows of the Transformer's positional-encoding buffer (PositionalEncoding(max_len=5000), architectures.py:31)
 PE_MAX_LEN = 5000
@@ -67,6 +68,8 @@ class HeadConfig:
     transformer_n_head: int = 4
     tcn_channels: List[int] = field(default_factory=lambda: [64, 64, 128])   # model.py:228-229 config keys of the TCN head
     tcn_kernel_size: int = 3
+    branchformer_d_model: int = 144    # model.py:263-274 config keys of the E-Branchformer head
+    branchformer_n_head: int = 4
 
     def __post_init__(self):
         self.model_type = self.model_type.lower()
@@ -90,6 +93,13 @@ class HeadConfig:
                 raise ValueError(f"tcn_channels must be positive (got {self.tcn_channels})")
             if self.tcn_kernel_size < 2:
                 raise ValueError(f"tcn_kernel_size must be >= 2 (got {self.tcn_kernel_size})")
+
+        self.branchformer_d_model, self.branchformer_n_head = int(self.branchformer_d_model), int(self.branchformer_n_head)
+        if self.model_type == "e_branchformer":
+            # nn.MultiheadAttention's own requirement (embed_dim divisible by num_heads)
+            if self.branchformer_d_model <= 0 or self.branchformer_n_head <= 0 or self.branchformer_d_model % self.branchformer_n_head:
+                raise ValueError(f"branchformer_d_model must be divisible by branchformer_n_head "
+                                 f"(got {self.branchformer_d_model} / {self.branchformer_n_head})")
 
     def to_dict(self):
         return asdict(self)
@@ -204,6 +214,26 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
             _ln(s, f"{p}.norm1", D)
             _ln(s, f"{p}.norm2", D)
         _lin(s, "model.output_proj", E, D)
+    elif mt == "e_branchformer":          # architectures.py:546-616 (EBranchformerBlock, EBranchformerModel)
+        D = cfg.branchformer_d_model
+        _lin(s, "model.input_proj", D, F)
+        for i in range(nb):
+            p = f"model.branchformer_blocks.{i}"
+            _ln(s, f"{p}.attn_branch_norm", D)
+            s[f"{p}.attention.in_proj_weight"] = (3 * D, D)
+            s[f"{p}.attention.in_proj_bias"] = (3 * D,)
+            _lin(s, f"{p}.attention.out_proj", D, D)
+            _ln(s, f"{p}.conv_branch.layer_norm", D)
+            s[f"{p}.conv_branch.conv1.weight"] = (2 * D, D, 1); s[f"{p}.conv_branch.conv1.bias"] = (2 * D,)
+            s[f"{p}.conv_branch.depthwise_conv.weight"] = (D, 1, 31); s[f"{p}.conv_branch.depthwise_conv.bias"] = (D,)
+            _bn(s, f"{p}.conv_branch.batch_norm", D)
+            s[f"{p}.conv_branch.conv2.weight"] = (D, D, 1); s[f"{p}.conv_branch.conv2.bias"] = (D,)
+            _lin(s, f"{p}.merger.gate", D, D)
+            _ln(s, f"{p}.final_norm", D)
+            _ln(s, f"{p}.ffn.layer_norm", D)
+            _lin(s, f"{p}.ffn.linear1", 4 * D, D)
+            _lin(s, f"{p}.ffn.linear2", D, 4 * D)
+        _lin(s, "model.output_proj", E, D)
     elif mt == "tcn":                     # architectures.py:290-367 (TemporalBlock, TCNModel)
         k, cin = cfg.tcn_kernel_size, F
         for i, co in enumerate(cfg.tcn_channels):
@@ -281,6 +311,11 @@ def head_macs(cfg: HeadConfig) -> int:
         # in_proj, q k^T and (softmax) v, out_proj, linear1, linear2
         per = T * 3 * D * D + 2 * T * T * D + T * D * D + 2 * T * D * 4 * D
         m += nb * per
+    elif mt == "e_branchformer":
+        D = cfg.branchformer_d_model
+        m += T * F * D + D * E
+        # per row: in_proj 3 D^2, out_proj D^2, conv1 2 D^2, depthwise 31 D, conv2 D^2, gate D^2, ffn 8 D^2; q k^T and (softmax) v 2 T D
+        m += nb * T * (16 * D * D + 31 * D + 2 * T * D)
     elif mt == "tcn":
         # the reference's full-sequence count: conv1, conv2 (and the downsample) at every step, then fc of the last step
         k, cin = cfg.tcn_kernel_size, F

@@ -15,6 +15,9 @@ struct AttnArgs {
     float o_un;                      // 1 / (scale of the packed out_proj weights x in_proj weight scale x cV)
     float qscale;                    // 1 / sqrt(head dim)
     int stagger = 0;                 // set by the launcher: start-up delay step in shader clocks (workgroups start in eight phases)
+    // the E-Branchformer's attention branch: ln_w / ln_b != nullptr (both or neither) = LayerNorm of the clip's rows in front
+    // (q = k = v = LayerNorm(h)) and out = out_proj(...) WITHOUT the rows of h, out != h.  The defaults are the Conformer's module
+    const float* ln_w = nullptr; const float* ln_b = nullptr;
 };
 
 bool attn_x3_supported(int T, int D, int n_head);

@@ -141,7 +141,9 @@ __global__ void __launch_bounds__(256) attn_bias_kernel(const float* __restrict_
 
 // NT16C: number of 16-key blocks, ceil(T / 16), as a compile-time constant (branch-free score / P V loops: the scheduler can then put a
 // block's probability split under the previous block's MFMAs); 0 = taken from T at run time
-template <int D16, int NH, int DH, int NT16C>
+// BRANCH (the E-Branchformer's attention branch, architectures.py:578-580): the clip's rows pass through LayerNorm(ln_w, ln_b) first - a row
+// lives in the two lanes (n, 0) and (n, 1), layernorm_kernel's arithmetic - and out = out_proj(...) WITHOUT the residual, beside h
+template <int D16, int NH, int DH, int NT16C, bool BRANCH = false>
 __global__ void __launch_bounds__(256) attn_x3_kernel(AttnArgs a) {
     constexpr int D = 16 * D16, L = DH - 32, NOB = (D + 31) / 32;
     static_assert(DH >= 32 && DH <= 36 && L % 4 == 0 && NH * 8 <= 32 && NH * DH == D, "attn_x3: one 32-dim tile + at most 4 left-over dims per head");
@@ -249,6 +251,30 @@ __global__ void __launch_bounds__(256) attn_x3_kernel(AttnArgs a) {
         f16x8 xf[D16][2];
         float isx;                                             // 1 / the clip's scale
         {
+            if constexpr (BRANCH) {
+                float s = 0.0f;
+#pragma unroll
+                for (int kb = 0; kb < D16; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s += v[kb][e];
+                const float mu = (s + __shfl_xor(s, 32, 64)) / (float)D;
+                float q = 0.0f;
+#pragma unroll
+                for (int kb = 0; kb < D16; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { const float d = v[kb][e] - mu; q = fmaf(d, d, q); }
+                const float rstd = 1.0f / sqrtf((q + __shfl_xor(q, 32, 64)) / (float)D + 1e-5f);
+#pragma unroll
+                for (int kb = 0; kb < D16; ++kb) {
+                    const float* wp = a.ln_w + 16 * kb + 8 * h;
+                    const float* bp = a.ln_b + 16 * kb + 8 * h;
+                    const float4 w0 = *reinterpret_cast<const float4*>(wp), w1 = *reinterpret_cast<const float4*>(wp + 4);
+                    const float4 b0 = *reinterpret_cast<const float4*>(bp), b1 = *reinterpret_cast<const float4*>(bp + 4);
+                    const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w}, b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[kb][e] = (v[kb][e] - mu) * rstd * w[e] + b[e];
+                }
+            }
             float m = 0.0f;
 #pragma unroll
             for (int kb = 0; kb < D16; ++kb)
@@ -537,10 +563,10 @@ __global__ void __launch_bounds__(256) attn_x3_kernel(AttnArgs a) {
             // residual block up front measured the same, tools/ubench/attn_trace.)
             float4 rcur[4], rnxt[4];
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) rcur[jj] = *reinterpret_cast<const float4*>(rrow[jj]);
+            for (int jj = 0; jj < 4; ++jj) rcur[jj] = BRANCH ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(rrow[jj]);
 #pragma unroll
             for (int ob = 0; ob < NOB; ++ob) {
-                if (ob + 1 < NOB && 32 * (ob + 1) + 4 * tq < D) {
+                if (!BRANCH && ob + 1 < NOB && 32 * (ob + 1) + 4 * tq < D) {
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) rnxt[jj] = *reinterpret_cast<const float4*>(rrow[jj] + 32 * (ob + 1));
                 }
@@ -564,8 +590,10 @@ __global__ void __launch_bounds__(256) attn_x3_kernel(AttnArgs a) {
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
+                if constexpr (!BRANCH) {
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) rcur[jj] = rnxt[jj];
+                    for (int jj = 0; jj < 4; ++jj) rcur[jj] = rnxt[jj];
+                }
             }
         }
         ATT_STAMP(20)
@@ -597,11 +625,18 @@ hipError_t launch_attn_x3(const AttnArgs& a0, int D, int n_head, int cus, hipStr
     if (a0.B <= 0) return hipSuccess;
     if (!attn_x3_supported(a0.T, D, n_head)) return hipErrorInvalidValue;
     if (((reinterpret_cast<uintptr_t>(a0.h) | reinterpret_cast<uintptr_t>(a0.out) | reinterpret_cast<uintptr_t>(a0.bc)) & 15) != 0) return hipErrorInvalidValue;
+    // the branch form: both LayerNorm vectors and the output beside the input (the rows are read once, before any store)
+    if ((a0.ln_w != nullptr) != (a0.ln_b != nullptr)) return hipErrorInvalidValue;
+    if (a0.ln_w && (a0.out == a0.h || ((reinterpret_cast<uintptr_t>(a0.ln_w) | reinterpret_cast<uintptr_t>(a0.ln_b)) & 15) != 0)) return hipErrorInvalidValue;
     const dim3 grid(a0.B < cus ? a0.B : cus);
     AttnArgs a = a0;
     a.stagger = a0.B >= 4 * cus ? 2000 : 0;                    // (fewer clips per workgroup: the delay would not pay back)
     const int nt16 = (a.T + 15) / 16;
-    if (nt16 == 7) hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 7>), grid, dim3(256), 0, s, a);          // T = 97 .. 112: 1 s clips at the 10 ms hop
+    if (a.ln_w) {
+        if (nt16 == 7) hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 7, true>), grid, dim3(256), 0, s, a);
+        else if (nt16 == 8) hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 8, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 0, true>), grid, dim3(256), 0, s, a);
+    } else if (nt16 == 7) hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 7>), grid, dim3(256), 0, s, a);          // T = 97 .. 112: 1 s clips at the 10 ms hop
     else if (nt16 == 8) hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 8>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_x3_kernel<9, 4, 36, 0>), grid, dim3(256), 0, s, a);
     return hipGetLastError();

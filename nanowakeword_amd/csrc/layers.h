@@ -135,6 +135,8 @@ hipError_t launch_unary(const float* x, float* y, size_t n, int act, hipStream_t
 hipError_t launch_scale_add_pe(float* x, const float* pe, int B, int T, int D, float scale, hipStream_t s);
 // GLU over the last axis: in [R][2D] -> out [R][D] = in[:, :D] * sigmoid(in[:, D:])
 hipError_t launch_glu(const float* in, float* out, int R, int D, hipStream_t s);
+// E-Branchformer merge + residual: x [n] += a g + c (1 - g), g = sigmoid(z) (the gate Linear's output); MergingModule, architectures.py:555-561
+hipError_t launch_branch_merge(float* x, const float* a, const float* c, const float* z, size_t n, hipStream_t s);
 // depthwise conv1d over time, 'same' padding, + bias, folded BN (alpha,beta), Swish: x [B][T][D] -> y [B][T][D]
 hipError_t launch_dwconv1d_bn_swish(const float* x, const float* w /*[D][K]*/, const float* bias, const float* alpha,
                                     const float* beta, float* y, int B, int T, int D, int K, hipStream_t s);

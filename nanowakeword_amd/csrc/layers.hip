@@ -938,6 +938,20 @@ hipError_t launch_glu(const float* in, float* out, int R, int D, hipStream_t s) 
     return hipGetLastError();
 }
 
+// E-Branchformer MergingModule + residual, elementwise: x += a g + c (1 - g), g = sigmoid(z) (architectures.py:555-561, 590)
+__global__ void __launch_bounds__(256) branch_merge_kernel(float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ c,
+                                                           const float* __restrict__ z, size_t n) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const float g = 1.0f / (1.0f + expf(-z[idx]));
+    x[idx] += fmaf(a[idx], g, c[idx] * (1.0f - g));
+}
+hipError_t launch_branch_merge(float* x, const float* a, const float* c, const float* z, size_t n, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(branch_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, a, c, z, n);
+    return hipGetLastError();
+}
+
 __global__ void __launch_bounds__(256)
 dwconv1d_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                 const float* __restrict__ alpha, const float* __restrict__ beta, float* __restrict__ y, int T, int D,

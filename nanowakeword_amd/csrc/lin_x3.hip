@@ -374,6 +374,8 @@ __global__ void __launch_bounds__(64 * NWV, 2) lin_x3_kernel(LinArgs a) {
 }  // namespace
 
 // K = 192 / 256 (round 6): two-term instances only (the three-term GLU blocks exceed the LDS); one workgroup per CU there
+// LayerNorm in front of the plain epilogue (0): every width but 192, whose two-term instance would need 258 registers (it spilled two)
+bool lin_x3_ln_plain_supported(int K) { return K != 192; }
 bool lin_x3_supported(int K, int N, bool h2) { return (K == 32 || K == 64 || K == 96 || K == 128 || K == 144 || (h2 && (K == 192 || K == 256))) && N % 4 == 0 && N >= 4; }
 
 size_t lin_x3_packed_bytes(int K, int n_out, int parts, int terms) { return (size_t)((n_out + 31) / 32) * lin_x3_block_bytes(K, parts, terms); }
@@ -389,7 +391,7 @@ hipError_t launch_lin_x3_pack(const float* W, const float* bias, void* out, int 
 
 hipError_t launch_lin_x3(const LinArgs& a0, int K, int epi, bool ln, hipStream_t s) {
     if (a0.M <= 0) return hipSuccess;
-    if (!lin_x3_supported(K, a0.N, a0.h2 != 0) || (ln && epi != 2) || (a0.ldx % 4) || (a0.ldc % 4)) return hipErrorInvalidValue;
+    if (!lin_x3_supported(K, a0.N, a0.h2 != 0) || (ln && epi != 2 && !(epi == 0 && lin_x3_ln_plain_supported(K))) || (a0.ldx % 4) || (a0.ldc % 4)) return hipErrorInvalidValue;
     if (epi == 3 && (a0.qkv_T <= 0 || !a0.res || (a0.ldres % 4))) return hipErrorInvalidValue;
     if (a0.qkv_T > 0 && epi != 3 && (epi != 0 || a0.N > 1024 || a0.N % 3 || a0.qkv_dh <= 0 || (a0.N / 3) % a0.qkv_dh || a0.qkv_dh % 4 || a0.M % a0.qkv_T))
         return hipErrorInvalidValue;
@@ -414,10 +416,11 @@ hipError_t launch_lin_x3(const LinArgs& a0, int K, int epi, bool ln, hipStream_t
 #define LIN_GO_H2ONLY(K16V, EPIV, LNV)                                                                             \
     if (a.h2) { LIN_GO2(K16V, EPIV, LNV, true) } else return hipErrorInvalidValue;
 #define LIN_EPI(K16V)                                                                                              \
-    if (epi == 0) { LIN_GO(K16V, 0, false) } else if (epi == 1) { LIN_GO(K16V, 1, false) } else if (epi == 3) { LIN_GO(K16V, 3, false) }        \
+    if (epi == 0 && ln) { LIN_GO(K16V, 0, true) } else if (epi == 0) { LIN_GO(K16V, 0, false) } else if (epi == 1) { LIN_GO(K16V, 1, false) } else if (epi == 3) { LIN_GO(K16V, 3, false) }        \
     else if (ln) { LIN_GO(K16V, 2, true) } else { LIN_GO(K16V, 2, false) }
 #define LIN_EPI_H2(K16V)                                                                                           \
-    if (epi == 0) { LIN_GO_H2ONLY(K16V, 0, false) } else if (epi == 1) { LIN_GO_H2ONLY(K16V, 1, false) }                                    \
+    if (epi == 0 && ln) { if constexpr (K16V != 12) { LIN_GO_H2ONLY(K16V, 0, true) } else return hipErrorInvalidValue; }                   \
+    else if (epi == 0) { LIN_GO_H2ONLY(K16V, 0, false) } else if (epi == 1) { LIN_GO_H2ONLY(K16V, 1, false) }                             \
     else if (epi == 3) { LIN_GO_H2ONLY(K16V, 3, false) } else if (ln) { LIN_GO_H2ONLY(K16V, 2, true) } else { LIN_GO_H2ONLY(K16V, 2, false) }
     switch (K) {
         case 32: LIN_EPI(2) break;

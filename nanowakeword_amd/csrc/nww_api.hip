@@ -62,7 +62,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_TCN) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_E_BRANCHFORMER) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)
@@ -84,9 +84,9 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     }
     if ((c.head_type == NWW_HEAD_CRNN || c.head_type == NWW_HEAD_GRU) && c.layer_dim > 512)
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "recurrent hidden size (layer_dim = %d) must be <= 512", c.layer_dim);
-    // the Transformer's d_model / n_head travel in the Conformer's slots (include/nww.h)
-    const bool attn_head = c.head_type == NWW_HEAD_CONFORMER || c.head_type == NWW_HEAD_TRANSFORMER;
-    const char* attn_name = c.head_type == NWW_HEAD_TRANSFORMER ? "transformer" : "conformer";
+    // the Transformer's and the E-Branchformer's d_model / n_head travel in the Conformer's slots (include/nww.h)
+    const bool attn_head = c.head_type == NWW_HEAD_CONFORMER || c.head_type == NWW_HEAD_TRANSFORMER || c.head_type == NWW_HEAD_E_BRANCHFORMER;
+    const char* attn_name = c.head_type == NWW_HEAD_TRANSFORMER ? "transformer" : c.head_type == NWW_HEAD_E_BRANCHFORMER ? "branchformer" : "conformer";
     if (attn_head && (c.conformer_n_head <= 0 || c.conformer_d_model % c.conformer_n_head))
         return fail(nullptr, NWW_ERR_INVALID, "%s_d_model must be divisible by %s_n_head", attn_name, attn_name);
     if (c.act_dtype != NWW_ACT_DTYPE_F32 && c.act_dtype != NWW_ACT_DTYPE_BF16 && c.act_dtype != NWW_ACT_DTYPE_F16)

@@ -25,6 +25,7 @@
 #include "attn_x3.h"
 #include "dual_x3.h"
 #include "emb_stream.h"
+#include "merge_x3.h"
 #include "tcn_x3.h"
 
 // rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
@@ -173,7 +174,7 @@ void nww_build_spec(nww_handle* h);            // nww_plan.hip
 // The run-time knobs, read from the environment on the first call (nww_plan.hip).  Each selection knob defaults to the
 // specialised kernel; setting it picks a general one.
 struct Knobs {
-    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, mha_mfma, bc_front, bc_chain, tail;
+    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, mha_mfma, bc_front, bc_chain, tail;
     int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
     int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2
 };

@@ -8,7 +8,7 @@ const Knobs& nww_knobs() {
         Knobs r;
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
-        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
+        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
         r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
@@ -125,6 +125,26 @@ void nww_build_spec(nww_handle* h) {
                 s.lin(p + ".self_attn.out_proj", D, D);
                 s.lin(p + ".linear1", 4 * D, D); s.lin(p + ".linear2", D, 4 * D);
                 s.ln(p + ".norm1", D); s.ln(p + ".norm2", D);
+            }
+            s.lin("model.output_proj", E, D);
+            break;
+        }
+        case NWW_HEAD_E_BRANCHFORMER: {           // EBranchformerModel (architectures.py:546-616); d_model / n_head in the conformer_* slots
+            const int D = c.conformer_d_model;
+            s.lin("model.input_proj", D, F);
+            for (int i = 0; i < nb; ++i) {
+                const std::string p = "model.branchformer_blocks." + std::to_string(i);
+                s.ln(p + ".attn_branch_norm", D);
+                s.add(p + ".attention.in_proj_weight", {3 * D, D}); s.add(p + ".attention.in_proj_bias", {3 * D});
+                s.lin(p + ".attention.out_proj", D, D);
+                s.ln(p + ".conv_branch.layer_norm", D);
+                s.add(p + ".conv_branch.conv1.weight", {2 * D, D, 1}); s.add(p + ".conv_branch.conv1.bias", {2 * D});
+                s.add(p + ".conv_branch.depthwise_conv.weight", {D, 1, 31}); s.add(p + ".conv_branch.depthwise_conv.bias", {D});
+                s.bn(p + ".conv_branch.batch_norm", D);
+                s.add(p + ".conv_branch.conv2.weight", {D, D, 1}); s.add(p + ".conv_branch.conv2.bias", {D});
+                s.lin(p + ".merger.gate", D, D);
+                s.ln(p + ".final_norm", D);
+                s.ln(p + ".ffn.layer_norm", D); s.lin(p + ".ffn.linear1", 4 * D, D); s.lin(p + ".ffn.linear2", D, 4 * D);
             }
             s.lin("model.output_proj", E, D);
             break;
@@ -355,6 +375,7 @@ bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int 
                 const float* bias, int epi, int res_id = 99, float rscale = 1.f, const float* ln_w = nullptr,
                 const float* ln_b = nullptr, int qkv_T = 0, int qkv_dh = 0, const float* res_tab = nullptr) {
     if (!nww_knobs().lin_x3 || p.h->conv_products != 6 || !lin_x3_supported(K, N, true)) return false;
+    if (ln_w && epi != 2 && !(epi == 0 && lin_x3_ln_plain_supported(K))) return false;
     const int parts = epi == 2 ? 2 : 1;
     // under NWW_ARITH_F16X3: two binary16 terms per operand, the input rows scaled per row in the kernel (LinArgs::h2: no bound on the
     // tensor needed); conv_arith = bf16x6 keeps the three-term bf16 form
@@ -790,7 +811,8 @@ int build_frontend_tables(nww_handle* h) {
 // ------------------------------------------------------------------------------------------ attention modules
 // The Conformer's whole attention module (in_proj, per-head softmax(q k^T) v, out_proj, residual) in one launch per clip-resident
 // workgroup (attn_x3.hip) under the default arithmetic at the compiled shape; false: nothing planned (NWW_ATTN_FUSED = 0 among others)
-bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH) {
+// ln_w / ln_b / out (the E-Branchformer's branch): LayerNorm of the rows in front, no residual, the result in buffer `out` beside h
+bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH, const float* ln_w = nullptr, const float* ln_b = nullptr, int out = -1) {
     if (!(nww_knobs().attn_fused && p.h->f16 && p.h->conv_products == 6 && attn_x3_supported(T, D, NH))) return false;
     const float *iw = p.W(q + ".attention.in_proj_weight"), *ib = p.W(q + ".attention.in_proj_bias");
     const float *ow = p.W(q + ".attention.out_proj.weight"), *ob = p.W(q + ".attention.out_proj.bias");
@@ -819,8 +841,10 @@ bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH)
     p.h->packed_weights.push_back(bc);
     const float cK = lk > 1e-30 ? (float)f16_pow2_floor(1.0 / lk) : 1.0f, cV = lv > 1e-30 ? (float)f16_pow2_floor(1.0 / lv) : 1.0f;
     const float w_un = 1.0f / ws_in, o_un = 1.0f / (ws_out * ws_in * cV), qs = 1.0f / std::sqrt((float)(D / NH));
-    p.add("attn_x3:" + q + ".attention (in_proj+softmax(qk)v+out_proj+res) [f16x3]", [=](Run& r) {
-        AttnArgs a{r.buf[hb], r.buf[hb], static_cast<const unsigned char*>(packed), static_cast<const float*>(bc), r.B, T, w_un, cK, cV, o_un, qs};
+    if (ln_w) p.need(out, (size_t)T * D);
+    p.add("attn_x3:" + q + (ln_w ? ".attention (ln+in_proj+softmax(qk)v+out_proj) [f16x3]" : ".attention (in_proj+softmax(qk)v+out_proj+res) [f16x3]"), [=](Run& r) {
+        AttnArgs a{r.buf[hb], r.buf[ln_w ? out : hb], static_cast<const unsigned char*>(packed), static_cast<const float*>(bc), r.B, T, w_un, cK, cV, o_un, qs};
+        if (ln_w) { a.ln_w = ln_w; a.ln_b = ln_b; }
         return launch_attn_x3(a, D, NH, r.cu_count, r.stream);
     });
     return true;
@@ -828,7 +852,11 @@ bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH)
 
 // h <- h + out_proj(softmax(q k^T / sqrt(dh)) v), q | k | v = in_proj(h), in three launches: block q's module `module` (".attention" /
 // ".self_attn"); buffers hb (h), big (q | k | v), t1 (the heads' outputs).  exact_sub: mha_h2's softmax form (launch_mha_h2)
-void add_attention_module(PlanCtx& p, const std::string& q, const char* module, int hb, int big, int t1, int T, int D, int NH, int exact_sub) {
+// ln_w / ln_b / out (the E-Branchformer's branch): q | k | v = in_proj(LayerNorm(h)) - the LayerNorm inside the short-K in_proj where that
+// kernel runs, else on its own into `out` - and out_proj WITHOUT the residual into buffer `out`
+// (ln_name: the LayerNorm's module, ".attn_branch_norm")
+void add_attention_module(PlanCtx& p, const std::string& q, const char* module, int hb, int big, int t1, int T, int D, int NH, int exact_sub,
+                          const float* ln_w = nullptr, const float* ln_b = nullptr, int out = -1, const char* ln_name = "") {
     const std::string m = q + module;
     // in_proj writes q, k, v head-major when the matrix-core attention consumes them: every (clip, head) block is then
     // one contiguous run for its LDS-DMA
@@ -836,11 +864,22 @@ void add_attention_module(PlanCtx& p, const std::string& q, const char* module, 
     const bool want_hm = mha_mfma && mha_mfma_supported(T, D, NH) && 3 * D <= 1024;
     const float *iw = p.W(m + ".in_proj_weight"), *ib = p.W(m + ".in_proj_bias");
     bool head_major = false;
-    if (add_lin_x3(p, m + (want_hm ? ".in_proj(head-major)" : ".in_proj"), hb, big, T, 3 * D, D, iw, ib, 0, 99, 1.f, nullptr, nullptr,
-                   want_hm ? T : 0, want_hm ? D / NH : 0))
+    const std::string in_name = m + (want_hm ? ".in_proj(head-major)" : ".in_proj");
+    int in_id = hb;
+    if (add_lin_x3(p, ln_w ? q + ln_name + "+" + std::string(module).substr(1) + (want_hm ? ".in_proj(head-major)" : ".in_proj") : in_name, hb, big, T, 3 * D, D, iw, ib, 0, 99, 1.f, ln_w, ln_b,
+                   want_hm ? T : 0, want_hm ? D / NH : 0)) {
         head_major = want_hm;
-    else
-        add_gemm(p, m + ".in_proj", hb, big, T, 3 * D, D, iw, ib, ACT_NONE);
+    } else {
+        if (ln_w) {                                        // the LayerNorm on its own, into `out` (free until out_proj writes it)
+            p.need(out, (size_t)T * D);
+            p.add("layernorm:" + q + ln_name, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[out], ln_w, ln_b, r.B * T, D, ACT_NONE, r.stream); });
+            in_id = out;
+        }
+        if (add_lin_x3(p, in_name, in_id, big, T, 3 * D, D, iw, ib, 0, 99, 1.f, nullptr, nullptr, want_hm ? T : 0, want_hm ? D / NH : 0))
+            head_major = want_hm;
+        else
+            add_gemm(p, m + ".in_proj", in_id, big, T, 3 * D, D, iw, ib, ACT_NONE);
+    }
     const int hm = head_major ? 1 : 0;
     if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
         p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm, exact_sub); });
@@ -848,7 +887,8 @@ void add_attention_module(PlanCtx& p, const std::string& q, const char* module, 
         p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm); });
     else
         p.add("mha_core:" + q, [=](Run& r) { return launch_mha_core(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream); });
-    add_linear(p, m + ".out_proj+res", t1, hb, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"), hb, 1.0f);
+    if (ln_w) add_linear(p, m + ".out_proj", t1, out, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"));
+    else add_linear(p, m + ".out_proj+res", t1, hb, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"), hb, 1.0f);
 }
 
 // ------------------------------------------------------------------------------------------ per-head plans
@@ -1512,6 +1552,100 @@ int plan_transformer(PlanCtx& p) {                  // TransformerModel: archite
     return NWW_OK;
 }
 
+int plan_e_branchformer(PlanCtx& p) {               // EBranchformerModel: architectures.py:546-616
+    const nww_config& c = p.h->cfg;
+    const int T = c.in_rows, F = c.in_cols, nb = c.n_blocks;
+    const int D = c.conformer_d_model, NH = c.conformer_n_head;
+    // x, glu output / heads' outputs / time mean, depthwise output, wide scratch (q | k | v, the ffn's hidden rows, the gate), the attention
+    // branch's output, the conv branch's output (fallback only)
+    const int hb = 0, t1 = 1, t3 = 2, big = 3, ab = 4, cb = 5;
+    p.need(hb, (size_t)T * D); p.need(t1, (size_t)T * D); p.need(t3, (size_t)T * D); p.need(ab, (size_t)T * D);
+    // both branches read input_proj's output, so it cannot ride in a later launch
+    add_linear(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"));
+    for (int i = 0; i < nb; ++i) {
+        const std::string q = "model.branchformer_blocks." + std::to_string(i);
+        // ---- a = MHA(LayerNorm(x)): no residual here, the merge takes it.  One launch where attn_x3 takes the shape, else three
+        const float *anw = p.W(q + ".attn_branch_norm.weight"), *anb = p.W(q + ".attn_branch_norm.bias");
+        if (!add_attn_x3(p, q, hb, T, D, NH, anw, anb, ab)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0, anw, anb, ab, ".attn_branch_norm");
+        // ---- the ConvolutionModule up to its depthwise stage, as the Conformer's: LayerNorm + conv1 + GLU, depthwise + BN + swish -> t3
+        const std::string m = q + ".conv_branch";
+        const float *lw = p.W(m + ".layer_norm.weight"), *lb = p.W(m + ".layer_norm.bias");
+        const float *dw = p.W(m + ".depthwise_conv.weight"), *db = p.W(m + ".depthwise_conv.bias");
+        const float *ba = p.W(m + ".batch_norm.alpha"), *bb = p.W(m + ".batch_norm.beta");
+        if (!add_lin_x3(p, m + ".layer_norm+conv1(pw)+glu", hb, t1, T, D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), 2, 99, 1.f, lw, lb)) {
+            p.add("layernorm:" + m, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
+            add_gemm(p, m + ".conv1(pw)", t1, big, T, 2 * D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), ACT_NONE);
+            p.add("glu:" + m, [=](Run& r) { return launch_glu(r.buf[big], r.buf[t1], r.B * T, D, r.stream); });
+        }
+        p.add("dwconv1d+bn+swish:" + m, [=](Run& r) { return launch_dwconv1d_bn_swish(r.buf[t1], dw, db, ba, bb, r.buf[t3], r.B, T, D, 31, r.stream); });
+        // ---- x <- final_norm(x + a g + c (1 - g)), c = conv2(t3), g = sigmoid(gate(c)): one row-local launch (merge_x3.hip) under the
+        // default arithmetic - its rows are scaled one by one in the kernel, so it needs no bound on t3 or c - else four
+        const float *c2w = p.W(m + ".conv2.weight"), *c2b = p.W(m + ".conv2.bias");
+        const float *gw = p.W(q + ".merger.gate.weight"), *gb = p.W(q + ".merger.gate.bias");
+        const float *fnw = p.W(q + ".final_norm.weight"), *fnb = p.W(q + ".final_norm.bias");
+        bool merged = false;
+        if (nww_knobs().merge_fused && p.h->f16 && p.h->conv_products == 6 && merge_x3_supported(D)) {
+            const float wsc = f16_wscale(f16_fetch(p.h, c2w, (size_t)D * D)), wsg = f16_wscale(f16_fetch(p.h, gw, (size_t)D * D));
+            void* packed = nullptr;
+            if (wsc > 0.0f && wsg > 0.0f && hipMalloc(&packed, merge_x3_packed_bytes(D)) == hipSuccess &&
+                launch_merge_x3_pack(c2w, gw, packed, D, wsc, wsg, p.h->own_stream) == hipSuccess) {
+                p.h->packed_weights.push_back(packed);
+                p.add("merge_x3:" + q + " (conv2(pw)+gate+blend+res+final_norm) [f16x3]", [=](Run& r) {
+                    MergeArgs a{r.buf[t3], r.buf[ab], r.buf[hb], static_cast<const unsigned char*>(packed), c2b, gb, fnw, fnb, r.B * T, 1.0f / wsc, 1.0f / wsg};
+                    return launch_merge_x3(a, D, r.stream);
+                });
+                merged = true;
+            } else if (packed) {
+                (void)hipFree(packed);
+            }
+        }
+        if (!merged) {
+            add_linear(p, m + ".conv2(pw)", t3, cb, T, D, D, c2w, c2b);
+            add_linear(p, q + ".merger.gate", cb, big, T, D, D, gw, gb);
+            p.add("branch_merge:" + q + " (sigmoid+blend+res)", [=](Run& r) { return launch_branch_merge(r.buf[hb], r.buf[ab], r.buf[cb], r.buf[big], (size_t)r.B * T * D, r.stream); });
+            p.add("layernorm:" + q + ".final_norm", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], fnw, fnb, r.B * T, D, ACT_NONE, r.stream); });
+        }
+        // ---- x <- x + ffn(x): the Conformer's FeedForwardModule with the FULL residual; its plain fused form (ffn_x3.hip), scales from the
+        // weights alone as in plan_conformer (|LayerNorm(x)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v|)
+        const std::string ff = q + ".ffn";
+        const float *flw = p.W(ff + ".layer_norm.weight"), *flb = p.W(ff + ".layer_norm.bias");
+        const float *w1 = p.W(ff + ".linear1.weight"), *b1 = p.W(ff + ".linear1.bias"), *w2 = p.W(ff + ".linear2.weight"), *b2 = p.W(ff + ".linear2.bias");
+        bool fused = false;
+        if (nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16)) {
+            float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f;
+            if (p.h->f16) {
+                const double bx = f16_ln_bound(p.h, flw, flb, D);
+                const auto hw1 = f16_fetch(p.h, w1, (size_t)4 * D * D), hw2 = f16_fetch(p.h, w2, (size_t)4 * D * D), hb1 = f16_fetch(p.h, b1, (size_t)4 * D);
+                const double bh = f16_layer_bound(hw1, 4 * D, D, hb1, true, hb1, hb1, false, bx);
+                fx = f16_scale(bx); fw1 = f16_wscale(hw1); fh = f16_scale(bh); fw2 = f16_wscale(hw2);
+            }
+            const bool h2 = fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f;
+            void* packed = nullptr;
+            if (ffn_x3_supported(D, h2) && hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
+                launch_ffn_x3_pack(w1, b1, w2, packed, D, p.h->own_stream, h2 ? fw1 : 0.0f, h2 ? fw2 : 0.0f, 0) == hipSuccess) {
+                p.h->packed_weights.push_back(packed);
+                p.add("ffn_x3:" + ff + " (ln+linear1+swish+linear2+res)" + (h2 ? " [f16x3]" : ""), [=](Run& r) {
+                    FfnArgs a{r.buf[hb], flw, flb, static_cast<const unsigned char*>(packed), b2, r.B * T, 1.0f};
+                    if (h2) { a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2; }
+                    return launch_ffn_x3(a, D, r.stream);
+                });
+                fused = true;
+            } else if (packed) {
+                (void)hipFree(packed);
+            }
+        }
+        if (!fused) {
+            p.add("layernorm:" + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], flw, flb, r.B * T, D, ACT_NONE, r.stream); });
+            add_gemm(p, ff + ".linear1+swish", t1, big, T, 4 * D, D, w1, b1, ACT_SILU);
+            add_gemm(p, ff + ".linear2+res", big, hb, T, D, 4 * D, w2, b2, ACT_NONE, nullptr, nullptr, hb, 1.0f);
+        }
+    }
+    // no LayerNorm in front of the mean (unlike the Conformer), so no plan-time bound for the exact-sum epilogue: the plain mean
+    p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
+    set_tail(p, "output_proj", t1, D, p.W("model.output_proj.weight"), p.W("model.output_proj.bias"));
+    return NWW_OK;
+}
+
 int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.py:290-367; the head reads tcn_out[:, :, T - 1] only
     const nww_config& c = p.h->cfg;
     const int T = c.in_rows, F = c.in_cols;
@@ -1647,6 +1781,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         case NWW_HEAD_CONFORMER: rc = plan_conformer(p); break;
         case NWW_HEAD_TRANSFORMER: rc = plan_transformer(p); break;
         case NWW_HEAD_TCN: rc = plan_tcn(p); break;
+        case NWW_HEAD_E_BRANCHFORMER: rc = plan_e_branchformer(p); break;
     }
     if (rc != NWW_OK) return rc;
     plan_tail(p);

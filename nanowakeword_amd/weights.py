@@ -38,7 +38,8 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
                       n_head: Optional[int] = None) -> HeadConfig:
     """Model type / layer_dim / n_blocks / embedding_dim from key names and shapes.  ``input_shape`` is needed
     when the weights do not determine it (DNN/CNN flatten sizes fix only T*F or (T//4)*(F//4)).  ``n_head``: the
-    Transformer's attention heads (transformer_n_head), which no weight shape records; default 4 as Model()'s."""
+    Transformer's / E-Branchformer's attention heads (transformer_n_head / branchformer_n_head), which no weight shape records;
+    default 4 as Model()'s."""
     keys = set(sd)
     shp = lambda k: tuple(np.shape(sd[k]))
     E = shp("classifier.0.weight")[1]
@@ -96,6 +97,13 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         nb = n_indexed(r"model\.transformer_encoder\.layers\.(\d+)\.norm1\.weight")
         # n_head is not recoverable from the weights: Model()'s default (model.py:201) unless the caller says otherwise
         cfg = HeadConfig("transformer", input_shape, n_blocks=nb, transformer_d_model=D, transformer_n_head=n_head or 4, **kw)
+    elif "model.input_proj.weight" in keys and any(k.startswith("model.branchformer_blocks.") for k in keys):
+        D, F = shp("model.input_proj.weight")
+        if input_shape is None:
+            raise ValueError("e_branchformer: pass input_shape=(T, F)")
+        nb = n_indexed(r"model\.branchformer_blocks\.(\d+)\.final_norm\.weight")
+        # n_head is not recoverable from the weights: Model()'s default (model.py:273) unless the caller says otherwise
+        cfg = HeadConfig("e_branchformer", input_shape, n_blocks=nb, branchformer_d_model=D, branchformer_n_head=n_head or 4, **kw)
     elif "model.tcn_blocks.0.conv1.weight" in keys:
         if input_shape is None:
             raise ValueError("tcn: the sequence length is not in the weights; pass input_shape=(T, F)")
@@ -108,7 +116,7 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e2e_dnn)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e_branchformer/e2e_dnn)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:
@@ -260,6 +268,10 @@ def state_dict_from_onnx(path_or_bytes):
             for i, n in enumerate(convs):
                 p = f"model.conformer_blocks.{i}.conv_module"
                 folded(n, f"{p}.depthwise_conv.weight", f"{p}.depthwise_conv.bias", f"{p}.batch_norm")
+        elif any(k.startswith("model.branchformer_blocks.") for k in named):        # E-Branchformer: the same ConvolutionModule
+            for i, n in enumerate(convs):
+                p = f"model.branchformer_blocks.{i}.conv_branch"
+                folded(n, f"{p}.depthwise_conv.weight", f"{p}.depthwise_conv.bias", f"{p}.batch_norm")
         elif (grus or lstms) and convs:                                             # CRNN (GRU or LSTM backend)
             for i, n in enumerate(convs):
                 folded(n, f"model.cnn.{4*i}.weight", f"model.cnn.{4*i}.bias", f"model.cnn.{4*i+1}")
@@ -272,14 +284,14 @@ def state_dict_from_onnx(path_or_bytes):
         raise ValueError("no 'classifier.0' Gemm: not a reference Model export")
     act = _activation_after(g, cls[0].outputs[0])
     cfg = infer_head_config(sd, input_shape=input_shape, activation=act)
-    if cfg.model_type in ("conformer", "transformer"):
+    if cfg.model_type in ("conformer", "transformer", "e_branchformer"):
         sm = [n for n in g.nodes if n.op_type == "Softmax"]
         qk = g.producer_of(sm[0].inputs[0]) if sm else None
         sc_node = g.producer_of(qk.inputs[0]) if qk is not None else None
         c = None
         if sc_node is not None and sc_node.op_type == "Mul":
             c = next((g.constant(t) for t in sc_node.inputs if g.constant(t) is not None), None)
-        D = cfg.conformer_d_model if cfg.model_type == "conformer" else cfg.transformer_d_model
+        D = {"conformer": cfg.conformer_d_model, "transformer": cfg.transformer_d_model, "e_branchformer": cfg.branchformer_d_model}[cfg.model_type]
         if c is not None:
             n_head = D // int(round(1.0 / float(np.asarray(c).ravel()[0]) ** 2))
         else:
@@ -295,6 +307,8 @@ def state_dict_from_onnx(path_or_bytes):
                 raise ValueError(f"{cfg.model_type}: cannot find the attention scale (1/sqrt(head_dim)) or head count in the graph")
         if cfg.model_type == "conformer":
             cfg.conformer_n_head = n_head
+        elif cfg.model_type == "e_branchformer":
+            cfg.branchformer_n_head = n_head
         else:
             cfg.transformer_n_head = n_head
     if g.metadata.get("mode") == "e2e" and mode != "e2e":

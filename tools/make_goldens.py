@@ -292,6 +292,7 @@ def main():
     make_round4_goldens(args.out)
     make_round6_goldens(args.out)
     make_transformer_goldens(args.out)
+    make_ebranchformer_goldens(args.out)
     make_tcn_goldens(args.out)
     print("done ->", args.out)
 
@@ -763,6 +764,90 @@ def make_tcn_goldens(out_dir):
     print("onnx fixture tcn", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
 
 
+def ebranchformer_cases():
+    """E-Branchformer cases of heads_ebranchformer.npz (name, HeadConfig): the reference defaults (d_model 144, 4 heads) at both feature shapes,
+    two blocks, and d_model 48 (a width without fused instances).  Few clips per case: the default width is 0.35 M parameters, the file stays small."""
+    from nanowakeword_amd.config import HeadConfig
+    eb = lambda shape, D=144, H=4, **kw: HeadConfig("e_branchformer", shape, branchformer_d_model=D, branchformer_n_head=H, **kw)
+    return [
+        ("ebranchformer_16x96", eb((16, 96))),
+        ("ebranchformer_101x64", eb((101, 64))),
+        ("ebranchformer_33x64_b2", eb((33, 64), n_blocks=2)),
+        ("ebranchformer_16x96_d48_h4", eb((16, 96), 48, 4, embedding_dim=32)),
+    ]
+
+
+def ebranchformer_ref_model(Model, cfg, sd):
+    """The reference's own Model(model_type="e_branchformer") with the synthetic weights loaded; its state_dict keys / shapes must equal
+    param_spec (model.py:263-274, architectures.py:546-616)."""
+    from nanowakeword_amd.config import param_spec
+    conf = {"activation_function": cfg.activation, "embedding_dim": cfg.embedding_dim,
+            "branchformer_d_model": cfg.branchformer_d_model, "branchformer_n_head": cfg.branchformer_n_head}
+    m = Model(conf, "g", input_shape=cfg.input_shape, model_type=cfg.model_type, layer_dim=cfg.layer_dim, n_blocks=cfg.n_blocks)
+    ref_keys = {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.endswith("num_batches_tracked")}
+    spec = dict(param_spec(cfg))
+    assert ref_keys == spec, (set(ref_keys) ^ set(spec), {k: (ref_keys[k], spec[k]) for k in set(ref_keys) & set(spec) if ref_keys[k] != spec[k]})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.eval()
+
+
+def make_ebranchformer_goldens(out_dir):
+    """E-Branchformer head (own files: earlier fixtures stay byte-identical): logits and embeddings of the reference's Model on seeded synthetic
+    weights -> heads_ebranchformer.npz, and a reference export of a reduced width with its probabilities -> onnx/e_branchformer.onnx +
+    expected_e_branchformer.npz."""
+    install_stubs()
+    torch.set_num_threads(1)
+    from nanowakeword.modules.model import Model
+    from nanowakeword._export import onnx as ref_onnx
+    from nanowakeword_amd.config import HeadConfig
+    from nanowakeword_amd.synth import synth_features, synth_state_dict, state_dict_checksum
+    fr = dict(np.load(os.path.join(out_dir, "frontend.npz"), allow_pickle=False))
+    db64 = fr["db64"]
+    heads, meta = {}, {}
+    for name, cfg in ebranchformer_cases():
+        sd = synth_state_dict(cfg)
+        m = ebranchformer_ref_model(Model, cfg, sd)
+        feats = synth_features(3, cfg.input_shape)
+        with torch.no_grad():
+            out = {"feats": feats, "logits_feat": m(torch.from_numpy(feats)).numpy(), "emb_feat": m.model(torch.from_numpy(feats)).numpy()}
+            if cfg.input_shape == (101, 64):
+                out["logits_pcm"] = m(torch.from_numpy(np.ascontiguousarray(db64.transpose(0, 2, 1)))).numpy()
+        out["sd_checksum"] = np.array(state_dict_checksum(sd))
+        out["ref_spec_json"] = np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))
+        meta[name] = cfg.to_dict()
+        for k, v in out.items():
+            heads[f"{name}/{k}"] = v
+        print("e_branchformer", name, {k: getattr(v, "shape", v) for k, v in out.items()}, "logits", out["logits_feat"].ravel())
+    heads["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(out_dir, "heads_ebranchformer.npz"), **heads)
+
+    # the reference's own export of a small E-Branchformer (recipe of make_onnx_fixtures)
+    onnx_dir = os.path.join(out_dir, "onnx")
+    from torch.onnx._internal.torchscript_exporter import onnx_proto_utils
+    onnx_proto_utils._add_onnxscript_fn = lambda model_bytes, custom_opsets: model_bytes
+    orig_export = torch.onnx.export
+
+    def export_torchscript(*a, **k):
+        k.setdefault("dynamo", False)
+        return orig_export(*a, **k)
+    torch.onnx.export = export_torchscript
+    cfg = HeadConfig("e_branchformer", (16, 32), n_blocks=2, embedding_dim=16, branchformer_d_model=32, branchformer_n_head=8)
+    sd = synth_state_dict(cfg)
+    m = ebranchformer_ref_model(Model, cfg, sd)
+    ref_onnx.export_onnx_model(m, cfg.input_shape, {}, "e_branchformer", onnx_dir)
+    path = os.path.join(onnx_dir, "e_branchformer.onnx")
+    assert os.path.exists(path), "export of the e_branchformer failed"
+    feats = synth_features(4, cfg.input_shape)
+    with torch.no_grad():
+        logits = m(torch.from_numpy(feats)).numpy()
+    arrays = {"e_branchformer/feats": feats, "e_branchformer/logits": logits.reshape(-1).astype(np.float32),
+              "e_branchformer/probs": (1.0 / (1.0 + np.exp(-logits.astype(np.float64)))).reshape(-1).astype(np.float32),
+              "meta_json": np.array(json.dumps({"e_branchformer": cfg.to_dict()}))}
+    np.savez_compressed(os.path.join(onnx_dir, "expected_e_branchformer.npz"), **arrays)
+    torch.onnx.export = orig_export
+    print("onnx fixture e_branchformer", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
+
+
 def make_wire_fixtures(path):
     """Messages produced by the reference's own encoders (remote_verifier.py:147-158) for tests/test_wire.py."""
     from nanowakeword.interpreter import remote_verifier as rv
@@ -914,6 +999,8 @@ if __name__ == "__main__":
         make_round6_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--transformer-only":
         make_transformer_goldens(os.path.join(REPO, "tests", "golden"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--ebranchformer-only":
+        make_ebranchformer_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--r02-only":
         make_round2_goldens(os.path.join(REPO, "tests", "golden"))
     else:
