@@ -45,6 +45,7 @@ extern "C" {
 #define NWW_HEAD_TRANSFORMER 7 /* TransformerModel        architectures.py:164-206 */
 #define NWW_HEAD_TCN 8         /* TCNModel                architectures.py:290-367 */
 #define NWW_HEAD_E_BRANCHFORMER 9 /* EBranchformerModel   architectures.py:546-616 */
+#define NWW_HEAD_QUARTZNET 10  /* QuartzNetModel          architectures.py:370-437 */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1
@@ -72,7 +73,10 @@ typedef struct nww_config {
     int32_t in_rows, in_cols;  /* Model(input_shape=(in_rows, in_cols))                       */
     int32_t layer_dim, n_blocks, embedding_dim, activation;
     /* crnn_cnn_channels (<= 4 stages) for NWW_HEAD_CRNN; tcn_channels (1..4 levels, model.py:228) for NWW_HEAD_TCN, whose
-       tcn_kernel_size (>= 2) travels in layer_dim (TCNModel reads no layer_dim)                                        */
+       tcn_kernel_size (>= 2) travels in layer_dim (TCNModel reads no layer_dim); quartznet_config (model.py:239-248) for
+       NWW_HEAD_QUARTZNET: n_crnn_channels = its number of [channels, kernel, repetitions] entries (1..4), crnn_channels[i] = entry
+       i's channels, quartznet_kr[i] (below) = its kernel + 65536 * its repetitions.  More than 4 entries, or more than 16 blocks
+       once the repetitions are expanded, is NWW_ERR_UNSUPPORTED at nww_create                                          */
     int32_t n_crnn_channels;
     int32_t crnn_channels[4];
     /* d_model / n_head of the attention encoder (Conformer, Transformer, E-Branchformer): conformer_d_model / conformer_n_head
@@ -110,7 +114,9 @@ typedef struct nww_config {
        bf16 logits agree with the float32 reference to ~2e-2 on the test clips except all-zero PCM (0.2); f16 logits to ~5e-3 on
        every clip.  f16 assumes features within +-NWW_F16_FEATURE_BOUND, like NWW_ARITH_F16X3.                               */
     int32_t act_dtype;
-    int32_t reserved[4];
+    /* NWW_HEAD_QUARTZNET: kernel + 65536 * repetitions of quartznet_config entry i (kernel 1..65535, repetitions >= 1); zero and
+       ignored for every other head (these were the four reserved words: the struct keeps its 132 bytes and every offset)    */
+    int32_t quartznet_kr[4];
 } nww_config;
 #define NWW_ACT_DTYPE_F32 0
 #define NWW_ACT_DTYPE_BF16 1

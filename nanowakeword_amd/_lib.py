@@ -28,7 +28,7 @@ class NwwConfig(C.Structure):
         ("conv_arith", C.c_int32),
         ("crnn_rnn_lstm", C.c_int32),
         ("act_dtype", C.c_int32),
-        ("reserved", C.c_int32 * 4),
+        ("quartznet_kr", C.c_int32 * 4),      # kernel + 65536 * repetitions of each quartznet_config entry (include/nww.h)
     ]
 
 
@@ -163,15 +163,23 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
     c.in_rows, c.in_cols = head.input_shape
     c.layer_dim, c.n_blocks, c.embedding_dim = head.layer_dim, head.n_blocks, head.embedding_dim
     c.activation = ACT_CODE[head.activation]
-    # the TCN's channel list travels in the CRNN's channel slots and its kernel size in layer_dim (include/nww.h)
-    ch = list(head.tcn_channels if head.model_type == "tcn" else head.crnn_cnn_channels)
-    if head.model_type == "tcn":
-        c.layer_dim = head.tcn_kernel_size
-    if len(ch) > 4:
-        raise ValueError("tcn_channels supports at most 4 levels" if head.model_type == "tcn" else "crnn_cnn_channels supports at most 4 stages")
-    c.n_crnn_channels = len(ch)
-    for i, v in enumerate(ch):
-        c.crnn_channels[i] = int(v)
+    if head.model_type == "quartznet":
+        # [channels, kernel, repetitions] entries: channels in the CRNN's channel slots, kernel + 65536 * repetitions beside them; the
+        # entry count goes over as it is, so that nww_create refuses more than four instead of a truncated list running
+        c.n_crnn_channels = len(head.quartznet_config)
+        for i, (co, k, r) in enumerate(head.quartznet_config[:4]):
+            c.crnn_channels[i] = int(co)
+            c.quartznet_kr[i] = int(k) + 65536 * int(r)
+    else:
+        # the TCN's channel list travels in the CRNN's channel slots and its kernel size in layer_dim (include/nww.h)
+        ch = list(head.tcn_channels if head.model_type == "tcn" else head.crnn_cnn_channels)
+        if head.model_type == "tcn":
+            c.layer_dim = head.tcn_kernel_size
+        if len(ch) > 4:
+            raise ValueError("tcn_channels supports at most 4 levels" if head.model_type == "tcn" else "crnn_cnn_channels supports at most 4 stages")
+        c.n_crnn_channels = len(ch)
+        for i, v in enumerate(ch):
+            c.crnn_channels[i] = int(v)
     # the two slots carry d_model / n_head of whichever attention encoder the head has (include/nww.h)
     if head.model_type == "transformer":
         c.conformer_d_model, c.conformer_n_head = head.transformer_d_model, head.transformer_n_head

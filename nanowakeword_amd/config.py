@@ -15,13 +15,16 @@ from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Tuple
 
-HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn", "e_branchformer")
+HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn", "e_branchformer",
+              "quartznet")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
 HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8,
-             "e_branchformer": 9}
+             "e_branchformer": 9, "quartznet": 10}
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
+# nww_config carries at most 4 [channels, kernel, repetitions] entries of a QuartzNet and the planner at most 16 blocks
+QUARTZNET_MAX_ENTRIES, QUARTZNET_MAX_BLOCKS = 4, 16
 # rows of the Transformer's positional-encoding buffer (PositionalEncoding(max_len=5000), architectures.py:31)
 PE_MAX_LEN = 5000
 
@@ -70,6 +73,8 @@ class HeadConfig:
     tcn_kernel_size: int = 3
     branchformer_d_model: int = 144    # model.py:263-274 config keys of the E-Branchformer head
     branchformer_n_head: int = 4
+    # model.py:239-248 config key of the QuartzNet head: [[channels, kernel, repetitions], ...]
+    quartznet_config: List[List[int]] = field(default_factory=lambda: [[256, 33, 1], [256, 33, 1], [512, 39, 1]])
 
     def __post_init__(self):
         self.model_type = self.model_type.lower()
@@ -101,8 +106,37 @@ class HeadConfig:
                 raise ValueError(f"branchformer_d_model must be divisible by branchformer_n_head "
                                  f"(got {self.branchformer_d_model} / {self.branchformer_n_head})")
 
+        if self.model_type == "quartznet":
+            qc = [list(e) for e in self.quartznet_config]
+            if not 1 <= len(qc) <= QUARTZNET_MAX_ENTRIES:
+                raise ValueError(f"quartznet_config must have 1..{QUARTZNET_MAX_ENTRIES} [channels, kernel, repetitions] entries (got {len(qc)})")
+            if any(len(e) != 3 for e in qc):
+                raise ValueError(f"quartznet_config entries must be [channels, kernel, repetitions] (got {qc})")
+            qc = [[int(v) for v in e] for e in qc]
+            if any(c <= 0 for c, _, _ in qc):
+                raise ValueError(f"quartznet_config channels must be positive (got {qc})")
+            if any(k < 1 or k > 0xFFFF for _, k, _ in qc):
+                raise ValueError(f"quartznet_config kernel sizes must be 1..65535 (got {qc})")
+            if any(r < 1 for _, _, r in qc):
+                raise ValueError(f"quartznet_config repetitions must be >= 1 (got {qc})")
+            if sum(r for _, _, r in qc) > QUARTZNET_MAX_BLOCKS:
+                raise ValueError(f"quartznet_config expands to {sum(r for _, _, r in qc)} blocks; at most {QUARTZNET_MAX_BLOCKS} are supported")
+            self.quartznet_config = qc
+        else:
+            self.quartznet_config = [[int(v) for v in e] for e in self.quartznet_config]
+
     def to_dict(self):
         return asdict(self)
+
+
+def quartznet_blocks(cfg: "HeadConfig"):
+    """(Cin, Cout, k) of every QuartzNetBlock in order (QuartzNetModel.__init__, architectures.py:410-423)."""
+    out, cin = [], cfg.input_shape[1]
+    for c, k, r in cfg.quartznet_config:
+        for _ in range(r):
+            out.append((cin, c, k))
+            cin = c
+    return out
 
 
 def _bn(spec, prefix, c):
@@ -244,6 +278,16 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
                 s[f"{p}.downsample.weight"] = (co, cin, 1); s[f"{p}.downsample.bias"] = (co,)
             cin = co
         _lin(s, "model.fc", E, cin)
+    elif mt == "quartznet":               # architectures.py:370-437 (QuartzNetBlock, QuartzNetModel)
+        for i, (cin, co, k) in enumerate(quartznet_blocks(cfg)):
+            p = f"model.quartznet_blocks.{i}"
+            s[f"{p}.depthwise_conv.weight"] = (cin, 1, k); s[f"{p}.depthwise_conv.bias"] = (cin,)
+            s[f"{p}.pointwise_conv.weight"] = (co, cin, 1); s[f"{p}.pointwise_conv.bias"] = (co,)
+            _bn(s, f"{p}.batch_norm", co)
+            if cin != co:                 # the projected residual exists only when the widths differ
+                s[f"{p}.residual_connector.0.weight"] = (co, cin, 1); s[f"{p}.residual_connector.0.bias"] = (co,)
+                _bn(s, f"{p}.residual_connector.1", co)
+        _lin(s, "model.fc", E, quartznet_blocks(cfg)[-1][1])
     elif mt == "e2e_dnn":                 # architectures.py:840-865 (E2E_MelSpectrogram_CNN body)
         cin = 1
         for i, c in enumerate((16, 32, 64)):
@@ -323,4 +367,9 @@ def head_macs(cfg: HeadConfig) -> int:
             m += T * k * cin * co + T * k * co * co + (T * cin * co if cin != co else 0)
             cin = co
         m += cin * E
+    elif mt == "quartznet":
+        # per step: depthwise k Cin, pointwise Cin Cout, the projected residual Cin Cout where the widths differ; then fc
+        for cin, co, k in quartznet_blocks(cfg):
+            m += T * (k * cin + cin * co + (cin * co if cin != co else 0))
+        m += quartznet_blocks(cfg)[-1][1] * E
     return int(m)

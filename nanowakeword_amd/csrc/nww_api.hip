@@ -62,7 +62,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_E_BRANCHFORMER) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_QUARTZNET) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)
@@ -81,6 +81,21 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
         for (int i = 0; i < c.n_crnn_channels; ++i)
             if (c.crnn_channels[i] <= 0) return fail(nullptr, NWW_ERR_INVALID, "tcn_channels[%d] = %d must be positive", i, c.crnn_channels[i]);
         if (c.layer_dim < 2) return fail(nullptr, NWW_ERR_INVALID, "tcn_kernel_size must be >= 2 (got %d)", c.layer_dim);
+    }
+    // the QuartzNet's [channels, kernel, repetitions] entries: channels in crnn_channels, kernel + 65536 * repetitions in quartznet_kr
+    if (c.head_type == NWW_HEAD_QUARTZNET) {
+        if (c.n_crnn_channels < 1) return fail(nullptr, NWW_ERR_INVALID, "quartznet_config must have 1..4 [channels, kernel, repetitions] entries (got %d)", c.n_crnn_channels);
+        if (c.n_crnn_channels > 4)
+            return fail(nullptr, NWW_ERR_UNSUPPORTED, "quartznet_config must have 1..4 [channels, kernel, repetitions] entries (got %d)", c.n_crnn_channels);
+        int blocks = 0;
+        for (int i = 0; i < c.n_crnn_channels; ++i) {
+            const int k = c.quartznet_kr[i] & 0xFFFF, r = c.quartznet_kr[i] >> 16;
+            if (c.crnn_channels[i] <= 0) return fail(nullptr, NWW_ERR_INVALID, "quartznet_config[%d] channels = %d must be positive", i, c.crnn_channels[i]);
+            if (c.quartznet_kr[i] < 0 || k < 1) return fail(nullptr, NWW_ERR_INVALID, "quartznet_config[%d] kernel size must be >= 1 (got %d)", i, k);
+            if (r < 1) return fail(nullptr, NWW_ERR_INVALID, "quartznet_config[%d] repetitions must be >= 1 (got %d)", i, r);
+            blocks += r;
+        }
+        if (blocks > 16) return fail(nullptr, NWW_ERR_UNSUPPORTED, "quartznet_config expands to %d blocks; at most 16 are supported", blocks);
     }
     if ((c.head_type == NWW_HEAD_CRNN || c.head_type == NWW_HEAD_GRU) && c.layer_dim > 512)
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "recurrent hidden size (layer_dim = %d) must be <= 512", c.layer_dim);

@@ -27,6 +27,7 @@
 #include "emb_stream.h"
 #include "merge_x3.h"
 #include "tcn_x3.h"
+#include "qn_x3.h"
 
 // rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
 // architectures.py:31)
@@ -170,11 +171,20 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
 void nww_build_spec(nww_handle* h);            // nww_plan.hip
+// NWW_HEAD_QUARTZNET: (Cin, Cout, k) of every block from the packed [channels, kernel, repetitions] entries (include/nww.h)
+struct QnBlock { int cin, cout, k; };
+inline std::vector<QnBlock> nww_quartznet_blocks(const nww_config& c) {
+    std::vector<QnBlock> v;
+    int cin = c.in_cols;
+    for (int i = 0; i < c.n_crnn_channels && i < 4; ++i)
+        for (int r = 0; r < (c.quartznet_kr[i] >> 16); ++r) { v.push_back({cin, c.crnn_channels[i], c.quartznet_kr[i] & 0xFFFF}); cin = c.crnn_channels[i]; }
+    return v;
+}
 
 // The run-time knobs, read from the environment on the first call (nww_plan.hip).  Each selection knob defaults to the
 // specialised kernel; setting it picks a general one.
 struct Knobs {
-    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, mha_mfma, bc_front, bc_chain, tail;
+    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, mha_mfma, bc_front, bc_chain, tail;
     int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
     int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2
 };

@@ -8,7 +8,7 @@ const Knobs& nww_knobs() {
         Knobs r;
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
-        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
+        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
         r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
@@ -161,6 +161,22 @@ void nww_build_spec(nww_handle* h) {
                 cin = co;
             }
             s.lin("model.fc", E, cin);
+            break;
+        }
+        case NWW_HEAD_QUARTZNET: {                // QuartzNetModel (architectures.py:370-437); the entries as include/nww.h packs them
+            const auto blocks = nww_quartznet_blocks(c);
+            for (size_t i = 0; i < blocks.size(); ++i) {
+                const QnBlock& q = blocks[i];
+                const std::string p = "model.quartznet_blocks." + std::to_string(i);
+                s.add(p + ".depthwise_conv.weight", {q.cin, 1, q.k}); s.add(p + ".depthwise_conv.bias", {q.cin});
+                s.add(p + ".pointwise_conv.weight", {q.cout, q.cin, 1}); s.add(p + ".pointwise_conv.bias", {q.cout});
+                s.bn(p + ".batch_norm", q.cout);
+                if (q.cin != q.cout) {
+                    s.add(p + ".residual_connector.0.weight", {q.cout, q.cin, 1}); s.add(p + ".residual_connector.0.bias", {q.cout});
+                    s.bn(p + ".residual_connector.1", q.cout);
+                }
+            }
+            s.lin("model.fc", E, blocks.back().cout);
             break;
         }
         case NWW_HEAD_E2E_DNN: {
@@ -764,6 +780,67 @@ void transpose_depthwise(nww_handle* h) {
             for (int tap = 0; tap < 9; ++tap) wt.data[(size_t)tap * C + ch] = w.data[(size_t)ch * 9 + tap];
         wt.loaded = true;
         h->tensors[k + "_t"] = wt;
+    }
+}
+
+// QuartzNet: everything a block's launches read, folded ONCE in float64 (derived tensors "<block>.qn.*"):
+//   pw [Cout][Cin] = alpha pointwise, res [Cout][Cin] = alpha_r projection, bias [Cout] = alpha (W_pw b_dw + b_pw) + beta (+ alpha_r b_res + beta_r),
+//   dw_t [k][Cp] the depthwise taps tap-major, zeros past Cin (Cp = Cin up to 32), amax [1] = max_c sum_j |tap|, and where qn_x3 has the
+//   widths wcat [Cout][qn_x3_ktot]: pw and res side by side in the fused kernel's chunk order (qn_x3_col)
+void fold_quartznet(nww_handle* h) {
+    const auto blocks = nww_quartznet_blocks(h->cfg);
+    for (size_t i = 0; i < blocks.size(); ++i) {
+        const int Cin = blocks[i].cin, Cout = blocks[i].cout, k = blocks[i].k, Cp = qn_x3_cp(Cin);
+        const bool proj = Cin != Cout;
+        const std::string p = "model.quartznet_blocks." + std::to_string(i);
+        auto D = [&](const std::string& key) -> const std::vector<float>& { return h->tensors[p + key].data; };
+        auto fold = [&](const std::string& bn, std::vector<double>& al, std::vector<double>& be) {
+            const auto &w = D(bn + ".weight"), &b = D(bn + ".bias"), &mu = D(bn + ".running_mean"), &var = D(bn + ".running_var");
+            al.resize(Cout); be.resize(Cout);
+            for (int c = 0; c < Cout; ++c) { al[c] = (double)w[c] / std::sqrt((double)var[c] + 1e-5); be[c] = (double)b[c] - (double)mu[c] * al[c]; }
+        };
+        const auto &dw = D(".depthwise_conv.weight"), &bdw = D(".depthwise_conv.bias"), &pw = D(".pointwise_conv.weight"), &bpw = D(".pointwise_conv.bias");
+        std::vector<double> al, be, alr, ber;
+        fold(".batch_norm", al, be);
+        if (proj) fold(".residual_connector.1", alr, ber);
+        HostTensor tpw, tres, tb, tdw, tam, tcat;
+        tpw.shape = {Cout, Cin}; tpw.data.resize((size_t)Cout * Cin);
+        tb.shape = {Cout}; tb.data.resize(Cout);
+        if (proj) { tres.shape = {Cout, Cin}; tres.data.resize((size_t)Cout * Cin); }
+        const bool cat = Cout % 32 == 0 && Cin <= QN_MAX_C && Cout <= QN_MAX_C;
+        const int Ktot = qn_x3_ktot(Cin, proj);
+        if (cat) { tcat.shape = {Cout, Ktot}; tcat.data.assign((size_t)Cout * Ktot, 0.0f); }
+        for (int co = 0; co < Cout; ++co) {
+            double bias = (double)bpw[co];
+            for (int ci = 0; ci < Cin; ++ci) {
+                const double w = (double)pw[(size_t)co * Cin + ci];
+                bias += w * (double)bdw[ci];
+                tpw.data[(size_t)co * Cin + ci] = (float)(al[co] * w);
+                if (cat) tcat.data[(size_t)co * Ktot + qn_x3_col(Cin, proj, 0, ci)] = tpw.data[(size_t)co * Cin + ci];
+            }
+            bias = al[co] * bias + be[co];
+            if (proj) {
+                const auto &rw = D(".residual_connector.0.weight"), &rb = D(".residual_connector.0.bias");
+                for (int ci = 0; ci < Cin; ++ci) {
+                    tres.data[(size_t)co * Cin + ci] = (float)(alr[co] * (double)rw[(size_t)co * Cin + ci]);
+                    if (cat) tcat.data[(size_t)co * Ktot + qn_x3_col(Cin, proj, 1, ci)] = tres.data[(size_t)co * Cin + ci];
+                }
+                bias += alr[co] * (double)rb[co] + ber[co];
+            }
+            tb.data[co] = (float)bias;
+        }
+        tdw.shape = {k, Cp}; tdw.data.assign((size_t)k * Cp, 0.0f);
+        double amax = 0.0;
+        for (int ci = 0; ci < Cin; ++ci) {
+            double sum = 0.0;
+            for (int j = 0; j < k; ++j) { tdw.data[(size_t)j * Cp + ci] = dw[(size_t)ci * k + j]; sum += std::fabs((double)dw[(size_t)ci * k + j]); }
+            amax = std::fmax(amax, sum);
+        }
+        tam.shape = {1}; tam.data = {(float)(amax * (1.0 + 1e-6))};        // rounded up: it is a bound
+        for (auto* t : {&tpw, &tres, &tb, &tdw, &tam, &tcat}) t->loaded = !t->data.empty();
+        h->tensors[p + ".qn.pw"] = tpw; h->tensors[p + ".qn.bias"] = tb; h->tensors[p + ".qn.dw_t"] = tdw; h->tensors[p + ".qn.amax"] = tam;
+        if (proj) h->tensors[p + ".qn.res"] = tres;
+        if (cat) h->tensors[p + ".qn.wcat"] = tcat;
     }
 }
 
@@ -1723,6 +1800,70 @@ int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.p
     return NWW_OK;
 }
 
+int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architectures.py:370-437; time-major rows [T][C], as the head input is
+    const nww_config& c = p.h->cfg;
+    const int T = c.in_rows;
+    const auto blocks = nww_quartznet_blocks(c);
+    const int nblk = (int)blocks.size();
+    // ping-pong block outputs, depthwise output, pointwise output, projection output, time mean
+    const int dbuf = 2, ybuf = 3, rbuf = 4, mbuf = 5;
+    const int C_last = blocks.back().cout;
+    p.need(mbuf, (size_t)C_last);
+    int in = -1;
+    bool mean_done = false;
+    for (int i = 0; i < nblk; ++i) {
+        const int Cin = blocks[i].cin, Cout = blocks[i].cout, k = blocks[i].k, Cp = qn_x3_cp(Cin);
+        const bool proj = Cin != Cout, last = i == nblk - 1;
+        const std::string q = "model.quartznet_blocks." + std::to_string(i);
+        const int out = i % 2;
+        const float *dwt = p.W(q + ".qn.dw_t"), *bias = p.W(q + ".qn.bias");
+        // ---- the whole block in one clip-resident launch (qn_x3.hip) under the default arithmetic at the shapes it takes: two binary16 terms per
+        // operand, each row scaled by its own power of two inside the kernel - no bound on the features, no clamp
+        bool fused = false;
+        if (nww_knobs().qn_fused && p.h->f16 && p.h->conv_products == 6 && qn_x3_supported(T, Cin, Cout, k) && p.W(q + ".qn.wcat")) {
+            const HostTensor& cat = p.h->tensors[q + ".qn.wcat"];
+            const float ws = f16_wscale(cat.data);
+            void* packed = nullptr;
+            if (ws > 0.0f && hipMalloc(&packed, qn_x3_packed_bytes(Cin, Cout, proj)) == hipSuccess &&
+                launch_qn_x3_pack(p.W(q + ".qn.wcat"), packed, Cout, qn_x3_ktot(Cin, proj), ws, p.h->own_stream) == hipSuccess) {
+                p.h->packed_weights.push_back(packed);
+                const float amax = p.h->tensors[q + ".qn.amax"].data[0];
+                if (!last) p.need(out, (size_t)T * Cout);
+                p.add("qn_x3:" + q + " (dw" + std::to_string(k) + "+pw+bn" + (proj ? "+proj" : "+x") + "+relu" + (last ? "+mean:time" : "") + ") [f16x3]", [=](Run& r) {
+                    QnArgs a;
+                    a.x = src(r, in); a.out = last ? r.buf[mbuf] : r.buf[out]; a.packed = static_cast<const unsigned char*>(packed); a.dw = dwt; a.bias = bias;
+                    a.B = r.B; a.T = T; a.Cin = Cin; a.Cp = Cp; a.Cout = Cout; a.k = k; a.proj = proj ? 1 : 0; a.mean = last ? 1 : 0;
+                    a.amax = amax; a.w_un = 1.0f / ws;
+                    return launch_qn_x3(a, r.cu_count, r.stream);
+                });
+                fused = true;
+                mean_done = last;
+            } else if (packed) {
+                (void)hipFree(packed);
+            }
+        }
+        if (!fused) {
+            // the same folded operands on the general launches: depthwise, pointwise (+ the folded bias), the projection, add + ReLU
+            p.need(dbuf, (size_t)T * Cin); p.need(ybuf, (size_t)T * Cout); p.need(out, (size_t)T * Cout);
+            p.add("dwconv1d:" + q + " (k " + std::to_string(k) + ")", [=](Run& r) { return launch_dwconv1d_same(src(r, in), dwt, r.buf[dbuf], r.B, T, Cin, k, Cp, r.stream); });
+            add_linear(p, q + ".pointwise_conv+bn", dbuf, ybuf, T, Cout, Cin, p.W(q + ".qn.pw"), bias);
+            int res = in;
+            if (proj) {
+                add_linear(p, q + ".residual_connector+bn", in, rbuf, T, Cout, Cin, p.W(q + ".qn.res"), nullptr);
+                res = rbuf;
+            }
+            p.add("add+relu:" + q, [=](Run& r) { return launch_add_relu(r.buf[ybuf], src(r, res), r.buf[out], (size_t)r.B * T * Cout, r.stream); });
+        }
+        in = out;
+    }
+    if (!mean_done) {
+        const int fin = in;
+        p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[fin], r.buf[mbuf], r.B, T, C_last, r.stream); });
+    }
+    set_tail(p, "fc", mbuf, C_last, p.W("model.fc.weight"), p.W("model.fc.bias"));
+    return NWW_OK;
+}
+
 // the head's last Linear (-> embedding) + Model.classifier (model.py:291-296) (+ sigmoid) -> emb [B][E], logits [B] (, probs [B])
 void plan_tail(PlanCtx& p) {
     const int E = p.h->cfg.embedding_dim, act = p.h->cfg.activation;
@@ -1767,6 +1908,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         if (!h->tensors[k].loaded) return fail(h, NWW_ERR_MISSING, "Missing key(s) in state_dict: '%s'", k.c_str());
     fold_batchnorms(h);
     if (h->cfg.head_type == NWW_HEAD_BCRESNET) transpose_depthwise(h);
+    if (h->cfg.head_type == NWW_HEAD_QUARTZNET) fold_quartznet(h);
     int rc = upload_weight_arena(h);
     if (rc == NWW_OK) rc = build_frontend_tables(h);
     if (rc != NWW_OK) return rc;
@@ -1782,6 +1924,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         case NWW_HEAD_TRANSFORMER: rc = plan_transformer(p); break;
         case NWW_HEAD_TCN: rc = plan_tcn(p); break;
         case NWW_HEAD_E_BRANCHFORMER: rc = plan_e_branchformer(p); break;
+        case NWW_HEAD_QUARTZNET: rc = plan_quartznet(p); break;
     }
     if (rc != NWW_OK) return rc;
     plan_tail(p);

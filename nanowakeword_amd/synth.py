@@ -92,12 +92,13 @@ _FIRST_LAYER_KEYS = {
     "model.layer1.weight", "model.conv1.weight", "model.cnn.0.weight", "model.gru.weight_ih_l0",
     "model.gru.weight_ih_l0_reverse", "model.init_conv.0.weight", "model.input_proj.weight",
     "model.conv_block.0.weight", "model.tcn_blocks.0.conv1.weight", "model.tcn_blocks.0.downsample.weight",
+    "model.quartznet_blocks.0.depthwise_conv.weight", "model.quartznet_blocks.0.residual_connector.0.weight",
 }
 
 
 def _is_seq_bn(key: str) -> bool:
     """BatchNorm layers that sit in nn.Sequential containers have numeric names
-    (model.cnn.1, model.conv_block.5, model.init_conv.1, model.blockN.shortcut.1)."""
+    (model.cnn.1, model.conv_block.5, model.init_conv.1, model.blockN.shortcut.1, model.quartznet_blocks.N.residual_connector.1)."""
     parts = key.split(".")
     if len(parts) < 3:
         return False
@@ -107,7 +108,7 @@ def _is_seq_bn(key: str) -> bool:
     n = int(parent_leaf)
     if cont in ("cnn", "conv_block"):
         return n % 4 == 1
-    if cont in ("init_conv", "shortcut"):
+    if cont in ("init_conv", "shortcut", "residual_connector"):
         return n == 1
     return False
 

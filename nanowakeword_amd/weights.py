@@ -113,10 +113,27 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         if input_shape[1] != F:
             raise ValueError(f"input_shape F={input_shape[1]} but the TCN expects {F} features")
         cfg = HeadConfig("tcn", input_shape, tcn_channels=chans, tcn_kernel_size=k, **kw)
+    elif any(k.startswith("model.quartznet_blocks.") for k in keys):
+        if input_shape is None:
+            raise ValueError("quartznet: the sequence length is not in the weights; pass input_shape=(T, F)")
+        nblk = n_indexed(r"model\.quartznet_blocks\.(\d+)\.pointwise_conv\.weight")
+        F = shp("model.quartznet_blocks.0.pointwise_conv.weight")[1]
+        if input_shape[1] != F:
+            raise ValueError(f"input_shape F={input_shape[1]} but the QuartzNet expects {F} features")
+        # consecutive blocks of equal (channels, kernel) are one [channels, kernel, repetitions] entry again
+        qc = []
+        for i in range(nblk):
+            co = shp(f"model.quartznet_blocks.{i}.pointwise_conv.weight")[0]
+            k = shp(f"model.quartznet_blocks.{i}.depthwise_conv.weight")[2]
+            if qc and qc[-1][:2] == [co, k]:
+                qc[-1][2] += 1
+            else:
+                qc.append([co, k, 1])
+        cfg = HeadConfig("quartznet", input_shape, quartznet_config=qc, **kw)
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e_branchformer/e2e_dnn)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:
@@ -272,6 +289,22 @@ def state_dict_from_onnx(path_or_bytes):
             for i, n in enumerate(convs):
                 p = f"model.branchformer_blocks.{i}.conv_branch"
                 folded(n, f"{p}.depthwise_conv.weight", f"{p}.depthwise_conv.bias", f"{p}.batch_norm")
+        elif any(k.startswith("model.quartznet_blocks.") for k in named):           # QuartzNet: the depthwise conv keeps its name, the
+            i = 0                                                                   # pointwise and the projection are folded with their BatchNorms
+            while f"{_WRAP}model.quartznet_blocks.{i}.depthwise_conv.weight" in g.initializers:
+                p = f"model.quartznet_blocks.{i}"
+                dw = next(n for n in g.nodes if n.op_type == "Conv" and n.inputs[1] == f"{_WRAP}{p}.depthwise_conv.weight")
+                pw = [n for n in convs if n.inputs[0] == dw.outputs[0]]
+                sc = [n for n in convs if n.inputs[0] == dw.inputs[0]]
+                if len(pw) != 1 or len(sc) > 1:
+                    raise ValueError(f"quartznet block {i}: unexpected graph structure")
+                W = np.asarray(g.initializers[pw[0].inputs[1]], np.float32)
+                folded(pw[0], f"{p}.pointwise_conv.weight", f"{p}.pointwise_conv.bias", f"{p}.batch_norm")
+                if sc:
+                    folded(sc[0], f"{p}.residual_connector.0.weight", f"{p}.residual_connector.0.bias", f"{p}.residual_connector.1")
+                elif W.shape[0] != W.shape[1]:
+                    raise ValueError(f"quartznet block {i}: widths differ but no projection was found")
+                i += 1
         elif (grus or lstms) and convs:                                             # CRNN (GRU or LSTM backend)
             for i, n in enumerate(convs):
                 folded(n, f"model.cnn.{4*i}.weight", f"model.cnn.{4*i}.bias", f"model.cnn.{4*i+1}")

@@ -19,12 +19,13 @@ def main():
     from nanowakeword_amd.config import FrontendConfig, HeadConfig, head_macs
     from nanowakeword_amd.session import HipModel, torchaudio_tables
     from nanowakeword_amd.synth import synth_pcm, synth_state_dict
-    # the oracle package has no E-Branchformer yet: that head's oracle leg runs the restatement the tests use
+    # the oracle package has no E-Branchformer or QuartzNet yet: those heads' oracle legs run the restatements the tests use
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import ebranchformer_oracle
+    import quartznet_oracle
 
     def oracle_forward(x, sd, cfg):
-        return (ebranchformer_oracle if cfg.model_type == "e_branchformer" else oracle).model_forward(x, sd, cfg)
+        return {"e_branchformer": ebranchformer_oracle, "quartznet": quartznet_oracle}.get(cfg.model_type, oracle).model_forward(x, sd, cfg)
     dev = torch.device("cuda", 0)
     only = sys.argv[1:]
     configs = [
@@ -40,6 +41,7 @@ def main():
         ("gru 64-mel B=4096", HeadConfig("gru", (101, 64)), FrontendConfig(), 4096, 10),
         ("tcn 64-mel B=4096", HeadConfig("tcn", (101, 64)), FrontendConfig(), 4096, 30),
         ("e_branchformer 64-mel B=2048", HeadConfig("e_branchformer", (101, 64)), FrontendConfig(), 2048, 10),
+        ("quartznet 64-mel B=2048", HeadConfig("quartznet", (101, 64)), FrontendConfig(), 2048, 30),
         # the reference's other activations (model.py:81-87) at speed: each within 1.15 x of its ReLU row
         ("C2-gelu cnn 64-mel B=4096 activation=gelu", HeadConfig("cnn", (101, 64), activation="gelu"), FrontendConfig(), 4096, 30),
         ("C2-silu cnn 64-mel B=4096 activation=silu", HeadConfig("cnn", (101, 64), activation="silu"), FrontendConfig(), 4096, 30),

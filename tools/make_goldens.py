@@ -848,6 +848,97 @@ def make_ebranchformer_goldens(out_dir):
     print("onnx fixture e_branchformer", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
 
 
+def quartznet_cases():
+    """QuartzNet head cases of heads_quartznet.npz (name, HeadConfig, outlier): the reference defaults ([[256, 33, 1], [256, 33, 1],
+    [512, 39, 1]]) at (16, 96), (101, 64) and (98, 40), repetitions > 1 with identity-residual blocks, the reference's e2e widths, an even
+    kernel (the odd padding row goes behind), a clip shorter than the kernel, one loud frame, and the GELU classifier (the blocks stay ReLU)."""
+    from nanowakeword_amd.config import HeadConfig
+    qn = lambda shape, qc=None, **kw: HeadConfig("quartznet", shape, **({} if qc is None else {"quartznet_config": qc}), **kw)
+    return [
+        ("quartznet_16x96", qn((16, 96)), False),
+        ("quartznet_101x64", qn((101, 64)), False),
+        ("quartznet_98x40", qn((98, 40)), False),
+        ("quartznet_33x64_reps", qn((33, 64), [[64, 11, 2], [64, 13, 1]]), False),
+        ("quartznet_101x64_e2e_widths", qn((101, 64), [[64, 11, 1], [64, 13, 1], [64, 17, 1]]), False),
+        ("quartznet_33x64_even_k", qn((33, 64), [[128, 8, 1], [128, 8, 1]], embedding_dim=32), False),
+        ("quartznet_5x12", qn((5, 12), [[32, 9, 1], [48, 7, 2]], embedding_dim=16), False),
+        ("quartznet_16x96_outlier", qn((16, 96)), True),
+        ("quartznet_16x96_gelu", qn((16, 96), activation="gelu"), False),
+    ]
+
+
+def quartznet_ref_model(Model, cfg, sd):
+    """The reference's own Model(model_type="quartznet") with the synthetic weights loaded; its state_dict keys / shapes must equal
+    param_spec (model.py:239-248, architectures.py:370-437)."""
+    from nanowakeword_amd.config import param_spec
+    conf = {"activation_function": cfg.activation, "embedding_dim": cfg.embedding_dim, "quartznet_config": [list(e) for e in cfg.quartznet_config]}
+    m = Model(conf, "g", input_shape=cfg.input_shape, model_type=cfg.model_type, layer_dim=cfg.layer_dim, n_blocks=cfg.n_blocks)
+    ref_keys = {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.endswith("num_batches_tracked")}
+    spec = dict(param_spec(cfg))
+    assert ref_keys == spec, (set(ref_keys) ^ set(spec), {k: (ref_keys[k], spec[k]) for k in set(ref_keys) & set(spec) if ref_keys[k] != spec[k]})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.eval()
+
+
+def make_quartznet_goldens(out_dir):
+    """QuartzNet head (own files: earlier fixtures stay byte-identical): logits and embeddings of the reference's Model on seeded synthetic
+    weights -> heads_quartznet.npz, and a reference export of a reduced config with its probabilities -> onnx/quartznet.onnx +
+    expected_quartznet.npz."""
+    install_stubs()
+    torch.set_num_threads(1)
+    from nanowakeword.modules.model import Model
+    from nanowakeword._export import onnx as ref_onnx
+    from nanowakeword_amd.config import HeadConfig
+    from nanowakeword_amd.synth import synth_features, synth_state_dict, state_dict_checksum
+    fr = dict(np.load(os.path.join(out_dir, "frontend.npz"), allow_pickle=False))
+    db64 = fr["db64"]
+    heads, meta = {}, {}
+    for name, cfg, outlier in quartznet_cases():
+        sd = synth_state_dict(cfg)
+        m = quartznet_ref_model(Model, cfg, sd)
+        feats = synth_features(3, cfg.input_shape)
+        if outlier:
+            feats[1, 10, :] *= np.float32(32.0)    # one loud frame (the reference itself sits 1e-5 from float64 here; it loses a digit per x10): per-row scaling
+        with torch.no_grad():
+            out = {"feats": feats, "logits_feat": m(torch.from_numpy(feats)).numpy(), "emb_feat": m.model(torch.from_numpy(feats)).numpy()}
+            if cfg.input_shape == (101, 64) and name == "quartznet_101x64":
+                out["logits_pcm"] = m(torch.from_numpy(np.ascontiguousarray(db64.transpose(0, 2, 1)))).numpy()
+        out["sd_checksum"] = np.array(state_dict_checksum(sd))
+        out["ref_spec_json"] = np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))
+        meta[name] = cfg.to_dict()
+        for k, v in out.items():
+            heads[f"{name}/{k}"] = v
+        print("quartznet", name, {k: getattr(v, "shape", v) for k, v in out.items()}, "logits", out["logits_feat"].ravel())
+    heads["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(out_dir, "heads_quartznet.npz"), **heads)
+
+    # the reference's own export of a small QuartzNet (recipe of make_onnx_fixtures): a projected block, then two identity-residual ones
+    onnx_dir = os.path.join(out_dir, "onnx")
+    from torch.onnx._internal.torchscript_exporter import onnx_proto_utils
+    onnx_proto_utils._add_onnxscript_fn = lambda model_bytes, custom_opsets: model_bytes
+    orig_export = torch.onnx.export
+
+    def export_torchscript(*a, **k):
+        k.setdefault("dynamo", False)
+        return orig_export(*a, **k)
+    torch.onnx.export = export_torchscript
+    cfg = HeadConfig("quartznet", (16, 32), embedding_dim=16, quartznet_config=[[32, 5, 1], [48, 7, 2]])
+    sd = synth_state_dict(cfg)
+    m = quartznet_ref_model(Model, cfg, sd)
+    ref_onnx.export_onnx_model(m, cfg.input_shape, {}, "quartznet", onnx_dir)
+    path = os.path.join(onnx_dir, "quartznet.onnx")
+    assert os.path.exists(path), "export of the quartznet failed"
+    feats = synth_features(4, cfg.input_shape)
+    with torch.no_grad():
+        logits = m(torch.from_numpy(feats)).numpy()
+    arrays = {"quartznet/feats": feats, "quartznet/logits": logits.reshape(-1).astype(np.float32),
+              "quartznet/probs": (1.0 / (1.0 + np.exp(-logits.astype(np.float64)))).reshape(-1).astype(np.float32),
+              "meta_json": np.array(json.dumps({"quartznet": cfg.to_dict()}))}
+    np.savez_compressed(os.path.join(onnx_dir, "expected_quartznet.npz"), **arrays)
+    torch.onnx.export = orig_export
+    print("onnx fixture quartznet", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
+
+
 def make_wire_fixtures(path):
     """Messages produced by the reference's own encoders (remote_verifier.py:147-158) for tests/test_wire.py."""
     from nanowakeword.interpreter import remote_verifier as rv
@@ -1001,6 +1092,8 @@ if __name__ == "__main__":
         make_transformer_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--ebranchformer-only":
         make_ebranchformer_goldens(os.path.join(REPO, "tests", "golden"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--quartznet-only":
+        make_quartznet_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--r02-only":
         make_round2_goldens(os.path.join(REPO, "tests", "golden"))
     else:
