@@ -1,7 +1,7 @@
 """CPU oracle for the PCM -> log-mel -> head -> logit hot path.
 
 TEST INFRASTRUCTURE ONLY.  This package is a numpy restatement of the
-reference's algorithm (nanowakeword @ v3.0.0: the frontend and all nine
+reference's algorithm (nanowakeword @ v3.0.0: the frontend and all eleven
 classifier heads, ``heads._NETS``) and exists to *check* the HIP path.  Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 ``cpu_baseline`` leg may import it; nothing under ``nanowakeword_amd/`` does,
 and the product path raises if the HIP library is missing instead of falling
@@ -26,4 +26,4 @@ parity claim for that mode.
 """
 from .frontend import (default_tables, dft_bases, frame_count, frame_signal,  # noqa: F401
                        mel_power, logmel_db, frontend_logmel)
-from .heads import classify, head_forward, model_forward, sigmoid, tcn_receptive_field  # noqa: F401
+from .heads import classify, depthwise_same, head_forward, model_forward, sigmoid, tcn_receptive_field  # noqa: F401

@@ -331,8 +331,60 @@ def tcn_receptive_field(cfg):
     return 1 + 2 * (cfg.tcn_kernel_size - 1) * (2 ** len(cfg.tcn_channels) - 1)
 
 
+def branchformer_block(x, sd, p, n_head):
+    """EBranchformerBlock / MergingModule (architectures.py:546-596) on the residual stream x [B,T,D]: a = MHA(LN_attn(x)) with no residual
+    of its own, c = ConvolutionModule(x) (the Conformer's), g = sigmoid(gate(c)) - the gate reads the CONV branch -
+    x = LN_final(x + a g + c (1 - g)), then x + FFN(x) with the full residual."""
+    a = mha(layer_norm(x, sd[p + ".attn_branch_norm.weight"], sd[p + ".attn_branch_norm.bias"]), sd, p + ".attention", n_head)
+    c = _conv_module(x, sd, p + ".conv_branch")
+    g = sigmoid(linear(c, sd[p + ".merger.gate.weight"], sd[p + ".merger.gate.bias"]))
+    x = layer_norm(x + (a * g + c * (1 - g)), sd[p + ".final_norm.weight"], sd[p + ".final_norm.bias"])
+    return x + _ffn(x, sd, p + ".ffn")
+
+
+def net_e_branchformer(x, sd, cfg):
+    """EBranchformerModel (architectures.py:597-616): input_proj, the blocks, the mean over time (no LayerNorm in front of it), output_proj."""
+    h = linear(x, sd["model.input_proj.weight"], sd["model.input_proj.bias"])
+    for i in range(cfg.n_blocks):
+        h = branchformer_block(h, sd, f"model.branchformer_blocks.{i}", cfg.branchformer_n_head)
+    return linear(h.mean(axis=1), sd["model.output_proj.weight"], sd["model.output_proj.bias"])
+
+
+def depthwise_same(x, w, b):
+    """nn.Conv1d(C, C, k, padding='same', groups=C) time-major: x [B,T,C], w [C,1,k], b [C] -> [B,T,C],
+    y[t, c] = b[c] + sum_j w[c, 0, j] x[t + j - (k - 1) // 2, c] with zeros outside the clip (PyTorch pads the odd row behind)."""
+    k = w.shape[2]
+    left = (k - 1) // 2
+    xp = np.pad(x, ((0, 0), (left, k - 1 - left), (0, 0)))
+    win = sliding_window_view(xp, k, axis=1)                                  # [B,T,C,k]
+    return np.einsum("btck,ck->btc", win, w[:, 0, :], optimize=True).astype(x.dtype) + b
+
+
+def quartznet_block(x, sd, p):
+    """QuartzNetBlock (architectures.py:370-407), time-major: d = depthwise_conv(x), y = batch_norm(pointwise_conv(d)) with no activation
+    between the two convs, r = BN(conv1x1(x)) where the widths differ, else x; relu(y + r) - nn.ReLU, hard-wired: activation_function
+    reaches the classifier only."""
+    d = depthwise_same(x, sd[p + ".depthwise_conv.weight"], sd[p + ".depthwise_conv.bias"])
+    y = batch_norm(linear(d, sd[p + ".pointwise_conv.weight"][:, :, 0], sd[p + ".pointwise_conv.bias"]), sd, p + ".batch_norm", axis=2)
+    r = x
+    if p + ".residual_connector.0.weight" in sd:
+        r = batch_norm(linear(x, sd[p + ".residual_connector.0.weight"][:, :, 0], sd[p + ".residual_connector.0.bias"]), sd,
+                       p + ".residual_connector.1", axis=2)
+    return np.maximum(y + r, 0).astype(x.dtype)
+
+
+def net_quartznet(x, sd, cfg):
+    """QuartzNetModel (architectures.py:410-437): the blocks of quartznet_config ([channels, kernel, repetitions] entries), the mean over
+    time, fc."""
+    h = x
+    for i in range(sum(r for _, _, r in cfg.quartznet_config)):
+        h = quartznet_block(h, sd, f"model.quartznet_blocks.{i}")
+    return linear(h.mean(axis=1), sd["model.fc.weight"], sd["model.fc.bias"])
+
+
 _NETS = {"dnn": net_dnn, "cnn": net_cnn, "crnn": net_crnn, "gru": net_gru, "bcresnet": net_bcresnet, "conformer": net_conformer,
-         "e2e_dnn": net_e2e_cnn_body, "transformer": net_transformer, "tcn": net_tcn}
+         "e2e_dnn": net_e2e_cnn_body, "transformer": net_transformer, "tcn": net_tcn, "e_branchformer": net_e_branchformer,
+         "quartznet": net_quartznet}
 
 
 def head_forward(x, sd, cfg, dtype=F32):

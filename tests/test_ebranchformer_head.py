@@ -1,5 +1,5 @@
 """E-Branchformer head (model_type="e_branchformer"): configuration, state_dict spec, C-slot mapping, .pt / .onnx ingestion and the numpy
-restatement (tests/ebranchformer_oracle.py) against the reference-generated fixtures and against itself in float64.  CPU only."""
+restatement (oracle/heads.py) against the reference-generated fixtures and against itself in float64.  CPU only."""
 import ctypes
 import json
 import os
@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-import ebranchformer_oracle as eo
+import oracle
 from nanowakeword_amd.config import HEAD_CODE, FrontendConfig, HeadConfig, head_macs, param_spec
 from nanowakeword_amd.synth import state_dict_checksum, synth_features, synth_state_dict
 from parity import GOLDEN, load_head_goldens
@@ -84,10 +84,10 @@ def test_restatement_matches_reference_golden(golden):
         sd = synth_state_dict(cfg)
         assert state_dict_checksum(sd) == str(d[f"{name}/sd_checksum"]), name
         feats = d[f"{name}/feats"]
-        emb = eo.head_forward(feats, sd, cfg)
+        emb = oracle.head_forward(feats, sd, cfg)
         ref_e = d[f"{name}/emb_feat"]
         assert np.abs(emb - ref_e).max() <= 1e-5 * max(1.0, np.abs(ref_e).max()), (name, np.abs(emb - ref_e).max())
-        lg = eo.model_forward(feats, sd, cfg)
+        lg = oracle.model_forward(feats, sd, cfg)
         assert lg.dtype == np.float32 and np.abs(lg - d[f"{name}/logits_feat"]).max() <= 1e-5, (name, np.abs(lg - d[f"{name}/logits_feat"]).max())
 
 
@@ -97,11 +97,11 @@ def test_restatement_float32_vs_float64(golden):
         cfg = HeadConfig(**m)
         sd = synth_state_dict(cfg)
         x = synth_features(6, cfg.input_shape, seed=3)
-        e64 = eo.head_forward(x, sd, cfg, dtype=np.float64)
+        e64 = oracle.head_forward(x, sd, cfg, dtype=np.float64)
         assert e64.dtype == np.float64
-        e32 = eo.head_forward(x, sd, cfg)
+        e32 = oracle.head_forward(x, sd, cfg)
         assert np.abs(e32 - e64).max() <= 1e-5 * max(1.0, np.abs(e64).max()), (name, np.abs(e32 - e64).max())
-        assert np.abs(eo.model_forward(x, sd, cfg) - eo.model_forward(x, sd, cfg, dtype=np.float64)).max() <= 1e-5, name
+        assert np.abs(oracle.model_forward(x, sd, cfg) - oracle.model_forward(x, sd, cfg, dtype=np.float64)).max() <= 1e-5, name
 
 
 def test_gate_ends_select_one_branch():
@@ -113,15 +113,15 @@ def test_gate_ends_select_one_branch():
     for bias, dead in ((30.0, "conv_branch.conv2.bias"), (-30.0, "attention.out_proj.bias")):
         sd = synth_state_dict(cfg)
         sd["model.branchformer_blocks.0.merger.gate.bias"] = np.full(32, bias, np.float32)
-        base = eo.head_forward(x, sd, cfg, dtype=np.float64)
+        base = oracle.head_forward(x, sd, cfg, dtype=np.float64)
         sd2 = dict(sd)
         # a change of the dead branch's output moves nothing (conv2's bias also shifts the gate's input: +-30 dominates it)
         sd2["model.branchformer_blocks.0." + dead] = sd["model.branchformer_blocks.0." + dead] + bump
-        assert np.abs(eo.head_forward(x, sd2, cfg, dtype=np.float64) - base).max() <= 1e-9, dead
+        assert np.abs(oracle.head_forward(x, sd2, cfg, dtype=np.float64) - base).max() <= 1e-9, dead
         live = "attention.out_proj.bias" if dead.startswith("conv") else "conv_branch.conv2.bias"
         sd3 = dict(sd)
         sd3["model.branchformer_blocks.0." + live] = sd["model.branchformer_blocks.0." + live] + bump
-        assert np.abs(eo.head_forward(x, sd3, cfg, dtype=np.float64) - base).max() >= 1e-4, live
+        assert np.abs(oracle.head_forward(x, sd3, cfg, dtype=np.float64) - base).max() >= 1e-4, live
 
 
 def test_pt_ingestion(tmp_path):
@@ -155,6 +155,6 @@ def test_onnx_ingestion():
     # the exporter folds the BatchNorm into the depthwise conv: those tensors come back folded (the same function), the rest bit for bit
     folded = ("depthwise_conv.", "batch_norm.")
     assert all(np.array_equal(sd[k], ref[k]) for k in ref if not any(f in k for f in folded))
-    lg = eo.model_forward(e["e_branchformer/feats"], sd, cfg).ravel()
+    lg = oracle.model_forward(e["e_branchformer/feats"], sd, cfg).ravel()
     assert np.abs(lg - e["e_branchformer/logits"]).max() <= 1e-5
-    assert np.abs(eo.model_forward(e["e_branchformer/feats"], ref, want).ravel() - e["e_branchformer/logits"]).max() <= 1e-5
+    assert np.abs(oracle.model_forward(e["e_branchformer/feats"], ref, want).ravel() - e["e_branchformer/logits"]).max() <= 1e-5

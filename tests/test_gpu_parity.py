@@ -351,7 +351,16 @@ def test_cnn_trunk_odd_shapes(hip, shape, arith):
 _F64_HEADS = (("cnn", (101, 64), {}), ("dnn", (98, 40), {}), ("crnn", (101, 64), {}), ("crnn", (101, 64), {"crnn_rnn_type": "lstm"}),
               ("e2e_dnn", (101, 64), {}), ("conformer", (101, 64), {}), ("gru", (101, 64), {}), ("bcresnet", (101, 64), {}),
               ("transformer", (101, 64), {}), ("transformer", (16, 96), {}), ("tcn", (101, 64), {}), ("tcn", (16, 96), {}),
-              ("tcn", (101, 64), {"tcn_channels": [64, 64, 128, 128]}))          # a 61-step cone: two 32-row tiles
+              ("tcn", (101, 64), {"tcn_channels": [64, 64, 128, 128]}),          # a 61-step cone: two 32-row tiles
+              ("e_branchformer", (101, 64), {}), ("e_branchformer", (16, 96), {}), ("quartznet", (101, 64), {}), ("quartznet", (16, 96), {}),
+              # a width whose second workgroup holds one output block, an identity block there, and a projection down from 288 = 4 x 64 + 32
+              ("quartznet", (33, 64), {"quartznet_config": [[288, 33, 2], [96, 39, 1]]}))
+
+# heads scored relative to max(1, |logit|max) in test_arithmetic_modes_against_float64: nothing (TCN) or only a folded BatchNorm
+# (QuartzNet) normalises them, and the float32 numpy restatement itself is outside 1e-5 absolute of float64 on 48 clips, seed 21 -
+# QuartzNet (101, 64): |logit|max 4.82, 1.31e-5 absolute, 2.7e-6 relative; (16, 96): 8.22, 6.3e-6.  The E-Branchformer rows stay absolute:
+# LayerNorms hold its stream and its restatement is 1.3e-6 ((101, 64), |logit|max 2.29) / 2.1e-6 ((16, 96), 2.61) from float64
+_F64_RELATIVE = ("tcn", "quartznet")
 
 
 # the TCN contract of test_gpu_tcn.py (LOGIT_ATOL + LOGIT_ULPS |ref|): two float32 ulps of the logit on top of the 1e-4 bar
@@ -367,6 +376,16 @@ def _arith_errors_vs_float64(HipModel, cfg, sd, feats, modes=("f32", "bf16x9", "
             # the comparison is the fused two-term kernel beside the im2col + GEMM fallback: hold the plan to that
             plan = m.describe_plan()
             assert ("tcn_x3:" in plan) == (mode == "f16x3") and ("im2col:" in plan and "gemm:" in plan) == (mode != "f16x3"), (mode, plan)
+        elif cfg.model_type == "quartznet":
+            # every block on the fused kernel under the default arithmetic, the general launches under the other three
+            plan = m.describe_plan()
+            nblk = sum(r for _, _, r in cfg.quartznet_config)
+            assert plan.count("qn_x3:") == (nblk if mode == "f16x3" else 0) and plan.count("dwconv1d:") == (0 if mode == "f16x3" else nblk), (mode, plan)
+        elif cfg.model_type == "e_branchformer":
+            # plan_e_branchformer gives the merge to merge_x3 under the two-term binary16 arithmetic only (h->f16 && conv_products == 6):
+            # bf16x9 (conv_products = 9, f16 off) gets the four general launches, as f32 and bf16x6 do
+            plan = m.describe_plan()
+            assert plan.count("merge_x3:") == (cfg.n_blocks if mode == "f16x3" else 0) and plan.count("branch_merge:") == (0 if mode == "f16x3" else cfg.n_blocks), (mode, plan)
         lg, _ = m.forward_features(feats)
         assert np.isfinite(lg).all(), (cfg.model_type, mode)
         if tcn_contract:
@@ -377,9 +396,11 @@ def _arith_errors_vs_float64(HipModel, cfg, sd, feats, modes=("f32", "bf16x9", "
 
 
 def _f64_id(h, shape, k):
-    # the first eight rows keep the ids they have always had; the Transformer / TCN rows come at two shapes each
-    tag = h + ("-" + "-".join("_".join(map(str, v)) if isinstance(v, list) else str(v) for v in k.values()) if k else "")
-    return tag + ("-%dx%d" % shape if h in ("transformer", "tcn") else "")
+    # the first eight rows keep the ids they have always had; the rows of the five newest heads come at more than one shape each
+    def flat(v):
+        return "_".join(flat(e) for e in v) if isinstance(v, list) else str(v)
+    tag = h + ("-" + "-".join(flat(v) for v in k.values()) if k else "")
+    return tag + ("-%dx%d" % shape if h in ("transformer", "tcn", "e_branchformer", "quartznet") else "")
 
 
 _F64_IDS = [_f64_id(h, s, k) for h, s, k in _F64_HEADS]
@@ -397,9 +418,10 @@ def test_arithmetic_modes_against_float64(hip, head, shape, kw):
     feats = synth_features(48, cfg.input_shape, seed=21)
     err, scale = _arith_errors_vs_float64(HipModel, cfg, sd, feats, tcn_contract=head == "tcn")
     print(head, shape, kw, "max |dlogit| vs float64:", err, "|logit|max", scale)
-    if head == "tcn":
+    if head in _F64_RELATIVE:
         # the TCN normalises nothing and its logits on these weights are 10 .. 25: the float32 numpy restatement itself is up to 1.1e-5
-        # (absolute) from float64 there, 7.5e-7 relative to the largest logit - the same two bounds, relative as in the heavy-tailed test
+        # (absolute) from float64 there, 7.5e-7 relative to the largest logit - the same two bounds, relative as in the heavy-tailed test;
+        # QuartzNet likewise (the figures beside _F64_RELATIVE)
         err = {k: v / max(1.0, scale) for k, v in err.items()}
     # every mode 10x inside the 1e-4 bar; the BcResNet head's own float32 noise (ten layers, no normalisation of the residual
     # stream) is 2.3e-5 in EVERY mode, the float32 MFMA path included: 3x inside
@@ -428,6 +450,12 @@ def _heavy_tailed(sd, factor, frac=0.005, seed=77):
     return out
 
 
+# _heavy_tailed's seed where the default one leaves nothing to measure.  The narrow QuartzNet row under seed 77 collapses (float64 oracle, 24
+# clips, seed 22: |logit|max 0.030 / 0.016, ptp 5.4e-3 / 2.7e-5 at x 2^12 / x 2^20); of seeds 78 .. 85 tried in order on the CPU, 85 is the
+# first that keeps ptp above 1e-2 at both factors (|logit|max 0.107 / 0.082, ptp 0.027 / 0.028, float32 restatement 2e-8 relative)
+_HEAVY_SEED = {"quartznet-288_33_2_96_39_1-33x64": 85}
+
+
 @pytest.mark.parametrize("factor", [2.0 ** 12, 2.0 ** 20])
 @pytest.mark.parametrize("head,shape,kw", _F64_HEADS, ids=_F64_IDS)
 def test_heavy_tailed_weights_against_float64(hip, head, shape, kw, factor):
@@ -437,7 +465,7 @@ def test_heavy_tailed_weights_against_float64(hip, head, shape, kw, factor):
     nww_plan.hip F16Range - and this test is what holds that guard to account)."""
     HipModel, _ = hip
     cfg = HeadConfig(head, shape, **kw)
-    sd = _heavy_tailed(synth_state_dict(cfg), factor)
+    sd = _heavy_tailed(synth_state_dict(cfg), factor, seed=_HEAVY_SEED.get(_f64_id(head, shape, kw), 77))
     feats = synth_features(24, cfg.input_shape, seed=22)
     err, scale = _arith_errors_vs_float64(HipModel, cfg, sd, feats, modes=("f32", "f16x3"))
     rel = {k: v / max(1.0, scale) for k, v in err.items()}

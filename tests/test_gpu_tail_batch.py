@@ -1,8 +1,10 @@
 """The large-batch classifier tail (persistent workgroups, weights in LDS, split-K partials summed in the tail) against the
 small-batch kernels it must equal bit for bit (run with -m gpu).
 
-For the CNN head (the tail receives fc1's split-K partials), the GRU head (plain x rows) and the Transformer / TCN heads (plain rows
-too, K = 128, from mean_finish / tcn_x3, whose grids depend on B): logits AND embeddings of the first
+For the CNN head (the tail receives fc1's split-K partials), the GRU head (plain x rows), the Transformer / TCN heads (plain rows
+too, K = 128, from mean_finish / tcn_x3, whose grids depend on B), the E-Branchformer (K = 144, rows from the time mean behind ffn_x3) and
+QuartzNet (rows from qn_x3 +mean:time, each workgroup walking B / gridDim.x clips; K = 512 at the defaults, beyond the large-batch kernel's
+LDS budget, and K = 128 on a one-block configuration, inside it): logits AND embeddings of the first
 B clips of one clip set at B in {17, 1024, 1025, 4096, 4099} equal those of the same clips pushed through in batches of 8 (the
 deferred-reduce small path) and of 1.  A CNN head whose tail weights exceed the kernel's LDS budget (embedding_dim 256) keeps the
 earlier kernel at every batch size: its plan step says so, and the results agree in the same way."""
@@ -51,9 +53,17 @@ def _check(HipModel, cfg, sizes, want_batch_kernel):
     m.close()
 
 
-@pytest.mark.parametrize("head", ["cnn", "gru", "transformer", "tcn"])
-def test_large_batch_tail_equals_small_batches(HipModel, head):
-    _check(HipModel, HeadConfig(head, (101, 64)), SIZES, True)
+# the two newest heads at (16, 96): the tail's operand does not depend on T and the 4099 single-clip calls stay short.  QuartzNet's default tail
+# has K = 512: (E + 8) rows of 516 floats alone are 149 KB, past TB_LDS_MAX = 96 KB, so it keeps the earlier kernel at every batch size (as the
+# embedding_dim 256 case below); [[128, 33, 1]] (K = 128, 50 KB) has a qn_x3 +mean:time launch feed the persistent kernel
+_TAIL_HEADS = [("cnn", (101, 64), {}, True), ("gru", (101, 64), {}, True), ("transformer", (101, 64), {}, True), ("tcn", (101, 64), {}, True),
+               ("e_branchformer", (16, 96), {}, True), ("quartznet", (16, 96), {}, False),
+               ("quartznet", (16, 96), {"quartznet_config": [[128, 33, 1]]}, True)]
+
+
+@pytest.mark.parametrize("head,shape,kw,want_batch_kernel", _TAIL_HEADS, ids=[h + ("-128_33_1" if kw else "") for h, _, kw, _ in _TAIL_HEADS])
+def test_large_batch_tail_equals_small_batches(HipModel, head, shape, kw, want_batch_kernel):
+    _check(HipModel, HeadConfig(head, shape, **kw), SIZES, want_batch_kernel)
 
 
 def test_tail_weights_beyond_lds_budget_fall_back(HipModel):

@@ -1,5 +1,5 @@
 """QuartzNet head (model_type="quartznet"): configuration, state_dict spec, C-slot packing, .pt / .onnx ingestion and the numpy restatement
-(tests/quartznet_oracle.py) against the reference-generated fixtures and against itself in float64.  CPU only."""
+(oracle/heads.py) against the reference-generated fixtures and against itself in float64.  CPU only."""
 import ctypes
 import json
 import os
@@ -9,7 +9,6 @@ import numpy as np
 import pytest
 
 import oracle
-import quartznet_oracle as qo
 from nanowakeword_amd.config import HEAD_CODE, FrontendConfig, HeadConfig, head_macs, param_spec, quartznet_blocks
 from nanowakeword_amd.synth import state_dict_checksum, synth_features, synth_state_dict
 from parity import GOLDEN, LOGIT_ATOL, load_head_goldens
@@ -101,10 +100,10 @@ def test_restatement_matches_reference_golden(golden):
         sd = synth_state_dict(cfg)
         assert state_dict_checksum(sd) == str(d[f"{name}/sd_checksum"]), name
         feats = d[f"{name}/feats"]
-        emb = qo.head_forward(feats, sd, cfg)
+        emb = oracle.head_forward(feats, sd, cfg)
         ref_e = d[f"{name}/emb_feat"]
         assert np.abs(emb - ref_e).max() <= 2e-5 * max(1.0, np.abs(ref_e).max()), (name, np.abs(emb - ref_e).max())
-        lg = qo.model_forward(feats, sd, cfg)
+        lg = oracle.model_forward(feats, sd, cfg)
         err = np.abs(lg - d[f"{name}/logits_feat"]).max()
         print(name, "restatement max |dlogit| vs reference: %.2e" % err)
         assert lg.dtype == np.float32 and err <= LOGIT_ATOL, (name, err)
@@ -121,11 +120,11 @@ def test_restatement_float32_vs_float64(golden):
         cfg = HeadConfig(**m)
         sd = synth_state_dict(cfg)
         x = synth_features(6, cfg.input_shape, seed=3)
-        e64 = qo.head_forward(x, sd, cfg, dtype=np.float64)
+        e64 = oracle.head_forward(x, sd, cfg, dtype=np.float64)
         assert e64.dtype == np.float64
-        e32 = qo.head_forward(x, sd, cfg)
+        e32 = oracle.head_forward(x, sd, cfg)
         assert np.abs(e32 - e64).max() <= 2e-5 * max(1.0, np.abs(e64).max()), (name, np.abs(e32 - e64).max())
-        assert np.abs(qo.model_forward(x, sd, cfg) - qo.model_forward(x, sd, cfg, dtype=np.float64)).max() <= LOGIT_ATOL, name
+        assert np.abs(oracle.model_forward(x, sd, cfg) - oracle.model_forward(x, sd, cfg, dtype=np.float64)).max() <= LOGIT_ATOL, name
 
 
 def test_even_kernel_padding_and_kernel_longer_than_the_clip():
@@ -135,7 +134,7 @@ def test_even_kernel_padding_and_kernel_longer_than_the_clip():
         w = np.arange(1, k + 1, dtype=np.float64).reshape(1, 1, k)
         for t0 in (0, T // 2, T - 1):
             x = np.zeros((1, T, 1)); x[0, t0, 0] = 1.0
-            y = qo.depthwise_same(x, w, np.zeros(1))[0, :, 0]
+            y = oracle.depthwise_same(x, w, np.zeros(1))[0, :, 0]
             want = np.zeros(T)
             for j in range(k):
                 t = t0 + (k - 1) // 2 - j
@@ -148,7 +147,7 @@ def test_even_kernel_padding_and_kernel_longer_than_the_clip():
         x = torch.randn(2, 3, T, dtype=torch.float64, generator=torch.Generator().manual_seed(1))
         with torch.no_grad():
             ref = conv(x).numpy().transpose(0, 2, 1)
-        got = qo.depthwise_same(x.numpy().transpose(0, 2, 1), conv.weight.detach().numpy(), conv.bias.detach().numpy())
+        got = oracle.depthwise_same(x.numpy().transpose(0, 2, 1), conv.weight.detach().numpy(), conv.bias.detach().numpy())
         assert np.abs(got - ref).max() <= 1e-12, (T, k)
 
 
@@ -157,10 +156,10 @@ def test_activation_reaches_the_classifier_only():
     sd = synth_state_dict(relu)
     assert state_dict_checksum(sd) == state_dict_checksum(synth_state_dict(gelu))
     x = synth_features(4, (16, 96), seed=5)
-    assert np.array_equal(qo.head_forward(x, sd, relu), qo.head_forward(x, sd, gelu))          # the blocks stay ReLU
-    assert np.abs(qo.model_forward(x, sd, relu) - qo.model_forward(x, sd, gelu)).max() > 1e-3
-    e = qo.head_forward(x, sd, gelu)
-    assert np.array_equal(qo.model_forward(x, sd, gelu), oracle.classify(e, sd, gelu))
+    assert np.array_equal(oracle.head_forward(x, sd, relu), oracle.head_forward(x, sd, gelu))          # the blocks stay ReLU
+    assert np.abs(oracle.model_forward(x, sd, relu) - oracle.model_forward(x, sd, gelu)).max() > 1e-3
+    e = oracle.head_forward(x, sd, gelu)
+    assert np.array_equal(oracle.model_forward(x, sd, gelu), oracle.classify(e, sd, gelu))
 
 
 def test_pt_ingestion(tmp_path):
@@ -199,7 +198,7 @@ def test_onnx_ingestion():
     # the exporter folds each BatchNorm into the 1x1 conv in front of it: those come back folded (the same function), the rest bit for bit
     folded = ("pointwise_conv.", "batch_norm.", "residual_connector.")
     assert all(np.array_equal(sd[k], ref[k]) for k in ref if not any(f in k for f in folded))
-    lg = qo.model_forward(e["quartznet/feats"], sd, cfg).ravel()
+    lg = oracle.model_forward(e["quartznet/feats"], sd, cfg).ravel()
     print("onnx: max |dlogit| vs the reference's logits: %.2e" % np.abs(lg - e["quartznet/logits"]).max())
     assert np.abs(lg - e["quartznet/logits"]).max() <= LOGIT_ATOL
-    assert np.abs(qo.model_forward(e["quartznet/feats"], ref, want).ravel() - e["quartznet/logits"]).max() <= LOGIT_ATOL
+    assert np.abs(oracle.model_forward(e["quartznet/feats"], ref, want).ravel() - e["quartznet/logits"]).max() <= LOGIT_ATOL

@@ -19,13 +19,7 @@ def main():
     from nanowakeword_amd.config import FrontendConfig, HeadConfig, head_macs
     from nanowakeword_amd.session import HipModel, torchaudio_tables
     from nanowakeword_amd.synth import synth_pcm, synth_state_dict
-    # the oracle package has no E-Branchformer or QuartzNet yet: those heads' oracle legs run the restatements the tests use
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import ebranchformer_oracle
-    import quartznet_oracle
-
-    def oracle_forward(x, sd, cfg):
-        return {"e_branchformer": ebranchformer_oracle, "quartznet": quartznet_oracle}.get(cfg.model_type, oracle).model_forward(x, sd, cfg)
+    oracle_forward = oracle.model_forward
     dev = torch.device("cuda", 0)
     only = sys.argv[1:]
     configs = [
