@@ -46,6 +46,7 @@ extern "C" {
 #define NWW_HEAD_TCN 8         /* TCNModel                architectures.py:290-367 */
 #define NWW_HEAD_E_BRANCHFORMER 9 /* EBranchformerModel   architectures.py:546-616 */
 #define NWW_HEAD_QUARTZNET 10  /* QuartzNetModel          architectures.py:370-437 */
+#define NWW_HEAD_E2E_QUARTZNET 11 /* E2ERawQuartzNet      architectures.py:798-817; model.py:119-132 (learned filters on raw PCM, no STFT) */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1
@@ -71,6 +72,12 @@ typedef struct nww_config {
     /* head: kwargs/config keys of Model() (model.py:67-296)                                  */
     int32_t head_type;         /* NWW_HEAD_*                                                  */
     int32_t in_rows, in_cols;  /* Model(input_shape=(in_rows, in_cols))                       */
+    /* NWW_HEAD_E2E_QUARTZNET: layer_dim carries e2e_frontend_channels and n_blocks e2e_frontend_depth (1..4; E2ERawQuartzNet reads
+       neither, as TCNModel reads no layer_dim); in_cols = layer_dim << (n_blocks - 1) (<= 512) is what its QuartzNet backbone sees,
+       in_rows the raw frontend's rows for the clip length: per stage L' = (L - 1) / stride + 1 with strides 16, 4, 4, ...; its
+       e2e_quartznet_config travels as NWW_HEAD_QUARTZNET's entries do; mel_major_features = 0 and the mel fields are ignored.
+       For this head nww_num_frames is that frame law, nww_frontend* return the learned frontend's output ([B][in_cols][rows], or
+       [B][rows][in_cols] with frames_major; melpower_out must be NULL), nww_forward_features* run the backbone alone */
     int32_t layer_dim, n_blocks, embedding_dim, activation;
     /* crnn_cnn_channels (<= 4 stages) for NWW_HEAD_CRNN; tcn_channels (1..4 levels, model.py:228) for NWW_HEAD_TCN, whose
        tcn_kernel_size (>= 2) travels in layer_dim (TCNModel reads no layer_dim); quartznet_config (model.py:239-248) for

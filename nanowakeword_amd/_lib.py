@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from .config import FrontendConfig, HeadConfig, HEAD_CODE, ACT_CODE
+from .config import FrontendConfig, HeadConfig, HEAD_CODE, ACT_CODE, raw_frontend_depth
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NWW_LIB_PATH") or os.path.join(_PKG, "libnwwhip.so")   # override: A/B builds only
@@ -163,13 +163,17 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
     c.in_rows, c.in_cols = head.input_shape
     c.layer_dim, c.n_blocks, c.embedding_dim = head.layer_dim, head.n_blocks, head.embedding_dim
     c.activation = ACT_CODE[head.activation]
-    if head.model_type == "quartznet":
+    if head.model_type in ("quartznet", "e2e_quartznet"):
         # [channels, kernel, repetitions] entries: channels in the CRNN's channel slots, kernel + 65536 * repetitions beside them; the
         # entry count goes over as it is, so that nww_create refuses more than four instead of a truncated list running
-        c.n_crnn_channels = len(head.quartznet_config)
-        for i, (co, k, r) in enumerate(head.quartznet_config[:4]):
+        qc = head.e2e_quartznet_config if head.model_type == "e2e_quartznet" else head.quartznet_config
+        c.n_crnn_channels = len(qc)
+        for i, (co, k, r) in enumerate(qc[:4]):
             c.crnn_channels[i] = int(co)
             c.quartznet_kr[i] = int(k) + 65536 * int(r)
+        if head.model_type == "e2e_quartznet":
+            # the raw frontend's width and depth travel in layer_dim / n_blocks, which E2ERawQuartzNet does not read (include/nww.h)
+            c.layer_dim, c.n_blocks = head.e2e_frontend_channels, raw_frontend_depth(head)
     else:
         # the TCN's channel list travels in the CRNN's channel slots and its kernel size in layer_dim (include/nww.h)
         ch = list(head.tcn_channels if head.model_type == "tcn" else head.crnn_cnn_channels)

@@ -13,18 +13,20 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn", "e_branchformer",
-              "quartznet")
+              "quartznet", "e2e_quartznet")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
 HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8,
-             "e_branchformer": 9, "quartznet": 10}
+             "e_branchformer": 9, "quartznet": 10, "e2e_quartznet": 11}
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
 # nww_config carries at most 4 [channels, kernel, repetitions] entries of a QuartzNet and the planner at most 16 blocks
 QUARTZNET_MAX_ENTRIES, QUARTZNET_MAX_BLOCKS = 4, 16
+# RawAudioFrontend (architectures.py:692-710): stage 0 is Conv1d(k 41, stride 16, pad 20), every later stage Conv1d(k 13, stride 4, pad 6)
+RAW_FRONTEND_MAX_DEPTH, RAW_FRONTEND_MAX_WIDTH = 4, 512
 # rows of the Transformer's positional-encoding buffer (PositionalEncoding(max_len=5000), architectures.py:31)
 PE_MAX_LEN = 5000
 
@@ -75,6 +77,10 @@ class HeadConfig:
     branchformer_n_head: int = 4
     # model.py:239-248 config key of the QuartzNet head: [[channels, kernel, repetitions], ...]
     quartznet_config: List[List[int]] = field(default_factory=lambda: [[256, 33, 1], [256, 33, 1], [512, 39, 1]])
+    # model.py:99-100,119-132 config keys of the raw-PCM heads (mode="e2e"); depth None is the model type's own default (3 for e2e_quartznet)
+    e2e_frontend_channels: int = 32
+    e2e_frontend_depth: Optional[int] = None
+    e2e_quartznet_config: List[List[int]] = field(default_factory=lambda: [[64, 11, 1], [64, 13, 1], [64, 17, 1]])
 
     def __post_init__(self):
         self.model_type = self.model_type.lower()
@@ -106,24 +112,43 @@ class HeadConfig:
                 raise ValueError(f"branchformer_d_model must be divisible by branchformer_n_head "
                                  f"(got {self.branchformer_d_model} / {self.branchformer_n_head})")
 
-        if self.model_type == "quartznet":
-            qc = [list(e) for e in self.quartznet_config]
-            if not 1 <= len(qc) <= QUARTZNET_MAX_ENTRIES:
-                raise ValueError(f"quartznet_config must have 1..{QUARTZNET_MAX_ENTRIES} [channels, kernel, repetitions] entries (got {len(qc)})")
-            if any(len(e) != 3 for e in qc):
-                raise ValueError(f"quartznet_config entries must be [channels, kernel, repetitions] (got {qc})")
-            qc = [[int(v) for v in e] for e in qc]
-            if any(c <= 0 for c, _, _ in qc):
-                raise ValueError(f"quartznet_config channels must be positive (got {qc})")
-            if any(k < 1 or k > 0xFFFF for _, k, _ in qc):
-                raise ValueError(f"quartznet_config kernel sizes must be 1..65535 (got {qc})")
-            if any(r < 1 for _, _, r in qc):
-                raise ValueError(f"quartznet_config repetitions must be >= 1 (got {qc})")
-            if sum(r for _, _, r in qc) > QUARTZNET_MAX_BLOCKS:
-                raise ValueError(f"quartznet_config expands to {sum(r for _, _, r in qc)} blocks; at most {QUARTZNET_MAX_BLOCKS} are supported")
-            self.quartznet_config = qc
-        else:
-            self.quartznet_config = [[int(v) for v in e] for e in self.quartznet_config]
+        self.quartznet_config = self._quartznet_entries("quartznet_config", self.quartznet_config, self.model_type == "quartznet")
+        self.e2e_quartznet_config = self._quartznet_entries("e2e_quartznet_config", self.e2e_quartznet_config, self.model_type == "e2e_quartznet")
+        self.e2e_frontend_channels = int(self.e2e_frontend_channels)
+        self.e2e_frontend_depth = None if self.e2e_frontend_depth is None else int(self.e2e_frontend_depth)
+        if self.model_type == "e2e_quartznet":
+            depth = raw_frontend_depth(self)
+            if not 1 <= depth <= RAW_FRONTEND_MAX_DEPTH:
+                raise ValueError(f"e2e_frontend_depth must be 1..{RAW_FRONTEND_MAX_DEPTH} (got {depth})")
+            if self.e2e_frontend_channels <= 0:
+                raise ValueError(f"e2e_frontend_channels must be positive (got {self.e2e_frontend_channels})")
+            width = self.e2e_frontend_channels * 2 ** (depth - 1)
+            if width > RAW_FRONTEND_MAX_WIDTH:
+                raise ValueError(f"the raw frontend's final width e2e_frontend_channels * 2^(depth - 1) = {width} must be <= {RAW_FRONTEND_MAX_WIDTH}")
+            if self.input_shape[1] != width:
+                raise ValueError(f"input_shape is what the backbone sees, (rows, {width}) for e2e_frontend_channels = {self.e2e_frontend_channels} "
+                                 f"at depth {depth} (got {self.input_shape})")
+
+    @staticmethod
+    def _quartznet_entries(name, entries, validate):
+        """[[channels, kernel, repetitions], ...] as lists of ints; the limits hold for the head that reads the field."""
+        if not validate:
+            return [[int(v) for v in e] for e in entries]
+        qc = [list(e) for e in entries]
+        if not 1 <= len(qc) <= QUARTZNET_MAX_ENTRIES:
+            raise ValueError(f"{name} must have 1..{QUARTZNET_MAX_ENTRIES} [channels, kernel, repetitions] entries (got {len(qc)})")
+        if any(len(e) != 3 for e in qc):
+            raise ValueError(f"{name} entries must be [channels, kernel, repetitions] (got {qc})")
+        qc = [[int(v) for v in e] for e in qc]
+        if any(c <= 0 for c, _, _ in qc):
+            raise ValueError(f"{name} channels must be positive (got {qc})")
+        if any(k < 1 or k > 0xFFFF for _, k, _ in qc):
+            raise ValueError(f"{name} kernel sizes must be 1..65535 (got {qc})")
+        if any(r < 1 for _, _, r in qc):
+            raise ValueError(f"{name} repetitions must be >= 1 (got {qc})")
+        if sum(r for _, _, r in qc) > QUARTZNET_MAX_BLOCKS:
+            raise ValueError(f"{name} expands to {sum(r for _, _, r in qc)} blocks; at most {QUARTZNET_MAX_BLOCKS} are supported")
+        return qc
 
     def to_dict(self):
         return asdict(self)
@@ -132,11 +157,45 @@ class HeadConfig:
 def quartznet_blocks(cfg: "HeadConfig"):
     """(Cin, Cout, k) of every QuartzNetBlock in order (QuartzNetModel.__init__, architectures.py:410-423)."""
     out, cin = [], cfg.input_shape[1]
-    for c, k, r in cfg.quartznet_config:
+    for c, k, r in (cfg.e2e_quartznet_config if cfg.model_type == "e2e_quartznet" else cfg.quartznet_config):
         for _ in range(r):
             out.append((cin, c, k))
             cin = c
     return out
+
+
+def raw_frontend_depth(cfg: "HeadConfig") -> int:
+    """Stages of the raw-PCM frontend: e2e_frontend_depth, or the model type's default (model.py:121)."""
+    return 3 if cfg.e2e_frontend_depth is None else cfg.e2e_frontend_depth
+
+
+def raw_frontend_stages(cfg: "HeadConfig"):
+    """(Cin, Cout, kernel, stride) of every RawAudioFrontend stage (architectures.py:692-710); padding is kernel // 2 zeros each side."""
+    out, cin = [], 1
+    for i in range(raw_frontend_depth(cfg)):
+        co = cfg.e2e_frontend_channels * 2 ** i
+        out.append((cin, co, 41 if i == 0 else 13, 16 if i == 0 else 4))
+        cin = co
+    return out
+
+
+def raw_frontend_frames(cfg: "HeadConfig", n_samples: int) -> int:
+    """Frame law of the raw frontend (bit-exact requirement): per stage L' = (L - 1) // stride + 1, for any L >= 1."""
+    n = int(n_samples)
+    if n < 1:
+        raise ValueError("a clip needs at least one sample")
+    for _, _, _, s in raw_frontend_stages(cfg):
+        n = (n - 1) // s + 1
+    return n
+
+
+def raw_frontend_macs(cfg: "HeadConfig", n_samples: int) -> int:
+    """Multiply-accumulates of the raw frontend for a clip of n_samples, rows from the frame law."""
+    m, n = 0, int(n_samples)
+    for cin, co, k, s in raw_frontend_stages(cfg):
+        n = (n - 1) // s + 1
+        m += n * k * cin * co
+    return m
 
 
 def _bn(spec, prefix, c):
@@ -278,16 +337,22 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
                 s[f"{p}.downsample.weight"] = (co, cin, 1); s[f"{p}.downsample.bias"] = (co,)
             cin = co
         _lin(s, "model.fc", E, cin)
-    elif mt == "quartznet":               # architectures.py:370-437 (QuartzNetBlock, QuartzNetModel)
+    elif mt in ("quartznet", "e2e_quartznet"):   # architectures.py:370-437 (QuartzNetBlock, QuartzNetModel); :798-817 E2ERawQuartzNet
+        qp = "model."
+        if mt == "e2e_quartznet":         # RawAudioFrontend's nn.Sequential: Conv1d (no bias), BatchNorm1d, ReLU per stage
+            qp = "model.backbone."
+            for i, (cin, co, k, _) in enumerate(raw_frontend_stages(cfg)):
+                s[f"model.frontend.conv_blocks.{3*i}.weight"] = (co, cin, k)
+                _bn(s, f"model.frontend.conv_blocks.{3*i+1}", co)
         for i, (cin, co, k) in enumerate(quartznet_blocks(cfg)):
-            p = f"model.quartznet_blocks.{i}"
+            p = f"{qp}quartznet_blocks.{i}"
             s[f"{p}.depthwise_conv.weight"] = (cin, 1, k); s[f"{p}.depthwise_conv.bias"] = (cin,)
             s[f"{p}.pointwise_conv.weight"] = (co, cin, 1); s[f"{p}.pointwise_conv.bias"] = (co,)
             _bn(s, f"{p}.batch_norm", co)
             if cin != co:                 # the projected residual exists only when the widths differ
                 s[f"{p}.residual_connector.0.weight"] = (co, cin, 1); s[f"{p}.residual_connector.0.bias"] = (co,)
                 _bn(s, f"{p}.residual_connector.1", co)
-        _lin(s, "model.fc", E, quartznet_blocks(cfg)[-1][1])
+        _lin(s, f"{qp}fc", E, quartznet_blocks(cfg)[-1][1])
     elif mt == "e2e_dnn":                 # architectures.py:840-865 (E2E_MelSpectrogram_CNN body)
         cin = 1
         for i, c in enumerate((16, 32, 64)):
@@ -367,7 +432,15 @@ def head_macs(cfg: HeadConfig) -> int:
             m += T * k * cin * co + T * k * co * co + (T * cin * co if cin != co else 0)
             cin = co
         m += cin * E
-    elif mt == "quartznet":
+    elif mt in ("quartznet", "e2e_quartznet"):
+        if mt == "e2e_quartznet":
+            # an UPPER estimate for the raw frontend: the clip length is not in the config, so rows of a stage are taken as rows of the
+            # next x its stride (1008 and 252 at the defaults where a 1 s clip has 1000 and 250: 14.74 against 14.68 MMAC);
+            # raw_frontend_macs(cfg, n_samples) is the exact count for a clip length
+            rows = T
+            for cin, co, k, stride in reversed(raw_frontend_stages(cfg)):
+                m += rows * k * cin * co
+                rows *= stride
         # per step: depthwise k Cin, pointwise Cin Cout, the projected residual Cin Cout where the widths differ; then fc
         for cin, co, k in quartznet_blocks(cfg):
             m += T * (k * cin + cin * co + (cin * co if cin != co else 0))

@@ -62,7 +62,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_QUARTZNET) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_E2E_QUARTZNET) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)
@@ -83,7 +83,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
         if (c.layer_dim < 2) return fail(nullptr, NWW_ERR_INVALID, "tcn_kernel_size must be >= 2 (got %d)", c.layer_dim);
     }
     // the QuartzNet's [channels, kernel, repetitions] entries: channels in crnn_channels, kernel + 65536 * repetitions in quartznet_kr
-    if (c.head_type == NWW_HEAD_QUARTZNET) {
+    if (c.head_type == NWW_HEAD_QUARTZNET || c.head_type == NWW_HEAD_E2E_QUARTZNET) {
         if (c.n_crnn_channels < 1) return fail(nullptr, NWW_ERR_INVALID, "quartznet_config must have 1..4 [channels, kernel, repetitions] entries (got %d)", c.n_crnn_channels);
         if (c.n_crnn_channels > 4)
             return fail(nullptr, NWW_ERR_UNSUPPORTED, "quartznet_config must have 1..4 [channels, kernel, repetitions] entries (got %d)", c.n_crnn_channels);
@@ -96,6 +96,15 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
             blocks += r;
         }
         if (blocks > 16) return fail(nullptr, NWW_ERR_UNSUPPORTED, "quartznet_config expands to %d blocks; at most 16 are supported", blocks);
+    }
+    // the raw-PCM frontend's channels / depth travel in layer_dim / n_blocks (include/nww.h)
+    if (c.head_type == NWW_HEAD_E2E_QUARTZNET) {
+        if (c.n_blocks < 1 || c.n_blocks > 4) return fail(nullptr, NWW_ERR_INVALID, "e2e_frontend_depth must be 1..4 (got %d)", c.n_blocks);
+        if (c.layer_dim > 512 || (c.layer_dim << (c.n_blocks - 1)) > 512)
+            return fail(nullptr, NWW_ERR_INVALID, "the raw frontend's final width e2e_frontend_channels * 2^(depth - 1) must be <= 512 (got %d at depth %d)", c.layer_dim, c.n_blocks);
+        if (c.in_cols != (c.layer_dim << (c.n_blocks - 1)))
+            return fail(nullptr, NWW_ERR_INVALID, "in_cols = %d but the raw frontend gives %d channels", c.in_cols, c.layer_dim << (c.n_blocks - 1));
+        if (c.mel_major_features) return fail(nullptr, NWW_ERR_INVALID, "mel_major_features must be 0 for the raw-PCM heads");
     }
     if ((c.head_type == NWW_HEAD_CRNN || c.head_type == NWW_HEAD_GRU) && c.layer_dim > 512)
         return fail(nullptr, NWW_ERR_UNSUPPORTED, "recurrent hidden size (layer_dim = %d) must be <= 512", c.layer_dim);
@@ -142,8 +151,9 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
 
 static void free_ws(nww_handle* h) {
     for (void* p : {(void*)h->d_ws, (void*)h->d_pcm, (void*)h->d_logmel, (void*)h->d_feats, (void*)h->d_emb,
-                    (void*)h->d_hid, (void*)h->d_logits, (void*)h->d_probs, (void*)h->d_splitk})
+                    (void*)h->d_hid, (void*)h->d_logits, (void*)h->d_probs, (void*)h->d_splitk, (void*)h->d_raw[0], (void*)h->d_raw[1]})
         if (p) (void)hipFree(p);
+    h->d_raw[0] = h->d_raw[1] = nullptr;
     h->d_ws = nullptr; h->d_pcm = nullptr; h->d_logmel = nullptr; h->d_feats = nullptr; h->d_emb = nullptr;
     h->d_hid = nullptr; h->d_logits = nullptr; h->d_probs = nullptr; h->d_splitk = nullptr; h->cap_B = 0; h->cap_N = 0;
 }
@@ -217,7 +227,7 @@ extern "C" int nww_load_tensor(nww_handle* h, const char* key, const void* host,
     return NWW_OK;
 }
 
-extern "C" int32_t nww_num_frames(const nww_handle* h, int32_t n) { return h ? fe_num_frames(h->fe, n) : -1; }
+extern "C" int32_t nww_num_frames(const nww_handle* h, int32_t n) { return h ? nww_pcm_rows(h, n) : -1; }
 
 extern "C" int nww_set_profiling(nww_handle* h, int32_t enable) {
     if (!h) return NWW_ERR_INVALID;
@@ -264,6 +274,11 @@ extern "C" float nww_feature_clamp(const nww_handle* h) {
 extern "C" int nww_describe_plan(const nww_handle* h, char* buf, int32_t buflen) {
     if (!h || !buf || buflen <= 0) return NWW_ERR_INVALID;
     std::string s = "frontend:fe_stft_mel_db_kernel\n";
+    if (nww_raw_head(h->cfg)) {                        // the learned raw-PCM frontend: one line per launch
+        s.clear();
+        if (h->raw_fused) s += "frontend:" + h->raw_fused_name + "\n";
+        else for (const auto& st : h->raw) s += "frontend:" + st.name + "\n";
+    }
     for (const auto& st : h->plan) s += st.name + "\n";
     s += "unary:sigmoid\n";
     std::snprintf(buf, (size_t)buflen, "%s", s.c_str());
@@ -280,10 +295,21 @@ int nww_ensure_ws(nww_handle* h, int B, int N) {
     size_t per = 0;
     for (int i = 0; i < 6; ++i) per += (h->buf_per_clip[i] + 3) & ~(size_t)3;
     HIP_TRY(h, hipMalloc(&h->d_ws, (per * (size_t)((nB + 127) / 128 * 128) + 4) * sizeof(float)));
-    const int T = nN > 0 ? fe_num_frames(h->fe, nN) : 0;
+    const int T = nN > 0 ? nww_pcm_rows(h, nN) : 0;
     if (nN > 0) {
         HIP_TRY(h, hipMalloc(&h->d_pcm, (size_t)nB * nN * sizeof(int16_t) + 16));
-        if (T > 0) HIP_TRY(h, hipMalloc(&h->d_logmel, (size_t)nB * T * c.n_mels * sizeof(float) + 16));
+        if (T > 0) HIP_TRY(h, hipMalloc(&h->d_logmel, (size_t)nB * T * (nww_raw_head(c) ? c.in_cols : c.n_mels) * sizeof(float) + 16));
+        if (nww_raw_head(c) && h->raw.size() > 1 && !h->raw_fused) {
+            // the rows between the stages: stage i writes d_raw[i & 1] (the last one d_logmel)
+            size_t per[2] = {0, 0};
+            int L = nN;
+            for (size_t i = 0; i + 1 < h->raw.size(); ++i) {
+                L = raw_conv_rows(L, h->raw[i].stride);
+                per[i & 1] = std::max(per[i & 1], (size_t)L * h->raw[i].cout);
+            }
+            for (int q = 0; q < 2; ++q)
+                if (per[q]) HIP_TRY(h, hipMalloc(&h->d_raw[q], per[q] * (size_t)nB * sizeof(float) + 16));
+        }
     }
     HIP_TRY(h, hipMalloc(&h->d_feats, (size_t)nB * c.in_rows * c.in_cols * sizeof(float) + 16));
     HIP_TRY(h, hipMalloc(&h->d_emb, (size_t)nB * c.embedding_dim * sizeof(float) + 16));
@@ -356,8 +382,46 @@ int nww_check_run(nww_handle* h, int B) {
     return NWW_OK;
 }
 
+// the learned raw-PCM frontend: one conv1d_strided launch per stage (float32 fmaf on the folded operands), rows ping-ponging between
+// d_raw[0] and d_raw[1]; the last stage writes d_out time-major [B][rows][C], or [B][C][rows] when frames_major is 0
+static int nww_raw_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_out, int frames_major, hipStream_t s,
+                                   int* frames_out, size_t row_stride) {
+    const int T = nww_pcm_rows(h, N);
+    if (T <= 0) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
+    if (frames_out) *frames_out = T;
+    int rc = nww_ensure_ws(h, B, N);
+    if (rc) return rc;
+    int L = N;
+    if (h->raw_fused) {
+        RawX3Args a = h->raw_x3;
+        a.pcm = d_pcm; a.pcm_stride = row_stride ? row_stride : (size_t)N; a.y = d_out; a.B = B; a.N = N; a.ct_out = !frames_major;
+        for (int i = 0; i < a.depth; ++i) { L = raw_conv_rows(L, i == 0 ? 16 : 4); a.L[i] = L; }
+        hipError_t e = launch_raw_x3(a, s);
+        if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch '%s' failed: %s", h->raw_fused_name.c_str(), hipGetErrorString(e));
+        return NWW_OK;
+    }
+    const float* in = nullptr;
+    for (size_t i = 0; i < h->raw.size(); ++i) {
+        const auto& st = h->raw[i];
+        const bool last = i + 1 == h->raw.size();
+        RawConvArgs a;
+        if (i == 0) { a.pcm = d_pcm; a.pcm_stride = row_stride ? row_stride : (size_t)N; } else a.x = in;
+        a.w = st.w; a.bias = st.b; a.y = last ? d_out : h->d_raw[i & 1];
+        a.B = B; a.L = L; a.Cin = st.cin; a.Cout = st.cout; a.k = st.k; a.stride = st.stride; a.ct_out = last && !frames_major;
+        hipError_t e = launch_conv1d_strided(a, s);
+        if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch '%s' failed: %s", st.name.c_str(), hipGetErrorString(e));
+        in = a.y;
+        L = raw_conv_rows(L, st.stride);
+    }
+    return NWW_OK;
+}
+
 int nww_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_db, float* d_mel, int frames_major,
                         hipStream_t s, int* frames_out, size_t row_stride, const Fe2Sub* sub) {
+    if (nww_raw_head(h->cfg)) {
+        if (d_mel || sub) return fail(h, NWW_ERR_INVALID, "the raw-PCM frontend has no mel power and no frame subsets");
+        return nww_raw_frontend_on_dev(h, d_pcm, B, N, d_db, frames_major, s, frames_out, row_stride);
+    }
     const int T = fe_num_frames(h->fe, N);
     if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
     if (frames_out) *frames_out = T;
@@ -379,9 +443,10 @@ extern "C" int nww_frontend_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, 
 int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_logits, float* d_probs, hipStream_t s,
                            size_t row_stride, unsigned int* done_flag, unsigned int done_seq, bool* done_armed) {
     const nww_config& c = h->cfg;
-    const int T = fe_num_frames(h->fe, N);
+    const int T = nww_pcm_rows(h, N);
+    if (T <= 0 && nww_raw_head(c)) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
     if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
-    const int rows = c.mel_major_features ? c.n_mels : T, cols = c.mel_major_features ? T : c.n_mels;
+    const int rows = c.mel_major_features ? c.n_mels : T, cols = nww_raw_head(c) ? c.in_cols : c.mel_major_features ? T : c.n_mels;
     if (rows != c.in_rows || cols != c.in_cols)
         return fail(h, NWW_ERR_SHAPE, "frontend yields (%d,%d) features for %d samples but the head was built for input_shape=(%d,%d)",
                     rows, cols, N, c.in_rows, c.in_cols);
@@ -423,12 +488,14 @@ extern "C" int nww_frontend_ex(nww_handle* h, const int16_t* pcm, int32_t B, int
     if (rc) return rc;
     if (!pcm) return fail(h, NWW_ERR_INVALID, "Input audio must be a non-null int16 array");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int T = fe_num_frames(h->fe, N);
+    const int T = nww_pcm_rows(h, N);
+    if (T <= 0 && nww_raw_head(h->cfg)) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
     if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
+    if (nww_raw_head(h->cfg) && melpower_out) return fail(h, NWW_ERR_INVALID, "melpower_out must be NULL: the raw-PCM frontend has no mel power");
     rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
-    const size_t n_out = (size_t)B * T * h->cfg.n_mels;
+    const size_t n_out = (size_t)B * T * (nww_raw_head(h->cfg) ? h->cfg.in_cols : h->cfg.n_mels);
     struct DevScratch {            // frees the optional mel-power scratch on every exit path
         float* p = nullptr;
         ~DevScratch() { if (p) (void)hipFree(p); }

@@ -4,6 +4,7 @@
 // nww_emb.hip: embedding-mode state (nww_emb_*).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -28,6 +29,8 @@
 #include "merge_x3.h"
 #include "tcn_x3.h"
 #include "qn_x3.h"
+#include "raw_conv.h"
+#include "raw_x3.h"
 
 // rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
 // architectures.py:31)
@@ -99,6 +102,13 @@ struct nww_handle {
     int cap_rows = 0;              // cap_B rounded up to 128: the blocked trunk -> fc1 buffer is written in 128-clip row blocks
     float* d_ws = nullptr;
     int16_t* d_pcm = nullptr;
+    // NWW_HEAD_E2E_QUARTZNET: the stages of the learned raw-PCM frontend (planned at nww_finalize) and the two buffers its
+    // intermediate rows alternate between; its last stage writes d_logmel (time-major, what the backbone reads)
+    struct RawStage { std::string name; int cin, cout, k, stride; const float *w, *b; };
+    std::vector<RawStage> raw;
+    // ... or the whole frontend as one raw_x3 launch (the default under f16x3 at the shapes it takes): its arguments but the run's own
+    bool raw_fused = false; std::string raw_fused_name; RawX3Args raw_x3;
+    float* d_raw[2] = {nullptr, nullptr};
     float* d_logmel = nullptr;     // [B][n_mels*frames]
     float* d_feats = nullptr;      // staging for host feature input
     float* d_emb = nullptr;
@@ -171,6 +181,17 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
 void nww_build_spec(nww_handle* h);            // nww_plan.hip
+inline bool nww_raw_head(const nww_config& c) { return c.head_type == NWW_HEAD_E2E_QUARTZNET; }
+// rows the head's frontend yields for N samples: the STFT's frame count, or for the raw-PCM heads the strided convs' frame law
+// (stage 0 stride 16, every later stage 4; zero padding, so any N >= 1 has rows)
+inline int nww_pcm_rows(const nww_handle* h, int N) {
+    if (!nww_raw_head(h->cfg)) return fe_num_frames(h->fe, N);
+    int L = N;
+    for (int i = 0; i < h->cfg.n_blocks; ++i) L = raw_conv_rows(L, i == 0 ? 16 : 4);
+    return L < 1 ? -1 : L;
+}
+// the QuartzNet blocks' and fc's key prefix: the raw-PCM head holds them under model.backbone
+inline std::string nww_quartznet_prefix(const nww_config& c) { return nww_raw_head(c) ? "model.backbone." : "model."; }
 // NWW_HEAD_QUARTZNET: (Cin, Cout, k) of every block from the packed [channels, kernel, repetitions] entries (include/nww.h)
 struct QnBlock { int cin, cout, k; };
 inline std::vector<QnBlock> nww_quartznet_blocks(const nww_config& c) {
@@ -184,7 +205,7 @@ inline std::vector<QnBlock> nww_quartznet_blocks(const nww_config& c) {
 // The run-time knobs, read from the environment on the first call (nww_plan.hip).  Each selection knob defaults to the
 // specialised kernel; setting it picks a general one.
 struct Knobs {
-    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, mha_mfma, bc_front, bc_chain, tail;
+    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, raw_fused, mha_mfma, bc_front, bc_chain, tail;
     int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
     int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2
 };

@@ -8,7 +8,7 @@ const Knobs& nww_knobs() {
         Knobs r;
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
-        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
+        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
         r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
@@ -163,11 +163,20 @@ void nww_build_spec(nww_handle* h) {
             s.lin("model.fc", E, cin);
             break;
         }
+        case NWW_HEAD_E2E_QUARTZNET:              // E2ERawQuartzNet (architectures.py:798-817): RawAudioFrontend's Conv1d (no bias) + BatchNorm1d
+            for (int i = 0, cin = 1; i < nb; ++i) {   // per stage (channels in layer_dim, depth in n_blocks), then the QuartzNet under model.backbone
+                const int co = L << i;
+                s.add("model.frontend.conv_blocks." + std::to_string(3 * i) + ".weight", {co, cin, i == 0 ? 41 : 13});
+                s.bn("model.frontend.conv_blocks." + std::to_string(3 * i + 1), co);
+                cin = co;
+            }
+            [[fallthrough]];
         case NWW_HEAD_QUARTZNET: {                // QuartzNetModel (architectures.py:370-437); the entries as include/nww.h packs them
             const auto blocks = nww_quartznet_blocks(c);
+            const std::string qp = nww_quartznet_prefix(c);
             for (size_t i = 0; i < blocks.size(); ++i) {
                 const QnBlock& q = blocks[i];
-                const std::string p = "model.quartznet_blocks." + std::to_string(i);
+                const std::string p = qp + "quartznet_blocks." + std::to_string(i);
                 s.add(p + ".depthwise_conv.weight", {q.cin, 1, q.k}); s.add(p + ".depthwise_conv.bias", {q.cin});
                 s.add(p + ".pointwise_conv.weight", {q.cout, q.cin, 1}); s.add(p + ".pointwise_conv.bias", {q.cout});
                 s.bn(p + ".batch_norm", q.cout);
@@ -176,7 +185,7 @@ void nww_build_spec(nww_handle* h) {
                     s.bn(p + ".residual_connector.1", q.cout);
                 }
             }
-            s.lin("model.fc", E, blocks.back().cout);
+            s.lin(qp + "fc", E, blocks.back().cout);
             break;
         }
         case NWW_HEAD_E2E_DNN: {
@@ -792,7 +801,7 @@ void fold_quartznet(nww_handle* h) {
     for (size_t i = 0; i < blocks.size(); ++i) {
         const int Cin = blocks[i].cin, Cout = blocks[i].cout, k = blocks[i].k, Cp = qn_x3_cp(Cin);
         const bool proj = Cin != Cout;
-        const std::string p = "model.quartznet_blocks." + std::to_string(i);
+        const std::string p = nww_quartznet_prefix(h->cfg) + "quartznet_blocks." + std::to_string(i);
         auto D = [&](const std::string& key) -> const std::vector<float>& { return h->tensors[p + key].data; };
         auto fold = [&](const std::string& bn, std::vector<double>& al, std::vector<double>& be) {
             const auto &w = D(bn + ".weight"), &b = D(bn + ".bias"), &mu = D(bn + ".running_mean"), &var = D(bn + ".running_var");
@@ -841,6 +850,40 @@ void fold_quartznet(nww_handle* h) {
         h->tensors[p + ".qn.pw"] = tpw; h->tensors[p + ".qn.bias"] = tb; h->tensors[p + ".qn.dw_t"] = tdw; h->tensors[p + ".qn.amax"] = tam;
         if (proj) h->tensors[p + ".qn.res"] = tres;
         if (cat) h->tensors[p + ".qn.wcat"] = tcat;
+    }
+}
+
+// The raw-PCM frontend: each stage's BatchNorm folded into its conv ONCE in float64 (derived tensors "<conv>.raw.*"):
+//   w [k][Cin][Cout] = alpha weight, tap-major so that the lanes of conv1d_strided read consecutive floats; b [Cout] = beta (the convs
+//   have no bias of their own)
+void fold_raw_frontend(nww_handle* h) {
+    const nww_config& c = h->cfg;
+    for (int i = 0, Cin = 1; i < c.n_blocks; ++i) {
+        const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13;
+        const std::string conv = "model.frontend.conv_blocks." + std::to_string(3 * i), bn = "model.frontend.conv_blocks." + std::to_string(3 * i + 1);
+        const auto &w = h->tensors[conv + ".weight"].data, &g = h->tensors[bn + ".weight"].data, &b = h->tensors[bn + ".bias"].data,
+                   &mu = h->tensors[bn + ".running_mean"].data, &var = h->tensors[bn + ".running_var"].data;
+        HostTensor tw, tb;
+        tw.shape = {k, Cin, Cout}; tw.data.resize((size_t)k * Cin * Cout);
+        tb.shape = {Cout}; tb.data.resize(Cout);
+        for (int co = 0; co < Cout; ++co) {
+            const double al = (double)g[co] / std::sqrt((double)var[co] + 1e-5);
+            tb.data[co] = (float)((double)b[co] - (double)mu[co] * al);
+            for (int ci = 0; ci < Cin; ++ci)
+                for (int j = 0; j < k; ++j) tw.data[((size_t)j * Cin + ci) * Cout + co] = (float)(al * (double)w[((size_t)co * Cin + ci) * k + j]);
+        }
+        tw.loaded = tb.loaded = true;
+        h->tensors[conv + ".raw.w"] = tw; h->tensors[conv + ".raw.b"] = tb;
+        if (i > 0 && Cout % 32 == 0 && Cin % 16 == 0) {      // raw_x3's operand: the same folded weights as [Cout][k Cin], tap-major columns
+            HostTensor tk;
+            tk.shape = {Cout, k * Cin}; tk.data.resize((size_t)Cout * k * Cin);
+            for (int co = 0; co < Cout; ++co)
+                for (int j = 0; j < k; ++j)
+                    for (int ci = 0; ci < Cin; ++ci) tk.data[((size_t)co * k + j) * Cin + ci] = tw.data[((size_t)j * Cin + ci) * Cout + co];
+            tk.loaded = true;
+            h->tensors[conv + ".raw.wk"] = tk;
+        }
+        Cin = Cout;
     }
 }
 
@@ -1800,8 +1843,59 @@ int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.p
     return NWW_OK;
 }
 
+// E2ERawQuartzNet (architectures.py:798-817): the raw-PCM frontend's launches, which run where the other heads' STFT frontend runs
+// (nww_frontend_on_dev), so that nww_forward_features* is the backbone alone; the backbone and the tail are plan_quartznet's
+void plan_raw_frontend(PlanCtx& p) {
+    const nww_config& c = p.h->cfg;
+    for (int i = 0, Cin = 1; i < c.n_blocks; ++i) {
+        const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13, stride = i == 0 ? 16 : 4;
+        const std::string conv = "model.frontend.conv_blocks." + std::to_string(3 * i);
+        p.h->raw.push_back({"conv1d_strided:" + conv + " (k " + std::to_string(k) + " stride " + std::to_string(stride) + " " + std::to_string(Cin) + "->" +
+                                std::to_string(Cout) + ")+bn+relu [f32]",
+                            Cin, Cout, k, stride, p.W(conv + ".raw.w"), p.W(conv + ".raw.b")});
+        Cin = Cout;
+    }
+    // ---- the whole frontend in one launch (raw_x3.hip) under the default arithmetic at the shapes it takes.  |x| <= 1 bounds every
+    // stage through the folded weights' row 1-norms; the planes' powers of two come from those bounds, so nothing is clamped
+    nww_handle* h = p.h;
+    if (!(nww_knobs().raw_fused && h->f16 && h->conv_products == 6 && raw_x3_supported(c.layer_dim, c.n_blocks))) return;
+    RawX3Args a;
+    a.depth = c.n_blocks; a.C1 = c.layer_dim;
+    double bound = 1.0;
+    for (int i = 0, Cin = 1; i < c.n_blocks; ++i) {
+        const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13;
+        const std::string conv = "model.frontend.conv_blocks." + std::to_string(3 * i);
+        const HostTensor &w = h->tensors[conv + ".raw.w"], &b = h->tensors[conv + ".raw.b"];
+        if (i == 0) {
+            a.w1 = p.W(conv + ".raw.w"); a.b1 = p.W(conv + ".raw.b");
+        } else {
+            if (!p.W(conv + ".raw.wk")) return;
+            const float ws = f16_wscale(w.data), sc = f16_scale(bound);
+            void* packed = nullptr;
+            if (!(ws > 0.0f) || !(sc > 0.0f) || hipMalloc(&packed, (size_t)(Cout / 32) * (k * Cin / 16) * 2048) != hipSuccess) return;
+            h->packed_weights.push_back(packed);
+            if (launch_qn_x3_pack(p.W(conv + ".raw.wk"), packed, Cout, k * Cin, ws, h->own_stream) != hipSuccess) return;
+            a.packed[i - 1] = static_cast<const unsigned char*>(packed); a.bias[i - 1] = p.W(conv + ".raw.b");
+            a.scale[i - 1] = sc; a.un[i - 1] = 1.0f / (ws * sc);
+        }
+        double worst = 0.0;                                   // this stage's output bound
+        for (int co = 0; co < Cout; ++co) {
+            double t = 0.0;
+            for (int q = 0; q < k * Cin; ++q) t += std::fabs((double)w.data[(size_t)q * Cout + co]);
+            worst = std::fmax(worst, t * bound + std::fabs((double)b.data[co]));
+        }
+        bound = worst * (1.0 + 1e-6);
+        Cin = Cout;
+    }
+    h->raw_x3 = a;
+    h->raw_fused = true;
+    h->raw_fused_name = "raw_x3:model.frontend (" + std::to_string(c.n_blocks) + " stages 1->" + std::to_string(c.layer_dim << (c.n_blocks - 1)) +
+                        ", conv+bn+relu) [f16x3]";
+}
+
 int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architectures.py:370-437; time-major rows [T][C], as the head input is
     const nww_config& c = p.h->cfg;
+    const std::string qp = nww_quartznet_prefix(c);
     const int T = c.in_rows;
     const auto blocks = nww_quartznet_blocks(c);
     const int nblk = (int)blocks.size();
@@ -1814,7 +1908,7 @@ int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architect
     for (int i = 0; i < nblk; ++i) {
         const int Cin = blocks[i].cin, Cout = blocks[i].cout, k = blocks[i].k, Cp = qn_x3_cp(Cin);
         const bool proj = Cin != Cout, last = i == nblk - 1;
-        const std::string q = "model.quartznet_blocks." + std::to_string(i);
+        const std::string q = qp + "quartznet_blocks." + std::to_string(i);
         const int out = i % 2;
         const float *dwt = p.W(q + ".qn.dw_t"), *bias = p.W(q + ".qn.bias");
         // ---- the whole block in one clip-resident launch (qn_x3.hip) under the default arithmetic at the shapes it takes: two binary16 terms per
@@ -1860,7 +1954,7 @@ int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architect
         const int fin = in;
         p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[fin], r.buf[mbuf], r.B, T, C_last, r.stream); });
     }
-    set_tail(p, "fc", mbuf, C_last, p.W("model.fc.weight"), p.W("model.fc.bias"));
+    set_tail(p, "fc", mbuf, C_last, p.W(qp + "fc.weight"), p.W(qp + "fc.bias"));
     return NWW_OK;
 }
 
@@ -1908,7 +2002,8 @@ extern "C" int nww_finalize(nww_handle* h) {
         if (!h->tensors[k].loaded) return fail(h, NWW_ERR_MISSING, "Missing key(s) in state_dict: '%s'", k.c_str());
     fold_batchnorms(h);
     if (h->cfg.head_type == NWW_HEAD_BCRESNET) transpose_depthwise(h);
-    if (h->cfg.head_type == NWW_HEAD_QUARTZNET) fold_quartznet(h);
+    if (h->cfg.head_type == NWW_HEAD_QUARTZNET || h->cfg.head_type == NWW_HEAD_E2E_QUARTZNET) fold_quartznet(h);
+    if (nww_raw_head(h->cfg)) fold_raw_frontend(h);
     int rc = upload_weight_arena(h);
     if (rc == NWW_OK) rc = build_frontend_tables(h);
     if (rc != NWW_OK) return rc;
@@ -1925,6 +2020,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         case NWW_HEAD_TCN: rc = plan_tcn(p); break;
         case NWW_HEAD_E_BRANCHFORMER: rc = plan_e_branchformer(p); break;
         case NWW_HEAD_QUARTZNET: rc = plan_quartznet(p); break;
+        case NWW_HEAD_E2E_QUARTZNET: plan_raw_frontend(p); rc = plan_quartznet(p); break;
     }
     if (rc != NWW_OK) return rc;
     plan_tail(p);

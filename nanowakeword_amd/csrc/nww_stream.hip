@@ -56,6 +56,7 @@ extern "C" int nww_stream_close(nww_handle* h) {
 static int plan_incremental(nww_handle* h, int S, int W, int hop) {
     const int mode = nww_knobs().stream_inc;
     const nww_config& c = h->cfg;
+    if (nww_raw_head(c)) return NWW_OK;                        // the raw-PCM frontend re-scores the whole window every hop
     const int T = fe_num_frames(h->fe, W), hl = h->fe.hop;
     const bool frames_major = !c.mel_major_features || h->e2e_transposed;
     static const int mel_env = 2;
@@ -115,8 +116,8 @@ extern "C" int nww_stream_open(nww_handle* h, int32_t S, int32_t W, int32_t hop)
     if (W <= 0 || hop <= 0 || hop > W || (W % 8) || (hop % 8))
         return fail(h, NWW_ERR_INVALID, "window and hop must be positive multiples of 8 samples with hop <= window");
     const nww_config& c = h->cfg;
-    const int T = fe_num_frames(h->fe, W);
-    const int rows = c.mel_major_features ? c.n_mels : T, cols = c.mel_major_features ? T : c.n_mels;
+    const int T = nww_pcm_rows(h, W);
+    const int rows = c.mel_major_features ? c.n_mels : T, cols = nww_raw_head(c) ? c.in_cols : c.mel_major_features ? T : c.n_mels;
     if (T <= 0 || rows != c.in_rows || cols != c.in_cols)
         return fail(h, NWW_ERR_SHAPE, "a %d-sample window gives (%d,%d) features but the head expects (%d,%d)", W, rows, cols, c.in_rows, c.in_cols);
     nww_stream_close(h);

@@ -1,0 +1,175 @@
+// raw_x3.hip - the raw-PCM frontend in one launch.  A workgroup takes 32 rows of the LAST stage of one clip and recomputes the halo in
+// front of them: 137 rows of the stage before (4 . 31 + 13) and, at depth 3, 557 rows of stage 0.  The intermediate rows never leave
+// LDS: each is two binary16 planes (hi, lo of value x a plan-time power of two), time-major.
+//   stage 0 (1 -> C1, k 41, stride 16): float32 fmaf on the VALU straight from the int16 samples in LDS, in conv1d_strided's order - a
+//     thread keeps its channel's 41 taps (x 2^-15, exact) in registers and the lanes of a row read the same words (broadcast);
+//   later stages (k 13, stride 4): implicit GEMMs, transposed as in qn_x3.hip: acc [32 outputs x 32 rows] += W[32 x 16] . X^T[16 x 32];
+//     a K-chunk of 16 is 16 channels of ONE tap, so lane (n, h)'s B fragment is 16 bytes of row 4 r + j - read straight out of the plane.
+//     Three v_mfma_f32_32x32x16_f16 per chunk (hi.hi, hi.lo, lo.hi), float32 accumulation, weight fragments packed at plan time.
+// Scaling clamps nothing: |x| <= 1 bounds every stage's output through the folded weights' row 1-norms (plan time), the bound's power of
+// two puts it in [2^14, 2^15).  No scale depends on the data, so a clip's rows do not depend on its batch or slot.
+// Plane rows are stored by residue: local row i at position (i & 3) Q + (i >> 2), Q = ceil(R / 4), so that the 32 rows 4 r + j a tap
+// reads are consecutive positions; with pitches of 12, 20 and 36 dwords sixteen consecutive positions start at sixteen different
+// multiples of 4 banks.  Rows outside the clip are the next stage's zero padding and are stored as zeros.
+#include <stdint.h>
+#include "layers.h"
+#include "split_h2.h"
+#include "raw_x3.h"
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+namespace {
+
+constexpr int RX_THREADS = 512;
+constexpr int RX_ROWS = 32;                // rows of the last stage per workgroup
+constexpr int RX_R1 = 4 * (RX_ROWS - 1) + 13;      // 137
+constexpr int RX_R0 = 4 * (RX_R1 - 1) + 13;        // 557
+
+__host__ __device__ constexpr int rx_plane_rows(int R) { return 4 * ((R + 3) / 4); }
+__host__ __device__ constexpr int rx_pcm_halves(int R) { return ((R - 1) * 16 + 41 + 1 + 7) & ~7; }
+
+__device__ __forceinline__ int rx_pos(int i, int Q) { return (i & 3) * Q + (i >> 2); }
+
+__device__ __forceinline__ void rx_mfma3h(uint4 wh, uint4 wl, uint4 xh, uint4 xl, f32x16& acc) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wl), __builtin_bit_cast(f16x8, xh), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, xl), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, xh), acc, 0, 0, 0);
+}
+
+// One strided stage on the matrix pipe.  Reads plane (PH, PL) [Rin rows][pitch halves] of Cin channels; yields Rout local rows (local
+// row r is row gout0 + r of the clip's Lst rows at this stage) of Cout channels: into the plane (OH, OL) times oscale, or to y.
+__device__ __forceinline__ void rx_stage(const _Float16* PH, const _Float16* PL, int pitch, int Rin, int Cin, int Cout, const unsigned char* packed,
+                                         const float* __restrict__ bias, float un, int Rout, int gout0, int Lst, _Float16* OH, _Float16* OL, int opitch,
+                                         float oscale, float* __restrict__ y, int ct_out, int wave, int lane) {
+    const int n = lane & 31, h = lane >> 5;
+    const int ncb = Cout / 32, nrt = (Rout + 31) / 32, Qin = (Rin + 3) >> 2, Qout = (Rout + 3) >> 2, cpj = Cin / 16, K16 = 13 * cpj;
+    for (int item = wave; item < ncb * nrt; item += RX_THREADS / 64) {
+        const int cb = item % ncb, rt = item / ncb, r = 32 * rt + n;
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+        const unsigned char* wp = packed + (size_t)cb * K16 * 2048 + (size_t)lane * 16;
+        for (int j = 0; j < 13; ++j) {
+            const int i = min(4 * r + j, Rin - 1);             // rows past the tile's last feed only rows that are not kept
+            const int base = rx_pos(i, Qin) * pitch + 8 * h;
+            for (int cc = 0; cc < cpj; ++cc) {
+                const unsigned char* w = wp + (size_t)(j * cpj + cc) * 2048;
+                rx_mfma3h(*reinterpret_cast<const uint4*>(w), *reinterpret_cast<const uint4*>(w + 1024),
+                          *reinterpret_cast<const uint4*>(PH + base + 16 * cc), *reinterpret_cast<const uint4*>(PL + base + 16 * cc), acc);
+            }
+        }
+        const int tg = gout0 + r;
+        const bool live = r < Rout && tg >= 0 && tg < Lst;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int co = 32 * cb + 8 * g + 4 * h;
+            const float4 b4 = *reinterpret_cast<const float4*>(bias + co);
+            float v[4] = {fmaf(acc[4 * g], un, b4.x), fmaf(acc[4 * g + 1], un, b4.y), fmaf(acc[4 * g + 2], un, b4.z), fmaf(acc[4 * g + 3], un, b4.w)};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = live ? fmaxf(v[e], 0.0f) : 0.0f;
+            if (OH) {
+                if (r < Rout) {
+                    uint32_t h0, l0, h1, l1;
+                    nww_split2h(v[0] * oscale, v[1] * oscale, h0, l0);
+                    nww_split2h(v[2] * oscale, v[3] * oscale, h1, l1);
+                    const int off = rx_pos(r, Qout) * opitch + co;
+                    *reinterpret_cast<uint2*>(OH + off) = make_uint2(h0, h1);
+                    *reinterpret_cast<uint2*>(OL + off) = make_uint2(l0, l1);
+                }
+            } else if (live) {
+                if (ct_out) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[(size_t)(co + e) * Lst + tg] = v[e];
+                } else {
+                    *reinterpret_cast<float4*>(y + (size_t)tg * Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
+                }
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RX_THREADS) raw_x3_kernel(RawX3Args a, int tiles) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rx_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * RX_ROWS;
+    const int C1 = a.C1, depth = a.depth;
+    const int R0 = depth == 3 ? RX_R0 : RX_R1;                 // stage-0 rows this tile needs
+    const int p0pitch = C1 + 8, p1pitch = 2 * C1 + 8;
+    int16_t* PC = reinterpret_cast<int16_t*>(rx_lds);
+    _Float16* P0H = reinterpret_cast<_Float16*>(PC + rx_pcm_halves(R0));
+    _Float16* P0L = P0H + rx_plane_rows(R0) * p0pitch;
+    _Float16* P1H = P0L + rx_plane_rows(R0) * p0pitch;        // depth 3 only
+    _Float16* P1L = P1H + rx_plane_rows(RX_R1) * p1pitch;
+    // global row of local row 0 at each level, from the last stage down; then the first sample
+    const int gl = t0, gm = 4 * gl - 6, g0 = depth == 3 ? 4 * gm - 6 : gm, s0 = 16 * g0 - 20;
+    const int nsamp = (R0 - 1) * 16 + 41 + 1;
+    const int16_t* pb = a.pcm + (size_t)b * a.pcm_stride;
+    for (int i = tid; i < nsamp; i += RX_THREADS) {
+        const int gi = s0 + i;
+        PC[i] = gi >= 0 && gi < a.N ? pb[gi] : (int16_t)0;
+    }
+    __syncthreads();
+
+    // ---- stage 0 on the VALU: thread = (channel, row lane); the channel's taps stay in registers
+    {
+        const int co = tid % C1, rl = tid / C1, rstep = RX_THREADS / C1, Q0 = (R0 + 3) >> 2;
+        float w[41];
+#pragma unroll
+        for (int j = 0; j < 41; ++j) w[j] = a.w1[j * C1 + co] * (1.0f / 32768.0f);
+        const float b0 = a.b1[co], sc = a.scale[0];
+        for (int r = rl; r < R0; r += rstep) {
+            const uint32_t* sp = reinterpret_cast<const uint32_t*>(PC + 16 * r);
+            float acc = b0;
+#pragma unroll
+            for (int q = 0; q < 21; ++q) {
+                const uint32_t u = sp[q];
+                acc = fmaf((float)(int16_t)(u & 0xffffu), w[2 * q], acc);
+                if (2 * q + 1 < 41) acc = fmaf((float)((int32_t)u >> 16), w[2 * q + 1], acc);
+            }
+            const int tg = g0 + r;
+            const float v = tg >= 0 && tg < a.L[0] ? fmaxf(acc, 0.0f) * sc : 0.0f;
+            uint32_t hi, lo;
+            nww_split2h(v, 0.0f, hi, lo);
+            const int off = rx_pos(r, Q0) * p0pitch + co;
+            reinterpret_cast<uint16_t*>(P0H)[off] = (uint16_t)(hi & 0xffffu);
+            reinterpret_cast<uint16_t*>(P0L)[off] = (uint16_t)(lo & 0xffffu);
+        }
+    }
+    __syncthreads();
+
+    float* yb = a.y + (size_t)b * a.L[depth - 1] * (C1 << (depth - 1));
+    if (depth == 3) {
+        rx_stage(P0H, P0L, p0pitch, RX_R0, C1, 2 * C1, a.packed[0], a.bias[0], a.un[0], RX_R1, gm, a.L[1], P1H, P1L, p1pitch, a.scale[1], nullptr, 0, wave, lane);
+        __syncthreads();
+        rx_stage(P1H, P1L, p1pitch, RX_R1, 2 * C1, 4 * C1, a.packed[1], a.bias[1], a.un[1], RX_ROWS, gl, a.L[2], nullptr, nullptr, 0, 0.0f, yb, a.ct_out, wave, lane);
+    } else {
+        rx_stage(P0H, P0L, p0pitch, RX_R1, C1, 2 * C1, a.packed[0], a.bias[0], a.un[0], RX_ROWS, gl, a.L[1], nullptr, nullptr, 0, 0.0f, yb, a.ct_out, wave, lane);
+    }
+}
+
+}  // namespace
+
+bool raw_x3_supported(int channels, int depth) { return (channels == 16 || channels == 32) && (depth == 2 || depth == 3); }
+
+size_t raw_x3_lds_bytes(int channels, int depth) {
+    const int R0 = depth == 3 ? RX_R0 : RX_R1;
+    size_t bytes = (size_t)rx_pcm_halves(R0) * 2 + (size_t)2 * rx_plane_rows(R0) * (channels + 8) * 2;
+    if (depth == 3) bytes += (size_t)2 * rx_plane_rows(RX_R1) * (2 * channels + 8) * 2;
+    return bytes;
+}
+
+hipError_t launch_raw_x3(const RawX3Args& a, hipStream_t s) {
+    if (a.B <= 0) return hipSuccess;
+    if (!raw_x3_supported(a.C1, a.depth) || a.N < 1 || a.pcm_stride < (size_t)a.N || !a.pcm || !a.y || !a.w1 || !a.b1 || !a.packed[0] || !a.bias[0] ||
+        (a.depth == 3 && (!a.packed[1] || !a.bias[1])) || a.L[a.depth - 1] < 1)
+        return hipErrorInvalidValue;
+    const size_t lds = raw_x3_lds_bytes(a.C1, a.depth);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(&raw_x3_kernel), lds);
+    if (e != hipSuccess) return e;
+    const int tiles = (a.L[a.depth - 1] + RX_ROWS - 1) / RX_ROWS;
+    if ((size_t)tiles * a.B > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(raw_x3_kernel, dim3((unsigned)((size_t)tiles * a.B)), dim3(RX_THREADS), lds, s, a, tiles);
+    return hipGetLastError();
+}

@@ -165,13 +165,19 @@ class HipModel:
         return np.ascontiguousarray(pcm)
 
     def frontend(self, pcm, return_power: bool = False):
-        """int16 [B,N] -> log-mel dB float32 [B, n_mels, frames] (+ mel power)."""
+        """int16 [B,N] -> log-mel dB float32 [B, n_mels, frames] (+ mel power); for model_type="e2e_quartznet" the learned raw-PCM
+        frontend's output [B, channels, rows] (no mel power there)."""
         pcm = self._pcm(pcm)
         B, N = pcm.shape
         T = self.num_frames(N)
+        raw = self.head.model_type == "e2e_quartznet"
+        if T <= 0 and raw:
+            raise ValueError(f"a clip needs at least one sample (got {N})")
         if T <= 0:
             raise ValueError(f"Input clip of {N} samples is too short (n_fft={self.fe.n_fft}, center={self.fe.center})")
-        out = np.empty((B, self.fe.n_mels, T), np.float32)
+        if raw and return_power:
+            raise ValueError("the raw-PCM frontend has no mel power")
+        out = np.empty((B, self.head.input_shape[1] if raw else self.fe.n_mels, T), np.float32)
         pw = np.empty_like(out) if return_power else None
         fr = C.c_int32()
         self._check(self.lib.nww_frontend_ex(self._h, pcm.ctypes.data_as(C.c_void_p), B, N, out.ctypes.data_as(C.c_void_p),
@@ -393,6 +399,10 @@ class HipModel:
     def get_profile(self):
         """[(launch name, total ms, launches)] accumulated since set_profiling(True); HIP events on the launch stream."""
         names = self.describe_plan().strip().split("\n")
+        # interval 0 is the whole frontend: the raw-PCM heads list one line per frontend launch, which share it
+        n_fe = sum(l.startswith("frontend:") for l in names)
+        if n_fe > 1:
+            names = [" + ".join(names[:n_fe])] + names[n_fe:]
         n = C.c_int32(len(names) + 8)
         ms = (C.c_float * n.value)()
         cnt = (C.c_int32 * n.value)()
@@ -434,7 +444,10 @@ class HipSession:
         self.accepts_int16 = True       # HipInterpreter then skips the float32 round trip of nanointerpreter.py:750
         if mode == "e2e":
             T = model.num_frames(self.clip_samples)
-            rows, cols = (model.fe.n_mels, T) if model.head.model_type == "e2e_dnn" else (T, model.fe.n_mels)
+            if model.head.model_type == "e2e_quartznet":      # learned filters on raw PCM: num_frames is the raw frontend's frame law
+                rows, cols = T, model.head.input_shape[1]
+            else:
+                rows, cols = (model.fe.n_mels, T) if model.head.model_type == "e2e_dnn" else (T, model.fe.n_mels)
             if (rows, cols) != tuple(model.head.input_shape):
                 raise ValueError(f"clip_samples={clip_samples} gives ({rows},{cols}) features, head expects {model.head.input_shape}")
 

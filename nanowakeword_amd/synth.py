@@ -94,11 +94,14 @@ _FIRST_LAYER_KEYS = {
     "model.conv_block.0.weight", "model.tcn_blocks.0.conv1.weight", "model.tcn_blocks.0.downsample.weight",
     "model.quartznet_blocks.0.depthwise_conv.weight", "model.quartznet_blocks.0.residual_connector.0.weight",
 }
+# model.frontend.conv_blocks.0.weight, the raw-PCM heads' first layer, is deliberately absent: it sees PCM / 32768 in [-1, 1], not dB-scale
+# features, so it keeps the plain variance-preserving gain and the stages behind it see O(1) activations
 
 
 def _is_seq_bn(key: str) -> bool:
     """BatchNorm layers that sit in nn.Sequential containers have numeric names
-    (model.cnn.1, model.conv_block.5, model.init_conv.1, model.blockN.shortcut.1, model.quartznet_blocks.N.residual_connector.1)."""
+    (model.cnn.1, model.conv_block.5, model.init_conv.1, model.blockN.shortcut.1, model.quartznet_blocks.N.residual_connector.1,
+    model.frontend.conv_blocks.4: RawAudioFrontend's stages are Conv1d, BatchNorm1d, ReLU)."""
     parts = key.split(".")
     if len(parts) < 3:
         return False
@@ -110,6 +113,8 @@ def _is_seq_bn(key: str) -> bool:
         return n % 4 == 1
     if cont in ("init_conv", "shortcut", "residual_connector"):
         return n == 1
+    if cont == "conv_blocks":
+        return n % 3 == 1
     return False
 
 

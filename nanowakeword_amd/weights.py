@@ -20,7 +20,7 @@ from typing import Mapping, Optional, Tuple
 
 import numpy as np
 
-from .config import FrontendConfig, HeadConfig, param_spec
+from .config import FrontendConfig, HeadConfig, param_spec, raw_frontend_frames
 
 
 def state_dict_from_pt(path: str) -> dict:
@@ -113,27 +113,28 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         if input_shape[1] != F:
             raise ValueError(f"input_shape F={input_shape[1]} but the TCN expects {F} features")
         cfg = HeadConfig("tcn", input_shape, tcn_channels=chans, tcn_kernel_size=k, **kw)
+    elif "model.frontend.conv_blocks.0.weight" in keys and any(k.startswith("model.backbone.quartznet_blocks.") for k in keys):
+        if input_shape is None:
+            raise ValueError("e2e_quartznet: the clip length is not in the weights; pass input_shape=(rows, channels) as the backbone sees it")
+        depth = n_indexed(r"model\.frontend\.conv_blocks\.(\d+)\.running_var") // 3 + 1
+        ch = shp("model.frontend.conv_blocks.0.weight")[0]
+        F = ch * 2 ** (depth - 1)
+        if input_shape[1] != F:
+            raise ValueError(f"input_shape F={input_shape[1]} but the raw frontend gives {F} channels")
+        cfg = HeadConfig("e2e_quartznet", input_shape, e2e_frontend_channels=ch, e2e_frontend_depth=depth,
+                         e2e_quartznet_config=_quartznet_entries(shp, n_indexed, "model.backbone."), **kw)
     elif any(k.startswith("model.quartznet_blocks.") for k in keys):
         if input_shape is None:
             raise ValueError("quartznet: the sequence length is not in the weights; pass input_shape=(T, F)")
-        nblk = n_indexed(r"model\.quartznet_blocks\.(\d+)\.pointwise_conv\.weight")
         F = shp("model.quartznet_blocks.0.pointwise_conv.weight")[1]
         if input_shape[1] != F:
             raise ValueError(f"input_shape F={input_shape[1]} but the QuartzNet expects {F} features")
-        # consecutive blocks of equal (channels, kernel) are one [channels, kernel, repetitions] entry again
-        qc = []
-        for i in range(nblk):
-            co = shp(f"model.quartznet_blocks.{i}.pointwise_conv.weight")[0]
-            k = shp(f"model.quartznet_blocks.{i}.depthwise_conv.weight")[2]
-            if qc and qc[-1][:2] == [co, k]:
-                qc[-1][2] += 1
-            else:
-                qc.append([co, k, 1])
+        qc = _quartznet_entries(shp, n_indexed, "model.")
         cfg = HeadConfig("quartznet", input_shape, quartznet_config=qc, **kw)
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn/e2e_quartznet)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:
@@ -141,6 +142,20 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         if shp(k) != s:
             raise ValueError(f"size mismatch for {k}: checkpoint {shp(k)} vs model {s} (wrong input_shape?)")
     return cfg
+
+
+def _quartznet_entries(shp, n_indexed, prefix):
+    """[channels, kernel, repetitions] entries from the block shapes under ``prefix``: consecutive blocks of equal (channels, kernel) are
+    one entry again."""
+    qc = []
+    for i in range(n_indexed(re.escape(prefix) + r"quartznet_blocks\.(\d+)\.pointwise_conv\.weight")):
+        co = shp(f"{prefix}quartznet_blocks.{i}.pointwise_conv.weight")[0]
+        k = shp(f"{prefix}quartznet_blocks.{i}.depthwise_conv.weight")[2]
+        if qc and qc[-1][:2] == [co, k]:
+            qc[-1][2] += 1
+        else:
+            qc.append([co, k, 1])
+    return qc
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -254,8 +269,49 @@ def state_dict_from_onnx(path_or_bytes):
             W, R, B = (np.asarray(g.initializers[t]) for t in n.inputs[1:4])
             _unpack_onnx_lstm(sd, prefix, l, W, R, B, H)
 
+    def quartznet_blocks(prefix):
+        # the depthwise conv keeps its name, the pointwise conv and the projection are folded with their BatchNorms
+        i = 0
+        while f"{_WRAP}{prefix}quartznet_blocks.{i}.depthwise_conv.weight" in g.initializers:
+            p = f"{prefix}quartznet_blocks.{i}"
+            dw = next(n for n in g.nodes if n.op_type == "Conv" and n.inputs[1] == f"{_WRAP}{p}.depthwise_conv.weight")
+            pw = [n for n in convs if n.inputs[0] == dw.outputs[0]]
+            sc = [n for n in convs if n.inputs[0] == dw.inputs[0]]
+            if len(pw) != 1 or len(sc) > 1:
+                raise ValueError(f"quartznet block {i}: unexpected graph structure")
+            W = np.asarray(g.initializers[pw[0].inputs[1]], np.float32)
+            folded(pw[0], f"{p}.pointwise_conv.weight", f"{p}.pointwise_conv.bias", f"{p}.batch_norm")
+            if sc:
+                folded(sc[0], f"{p}.residual_connector.0.weight", f"{p}.residual_connector.0.bias", f"{p}.residual_connector.1")
+            elif W.shape[0] != W.shape[1]:
+                raise ValueError(f"quartznet block {i}: widths differ but no projection was found")
+            i += 1
+
     mode, clip_samples, fe = "features", 16000, None
-    if "model.mel_spec.real_basis" in named:                                        # E2E_MelSpectrogram_CNN
+    if any(k.startswith("model.backbone.quartznet_blocks.") for k in named):        # E2ERawQuartzNet: learned filters on raw PCM, no STFT
+        mode = "e2e"
+        if len(in_shape) not in (2, 3):
+            raise ValueError(f"e2e_quartznet model with input shape {in_shape}: expected [batch, 1, samples]")
+        clip_samples = int(in_shape[-1])
+        # RawAudioFrontend: the chain of strided convs from the graph input, each folded with its BatchNorm (the convs have no bias of
+        # their own, so the folded bias is the BatchNorm's beta)
+        t, stage, cfg_probe = g.inputs[0][0], 0, None
+        while True:
+            nxt = [n for n in convs if n.inputs[0] == t and int(n.attrs.get("strides", [1])[0]) > 1]
+            if len(nxt) != 1:
+                break
+            folded(nxt[0], f"model.frontend.conv_blocks.{3*stage}.weight", None, f"model.frontend.conv_blocks.{3*stage+1}")
+            relu = [n for n in _consumers(g, nxt[0].outputs[0]) if n.op_type == "Relu"]
+            if len(relu) != 1:
+                raise ValueError(f"e2e_quartznet frontend stage {stage}: expected Conv -> Relu")
+            t, stage = relu[0].outputs[0], stage + 1
+        if stage == 0:
+            raise ValueError("e2e_quartznet: no strided frontend conv reads the graph input")
+        quartznet_blocks("model.backbone.")
+        width = sd[f"model.frontend.conv_blocks.{3*(stage-1)}.weight"].shape[0]
+        cfg_probe = HeadConfig("e2e_quartznet", (1, width), e2e_frontend_channels=int(sd["model.frontend.conv_blocks.0.weight"].shape[0]), e2e_frontend_depth=stage)
+        input_shape = (raw_frontend_frames(cfg_probe, clip_samples), width)
+    elif "model.mel_spec.real_basis" in named:                                        # E2E_MelSpectrogram_CNN
         mode = "e2e"
         clip_samples = int(in_shape[-1])
         rb, fb = named["model.mel_spec.real_basis"], named["model.mel_spec.mel_fb"]
@@ -289,22 +345,8 @@ def state_dict_from_onnx(path_or_bytes):
             for i, n in enumerate(convs):
                 p = f"model.branchformer_blocks.{i}.conv_branch"
                 folded(n, f"{p}.depthwise_conv.weight", f"{p}.depthwise_conv.bias", f"{p}.batch_norm")
-        elif any(k.startswith("model.quartznet_blocks.") for k in named):           # QuartzNet: the depthwise conv keeps its name, the
-            i = 0                                                                   # pointwise and the projection are folded with their BatchNorms
-            while f"{_WRAP}model.quartznet_blocks.{i}.depthwise_conv.weight" in g.initializers:
-                p = f"model.quartznet_blocks.{i}"
-                dw = next(n for n in g.nodes if n.op_type == "Conv" and n.inputs[1] == f"{_WRAP}{p}.depthwise_conv.weight")
-                pw = [n for n in convs if n.inputs[0] == dw.outputs[0]]
-                sc = [n for n in convs if n.inputs[0] == dw.inputs[0]]
-                if len(pw) != 1 or len(sc) > 1:
-                    raise ValueError(f"quartznet block {i}: unexpected graph structure")
-                W = np.asarray(g.initializers[pw[0].inputs[1]], np.float32)
-                folded(pw[0], f"{p}.pointwise_conv.weight", f"{p}.pointwise_conv.bias", f"{p}.batch_norm")
-                if sc:
-                    folded(sc[0], f"{p}.residual_connector.0.weight", f"{p}.residual_connector.0.bias", f"{p}.residual_connector.1")
-                elif W.shape[0] != W.shape[1]:
-                    raise ValueError(f"quartznet block {i}: widths differ but no projection was found")
-                i += 1
+        elif any(k.startswith("model.quartznet_blocks.") for k in named):           # QuartzNet
+            quartznet_blocks("model.")
         elif (grus or lstms) and convs:                                             # CRNN (GRU or LSTM backend)
             for i, n in enumerate(convs):
                 folded(n, f"model.cnn.{4*i}.weight", f"model.cnn.{4*i}.bias", f"model.cnn.{4*i+1}")
@@ -406,7 +448,7 @@ def load_session(path: str, device: int = 0):
         head, fe, sd, extras, meta = load_bundle(path)
     # feature-mode heads never run the frontend and e2e exports carry their own tables (model.mel_spec.*): neither
     # needs torch to rebuild torchaudio's float32 tables
-    feature_mode = meta.get("mode", "e2e") == "features"
+    feature_mode = meta.get("mode", "e2e") == "features" or head.model_type == "e2e_quartznet"       # (learned filters: no mel tables at all)
     own_tables = "frontend.window" in extras or any(k.startswith("model.mel_spec.") for k in sd)
     model = HipModel(head, fe, device=device, state_dict=sd, window=extras.get("frontend.window"),
                      mel_fb=extras.get("frontend.mel_fb"), tables="builtin" if (feature_mode or own_tables) else "torchaudio")

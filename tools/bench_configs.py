@@ -13,6 +13,77 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def raw_frontend_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps):
+    """The raw-PCM head's extra legs: the learned frontend alone (nww_frontend_dev), an outside yardstick that is not code under test - the
+    same folded three-stage chain as torch.nn.functional.conv1d + ReLU in float32 on the same device tensors (MIOpen) - both alternating
+    three times in this session, the ratio to the frontend's HBM and float32-FMA bounds, and the oracle leg on the tests' restatement."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import raw_oracle
+    from nanowakeword_amd.config import raw_frontend_macs, raw_frontend_stages
+    B, N = pcm_h.shape
+    T, C = cfg.input_shape
+    fe_out = torch.empty((B, T, C), dtype=torch.float32, device=pcm.device)
+    ws, bs = [], []
+    strides = [s for _, _, _, s in raw_frontend_stages(cfg)]
+    for i in range(len(strides)):
+        w, p = sd[f"model.frontend.conv_blocks.{3*i}.weight"].astype(np.float64), f"model.frontend.conv_blocks.{3*i+1}"
+        al = sd[p + ".weight"].astype(np.float64) / np.sqrt(sd[p + ".running_var"].astype(np.float64) + 1e-5)
+        ws.append(torch.from_numpy((w * al[:, None, None]).astype(np.float32)).to(pcm.device))
+        bs.append(torch.from_numpy((sd[p + ".bias"] - sd[p + ".running_mean"] * al).astype(np.float32)).to(pcm.device))
+    x = (pcm.to(torch.float32) / 32768.0).unsqueeze(1).contiguous()
+
+    def ours():
+        m.frontend_dev(pcm.data_ptr(), B, N, fe_out.data_ptr(), True, stream)
+
+    # the generic plan in the same session: the knob is read once per process, and another conv_arith takes the very launches
+    # NWW_RAW_FUSED=0 takes (one conv1d_strided per stage)
+    from nanowakeword_amd.session import HipModel
+    mg = HipModel(cfg, m.fe, device=0, state_dict=sd, conv_arith="f32")
+    mg.reserve(B, N)
+    ge_out = torch.empty_like(fe_out)
+
+    def generic():
+        mg.frontend_dev(pcm.data_ptr(), B, N, ge_out.data_ptr(), True, stream)
+
+    def chain():
+        h = x
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            h = torch.relu(torch.nn.functional.conv1d(h, w, b, stride=strides[i], padding=w.shape[2] // 2))
+        return h
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+    runs = [(round(timed(ours), 4), round(timed(chain), 4), round(timed(generic), 4)) for _ in range(3)]
+    ours_ms, chain_ms, generic_ms = (min(r[q] for r in runs) for q in range(3))
+    fused_vs_generic = float((ge_out - fe_out).abs().max())
+    generic_plan = [l for l in mg.describe_plan().split("\n") if l.startswith("frontend:")]
+    mg.close()
+    agree = float((chain().transpose(1, 2) - fe_out).abs().max())
+    macs = raw_frontend_macs(cfg, N)                           # rows from the frame law at this clip length
+    hbm_ms = B * (N * 2 + T * C * 4) / 8e12 * 1e3                # int16 PCM in, float32 rows out at 8 TB/s
+    fma_ms = 2 * macs * B / 157.3e12 * 1e3                      # float32 vector FMA peak of the card
+    ref = raw_oracle.forward(pcm_h[:8], sd, cfg)[2].ravel()
+    t0 = time.perf_counter(); k = 0
+    while time.perf_counter() - t0 < 3.0:
+        raw_oracle.forward(pcm_h[:32], sd, cfg); k += 32
+    return {"generic_frontend_plan": generic_plan, "generic_frontend_ms_alternating": [r[2] for r in runs], "generic_frontend_ms": generic_ms,
+            "frontend_over_generic": round(ours_ms / generic_ms, 3), "max_abs_frontend_vs_generic": fused_vs_generic,
+            "frontend_ms_alternating": [r[0] for r in runs], "torch_conv1d_chain_ms_alternating": [r[1] for r in runs],
+            "frontend_plan": [l for l in m.describe_plan().split("\n") if l.startswith("frontend:")], "frontend_mmac_per_clip": round(macs / 1e6, 2),
+            "frontend_ms": ours_ms, "torch_conv1d_chain_ms": chain_ms, "frontend_over_torch_chain": round(ours_ms / chain_ms, 3),
+            "max_abs_frontend_vs_torch_chain": agree, "frontend_hbm_bound_ms": round(hbm_ms, 4), "frontend_f32_fma_bound_ms": round(fma_ms, 4),
+            "frontend_over_hbm_bound": round(ours_ms / hbm_ms, 1), "frontend_over_f32_fma_bound": round(ours_ms / fma_ms, 1),
+            "max_abs_dlogit_vs_oracle": float(np.abs(logits[:8].cpu().numpy() - ref).max()),
+            "cpu_oracle_clips_per_s": round(k / (time.perf_counter() - t0), 1)}
+
+
 def main():
     import torch
     import oracle
@@ -36,6 +107,7 @@ def main():
         ("tcn 64-mel B=4096", HeadConfig("tcn", (101, 64)), FrontendConfig(), 4096, 30),
         ("e_branchformer 64-mel B=2048", HeadConfig("e_branchformer", (101, 64)), FrontendConfig(), 2048, 10),
         ("quartznet 64-mel B=2048", HeadConfig("quartznet", (101, 64)), FrontendConfig(), 2048, 30),
+        ("e2e_quartznet 1 s B=2048", HeadConfig("e2e_quartznet", (63, 128)), FrontendConfig(), 2048, 30),
         # the reference's other activations (model.py:81-87) at speed: each within 1.15 x of its ReLU row
         ("C2-gelu cnn 64-mel B=4096 activation=gelu", HeadConfig("cnn", (101, 64), activation="gelu"), FrontendConfig(), 4096, 30),
         ("C2-silu cnn 64-mel B=4096 activation=silu", HeadConfig("cnn", (101, 64), activation="silu"), FrontendConfig(), 4096, 30),
@@ -85,6 +157,11 @@ def main():
             out.update({"clips_per_s": round(B * steps / dt, 1), "ms_per_step": round(dt / steps * 1e3, 4),
                         "head_tflops": round(2 * head_macs(cfg) * B * steps / dt / 1e12, 2),
                         "kernel_ms": {n: round(ms / max(c, 1), 4) for n, ms, c in prof if c > 0}})
+            if cfg.model_type == "e2e_quartznet":
+                out.update(raw_frontend_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps))
+                print(json.dumps(out), flush=True)
+                m.close()
+                continue
             n_chk = 8
             lm = oracle.frontend_logmel(pcm_h[:n_chk], window, fb, n_mels=fe.n_mels, center=fe.center)
             if cfg.model_type != "e2e_dnn":
