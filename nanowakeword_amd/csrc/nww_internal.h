@@ -1,6 +1,6 @@
 // nww_internal.h - what the translation units of the C-ABI share: the handle, a forward's run state, error helpers and the
-// device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_plan.hip: state_dict spec
-// and the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
+// device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_weights.hip: state_dict spec
+// and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
 // nww_emb.hip: embedding-mode state (nww_emb_*).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -180,7 +180,13 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
                            size_t row_stride = 0, unsigned int* done_flag = nullptr, unsigned int done_seq = 0, bool* done_armed = nullptr);
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
-void nww_build_spec(nww_handle* h);            // nww_plan.hip
+void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next six: what nww_finalize does to the loaded weights before it plans
+void fold_batchnorms(nww_handle* h);
+void transpose_depthwise(nww_handle* h);
+void fold_quartznet(nww_handle* h);
+void fold_raw_frontend(nww_handle* h);
+int upload_weight_arena(nww_handle* h);
+int build_frontend_tables(nww_handle* h);
 inline bool nww_raw_head(const nww_config& c) { return c.head_type == NWW_HEAD_E2E_QUARTZNET; }
 // rows the head's frontend yields for N samples: the STFT's frame count, or for the raw-PCM heads the strided convs' frame law
 // (stage 0 stride 16, every later stage 4; zero padding, so any N >= 1 has rows)

@@ -1,4 +1,4 @@
-// nww_plan.hip - Model.state_dict() spec per head and the launch plans nww_finalize builds from the loaded weights.
+// nww_plan.hip - the plan knobs and the launch plans nww_finalize builds from the loaded weights: plan helpers, one planner per head.
 #include "nww_internal.h"
 #include "bc_chain.h"
 
@@ -16,198 +16,11 @@ const Knobs& nww_knobs() {
     return k;
 }
 
-// ------------------------------------------------------------------------------------------ spec
-namespace {
-using Shape = std::vector<int64_t>;
-struct SpecBuilder {
-    std::vector<std::string>& keys;
-    std::map<std::string, HostTensor>& t;
-    void add(const std::string& k, Shape s) { keys.push_back(k); t[k].shape = std::move(s); }
-    void lin(const std::string& p, int out, int in) { add(p + ".weight", {out, in}); add(p + ".bias", {out}); }
-    void ln(const std::string& p, int d) { add(p + ".weight", {d}); add(p + ".bias", {d}); }
-    void bn(const std::string& p, int c) {
-        add(p + ".weight", {c}); add(p + ".bias", {c}); add(p + ".running_mean", {c}); add(p + ".running_var", {c});
-    }
-    void gru(const std::string& p, int in, int H, int layers, int G = 3) {   // G = 3: nn.GRU, 4: nn.LSTM
-        for (int l = 0; l < layers; ++l) {
-            const int isz = l == 0 ? in : 2 * H;
-            for (const char* sfx : {"", "_reverse"}) {
-                const std::string s = "_l" + std::to_string(l) + sfx;
-                add(p + ".weight_ih" + s, {G * H, isz}); add(p + ".weight_hh" + s, {G * H, H});
-                add(p + ".bias_ih" + s, {G * H}); add(p + ".bias_hh" + s, {G * H});
-            }
-        }
-    }
-};
-
-void crnn_out(const nww_config& c, int* C, int* H, int* W) {
-    int h = c.in_rows, w = c.in_cols;
-    for (int i = 0; i < c.n_crnn_channels; ++i) { h /= 2; w /= 2; }
-    *C = c.crnn_channels[c.n_crnn_channels - 1]; *H = h; *W = w;
-}
-
-// Mirrors nanowakeword_amd/config.py:param_spec == Model.state_dict() of the reference (model.py:67-296).
-}  // namespace
-
-void nww_build_spec(nww_handle* h) {
-    const nww_config& c = h->cfg;
-    SpecBuilder s{h->keys, h->tensors};
-    const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, E = c.embedding_dim, nb = c.n_blocks;
-    switch (c.head_type) {
-        case NWW_HEAD_DNN:
-            s.lin("model.layer1", L, T * F); s.ln("model.layernorm1", L);
-            for (int i = 0; i < nb; ++i) {
-                const std::string p = "model.blocks." + std::to_string(i);
-                s.lin(p + ".fcn_layer", L, L); s.ln(p + ".layer_norm", L);
-            }
-            s.lin("model.last_layer", E, L);
-            break;
-        case NWW_HEAD_CNN:
-            s.add("model.conv1.weight", {16, 1, 3, 3}); s.add("model.conv1.bias", {16});
-            s.add("model.conv2.weight", {32, 16, 3, 3}); s.add("model.conv2.bias", {32});
-            s.lin("model.fc1", 128, 32 * (T / 4) * (F / 4)); s.lin("model.fc2", E, 128);
-            break;
-        case NWW_HEAD_CRNN: {
-            int cin = 1;
-            for (int i = 0; i < c.n_crnn_channels; ++i) {
-                const int co = c.crnn_channels[i];
-                const std::string p = "model.cnn." + std::to_string(4 * i);
-                s.add(p + ".weight", {co, cin, 3, 3}); s.add(p + ".bias", {co});
-                s.bn("model.cnn." + std::to_string(4 * i + 1), co);
-                cin = co;
-            }
-            int C, H, W; crnn_out(c, &C, &H, &W);
-            s.gru("model.rnn", C * H, L, nb, c.crnn_rnn_lstm ? 4 : 3); s.lin("model.fc", E, 2 * L);
-            break;
-        }
-        case NWW_HEAD_GRU:
-            s.gru("model.gru", F, L, nb); s.lin("model.fc", E, 2 * L);
-            break;
-        case NWW_HEAD_BCRESNET: {
-            s.add("model.init_conv.0.weight", {32, 1, 3, 3}); s.bn("model.init_conv.1", 32);
-            const int ch[4] = {32, 64, 128, 256};
-            for (int i = 1; i <= 3; ++i) {
-                const std::string p = "model.block" + std::to_string(i);
-                s.add(p + ".depthwise.weight", {ch[i - 1], 1, 3, 3});
-                s.add(p + ".pointwise.weight", {ch[i], ch[i - 1], 1, 1}); s.bn(p + ".bn1", ch[i]);
-                s.add(p + ".shortcut.0.weight", {ch[i], ch[i - 1], 1, 1}); s.bn(p + ".shortcut.1", ch[i]);
-            }
-            s.lin("model.fc", E, 256);
-            break;
-        }
-        case NWW_HEAD_CONFORMER: {
-            const int D = c.conformer_d_model;
-            s.lin("model.input_proj", D, F);
-            for (int i = 0; i < nb; ++i) {
-                const std::string p = "model.conformer_blocks." + std::to_string(i);
-                for (const char* ff : {".ff1", ".ff2"}) {
-                    s.ln(p + ff + ".layer_norm", D); s.lin(p + ff + ".linear1", 4 * D, D); s.lin(p + ff + ".linear2", D, 4 * D);
-                }
-                s.add(p + ".attention.in_proj_weight", {3 * D, D}); s.add(p + ".attention.in_proj_bias", {3 * D});
-                s.lin(p + ".attention.out_proj", D, D);
-                s.ln(p + ".conv_module.layer_norm", D);
-                s.add(p + ".conv_module.conv1.weight", {2 * D, D, 1}); s.add(p + ".conv_module.conv1.bias", {2 * D});
-                s.add(p + ".conv_module.depthwise_conv.weight", {D, 1, 31}); s.add(p + ".conv_module.depthwise_conv.bias", {D});
-                s.bn(p + ".conv_module.batch_norm", D);
-                s.add(p + ".conv_module.conv2.weight", {D, D, 1}); s.add(p + ".conv_module.conv2.bias", {D});
-                s.ln(p + ".layer_norm", D);
-            }
-            s.lin("model.output_proj", E, D);
-            break;
-        }
-        case NWW_HEAD_TRANSFORMER: {              // TransformerModel (architectures.py:164-206); d_model / n_head in the conformer_* slots
-            const int D = c.conformer_d_model;
-            s.lin("model.input_proj", D, F);
-            s.add("model.pos_encoder.pe", {NWW_PE_MAX_LEN, 1, D});
-            for (int i = 0; i < nb; ++i) {
-                const std::string p = "model.transformer_encoder.layers." + std::to_string(i);
-                s.add(p + ".self_attn.in_proj_weight", {3 * D, D}); s.add(p + ".self_attn.in_proj_bias", {3 * D});
-                s.lin(p + ".self_attn.out_proj", D, D);
-                s.lin(p + ".linear1", 4 * D, D); s.lin(p + ".linear2", D, 4 * D);
-                s.ln(p + ".norm1", D); s.ln(p + ".norm2", D);
-            }
-            s.lin("model.output_proj", E, D);
-            break;
-        }
-        case NWW_HEAD_E_BRANCHFORMER: {           // EBranchformerModel (architectures.py:546-616); d_model / n_head in the conformer_* slots
-            const int D = c.conformer_d_model;
-            s.lin("model.input_proj", D, F);
-            for (int i = 0; i < nb; ++i) {
-                const std::string p = "model.branchformer_blocks." + std::to_string(i);
-                s.ln(p + ".attn_branch_norm", D);
-                s.add(p + ".attention.in_proj_weight", {3 * D, D}); s.add(p + ".attention.in_proj_bias", {3 * D});
-                s.lin(p + ".attention.out_proj", D, D);
-                s.ln(p + ".conv_branch.layer_norm", D);
-                s.add(p + ".conv_branch.conv1.weight", {2 * D, D, 1}); s.add(p + ".conv_branch.conv1.bias", {2 * D});
-                s.add(p + ".conv_branch.depthwise_conv.weight", {D, 1, 31}); s.add(p + ".conv_branch.depthwise_conv.bias", {D});
-                s.bn(p + ".conv_branch.batch_norm", D);
-                s.add(p + ".conv_branch.conv2.weight", {D, D, 1}); s.add(p + ".conv_branch.conv2.bias", {D});
-                s.lin(p + ".merger.gate", D, D);
-                s.ln(p + ".final_norm", D);
-                s.ln(p + ".ffn.layer_norm", D); s.lin(p + ".ffn.linear1", 4 * D, D); s.lin(p + ".ffn.linear2", D, 4 * D);
-            }
-            s.lin("model.output_proj", E, D);
-            break;
-        }
-        case NWW_HEAD_TCN: {                      // TCNModel (architectures.py:290-367); tcn_channels in crnn_channels, tcn_kernel_size in layer_dim
-            const int k = c.layer_dim;
-            int cin = F;
-            for (int i = 0; i < c.n_crnn_channels; ++i) {
-                const int co = c.crnn_channels[i];
-                const std::string p = "model.tcn_blocks." + std::to_string(i);
-                s.add(p + ".conv1.weight", {co, cin, k}); s.add(p + ".conv1.bias", {co});
-                s.add(p + ".conv2.weight", {co, co, k}); s.add(p + ".conv2.bias", {co});
-                if (cin != co) { s.add(p + ".downsample.weight", {co, cin, 1}); s.add(p + ".downsample.bias", {co}); }
-                cin = co;
-            }
-            s.lin("model.fc", E, cin);
-            break;
-        }
-        case NWW_HEAD_E2E_QUARTZNET:              // E2ERawQuartzNet (architectures.py:798-817): RawAudioFrontend's Conv1d (no bias) + BatchNorm1d
-            for (int i = 0, cin = 1; i < nb; ++i) {   // per stage (channels in layer_dim, depth in n_blocks), then the QuartzNet under model.backbone
-                const int co = L << i;
-                s.add("model.frontend.conv_blocks." + std::to_string(3 * i) + ".weight", {co, cin, i == 0 ? 41 : 13});
-                s.bn("model.frontend.conv_blocks." + std::to_string(3 * i + 1), co);
-                cin = co;
-            }
-            [[fallthrough]];
-        case NWW_HEAD_QUARTZNET: {                // QuartzNetModel (architectures.py:370-437); the entries as include/nww.h packs them
-            const auto blocks = nww_quartznet_blocks(c);
-            const std::string qp = nww_quartznet_prefix(c);
-            for (size_t i = 0; i < blocks.size(); ++i) {
-                const QnBlock& q = blocks[i];
-                const std::string p = qp + "quartznet_blocks." + std::to_string(i);
-                s.add(p + ".depthwise_conv.weight", {q.cin, 1, q.k}); s.add(p + ".depthwise_conv.bias", {q.cin});
-                s.add(p + ".pointwise_conv.weight", {q.cout, q.cin, 1}); s.add(p + ".pointwise_conv.bias", {q.cout});
-                s.bn(p + ".batch_norm", q.cout);
-                if (q.cin != q.cout) {
-                    s.add(p + ".residual_connector.0.weight", {q.cout, q.cin, 1}); s.add(p + ".residual_connector.0.bias", {q.cout});
-                    s.bn(p + ".residual_connector.1", q.cout);
-                }
-            }
-            s.lin(qp + "fc", E, blocks.back().cout);
-            break;
-        }
-        case NWW_HEAD_E2E_DNN: {
-            int cin = 1;
-            const int ch[3] = {16, 32, 64};
-            for (int i = 0; i < 3; ++i) {
-                const std::string p = "model.conv_block." + std::to_string(4 * i);
-                s.add(p + ".weight", {ch[i], cin, 3, 3}); s.add(p + ".bias", {ch[i]});
-                s.bn("model.conv_block." + std::to_string(4 * i + 1), ch[i]);
-                cin = ch[i];
-            }
-            s.lin("model.fc1", 128, 256); s.bn("model.bn1", 128); s.lin("model.out", E, 128);
-            break;
-        }
-    }
-    s.lin("classifier.0", E / 2, E);
-    s.lin("classifier.3", 1, E / 2);
-}
-
-
 // ------------------------------------------------------------------------------------------ plan helpers
 namespace {
+
+// what src() / dst() take beside a workspace buffer's index (>= 0): the head input x, the embedding, the classifier's hidden row, the logits
+enum : int { BUF_X = -1, BUF_EMB = -2, BUF_HID = -3, BUF_LOGITS = -4, BUF_NONE = 99 };
 
 struct PlanCtx {
     nww_handle* h;
@@ -221,9 +34,28 @@ struct PlanCtx {
     void add(const std::string& name, std::function<hipError_t(Run&)> fn) { h->plan.push_back({name, std::move(fn)}); }
     void pop_last() { if (!h->plan.empty()) h->plan.pop_back(); }        // a step just planned is re-planned in another form
     // the head's last Linear (-> embedding), deferred so that it can be fused with the classifier into one launch
-    std::string tail_name; int tail_in = 99, tail_K = 0; const float *tail_W = nullptr, *tail_b = nullptr;
+    std::string tail_name; int tail_in = BUF_NONE, tail_K = 0; const float *tail_W = nullptr, *tail_b = nullptr;
     // DNN: LayerNorm1 + blocks run inside the tail's launch (TailArgs::ln0_w); mid[i]: block i's fcn_layer weight, bias, layer_norm weight, bias
     struct DnnBody { bool on = false; const float *ln0_w = nullptr, *ln0_b = nullptr; int n_mid = 0; const float* mid[4][4] = {}; } dnn;
+    // Device memory for the packed weight images of one step (a single image, a pair or a list), all or nothing: pack() allocates an
+    // image and runs the pack launch handed to it (on own_stream, nothing waits) - nullptr and nothing held if either fails -,
+    // commit() hands the images to the handle, which frees them at nww_destroy, and what was not committed is freed when the scope ends
+    struct Packs {
+        nww_handle* h;
+        std::vector<void*> held;
+        explicit Packs(PlanCtx& p) : h(p.h) {}
+        Packs(const Packs&) = delete;
+        ~Packs() { for (void* d : held) (void)hipFree(d); }
+        void* alloc(size_t bytes) { void* d = nullptr; if (hipMalloc(&d, bytes) != hipSuccess) return nullptr; held.push_back(d); return d; }
+        template <class Launch> void* pack(size_t bytes, Launch&& launch) {      // launch(void* image) -> hipError_t
+            void* d = alloc(bytes);
+            if (d && launch(d) != hipSuccess) { held.pop_back(); (void)hipFree(d); d = nullptr; }
+            return d;
+        }
+        void commit() { h->packed_weights.insert(h->packed_weights.end(), held.begin(), held.end()); held.clear(); }
+    };
+    // a single image: kept if it was built, else nullptr
+    template <class Launch> void* pack_one(size_t bytes, Launch&& launch) { Packs pk(*this); void* d = pk.pack(bytes, launch); pk.commit(); return d; }
 };
 
 // ---- two-term binary16 arithmetic (NWW_ARITH_F16X3): plan-time bounds and power-of-two scales
@@ -270,6 +102,10 @@ double f16_ln_bound(nww_handle* h, const float* w, const float* b, int D) {
     for (int k = 0; k < D; ++k) bound = std::fmax(bound, std::sqrt((double)D) * std::fabs((double)hw[k]) + std::fabs((double)hb[k]));
     return bound;
 }
+bool f16_all_nonneg(nww_handle* h, const float* d, int n) {      // folded-BN factors: max-pool commutes with BN + ReLU when none is negative
+    for (float v : f16_fetch(h, d, n)) if (!(v >= 0.0f)) return false;
+    return true;
+}
 // scale of the LayerNorm'd rows that the ffn_x3 epilogues sum exactly over time: |LayerNorm| x scale <= 2^36; 0 = no usable bound
 float f16_mean_scale(double bound) {
     const float s = bound < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(bound, 1e-30)) : 0.0f;
@@ -302,16 +138,21 @@ double f16_layer_typ(const std::vector<float>& w, int Cout, int K, const std::ve
     return acc / (Cout > 0 ? Cout : 1) * typ_in;
 }
 
-// source selector for a step input: -1 = head input x, -2 = emb, -3 = hid, >=0 workspace buffer
-inline const float* src(Run& r, int id) { return id == -1 ? r.x : id == -2 ? r.emb : id == -3 ? r.hid : r.buf[id]; }
-inline float* dst(Run& r, int id) { return id == -2 ? r.emb : id == -3 ? r.hid : id == -4 ? r.logits : r.buf[id]; }
+// a step's input / output: one of the named selectors above or a workspace buffer
+inline const float* src(Run& r, int id) { return id == BUF_X ? r.x : id == BUF_EMB ? r.emb : id == BUF_HID ? r.hid : r.buf[id]; }
+inline float* dst(Run& r, int id) { return id == BUF_EMB ? r.emb : id == BUF_HID ? r.hid : id == BUF_LOGITS ? r.logits : r.buf[id]; }
 
+struct GemmOpts {
+    const float *alpha = nullptr, *beta = nullptr;       // a folded BatchNorm behind the bias
+    int res_id = BUF_NONE; float rscale = 1.f;           // out = res + rscale act(...)
+    bool* a_blocked_inout = nullptr;                     // in: the producer can write A as this kernel's tiles; out: it has to
+    bool feeds_tail = false, feeds_ln = false;           // the consumer (the fused tail / a LayerNorm) can sum split-K partials itself
+    F16Range a_range; bool a_bound_assumed = false;      // the range of A, for the two-term form; assumed: the kernel enforces it by clamping A
+};
 // rows_per_clip: M = B*rows_per_clip
 void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int rows_per_clip, int N, int K,
-              const float* W, const float* bias, int act, const float* alpha = nullptr, const float* beta = nullptr,
-              int res_id = 99, float rscale = 1.f, bool* a_blocked_inout = nullptr, bool feeds_tail = false, bool feeds_ln = false,
-              F16Range a_range = F16Range{}, bool a_bound_assumed = false) {
-    const double a_bound = a_range.ok() ? a_range.bound : 0.0;
+              const float* W, const float* bias, int act, const GemmOpts& o = GemmOpts{}) {
+    const double a_bound = o.a_range.ok() ? o.a_range.bound : 0.0;
     const int tail_E = p.h->cfg.embedding_dim;
     if (out_id >= 0) p.need(out_id, (size_t)rows_per_clip * N);
     // Contractions run on the bf16 matrix cores by exact operand splitting (gemm_x3.hip) where that kernel wins -
@@ -350,18 +191,18 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
         if (it != p.h->x3_weights.end()) wx3 = it->second;
     }
     const bool h2 = h2_req && wx3 != nullptr;                  // the two-term epilogue only with its image
-    if (h2 && a_bound_assumed && in_id == -1) p.h->clamps_features = true;
+    if (h2 && o.a_bound_assumed && in_id == BUF_X) p.h->clamps_features = true;
     // the producer may write A directly as this kernel's [128][32] tiles (the fused trunk feeding fc1)
-    const int a_blocked = (a_blocked_inout && *a_blocked_inout && wx3 && K % 32 == 0 && rows_per_clip == 1) ? K / 32 : 0;
-    if (a_blocked_inout) *a_blocked_inout = a_blocked != 0;
+    const int a_blocked = (o.a_blocked_inout && *o.a_blocked_inout && wx3 && K % 32 == 0 && rows_per_clip == 1) ? K / 32 : 0;
+    if (o.a_blocked_inout) *o.a_blocked_inout = a_blocked != 0;
     if (K >= 2048 && (size_t)16 * rows_per_clip * N > p.h->splitk_per_clip) p.h->splitk_per_clip = (size_t)16 * rows_per_clip * N;
     p.add("gemm:" + name + (h2 && wx3 ? " [f16x3]" : ""), [=](Run& r) {
         GemmArgs g;
         g.A = src(r, in_id); g.lda = K; g.W = W; g.C = dst(r, out_id); g.ldc = N;
-        g.M = r.B * rows_per_clip; g.N = N; g.K = K; g.bias = bias; g.alpha = alpha; g.beta = beta; g.act = act;
-        g.res = res_id == 99 ? nullptr : src(r, res_id); g.ldres = N; g.rscale = rscale;
+        g.M = r.B * rows_per_clip; g.N = N; g.K = K; g.bias = bias; g.alpha = o.alpha; g.beta = o.beta; g.act = act;
+        g.res = o.res_id == BUF_NONE ? nullptr : src(r, o.res_id); g.ldres = N; g.rscale = o.rscale;
         g.Wx3 = wx3;
-        if (h2) { g.h2 = 1; g.a_scale = h2_as; g.c_scale = 1.0f / (h2_as * h2_ws); g.a_clamp = a_bound_assumed ? (float)a_bound : 0.0f; }
+        if (h2) { g.h2 = 1; g.a_scale = h2_as; g.c_scale = 1.0f / (h2_as * h2_ws); g.a_clamp = o.a_bound_assumed ? (float)a_bound : 0.0f; }
         g.a_blocked = a_blocked;
         g.splitk = gemm_recommended_splitk(g.M, N, K, r.cu_count);
         // split-operand layers: chunks of ~16-25 k-tiles, so that a small batch's chunk is ONE round of gemm_x3_chain_kernel
@@ -377,14 +218,14 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
         // output less.  A handful of clips (the interpreter's calls; B = 1: 62 -> 58 us back-to-back) on the latency kernel, large batches
         // where the persistent tail runs (tail_batch_runs, the predicate launch_classifier_tail itself uses; B = 4096: reduce + tail
         // 0.0076 + 0.0167 -> 0.0121 ms).  In between the reduce launch stays: the latency kernel's few workgroups read the partials slower.
-        if (feeds_tail && partials && !g.res && (g.M <= 8 || tail_batch_runs(g.M, N, tail_E, false, g.splitk))) {
+        if (o.feeds_tail && partials && !g.res && (g.M <= 8 || tail_batch_runs(g.M, N, tail_E, false, g.splitk))) {
             g.defer_reduce = true;
             r.deferred.active = true; r.deferred.out_id = out_id; r.deferred.parts = g.splitk; r.deferred.stride = (size_t)g.M * N;
-            r.deferred.bias = bias; r.deferred.alpha = alpha; r.deferred.beta = beta; r.deferred.act = act;
+            r.deferred.bias = bias; r.deferred.alpha = o.alpha; r.deferred.beta = o.beta; r.deferred.act = act;
         }
         // a LayerNorm right behind a split-K Linear (DNN layer1) sums the partials itself, at every batch size: the reduce launch
         // and its round trip go (the caller's LayerNorm step checks r.deferred)
-        if (feeds_ln && partials && !g.res && !alpha && act == ACT_NONE && N <= 256) {
+        if (o.feeds_ln && partials && !g.res && !o.alpha && act == ACT_NONE && N <= 256) {
             g.defer_reduce = true;
             r.deferred.active = true; r.deferred.out_id = out_id; r.deferred.parts = g.splitk; r.deferred.stride = (size_t)g.M * N;
             r.deferred.bias = bias; r.deferred.alpha = nullptr; r.deferred.beta = nullptr; r.deferred.act = ACT_NONE;
@@ -394,14 +235,19 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
 }
 
 // Short-K Linear on the input-stationary split-operand kernel (lin_x3.hip); false -> the caller plans the general GEMM.
-// epi 0: out = y + b; 1: out = res + rscale (y + b); 2: LayerNorm(ln_w, ln_b) first when given, W = [2N][K], out = a * sigmoid(b);
-// 3: out = rscale (y + b) + res_tab[(row % qkv_T) N ..] (a [>= qkv_T][N] table, the Transformer's positional encoding)
+// LIN_BIAS: out = y + b; LIN_RES: out = res + rscale (y + b); LIN_GLU: W = [2N][K], out = a * sigmoid(b);
+// LIN_RES_TAB: out = rscale (y + b) + res_tab[(row % qkv_T) N ..] (a [>= qkv_T][N] table, the Transformer's positional encoding)
+enum LinEpi : int { LIN_BIAS = 0, LIN_RES = 1, LIN_GLU = 2, LIN_RES_TAB = 3 };
+struct LinOpts {
+    int epi = LIN_BIAS, res_id = BUF_NONE; float rscale = 1.f; const float* res_tab = nullptr;
+    const float *ln_w = nullptr, *ln_b = nullptr;        // LayerNorm of the input rows first (LIN_GLU, and LIN_BIAS at the widths that have it)
+    int qkv_T = 0, qkv_dh = 0;                           // q | k | v written head-major: the clip's rows and the head width
+};
 bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int rows_per_clip, int N, int K, const float* W,
-                const float* bias, int epi, int res_id = 99, float rscale = 1.f, const float* ln_w = nullptr,
-                const float* ln_b = nullptr, int qkv_T = 0, int qkv_dh = 0, const float* res_tab = nullptr) {
+                const float* bias, const LinOpts& o = LinOpts{}) {
     if (!nww_knobs().lin_x3 || p.h->conv_products != 6 || !lin_x3_supported(K, N, true)) return false;
-    if (ln_w && epi != 2 && !(epi == 0 && lin_x3_ln_plain_supported(K))) return false;
-    const int parts = epi == 2 ? 2 : 1;
+    if (o.ln_w && o.epi != LIN_GLU && !(o.epi == LIN_BIAS && lin_x3_ln_plain_supported(K))) return false;
+    const int parts = o.epi == LIN_GLU ? 2 : 1;
     // under NWW_ARITH_F16X3: two binary16 terms per operand, the input rows scaled per row in the kernel (LinArgs::h2: no bound on the
     // tensor needed); conv_arith = bf16x6 keeps the three-term bf16 form
     float ws = 0.0f;
@@ -409,29 +255,29 @@ bool add_lin_x3(PlanCtx& p, const std::string& name, int in_id, int out_id, int 
     const bool h2 = ws > 0.0f;
     if (!lin_x3_supported(K, N, h2)) return false;                 // K = 192 / 256 exist in the two-term form only
     const int terms = h2 ? 2 : 3;
-    void* packed = nullptr;
-    if (hipMalloc(&packed, lin_x3_packed_bytes(K, N, parts, terms)) != hipSuccess) return false;
-    if (launch_lin_x3_pack(W, bias, packed, K, N, parts, N, p.h->own_stream, terms, h2 ? ws : 1.0f) != hipSuccess) { (void)hipFree(packed); return false; }
-    p.h->packed_weights.push_back(packed);
+    void* packed = p.pack_one(lin_x3_packed_bytes(K, N, parts, terms), [&](void* d) { return launch_lin_x3_pack(W, bias, d, K, N, parts, N, p.h->own_stream, terms, h2 ? ws : 1.0f); });
+    if (!packed) return false;
     p.need(out_id, (size_t)rows_per_clip * N);
     const float w_un = h2 ? 1.0f / ws : 1.0f;
     p.add("lin_x3:" + name + (h2 ? " [f16x3]" : ""), [=](Run& r) {
         LinArgs a;
         a.x = src(r, in_id); a.ldx = K; a.out = dst(r, out_id); a.ldc = N;
-        a.res = res_tab ? res_tab : res_id == 99 ? nullptr : src(r, res_id); a.ldres = N; a.rscale = rscale;
-        a.ln_w = ln_w; a.ln_b = ln_b; a.packed = static_cast<const unsigned char*>(packed);
-        a.M = r.B * rows_per_clip; a.N = N; a.qkv_T = qkv_T; a.qkv_dh = qkv_dh;
+        a.res = o.res_tab ? o.res_tab : o.res_id == BUF_NONE ? nullptr : src(r, o.res_id); a.ldres = N; a.rscale = o.rscale;
+        a.ln_w = o.ln_w; a.ln_b = o.ln_b; a.packed = static_cast<const unsigned char*>(packed);
+        a.M = r.B * rows_per_clip; a.N = N; a.qkv_T = o.qkv_T; a.qkv_dh = o.qkv_dh;
         a.h2 = h2 ? 1 : 0; a.w_un = w_un;
-        return launch_lin_x3(a, K, epi, ln_w != nullptr, r.stream);
+        return launch_lin_x3(a, K, o.epi, o.ln_w != nullptr, r.stream);
     });
     return true;
 }
 
 // A Linear (+ residual res_id times rscale) on the short-K kernel where it applies, else on the general GEMM with the same operands
 void add_linear(PlanCtx& p, const std::string& name, int in_id, int out_id, int rows_per_clip, int N, int K, const float* W,
-                const float* bias, int res_id = 99, float rscale = 1.f) {
-    if (!add_lin_x3(p, name, in_id, out_id, rows_per_clip, N, K, W, bias, res_id == 99 ? 0 : 1, res_id, rscale))
-        add_gemm(p, name, in_id, out_id, rows_per_clip, N, K, W, bias, ACT_NONE, nullptr, nullptr, res_id, rscale);
+                const float* bias, int res_id = BUF_NONE, float rscale = 1.f) {
+    LinOpts lo; lo.epi = res_id == BUF_NONE ? LIN_BIAS : LIN_RES; lo.res_id = res_id; lo.rscale = rscale;
+    GemmOpts go; go.res_id = res_id; go.rscale = rscale;
+    if (!add_lin_x3(p, name, in_id, out_id, rows_per_clip, N, K, W, bias, lo))
+        add_gemm(p, name, in_id, out_id, rows_per_clip, N, K, W, bias, ACT_NONE, go);
 }
 
 void set_tail(PlanCtx& p, const std::string& name, int in_id, int K, const float* W, const float* b) {
@@ -450,13 +296,14 @@ void add_conv(PlanCtx& p, const std::string& name, int in_id, int out_id, int Ci
 }
 
 static int trunk_fits(int C1, int H, int W) { int per_cu = 0; return trunk_pick_strips(C1, H, W, &per_cu); }
+// out_blocked, read at run time: the output as the consumer GEMM's A tiles (add_gemm decides); the two-term form: the input's range in, the output's out
+struct TrunkOpts { const bool* out_blocked = nullptr; F16Range in_range; F16Range* out_range = nullptr; };
 // fused conv1+pool+conv2+pool (trunk.hip) when the 1->16->32 pattern fits LDS; returns false if not applicable
 bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C1, int C2, int H, int W,
                const float* w1, const float* b1, const float* al1, const float* be1, const float* w2,
-               const float* b2, const float* al2, const float* be2, int act, const bool* out_blocked = nullptr,
-               F16Range in_range = F16Range{}, F16Range* out_range = nullptr) {
-    if (out_range) *out_range = F16Range{};
-    const double in_bound = in_range.ok() ? in_range.bound : 0.0;
+               const float* b2, const float* al2, const float* be2, int act, const TrunkOpts& o = TrunkOpts{}) {
+    if (o.out_range) *o.out_range = F16Range{};
+    const double in_bound = o.in_range.ok() ? o.in_range.bound : 0.0;
     if (!nww_knobs().trunk || C1 != 16 || C2 != 32 || H < 4 || W < 4 || trunk_fits(C1, H, W) == 0) return false;
     p.need(out_id, (size_t)C2 * (H / 4) * (W / 4));
     const int max_grid = p.h->cu_count;
@@ -464,8 +311,6 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
     const int x3 = p.h->conv_products;
     if ((x3 == 6 || x3 == 9) && trunk_b_pick_strips(H, W) > 0) {
         // both convolutions' weights as the MFMA register images, split into bf16 terms once (trunk_b.hip)
-        void* packed = nullptr;
-        if (hipMalloc(&packed, trunk_b_packed_bytes()) != hipSuccess) return false;
         // NWW_ARITH_F16X3: two binary16 terms per operand when the input is bounded; the scales from bounds on conv1's / conv2's outputs
         float f_in = 0.0f, f_s1 = 0.0f, f_w1 = 0.0f, f_w2 = 0.0f;
         double bound2 = 0.0, typ2 = 0.0;
@@ -475,33 +320,30 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
             const auto ha1 = f16_fetch(p.h, al1, C1), he1 = f16_fetch(p.h, be1, C1), ha2 = f16_fetch(p.h, al2, C2), he2 = f16_fetch(p.h, be2, C2);
             const double bound1 = f16_layer_bound(hw1, C1, 9, hb1, b1 != nullptr, ha1, he1, al1 != nullptr, in_bound);
             bound2 = f16_layer_bound(hw2, C2, C1 * 9, hb2, b2 != nullptr, ha2, he2, al2 != nullptr, bound1);
-            const F16Range r1{bound1, f16_layer_typ(hw1, C1, 9, ha1, al1 != nullptr, in_range.typ)};
+            const F16Range r1{bound1, f16_layer_typ(hw1, C1, 9, ha1, al1 != nullptr, o.in_range.typ)};
             typ2 = f16_layer_typ(hw2, C2, C1 * 9, ha2, al2 != nullptr, r1.typ);
             if (r1.ok()) { f_in = f16_scale(in_bound); f_s1 = f16_scale(bound1); f_w1 = f16_wscale(hw1); f_w2 = f16_wscale(hw2); }
         }
         const bool f16 = f_in > 0.0f && f_s1 > 0.0f && f_w1 > 0.0f && f_w2 > 0.0f;
-        if ((f16 ? launch_trunk_b_pack_f16(w1, w2, static_cast<unsigned char*>(packed), f_w1, f_w2, p.h->own_stream)
-                 : launch_trunk_b_pack(w1, w2, static_cast<unsigned char*>(packed), p.h->own_stream)) != hipSuccess) { (void)hipFree(packed); return false; }
-        p.h->packed_weights.push_back(packed);
-        if (f16 && out_range) *out_range = F16Range{bound2, typ2};
+        void* packed = p.pack_one(trunk_b_packed_bytes(), [&](void* d) {
+            return f16 ? launch_trunk_b_pack_f16(w1, w2, static_cast<unsigned char*>(d), f_w1, f_w2, p.h->own_stream)
+                       : launch_trunk_b_pack(w1, w2, static_cast<unsigned char*>(d), p.h->own_stream);
+        });
+        if (!packed) return false;
+        if (f16 && o.out_range) *o.out_range = F16Range{bound2, typ2};
         const int products = f16 ? 3 : x3;
         // BN + ReLU stems (CRNN, E2E): all folded-BN factors of both layers non-negative (gamma > 0, the usual case) -> the pooled value is
         // the window's maximum pushed through BN + ReLU (trunk_b.hip: POS instance)
-        int bn_pos = 0;
-        if (f16 && al1 && al2 && act == ACT_RELU) {
-            bn_pos = 1;
-            for (float v : f16_fetch(p.h, al1, C1)) if (!(v >= 0.0f)) bn_pos = 0;
-            for (float v : f16_fetch(p.h, al2, C2)) if (!(v >= 0.0f)) bn_pos = 0;
-        }
-        if (in_id == -1 && !p.h->e2e_transposed) p.h->x_stride_ok = true;                   // this step reads the head input with any clip stride
-        if (f16 && in_id == -1) p.h->clamps_features = true;
+        const int bn_pos = f16 && al1 && al2 && act == ACT_RELU && f16_all_nonneg(p.h, al1, C1) && f16_all_nonneg(p.h, al2, C2);
+        if (in_id == BUF_X && !p.h->e2e_transposed) p.h->x_stride_ok = true;                // this step reads the head input with any clip stride
+        if (f16 && in_id == BUF_X) p.h->clamps_features = true;
         p.add("trunk_x3:" + name + (f16 ? " [f16x3]" : ""), [=](Run& r) {
             TrunkArgs a{src(r, in_id), w1, b1, al1, be1, w2, b2, al2, be2, dst(r, out_id), r.B, H, W, act};
-            if (out_blocked && *out_blocked) a.out_blocked = C2 * (H / 4) * (W / 4) / 32;     // decided by the consumer (add_gemm) at plan time
+            if (o.out_blocked && *o.out_blocked) a.out_blocked = C2 * (H / 4) * (W / 4) / 32;     // decided by the consumer (add_gemm) at plan time
             a.wpack = static_cast<const unsigned char*>(packed);
             if (f16) { a.f16_in = f_in; a.f16_k1 = f_in * f_w1; a.f16_s1 = f_s1; a.f16_k2 = f_s1 * f_w2; a.f16_so = 1.0f; a.f16_clamp = (float)in_bound; }
             a.bn_pos = bn_pos;
-            if (in_id == -1) a.in_clip_stride = r.x_stride;
+            if (in_id == BUF_X) a.in_clip_stride = r.x_stride;
             if (r.stream_mode) {                        // streaming hop: pooled rows into the per-stream rings, all of them or the invalidated ones
                 a.out = r.a2_ring; a.out_ring_rows = r.a2_rows; a.out_row0 = r.a2_row0;
                 a.out_ch_stride = r.a2_ch_stride; a.out_clip_stride = r.a2_clip_stride;
@@ -519,16 +361,22 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
     return true;
 }
 
+struct ConvMfmaOpts {
+    int avg_kw = 0, avg_sw = 0, avg_ow = 0, avg_y = 0;   // an average pool behind the conv: window, stride, outputs (0: none); along y instead of x
+    bool* seq_inout = nullptr;                           // in: write the recurrent layers' sequence layout; out: whether this instance does
+    bool* ring_in = nullptr;                             // in: the input may come from the streaming rings; out: whether this instance reads them
+    F16Range in_range; F16Range* out_range = nullptr;    // the two-term form: the input's range in, the output's out
+    int scratch_id = BUF_NONE;                           // raw sums of the k-split passes (more than 32 input channels)
+};
 // 3x3 conv stage with 32 input channels on MFMA (trunk.hip) when it fits; false -> caller uses the VALU kernel
 bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, int Cin, int Cout, int H, int W,
                    const float* w, const float* bias, const float* alpha, const float* beta, int act, int pool,
-                   int avg_kw = 0, int avg_sw = 0, int avg_ow = 0, bool* seq_inout = nullptr, int avg_y = 0, bool* ring_in = nullptr,
-                   F16Range in_range = F16Range{}, F16Range* out_range = nullptr, int scratch_id = -1) {
-    if (out_range) *out_range = F16Range{};
-    const double in_bound = in_range.ok() ? in_range.bound : 0.0;
+                   const ConvMfmaOpts& o = ConvMfmaOpts{}) {
+    if (o.out_range) *o.out_range = F16Range{};
+    const double in_bound = o.in_range.ok() ? o.in_range.bound : 0.0;
     const int enabled = nww_knobs().conv_mfma, x3_enabled = nww_knobs().conv3_x3;
     // 64 input channels (a fourth CRNN stage): conv3_x3's wide instance - two-term arithmetic on a bounded input only
-    bool wide = Cin == 64 && enabled && x3_enabled && pool && avg_ow == 0 && !avg_y && p.h->conv_products == 6 && p.h->f16 && in_bound > 0.0 &&
+    bool wide = Cin == 64 && enabled && x3_enabled && pool && o.avg_ow == 0 && !o.avg_y && p.h->conv_products == 6 && p.h->f16 && in_bound > 0.0 &&
                 Cout % 32 == 0 && conv3_x3_wide_fits(Cin, H, W, Cout);
     if (wide) {
         const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
@@ -538,65 +386,65 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
     // 32-channel three-term instance once per 32 input channels - every pass but the last leaves raw, un-pooled sums in a scratch buffer, the
     // next one starts its accumulators from them (k-split; the planes of such stages are a few hundred pixels)
     if (!wide && Cin > 32) {
-        if (!enabled || !x3_enabled || Cin % 32 != 0 || Cin > 256 || !pool || avg_ow > 0 || avg_y || p.h->conv_products != 6 || scratch_id < 0 ||
+        if (!enabled || !x3_enabled || Cin % 32 != 0 || Cin > 256 || !pool || o.avg_ow > 0 || o.avg_y || p.h->conv_products != 6 || o.scratch_id == BUF_NONE ||
             Cout % 32 != 0) return false;
         const bool whole = conv3_x3_fits(H, W, Cout, 0, 1) && conv3_x3_fits(H, W, Cout, 0, 0);
         const int sh = whole ? 0 : conv3_x3_strip_rows(H, W, Cout);          // larger planes: in strips of rows
         if (!whole && sh == 0) return false;
-        if (ring_in) *ring_in = false;
+        if (o.ring_in) *o.ring_in = false;
         p.need(out_id, (size_t)Cout * (H / 2) * (W / 2));
-        p.need(scratch_id, (size_t)Cout * H * W);
+        p.need(o.scratch_id, (size_t)Cout * H * W);
         const int np = Cin / 32, grid = p.h->cu_count * ((sh ? conv3_x3_strip_lds_bytes(sh, W) : conv3_x3_lds_bytes(H, W, 0)) * 2 <= 160 * 1024 ? 2 : 1);
-        const int seq_out = (seq_inout && *seq_inout) ? 1 : 0;
+        const int seq_out = (o.seq_inout && *o.seq_inout) ? 1 : 0;
         for (int pass = 0; pass < np; ++pass) {
             const bool fin = pass == np - 1;
             p.add(std::string(fin && seq_out ? "conv3_x3+seq:" : "conv3_x3:") + name + " (input channels " + std::to_string(32 * pass) + "-" + std::to_string(32 * pass + 31) +
                       (fin ? ", epilogue)" : ", raw sums)"), [=](Run& r) {
-                ConvMfmaArgs a{src(r, in_id), w, fin ? bias : nullptr, fin ? alpha : nullptr, fin ? beta : nullptr, fin ? dst(r, out_id) : r.buf[scratch_id],
+                ConvMfmaArgs a{src(r, in_id), w, fin ? bias : nullptr, fin ? alpha : nullptr, fin ? beta : nullptr, fin ? dst(r, out_id) : r.buf[o.scratch_id],
                                r.B, H, W, Cout, fin ? act : (int)ACT_NONE, fin ? 1 : 0};
-                a.w_cin = Cin; a.w_cin_off = 32 * pass; a.acc_in = pass ? r.buf[scratch_id] : nullptr; a.seq_out = fin ? seq_out : 0; a.strip_h = sh;
+                a.w_cin = Cin; a.w_cin_off = 32 * pass; a.acc_in = pass ? r.buf[o.scratch_id] : nullptr; a.seq_out = fin ? seq_out : 0; a.strip_h = sh;
                 return launch_conv3_x3(a, grid, r.stream);
             });
         }
         return true;
     }
     if (wide) {
-        if (ring_in) *ring_in = false;
+        if (o.ring_in) *o.ring_in = false;
     } else if (!enabled || Cin != 32 || Cout % 32 != 0 || H < 2 || W < 2)
         return false;
     // (the float32-MFMA instance shares its 8 waves among the 32-channel groups; conv3_x3 takes one group per workgroup)
     const bool f32_fits = !wide && (8 % (Cout / 32)) == 0 && conv_mfma_lds_bytes(Cin, H, W) <= 160 * 1024;
     // pooled planes of more than 512 pixels (clips longer than ~1.3 s, a second stage behind an unfused first one): conv3_x3 in strips of rows
-    const int strip_h = (!wide && pool && avg_ow == 0 && !avg_y && !conv3_x3_fits(H, W, Cout, avg_ow, pool)) ? conv3_x3_strip_rows(H, W, Cout) : 0;
-    const bool x3_shape = strip_h > 0 || conv3_x3_fits(H, W, Cout, avg_ow, pool);
+    const int strip_h = (!wide && pool && o.avg_ow == 0 && !o.avg_y && !conv3_x3_fits(H, W, Cout, o.avg_ow, pool)) ? conv3_x3_strip_rows(H, W, Cout) : 0;
+    const bool x3_shape = strip_h > 0 || conv3_x3_fits(H, W, Cout, o.avg_ow, pool);
     if (!wide && !f32_fits && !(x3_enabled && p.h->conv_products == 6 && x3_shape)) return false;
     const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-    p.need(out_id, avg_ow > 0 ? (size_t)Cout * avg_ow : (size_t)Cout * Ho * Wo);
+    p.need(out_id, o.avg_ow > 0 ? (size_t)Cout * o.avg_ow : (size_t)Cout * Ho * Wo);
     const int max_grid = p.h->cu_count;
     // split-operand bf16 instance (conv3_x3.hip) under the same arithmetic switch as the fused trunk; the 9-product
     // mode keeps the float32-MFMA kernel (the conv3 instance implements the 6-product form only)
     if (wide || (x3_enabled && p.h->conv_products == 6 && x3_shape)) {
-        const size_t lds = wide ? conv3_x3_wide_lds_bytes(Cin, H, W) : strip_h ? conv3_x3_strip_lds_bytes(strip_h, W) : conv3_x3_lds_bytes(H, W, avg_ow);
-        if (strip_h && ring_in) *ring_in = false;                                             // strips read dense planes
+        const size_t lds = wide ? conv3_x3_wide_lds_bytes(Cin, H, W) : strip_h ? conv3_x3_strip_lds_bytes(strip_h, W) : conv3_x3_lds_bytes(H, W, o.avg_ow);
+        if (strip_h && o.ring_in) *o.ring_in = false;                                             // strips read dense planes
         const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-        const int seq_out = (seq_inout && *seq_inout && pool && avg_ow == 0) ? 1 : 0;      // the caller wants the sequence layout
-        const bool ring_ok = ring_in && *ring_in;                                             // ... and may hand the input over in rings
+        const int seq_out = (o.seq_inout && *o.seq_inout && pool && o.avg_ow == 0) ? 1 : 0;      // the caller wants the sequence layout
+        const bool ring_ok = o.ring_in && *o.ring_in;                                             // ... and may hand the input over in rings
         // NWW_ARITH_F16X3: two binary16 terms when the input is bounded (the fused trunk's plan-time bound)
         float h2_in = 0.0f, h2_w = 0.0f;
         if (p.h->f16 && in_bound > 0.0) {
             const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
             h2_in = f16_scale(in_bound); h2_w = f16_wscale(hw);
-            if (out_range && h2_in > 0.0f && h2_w > 0.0f) {
+            if (o.out_range && h2_in > 0.0f && h2_w > 0.0f) {
                 const auto hal = f16_fetch(p.h, alpha, Cout);
-                *out_range = F16Range{f16_layer_bound(hw, Cout, Cin * 9, f16_fetch(p.h, bias, Cout), bias != nullptr, hal, f16_fetch(p.h, beta, Cout), alpha != nullptr, in_bound),
-                                      f16_layer_typ(hw, Cout, Cin * 9, hal, alpha != nullptr, in_range.typ)};
+                *o.out_range = F16Range{f16_layer_bound(hw, Cout, Cin * 9, f16_fetch(p.h, bias, Cout), bias != nullptr, hal, f16_fetch(p.h, beta, Cout), alpha != nullptr, in_bound),
+                                      f16_layer_typ(hw, Cout, Cin * 9, hal, alpha != nullptr, o.in_range.typ)};
             }
         }
         const bool h2 = h2_in > 0.0f && h2_w > 0.0f;
-        p.add(std::string(avg_ow > 0 ? "conv3_x3+avgpool:" : seq_out ? "conv3_x3+seq:" : "conv3_x3:") + name + (strip_h ? " (strips of " + std::to_string(strip_h) + " rows)" : "") + (h2 ? " [f16x3]" : ""), [=](Run& r) {
+        p.add(std::string(o.avg_ow > 0 ? "conv3_x3+avgpool:" : seq_out ? "conv3_x3+seq:" : "conv3_x3:") + name + (strip_h ? " (strips of " + std::to_string(strip_h) + " rows)" : "") + (h2 ? " [f16x3]" : ""), [=](Run& r) {
             ConvMfmaArgs a{src(r, in_id), w, bias, alpha, beta, dst(r, out_id), r.B, H, W, Cout, act, pool};
             a.Cin = Cin; a.w_cin = Cin; a.strip_h = strip_h;
-            a.avg_kw = avg_kw; a.avg_sw = avg_sw; a.avg_ow = avg_ow; a.seq_out = seq_out; a.avg_y = avg_y;
+            a.avg_kw = o.avg_kw; a.avg_sw = o.avg_sw; a.avg_ow = o.avg_ow; a.seq_out = seq_out; a.avg_y = o.avg_y;
             if (h2) { a.h2_in = h2_in; a.h2_w = h2_w; }
             if (ring_ok && r.stream_mode) {             // streaming hop: the fused trunk's pooled rows are read from their rings
                 a.in = r.a2_ring; a.in_ring_rows = r.a2_rows; a.in_row0 = r.a2_row0;
@@ -611,12 +459,12 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
         });
         return true;
     }
-    if (avg_y) return false;                                   // only conv3_x3 pools along y (the caller checked e2e_transposed_ok)
-    if (seq_inout) *seq_inout = false;                         // the float32-MFMA instance writes planes
-    if (ring_in) *ring_in = false;                             // ... and reads dense planes
-    p.add(std::string(avg_ow > 0 ? "conv3x3_mfma+avgpool:" : "conv3x3_mfma:") + name, [=](Run& r) {
+    if (o.avg_y) return false;                                   // only conv3_x3 pools along y (the caller checked e2e_transposed_ok)
+    if (o.seq_inout) *o.seq_inout = false;                         // the float32-MFMA instance writes planes
+    if (o.ring_in) *o.ring_in = false;                             // ... and reads dense planes
+    p.add(std::string(o.avg_ow > 0 ? "conv3x3_mfma+avgpool:" : "conv3x3_mfma:") + name, [=](Run& r) {
         ConvMfmaArgs a{src(r, in_id), w, bias, alpha, beta, dst(r, out_id), r.B, H, W, Cout, act, pool};
-        a.avg_kw = avg_kw; a.avg_sw = avg_sw; a.avg_ow = avg_ow;
+        a.avg_kw = o.avg_kw; a.avg_sw = o.avg_sw; a.avg_ow = o.avg_ow;
         return launch_conv3x3_mfma(a, Cin, max_grid, r.stream);
     });
     return true;
@@ -662,7 +510,7 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
         // projection is computed inside the recurrence kernel - x_t W_ih^T on the matrix pipe beside h W_hh^T - instead of a GEMM that
         // writes T x 3H gate pre-activations per clip to HBM for the recurrence to read back (635 MB each way at B = 4096, T = 101, H = 128).
         const float* wih_f = p.W(prefix + ".weight_ih_l" + std::to_string(l));
-        const float wi_scale = (fold && l == 0 && in_id == -1 && G == 3 && products == 3 && (cur_I == 32 || cur_I == 64) && (H == 32 || H == 64 || H == 128) &&
+        const float wi_scale = (fold && l == 0 && in_id == BUF_X && G == 3 && products == 3 && (cur_I == 32 || cur_I == 64) && (H == 32 || H == 64 || H == 128) &&
                                 wih_f && (reinterpret_cast<uintptr_t>(wih_f) & 15) == 0)
                                    ? f16_wscale(f16_fetch(p.h, wih_f, (size_t)G * H * cur_I)) : 0.0f;
         const float* whh_fwd = p.W(prefix + ".weight_hh_l" + std::to_string(l));
@@ -697,11 +545,8 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
             // widths the register-resident / 32-units-per-wave kernels do not take: zero-padded weight rows for the any-width kernel
             int ldw = 0;
             if (H % 4 != 0 || H > 256) {
-                float* padded = nullptr;
-                if (hipMalloc(&padded, rnn_wide_weight_bytes(G, H)) == hipSuccess && launch_rnn_pad_weights(whh_f, padded, G, H, p.h->own_stream) == hipSuccess) {
-                    p.h->packed_weights.push_back(padded);
-                    whh_f = padded; ldw = (H + 7) & ~7;
-                } else if (padded) (void)hipFree(padded);
+                void* padded = p.pack_one(rnn_wide_weight_bytes(G, H), [&](void* d) { return launch_rnn_pad_weights(whh_f, static_cast<float*>(d), G, H, p.h->own_stream); });
+                if (padded) { whh_f = static_cast<const float*>(padded); ldw = (H + 7) & ~7; }
             }
             const float* bhh_f = fold ? p.W(prefix + ".bias_hh_l" + std::to_string(l)) : bhh;
             const std::string nm = fold ? (G == 4 ? "lstm:" : "gru:") + prefix + "_l" + std::to_string(l) + " + first reverse step"
@@ -710,16 +555,10 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
             const int products_l = (products == 3 && !(w_scale > 0.0f)) ? p.h->conv_products : products;
             const void* w_packed = nullptr;
             if (streamed && products_l == 3 && ldw == 0) {
-                void* pk = nullptr;
-                if (hipMalloc(&pk, rnn_stream_packed_bytes(G, H)) == hipSuccess && launch_rnn_stream_pack(whh_f, pk, G, H, w_scale, p.h->own_stream) == hipSuccess) {
-                    p.h->packed_weights.push_back(pk);
-                    w_packed = pk;
-                } else {
-                    // the folded form (reverse step inside the forward launch) exists only on the streamed kernel for these widths: without its
-                    // packed W_hh every forward would fail at run time - fail the finalize instead
-                    if (pk) (void)hipFree(pk);
-                    if (fold) p.h->plan_error = "out of device memory for the streamed W_hh image of " + prefix;
-                }
+                w_packed = p.pack_one(rnn_stream_packed_bytes(G, H), [&](void* d) { return launch_rnn_stream_pack(whh_f, d, G, H, w_scale, p.h->own_stream); });
+                // the folded form (reverse step inside the forward launch) exists only on the streamed kernel for these widths: without its
+                // packed W_hh every forward would fail at run time - fail the finalize instead
+                if (!w_packed && fold) p.h->plan_error = "out of device memory for the streamed W_hh image of " + prefix;
             }
             const bool fused_here = fuse_ih && fold && products_l == 3 && ldw == 0;
             const float* bih_f = p.W(prefix + ".bias_ih_l" + std::to_string(l));
@@ -750,189 +589,14 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
     }
 }
 
-// ------------------------------------------------------------------------------------------ weights and frontend tables
-// every BatchNorm folded (eval): alpha = w/sqrt(var+eps), beta = b - mean*alpha (PyTorch CPU kernel form)
-void fold_batchnorms(nww_handle* h) {
-    std::vector<std::string> bn_prefixes;
-    for (const auto& k : h->keys) {
-        const std::string sfx = ".running_var";
-        if (k.size() > sfx.size() && k.compare(k.size() - sfx.size(), sfx.size(), sfx) == 0)
-            bn_prefixes.push_back(k.substr(0, k.size() - sfx.size()));
-    }
-    for (const auto& p : bn_prefixes) {
-        const HostTensor &w = h->tensors[p + ".weight"], &b = h->tensors[p + ".bias"], &m = h->tensors[p + ".running_mean"],
-                         &v = h->tensors[p + ".running_var"];
-        HostTensor al, be;
-        al.shape = be.shape = w.shape;
-        al.data.resize(w.data.size()); be.data.resize(w.data.size());
-        for (size_t i = 0; i < w.data.size(); ++i) {
-            const float invstd = 1.0f / std::sqrt(v.data[i] + 1e-5f);
-            al.data[i] = w.data[i] * invstd;
-            be.data[i] = b.data[i] - m.data[i] * al.data[i];
-        }
-        al.loaded = be.loaded = true;
-        h->tensors[p + ".alpha"] = al;
-        h->tensors[p + ".beta"] = be;
-    }
-}
-
-// BcResNet: depthwise 3x3 weights tap-major [9][C] for the channels-last kernels
-void transpose_depthwise(nww_handle* h) {
-    for (int i = 1; i <= 3; ++i) {
-        const std::string k = "model.block" + std::to_string(i) + ".depthwise.weight";
-        const HostTensor& w = h->tensors[k];
-        const int C = (int)w.shape[0];
-        HostTensor wt;
-        wt.shape = {9, C};
-        wt.data.resize((size_t)9 * C);
-        for (int ch = 0; ch < C; ++ch)
-            for (int tap = 0; tap < 9; ++tap) wt.data[(size_t)tap * C + ch] = w.data[(size_t)ch * 9 + tap];
-        wt.loaded = true;
-        h->tensors[k + "_t"] = wt;
-    }
-}
-
-// QuartzNet: everything a block's launches read, folded ONCE in float64 (derived tensors "<block>.qn.*"):
-//   pw [Cout][Cin] = alpha pointwise, res [Cout][Cin] = alpha_r projection, bias [Cout] = alpha (W_pw b_dw + b_pw) + beta (+ alpha_r b_res + beta_r),
-//   dw_t [k][Cp] the depthwise taps tap-major, zeros past Cin (Cp = Cin up to 32), amax [1] = max_c sum_j |tap|, and where qn_x3 has the
-//   widths wcat [Cout][qn_x3_ktot]: pw and res side by side in the fused kernel's chunk order (qn_x3_col)
-void fold_quartznet(nww_handle* h) {
-    const auto blocks = nww_quartznet_blocks(h->cfg);
-    for (size_t i = 0; i < blocks.size(); ++i) {
-        const int Cin = blocks[i].cin, Cout = blocks[i].cout, k = blocks[i].k, Cp = qn_x3_cp(Cin);
-        const bool proj = Cin != Cout;
-        const std::string p = nww_quartznet_prefix(h->cfg) + "quartznet_blocks." + std::to_string(i);
-        auto D = [&](const std::string& key) -> const std::vector<float>& { return h->tensors[p + key].data; };
-        auto fold = [&](const std::string& bn, std::vector<double>& al, std::vector<double>& be) {
-            const auto &w = D(bn + ".weight"), &b = D(bn + ".bias"), &mu = D(bn + ".running_mean"), &var = D(bn + ".running_var");
-            al.resize(Cout); be.resize(Cout);
-            for (int c = 0; c < Cout; ++c) { al[c] = (double)w[c] / std::sqrt((double)var[c] + 1e-5); be[c] = (double)b[c] - (double)mu[c] * al[c]; }
-        };
-        const auto &dw = D(".depthwise_conv.weight"), &bdw = D(".depthwise_conv.bias"), &pw = D(".pointwise_conv.weight"), &bpw = D(".pointwise_conv.bias");
-        std::vector<double> al, be, alr, ber;
-        fold(".batch_norm", al, be);
-        if (proj) fold(".residual_connector.1", alr, ber);
-        HostTensor tpw, tres, tb, tdw, tam, tcat;
-        tpw.shape = {Cout, Cin}; tpw.data.resize((size_t)Cout * Cin);
-        tb.shape = {Cout}; tb.data.resize(Cout);
-        if (proj) { tres.shape = {Cout, Cin}; tres.data.resize((size_t)Cout * Cin); }
-        const bool cat = Cout % 32 == 0 && Cin <= QN_MAX_C && Cout <= QN_MAX_C;
-        const int Ktot = qn_x3_ktot(Cin, proj);
-        if (cat) { tcat.shape = {Cout, Ktot}; tcat.data.assign((size_t)Cout * Ktot, 0.0f); }
-        for (int co = 0; co < Cout; ++co) {
-            double bias = (double)bpw[co];
-            for (int ci = 0; ci < Cin; ++ci) {
-                const double w = (double)pw[(size_t)co * Cin + ci];
-                bias += w * (double)bdw[ci];
-                tpw.data[(size_t)co * Cin + ci] = (float)(al[co] * w);
-                if (cat) tcat.data[(size_t)co * Ktot + qn_x3_col(Cin, proj, 0, ci)] = tpw.data[(size_t)co * Cin + ci];
-            }
-            bias = al[co] * bias + be[co];
-            if (proj) {
-                const auto &rw = D(".residual_connector.0.weight"), &rb = D(".residual_connector.0.bias");
-                for (int ci = 0; ci < Cin; ++ci) {
-                    tres.data[(size_t)co * Cin + ci] = (float)(alr[co] * (double)rw[(size_t)co * Cin + ci]);
-                    if (cat) tcat.data[(size_t)co * Ktot + qn_x3_col(Cin, proj, 1, ci)] = tres.data[(size_t)co * Cin + ci];
-                }
-                bias += alr[co] * (double)rb[co] + ber[co];
-            }
-            tb.data[co] = (float)bias;
-        }
-        tdw.shape = {k, Cp}; tdw.data.assign((size_t)k * Cp, 0.0f);
-        double amax = 0.0;
-        for (int ci = 0; ci < Cin; ++ci) {
-            double sum = 0.0;
-            for (int j = 0; j < k; ++j) { tdw.data[(size_t)j * Cp + ci] = dw[(size_t)ci * k + j]; sum += std::fabs((double)dw[(size_t)ci * k + j]); }
-            amax = std::fmax(amax, sum);
-        }
-        tam.shape = {1}; tam.data = {(float)(amax * (1.0 + 1e-6))};        // rounded up: it is a bound
-        for (auto* t : {&tpw, &tres, &tb, &tdw, &tam, &tcat}) t->loaded = !t->data.empty();
-        h->tensors[p + ".qn.pw"] = tpw; h->tensors[p + ".qn.bias"] = tb; h->tensors[p + ".qn.dw_t"] = tdw; h->tensors[p + ".qn.amax"] = tam;
-        if (proj) h->tensors[p + ".qn.res"] = tres;
-        if (cat) h->tensors[p + ".qn.wcat"] = tcat;
-    }
-}
-
-// The raw-PCM frontend: each stage's BatchNorm folded into its conv ONCE in float64 (derived tensors "<conv>.raw.*"):
-//   w [k][Cin][Cout] = alpha weight, tap-major so that the lanes of conv1d_strided read consecutive floats; b [Cout] = beta (the convs
-//   have no bias of their own)
-void fold_raw_frontend(nww_handle* h) {
-    const nww_config& c = h->cfg;
-    for (int i = 0, Cin = 1; i < c.n_blocks; ++i) {
-        const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13;
-        const std::string conv = "model.frontend.conv_blocks." + std::to_string(3 * i), bn = "model.frontend.conv_blocks." + std::to_string(3 * i + 1);
-        const auto &w = h->tensors[conv + ".weight"].data, &g = h->tensors[bn + ".weight"].data, &b = h->tensors[bn + ".bias"].data,
-                   &mu = h->tensors[bn + ".running_mean"].data, &var = h->tensors[bn + ".running_var"].data;
-        HostTensor tw, tb;
-        tw.shape = {k, Cin, Cout}; tw.data.resize((size_t)k * Cin * Cout);
-        tb.shape = {Cout}; tb.data.resize(Cout);
-        for (int co = 0; co < Cout; ++co) {
-            const double al = (double)g[co] / std::sqrt((double)var[co] + 1e-5);
-            tb.data[co] = (float)((double)b[co] - (double)mu[co] * al);
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int j = 0; j < k; ++j) tw.data[((size_t)j * Cin + ci) * Cout + co] = (float)(al * (double)w[((size_t)co * Cin + ci) * k + j]);
-        }
-        tw.loaded = tb.loaded = true;
-        h->tensors[conv + ".raw.w"] = tw; h->tensors[conv + ".raw.b"] = tb;
-        if (i > 0 && Cout % 32 == 0 && Cin % 16 == 0) {      // raw_x3's operand: the same folded weights as [Cout][k Cin], tap-major columns
-            HostTensor tk;
-            tk.shape = {Cout, k * Cin}; tk.data.resize((size_t)Cout * k * Cin);
-            for (int co = 0; co < Cout; ++co)
-                for (int j = 0; j < k; ++j)
-                    for (int ci = 0; ci < Cin; ++ci) tk.data[((size_t)co * k + j) * Cin + ci] = tw.data[((size_t)j * Cin + ci) * Cout + co];
-            tk.loaded = true;
-            h->tensors[conv + ".raw.wk"] = tk;
-        }
-        Cin = Cout;
-    }
-}
-
-// every loaded tensor but the frontend's in one device arena, each 16-byte aligned
-int upload_weight_arena(nww_handle* h) {
-    size_t total = 0;
-    for (auto& kv : h->tensors) {
-        if (!kv.second.loaded || kv.first.rfind("frontend.", 0) == 0) continue;
-        kv.second.dev_off = total;
-        total += (kv.second.data.size() + 3) & ~(size_t)3;
-    }
-    HIP_TRY(h, hipMalloc(&h->d_weights, (total + 4) * sizeof(float)));
-    for (auto& kv : h->tensors) {
-        if (!kv.second.loaded || kv.first.rfind("frontend.", 0) == 0) continue;
-        HIP_TRY(h, hipMemcpy(h->d_weights + kv.second.dev_off, kv.second.data.data(), kv.second.data.size() * sizeof(float),
-                             hipMemcpyHostToDevice));
-    }
-    return NWW_OK;
-}
-
-int build_frontend_tables(nww_handle* h) {
-    std::vector<float> win, fb;
-    auto wi = h->tensors.find("frontend.window");
-    if (wi != h->tensors.end() && wi->second.loaded) win = wi->second.data; else fe_default_window(h->fe.win_length, win);
-    auto fi = h->tensors.find("frontend.mel_fb");
-    if (fi != h->tensors.end() && fi->second.loaded) fb = fi->second.data; else fe_default_melfb(h->fe, fb);
-    FeTables tb;
-    const std::string e = fe_build_tables(h->fe, win.data(), fb.data(), &tb);
-    if (!e.empty()) return fail(h, NWW_ERR_INVALID, "frontend tables: %s", e.c_str());
-    const size_t tbytes = (sizeof(FeTables) + 15) & ~(size_t)15;
-    HIP_TRY(h, hipMalloc(&h->d_tables, tbytes));
-    HIP_TRY(h, hipMemset(h->d_tables, 0, tbytes));
-    HIP_TRY(h, hipMemcpy(h->d_tables, &tb, sizeof(FeTables), hipMemcpyHostToDevice));
-    h->mel_max_taps = 0;
-    for (int j = 0; j < h->fe.n_mels; ++j) h->mel_max_taps = tb.mel_cnt[j] > h->mel_max_taps ? tb.mel_cnt[j] : h->mel_max_taps;
-    std::vector<Fe2MelPlan> plan(1);
-    const std::string e2 = fe2_build_mel_plan(h->fe, fb.data(), plan.data());
-    if (!e2.empty()) return fail(h, NWW_ERR_INVALID, "frontend mel plan: %s", e2.c_str());
-    HIP_TRY(h, hipMalloc(&h->d_melplan, sizeof(Fe2MelPlan)));
-    HIP_TRY(h, hipMemcpy(h->d_melplan, plan.data(), sizeof(Fe2MelPlan), hipMemcpyHostToDevice));
-    // (the DFT on the matrix pipe - frontend3 - was built in round 5, parity-green and slower: tools/ubench/fe3/)
-    return NWW_OK;
-}
-
 // ------------------------------------------------------------------------------------------ attention modules
+// The E-Branchformer's attention branch: the module reads LayerNorm(ln_w, ln_b)(h) - ln_name: that LayerNorm's module,
+// ".attn_branch_norm" - and writes buffer `out` WITHOUT the residual, which the merge takes
+struct AttnBranch { const float *ln_w = nullptr, *ln_b = nullptr; int out = BUF_NONE; const char* ln_name = ""; };
 // The Conformer's whole attention module (in_proj, per-head softmax(q k^T) v, out_proj, residual) in one launch per clip-resident
 // workgroup (attn_x3.hip) under the default arithmetic at the compiled shape; false: nothing planned (NWW_ATTN_FUSED = 0 among others)
-// ln_w / ln_b / out (the E-Branchformer's branch): LayerNorm of the rows in front, no residual, the result in buffer `out` beside h
-bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH, const float* ln_w = nullptr, const float* ln_b = nullptr, int out = -1) {
+// br (the E-Branchformer's branch): LayerNorm of the rows in front, no residual, the result in buffer br.out beside h
+bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH, const AttnBranch& br = AttnBranch{}) {
     if (!(nww_knobs().attn_fused && p.h->f16 && p.h->conv_products == 6 && attn_x3_supported(T, D, NH))) return false;
     const float *iw = p.W(q + ".attention.in_proj_weight"), *ib = p.W(q + ".attention.in_proj_bias");
     const float *ow = p.W(q + ".attention.out_proj.weight"), *ob = p.W(q + ".attention.out_proj.bias");
@@ -949,22 +613,17 @@ bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH,
         return worst;
     };
     const double lk = l1max(D) * ws_in * 1.02, lv = l1max(2 * D) * ws_in * 1.02;
-    void *packed = nullptr, *bc = nullptr;
-    if (!(ws_in > 0.0f && ws_out > 0.0f && lk < 1e30 && lv < 1e30 &&
-          hipMalloc(&packed, attn_x3_packed_bytes(D, NH)) == hipSuccess && hipMalloc(&bc, (size_t)D * sizeof(float)) == hipSuccess &&
-          launch_attn_x3_pack(iw, ib, ow, ob, packed, static_cast<float*>(bc), D, NH, ws_in, ws_out, p.h->own_stream) == hipSuccess)) {
-        if (packed) (void)hipFree(packed);
-        if (bc) (void)hipFree(bc);
-        return false;
-    }
-    p.h->packed_weights.push_back(packed);
-    p.h->packed_weights.push_back(bc);
+    if (!(ws_in > 0.0f && ws_out > 0.0f && lk < 1e30 && lv < 1e30)) return false;
+    PlanCtx::Packs pk(p);
+    void *packed = pk.alloc(attn_x3_packed_bytes(D, NH)), *bc = packed ? pk.alloc((size_t)D * sizeof(float)) : nullptr;      // one launch fills both
+    if (!bc || launch_attn_x3_pack(iw, ib, ow, ob, packed, static_cast<float*>(bc), D, NH, ws_in, ws_out, p.h->own_stream) != hipSuccess) return false;
+    pk.commit();
     const float cK = lk > 1e-30 ? (float)f16_pow2_floor(1.0 / lk) : 1.0f, cV = lv > 1e-30 ? (float)f16_pow2_floor(1.0 / lv) : 1.0f;
     const float w_un = 1.0f / ws_in, o_un = 1.0f / (ws_out * ws_in * cV), qs = 1.0f / std::sqrt((float)(D / NH));
-    if (ln_w) p.need(out, (size_t)T * D);
-    p.add("attn_x3:" + q + (ln_w ? ".attention (ln+in_proj+softmax(qk)v+out_proj) [f16x3]" : ".attention (in_proj+softmax(qk)v+out_proj+res) [f16x3]"), [=](Run& r) {
-        AttnArgs a{r.buf[hb], r.buf[ln_w ? out : hb], static_cast<const unsigned char*>(packed), static_cast<const float*>(bc), r.B, T, w_un, cK, cV, o_un, qs};
-        if (ln_w) { a.ln_w = ln_w; a.ln_b = ln_b; }
+    if (br.ln_w) p.need(br.out, (size_t)T * D);
+    p.add("attn_x3:" + q + (br.ln_w ? ".attention (ln+in_proj+softmax(qk)v+out_proj) [f16x3]" : ".attention (in_proj+softmax(qk)v+out_proj+res) [f16x3]"), [=](Run& r) {
+        AttnArgs a{r.buf[hb], r.buf[br.ln_w ? br.out : hb], static_cast<const unsigned char*>(packed), static_cast<const float*>(bc), r.B, T, w_un, cK, cV, o_un, qs};
+        if (br.ln_w) { a.ln_w = br.ln_w; a.ln_b = br.ln_b; }
         return launch_attn_x3(a, D, NH, r.cu_count, r.stream);
     });
     return true;
@@ -972,11 +631,10 @@ bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH,
 
 // h <- h + out_proj(softmax(q k^T / sqrt(dh)) v), q | k | v = in_proj(h), in three launches: block q's module `module` (".attention" /
 // ".self_attn"); buffers hb (h), big (q | k | v), t1 (the heads' outputs).  exact_sub: mha_h2's softmax form (launch_mha_h2)
-// ln_w / ln_b / out (the E-Branchformer's branch): q | k | v = in_proj(LayerNorm(h)) - the LayerNorm inside the short-K in_proj where that
-// kernel runs, else on its own into `out` - and out_proj WITHOUT the residual into buffer `out`
-// (ln_name: the LayerNorm's module, ".attn_branch_norm")
+// br (the E-Branchformer's branch): q | k | v = in_proj(LayerNorm(h)) - the LayerNorm inside the short-K in_proj where that
+// kernel runs, else on its own into br.out - and out_proj WITHOUT the residual into buffer br.out
 void add_attention_module(PlanCtx& p, const std::string& q, const char* module, int hb, int big, int t1, int T, int D, int NH, int exact_sub,
-                          const float* ln_w = nullptr, const float* ln_b = nullptr, int out = -1, const char* ln_name = "") {
+                          const AttnBranch& br = AttnBranch{}) {
     const std::string m = q + module;
     // in_proj writes q, k, v head-major when the matrix-core attention consumes them: every (clip, head) block is then
     // one contiguous run for its LDS-DMA
@@ -986,16 +644,18 @@ void add_attention_module(PlanCtx& p, const std::string& q, const char* module, 
     bool head_major = false;
     const std::string in_name = m + (want_hm ? ".in_proj(head-major)" : ".in_proj");
     int in_id = hb;
-    if (add_lin_x3(p, ln_w ? q + ln_name + "+" + std::string(module).substr(1) + (want_hm ? ".in_proj(head-major)" : ".in_proj") : in_name, hb, big, T, 3 * D, D, iw, ib, 0, 99, 1.f, ln_w, ln_b,
-                   want_hm ? T : 0, want_hm ? D / NH : 0)) {
+    LinOpts lo;
+    if (want_hm) { lo.qkv_T = T; lo.qkv_dh = D / NH; }
+    LinOpts lo_ln = lo; lo_ln.ln_w = br.ln_w; lo_ln.ln_b = br.ln_b;
+    if (add_lin_x3(p, br.ln_w ? q + br.ln_name + "+" + std::string(module).substr(1) + (want_hm ? ".in_proj(head-major)" : ".in_proj") : in_name, hb, big, T, 3 * D, D, iw, ib, lo_ln)) {
         head_major = want_hm;
     } else {
-        if (ln_w) {                                        // the LayerNorm on its own, into `out` (free until out_proj writes it)
-            p.need(out, (size_t)T * D);
-            p.add("layernorm:" + q + ln_name, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[out], ln_w, ln_b, r.B * T, D, ACT_NONE, r.stream); });
-            in_id = out;
+        if (br.ln_w) {                                        // the LayerNorm on its own, into `br.out` (free until out_proj writes it)
+            p.need(br.out, (size_t)T * D);
+            p.add("layernorm:" + q + br.ln_name, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[br.out], br.ln_w, br.ln_b, r.B * T, D, ACT_NONE, r.stream); });
+            in_id = br.out;
         }
-        if (add_lin_x3(p, in_name, in_id, big, T, 3 * D, D, iw, ib, 0, 99, 1.f, nullptr, nullptr, want_hm ? T : 0, want_hm ? D / NH : 0))
+        if (add_lin_x3(p, in_name, in_id, big, T, 3 * D, D, iw, ib, lo))
             head_major = want_hm;
         else
             add_gemm(p, m + ".in_proj", in_id, big, T, 3 * D, D, iw, ib, ACT_NONE);
@@ -1007,8 +667,137 @@ void add_attention_module(PlanCtx& p, const std::string& q, const char* module, 
         p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm); });
     else
         p.add("mha_core:" + q, [=](Run& r) { return launch_mha_core(r.buf[big], r.buf[t1], r.B, T, D, NH, r.stream); });
-    if (ln_w) add_linear(p, m + ".out_proj", t1, out, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"));
+    if (br.ln_w) add_linear(p, m + ".out_proj", t1, br.out, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"));
     else add_linear(p, m + ".out_proj+res", t1, hb, T, D, D, p.W(m + ".out_proj.weight"), p.W(m + ".out_proj.bias"), hb, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------ feed-forward and convolution modules
+// A feed-forward module's weights, the LayerNorm in front included (the Transformer's norm1)
+struct FfnWeights { const float *ln_w, *ln_b, *w1, *b1, *w2, *b2; };
+FfnWeights ffn_weights(PlanCtx& p, const std::string& ln, const std::string& m) {      // ln: the LayerNorm's module, m: the Linears' parent
+    return {p.W(ln + ".weight"), p.W(ln + ".bias"), p.W(m + ".linear1.weight"), p.W(m + ".linear1.bias"), p.W(m + ".linear2.weight"), p.W(m + ".linear2.bias")};
+}
+// NWW_ARITH_F16X3: both operands of both products are bounded whatever the residual stream holds - |LayerNorm(h)_i| <= sqrt(D) |w_i|
+// + |b_i|, |swish(v)| <= |v|, relu(v) <= |v| - so the scales need nothing but the weights
+struct FfnScales {
+    float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f;
+    bool ok() const { return fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f; }
+};
+FfnScales ffn_f16_scales(PlanCtx& p, const FfnWeights& w, int D) {
+    FfnScales s;
+    const double bx = f16_ln_bound(p.h, w.ln_w, w.ln_b, D);
+    const auto w1 = f16_fetch(p.h, w.w1, (size_t)4 * D * D), w2 = f16_fetch(p.h, w.w2, (size_t)4 * D * D), b1 = f16_fetch(p.h, w.b1, (size_t)4 * D);
+    const double bh = f16_layer_bound(w1, 4 * D, D, b1, true, b1, b1, false, bx);
+    s.fx = f16_scale(bx); s.fw1 = f16_wscale(w1); s.fh = f16_scale(bh); s.fw2 = f16_wscale(w2);
+    return s;
+}
+// The module in three launches: LayerNorm(hb) -> ln_out, linear1 + act -> big, hb <- hb + rscale linear2
+void add_ffn_unfused(PlanCtx& p, const FfnWeights& w, int act, float rscale, int hb, int ln_out, int big, int T, int D,
+                     const std::string& ln_name, const std::string& l1_name, const std::string& l2_name) {
+    p.add("layernorm:" + ln_name, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[ln_out], w.ln_w, w.ln_b, r.B * T, D, ACT_NONE, r.stream); });
+    add_gemm(p, l1_name, ln_out, big, T, 4 * D, D, w.w1, w.b1, act);
+    GemmOpts res; res.res_id = hb; res.rscale = rscale;
+    add_gemm(p, l2_name, big, hb, T, D, 4 * D, w.w2, w.b2, ACT_NONE, res);
+}
+
+// round 6: the row-local Linears next to a feed-forward module run INSIDE its launch (FfnArgs::px: input_proj in front of the first
+// block's ff1, conv2 + residual in front of every ff2), and the last block's LayerNorm + time average behind its ff2
+// (FfnArgs::msum); NWW_FFN_FUSED = 0 and the other arithmetics keep the separate launches.
+// kind: 0 none, 1 input_proj (x = the head input), 2 conv_module.conv2 + residual (x = the depthwise output in t3); name: the
+// Linear's step when it is planned on its own because the form planned does not take it
+struct FfnPro { int kind = 0; std::string name; const float *w = nullptr, *b = nullptr; int k = 0; };
+// the block's final LayerNorm + mean over time (block: its name, for the step that finishes the mean)
+struct FfnEpi { bool want = false; std::string block; const float *ln_w = nullptr, *ln_b = nullptr; };
+// The pre-norm module (swish) hb <- hb + rscale ffn(hb) in block-scope buffers hb, t1, t3, big; `name`: the module's.  A step takes one
+// of four forms, richest first: prologue + epilogue, prologue, plain ffn_x3, unfused (LayerNorm + two GEMMs).  Returns whether the
+// epilogue was fused.
+bool add_ffn(PlanCtx& p, const std::string& name, const FfnWeights& w, float rscale, int hb, int t1, int t3, int big, int T, int D,
+             const FfnPro& pro = FfnPro{}, const FfnEpi& epi = FfnEpi{}) {
+    struct Form { int pro = 0; bool epi = false, fused = false, h2 = false; FfnScales s; float pws = 0.0f, mscale = 0.0f; } f;
+    // the richest feasible form with at most the requested prologue / epilogue: plan-time scales only, nothing allocated or launched.
+    // LayerNorm + linear1 + swish + linear2 + residual in one kernel (ffn_x3.hip); same arithmetic switch as the split-operand GEMMs
+    // it replaces
+    if (nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16)) {
+        if (p.h->f16) f.s = ffn_f16_scales(p, w, D);
+        f.h2 = f.s.ok();
+        f.fused = ffn_x3_supported(D, f.h2);
+    }
+    if (f.fused && f.h2) {                                 // the prologue / epilogue instances: two-term form only
+        // the prologue Linear's weights (two binary16 terms; its input rows are scaled per row in the kernel)
+        if (pro.kind && ffn_x3_pro_supported(D, pro.k) && pro.b) {
+            f.pws = f16_wscale(f16_fetch(p.h, pro.w, (size_t)D * pro.k));
+            if (f.pws > 0.0f) f.pro = pro.kind;
+        }
+        if (epi.want && f.pro == pro.kind && ffn_x3_epi_supported(D, T)) {
+            f.mscale = f16_mean_scale(f16_ln_bound(p.h, epi.ln_w, epi.ln_b, D));
+            f.epi = f.mscale > 0.0f;
+        }
+    }
+    const char* res = rscale == 0.5f ? "0.5res" : "res";
+    // allocates, packs and plans form f; false (an allocation or a pack failed): nothing planned, nothing kept
+    auto build = [&]() -> bool {
+        if (!f.fused) {
+            add_ffn_unfused(p, w, ACT_SILU, rscale, hb, t1, big, T, D, name, name + ".linear1+swish", name + ".linear2+" + res);
+            return true;
+        }
+        const int kind = f.pro, pk = kind ? pro.k : 0;
+        PlanCtx::Packs packs(p);
+        const void* ppk = !kind ? nullptr : packs.pack(ffn_x3_pro_tile_bytes(pk) * ((D + 31) / 32), [&](void* d) { return launch_ffn_x3_pro_pack(pro.w, d, D, pk, f.pws, p.h->own_stream); });
+        if (kind && !ppk) return false;
+        const void* packed = packs.pack(ffn_x3_packed_bytes(D), [&](void* d) {
+            return launch_ffn_x3_pack(w.w1, w.b1, w.w2, d, D, p.h->own_stream, f.h2 ? f.s.fw1 : 0.0f, f.h2 ? f.s.fw2 : 0.0f, kind ? 1 : 0);
+        });
+        if (!packed) return false;
+        packs.commit();
+        const float *lw = w.ln_w, *lb = w.ln_b, *b2 = w.b2, *pbias = kind ? pro.b : nullptr, *l2w = epi.ln_w, *l2b = epi.ln_b;
+        const float p_un = kind ? 1.0f / f.pws : 1.0f, mscale = f.mscale;
+        const bool fepi = f.epi, h2 = f.h2;
+        const FfnScales s = f.s;                           // (the launches keep copies: f changes when a build fails)
+        // the epilogue's exact partial sums: per 32-row tile two segments x two planes of D floats (the idle wide scratch buffer)
+        if (fepi) p.need(big, (size_t)((T + 31) / 32 + 1) * 4 * D + (size_t)16 * D);
+        const std::string what = std::string(kind == 1 ? "input_proj+" : kind == 2 ? "conv2(pw)+res+" : "") + "ln+linear1+swish+linear2+" + res + (fepi ? "+layernorm+time sums" : "");
+        p.add("ffn_x3:" + name + " (" + what + ")" + (h2 ? " [f16x3]" : ""), [=](Run& r) {
+            FfnArgs a{r.buf[hb], lw, lb, static_cast<const unsigned char*>(packed), b2, r.B * T, rscale};
+            if (h2) { a.h2_x = s.fx; a.h2_w1 = s.fw1; a.h2_h = s.fh; a.h2_w2 = s.fw2; }
+            if (kind) {
+                a.px = kind == 1 ? r.x : r.buf[t3]; a.ppacked = static_cast<const unsigned char*>(ppk); a.pb = pbias;
+                a.pro_k = pk; a.pro_res = kind == 2 ? 1 : 0; a.p_un = p_un;
+            }
+            if (fepi) { a.ln2_w = l2w; a.ln2_b = l2b; a.msum = r.buf[big]; a.T = T; a.m_scale = mscale; }
+            return launch_ffn_x3(a, D, r.stream);
+        });
+        if (fepi)
+            p.add("mean_finish:" + epi.block + " (time average of the exact tile sums)", [=](Run& r) {
+                return launch_ffn_x3_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, mscale, r.stream);
+            });
+        return true;
+    };
+    auto separate_pro = [&] { add_linear(p, pro.name, pro.kind == 1 ? BUF_X : t3, hb, T, D, pro.k, pro.w, pro.b, pro.kind == 2 ? hb : BUF_NONE); };
+    // the richest form that can be built, one form down after each failed build
+    if (pro.kind && !f.pro) separate_pro();
+    while (!build()) {
+        if (f.epi) f.epi = false;
+        else if (f.pro) { f.pro = 0; separate_pro(); }
+        else f.fused = false;
+    }
+    return f.epi;
+}
+
+// The ConvolutionModule `m` up to its depthwise stage: LayerNorm + conv1 + GLU (hb -> t1), depthwise + BN + swish (-> t3)
+// (the whole module as ONE clip-resident launch was built and measured: bit-identical, 0.27 ms against 0.25 for the three launches
+// below - tools/ubench/convmod_x3.hip)
+void add_conv_module_front(PlanCtx& p, const std::string& m, int hb, int t1, int t3, int big, int T, int D) {
+    const float *lw = p.W(m + ".layer_norm.weight"), *lb = p.W(m + ".layer_norm.bias");
+    const float *dw = p.W(m + ".depthwise_conv.weight"), *db = p.W(m + ".depthwise_conv.bias");
+    const float *ba = p.W(m + ".batch_norm.alpha"), *bb = p.W(m + ".batch_norm.beta");
+    // LayerNorm + pointwise conv1 + GLU in one launch (lin_x3.hip), else the three separate ones
+    LinOpts glu; glu.epi = LIN_GLU; glu.ln_w = lw; glu.ln_b = lb;
+    if (!add_lin_x3(p, m + ".layer_norm+conv1(pw)+glu", hb, t1, T, D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), glu)) {
+        p.add("layernorm:" + m, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
+        add_gemm(p, m + ".conv1(pw)", t1, big, T, 2 * D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), ACT_NONE);
+        p.add("glu:" + m, [=](Run& r) { return launch_glu(r.buf[big], r.buf[t1], r.B * T, D, r.stream); });
+    }
+    p.add("dwconv1d+bn+swish:" + m, [=](Run& r) { return launch_dwconv1d_bn_swish(r.buf[t1], dw, db, ba, bb, r.buf[t3], r.B, T, D, 31, r.stream); });
 }
 
 // ------------------------------------------------------------------------------------------ per-head plans
@@ -1017,7 +806,8 @@ void add_attention_module(PlanCtx& p, const std::string& q, const char* module, 
 int plan_dnn(PlanCtx& p) {                          // Net: architectures.py:110-126
     const nww_config& c = p.h->cfg;
     const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, nb = c.n_blocks, act = c.activation;
-    add_gemm(p, "layer1", -1, 0, 1, L, T * F, p.W("model.layer1.weight"), p.W("model.layer1.bias"), ACT_NONE, nullptr, nullptr, 99, 1.f, nullptr, false, true, F16_FEATURES, true);
+    GemmOpts l1; l1.feeds_ln = true; l1.a_range = F16_FEATURES; l1.a_bound_assumed = true;
+    add_gemm(p, "layer1", BUF_X, 0, 1, L, T * F, p.W("model.layer1.weight"), p.W("model.layer1.bias"), ACT_NONE, l1);
     // Everything behind layer1 runs inside the tail's launch (layers.hip: TailArgs::ln0_w) when the widths allow: LayerNorm1 on
     // layer1's split-K partials, the blocks' Linear + LayerNorm, last_layer, classifier - two launches per forward instead of six
     if (nww_knobs().tail && L <= 256 && nb <= 4 && tail_supported(L, c.embedding_dim)) {
@@ -1063,17 +853,17 @@ int plan_cnn(PlanCtx& p) {                          // CNNModel: architectures.p
     h->trunk_blocked = (h->conv_products == 6 || h->conv_products == 9) && trunk_b_pick_strips(T, F) > 0 &&
                        (W2 % 4) == 0 && ((H2 * W2) % 4) == 0 && ((32 * H2 * W2) % 32) == 0;
     F16Range a2_bound;                    // NWW_ARITH_F16X3: the range of the trunk's output, fc1's operand
-    const bool fused = add_trunk(p, "conv1+pool+conv2+pool", -1, 1, 16, 32, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr,
-                                 p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, &h->trunk_blocked,
-                                 F16_FEATURES, &a2_bound);
+    TrunkOpts to; to.out_blocked = &h->trunk_blocked; to.in_range = F16_FEATURES; to.out_range = &a2_bound;
+    const bool fused = add_trunk(p, "conv1+pool+conv2+pool", BUF_X, 1, 16, 32, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr,
+                                 p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, to);
     if (!fused) {
         h->trunk_blocked = false;
-        add_conv(p, "conv1", -1, 0, 1, 16, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr, act, 1);
+        add_conv(p, "conv1", BUF_X, 0, 1, 16, T, F, p.W("model.conv1.weight"), p.W("model.conv1.bias"), nullptr, nullptr, act, 1);
         add_conv(p, "conv2", 0, 1, 16, 32, T / 2, F / 2, p.W("model.conv2.weight"), p.W("model.conv2.bias"), nullptr, nullptr, act, 1);
     }
     // fc1's split-K partials are reduced by the classifier tail itself when that is the fused kernel
-    add_gemm(p, "fc1", 1, 0, 1, 128, 32 * H2 * W2, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, nullptr, nullptr, 99, 1.f,
-             &h->trunk_blocked, nww_knobs().tail && tail_supported(128, c.embedding_dim), false, a2_bound);
+    GemmOpts fc1; fc1.a_blocked_inout = &h->trunk_blocked; fc1.feeds_tail = nww_knobs().tail && tail_supported(128, c.embedding_dim); fc1.a_range = a2_bound;
+    add_gemm(p, "fc1", 1, 0, 1, 128, 32 * H2 * W2, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, fc1);
     set_tail(p, "fc2", 0, 128, p.W("model.fc2.weight"), p.W("model.fc2.bias"));
     return NWW_OK;
 }
@@ -1086,10 +876,10 @@ bool plan_e2e_dnn_transposed(PlanCtx& p) {
     if (!e2e_transposed_ok(p, Hh, Ww)) return false;
     const size_t steps_before = h->plan.size();
     const int Ht = Ww, Wt = Hh;       // the plane the kernels see: (frames, n_mels)
-    float* wt = nullptr;
     const int nf[3] = {16, 32 * 16, 64 * 32};
-    if (hipMalloc(&wt, (size_t)(nf[0] + nf[1] + nf[2]) * 9 * sizeof(float)) != hipSuccess) return false;
-    h->packed_weights.push_back(wt);
+    PlanCtx::Packs pk(p);                         // the three transposed weights in one allocation, kept only with the plan
+    float* wt = static_cast<float*>(pk.alloc((size_t)(nf[0] + nf[1] + nf[2]) * 9 * sizeof(float)));
+    if (!wt) return false;
     float* wts[3] = {wt, wt + (size_t)nf[0] * 9, wt + (size_t)(nf[0] + nf[1]) * 9};
     for (int i = 0; i < 3; ++i)
         if (launch_transpose3x3(p.W("model.conv_block." + std::to_string(4 * i) + ".weight"), wts[i], nf[i], h->own_stream) != hipSuccess)
@@ -1105,18 +895,18 @@ bool plan_e2e_dnn_transposed(PlanCtx& p) {
     const int h3 = Ht / 4, w3 = Wt / 4;           // (25, 16): AdaptiveAvgPool2d((1,4))'s windows run along the FRAMES, here y
     const int sw4 = h3 / 4, kw4 = h3 - 3 * sw4;
     F16Range tbound;                              // NWW_ARITH_F16X3: the range of the trunk's output, the third conv's operand
-    const bool ok = add_trunk(p, "conv_block.0-7 (transposed plane)", -1, 1, 16, 32, Ht, Wt, wts[0], p.W("model.conv_block.0.bias"),
-                              p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), wts[1], p.W("model.conv_block.4.bias"),
-                              p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, nullptr, F16_FEATURES, &tbound) &&
-                    h->plan.back().name.rfind("trunk_x3:", 0) == 0 && h3 >= 4 &&
-                    add_conv_mfma(p, "model.conv_block.8 (transposed plane)", 1, 0, 32, 64, h3, w3, wts[2], p.W("model.conv_block.8.bias"),
-                                  p.W("model.conv_block.9.alpha"), p.W("model.conv_block.9.beta"), act, 0, kw4, sw4, 4, nullptr, 1, nullptr, tbound);
-    if (!ok) {
-        h->plan.resize(steps_before);
-        h->e2e_transposed = false;
-        return false;
-    }
-    add_gemm(p, "fc1+bn1", 0, 1, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, p.W("model.bn1.alpha"), p.W("model.bn1.beta"));
+    TrunkOpts to; to.in_range = F16_FEATURES; to.out_range = &tbound;
+    auto undo = [&] { h->plan.resize(steps_before); h->e2e_transposed = false; return false; };
+    if (!(add_trunk(p, "conv_block.0-7 (transposed plane)", BUF_X, 1, 16, 32, Ht, Wt, wts[0], p.W("model.conv_block.0.bias"),
+                    p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), wts[1], p.W("model.conv_block.4.bias"),
+                    p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, to) &&
+          h->plan.back().name.rfind("trunk_x3:", 0) == 0 && h3 >= 4)) return undo();
+    ConvMfmaOpts co; co.avg_kw = kw4; co.avg_sw = sw4; co.avg_ow = 4; co.avg_y = 1; co.in_range = tbound;
+    if (!add_conv_mfma(p, "model.conv_block.8 (transposed plane)", 1, 0, 32, 64, h3, w3, wts[2], p.W("model.conv_block.8.bias"),
+                       p.W("model.conv_block.9.alpha"), p.W("model.conv_block.9.beta"), act, 0, co)) return undo();
+    pk.commit();
+    GemmOpts bn1; bn1.alpha = p.W("model.bn1.alpha"); bn1.beta = p.W("model.bn1.beta");
+    add_gemm(p, "fc1+bn1", 0, 1, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, bn1);
     set_tail(p, "out", 1, 128, p.W("model.out.weight"), p.W("model.out.bias"));
     return true;
 }
@@ -1126,13 +916,14 @@ int plan_e2e_dnn(PlanCtx& p) {                      // E2E_MelSpectrogram_CNN bo
     nww_handle* h = p.h;
     const int Hh = h->cfg.in_rows, Ww = h->cfg.in_cols, act = h->cfg.activation;     // (n_mels, frames)
     const int ch[3] = {16, 32, 64};
-    int cin = 1, hh = Hh, ww = Ww, cur = -1;
+    int cin = 1, hh = Hh, ww = Ww, cur = BUF_X;
     int first = 0;
     bool fused_pool = false;
     F16Range cbound;                                  // NWW_ARITH_F16X3: range of the current stage's input (empty: unknown)
-    if (add_trunk(p, "conv_block.0-7", -1, 1, 16, 32, Hh, Ww, p.W("model.conv_block.0.weight"), p.W("model.conv_block.0.bias"),
+    TrunkOpts to; to.in_range = F16_FEATURES; to.out_range = &cbound;
+    if (add_trunk(p, "conv_block.0-7", BUF_X, 1, 16, 32, Hh, Ww, p.W("model.conv_block.0.weight"), p.W("model.conv_block.0.bias"),
                   p.W("model.conv_block.1.alpha"), p.W("model.conv_block.1.beta"), p.W("model.conv_block.4.weight"),
-                  p.W("model.conv_block.4.bias"), p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, nullptr, F16_FEATURES, &cbound)) {
+                  p.W("model.conv_block.4.bias"), p.W("model.conv_block.5.alpha"), p.W("model.conv_block.5.beta"), act, to)) {
         first = 2; cin = 32; hh = Hh / 4; ww = Ww / 4; cur = 1;
     }
     for (int i = first; i < 3; ++i) {
@@ -1140,16 +931,15 @@ int plan_e2e_dnn(PlanCtx& p) {                      // E2E_MelSpectrogram_CNN bo
         const int out = (i % 2 == 0) ? 0 : 1;
         if (i == 2 && ww >= 4) {
             // conv3 + AdaptiveAvgPool2d((1,4)) in its exported AvgPool2d form, fused when the MFMA kernel applies
-            const int sw4 = ww / 4, kw4 = ww - 3 * sw4;
-            if (add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 0, kw4, sw4, 4,
-                              nullptr, 0, nullptr, cbound)) {
+            ConvMfmaOpts po; po.avg_sw = ww / 4; po.avg_kw = ww - 3 * po.avg_sw; po.avg_ow = 4; po.in_range = cbound;
+            if (add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 0, po)) {
                 fused_pool = true; cin = ch[i]; cur = out;
                 continue;
             }
         }
         F16Range nb;
-        if (!add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2,
-                           0, 0, 0, nullptr, 0, nullptr, cbound, &nb))
+        ConvMfmaOpts co; co.in_range = cbound; co.out_range = &nb;
+        if (!add_conv_mfma(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2, co))
             add_conv(p, cw, cur, out, cin, ch[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, i < 2);
         cbound = nb;
         if (i < 2) { hh /= 2; ww /= 2; }
@@ -1166,7 +956,8 @@ int plan_e2e_dnn(PlanCtx& p) {                      // E2E_MelSpectrogram_CNN bo
         fc_in = pout;
     }
     const int fc_out = fc_in ^ 1;
-    add_gemm(p, "fc1+bn1", fc_in, fc_out, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, p.W("model.bn1.alpha"), p.W("model.bn1.beta"));
+    GemmOpts bn1; bn1.alpha = p.W("model.bn1.alpha"); bn1.beta = p.W("model.bn1.beta");
+    add_gemm(p, "fc1+bn1", fc_in, fc_out, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, bn1);
     set_tail(p, "out", fc_out, 128, p.W("model.out.weight"), p.W("model.out.bias"));
     return NWW_OK;
 }
@@ -1175,15 +966,16 @@ int plan_crnn(PlanCtx& p) {                         // CRNNModel: architectures.
     nww_handle* h = p.h;
     const nww_config& c = h->cfg;
     const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, nb = c.n_blocks, act = c.activation;
-    int cin = 1, hh = T, ww = F, cur = -1;
+    int cin = 1, hh = T, ww = F, cur = BUF_X;
     int first = 0;
     bool seq_written = false;
     F16Range cbound;                                  // NWW_ARITH_F16X3: range of the current stage's input (empty: unknown)
     const size_t steps_before = h->plan.size();
+    TrunkOpts to; to.in_range = F16_FEATURES; to.out_range = &cbound;
     if (c.n_crnn_channels >= 2 && c.crnn_channels[0] == 16 && c.crnn_channels[1] == 32 &&
-        add_trunk(p, "cnn.0-7", -1, 1, 16, 32, T, F, p.W("model.cnn.0.weight"), p.W("model.cnn.0.bias"), p.W("model.cnn.1.alpha"),
+        add_trunk(p, "cnn.0-7", BUF_X, 1, 16, 32, T, F, p.W("model.cnn.0.weight"), p.W("model.cnn.0.bias"), p.W("model.cnn.1.alpha"),
                   p.W("model.cnn.1.beta"), p.W("model.cnn.4.weight"), p.W("model.cnn.4.bias"), p.W("model.cnn.5.alpha"),
-                  p.W("model.cnn.5.beta"), act, nullptr, F16_FEATURES, &cbound)) {
+                  p.W("model.cnn.5.beta"), act, to)) {
         first = 2; cin = 32; hh = T / 4; ww = F / 4; cur = 1;
     }
     for (int i = first; i < c.n_crnn_channels; ++i) {
@@ -1194,7 +986,9 @@ int plan_crnn(PlanCtx& p) {                         // CRNNModel: architectures.
         // the stage right behind a fused split-operand trunk may take its input from the streaming rings (nww_stream.hip)
         bool ring = i == 2 && first == 2 && h->plan.size() == steps_before + 1 && h->plan.back().name.rfind("trunk_x3:", 0) == 0 && ((F / 4) % 4) == 0;
         F16Range nbr;
-        const bool mf = add_conv_mfma(p, cw, cur, out, cin, c.crnn_channels[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 1, 0, 0, 0, &seq, 0, &ring, cbound, &nbr, 2);      // (scratch: the recurrent layers' xg buffer, idle until they run)
+        ConvMfmaOpts co; co.seq_inout = &seq; co.ring_in = &ring; co.in_range = cbound; co.out_range = &nbr;
+        co.scratch_id = 2;                                // the recurrent layers' xg buffer, idle until they run
+        const bool mf = add_conv_mfma(p, cw, cur, out, cin, c.crnn_channels[i], hh, ww, p.W(cw + ".weight"), p.W(cw + ".bias"), p.W(bnp + ".alpha"), p.W(bnp + ".beta"), act, 1, co);
         cbound = nbr;
         if (!mf) {
             ring = false;
@@ -1222,7 +1016,7 @@ int plan_crnn(PlanCtx& p) {                         // CRNNModel: architectures.
 
 int plan_gru(PlanCtx& p) {                          // GRUModel: architectures.py:129-145
     const nww_config& c = p.h->cfg;
-    add_bigru_last(p, "model.gru", -1, c.in_rows, c.in_cols, c.layer_dim, c.n_blocks, 2, 0, 1, 4);
+    add_bigru_last(p, "model.gru", BUF_X, c.in_rows, c.in_cols, c.layer_dim, c.n_blocks, 2, 0, 1, 4);
     set_tail(p, "fc", 4, 2 * c.layer_dim, p.W("model.fc.weight"), p.W("model.fc.bias"));
     return NWW_OK;
 }
@@ -1296,7 +1090,6 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
         const int max_grid = p.h->cu_count;
         // the convolution from split operands on the bf16 matrix cores (trunk_b.hip) under the handle's arithmetic switch;
         // NWW_BC_FRONT = 2 keeps the float32-MFMA kernel
-        void* fpack = nullptr;
         int fprod = p.h->conv_products;
         // under NWW_ARITH_F16X3 (BN present): two binary16 terms per operand, features clamped to +-NWW_F16_FEATURE_BOUND as in the
         // CNN trunk
@@ -1305,23 +1098,18 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
             fin = f16_scale(F16_FEATURES.bound); fws = f16_wscale(f16_fetch(p.h, w0, 32 * 9));
             if (fin > 0.0f && fws > 0.0f) fprod = 3;
         }
-        if ((fprod == 6 || fprod == 9 || fprod == 3) && bc_front != 2 && bc_front_b_rows(T, F, 2) > 0 &&
-            hipMalloc(&fpack, bc_front_b_packed_bytes()) == hipSuccess) {
-            const hipError_t pe = fprod == 3 ? launch_bc_front_b_pack_f16(w0, static_cast<unsigned char*>(fpack), fws, p.h->own_stream)
-                                             : launch_bc_front_b_pack(w0, static_cast<unsigned char*>(fpack), p.h->own_stream);
-            if (pe == hipSuccess) p.h->packed_weights.push_back(fpack);
-            else { (void)hipFree(fpack); fpack = nullptr; }
-        }
+        void* fpack = nullptr;
+        if ((fprod == 6 || fprod == 9 || fprod == 3) && bc_front != 2 && bc_front_b_rows(T, F, 2) > 0)
+            fpack = p.pack_one(bc_front_b_packed_bytes(), [&](void* d) {
+                return fprod == 3 ? launch_bc_front_b_pack_f16(w0, static_cast<unsigned char*>(d), fws, p.h->own_stream)
+                                  : launch_bc_front_b_pack(w0, static_cast<unsigned char*>(d), p.h->own_stream);
+            });
         const float f_un = 1.0f / (fin > 0.0f ? fin * fws : 1.0f);
         // all folded-BN factors non-negative (the usual case: gamma > 0): max-pool commutes with BN + ReLU through the maximum alone
-        int bn_pos = 0;
-        if (a0) {
-            bn_pos = 1;
-            for (float v : f16_fetch(p.h, a0, 32)) if (!(v >= 0.0f)) bn_pos = 0;
-        }
+        const int bn_pos = a0 && f16_all_nonneg(p.h, a0, 32);
         if (fpack) p.h->clamps_features = true;
         p.add(std::string(fpack ? "conv1_dw_x3" : "conv1_dw_mfma") + ":init_conv + block1.depthwise (nhwc" + (act_f16 ? ", f16 out)" : act_bf16 ? ", bf16 out)" : ")") + (fpack && fprod == 3 ? " [f16x3]" : ""), [=](Run& r) {
-            Conv1DwArgs a{src(r, -1), w0, nullptr, a0, b0, dwt1, r.buf[2], r.buf[3], r.B, T, F, act, 2, 2};
+            Conv1DwArgs a{r.x, w0, nullptr, a0, b0, dwt1, r.buf[2], r.buf[3], r.B, T, F, act, 2, 2};
             a.bf16_out = act16; a.d_scale = s_d[1]; a.xs_scale = s_h[0];
             if (fpack) {
                 a.wpack = static_cast<const unsigned char*>(fpack);
@@ -1335,11 +1123,11 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
         p.need(0, (size_t)32 * (T / 2) * (F / 2));
         const int max_grid = p.h->cu_count;
         p.add("conv1_mfma:init_conv(nhwc)", [=](Run& r) {
-            Conv1NhwcArgs a{src(r, -1), w0, nullptr, a0, b0, r.buf[0], r.B, T, F, act};
+            Conv1NhwcArgs a{r.x, w0, nullptr, a0, b0, r.buf[0], r.B, T, F, act};
             return launch_conv1_pool_nhwc_mfma(a, max_grid, r.stream);
         });
     } else {
-        add_conv(p, "init_conv(nhwc)", -1, 0, 1, 32, T, F, p.W("model.init_conv.0.weight"), nullptr, p.W("model.init_conv.1.alpha"), p.W("model.init_conv.1.beta"), act, 1, 1);
+        add_conv(p, "init_conv(nhwc)", BUF_X, 0, 1, 32, T, F, p.W("model.init_conv.0.weight"), nullptr, p.W("model.init_conv.1.alpha"), p.W("model.init_conv.1.beta"), act, 1, 1);
     }
     int hh = T / 2, ww = F / 2, cur = 0;
     bool mean_fused = false;
@@ -1368,7 +1156,6 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
             const int rows = ho * wo;
             p.need(outb, (size_t)rows * co);
             // both products from split operands on the bf16 matrix cores (dual_x3.hip) under the same arithmetic switch
-            void* packed = nullptr;
             // float32 activations under NWW_ARITH_F16X3: two binary16 terms per operand, the activation rows scaled per pixel in
             // the kernel (DualArgs::h2) - no tensor bound needed
             const bool dual_h2 = p.h->f16 && !act_bf16;
@@ -1381,10 +1168,8 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
                 dps[i].pw_un = 1.0f / dps[i].pw_ws; dps[i].sc_un = 1.0f / dps[i].sc_ws;
             }
             const int terms = act_f16 || dual_h2 || will_chain ? 2 : 3;
-            if (p.h->conv_products == 6 && dual_x3_supported(ci, co) &&
-                hipMalloc(&packed, dual_x3_packed_bytes(ci, co, terms)) == hipSuccess) {
-                if (launch_dual_x3_pack(wpw, wsc, a1, b1, as, bs, packed, ci, co, p.h->own_stream, terms, dps[i]) == hipSuccess) {
-                    p.h->packed_weights.push_back(packed);
+            if (p.h->conv_products == 6 && dual_x3_supported(ci, co)) {
+                if (void* packed = p.pack_one(dual_x3_packed_bytes(ci, co, terms), [&](void* d) { return launch_dual_x3_pack(wpw, wsc, a1, b1, as, bs, d, ci, co, p.h->own_stream, terms, dps[i]); })) {
                     // when the block input is in HBM (every block but the one whose depthwise ran inside the fused front kernel) the
                     // shortcut rows are gathered from it and the depthwise kernel planned just above writes no copy of them
                     const bool gather = !have_dx;
@@ -1427,7 +1212,6 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
                     hh = ho; ww = wo; cur = outb; have_dx = false; dwb = 2; xsb = 3;
                     continue;
                 }
-                (void)hipFree(packed);
             }
             if (act_bf16) return fail(h, NWW_ERR_UNSUPPORTED, "act_dtype = bf16 / f16: block %d has no split-operand kernel (channels %d -> %d)", i, ci, co);
             p.add("gemm2:" + q + ".pointwise+bn+act + shortcut+bn", [=](Run& r) {
@@ -1461,127 +1245,20 @@ int plan_conformer(PlanCtx& p) {                    // ConformerModel: architect
     bool last_fused = false;
     p.need(t1, (size_t)T * D); p.need(t3, (size_t)T * D);
     p.need(hb, (size_t)T * D);
-    // round 6: the row-local Linears next to a feed-forward module run INSIDE its launch (FfnArgs::px: input_proj in front of the first
-    // block's ff1, conv2 + residual in front of every ff2), and the last block's LayerNorm + time average behind its ff2
-    // (FfnArgs::msum); NWW_FFN_FUSED = 0 and the other arithmetics keep the separate launches.
-    // A feed-forward step takes one of four forms, richest first: prologue + epilogue, prologue, plain ffn_x3, unfused (LayerNorm +
-    // two GEMMs).  pro: 0 none, 1 input_proj (x = the head input), 2 conv_module.conv2 + residual (x = the depthwise output in t3);
-    // epi: the block's final LayerNorm + mean over time.
-    struct FfnForm {
-        int pro = 0;
-        bool epi = false, fused = false, h2 = false;
-        float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f, pws = 0.0f, mscale = 0.0f;
-    };
     for (int i = 0; i < nb; ++i) {
-        const std::string q = "model.conformer_blocks." + std::to_string(i);
-        const float* pro_w[3] = {nullptr, p.W("model.input_proj.weight"), p.W(q + ".conv_module.conv2.weight")};
-        const float* pro_b[3] = {nullptr, p.W("model.input_proj.bias"), p.W(q + ".conv_module.conv2.bias")};
-        const int pro_k[3] = {0, F, D};
+        const std::string q = "model.conformer_blocks." + std::to_string(i), m = q + ".conv_module";
         const float *l2w = p.W(q + ".layer_norm.weight"), *l2b = p.W(q + ".layer_norm.bias");
-        // the richest feasible form with at most the requested prologue / epilogue: plan-time scales only, nothing allocated or launched
-        auto ffn_decide = [&](const std::string& ff, int pro, bool epi) {
-            FfnForm f;
-            // LayerNorm + linear1 + swish + linear2 + half-step residual in one kernel (ffn_x3.hip); same arithmetic
-            // switch as the split-operand GEMMs it replaces
-            if (!(nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16))) return f;
-            // NWW_ARITH_F16X3: both operands of both products are bounded whatever the residual stream holds -
-            // |LayerNorm(h)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v| - so the scales need nothing but the weights
-            if (p.h->f16) {
-                const double bx = f16_ln_bound(p.h, p.W(q + ff + ".layer_norm.weight"), p.W(q + ff + ".layer_norm.bias"), D);
-                const auto w1 = f16_fetch(p.h, p.W(q + ff + ".linear1.weight"), (size_t)4 * D * D), w2 = f16_fetch(p.h, p.W(q + ff + ".linear2.weight"), (size_t)4 * D * D);
-                const auto b1 = f16_fetch(p.h, p.W(q + ff + ".linear1.bias"), (size_t)4 * D);
-                const double bh = f16_layer_bound(w1, 4 * D, D, b1, true, b1, b1, false, bx);
-                f.fx = f16_scale(bx); f.fw1 = f16_wscale(w1); f.fh = f16_scale(bh); f.fw2 = f16_wscale(w2);
-            }
-            f.h2 = f.fx > 0.0f && f.fw1 > 0.0f && f.fh > 0.0f && f.fw2 > 0.0f;
-            f.fused = ffn_x3_supported(D, f.h2);
-            if (!f.fused || !f.h2) return f;                   // the prologue / epilogue instances: two-term form only
-            // the prologue Linear's weights (two binary16 terms; its input rows are scaled per row in the kernel)
-            if (pro && ffn_x3_pro_supported(D, pro_k[pro]) && pro_b[pro]) {
-                f.pws = f16_wscale(f16_fetch(p.h, pro_w[pro], (size_t)D * pro_k[pro]));
-                if (f.pws > 0.0f) f.pro = pro;
-            }
-            if (epi && f.pro == pro && ffn_x3_epi_supported(D, T)) {
-                f.mscale = f16_mean_scale(f16_ln_bound(p.h, l2w, l2b, D));
-                f.epi = f.mscale > 0.0f;
-            }
-            return f;
-        };
-        // allocates, packs and plans form f; false (an allocation or a pack failed): nothing planned, nothing kept
-        auto ffn_build = [&](const std::string& ff, const FfnForm& f) -> bool {
-            const float *lw = p.W(q + ff + ".layer_norm.weight"), *lb = p.W(q + ff + ".layer_norm.bias");
-            if (!f.fused) {
-                p.add("layernorm:" + q + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-                add_gemm(p, q + ff + ".linear1+swish", t1, big, T, 4 * D, D, p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), ACT_SILU);
-                add_gemm(p, q + ff + ".linear2+0.5res", big, hb, T, D, 4 * D, p.W(q + ff + ".linear2.weight"), p.W(q + ff + ".linear2.bias"), ACT_NONE, nullptr, nullptr, hb, 0.5f);
-                return true;
-            }
-            const int pro = f.pro, pk = pro_k[pro];
-            void *packed = nullptr, *ppk = nullptr;
-            if ((pro && (hipMalloc(&ppk, ffn_x3_pro_tile_bytes(pk) * ((D + 31) / 32)) != hipSuccess ||
-                         launch_ffn_x3_pro_pack(pro_w[pro], ppk, D, pk, f.pws, p.h->own_stream) != hipSuccess)) ||
-                hipMalloc(&packed, ffn_x3_packed_bytes(D)) != hipSuccess ||
-                launch_ffn_x3_pack(p.W(q + ff + ".linear1.weight"), p.W(q + ff + ".linear1.bias"), p.W(q + ff + ".linear2.weight"), packed, D,
-                                   p.h->own_stream, f.h2 ? f.fw1 : 0.0f, f.h2 ? f.fw2 : 0.0f, pro ? 1 : 0) != hipSuccess) {
-                if (packed) (void)hipFree(packed);
-                if (ppk) (void)hipFree(ppk);
-                return false;
-            }
-            p.h->packed_weights.push_back(packed);
-            if (ppk) p.h->packed_weights.push_back(ppk);
-            const float* b2 = p.W(q + ff + ".linear2.bias");
-            const float* pbias = pro_b[pro];
-            const float p_un = pro ? 1.0f / f.pws : 1.0f;
-            const bool epi = f.epi;
-            // the epilogue's exact partial sums: per 32-row tile two segments x two planes of D floats (the idle wide scratch buffer)
-            if (epi) p.need(big, (size_t)((T + 31) / 32 + 1) * 4 * D + (size_t)16 * D);
-            const std::string what = std::string(pro == 1 ? "input_proj+" : pro == 2 ? "conv2(pw)+res+" : "") + "ln+linear1+swish+linear2+0.5res" + (epi ? "+layernorm+time sums" : "");
-            p.add("ffn_x3:" + q + ff + " (" + what + ")" + (f.h2 ? " [f16x3]" : ""), [=](Run& r) {
-                FfnArgs a{r.buf[hb], lw, lb, static_cast<const unsigned char*>(packed), b2, r.B * T, 0.5f};
-                if (f.h2) { a.h2_x = f.fx; a.h2_w1 = f.fw1; a.h2_h = f.fh; a.h2_w2 = f.fw2; }
-                if (pro) {
-                    a.px = pro == 1 ? r.x : r.buf[t3]; a.ppacked = static_cast<const unsigned char*>(ppk); a.pb = pbias;
-                    a.pro_k = pk; a.pro_res = pro == 2 ? 1 : 0; a.p_un = p_un;
-                }
-                if (epi) { a.ln2_w = l2w; a.ln2_b = l2b; a.msum = r.buf[big]; a.T = T; a.m_scale = f.mscale; }
-                return launch_ffn_x3(a, D, r.stream);
-            });
-            if (epi)
-                p.add("mean_finish:" + q + " (time average of the exact tile sums)", [=](Run& r) {
-                    return launch_ffn_x3_mean_finish(r.buf[big], r.buf[t1], r.B, T, D, f.mscale, r.stream);
-                });
-            return true;
-        };
-        // the richest form that can be built, one form down after each failed build; separate_pro plans the prologue Linear on its
-        // own when the form planned does not take it.  Returns whether the epilogue was fused.
-        auto ffn = [&](const std::string& ff, int pro, bool epi, const auto& separate_pro) {
-            FfnForm f = ffn_decide(ff, pro, epi);
-            if (pro && !f.pro) separate_pro();
-            while (!ffn_build(ff, f)) {
-                if (f.epi) f.epi = false;
-                else if (f.pro) { f.pro = 0; separate_pro(); }
-                else f.fused = false;
-            }
-            return f.epi;
-        };
-        ffn(".ff1", i == 0 ? 1 : 0, false, [&] { add_linear(p, "input_proj", -1, hb, T, D, F, pro_w[1], pro_b[1]); });
+        // input_proj inside the first block's ff1
+        FfnPro in_proj;
+        if (i == 0) { in_proj.kind = 1; in_proj.name = "input_proj"; in_proj.w = p.W("model.input_proj.weight"); in_proj.b = p.W("model.input_proj.bias"); in_proj.k = F; }
+        add_ffn(p, q + ".ff1", ffn_weights(p, q + ".ff1.layer_norm", q + ".ff1"), 0.5f, hb, t1, t3, big, T, D, in_proj);
         // the attention module in one launch where attn_x3 takes it, else in three
         if (!add_attn_x3(p, q, hb, T, D, NH)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0);
-        const std::string m = q + ".conv_module";
-        const float *lw = p.W(m + ".layer_norm.weight"), *lb = p.W(m + ".layer_norm.bias");
-        const float *dw = p.W(m + ".depthwise_conv.weight"), *db = p.W(m + ".depthwise_conv.bias");
-        const float *ba = p.W(m + ".batch_norm.alpha"), *bb = p.W(m + ".batch_norm.beta");
-        // (the whole module as ONE clip-resident launch was built and measured: bit-identical, 0.27 ms against 0.25 for the three launches
-        // below - tools/ubench/convmod_x3.hip)
-        // LayerNorm + pointwise conv1 + GLU in one launch (lin_x3.hip), else the three separate ones
-        if (!add_lin_x3(p, m + ".layer_norm+conv1(pw)+glu", hb, t1, T, D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), 2, 99, 1.f, lw, lb)) {
-            p.add("layernorm:" + m, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-            add_gemm(p, m + ".conv1(pw)", t1, big, T, 2 * D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), ACT_NONE);
-            p.add("glu:" + m, [=](Run& r) { return launch_glu(r.buf[big], r.buf[t1], r.B * T, D, r.stream); });
-        }
-        p.add("dwconv1d+bn+swish:" + m, [=](Run& r) { return launch_dwconv1d_bn_swish(r.buf[t1], dw, db, ba, bb, r.buf[t3], r.B, T, D, 31, r.stream); });
+        add_conv_module_front(p, m, hb, t1, t3, big, T, D);
         // conv2 + residual inside ff2's launch, and behind the LAST block's ff2 its LayerNorm + the sums of the time average
-        const bool epi_fused = ffn(".ff2", 2, i == nb - 1, [&] { add_linear(p, m + ".conv2(pw)+res", t3, hb, T, D, D, pro_w[2], pro_b[2], hb, 1.0f); });
+        FfnPro conv2; conv2.kind = 2; conv2.name = m + ".conv2(pw)+res"; conv2.w = p.W(m + ".conv2.weight"); conv2.b = p.W(m + ".conv2.bias"); conv2.k = D;
+        FfnEpi mean; mean.want = i == nb - 1; mean.block = q; mean.ln_w = l2w; mean.ln_b = l2b;
+        const bool epi_fused = add_ffn(p, q + ".ff2", ffn_weights(p, q + ".ff2.layer_norm", q + ".ff2"), 0.5f, hb, t1, t3, big, T, D, conv2, mean);
         // the last block's LayerNorm feeds only the mean over time: one pass for both
         if (epi_fused) {
             last_fused = true;
@@ -1607,10 +1284,11 @@ int plan_transformer(PlanCtx& p) {                  // TransformerModel: archite
     p.need(hb, (size_t)T * D); p.need(t1, (size_t)T * D);
     const float* pe = p.W("model.pos_encoder.pe");
     const float xs = std::sqrt((float)D);          // math.sqrt(d_model), applied in float32 as torch does
-    // x = input_proj(x) sqrt(D) + pe[t]: the scale and the positional row in the short-K Linear's epilogue (lin_x3 epilogue 3), its
+    // x = input_proj(x) sqrt(D) + pe[t]: the scale and the positional row in the short-K Linear's epilogue (LIN_RES_TAB), its
     // input rows scaled per row (no clamp of the features); else the general GEMM and one elementwise pass
-    if (!add_lin_x3(p, "input_proj*sqrt(d)+pe", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), 3, 99, xs, nullptr, nullptr, T, 0, pe)) {
-        add_gemm(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
+    LinOpts pos; pos.epi = LIN_RES_TAB; pos.rscale = xs; pos.res_tab = pe; pos.qkv_T = T;
+    if (!add_lin_x3(p, "input_proj*sqrt(d)+pe", BUF_X, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), pos)) {
+        add_gemm(p, "input_proj", BUF_X, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"), ACT_NONE);
         p.add("scale+pe:input_proj", [=](Run& r) { return launch_scale_add_pe(r.buf[hb], pe, r.B, T, D, xs, r.stream); });
     }
     bool mean_done = false;
@@ -1621,25 +1299,19 @@ int plan_transformer(PlanCtx& p) {                  // TransformerModel: archite
         add_attention_module(p, q, ".self_attn", hb, big, t1, T, D, NH, 1);
         // ---- h <- norm2(y + linear2(relu(linear1(y)))), y = norm1(h): one launch (ffn_x3 post-norm instance); the last layer's norm2 feeds
         // only the time mean: exact per-tile sums instead of the store
-        const float *n1w = p.W(q + ".norm1.weight"), *n1b = p.W(q + ".norm1.bias"), *n2w = p.W(q + ".norm2.weight"), *n2b = p.W(q + ".norm2.bias");
-        const float *w1 = p.W(q + ".linear1.weight"), *b1 = p.W(q + ".linear1.bias"), *w2 = p.W(q + ".linear2.weight"), *b2 = p.W(q + ".linear2.bias");
-        bool fused = false;
+        const FfnWeights w = ffn_weights(p, q + ".norm1", q);
+        const float *n1w = w.ln_w, *n1b = w.ln_b, *b2 = w.b2, *n2w = p.W(q + ".norm2.weight"), *n2b = p.W(q + ".norm2.bias");
+        const void* packed = nullptr;
         if (nww_knobs().ffn_fused && p.h->f16 && p.h->conv_products == 6 && ffn_x3_post_supported(D)) {
-            // |norm1(h)_i| <= sqrt(D) |w_i| + |b_i| whatever h holds; relu(v) <= |v|: the scales need nothing but the weights
-            const double bx = f16_ln_bound(p.h, n1w, n1b, D);
-            const auto hw1 = f16_fetch(p.h, w1, (size_t)4 * D * D), hw2 = f16_fetch(p.h, w2, (size_t)4 * D * D), hb1 = f16_fetch(p.h, b1, (size_t)4 * D);
-            const double bh = f16_layer_bound(hw1, 4 * D, D, hb1, true, hb1, hb1, false, bx);
-            const float fx = f16_scale(bx), fw1 = f16_wscale(hw1), fh = f16_scale(bh), fw2 = f16_wscale(hw2);
+            const FfnScales s = ffn_f16_scales(p, w, D);
             const float mscale = last ? f16_mean_scale(f16_ln_bound(p.h, n2w, n2b, D)) : 0.0f;
-            void* packed = nullptr;
-            if (fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f && (!last || mscale > 0.0f) &&
-                hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
-                launch_ffn_x3_pack(w1, b1, w2, packed, D, p.h->own_stream, fw1, fw2, 0) == hipSuccess) {
-                p.h->packed_weights.push_back(packed);
+            if (s.ok() && (!last || mscale > 0.0f))
+                packed = p.pack_one(ffn_x3_packed_bytes(D), [&](void* d) { return launch_ffn_x3_pack(w.w1, w.b1, w.w2, d, D, p.h->own_stream, s.fw1, s.fw2, 0); });
+            if (packed) {
                 if (last) p.need(big, (size_t)((T + 31) / 32 + 4) * ffn_x3_post_nseg(T) * 2 * D);
                 p.add("ffn_x3:" + q + " (norm1+linear1+relu+linear2+res+norm2" + (last ? "+time sums" : "") + ", post-norm) [f16x3]", [=](Run& r) {
                     FfnArgs a{r.buf[hb], n1w, n1b, static_cast<const unsigned char*>(packed), b2, r.B * T, 1.0f};
-                    a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2;
+                    a.h2_x = s.fx; a.h2_w1 = s.fw1; a.h2_h = s.fh; a.h2_w2 = s.fw2;
                     a.ln2_w = n2w; a.ln2_b = n2b;
                     if (last) { a.msum = r.buf[big]; a.T = T; a.m_scale = mscale; }
                     return launch_ffn_x3_post(a, D, r.stream);
@@ -1650,15 +1322,10 @@ int plan_transformer(PlanCtx& p) {                  // TransformerModel: archite
                     });
                     mean_done = true;
                 }
-                fused = true;
-            } else if (packed) {
-                (void)hipFree(packed);
             }
         }
-        if (!fused) {
-            p.add("layernorm:" + q + ".norm1", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], n1w, n1b, r.B * T, D, ACT_NONE, r.stream); });
-            add_gemm(p, q + ".linear1+relu", hb, big, T, 4 * D, D, w1, b1, ACT_RELU);
-            add_gemm(p, q + ".linear2+res", big, hb, T, D, 4 * D, w2, b2, ACT_NONE, nullptr, nullptr, hb, 1.0f);
+        if (!packed) {
+            add_ffn_unfused(p, w, ACT_RELU, 1.0f, hb, hb, big, T, D, q + ".norm1", q + ".linear1+relu", q + ".linear2+res");
             if (last && D <= 256) {
                 p.add("layernorm+mean:" + q + ".norm2 + time", [=](Run& r) { return launch_ln_mean(r.buf[hb], r.buf[t1], n2w, n2b, r.B, T, D, r.stream); });
                 mean_done = true;
@@ -1681,23 +1348,15 @@ int plan_e_branchformer(PlanCtx& p) {               // EBranchformerModel: archi
     const int hb = 0, t1 = 1, t3 = 2, big = 3, ab = 4, cb = 5;
     p.need(hb, (size_t)T * D); p.need(t1, (size_t)T * D); p.need(t3, (size_t)T * D); p.need(ab, (size_t)T * D);
     // both branches read input_proj's output, so it cannot ride in a later launch
-    add_linear(p, "input_proj", -1, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"));
+    add_linear(p, "input_proj", BUF_X, hb, T, D, F, p.W("model.input_proj.weight"), p.W("model.input_proj.bias"));
     for (int i = 0; i < nb; ++i) {
         const std::string q = "model.branchformer_blocks." + std::to_string(i);
         // ---- a = MHA(LayerNorm(x)): no residual here, the merge takes it.  One launch where attn_x3 takes the shape, else three
-        const float *anw = p.W(q + ".attn_branch_norm.weight"), *anb = p.W(q + ".attn_branch_norm.bias");
-        if (!add_attn_x3(p, q, hb, T, D, NH, anw, anb, ab)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0, anw, anb, ab, ".attn_branch_norm");
-        // ---- the ConvolutionModule up to its depthwise stage, as the Conformer's: LayerNorm + conv1 + GLU, depthwise + BN + swish -> t3
+        AttnBranch br; br.ln_w = p.W(q + ".attn_branch_norm.weight"); br.ln_b = p.W(q + ".attn_branch_norm.bias"); br.out = ab; br.ln_name = ".attn_branch_norm";
+        if (!add_attn_x3(p, q, hb, T, D, NH, br)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0, br);
+        // ---- the ConvolutionModule up to its depthwise stage -> t3
         const std::string m = q + ".conv_branch";
-        const float *lw = p.W(m + ".layer_norm.weight"), *lb = p.W(m + ".layer_norm.bias");
-        const float *dw = p.W(m + ".depthwise_conv.weight"), *db = p.W(m + ".depthwise_conv.bias");
-        const float *ba = p.W(m + ".batch_norm.alpha"), *bb = p.W(m + ".batch_norm.beta");
-        if (!add_lin_x3(p, m + ".layer_norm+conv1(pw)+glu", hb, t1, T, D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), 2, 99, 1.f, lw, lb)) {
-            p.add("layernorm:" + m, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], lw, lb, r.B * T, D, ACT_NONE, r.stream); });
-            add_gemm(p, m + ".conv1(pw)", t1, big, T, 2 * D, D, p.W(m + ".conv1.weight"), p.W(m + ".conv1.bias"), ACT_NONE);
-            p.add("glu:" + m, [=](Run& r) { return launch_glu(r.buf[big], r.buf[t1], r.B * T, D, r.stream); });
-        }
-        p.add("dwconv1d+bn+swish:" + m, [=](Run& r) { return launch_dwconv1d_bn_swish(r.buf[t1], dw, db, ba, bb, r.buf[t3], r.B, T, D, 31, r.stream); });
+        add_conv_module_front(p, m, hb, t1, t3, big, T, D);
         // ---- x <- final_norm(x + a g + c (1 - g)), c = conv2(t3), g = sigmoid(gate(c)): one row-local launch (merge_x3.hip) under the
         // default arithmetic - its rows are scaled one by one in the kernel, so it needs no bound on t3 or c - else four
         const float *c2w = p.W(m + ".conv2.weight"), *c2b = p.W(m + ".conv2.bias");
@@ -1706,17 +1365,13 @@ int plan_e_branchformer(PlanCtx& p) {               // EBranchformerModel: archi
         bool merged = false;
         if (nww_knobs().merge_fused && p.h->f16 && p.h->conv_products == 6 && merge_x3_supported(D)) {
             const float wsc = f16_wscale(f16_fetch(p.h, c2w, (size_t)D * D)), wsg = f16_wscale(f16_fetch(p.h, gw, (size_t)D * D));
-            void* packed = nullptr;
-            if (wsc > 0.0f && wsg > 0.0f && hipMalloc(&packed, merge_x3_packed_bytes(D)) == hipSuccess &&
-                launch_merge_x3_pack(c2w, gw, packed, D, wsc, wsg, p.h->own_stream) == hipSuccess) {
-                p.h->packed_weights.push_back(packed);
+            const void* packed = !(wsc > 0.0f && wsg > 0.0f) ? nullptr : p.pack_one(merge_x3_packed_bytes(D), [&](void* d) { return launch_merge_x3_pack(c2w, gw, d, D, wsc, wsg, p.h->own_stream); });
+            if (packed) {
                 p.add("merge_x3:" + q + " (conv2(pw)+gate+blend+res+final_norm) [f16x3]", [=](Run& r) {
                     MergeArgs a{r.buf[t3], r.buf[ab], r.buf[hb], static_cast<const unsigned char*>(packed), c2b, gb, fnw, fnb, r.B * T, 1.0f / wsc, 1.0f / wsg};
                     return launch_merge_x3(a, D, r.stream);
                 });
                 merged = true;
-            } else if (packed) {
-                (void)hipFree(packed);
             }
         }
         if (!merged) {
@@ -1725,40 +1380,9 @@ int plan_e_branchformer(PlanCtx& p) {               // EBranchformerModel: archi
             p.add("branch_merge:" + q + " (sigmoid+blend+res)", [=](Run& r) { return launch_branch_merge(r.buf[hb], r.buf[ab], r.buf[cb], r.buf[big], (size_t)r.B * T * D, r.stream); });
             p.add("layernorm:" + q + ".final_norm", [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[hb], fnw, fnb, r.B * T, D, ACT_NONE, r.stream); });
         }
-        // ---- x <- x + ffn(x): the Conformer's FeedForwardModule with the FULL residual; its plain fused form (ffn_x3.hip), scales from the
-        // weights alone as in plan_conformer (|LayerNorm(x)_i| <= sqrt(D) |w_i| + |b_i|, |swish(v)| <= |v|)
+        // ---- x <- x + ffn(x): the Conformer's FeedForwardModule with the FULL residual, in its plain fused form (ffn_x3.hip) or unfused
         const std::string ff = q + ".ffn";
-        const float *flw = p.W(ff + ".layer_norm.weight"), *flb = p.W(ff + ".layer_norm.bias");
-        const float *w1 = p.W(ff + ".linear1.weight"), *b1 = p.W(ff + ".linear1.bias"), *w2 = p.W(ff + ".linear2.weight"), *b2 = p.W(ff + ".linear2.bias");
-        bool fused = false;
-        if (nww_knobs().ffn_fused && p.h->conv_products == 6 && ffn_x3_supported(D, p.h->f16)) {
-            float fx = 0.0f, fw1 = 0.0f, fh = 0.0f, fw2 = 0.0f;
-            if (p.h->f16) {
-                const double bx = f16_ln_bound(p.h, flw, flb, D);
-                const auto hw1 = f16_fetch(p.h, w1, (size_t)4 * D * D), hw2 = f16_fetch(p.h, w2, (size_t)4 * D * D), hb1 = f16_fetch(p.h, b1, (size_t)4 * D);
-                const double bh = f16_layer_bound(hw1, 4 * D, D, hb1, true, hb1, hb1, false, bx);
-                fx = f16_scale(bx); fw1 = f16_wscale(hw1); fh = f16_scale(bh); fw2 = f16_wscale(hw2);
-            }
-            const bool h2 = fx > 0.0f && fw1 > 0.0f && fh > 0.0f && fw2 > 0.0f;
-            void* packed = nullptr;
-            if (ffn_x3_supported(D, h2) && hipMalloc(&packed, ffn_x3_packed_bytes(D)) == hipSuccess &&
-                launch_ffn_x3_pack(w1, b1, w2, packed, D, p.h->own_stream, h2 ? fw1 : 0.0f, h2 ? fw2 : 0.0f, 0) == hipSuccess) {
-                p.h->packed_weights.push_back(packed);
-                p.add("ffn_x3:" + ff + " (ln+linear1+swish+linear2+res)" + (h2 ? " [f16x3]" : ""), [=](Run& r) {
-                    FfnArgs a{r.buf[hb], flw, flb, static_cast<const unsigned char*>(packed), b2, r.B * T, 1.0f};
-                    if (h2) { a.h2_x = fx; a.h2_w1 = fw1; a.h2_h = fh; a.h2_w2 = fw2; }
-                    return launch_ffn_x3(a, D, r.stream);
-                });
-                fused = true;
-            } else if (packed) {
-                (void)hipFree(packed);
-            }
-        }
-        if (!fused) {
-            p.add("layernorm:" + ff, [=](Run& r) { return launch_layernorm(r.buf[hb], r.buf[t1], flw, flb, r.B * T, D, ACT_NONE, r.stream); });
-            add_gemm(p, ff + ".linear1+swish", t1, big, T, 4 * D, D, w1, b1, ACT_SILU);
-            add_gemm(p, ff + ".linear2+res", big, hb, T, D, 4 * D, w2, b2, ACT_NONE, nullptr, nullptr, hb, 1.0f);
-        }
+        add_ffn(p, ff, ffn_weights(p, ff + ".layer_norm", ff), 1.0f, hb, t1, t3, big, T, D);
     }
     // no LayerNorm in front of the mean (unlike the Conformer), so no plan-time bound for the exact-sum epilogue: the plain mean
     p.add("mean:time", [=](Run& r) { return launch_mean_mid(r.buf[hb], r.buf[t1], r.B, T, D, r.stream); });
@@ -1782,18 +1406,18 @@ int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.p
         TcnArgs a;
         a.T = T; a.F = F; a.L = nl; a.k = k;
         for (int i = 0; i < nl; ++i) a.ch[i] = ch[i];
-        std::vector<void*> packs;
+        PlanCtx::Packs packs(p);
         bool ok = tcn_x3_plan(a);
         int cin = F;
         for (int i = 0; ok && i < nl; ++i) {
             auto pack = [&](const char* part, int ci, int taps, TcnConv& cv) {
                 const float* w = p.W(key(i, (std::string(part) + ".weight").c_str()));
                 const float ws = f16_wscale(f16_fetch(p.h, w, (size_t)ch[i] * ci * taps));
-                void* d = nullptr;
-                if (!(ws > 0.0f) || hipMalloc(&d, tcn_x3_packed_bytes(ci, ch[i], taps)) != hipSuccess) return false;
-                packs.push_back(d);
-                if (launch_tcn_x3_pack(w, d, ci, ch[i], taps, ws, p.h->own_stream) != hipSuccess) return false;
-                cv.packed = static_cast<const unsigned char*>(d);
+                if (!(ws > 0.0f)) return false;
+                cv.packed = static_cast<const unsigned char*>(packs.pack(tcn_x3_packed_bytes(ci, ch[i], taps), [&](void* d) {
+                    return launch_tcn_x3_pack(w, d, ci, ch[i], taps, ws, p.h->own_stream);
+                }));
+                if (!cv.packed) return false;
                 cv.bias = p.W(key(i, (std::string(part) + ".bias").c_str()));
                 cv.w_un = 1.0f / ws;
                 return true;
@@ -1802,7 +1426,7 @@ int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.p
             cin = ch[i];
         }
         if (ok) {
-            for (void* d : packs) p.h->packed_weights.push_back(d);
+            packs.commit();
             p.add("tcn_x3:" + std::to_string(nl) + " blocks, last " + std::to_string(a.S) + " steps of " + std::to_string(T) + " [f16x3]",
                   [=](Run& r) {
                       TcnArgs g = a;
@@ -1810,15 +1434,13 @@ int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.p
                       return launch_tcn_x3(g, r.stream);
                   });
             fused = true;
-        } else {
-            for (void* d : packs) (void)hipFree(d);
         }
     }
     if (!fused) {
         // every level over the whole sequence: causal im2col (taps x dilation, zero history), conv1 = GEMM + ReLU, conv2 = GEMM + ReLU
         // + the residual (or the downsample's GEMM), then the second ReLU; the last row of each clip feeds the tail
         const int col = 0, hid = 1, rsd = 4;
-        int in = -1, cin = F;
+        int in = BUF_X, cin = F;
         for (int i = 0; i < nl; ++i) {
             const int co = ch[i], dil = 1 << i, out = i % 2 == 0 ? 2 : 3;
             const std::string q = "model.tcn_blocks." + std::to_string(i);
@@ -1831,8 +1453,8 @@ int plan_tcn(PlanCtx& p) {                          // TCNModel: architectures.p
                 add_gemm(p, q + ".downsample", in, rsd, T, co, cin, p.W(key(i, "downsample.weight")), p.W(key(i, "downsample.bias")), ACT_NONE);
                 res = rsd;
             }
-            add_gemm(p, q + ".conv2+relu+res", col, out, T, co, co * k, p.W(key(i, "conv2.weight")), p.W(key(i, "conv2.bias")), ACT_RELU,
-                     nullptr, nullptr, res, 1.0f);
+            GemmOpts ro; ro.res_id = res;
+            add_gemm(p, q + ".conv2+relu+res", col, out, T, co, co * k, p.W(key(i, "conv2.weight")), p.W(key(i, "conv2.bias")), ACT_RELU, ro);
             p.add("unary:relu " + q, [=](Run& r) { return launch_unary(r.buf[out], r.buf[out], (size_t)r.B * T * co, ACT_RELU, r.stream); });
             in = out; cin = co;
         }
@@ -1861,6 +1483,7 @@ void plan_raw_frontend(PlanCtx& p) {
     if (!(nww_knobs().raw_fused && h->f16 && h->conv_products == 6 && raw_x3_supported(c.layer_dim, c.n_blocks))) return;
     RawX3Args a;
     a.depth = c.n_blocks; a.C1 = c.layer_dim;
+    PlanCtx::Packs pk(p);
     double bound = 1.0;
     for (int i = 0, Cin = 1; i < c.n_blocks; ++i) {
         const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13;
@@ -1871,11 +1494,12 @@ void plan_raw_frontend(PlanCtx& p) {
         } else {
             if (!p.W(conv + ".raw.wk")) return;
             const float ws = f16_wscale(w.data), sc = f16_scale(bound);
-            void* packed = nullptr;
-            if (!(ws > 0.0f) || !(sc > 0.0f) || hipMalloc(&packed, (size_t)(Cout / 32) * (k * Cin / 16) * 2048) != hipSuccess) return;
-            h->packed_weights.push_back(packed);
-            if (launch_qn_x3_pack(p.W(conv + ".raw.wk"), packed, Cout, k * Cin, ws, h->own_stream) != hipSuccess) return;
-            a.packed[i - 1] = static_cast<const unsigned char*>(packed); a.bias[i - 1] = p.W(conv + ".raw.b");
+            if (!(ws > 0.0f) || !(sc > 0.0f)) return;
+            a.packed[i - 1] = static_cast<const unsigned char*>(pk.pack((size_t)(Cout / 32) * (k * Cin / 16) * 2048, [&](void* d) {
+                return launch_qn_x3_pack(p.W(conv + ".raw.wk"), d, Cout, k * Cin, ws, h->own_stream);
+            }));
+            if (!a.packed[i - 1]) return;
+            a.bias[i - 1] = p.W(conv + ".raw.b");
             a.scale[i - 1] = sc; a.un[i - 1] = 1.0f / (ws * sc);
         }
         double worst = 0.0;                                   // this stage's output bound
@@ -1887,6 +1511,7 @@ void plan_raw_frontend(PlanCtx& p) {
         bound = worst * (1.0 + 1e-6);
         Cin = Cout;
     }
+    pk.commit();
     h->raw_x3 = a;
     h->raw_fused = true;
     h->raw_fused_name = "raw_x3:model.frontend (" + std::to_string(c.n_blocks) + " stages 1->" + std::to_string(c.layer_dim << (c.n_blocks - 1)) +
@@ -1903,7 +1528,7 @@ int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architect
     const int dbuf = 2, ybuf = 3, rbuf = 4, mbuf = 5;
     const int C_last = blocks.back().cout;
     p.need(mbuf, (size_t)C_last);
-    int in = -1;
+    int in = BUF_X;
     bool mean_done = false;
     for (int i = 0; i < nblk; ++i) {
         const int Cin = blocks[i].cin, Cout = blocks[i].cout, k = blocks[i].k, Cp = qn_x3_cp(Cin);
@@ -1917,10 +1542,10 @@ int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architect
         if (nww_knobs().qn_fused && p.h->f16 && p.h->conv_products == 6 && qn_x3_supported(T, Cin, Cout, k) && p.W(q + ".qn.wcat")) {
             const HostTensor& cat = p.h->tensors[q + ".qn.wcat"];
             const float ws = f16_wscale(cat.data);
-            void* packed = nullptr;
-            if (ws > 0.0f && hipMalloc(&packed, qn_x3_packed_bytes(Cin, Cout, proj)) == hipSuccess &&
-                launch_qn_x3_pack(p.W(q + ".qn.wcat"), packed, Cout, qn_x3_ktot(Cin, proj), ws, p.h->own_stream) == hipSuccess) {
-                p.h->packed_weights.push_back(packed);
+            const void* packed = !(ws > 0.0f) ? nullptr : p.pack_one(qn_x3_packed_bytes(Cin, Cout, proj), [&](void* d) {
+                return launch_qn_x3_pack(p.W(q + ".qn.wcat"), d, Cout, qn_x3_ktot(Cin, proj), ws, p.h->own_stream);
+            });
+            if (packed) {
                 const float amax = p.h->tensors[q + ".qn.amax"].data[0];
                 if (!last) p.need(out, (size_t)T * Cout);
                 p.add("qn_x3:" + q + " (dw" + std::to_string(k) + "+pw+bn" + (proj ? "+proj" : "+x") + "+relu" + (last ? "+mean:time" : "") + ") [f16x3]", [=](Run& r) {
@@ -1932,8 +1557,6 @@ int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architect
                 });
                 fused = true;
                 mean_done = last;
-            } else if (packed) {
-                (void)hipFree(packed);
             }
         }
         if (!fused) {
@@ -1985,9 +1608,9 @@ void plan_tail(PlanCtx& p) {
             return launch_classifier_tail(t, r.stream);
         });
     } else {
-        add_gemm(p, p.tail_name, p.tail_in, -2, 1, E, p.tail_K, p.tail_W, p.tail_b, ACT_NONE);
-        add_gemm(p, "classifier.0", -2, -3, 1, E / 2, E, p.W("classifier.0.weight"), p.W("classifier.0.bias"), act);
-        add_gemm(p, "classifier.3", -3, -4, 1, 1, E / 2, p.W("classifier.3.weight"), p.W("classifier.3.bias"), ACT_NONE);
+        add_gemm(p, p.tail_name, p.tail_in, BUF_EMB, 1, E, p.tail_K, p.tail_W, p.tail_b, ACT_NONE);
+        add_gemm(p, "classifier.0", BUF_EMB, BUF_HID, 1, E / 2, E, p.W("classifier.0.weight"), p.W("classifier.0.bias"), act);
+        add_gemm(p, "classifier.3", BUF_HID, BUF_LOGITS, 1, 1, E / 2, p.W("classifier.3.weight"), p.W("classifier.3.bias"), ACT_NONE);
     }
 }
 
