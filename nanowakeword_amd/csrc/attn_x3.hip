@@ -479,13 +479,13 @@ __global__ void __launch_bounds__(256) attn_x3_kernel(AttnArgs a) {
                     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[kt][r]);
                 }
                 mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float off = 14.0f - mx * unS;
+                // (the maximum leaves the raw scores before the scale, not through the fma's addend: mha_h2.hip says why)
                 float den = 0.0f;
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        st[kt][r] = __builtin_amdgcn_exp2f(fmaf(st[kt][r], unS, off));
+                        st[kt][r] = __builtin_amdgcn_exp2f(fmaf(st[kt][r] - mx, unS, 14.0f));
                         den += st[kt][r];
                     }
                 den += __shfl_xor(den, 32, 64);

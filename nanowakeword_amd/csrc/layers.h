@@ -148,10 +148,9 @@ bool mha_mfma_supported(int T, int D, int n_head);
 hipError_t launch_mha_mfma(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0);
 bool mha_head_dim_supported(int head_dim);
 // the same from two binary16 terms per operand on v_mfma_f32_32x32x16_f16 (mha_h2.hip; NWW_ARITH_F16X3): K, V scaled by the
-// unit's own maxima, every query row by its own
+// unit's own maxima, every query row by its own; the softmax subtracts the maximum from the raw scores before scaling them
 bool mha_h2_supported(int T, int D, int n_head);
-// exact_sub = 1: the softmax subtracts the maximum from the raw scores before scaling them (mha_h2.hip XSUB; the Transformer head)
-hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0, int exact_sub = 0);
+hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0);
 // [B][C][H][W] -> [B][W][C*H]  (CRNN: sequence over W, features C*H; architectures.py:272-276)
 hipError_t launch_crnn_seq(const float* in, float* out, int B, int C, int H, int W, hipStream_t s);
 // GRU recurrence for one direction. xg [B][T][3H] = x W_ih^T + b_ih (precomputed by GEMM).

@@ -51,10 +51,12 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // Head dims above 40 keep one wave per SIMD (the 64-wide instance needs ~330 registers - its K / V prefetch alone is 64 - and spilled 52 of
 // them under the two-waves-per-SIMD budget; its 72 KB of LDS still lets two workgroups share a CU when the registers allow)
-// XSUB: the maximum is subtracted from every raw score before the scale (exp2((s - max) unS + 14), as the reference's float32 s - max):
-// the folded form below rounds max x unS once, an error of half its ulp in the exponent - harmless at the Conformer's score magnitudes,
-// but scores of ~1e10 (a x1e4 outlier frame through the Transformer's sqrt(d_model)-scaled input projection) then flip probabilities
-template <int DH, bool XSUB = false>
+// The softmax subtracts the maximum from every raw score BEFORE the scale (exp2((s - max) unS + 14), as the reference's float32 s - max).
+// Folded into the fma's addend (off = 14 - max unS, exp2(s unS + off)) the maximum is rounded once at max x unS's own magnitude - half its
+// ulp in the exponent: one frame x1e4 gives its own query a score of ~1e8 on the Conformer's unnormalised residual stream (~1e10 behind the
+// Transformer's sqrt(d_model)-scaled input projection), the row's largest probability leaves exp2 up to 2^8 above 2^14 and its binary16
+// split overflows (tests/test_gpu_conformer_stress.py)
+template <int DH>
 __global__ void __launch_bounds__(256, (DH > 40 ? 1 : 2)) mha_h2_kernel(const float* __restrict__ qkv, float* __restrict__ out, int units, int T, int D,
                                                         int n_head, float scale, int head_major) {
     constexpr int NKB = (DH + 15) / 16, DHP = 16 * NKB;        // k-blocks of the score product, padded head dim
@@ -235,14 +237,12 @@ __global__ void __launch_bounds__(256, (DH > 40 ? 1 : 2)) mha_h2_kernel(const fl
                 for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[kt][r]);
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float off = 14.0f - mx * unS;
             float den = 0.0f;
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    if constexpr (XSUB) st[kt][r] = __builtin_amdgcn_exp2f(fmaf(st[kt][r] - mx, unS, 14.0f));
-                    else st[kt][r] = __builtin_amdgcn_exp2f(fmaf(st[kt][r], unS, off));
+                    st[kt][r] = __builtin_amdgcn_exp2f(fmaf(st[kt][r] - mx, unS, 14.0f));
                     den += st[kt][r];
                 }
             den += __shfl_xor(den, 32, 64);
@@ -316,7 +316,7 @@ bool mha_h2_supported(int T, int D, int n_head) {
     }
 }
 
-hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major, int exact_sub) {
+hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major) {
     if (!mha_h2_supported(T, D, n_head)) return hipErrorInvalidValue;
     const int dh = D / n_head, units = B * n_head;
     if (units <= 0) return hipSuccess;
@@ -326,12 +326,6 @@ hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int 
     const dim3 grid(units < slots ? units : slots);
 #define MHA_GO(DHV)                                                                                                \
     case DHV: {                                                                                                    \
-        if (exact_sub) {                                                                                           \
-            hipError_t ea = nww_allow_lds(reinterpret_cast<const void*>(mha_h2_kernel<DHV, true>), lds);           \
-            if (ea != hipSuccess) return ea;                                                                       \
-            hipLaunchKernelGGL((mha_h2_kernel<DHV, true>), grid, dim3(256), lds, s, qkv, out, units, T, D, n_head, scale, head_major); \
-            break;                                                                                                 \
-        }                                                                                                          \
         hipError_t ea = nww_allow_lds(reinterpret_cast<const void*>(mha_h2_kernel<DHV>), lds);                     \
         if (ea != hipSuccess) return ea;                                                                           \
         hipLaunchKernelGGL((mha_h2_kernel<DHV>), grid, dim3(256), lds, s, qkv, out, units, T, D, n_head, scale, head_major); \

@@ -630,10 +630,10 @@ bool add_attn_x3(PlanCtx& p, const std::string& q, int hb, int T, int D, int NH,
 }
 
 // h <- h + out_proj(softmax(q k^T / sqrt(dh)) v), q | k | v = in_proj(h), in three launches: block q's module `module` (".attention" /
-// ".self_attn"); buffers hb (h), big (q | k | v), t1 (the heads' outputs).  exact_sub: mha_h2's softmax form (launch_mha_h2)
+// ".self_attn"); buffers hb (h), big (q | k | v), t1 (the heads' outputs)
 // br (the E-Branchformer's branch): q | k | v = in_proj(LayerNorm(h)) - the LayerNorm inside the short-K in_proj where that
 // kernel runs, else on its own into br.out - and out_proj WITHOUT the residual into buffer br.out
-void add_attention_module(PlanCtx& p, const std::string& q, const char* module, int hb, int big, int t1, int T, int D, int NH, int exact_sub,
+void add_attention_module(PlanCtx& p, const std::string& q, const char* module, int hb, int big, int t1, int T, int D, int NH,
                           const AttnBranch& br = AttnBranch{}) {
     const std::string m = q + module;
     // in_proj writes q, k, v head-major when the matrix-core attention consumes them: every (clip, head) block is then
@@ -662,7 +662,7 @@ void add_attention_module(PlanCtx& p, const std::string& q, const char* module, 
     }
     const int hm = head_major ? 1 : 0;
     if (mha_mfma && p.h->f16 && mha_h2_supported(T, D, NH))
-        p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm, exact_sub); });
+        p.add("mha_h2:" + q + " [f16x3]", [=](Run& r) { return launch_mha_h2(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm); });
     else if (mha_mfma && mha_mfma_supported(T, D, NH))
         p.add("mha_mfma:" + q, [=](Run& r) { return launch_mha_mfma(r.buf[big], r.buf[t1], r.B, T, D, NH, r.cu_count, r.stream, hm); });
     else
@@ -1253,7 +1253,7 @@ int plan_conformer(PlanCtx& p) {                    // ConformerModel: architect
         if (i == 0) { in_proj.kind = 1; in_proj.name = "input_proj"; in_proj.w = p.W("model.input_proj.weight"); in_proj.b = p.W("model.input_proj.bias"); in_proj.k = F; }
         add_ffn(p, q + ".ff1", ffn_weights(p, q + ".ff1.layer_norm", q + ".ff1"), 0.5f, hb, t1, t3, big, T, D, in_proj);
         // the attention module in one launch where attn_x3 takes it, else in three
-        if (!add_attn_x3(p, q, hb, T, D, NH)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0);
+        if (!add_attn_x3(p, q, hb, T, D, NH)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH);
         add_conv_module_front(p, m, hb, t1, t3, big, T, D);
         // conv2 + residual inside ff2's launch, and behind the LAST block's ff2 its LayerNorm + the sums of the time average
         FfnPro conv2; conv2.kind = 2; conv2.name = m + ".conv2(pw)+res"; conv2.w = p.W(m + ".conv2.weight"); conv2.b = p.W(m + ".conv2.bias"); conv2.k = D;
@@ -1296,7 +1296,7 @@ int plan_transformer(PlanCtx& p) {                  // TransformerModel: archite
         const std::string q = "model.transformer_encoder.layers." + std::to_string(i);
         const bool last = i == nb - 1;
         // ---- h <- h + self_attn(h): head-major in_proj, the attention core, out_proj + residual (as the Conformer's attention module)
-        add_attention_module(p, q, ".self_attn", hb, big, t1, T, D, NH, 1);
+        add_attention_module(p, q, ".self_attn", hb, big, t1, T, D, NH);
         // ---- h <- norm2(y + linear2(relu(linear1(y)))), y = norm1(h): one launch (ffn_x3 post-norm instance); the last layer's norm2 feeds
         // only the time mean: exact per-tile sums instead of the store
         const FfnWeights w = ffn_weights(p, q + ".norm1", q);
@@ -1353,7 +1353,7 @@ int plan_e_branchformer(PlanCtx& p) {               // EBranchformerModel: archi
         const std::string q = "model.branchformer_blocks." + std::to_string(i);
         // ---- a = MHA(LayerNorm(x)): no residual here, the merge takes it.  One launch where attn_x3 takes the shape, else three
         AttnBranch br; br.ln_w = p.W(q + ".attn_branch_norm.weight"); br.ln_b = p.W(q + ".attn_branch_norm.bias"); br.out = ab; br.ln_name = ".attn_branch_norm";
-        if (!add_attn_x3(p, q, hb, T, D, NH, br)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, 0, br);
+        if (!add_attn_x3(p, q, hb, T, D, NH, br)) add_attention_module(p, q, ".attention", hb, big, t1, T, D, NH, br);
         // ---- the ConvolutionModule up to its depthwise stage -> t3
         const std::string m = q + ".conv_branch";
         add_conv_module_front(p, m, hb, t1, t3, big, T, D);

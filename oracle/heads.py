@@ -264,12 +264,16 @@ def _conv_module(x, sd, p):
     return h @ sd[p + ".conv2.weight"][:, :, 0].T + sd[p + ".conv2.bias"]
 
 
-def net_conformer(x, sd, cfg):
-    """ConformerModel / ConformerBlock (architectures.py:499-543); no pre-LN on attention (:512-513)."""
+def net_conformer(x, sd, cfg, attn_inputs=None):
+    """ConformerModel / ConformerBlock (architectures.py:499-543); no pre-LN on attention (:512-513).
+    attn_inputs: a list that receives every block's attention input [B,T,D] (the residual stream after ff1), for tests that
+    look at the scores the attention kernels see."""
     h = linear(x, sd["model.input_proj.weight"], sd["model.input_proj.bias"])
     for i in range(cfg.n_blocks):
         p = f"model.conformer_blocks.{i}"
         h = h + F32(0.5) * _ffn(h, sd, p + ".ff1")
+        if attn_inputs is not None:
+            attn_inputs.append(h)
         h = h + mha(h, sd, p + ".attention", cfg.conformer_n_head)
         h = h + _conv_module(h, sd, p + ".conv_module")
         h = h + F32(0.5) * _ffn(h, sd, p + ".ff2")
