@@ -1478,20 +1478,38 @@ void plan_raw_frontend(PlanCtx& p) {
         Cin = Cout;
     }
     // ---- the whole frontend in one launch (raw_x3.hip) under the default arithmetic at the shapes it takes.  |x| <= 1 bounds every
-    // stage through the folded weights' row 1-norms; the planes' powers of two come from those bounds, so nothing is clamped
+    // stage through the folded weights' row 1-norms; the planes' powers of two come from those bounds, so nothing is clamped.
+    // The bound compounds over the stages and follows the LOUDEST channel, so each plane is held to a range window as every other
+    // plan-time-scaled layer is (F16Range): beside the bound a typical magnitude per channel, typ_co = sqrt(sum_q w_q^2 typ_q^2 + b^2)
+    // from a typical |x| of 2^-5 (1024 LSB, -30 dBFS).  Per channel, not f16_layer_typ's mean: a channel whose folded BatchNorm gain is G
+    // times the others' (and whose weights in the next stage are 1 / G) would put G / Cout into a mean and hide the others.  What the
+    // plane's absolute error (2^-25 / scale on a value far below the bound) does to output channel co of the stage that reads it goes
+    // through that row's 2-norm, so the plane's magnitude as co sees it is typ_co / ||w_co||_2, and the smallest of those is held against
+    // the bound: within 2^4 f16_range_factor() (2^20: the quietest row keeps 20 bits, 1e-6; the window is taken against the quietest row
+    // and not a mean, hence the 2^4) the launch is raw_x3, otherwise one conv1d_strided launch per stage (float32).  DESIGN.md 4.4f
     nww_handle* h = p.h;
     if (!(nww_knobs().raw_fused && h->f16 && h->conv_products == 6 && raw_x3_supported(c.layer_dim, c.n_blocks))) return;
     RawX3Args a;
     a.depth = c.n_blocks; a.C1 = c.layer_dim;
     PlanCtx::Packs pk(p);
     double bound = 1.0;
+    std::vector<double> typ(1, 0.03125);                      // per channel of the stage's input
     for (int i = 0, Cin = 1; i < c.n_blocks; ++i) {
         const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13;
         const std::string conv = "model.frontend.conv_blocks." + std::to_string(3 * i);
         const HostTensor &w = h->tensors[conv + ".raw.w"], &b = h->tensors[conv + ".raw.b"];
+        std::vector<double> sig2(Cout, 0.0), norm2(Cout, 0.0);      // w [k][Cin][Cout]: column q is channel q % Cin
+        for (int q = 0; q < k * Cin; ++q)
+            for (int co = 0; co < Cout; ++co) {
+                const double w2 = (double)w.data[(size_t)q * Cout + co] * (double)w.data[(size_t)q * Cout + co];
+                norm2[co] += w2; sig2[co] += w2 * typ[q % Cin] * typ[q % Cin];
+            }
         if (i == 0) {
             a.w1 = p.W(conv + ".raw.w"); a.b1 = p.W(conv + ".raw.b");
         } else {
+            double seen = INFINITY;                              // the plane this stage reads, as its quietest output row sees it
+            for (int co = 0; co < Cout; ++co) if (norm2[co] > 0.0) seen = std::fmin(seen, std::sqrt(sig2[co] / norm2[co]));
+            if (!(seen < INFINITY) || !(bound <= seen * std::ldexp(f16_range_factor(), 4))) return;
             if (!p.W(conv + ".raw.wk")) return;
             const float ws = f16_wscale(w.data), sc = f16_scale(bound);
             if (!(ws > 0.0f) || !(sc > 0.0f)) return;
@@ -1509,6 +1527,8 @@ void plan_raw_frontend(PlanCtx& p) {
             worst = std::fmax(worst, t * bound + std::fabs((double)b.data[co]));
         }
         bound = worst * (1.0 + 1e-6);
+        typ.assign(Cout, 0.0);
+        for (int co = 0; co < Cout; ++co) typ[co] = std::sqrt(sig2[co] + (double)b.data[co] * (double)b.data[co]);
         Cin = Cout;
     }
     pk.commit();
