@@ -125,8 +125,63 @@ inline double f16_range_factor() {
 }
 struct F16Range {
     double bound = 0.0, typ = 0.0;
+    std::vector<double> ch;                               // the typical magnitude per channel (f16_rows_typ); empty: only the mean is known
     bool ok() const { return bound > 0.0 && typ > 0.0 && bound <= typ * f16_range_factor(); }
 };
+// The mean over the channels (f16_layer_typ) cannot see a model whose channel gains spread: a channel whose gain is G times the others' (and
+// whose weights in the next layer are 1 / G) puts G / Cout into the mean and hides the others, which then sit G below the bound.  So a
+// plan-time-scaled operand is also held against what each CONSUMER ROW sees of it.  Per row co of the layer that reads the operand:
+// sig2 = sum_q w_q^2 typ_q^2 over the contraction (typ_q: the typical magnitude of the input channel of index q) and norm2 = sum_q w_q^2.
+// The operand's absolute error (2^-25 / scale on a value far below the bound) reaches row co through the row's 2-norm, so the operand's
+// magnitude as co sees it is sqrt(sig2 / norm2); a row with no weight reads nothing and a channel no row reads weighs nothing.  The
+// smallest of those is held against the bound: within 2^4 f16_range_factor() (2^20: the quietest row keeps 20 bits, 1e-6; taken against
+// the quietest row and not a mean, hence the 2^4).  Used by the raw frontend's planes, add_trunk, add_conv_mfma and fc1's operand.
+struct F16Rows { std::vector<double> sig2, norm2; double wmax = 0.0; };
+// w_at(q, co): the weight of row co at contraction index q; ch_of(q): the input channel of index q
+template <class WAt, class ChOf>
+F16Rows f16_rows_moments(int Cout, int K, WAt&& w_at, ChOf&& ch_of, const std::vector<double>& typ_in) {
+    F16Rows m;
+    m.sig2.assign(Cout, 0.0); m.norm2.assign(Cout, 0.0);
+    for (int q = 0; q < K; ++q) {
+        const double t = typ_in[ch_of(q)];
+        for (int co = 0; co < Cout; ++co) {
+            const double w = (double)w_at(q, co), w2 = w * w;
+            m.norm2[co] += w2; m.sig2[co] += w2 * t * t;
+            m.wmax = std::fmax(m.wmax, std::fabs(w));
+        }
+    }
+    return m;
+}
+double f16_rows_seen(const F16Rows& m) {                 // the operand as its quietest consumer row sees it; INFINITY: no row reads it
+    double seen = INFINITY;
+    for (size_t co = 0; co < m.norm2.size(); ++co) if (m.norm2[co] > 0.0) seen = std::fmin(seen, std::sqrt(m.sig2[co] / m.norm2[co]));
+    return seen;
+}
+bool f16_rows_ok(double bound, const F16Rows& m) {
+    const double seen = f16_rows_seen(m);
+    return seen < INFINITY && bound <= seen * std::ldexp(f16_range_factor(), 4);
+}
+// The weights' side of the same thing: one power of two per tensor puts its largest weight in [2^14, 2^15), and a weight's `lo` term keeps
+// its 11 bits down to 2^-3 - so every row's RMS weight has to lie within 2^17 of the largest weight (a convolution without a BatchNorm whose
+// one output channel is G times the others' carries G in its own rows).  Conservative on purpose: one nearly dead row (pruned to 2^-17 of
+// the largest weight but not to zero) sends the layer to three terms although its lost bits cannot matter - the result stays right, the
+// step is slower; a row of exact zeros is exempt
+bool f16_rows_weights_ok(const F16Rows& m, int K) {
+    for (size_t co = 0; co < m.norm2.size(); ++co)
+        if (m.norm2[co] > 0.0 && m.wmax > std::sqrt(m.norm2[co] / K) * 131072.0) return false;
+    return true;
+}
+// the rows' outputs, per channel: typ_co = sqrt(sig2 + b^2), through a folded BatchNorm sqrt(sig2 al^2 + (b al + be)^2)
+std::vector<double> f16_rows_typ(const F16Rows& m, const std::vector<float>& b, bool has_b, const std::vector<float>& al,
+                                 const std::vector<float>& be, bool has_bn) {
+    std::vector<double> typ(m.sig2.size(), 0.0);
+    for (size_t co = 0; co < typ.size(); ++co) {
+        const double bb = has_b ? (double)b[co] : 0.0;
+        typ[co] = has_bn ? std::sqrt(m.sig2[co] * (double)al[co] * (double)al[co] + (bb * (double)al[co] + (double)be[co]) * (bb * (double)al[co] + (double)be[co]))
+                         : std::sqrt(m.sig2[co] + bb * bb);
+    }
+    return typ;
+}
 const F16Range F16_FEATURES{NWW_F16_FEATURE_BOUND, 32.0};
 double f16_layer_typ(const std::vector<float>& w, int Cout, int K, const std::vector<float>& al, bool has_bn, double typ_in) {
     double acc = 0;
@@ -172,8 +227,18 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
     // two binary16 terms (NWW_ARITH_F16X3) when the caller knows a bound on |A|: A times a_scale stays inside the binary16 range
     float h2_as = 0.0f, h2_ws = 0.0f;
     if (use_x3 && p.h->f16 && a_bound > 0.0) {
-        h2_as = f16_scale(a_bound);
-        if (h2_as > 0.0f) h2_ws = f16_wscale(f16_fetch(p.h, W, (size_t)N * K));
+        const auto hW = f16_fetch(p.h, W, (size_t)N * K);
+        // A's channels are contiguous blocks of K / channels columns (the trunk's [C][H / 4][W / 4] output, flattened): the bound is held
+        // against what the quietest row of W sees of them (f16_rows_ok), and W's rows against its largest weight
+        bool rows_ok = true;
+        const int nch = (int)o.a_range.ch.size();
+        if (nch > 0 && K % nch == 0) {
+            const int per = K / nch;
+            const F16Rows m = f16_rows_moments(N, K, [&](int q, int co) { return hW[(size_t)co * K + q]; }, [&](int q) { return q / per; }, o.a_range.ch);
+            rows_ok = f16_rows_ok(a_bound, m) && f16_rows_weights_ok(m, K);
+        }
+        h2_as = rows_ok ? f16_scale(a_bound) : 0.0f;
+        if (h2_as > 0.0f) h2_ws = f16_wscale(hW);
     }
     const bool h2_req = h2_as > 0.0f && h2_ws > 0.0f;
     if (use_x3) {
@@ -314,6 +379,7 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
         // NWW_ARITH_F16X3: two binary16 terms per operand when the input is bounded; the scales from bounds on conv1's / conv2's outputs
         float f_in = 0.0f, f_s1 = 0.0f, f_w1 = 0.0f, f_w2 = 0.0f;
         double bound2 = 0.0, typ2 = 0.0;
+        std::vector<double> ch2;
         if (p.h->f16 && x3 == 6 && in_bound > 0.0 && (act == ACT_RELU || act == ACT_GELU || act == ACT_SILU)) {
             const auto hw1 = f16_fetch(p.h, w1, (size_t)C1 * 9), hw2 = f16_fetch(p.h, w2, (size_t)C2 * C1 * 9);
             const auto hb1 = f16_fetch(p.h, b1, C1), hb2 = f16_fetch(p.h, b2, C2);
@@ -322,7 +388,15 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
             bound2 = f16_layer_bound(hw2, C2, C1 * 9, hb2, b2 != nullptr, ha2, he2, al2 != nullptr, bound1);
             const F16Range r1{bound1, f16_layer_typ(hw1, C1, 9, ha1, al1 != nullptr, o.in_range.typ)};
             typ2 = f16_layer_typ(hw2, C2, C1 * 9, ha2, al2 != nullptr, r1.typ);
-            if (r1.ok()) { f_in = f16_scale(in_bound); f_s1 = f16_scale(bound1); f_w1 = f16_wscale(hw1); f_w2 = f16_wscale(hw2); }
+            // per channel: conv1's output as conv2's quietest row sees it against bound1, and both layers' rows against their largest weight
+            const std::vector<double> tin = o.in_range.ch.size() == 1 ? o.in_range.ch : std::vector<double>(1, o.in_range.typ);
+            const F16Rows m1 = f16_rows_moments(C1, 9, [&](int q, int co) { return hw1[(size_t)co * 9 + q]; }, [](int) { return 0; }, tin);
+            const F16Rows m2 = f16_rows_moments(C2, C1 * 9, [&](int q, int co) { return hw2[(size_t)co * C1 * 9 + q]; }, [](int q) { return q / 9; },
+                                                f16_rows_typ(m1, hb1, b1 != nullptr, ha1, he1, al1 != nullptr));
+            ch2 = f16_rows_typ(m2, hb2, b2 != nullptr, ha2, he2, al2 != nullptr);
+            if (r1.ok() && f16_rows_ok(bound1, m2) && f16_rows_weights_ok(m1, 9) && f16_rows_weights_ok(m2, C1 * 9)) {
+                f_in = f16_scale(in_bound); f_s1 = f16_scale(bound1); f_w1 = f16_wscale(hw1); f_w2 = f16_wscale(hw2);
+            }
         }
         const bool f16 = f_in > 0.0f && f_s1 > 0.0f && f_w1 > 0.0f && f_w2 > 0.0f;
         void* packed = p.pack_one(trunk_b_packed_bytes(), [&](void* d) {
@@ -330,7 +404,7 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
                        : launch_trunk_b_pack(w1, w2, static_cast<unsigned char*>(d), p.h->own_stream);
         });
         if (!packed) return false;
-        if (f16 && o.out_range) *o.out_range = F16Range{bound2, typ2};
+        if (f16 && o.out_range) *o.out_range = F16Range{bound2, typ2, ch2};
         const int products = f16 ? 3 : x3;
         // BN + ReLU stems (CRNN, E2E): all folded-BN factors of both layers non-negative (gamma > 0, the usual case) -> the pooled value is
         // the window's maximum pushed through BN + ReLU (trunk_b.hip: POS instance)
@@ -373,8 +447,15 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
                    const float* w, const float* bias, const float* alpha, const float* beta, int act, int pool,
                    const ConvMfmaOpts& o = ConvMfmaOpts{}) {
     if (o.out_range) *o.out_range = F16Range{};
-    const double in_bound = o.in_range.ok() ? o.in_range.bound : 0.0;
+    double in_bound = o.in_range.ok() ? o.in_range.bound : 0.0;
     const int enabled = nww_knobs().conv_mfma, x3_enabled = nww_knobs().conv3_x3;
+    // the input's bound against what this stage's quietest row sees of its channels (f16_rows_ok), the rows against their largest weight
+    F16Rows rows;
+    if (p.h->f16 && in_bound > 0.0 && (int)o.in_range.ch.size() == Cin) {
+        const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
+        rows = f16_rows_moments(Cout, Cin * 9, [&](int q, int co) { return hw[(size_t)co * Cin * 9 + q]; }, [](int q) { return q / 9; }, o.in_range.ch);
+        if (!(f16_rows_ok(in_bound, rows) && f16_rows_weights_ok(rows, Cin * 9))) in_bound = 0.0;
+    }
     // 64 input channels (a fourth CRNN stage): conv3_x3's wide instance - two-term arithmetic on a bounded input only
     bool wide = Cin == 64 && enabled && x3_enabled && pool && o.avg_ow == 0 && !o.avg_y && p.h->conv_products == 6 && p.h->f16 && in_bound > 0.0 &&
                 Cout % 32 == 0 && conv3_x3_wide_fits(Cin, H, W, Cout);
@@ -413,7 +494,9 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
     } else if (!enabled || Cin != 32 || Cout % 32 != 0 || H < 2 || W < 2)
         return false;
     // (the float32-MFMA instance shares its 8 waves among the 32-channel groups; conv3_x3 takes one group per workgroup)
-    const bool f32_fits = !wide && (8 % (Cout / 32)) == 0 && conv_mfma_lds_bytes(Cin, H, W) <= 160 * 1024;
+    // (... and its fused average pool keeps 8 waves x 64 channels x 4 sums in the plane's LDS: launch_conv3x3_mfma refuses a plane smaller than that)
+    const bool f32_fits = !wide && (8 % (Cout / 32)) == 0 && conv_mfma_lds_bytes(Cin, H, W) <= 160 * 1024 &&
+                          !(o.avg_ow > 0 && (o.avg_ow > 4 || (size_t)8 * 64 * 4 * sizeof(float) > conv_mfma_lds_bytes(Cin, H, W)));
     // pooled planes of more than 512 pixels (clips longer than ~1.3 s, a second stage behind an unfused first one): conv3_x3 in strips of rows
     const int strip_h = (!wide && pool && o.avg_ow == 0 && !o.avg_y && !conv3_x3_fits(H, W, Cout, o.avg_ow, pool)) ? conv3_x3_strip_rows(H, W, Cout) : 0;
     const bool x3_shape = strip_h > 0 || conv3_x3_fits(H, W, Cout, o.avg_ow, pool);
@@ -435,9 +518,10 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
             const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
             h2_in = f16_scale(in_bound); h2_w = f16_wscale(hw);
             if (o.out_range && h2_in > 0.0f && h2_w > 0.0f) {
-                const auto hal = f16_fetch(p.h, alpha, Cout);
-                *o.out_range = F16Range{f16_layer_bound(hw, Cout, Cin * 9, f16_fetch(p.h, bias, Cout), bias != nullptr, hal, f16_fetch(p.h, beta, Cout), alpha != nullptr, in_bound),
+                const auto hal = f16_fetch(p.h, alpha, Cout), hbe = f16_fetch(p.h, beta, Cout), hbi = f16_fetch(p.h, bias, Cout);
+                *o.out_range = F16Range{f16_layer_bound(hw, Cout, Cin * 9, hbi, bias != nullptr, hal, hbe, alpha != nullptr, in_bound),
                                       f16_layer_typ(hw, Cout, Cin * 9, hal, alpha != nullptr, o.in_range.typ)};
+                if (!rows.sig2.empty()) o.out_range->ch = f16_rows_typ(rows, hbi, bias != nullptr, hal, hbe, alpha != nullptr);
             }
         }
         const bool h2 = h2_in > 0.0f && h2_w > 0.0f;
@@ -1498,18 +1582,12 @@ void plan_raw_frontend(PlanCtx& p) {
         const int Cout = c.layer_dim << i, k = i == 0 ? 41 : 13;
         const std::string conv = "model.frontend.conv_blocks." + std::to_string(3 * i);
         const HostTensor &w = h->tensors[conv + ".raw.w"], &b = h->tensors[conv + ".raw.b"];
-        std::vector<double> sig2(Cout, 0.0), norm2(Cout, 0.0);      // w [k][Cin][Cout]: column q is channel q % Cin
-        for (int q = 0; q < k * Cin; ++q)
-            for (int co = 0; co < Cout; ++co) {
-                const double w2 = (double)w.data[(size_t)q * Cout + co] * (double)w.data[(size_t)q * Cout + co];
-                norm2[co] += w2; sig2[co] += w2 * typ[q % Cin] * typ[q % Cin];
-            }
+        // w [k][Cin][Cout]: column q is channel q % Cin
+        const F16Rows rows = f16_rows_moments(Cout, k * Cin, [&](int q, int co) { return w.data[(size_t)q * Cout + co]; }, [&](int q) { return q % Cin; }, typ);
         if (i == 0) {
             a.w1 = p.W(conv + ".raw.w"); a.b1 = p.W(conv + ".raw.b");
         } else {
-            double seen = INFINITY;                              // the plane this stage reads, as its quietest output row sees it
-            for (int co = 0; co < Cout; ++co) if (norm2[co] > 0.0) seen = std::fmin(seen, std::sqrt(sig2[co] / norm2[co]));
-            if (!(seen < INFINITY) || !(bound <= seen * std::ldexp(f16_range_factor(), 4))) return;
+            if (!f16_rows_ok(bound, rows)) return;               // the plane this stage reads, as its quietest output row sees it
             if (!p.W(conv + ".raw.wk")) return;
             const float ws = f16_wscale(w.data), sc = f16_scale(bound);
             if (!(ws > 0.0f) || !(sc > 0.0f)) return;
@@ -1527,8 +1605,7 @@ void plan_raw_frontend(PlanCtx& p) {
             worst = std::fmax(worst, t * bound + std::fabs((double)b.data[co]));
         }
         bound = worst * (1.0 + 1e-6);
-        typ.assign(Cout, 0.0);
-        for (int co = 0; co < Cout; ++co) typ[co] = std::sqrt(sig2[co] + (double)b.data[co] * (double)b.data[co]);
+        typ = f16_rows_typ(rows, b.data, true, b.data, b.data, false);
         Cin = Cout;
     }
     pk.commit();
@@ -1634,6 +1711,96 @@ void plan_tail(PlanCtx& p) {
     }
 }
 
+// ---- channel gains balanced at load time (two-term arithmetic, ReLU heads with a plan-time-scaled conv trunk: cnn, crnn, e2e_dnn)
+// One power of two per TENSOR serves conv1's and conv2's outputs, so a channel whose gain is G times the others' pushes them log2 G bits
+// down the operand, and the range guard (F16Range, f16_rows_ok) then has to send the layer that reads it to three terms.  ReLU and the
+// pools are positively homogeneous: channel c of a layer x s_c and the next layer's weights on c / s_c, s_c a power of two, is the same
+// function with the same float32 bits.  So a channel whose worst-case bound lies 2^4 or more off the layer's median channel (the upper
+// median over the channels that count, see below) is given the
+// power of two that brings it next to the median - through the BatchNorm's weight and bias where the layer has one (the fold sees them),
+// else through the convolution's row and bias - before the BatchNorms are folded and the arena is uploaded.  Ordinary models (channel
+// bounds within a few x of each other) are not touched; GELU / SiLU heads cannot be (the guard decides for them).  -> the layer's bound after
+struct BalanceLayer { HostTensor *w = nullptr, *b = nullptr, *g = nullptr, *beta = nullptr, *mean = nullptr, *var = nullptr; };
+double balance_channels(const BalanceLayer& L, const std::vector<HostTensor*>& consumers, double in_bound) {
+    const int Cout = (int)L.w->shape[0], K = (int)(L.w->data.size() / Cout);
+    std::vector<double> bound(Cout, 0.0);
+    for (int c = 0; c < Cout; ++c) {
+        double t = 0.0;
+        for (int k = 0; k < K; ++k) t += std::fabs((double)L.w->data[(size_t)c * K + k]);
+        t = t * in_bound + (L.b ? std::fabs((double)L.b->data[c]) : 0.0);
+        if (L.g) {
+            const double al = (double)L.g->data[c] / std::sqrt((double)L.var->data[c] + 1e-5), be = (double)L.beta->data[c] - (double)L.mean->data[c] * al;
+            t = t * std::fabs(al) + std::fabs(be);
+        }
+        bound[c] = t;
+    }
+    // what a channel is worth to the layer behind it: its bound times the 2-norm of the weights that read it.  A channel worth less than 2^-8
+    // of the layer's best (a nearly dead BatchNorm channel, a pruned column) is neither moved nor counted: the median is taken over the rest
+    std::vector<double> worth(Cout, 0.0);
+    double best = 0.0;
+    for (int c = 0; c < Cout; ++c) {
+        double q = 0.0;
+        for (HostTensor* W : consumers) {
+            const size_t N = (size_t)W->shape[0], Kc = W->data.size() / N, per = Kc / Cout;
+            for (size_t n = 0; n < N; ++n)
+                for (size_t j = 0; j < per; ++j) { const double v = (double)W->data[n * Kc + (size_t)c * per + j]; q += v * v; }
+        }
+        worth[c] = bound[c] * std::sqrt(q);
+        if (std::isfinite(worth[c])) best = std::fmax(best, worth[c]);
+    }
+    std::vector<double> sorted;
+    for (int c = 0; c < Cout; ++c) if (worth[c] > 0.0 && worth[c] >= best * 0.00390625) sorted.push_back(bound[c]);
+    std::sort(sorted.begin(), sorted.end());
+    const double med = sorted.empty() ? 0.0 : sorted[sorted.size() / 2];
+    double worst = 0.0;
+    for (int c = 0; c < Cout; ++c) {
+        int e = 0;
+        if (med > 0.0 && worth[c] > 0.0 && worth[c] >= best * 0.00390625 && std::isfinite(bound[c]) && std::isfinite(med)) {
+            const double l = std::log2(bound[c] / med);
+            if (std::fabs(l) >= 4.0 && std::fabs(l) <= 40.0) e = -(int)std::lround(l);
+        }
+        if (e != 0) {
+            const float s = std::ldexp(1.0f, e), r = std::ldexp(1.0f, -e);
+            if (L.g) { L.g->data[c] *= s; L.beta->data[c] *= s; }
+            else { for (int k = 0; k < K; ++k) L.w->data[(size_t)c * K + k] *= s; if (L.b) L.b->data[c] *= s; }
+            for (HostTensor* W : consumers) {                   // [N][Cout * per]: channel c is columns c per .. c per + per - 1
+                const size_t N = (size_t)W->shape[0], Kc = W->data.size() / N, per = Kc / Cout;
+                for (size_t n = 0; n < N; ++n)
+                    for (size_t j = 0; j < per; ++j) W->data[n * Kc + (size_t)c * per + j] *= r;
+            }
+        }
+        worst = std::fmax(worst, std::ldexp(bound[c], e));
+    }
+    return worst;
+}
+void balance_channel_gains(nww_handle* h) {
+    const nww_config& c = h->cfg;
+    if (!(h->f16 && h->conv_products == 6 && c.activation == ACT_RELU)) return;
+    auto T = [&](const std::string& k) -> HostTensor* { auto it = h->tensors.find(k); return it == h->tensors.end() || !it->second.loaded ? nullptr : &it->second; };
+    auto layer = [&](const std::string& conv, const std::string& bn) {
+        BalanceLayer L; L.w = T(conv + ".weight"); L.b = T(conv + ".bias");
+        if (!bn.empty()) { L.g = T(bn + ".weight"); L.beta = T(bn + ".bias"); L.mean = T(bn + ".running_mean"); L.var = T(bn + ".running_var"); }
+        return L;
+    };
+    std::vector<std::pair<BalanceLayer, HostTensor*>> links;      // a layer and the weight that reads its channels
+    if (c.head_type == NWW_HEAD_CNN) {
+        links = {{layer("model.conv1", ""), T("model.conv2.weight")}, {layer("model.conv2", ""), T("model.fc1.weight")}};
+    } else if (c.head_type == NWW_HEAD_CRNN && c.n_crnn_channels >= 3 && c.crnn_channels[0] == 16 && c.crnn_channels[1] == 32) {
+        links = {{layer("model.cnn.0", "model.cnn.1"), T("model.cnn.4.weight")}, {layer("model.cnn.4", "model.cnn.5"), T("model.cnn.8.weight")}};
+    } else if (c.head_type == NWW_HEAD_E2E_DNN) {
+        links = {{layer("model.conv_block.0", "model.conv_block.1"), T("model.conv_block.4.weight")},
+                 {layer("model.conv_block.4", "model.conv_block.5"), T("model.conv_block.8.weight")}};
+    }
+    double bound = NWW_F16_FEATURE_BOUND;
+    for (auto& lk : links) {
+        const BalanceLayer& L = lk.first;
+        if (!L.w || !lk.second || L.w->shape.empty() || (L.g && !(L.beta && L.mean && L.var))) return;
+        const size_t Cout = (size_t)L.w->shape[0], N = (size_t)lk.second->shape[0];
+        if (Cout == 0 || N == 0 || L.w->data.size() % Cout || (lk.second->data.size() / N) % Cout) return;
+        bound = balance_channels(L, {lk.second}, bound);
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ finalize
@@ -1643,6 +1810,7 @@ extern "C" int nww_finalize(nww_handle* h) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     for (const auto& k : h->keys)
         if (!h->tensors[k].loaded) return fail(h, NWW_ERR_MISSING, "Missing key(s) in state_dict: '%s'", k.c_str());
+    balance_channel_gains(h);
     fold_batchnorms(h);
     if (h->cfg.head_type == NWW_HEAD_BCRESNET) transpose_depthwise(h);
     if (h->cfg.head_type == NWW_HEAD_QUARTZNET || h->cfg.head_type == NWW_HEAD_E2E_QUARTZNET) fold_quartznet(h);
