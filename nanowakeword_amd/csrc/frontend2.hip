@@ -67,8 +67,19 @@ __device__ __forceinline__ float fe2_db(float mel, float amin, float mult, float
 #define FE2_ARGS pcm, row_stride, B, N, T, ngroups, hop, pad, n_mels, amin, db_mult, floor_db, gtb, plan, out_db, out_mel, frames_major, dbg, gsz, sub
 // RING: the streaming instances (frame subsets, ring-addressed output; Fe2Sub) - compiled apart so that the batch kernels keep their
 // register budget (three more VGPRs put the 28-tap instance into scratch)
-template <int MEL, int FAST_OUT, int MAXT, bool RING>
+// FLAT: the batch instances (frames-major fast output, register filters, FE2_G frames per item, no frame subset).  An item is FE2_G consecutive frames
+// of the WHOLE BATCH (frame g = FE2_G * item + f of clip g / T), not of one clip: no clip pays for a short last group, only the launch's
+// last item can be short, and the dense [B][T][n_mels] output keeps an item's block contiguous across a clip boundary.  The two S1
+// slots of a trip may lie in different clips, so the clip base and the first sample are per lane; a trip reads its samples with the
+// aligned 4-byte loads unless one of its frames leaves [0, N) (or the batch is not 4-byte aligned) - then that trip alone takes
+// reflect-indexed 2-byte loads, all issued before one wait.  An item whose eight frames are all interior frames of one clip ("plain",
+// nine in ten) runs S1 without any test: trip k + 1's loads are issued unconditionally and stay in flight under trip k's arithmetic.
+template <int MEL, int FAST_OUT, int MAXT, bool RING, bool FLAT>
 __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
+    static_assert(!FLAT || (FAST_OUT && !RING && MEL == 2), "flat items: frames-major fast output, register filters, no frame subsets");
+#ifndef NWW_ABLATION
+    if (FLAT) dbg = 0;      // the stage switches are compiled out: a branch between a trip's loads and their use costs the overlap (S1)
+#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MFMA_MEL = MEL == 1;
     const int lane = threadIdx.x & 63;
@@ -96,9 +107,10 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
     const int ia2 = k3a ? FE_M - k3a : 0;                    // partner bin of k3a (Z[200] = Z[0])
     const int f2 = lane >> 3, k1_2 = lane & 7;               // S2: frame, row
     // copy-out: stage offsets of the lane's four 16-byte pieces of the (frames x n_mels) block (index division done once)
-    int co_off[4];
+    constexpr int NCO = FLAT ? 2 : 4;                        // flat items come with register filters: n_mels <= 64, at most 512 floats per block
+    int co_off[NCO];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    for (int r = 0; r < NCO; ++r) {
         const int i = 4 * lane + 256 * r, f = i / n_mels, j = i - f * n_mels;
         co_off[r] = f * FE2_FRAME_DW + FE2_STAGE_OFF + FE2_PSHIFT(f) + j;
     }
@@ -128,7 +140,7 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
     const uint32_t mel_meta = MFMA_MEL ? plan->chunk_meta[lane] : 0u;
     const bool aligned = ((reinterpret_cast<uintptr_t>(pcm) | (row_stride * sizeof(int16_t))) & 3) == 0;
 
-    const int total = B * ngroups;
+    const int total = FLAT ? (B * T + FE2_G - 1) / FE2_G : B * ngroups;      // (flat: the launcher checked that B * T + FE2_G fits an int)
     const int stride = gridDim.x * nwv;
     uint32_t cur[8];                                         // samples of the S1 iteration about to run (lane's column)
     auto geom = [&](int item, int& b, int& t0, int& nf) {
@@ -158,52 +170,159 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
         if (interior(t0, nf) && slot < nf && slot < 2)
             fe2_load_column(pcm + (size_t)b * row_stride, (t0 + slot) * hop - pad, n2, cur);
     };
-    int item = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * nwv + wv));
-    if (item < total) prefetch_first(item);
-    for (; item < total; item += stride) {
-        int b, t0, nf;
-        geom(item, b, t0, nf);
-        const int16_t* x = pcm + (size_t)b * row_stride;
-        const bool inner = interior(t0, nf);
-        const uint32_t* span = reinterpret_cast<const uint32_t*>(slab + 6 * FE2_FRAME_DW);
-        if (!inner) {      // edge item: reflect-padded span -> LDS
-            const int s0 = t0 * hop - pad, npairs = ((nf - 1) * hop + FE_NFFT) >> 1;
-            uint32_t* sp = reinterpret_cast<uint32_t*>(slab + 6 * FE2_FRAME_DW);
-            for (int i = lane; i < npairs; i += 64) {
-                const int q = s0 + 2 * i;
-                sp[i] = (uint32_t)(uint16_t)x[fe_reflect(q, N)] | ((uint32_t)(uint16_t)x[fe_reflect(q + 1, N)] << 16);
-            }
-            fe2_wave_sync();
-            if (slot < nf && slot < 2) {
+    // ---- flat items: the lane's frame of S1 trip k of the item whose first frame is frame t0 of the clip at x -> woff, the samples from
+    // x to the frame's own clip (a 32-bit offset on the wave-uniform base: the launcher checked the range), and its first sample s0.
+    // Frames behind the launch's last one repeat it (their rows are computed and never copied out).
+    auto flat_frame = [&](int t0, int nf, int k, uint32_t& woff, int& s0) {
+        int f = 2 * k + slot;
+        if (nf < FE2_G) f = min(f, nf - 1);                  // wave-uniform: the launch's last item only
+        int t = t0 + f;
+        woff = 0u;
+        if (t0 + FE2_G > T)                                  // wave-uniform: the item runs on into the next clip (clips, when T < FE2_G)
+            while (t >= T) { t -= T; woff += (uint32_t)row_stride; }
+        s0 = t * hop - pad;
+    };
+    // the trip's 8 sample pairs per lane; the branch is wave-uniform (one edge frame sends both slots of the trip down the 2-byte path)
+    auto flat_load = [&](const int16_t* x, uint32_t woff, int s0, uint32_t (&v)[8]) {
+        const bool edge = !aligned || __builtin_amdgcn_ballot_w64(s0 < 0 || s0 + FE_NFFT > N) != 0;
+        const char* xb = reinterpret_cast<const char*>(x);
+        if (!edge) {
+            const uint32_t o = 2u * (woff + (uint32_t)s0 + 2u * (uint32_t)n2);
 #pragma unroll
-                for (int n1 = 0; n1 < 8; ++n1) cur[n1] = span[((slot * hop) >> 1) + n2 + 25 * n1];
+            for (int n1 = 0; n1 < 8; ++n1) v[n1] = *reinterpret_cast<const uint32_t*>(xb + o + 100 * n1);
+        } else {
+            uint32_t lo[8], hi[8];
+#pragma unroll
+            for (int n1 = 0; n1 < 8; ++n1) {
+                const int q = s0 + 2 * (n2 + 25 * n1);
+                lo[n1] = *reinterpret_cast<const uint16_t*>(xb + 2u * (woff + (uint32_t)fe_reflect(q, N)));
+                hi[n1] = *reinterpret_cast<const uint16_t*>(xb + 2u * (woff + (uint32_t)fe_reflect(q + 1, N)));
+            }
+#pragma unroll
+            for (int n1 = 0; n1 < 8; ++n1) v[n1] = lo[n1] | (hi[n1] << 16);
+        }
+    };
+    // A "plain" item - eight frames of one clip, none of them an edge frame, 4-byte aligned, which is nine items in ten - runs S1
+    // without a branch inside the trip.  With a branch between a trip's loads and the arithmetic of the trip before, hipcc waits for
+    // the loads it has just issued (vmcnt(0) in front of the conversions), so the per-trip edge test lives in the other items only.
+    auto flat_plain = [&](int t0, int nf) {
+        const int s0 = t0 * hop - pad;
+        return aligned && nf == FE2_G && t0 + FE2_G <= T && s0 >= 0 && s0 + (FE2_G - 1) * hop + FE_NFFT <= N;
+    };
+    auto plain_off = [&](int t0, int k) { return 2u * (uint32_t)((t0 + 2 * k + slot) * hop - pad + 2 * n2); };      // bytes from the clip's base
+    auto plain_load = [&](const int16_t* x, uint32_t o, uint32_t (&v)[8]) {
+        const char* xb = reinterpret_cast<const char*>(x);
+#pragma unroll
+        for (int n1 = 0; n1 < 8; ++n1) v[n1] = *reinterpret_cast<const uint32_t*>(xb + o + 100 * n1);
+    };
+    auto flat_first = [&](const int16_t* x, int t0, int nf) {      // trip 0's samples -> cur
+        if (lane < 50) {
+            if (flat_plain(t0, nf)) {
+                plain_load(x, plain_off(t0, 0), cur);
+            } else {
+                uint32_t woff; int s0;
+                flat_frame(t0, nf, 0, woff, s0);
+                flat_load(x, woff, s0, cur);
             }
         }
-        // ---- S1: window + radix-8 + twiddle -> Y[f][k1][n2]; two frames per iteration, next iteration's samples in flight
-        const int nit = (nf + 1) >> 1;                          // frame pairs that exist (a short group stops early)
+    };
+    int item = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * nwv + wv));
+    // flat items: (clip, frame) of the item's first frame, advanced by FE2_G * stride frames per round without a division
+    int fb = 0, ft = 0, fdb = 0, fdt = 0;
+    if (FLAT) {
+        const int g0 = FE2_G * item, step = FE2_G * stride;
+        fb = g0 / T; ft = g0 - fb * T;
+        fdb = step / T; fdt = step - fdb * T;
+    }
+    if (item < total) {
+        if (FLAT) flat_first(pcm + (size_t)fb * row_stride, ft, min(FE2_G, B * T - FE2_G * item));
+        else prefetch_first(item);
+    }
+    for (; item < total; item += stride) {
+        int b, t0, nf;
+        if (FLAT) { b = fb; t0 = ft; nf = min(FE2_G, B * T - FE2_G * item); }
+        else geom(item, b, t0, nf);
+        const int16_t* x = pcm + (size_t)b * row_stride;
+        if (FLAT) {
+            // ---- S1, flat items: trip k + 1's samples are requested in front of trip k's arithmetic; nothing is zeroed or predicated
+            auto s1_trip = [&](int f) {
+                if (!(dbg & 1)) {
+                    nww_c32 z[8];
+                    fe2_s1(cur, win, tw, z);
+                    nww_c32* y = reinterpret_cast<nww_c32*>(slab + f * FE2_FRAME_DW) + n2;
+#pragma unroll
+                    for (int k1 = 0; k1 < 8; ++k1) y[k1 * 25] = z[k1];
+                }
+            };
+            if (lane < 50) {
+                if (flat_plain(t0, nf)) {
+                    // rolled on purpose: hipcc contracts the complex multiplies of each unrolled copy of the S1 body its own way (which of the
+                    // two products goes into the fma), and the log-mel of a frame would then depend on its trip (variant C)
+                    uint32_t o = plain_off(t0, 1);
 #pragma unroll 1
-        for (int it = 0; it < nit; ++it) {
-            const int f = 2 * it + slot, fn = f + 2;
-            uint32_t nxt[8];
+                    for (int k = 0; k < FE2_G / 2; ++k) {
+                        uint32_t nxt[8];
+                        plain_load(x, o, nxt);
+                        s1_trip(2 * k + slot);
 #pragma unroll
-            for (int n1 = 0; n1 < 8; ++n1) nxt[n1] = 0u;
-            if (slot < 2 && fn < nf && it + 1 < FE2_G / 2) {
-                if (inner) {
-                    fe2_load_column(x, (t0 + fn) * hop - pad, n2, nxt);
-                } else {
+                        for (int n1 = 0; n1 < 8; ++n1) cur[n1] = nxt[n1];
+                        if (k + 2 < FE2_G / 2) o += 4u * (uint32_t)hop;      // (the last trip re-reads its own samples: no branch round the loads)
+                    }
+                } else {      // an edge frame, a clip boundary, the launch's last item or an unaligned batch: per-trip test, rolled
+#pragma unroll 1
+                    for (int k = 0; k < FE2_G / 2; ++k) {
+                        uint32_t nxt[8];
+                        uint32_t woff; int s0;
+                        flat_frame(t0, nf, min(k + 1, FE2_G / 2 - 1), woff, s0);      // (the last trip re-reads its own samples: no branch)
+                        flat_load(x, woff, s0, nxt);
+                        s1_trip(2 * k + slot);
 #pragma unroll
-                    for (int n1 = 0; n1 < 8; ++n1) nxt[n1] = span[((fn * hop) >> 1) + n2 + 25 * n1];
+                        for (int n1 = 0; n1 < 8; ++n1) cur[n1] = nxt[n1];
+                    }
                 }
             }
-            if (slot < 2 && f < nf && !(dbg & 1)) {
-                nww_c32 z[8];
-                fe2_s1(cur, win, tw, z);
-                nww_c32* y = reinterpret_cast<nww_c32*>(slab + f * FE2_FRAME_DW) + n2;
+        } else {
+            const bool inner = interior(t0, nf);
+            const uint32_t* span = reinterpret_cast<const uint32_t*>(slab + 6 * FE2_FRAME_DW);
+            if (!inner) {      // edge item: reflect-padded span -> LDS
+                const int s0 = t0 * hop - pad, npairs = ((nf - 1) * hop + FE_NFFT) >> 1;
+                uint32_t* sp = reinterpret_cast<uint32_t*>(slab + 6 * FE2_FRAME_DW);
+                for (int i = lane; i < npairs; i += 64) {
+                    const int q = s0 + 2 * i;
+                    sp[i] = (uint32_t)(uint16_t)x[fe_reflect(q, N)] | ((uint32_t)(uint16_t)x[fe_reflect(q + 1, N)] << 16);
+                }
+                fe2_wave_sync();
+                if (slot < nf && slot < 2) {
 #pragma unroll
-                for (int k1 = 0; k1 < 8; ++k1) y[k1 * 25] = z[k1];
+                    for (int n1 = 0; n1 < 8; ++n1) cur[n1] = span[((slot * hop) >> 1) + n2 + 25 * n1];
+                }
             }
+            // ---- S1: window + radix-8 + twiddle -> Y[f][k1][n2]; two frames per iteration, next iteration's samples in flight
+            const int nit = (nf + 1) >> 1;                          // frame pairs that exist (a short group stops early)
+#pragma unroll 1
+            for (int it = 0; it < nit; ++it) {
+                const int f = 2 * it + slot, fn = f + 2;
+                uint32_t nxt[8];
 #pragma unroll
-            for (int n1 = 0; n1 < 8; ++n1) cur[n1] = nxt[n1];
+                for (int n1 = 0; n1 < 8; ++n1) nxt[n1] = 0u;
+                if (slot < 2 && fn < nf && it + 1 < FE2_G / 2) {
+                    if (inner) {
+                        fe2_load_column(x, (t0 + fn) * hop - pad, n2, nxt);
+                    } else {
+#pragma unroll
+                        for (int n1 = 0; n1 < 8; ++n1) nxt[n1] = span[((fn * hop) >> 1) + n2 + 25 * n1];
+                    }
+                }
+                if (slot < 2 && f < nf && !(dbg & 1)) {
+                    nww_c32 z[8];
+                    fe2_s1(cur, win, tw, z);
+                    nww_c32* y = reinterpret_cast<nww_c32*>(slab + f * FE2_FRAME_DW) + n2;
+#pragma unroll
+                    for (int k1 = 0; k1 < 8; ++k1) y[k1 * 25] = z[k1];
+                }
+#pragma unroll
+                for (int n1 = 0; n1 < 8; ++n1) cur[n1] = nxt[n1];
+            }
         }
         fe2_wave_sync();
         // ---- S2: 25-point DFT of row k1, in place, output in natural bin order Z[k1 + 8 k2]
@@ -215,7 +334,11 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
         }
         fe2_wave_sync();
         // next item's samples: in flight during S3/S4 (S2, the register-hungry stage, is behind us)
-        if (item + stride < total) prefetch_first(item + stride);
+        if (FLAT) {
+            fb += fdb; ft += fdt;
+            if (ft >= T) { ft -= T; ++fb; }
+            if (item + stride < total) flat_first(pcm + (size_t)fb * row_stride, ft, min(FE2_G, B * T - FE2_G * (item + stride)));
+        } else if (item + stride < total) prefetch_first(item + stride);
         // ---- S3: split + power, in place.  All of a frame's reads precede its writes (one wave, LDS in order).
         if (!(dbg & 4)) {
             const nww_c32* z0 = reinterpret_cast<const nww_c32*>(slab);
@@ -393,7 +516,7 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
             float* dst = out_db + ((size_t)b * T + t0) * n_mels;
             if ((n_mels & 3) == 0) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < NCO; ++r) {
                     const int i = 4 * lane + 256 * r;
                     if (i < cnt) *reinterpret_cast<float4*>(dst + i) = *reinterpret_cast<const float4*>(slab + co_off[r]);
                 }
@@ -409,8 +532,8 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
     }
 }
 
-template <int MEL, int FAST_OUT, int MAXT, bool RING = false>
-__global__ void __launch_bounds__(256, 3) fe2_wave_kernel(FE2_PARAMS) { fe2_wave_body<MEL, FAST_OUT, MAXT, RING>(FE2_ARGS); }
+template <int MEL, int FAST_OUT, int MAXT, bool RING = false, bool FLAT = false>
+__global__ void __launch_bounds__(256, 3) fe2_wave_kernel(FE2_PARAMS) { fe2_wave_body<MEL, FAST_OUT, MAXT, RING, FLAT>(FE2_ARGS); }
 
 // the streaming instances exist for the frames-major fast output with the mel stage on register filters or MFMA tiles
 bool fe2_subset_supported(const FeParams& p, int mel_mode) { return mel_mode != 0 && (p.n_mels & 3) == 0; }
@@ -444,15 +567,6 @@ hipError_t fe2_launch(const int16_t* d_pcm, size_t row_stride, int B, int N, int
     const int fast = (frames_major && d_db && !d_mel) ? 1 : 0;
     const bool ring = sub.nr > 0 || sub.ring_rows > 0;
     if (ring && (mode == 0 || !fast)) return hipErrorInvalidValue;
-    auto kern = mode == 0 ? fe2_wave_kernel<0, 0, 1>
-              : mode == 1 ? (ring ? fe2_wave_kernel<1, 1, 1, true> : fast ? fe2_wave_kernel<1, 1, 1> : fe2_wave_kernel<1, 0, 1>)
-              : max_taps <= 17 ? (ring ? fe2_wave_kernel<2, 1, 20, true> : fast ? fe2_wave_kernel<2, 1, 20> : fe2_wave_kernel<2, 0, 20>)
-                               : (ring ? fe2_wave_kernel<2, 1, 28, true> : fast ? fe2_wave_kernel<2, 1, 28> : fe2_wave_kernel<2, 0, 28>);
-    const void* fn = reinterpret_cast<const void*>(kern);
-    {
-        hipError_t e = nww_allow_lds(fn, (size_t)lds);
-        if (e != hipSuccess) return e;
-    }
 #ifdef NWW_ABLATION      // stage-skipping builds for phase timing (results are garbage): never in the shipped library
     static const int dbg = [] { const char* e = getenv("NWW_FE_DBG"); return e ? atoi(e) : 0; }();
 #else
@@ -466,7 +580,22 @@ hipError_t fe2_launch(const int16_t* d_pcm, size_t row_stride, int B, int N, int
         gsz = small_g;
         ngroups = count_groups(gsz);
     }
-    const long long total = (long long)B * ngroups;
+    // the batch launches (frames-major fast output, register filters, FE2_G frames per item, every frame): items over the batch's frames, not
+    // per clip.  Not the MFMA-mel instance: hipcc contracts its S1 body differently once the loop round it changes, and its log-mel would
+    // no longer be the per-clip map's bit for bit.  Not T == FE2_G either: there an item is a clip in both maps, every item has edge frames at
+    // both ends, and the per-clip map's staged span is the faster of the two (0.0184 against 0.0189 ms for 4096 clips).
+    const bool flat = fast && !ring && mode == 2 && gsz == FE2_G && T != FE2_G && (long long)B * T <= 0x7fffffffLL - FE2_G &&
+                      (unsigned long long)row_stride * FE2_G + (unsigned long long)N < (1ull << 31);     // (32-bit byte offsets inside an item)
+    auto kern = mode == 0 ? fe2_wave_kernel<0, 0, 1>
+              : mode == 1 ? (ring ? fe2_wave_kernel<1, 1, 1, true> : fast ? fe2_wave_kernel<1, 1, 1> : fe2_wave_kernel<1, 0, 1>)
+              : max_taps <= 17 ? (ring ? fe2_wave_kernel<2, 1, 20, true> : flat ? fe2_wave_kernel<2, 1, 20, false, true> : fast ? fe2_wave_kernel<2, 1, 20> : fe2_wave_kernel<2, 0, 20>)
+                               : (ring ? fe2_wave_kernel<2, 1, 28, true> : flat ? fe2_wave_kernel<2, 1, 28, false, true> : fast ? fe2_wave_kernel<2, 1, 28> : fe2_wave_kernel<2, 0, 28>);
+    const void* fn = reinterpret_cast<const void*>(kern);
+    {
+        hipError_t e = nww_allow_lds(fn, (size_t)lds);
+        if (e != hipSuccess) return e;
+    }
+    const long long total = flat ? ((long long)B * T + FE2_G - 1) / FE2_G : (long long)B * ngroups;
     long long need = (total + nwv - 1) / nwv;
     int grid = (int)(need < max_grid ? need : max_grid);
     if (grid < 1) grid = 1;
