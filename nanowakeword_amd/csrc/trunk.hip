@@ -200,10 +200,23 @@ __global__ void __launch_bounds__(64 * NW, 2) cnn_trunk_kernel(TrunkArgs a) {
             }
         }
     };
+    // (value by value, LSB loads per thread in flight before the first is used: the trip count is the workgroup's, the indices are
+    // clamped and what lies behind the rows is loaded again and dropped)
     auto load_plane_sync = [&](const float* xin) {
-        for (int idx = tid; idx < n_in; idx += NTHR) {
-            const int y = idx / W, x = idx - y * W;
-            In[(y + row_shift) * Wp0 + x + 1] = xin[idx];
+        constexpr int LSB = 8;
+        for (int base = 0; base < n_in; base += LSB * NTHR) {
+            float v[LSB];
+#pragma unroll
+            for (int u = 0; u < LSB; ++u) v[u] = xin[min(base + tid + u * NTHR, n_in - 1)];
+            // one statement that needs them all: the batch is in flight before the first wait, and a dropped value leaves no load pending
+            asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+#pragma unroll
+            for (int u = 0; u < LSB; ++u) {
+                const int idx = base + tid + u * NTHR;
+                if (idx >= n_in) continue;
+                const int y = idx / W, x = idx - y * W;
+                In[(y + row_shift) * Wp0 + x + 1] = v[u];
+            }
         }
     };
     const int b0 = STRIP ? (int)blockIdx.x / S : (int)blockIdx.x, bstep = STRIP ? (int)gridDim.x / S : (int)gridDim.x;

@@ -25,9 +25,13 @@
 // in registers (24 of 27; the last tap's three come from LDS per tile).
 //
 // Schedule: an item is (clip, row strip); all eight waves run conv1 of the item (planes -> A1), a barrier, then its conv2
-// tiles while the next item's rows travel from HBM into registers, a barrier.  The weight fragments of both convolutions
-// are split and laid out ONCE at plan time (launch_trunk_b_pack; splitting them in every workgroup cost 20 us of a 380 us
-// launch).  What bounds the kernel (tools/ubench/trunk_trace.hip): with all 256 CUs busy the chip is
+// tiles while the next item's rows travel from HBM into registers, a barrier.  Start-up (one persistent workgroup per CU: whatever
+// it costs is paid on every CU at once): the first item's rows, the weight fragments and the epilogue constants are all requested at
+// entry, the LDS is zeroed with 16-byte stores while they travel, and the first item's rows go to the planes the way every later
+// item's do; shapes without the chunk path stage every item value by value, eight loads per thread in flight.
+// The weight fragments of both convolutions are split and laid out ONCE at plan time (launch_trunk_b_pack; splitting them in
+// every workgroup cost 20 us of a 380 us launch).
+// What bounds the kernel (tools/ubench/trunk_trace.hip): with all 256 CUs busy the chip is
 // power-limited - the shader clock drops from 2.4 to 1.9-2.0 GHz while this kernel runs (2.37 GHz on 128 CUs, same clock
 // COUNT per item) - and schedules with very different overlap (conv1 of item k + 1 on four waves beside conv2 of item k
 // on the other four with double-buffered A1; the pooling epilogue of tile n inside tile n + 1's MFMA stream; wave
@@ -502,19 +506,72 @@ __device__ __forceinline__ void cnn_trunk_b_body(const TrunkArgs& a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, hi = lane >> 5;
 
-    // zero the planes and A1 once: halos stay zero, interiors are rewritten per item
-    for (int k = tid; k < (NT * plane_b + a1_b) / 4; k += NTHR) reinterpret_cast<uint32_t*>(lds_raw)[k] = 0u;
+    // input rows -> the NT planes of 16-bit terms (zero halo): value (y, x) at column x + 1 of local row y + row_shift.
+    // A thread moves CHUNKS of four plane columns 4 j .. 4 j + 3 = inputs x = 4 j - 1 .. 4 j + 2 (W / 4 + 1 chunks per row): one
+    // 16-byte load (dword aligned) and one aligned 8-byte LDS store per term.  Chunks of four INPUTS land two bytes off an
+    // 8-byte boundary, and those misaligned LDS stores cost 3.7 k of an item's 19 k clocks (tools/ubench/trunk_trace.hip, -DTB_ABL=32).
+    // (two-term form: the input is clamped to +-f16_clamp, the bound the plan-time scales were derived from - whatever comes in,
+    // no term can leave the binary16 range.  Log-mel dB values never reach it.)
+    const float s_in = F16 ? a.f16_in : 1.0f, c_in = F16 ? a.f16_clamp * s_in : 0.0f;
+    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+    constexpr int NPRE = 2;                                     // chunks per thread for the rows of an item in flight
+    const int CPR = W / 4 + 1, n_chunks = (n_in / W) * CPR;
+    const bool vec_in = (W & 3) == 0 && (in_clip & 3) == 0 && n_chunks <= NPRE * NTHR;
+    int ch_src[NPRE], ch_dst[NPRE], ch_kind[NPRE];              // float offset in the item's rows, byte offset in a plane, 0 / 1 / 2 = first / inner / last chunk of a row
+#pragma unroll
+    for (int q = 0; q < NPRE; ++q) {
+        const int c = tid + q * NTHR, y = c / CPR, j = c - y * CPR;
+        ch_kind[q] = c >= n_chunks ? -1 : j == 0 ? 0 : j == CPR - 1 ? 2 : 1;
+        ch_src[q] = c >= n_chunks ? 0 : y * W + (j == 0 ? 0 : j == CPR - 1 ? W - 4 : 4 * j - 1);      // (a surplus chunk: somewhere loadable)
+        ch_dst[q] = ((y + row_shift) * Wp0 + 4 * j) * 2;
+    }
+    // rows of item bb -> registers (a float4 or two per thread).  all: the surplus chunks load too (and are never stored) - no load
+    // of the start-up sits behind a branch
+    float4 pre[NPRE];
+    auto fetch_rows = [&](int bb, bool all = false) {
+        if (TB_ABL & 64) return;
+        const float* xin = a.in + (size_t)bb * in_clip + in_off;
+#pragma unroll
+        for (int q = 0; q < NPRE; ++q)
+            if (all || ch_kind[q] >= 0) {
+                const f32x4u v = *reinterpret_cast<const f32x4u*>(xin + ch_src[q]);
+                pre[q] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+    };
+    // Start-up: every load the first item needs is requested before anything waits - the first item's rows (the chunk path of every
+    // later item; a workgroup without an item fetches the last clip's and drops them), the weight fragments, the epilogue constants -
+    // and the LDS is zeroed while they travel.  (Zeroing first and the rows value by value behind it, one load in flight per thread:
+    // DESIGN.md 4.2.)
+    const bool first_vec = vec_in && !(TB_ABL & (32 | 64));
+    if (first_vec) fetch_rows(min(b0, a.B - 1), true);
 
     // weight fragments: conv2's first NWA (24 of 27, or all 18) stay in registers, the rest and conv1's are parked in LDS by wave 0
     const bf16x8* wp = reinterpret_cast<const bf16x8*>(a.wpack) + lane;
-    bf16x8 bw[NWA];
+    bf16x8 bw[NWA], wpark[NWL + NF1];
 #pragma unroll
     for (int j = 0; j < NWA; ++j) bw[j] = wp[j * 64];
     if (wave == 0) {
 #pragma unroll
-        for (int j = 0; j < NWL; ++j) *reinterpret_cast<bf16x8*>(W2L + j * 1024 + lane * 16) = wp[(NWA + j) * 64];
+        for (int j = 0; j < NWL + NF1; ++j) wpark[j] = wp[(NWA + j) * 64];
+    }
+    float bias2 = a.b2 ? a.b2[i] : 0.0f;
+    float al2 = (BN && a.al2) ? a.al2[i] : 1.0f, be2 = (BN && a.al2) ? a.be2[i] : 0.0f;
+    float b1v[8], nb1v[8], al1v[8], be1v[8];
 #pragma unroll
-        for (int j = 0; j < NF1; ++j) *reinterpret_cast<bf16x8*>(W1F + j * 1024 + lane * 16) = wp[(NF2 + j) * 64];
+    for (int cc = 0; cc < 8; ++cc) {
+        b1v[cc] = a.b1 ? a.b1[8 * hi + cc] : 0.0f;
+        al1v[cc] = (BN && a.al1) ? a.al1[8 * hi + cc] : 1.0f;
+        be1v[cc] = (BN && a.al1) ? a.be1[8 * hi + cc] : 0.0f;
+    }
+
+    // zero the planes and A1 once: halos stay zero, interiors are rewritten per item
+    for (int k = tid; k < (NT * plane_b + a1_b) / 16; k += NTHR) reinterpret_cast<uint4*>(lds_raw)[k] = make_uint4(0u, 0u, 0u, 0u);
+
+    if (wave == 0) {
+#pragma unroll
+        for (int j = 0; j < NWL; ++j) *reinterpret_cast<bf16x8*>(W2L + j * 1024 + lane * 16) = wpark[j];
+#pragma unroll
+        for (int j = 0; j < NF1; ++j) *reinterpret_cast<bf16x8*>(W1F + j * 1024 + lane * 16) = wpark[NWL + j];
     }
     // (measured for the two-term form: without any AGPR constraint hipcc allocates 183 VGPRs and VGPR-form MFMAs, whose operand
     // traffic starves the SIMD's other wave of VALU issue - 0.254 ms against 0.236 with the fragments pinned here)
@@ -525,18 +582,12 @@ __device__ __forceinline__ void cnn_trunk_b_body(const TrunkArgs& a) {
     const float k1 = F16 ? a.f16_k1 : 1.0f, s1 = F16 ? a.f16_s1 : 1.0f, k2 = F16 ? a.f16_k2 : 1.0f, s2 = F16 ? a.f16_so : 1.0f;
     constexpr bool RELU = ACT == ACT_RELU;
     const float post1 = RELU ? s1 / k1 : s1, post2 = RELU ? s2 / k2 : s2;
-    float bias2 = a.b2 ? a.b2[i] : 0.0f;
-    float al2 = (BN && a.al2) ? a.al2[i] : 1.0f, be2 = (BN && a.al2) ? a.be2[i] : 0.0f;
     if (F16) {
         bias2 *= k2;
         if (RELU) { al2 *= s2 / k2; be2 *= s2; } else al2 /= k2;
     }
-    float b1v[8], nb1v[8], al1v[8], be1v[8];
 #pragma unroll
     for (int cc = 0; cc < 8; ++cc) {
-        b1v[cc] = a.b1 ? a.b1[8 * hi + cc] : 0.0f;
-        al1v[cc] = (BN && a.al1) ? a.al1[8 * hi + cc] : 1.0f;
-        be1v[cc] = (BN && a.al1) ? a.be1[8 * hi + cc] : 0.0f;
         if (F16) {
             b1v[cc] *= k1;
             if (RELU) { al1v[cc] *= s1 / k1; be1v[cc] *= s1; } else al1v[cc] /= k1;
@@ -555,25 +606,6 @@ __device__ __forceinline__ void cnn_trunk_b_body(const TrunkArgs& a) {
     const int blk_kt = a.out_blocked;
     const int out_lane = ring ? i * (int)a.out_ch_stride + 4 * hi : i * H2 * W2 + 4 * hi;
 
-    // input rows -> the NT planes of 16-bit terms (zero halo): value (y, x) at column x + 1 of local row y + row_shift.
-    // A thread moves CHUNKS of four plane columns 4 j .. 4 j + 3 = inputs x = 4 j - 1 .. 4 j + 2 (W / 4 + 1 chunks per row): one
-    // 16-byte load (dword aligned) and one aligned 8-byte LDS store per term.  Chunks of four INPUTS land two bytes off an
-    // 8-byte boundary, and those misaligned LDS stores cost 3.7 k of an item's 19 k clocks (tools/ubench/trunk_trace.hip, -DTB_ABL=32).
-    // (two-term form: the input is clamped to +-f16_clamp, the bound the plan-time scales were derived from - whatever comes in,
-    // no term can leave the binary16 range.  Log-mel dB values never reach it.)
-    const float s_in = F16 ? a.f16_in : 1.0f, c_in = F16 ? a.f16_clamp * s_in : 0.0f;
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-    constexpr int NPRE = 2;                                     // chunks per thread for the rows of an item in flight
-    const int CPR = W / 4 + 1, n_chunks = (n_in / W) * CPR;
-    const bool vec_in = (W & 3) == 0 && (in_clip & 3) == 0 && n_chunks <= NPRE * NTHR;
-    int ch_src[NPRE], ch_dst[NPRE], ch_kind[NPRE];              // float offset in the item's rows, byte offset in a plane, 0 / 1 / 2 = first / inner / last chunk of a row
-#pragma unroll
-    for (int q = 0; q < NPRE; ++q) {
-        const int c = tid + q * NTHR, y = c / CPR, j = c - y * CPR;
-        ch_kind[q] = c >= n_chunks ? -1 : j == 0 ? 0 : j == CPR - 1 ? 2 : 1;
-        ch_src[q] = y * W + (j == 0 ? 0 : j == CPR - 1 ? W - 4 : 4 * j - 1);
-        ch_dst[q] = ((y + row_shift) * Wp0 + 4 * j) * 2;
-    }
     auto store_chunk = [&](unsigned char* planes, int q, float4 v) {
         if (ch_kind[q] == 0) v = make_float4(0.0f, v.x, v.y, v.z);             // column 0 is the halo
         else if (ch_kind[q] == 2) v = make_float4(v.w, 0.0f, 0.0f, 0.0f);     // input W - 1, then the halo
@@ -593,21 +625,35 @@ __device__ __forceinline__ void cnn_trunk_b_body(const TrunkArgs& a) {
                 *reinterpret_cast<uint2*>(d + t * plane_b) = make_uint2(pack_hi16(w[t][0], w[t][1]), pack_hi16(w[t][2], w[t][3]));
         }
     };
+    // the general loader (shapes without the chunk path): value by value, LSB loads per thread in flight before the first is used - the
+    // trip count is the workgroup's, the indices are clamped and what lies behind the rows is loaded again and dropped
     auto load_plane_sync = [&](unsigned char* planes, const float* xin) {
-        for (int idx = tid; idx < n_in; idx += NTHR) {
-            const int y = idx / W, x = idx - y * W;
-            unsigned char* d = planes + ((y + row_shift) * Wp0 + x + 1) * 2;
-            if (F16) {
-                uint32_t h, l;
-                nww_split2h(__builtin_amdgcn_fmed3f(xin[idx] * s_in, -c_in, c_in), 0.0f, h, l);
-                *reinterpret_cast<uint16_t*>(d) = (uint16_t)h;
-                *reinterpret_cast<uint16_t*>(d + plane_b) = (uint16_t)l;
-            } else {
-                uint32_t wh, wm, wlo;
-                split3(xin[idx], wh, wm, wlo);
-                *reinterpret_cast<uint16_t*>(d) = (uint16_t)(wh >> 16);
-                *reinterpret_cast<uint16_t*>(d + plane_b) = (uint16_t)(wm >> 16);
-                *reinterpret_cast<uint16_t*>(d + 2 * plane_b) = (uint16_t)(wlo >> 16);
+        constexpr int LSB = 8;
+        for (int base = 0; base < n_in; base += LSB * NTHR) {
+            float v[LSB];
+#pragma unroll
+            for (int u = 0; u < LSB; ++u) v[u] = xin[min(base + tid + u * NTHR, n_in - 1)];
+            // one statement that needs them all: the batch is in flight before the first wait, and a dropped value leaves no load pending
+            // on its register (hipcc would wait for it with vmcnt(0) wherever that register is next written - at the head of conv1)
+            asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+#pragma unroll
+            for (int u = 0; u < LSB; ++u) {
+                const int idx = base + tid + u * NTHR;
+                if (idx >= n_in) continue;
+                const int y = idx / W, x = idx - y * W;
+                unsigned char* d = planes + ((y + row_shift) * Wp0 + x + 1) * 2;
+                if (F16) {
+                    uint32_t h, l;
+                    nww_split2h(__builtin_amdgcn_fmed3f(v[u] * s_in, -c_in, c_in), 0.0f, h, l);
+                    *reinterpret_cast<uint16_t*>(d) = (uint16_t)h;
+                    *reinterpret_cast<uint16_t*>(d + plane_b) = (uint16_t)l;
+                } else {
+                    uint32_t wh, wm, wlo;
+                    split3(v[u], wh, wm, wlo);
+                    *reinterpret_cast<uint16_t*>(d) = (uint16_t)(wh >> 16);
+                    *reinterpret_cast<uint16_t*>(d + plane_b) = (uint16_t)(wm >> 16);
+                    *reinterpret_cast<uint16_t*>(d + 2 * plane_b) = (uint16_t)(wlo >> 16);
+                }
             }
         }
     };
@@ -742,20 +788,17 @@ __device__ __forceinline__ void cnn_trunk_b_body(const TrunkArgs& a) {
         }
     };
 
-    // rows of item bb -> registers (a float4 or two per thread)
-    float4 pre[NPRE];
-    auto fetch_rows = [&](int bb) {
-        if (TB_ABL & 64) return;
-        const float* xin = a.in + (size_t)bb * in_clip + in_off;
-#pragma unroll
-        for (int q = 0; q < NPRE; ++q)
-            if (ch_kind[q] >= 0) {
-                const f32x4u v = *reinterpret_cast<const f32x4u*>(xin + ch_src[q]);
-                pre[q] = make_float4(v[0], v[1], v[2], v[3]);
-            }
-    };
     __syncthreads();
-    if (b0 < a.B) load_plane_sync(In3, a.in + (size_t)b0 * in_clip + in_off);
+    // the first item's rows, in registers since the entry, go the way of every later item's; only then are the second item's requested
+    if (b0 < a.B) {
+        if (first_vec) {
+#pragma unroll
+            for (int q = 0; q < NPRE; ++q)
+                if (ch_kind[q] >= 0) store_chunk(In3, q, pre[q]);
+        } else {
+            load_plane_sync(In3, a.in + (size_t)b0 * in_clip + in_off);
+        }
+    }
     if (vec_in && b0 + bstep < a.B) fetch_rows(b0 + bstep);
     __syncthreads();
     // ---- two phases per item, all eight waves in each: conv1 (planes -> A1) | the next item's rows -> planes, conv2.
@@ -1331,6 +1374,7 @@ static hipError_t launch_cnn_trunk_b_stream(TrunkArgs aa, int products, int max_
 
 hipError_t launch_cnn_trunk_b(const TrunkArgs& a, int products, int max_grid, hipStream_t s) {
     if (!a.wpack || (products != 3 && products != 6 && products != 9)) return hipErrorInvalidValue;
+    if (a.B <= 0) return hipSuccess;        // (the kernel's start-up fetches clip min(b0, B - 1))
     TrunkArgs aa = a;
     if (a.n_sub > 0 || a.out_ring_rows > 0) return launch_cnn_trunk_b_stream(aa, products, max_grid, s);
     int S = trunk_b_pick_strips(a.H, a.W);
