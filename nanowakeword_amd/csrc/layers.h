@@ -2,6 +2,7 @@
 // activations NCHW per clip like the reference's torch modules so flatten orders match the weights.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "rnn.h"
 
 // Raise a kernel's dynamic-LDS limit once per (device, kernel).  The attribute is per device: a process that creates
 // handles on several GPUs must set it on each of them, so the cache is keyed by the current device as well.
@@ -153,49 +154,9 @@ bool mha_h2_supported(int T, int D, int n_head);
 hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0);
 // [B][C][H][W] -> [B][W][C*H]  (CRNN: sequence over W, features C*H; architectures.py:272-276)
 hipError_t launch_crnn_seq(const float* in, float* out, int B, int C, int H, int W, hipStream_t s);
-// GRU recurrence for one direction. xg [B][T][3H] = x W_ih^T + b_ih (precomputed by GEMM).
-// reverse=0: t = 0..T-1; reverse=1: t = T-1..0.  steps = number of steps to run (T, or 1 for the
-// "last step of a reverse direction" shortcut).  seq_out (may be null) [B][T][ld_seq] receives h at
-// column offset col_off for every visited t; last_out (may be null) [B][ld_last] at col_off gets the
-// h after the final visited step... see layers.hip.
-struct GruArgs {
-    const float* xg; const float* w_hh; const float* b_hh;
-    float* seq_out; int ld_seq; float* last_out; int ld_last; int col_off;
-    int B, T, H, reverse, steps;
-    int products = 0;      // 6 / 9: recurrent product from split operands on the bf16 matrix cores (rnn_x3.hip), 0: float32 MFMA;
-                           // 3: two binary16 terms per operand (h times 2^14 - |h| <= 1 - and W_hh times w_scale, a power of two)
-    float w_scale = 1.0f;
-    // rnn_x3 only: the FIRST step of the opposite direction (all that rnn_out[:, -1] needs of it; h = 0, so no recurrent product)
-    // computed in the same launch from its gate pre-activations xg2 [B][xg2_bstride] and recurrent bias -> last_out[:, col_off2 + j]
-    const float* xg2 = nullptr; size_t xg2_bstride = 0; const float* b_hh2 = nullptr; int col_off2 = 0;
-    int ldw = 0;           // > 0: w_hh is the zero-padded [gates H][ldw] copy of launch_rnn_pad_weights -> the any-width kernel (H <= 512)
-    // rnn_x3, GRU, products = 3 only: fin = 32 / 64 > 0 fuses the INPUT projection into the recurrence - xg is not read; the step's gate
-    // pre-activations x_t W_ih^T + b_ih come from x_in [B][T][fin] (clamped to +-x_clamp, times x_scale) and w_ih [3 H][fin] (times
-    // wi_scale) as two binary16 terms each, on the matrix pipe beside the recurrent product (the GRU head's 64 mel bins: no 635 MB
-    // round trip of gate pre-activations through HBM)
-    const float* x_in = nullptr; const float* w_ih = nullptr; const float* b_ih = nullptr;
-    int fin = 0; float x_scale = 1.0f, x_clamp = 0.0f, wi_scale = 1.0f;
-    // rnn_stream (128 < H <= 256, products = 3): W_hh x w_scale as two binary16 terms in MFMA fragment order (launch_rnn_stream_pack), read every step
-    const void* w_packed = nullptr;
-    int cu_count = 256;    // the device's compute units (rnn_stream: 16-clip tiles up to B = 16 x cu_count, 32-clip tiles beyond)
-    int dbg = 0;           // NWW_ABLATION builds only (rnn_stream: phase-skipping for timing; results are garbage)
-};
-size_t rnn_wide_weight_bytes(int gates, int H);
-hipError_t launch_rnn_pad_weights(const float* w_hh, float* out, int gates, int H, hipStream_t s);
-hipError_t launch_gru(const GruArgs& a, hipStream_t s);
 // out[f][kx][ky] = w[f][ky][kx] for nfilters 3x3 filters; [B][R][C] -> [B][C][R]
 hipError_t launch_transpose3x3(const float* w, float* out, int nfilters, hipStream_t s);
 hipError_t launch_transpose_planes(const float* in, float* out, int B, int R, int C, hipStream_t s);
-// rnn_x3.hip: gates = 3 (GRU) / 4 (LSTM), H in {32, 64, 128}
-bool rnn_x3_usable(const GruArgs& a);
-hipError_t launch_rnn_x3(const GruArgs& a, int gates, hipStream_t s);
-// rnn_stream.hip: 128 < H <= 256 (H % 4 == 0), two-term form, W_hh streamed from L2 each step
-bool rnn_stream_usable(const GruArgs& a);
-size_t rnn_stream_packed_bytes(int gates, int H);
-hipError_t launch_rnn_stream_pack(const float* w_hh, void* packed, int gates, int H, float w_scale, hipStream_t s);
-hipError_t launch_rnn_stream(const GruArgs& a, int gates, hipStream_t s);
-// LSTM recurrence for one direction, same arguments (xg is [B][T][4H], gate order i, f, g, o)
-hipError_t launch_lstm(const GruArgs& a, hipStream_t s);
 
 // Tail of every head in ONE launch: emb = x We^T + be  (the head's last Linear, written to `emb`),
 // hid = act(emb W0^T + b0), logit = hid . w3 + b3, prob = sigmoid(logit) when `probs` is set

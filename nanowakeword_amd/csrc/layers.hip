@@ -1134,578 +1134,6 @@ hipError_t launch_scale_add_pe(float* x, const float* pe, int B, int T, int D, f
 
 bool mha_head_dim_supported(int dh) { return dh >= 1 && mha_compiled_width(dh) > 0; }
 
-// ------------------------------------------------------------------------------------------ GRU recurrence
-// Gate functions of the register-resident recurrences on the hardware exp2 and reciprocal (1 ulp each): absolute error
-// <= 2e-7 against ~30 (sigmoid: expf + IEEE division) and ~40 (tanhf) instructions each - the gate arithmetic of a step was
-// as long as its matrix products.  tanh x = 1 - 2 / (1 + e^2x) saturates correctly through exp2 = 0 / inf.
-__device__ __forceinline__ float rnn_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float rnn_tanh(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * v)); }
-// One workgroup = 32 clips x all H hidden units; wave w owns hidden units [32w, 32w+32) and computes, per
-// step, the three 32x32 gate tiles (r, z, n columns j, H+j, 2H+j) of  hg = h W_hh^T  on MFMA f32, with h as the
-// A operand read from LDS ([32][H+4] floats) and W_hh rows streamed from L2.  Gate math runs in the MFMA C
-// layout (lane = hidden unit j, 16 clips per lane), so xg loads and h stores are coalesced along j, and
-// h_prev stays in registers across steps.  PyTorch semantics: r,z = sigmoid(xg + hg + b_hh);
-// n = tanh(xg_n + r*(hg_n + b_hn)); h' = (1-z) n + z h.
-__global__ void __launch_bounds__(512) gru_kernel(GruArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* hs = reinterpret_cast<float*>(smem_raw);           // [32][H+4]
-    const int H = a.H, ldh = H + 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 31, hh = lane >> 5;
-    const int b0 = blockIdx.x * 32;
-    const int j = wave * 32 + i;                              // hidden unit of this lane (C-layout column)
-    const bool jok = j < H;
-    const int jc = jok ? j : H - 1;
-    for (int idx = threadIdx.x; idx < 32 * ldh; idx += blockDim.x) hs[idx] = 0.0f;
-    float hprev[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hprev[r] = 0.0f;
-    const float bhr = a.b_hh[jc], bhz = a.b_hh[H + jc], bhn = a.b_hh[2 * H + jc];
-    const float* wr = a.w_hh + (size_t)jc * H + 4 * hh;       // B operand rows (col = lane&31 -> same jc)
-    const float* wz = a.w_hh + (size_t)(H + jc) * H + 4 * hh;
-    const float* wn = a.w_hh + (size_t)(2 * H + jc) * H + 4 * hh;
-    const float* arow = hs + (size_t)i * ldh + 4 * hh;        // A operand row (clip i)
-    __syncthreads();
-    for (int step = 0; step < a.steps; ++step) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-        f32x16 ar, az, an;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { ar[r] = 0.0f; az[r] = 0.0f; an[r] = 0.0f; }
-        // the input-side gate pre-activations of this step do not depend on h: fetch them (HBM, one row per clip)
-        // before the recurrent product so their latency hides under the MFMA loop
-        float xr[16], xz[16], xn[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int b = b0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            xr[r] = xz[r] = xn[r] = 0.0f;
-            if (b < a.B && jok) {
-                const float* xg = a.xg + ((size_t)b * a.T + t) * 3 * H;
-                xr[r] = xg[j]; xz[r] = xg[H + j]; xn[r] = xg[2 * H + j];
-            }
-        }
-        if (step > 0) {                                       // h == 0 on the first step
-            // W_hh streams from L2 every step; the next 8-k slice is requested before the current one is multiplied
-            float4 nbr = make_float4(0, 0, 0, 0), nbz = nbr, nbn = nbr;
-            if (4 * hh + 4 <= H) {
-                nbr = *reinterpret_cast<const float4*>(wr); nbz = *reinterpret_cast<const float4*>(wz);
-                nbn = *reinterpret_cast<const float4*>(wn);
-            }
-            for (int k = 0; k < H; k += 8) {
-                float4 av = make_float4(0, 0, 0, 0);
-                const float4 br = nbr, bz = nbz, bn = nbn;
-                if (k + 4 * hh + 4 <= H) av = *reinterpret_cast<const float4*>(arow + k);
-                nbr = nbz = nbn = make_float4(0, 0, 0, 0);
-                if (k + 8 + 4 * hh + 4 <= H) {
-                    nbr = *reinterpret_cast<const float4*>(wr + k + 8);
-                    nbz = *reinterpret_cast<const float4*>(wz + k + 8);
-                    nbn = *reinterpret_cast<const float4*>(wn + k + 8);
-                }
-                ar = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, br.x, ar, 0, 0, 0);
-                az = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bz.x, az, 0, 0, 0);
-                an = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bn.x, an, 0, 0, 0);
-                ar = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, br.y, ar, 0, 0, 0);
-                az = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bz.y, az, 0, 0, 0);
-                an = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bn.y, an, 0, 0, 0);
-                ar = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, br.z, ar, 0, 0, 0);
-                az = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bz.z, az, 0, 0, 0);
-                an = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bn.z, an, 0, 0, 0);
-                ar = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, br.w, ar, 0, 0, 0);
-                az = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bz.w, az, 0, 0, 0);
-                an = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bn.w, an, 0, 0, 0);
-            }
-        }
-        __syncthreads();                                      // every wave has finished reading hs
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = (r & 3) + 8 * (r >> 2) + 4 * hh;    // clip row within the block
-            const int b = b0 + c;
-            float hn = 0.0f;
-            if (b < a.B && jok) {
-                const float rg = 1.0f / (1.0f + expf(-(xr[r] + ar[r] + bhr)));
-                const float zg = 1.0f / (1.0f + expf(-(xz[r] + az[r] + bhz)));
-                const float ng = tanhf(xn[r] + rg * (an[r] + bhn));
-                hn = (1.0f - zg) * ng + zg * hprev[r];
-                if (a.seq_out) a.seq_out[((size_t)b * a.T + t) * a.ld_seq + a.col_off + j] = hn;
-                if (a.last_out && step == a.steps - 1) a.last_out[(size_t)b * a.ld_last + a.col_off + j] = hn;
-            }
-            hprev[r] = hn;
-            if (jok) hs[(size_t)c * ldh + j] = hn;
-        }
-        __syncthreads();
-    }
-}
-
-// Register-resident variant for H in {32, 64, 128} (H = 256 would need 384 weight registers at two waves per SIMD): one workgroup = 16 clips, wave w owns hidden units [32w, 32w+32)
-// as two 16-wide column blocks per gate on v_mfma_f32_16x16x4_f32.  Lane (n = l&15, g = l>>4) feeds k = g*H/4 + s at MFMA
-// step s, so its slice of every W_hh row it needs is H/4 CONTIGUOUS floats, loaded once and kept in 6*H/4 VGPRs for
-// all steps (one wave per SIMD: the 512-register budget is there) - the 32-clip kernel above re-streams W_hh (3*H*H
-// floats) from L2 on every step.  Half the clips per workgroup also means twice the workgroups (256 at B = 4096) and half
-// the MFMA chain per step.  C layout: column = hidden unit, rows 4g..4g+3 = clips, so xg loads / h stores stay coalesced
-// along the hidden dimension.
-template <int H>
-__global__ void __launch_bounds__(64 * (H / 32), 1) gru16_kernel(GruArgs a) {
-    constexpr int KS = H / 4, LDH = H + 4;                    // MFMA steps per product, LDS row stride
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* hs = reinterpret_cast<float*>(smem_raw);           // [16][H+4]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int b0 = blockIdx.x * 16;
-    for (int idx = threadIdx.x; idx < 16 * LDH; idx += blockDim.x) hs[idx] = 0.0f;
-    // W_hh -> registers: gate q (r, z, n), column block bl, k slice g
-    float wreg[3][2][KS];
-    float bh[3][2];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int bl = 0; bl < 2; ++bl) {
-            const int j = 32 * wave + 16 * bl + n;
-            const float4* src = reinterpret_cast<const float4*>(a.w_hh + (size_t)(q * H + j) * H + g * KS);
-#pragma unroll
-            for (int s4 = 0; s4 < KS / 4; ++s4) {
-                const float4 v = src[s4];
-                wreg[q][bl][4 * s4] = v.x; wreg[q][bl][4 * s4 + 1] = v.y; wreg[q][bl][4 * s4 + 2] = v.z; wreg[q][bl][4 * s4 + 3] = v.w;
-            }
-            bh[q][bl] = a.b_hh[q * H + j];
-        }
-    float hprev[2][4];
-#pragma unroll
-    for (int bl = 0; bl < 2; ++bl)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) hprev[bl][r] = 0.0f;
-    const float* arow = hs + n * LDH + g * KS;                // A operand: clip n, k slice g
-    // input-side pre-activations (independent of h) are fetched ONE STEP AHEAD: a row per clip from HBM takes longer than a step's
-    // recurrent product
-    float xq[3][2][4], xnext[3][2][4];
-    auto fetch = [&](int step, float (&x)[3][2][4]) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = b0 + 4 * g + r;
-            const float* xg = a.xg + ((size_t)min(b, a.B - 1) * a.T + t) * 3 * H + 32 * wave + n;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) { x[q][0][r] = xg[q * H]; x[q][1][r] = xg[q * H + 16]; }
-        }
-    };
-    fetch(0, xq);
-    __syncthreads();
-    for (int step = 0; step < a.steps; ++step) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-        f32x4 acc[3][2];
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int bl = 0; bl < 2; ++bl) acc[q][bl] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (step + 1 < a.steps) fetch(step + 1, xnext);
-        if (step > 0) {                                       // h == 0 on the first step
-#pragma unroll
-            for (int s4 = 0; s4 < KS / 4; ++s4) {
-                const float4 av = *reinterpret_cast<const float4*>(arow + 4 * s4);
-                const float ae[4] = {av.x, av.y, av.z, av.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int q = 0; q < 3; ++q)
-#pragma unroll
-                        for (int bl = 0; bl < 2; ++bl)
-                            acc[q][bl] = __builtin_amdgcn_mfma_f32_16x16x4f32(ae[e], wreg[q][bl][4 * s4 + e], acc[q][bl], 0, 0, 0);
-            }
-        }
-        __syncthreads();                                      // every wave has finished reading hs
-#pragma unroll
-        for (int bl = 0; bl < 2; ++bl) {
-            const int j = 32 * wave + 16 * bl + n;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = 4 * g + r, b = b0 + c;
-                float hn = 0.0f;
-                if (b < a.B) {
-                    const float rg = rnn_sigmoid(xq[0][bl][r] + acc[0][bl][r] + bh[0][bl]);
-                    const float zg = rnn_sigmoid(xq[1][bl][r] + acc[1][bl][r] + bh[1][bl]);
-                    const float ng = rnn_tanh(xq[2][bl][r] + rg * (acc[2][bl][r] + bh[2][bl]));
-                    hn = (1.0f - zg) * ng + zg * hprev[bl][r];
-                    if (a.seq_out) a.seq_out[((size_t)b * a.T + t) * a.ld_seq + a.col_off + j] = hn;
-                    if (a.last_out && step == a.steps - 1) a.last_out[(size_t)b * a.ld_last + a.col_off + j] = hn;
-                }
-                hprev[bl][r] = hn;
-                hs[c * LDH + j] = hn;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int bl = 0; bl < 2; ++bl)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) xq[q][bl][r] = xnext[q][bl][r];
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------------------------ LSTM recurrence
-// nn.LSTM cell (PyTorch gate order i, f, g, o in the 4H rows of W_ih / W_hh): with xg = x W_ih^T + b_ih precomputed,
-//   i, f, o = sigmoid(xg + h W_hh^T + b_hh), g = tanh(.), c' = f c + i g, h' = o tanh(c')
-// (CRNNModel's default backend: nanowakeword/modules/architectures.py:247-254, model.py:214).  Same argument block as the
-// GRU (xg is [B][T][4H]); same "reverse direction of the last layer runs one step" shortcut in the plan.
-//
-// Generic kernel (any H % 4 == 0, H <= 512): 32 clips per workgroup, wave w owns hidden units [32w, 32w+32), W_hh
-// streamed from L2 every step, four 32x32 accumulators on v_mfma_f32_32x32x2_f32; h and c stay in registers in the
-// C layout, h also in LDS as the next step's A operand.
-__global__ void __launch_bounds__(512) lstm_kernel(GruArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* hs = reinterpret_cast<float*>(smem_raw);           // [32][H+4]
-    const int H = a.H, ldh = H + 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 31, hh = lane >> 5;
-    const int b0 = blockIdx.x * 32;
-    const int j = wave * 32 + i;
-    const bool jok = j < H;
-    const int jc = jok ? j : H - 1;
-    for (int idx = threadIdx.x; idx < 32 * ldh; idx += blockDim.x) hs[idx] = 0.0f;
-    float cprev[16];                                         // (the previous h is not needed by the LSTM cell update: only c is carried)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cprev[r] = 0.0f;
-    float bh[4];
-    const float* wq[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        bh[q] = a.b_hh[q * H + jc];
-        wq[q] = a.w_hh + (size_t)(q * H + jc) * H + 4 * hh;
-    }
-    const float* arow = hs + (size_t)i * ldh + 4 * hh;
-    __syncthreads();
-    for (int step = 0; step < a.steps; ++step) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-        // (opaque per step: the 16 gate-row and output addresses of the lane are not hoisted out of the step loop and spilled)
-        int hh_o = lane >> 5;
-        asm volatile("" : "+v"(hh_o));
-        f32x16 acc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[q][r] = 0.0f;
-        float xq[4][16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int b = b0 + (r & 3) + 8 * (r >> 2) + 4 * hh_o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xq[q][r] = 0.0f;
-            if (b < a.B && jok) {
-                const float* xg = a.xg + ((size_t)b * a.T + t) * 4 * H;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) xq[q][r] = xg[q * H + j];
-            }
-        }
-        if (step > 0) {
-            for (int k = 0; k < H; k += 8) {
-                float4 av = make_float4(0, 0, 0, 0), bw[4];
-                const bool ok = k + 4 * hh + 4 <= H;
-                if (ok) av = *reinterpret_cast<const float4*>(arow + k);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) bw[q] = ok ? *reinterpret_cast<const float4*>(wq[q] + k) : make_float4(0, 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bw[q].x, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bw[q].y, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bw[q].z, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bw[q].w, acc[q], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = (r & 3) + 8 * (r >> 2) + 4 * hh_o;
-            const int b = b0 + c;
-            float hn = 0.0f, cn = 0.0f;
-            if (b < a.B && jok) {
-                const float ig = 1.0f / (1.0f + expf(-(xq[0][r] + acc[0][r] + bh[0])));
-                const float fg = 1.0f / (1.0f + expf(-(xq[1][r] + acc[1][r] + bh[1])));
-                const float gg = tanhf(xq[2][r] + acc[2][r] + bh[2]);
-                const float og = 1.0f / (1.0f + expf(-(xq[3][r] + acc[3][r] + bh[3])));
-                cn = fg * cprev[r] + ig * gg;
-                hn = og * tanhf(cn);
-                if (a.seq_out) a.seq_out[((size_t)b * a.T + t) * a.ld_seq + a.col_off + j] = hn;
-                if (a.last_out && step == a.steps - 1) a.last_out[(size_t)b * a.ld_last + a.col_off + j] = hn;
-            }
-            cprev[r] = cn;
-            if (jok) hs[(size_t)c * ldh + j] = hn;
-        }
-        __syncthreads();
-    }
-}
-
-// Register-resident variant for H in {32, 64, 128}: 16 clips per workgroup, wave w owns the 16 hidden units
-// [16w, 16w+16) of all four gates on v_mfma_f32_16x16x4_f32; its W_hh slices (4 gates x H/4 contiguous floats per lane)
-// are loaded once and stay in 4*H/4 VGPRs for every step (H = 128: 128 registers, eight waves = two per SIMD).
-template <int H>
-__global__ void __launch_bounds__(64 * (H / 16), 1) lstm16_kernel(GruArgs a) {
-    constexpr int KS = H / 4, LDH = H + 4;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* hs = reinterpret_cast<float*>(smem_raw);           // [16][H+4]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int b0 = blockIdx.x * 16;
-    const int j = 16 * wave + n;
-    for (int idx = threadIdx.x; idx < 16 * LDH; idx += blockDim.x) hs[idx] = 0.0f;
-    float wreg[4][KS], bh[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4* src = reinterpret_cast<const float4*>(a.w_hh + (size_t)(q * H + j) * H + g * KS);
-#pragma unroll
-        for (int s4 = 0; s4 < KS / 4; ++s4) {
-            const float4 v = src[s4];
-            wreg[q][4 * s4] = v.x; wreg[q][4 * s4 + 1] = v.y; wreg[q][4 * s4 + 2] = v.z; wreg[q][4 * s4 + 3] = v.w;
-        }
-        bh[q] = a.b_hh[q * H + j];
-    }
-    float hprev[4], cprev[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { hprev[r] = 0.0f; cprev[r] = 0.0f; }
-    const float* arow = hs + n * LDH + g * KS;
-    float xq[4][4], xnext[4][4];                              // input-side pre-activations, fetched one step ahead (gru16_kernel)
-    auto fetch = [&](int step, float (&x)[4][4]) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = b0 + 4 * g + r;
-            const float* xg = a.xg + ((size_t)min(b, a.B - 1) * a.T + t) * 4 * H + j;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) x[q][r] = xg[q * H];
-        }
-    };
-    fetch(0, xq);
-    __syncthreads();
-    for (int step = 0; step < a.steps; ++step) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-        f32x4 acc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (step + 1 < a.steps) fetch(step + 1, xnext);
-        if (step > 0) {
-#pragma unroll
-            for (int s4 = 0; s4 < KS / 4; ++s4) {
-                const float4 av = *reinterpret_cast<const float4*>(arow + 4 * s4);
-                const float ae[4] = {av.x, av.y, av.z, av.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(ae[e], wreg[q][4 * s4 + e], acc[q], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int c = 4 * g + r, b = b0 + c;
-            float hn = 0.0f, cn = 0.0f;
-            if (b < a.B) {
-                const float ig = rnn_sigmoid(xq[0][r] + acc[0][r] + bh[0]);
-                const float fg = rnn_sigmoid(xq[1][r] + acc[1][r] + bh[1]);
-                const float gg = rnn_tanh(xq[2][r] + acc[2][r] + bh[2]);
-                const float og = rnn_sigmoid(xq[3][r] + acc[3][r] + bh[3]);
-                cn = fg * cprev[r] + ig * gg;
-                hn = og * rnn_tanh(cn);
-                if (a.seq_out) a.seq_out[((size_t)b * a.T + t) * a.ld_seq + a.col_off + j] = hn;
-                if (a.last_out && step == a.steps - 1) a.last_out[(size_t)b * a.ld_last + a.col_off + j] = hn;
-            }
-            hprev[r] = hn; cprev[r] = cn;
-            hs[c * LDH + j] = hn;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xq[q][r] = xnext[q][r];
-        __syncthreads();
-    }
-}
-
-// the split-operand recurrence serves this layer (plan time: the plan folds the reverse direction's single step into it)
-// ------------------------------------------------------------------------------------------ any-width recurrence
-// nn.GRU / nn.LSTM take any hidden_size (architectures.py:132-145,238-254); the kernels above want H % 4 == 0 (16-byte weight rows)
-// and H <= 256 (a wave per 32 hidden units).  This one takes any H <= 512: W_hh re-laid at plan time as [G H][ldw] rows padded with
-// zeros to ldw = H rounded up to 8 (rnn_pad_rows_kernel), a wave walks tiles wave, wave + 8 (32 hidden units each) one after the
-// other within a step, and h lives in TWO LDS buffers (read step t, write step t + 1: one barrier per step).  Gate arithmetic as in
-// gru_kernel / lstm_kernel (expf / tanhf).  G = 3: GRU, 4: LSTM.
-__global__ void __launch_bounds__(256) rnn_pad_rows_kernel(const float* __restrict__ w, float* __restrict__ out, int rows, int H, int ldw) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (size_t)rows * ldw) return;
-    const int r = (int)(idx / ldw), k = (int)(idx - (size_t)r * ldw);
-    out[idx] = k < H ? w[(size_t)r * H + k] : 0.0f;
-}
-size_t rnn_wide_weight_bytes(int gates, int H) { return (size_t)gates * H * ((H + 7) & ~7) * sizeof(float); }
-hipError_t launch_rnn_pad_weights(const float* w_hh, float* out, int gates, int H, hipStream_t s) {
-    const int ldw = (H + 7) & ~7;
-    const size_t total = (size_t)gates * H * ldw;
-    hipLaunchKernelGGL(rnn_pad_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w_hh, out, gates * H, H, ldw);
-    return hipGetLastError();
-}
-
-// gate functions on the hardware exp2 / rcp (abs. error <= 2e-7, as rnn_x3.hip / rnn_stream.hip; the library expf / tanhf cost this kernel
-// 22 (GRU) / 52 (LSTM) spilled registers under its 256-register budget: VERDICT r05)
-__device__ __forceinline__ float wide_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float wide_tanh(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * v)); }
-template <int G>
-__global__ void __launch_bounds__(512) rnn_wide_kernel(GruArgs a) {
-    constexpr int TP = 2;                                     // tiles per wave: 8 waves x 2 x 32 = 512 hidden units
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int H = a.H, ldw = a.ldw, ldh = ldw + 4;
-    float* hbuf[2] = {reinterpret_cast<float*>(smem_raw), reinterpret_cast<float*>(smem_raw) + (size_t)32 * ldh};
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 31, hh = lane >> 5;
-    const int b0 = blockIdx.x * 32;
-    const int ntile = (H + 31) / 32;
-    for (int idx = threadIdx.x; idx < 2 * 32 * ldh; idx += blockDim.x) hbuf[0][idx] = 0.0f;
-    // the previous h of a (clip, unit) is read back from the LDS plane the products use (zero at step 0); only the LSTM's cell state lives in
-    // registers (h in registers as well cost 20 / 50 spilled ones under the 256-register budget of sixteen... eight waves)
-    float cprev[G == 4 ? TP : 1][16];
-#pragma unroll
-    for (int tp = 0; tp < (G == 4 ? TP : 1); ++tp)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cprev[tp][r] = 0.0f;
-    __syncthreads();
-    for (int step = 0; step < a.steps; ++step) {
-        const int t = a.reverse ? a.T - 1 - step : step;
-        const float* cur = hbuf[step & 1];
-        float* nxt = hbuf[(step & 1) ^ 1];
-        // lane coordinates re-derived from an opaque copy every step: from the plain ones the 16 output addresses per tile are loop-invariant,
-        // get hoisted out of the step loop and spill (50 registers in the LSTM instance)
-        int lane_o = lane;
-        asm volatile("" : "+v"(lane_o));
-        const int i = lane_o & 31, hh = lane_o >> 5;
-#pragma unroll
-        for (int tp = 0; tp < TP; ++tp) {
-            const int tile = wave + 8 * tp;
-            if (tile >= ntile) continue;                      // (wave-uniform)
-            const int j = tile * 32 + i;
-            const bool jok = j < H;
-            const int jc = jok ? j : H - 1;
-            f32x16 acc[G];
-#pragma unroll
-            for (int q = 0; q < G; ++q)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[q][r] = 0.0f;
-            if (step > 0) {
-                const float* arow = cur + (size_t)i * ldh + 4 * hh;
-                const float* wq[G];
-#pragma unroll
-                for (int q = 0; q < G; ++q) wq[q] = a.w_hh + (size_t)(q * H + jc) * ldw + 4 * hh;
-                for (int k = 0; k < ldw; k += 8) {
-                    const float4 av = *reinterpret_cast<const float4*>(arow + k);
-                    float4 bw[G];
-#pragma unroll
-                    for (int q = 0; q < G; ++q) bw[q] = *reinterpret_cast<const float4*>(wq[q] + k);
-#pragma unroll
-                    for (int q = 0; q < G; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bw[q].x, acc[q], 0, 0, 0);
-#pragma unroll
-                    for (int q = 0; q < G; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bw[q].y, acc[q], 0, 0, 0);
-#pragma unroll
-                    for (int q = 0; q < G; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bw[q].z, acc[q], 0, 0, 0);
-#pragma unroll
-                    for (int q = 0; q < G; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bw[q].w, acc[q], 0, 0, 0);
-                }
-            }
-            float bh[G];
-#pragma unroll
-            for (int q = 0; q < G; ++q) bh[q] = a.b_hh[q * H + jc];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                const int b = b0 + c;
-                float hn = 0.0f, cn = 0.0f;
-                if (b < a.B && jok) {
-                    const float* xg = a.xg + ((size_t)b * a.T + t) * G * H + j;
-                    if (G == 3) {
-                        const float rg = wide_sigmoid(xg[0] + acc[0][r] + bh[0]);
-                        const float zg = wide_sigmoid(xg[H] + acc[1][r] + bh[1]);
-                        const float ng = wide_tanh(xg[2 * H] + rg * (acc[2][r] + bh[2]));
-                        hn = (1.0f - zg) * ng + zg * cur[(size_t)c * ldh + j];
-                    } else {
-                        const float ig = wide_sigmoid(xg[0] + acc[0][r] + bh[0]);
-                        const float fg = wide_sigmoid(xg[H] + acc[1][r] + bh[1]);
-                        const float gg = wide_tanh(xg[2 * H] + acc[2][r] + bh[2]);
-                        const float og = wide_sigmoid(xg[3 * H] + acc[G - 1][r] + bh[G - 1]);
-                        cn = fg * cprev[G == 4 ? tp : 0][r] + ig * gg;
-                        hn = og * wide_tanh(cn);
-                    }
-                    if (a.seq_out) a.seq_out[((size_t)b * a.T + t) * a.ld_seq + a.col_off + j] = hn;
-                    if (a.last_out && step == a.steps - 1) a.last_out[(size_t)b * a.ld_last + a.col_off + j] = hn;
-                }
-                if (G == 4) cprev[G == 4 ? tp : 0][r] = cn;
-                if (jok) nxt[(size_t)c * ldh + j] = hn;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-static hipError_t launch_rnn_wide(const GruArgs& a, int gates, hipStream_t s) {
-    if (a.H < 1 || a.H > 512 || a.ldw != ((a.H + 7) & ~7) || a.xg2) return hipErrorInvalidValue;
-    const size_t lds = (size_t)2 * 32 * (a.ldw + 4) * sizeof(float);
-    const dim3 grid((a.B + 31) / 32);
-    if (gates == 3) {
-        hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(rnn_wide_kernel<3>), lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(rnn_wide_kernel<3>, grid, dim3(512), lds, s, a);
-    } else {
-        hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(rnn_wide_kernel<4>), lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(rnn_wide_kernel<4>, grid, dim3(512), lds, s, a);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_lstm(const GruArgs& a, hipStream_t s) {
-    if (a.w_packed) return launch_rnn_stream(a, 4, s);
-    if (a.ldw) return launch_rnn_wide(a, 4, s);                      // padded weights: the any-width kernel (planned for H % 4 != 0 or H > 256)
-    if (a.H % 4 != 0 || a.H > 256) return hipErrorInvalidValue;      // a wave per 32 hidden units, 512 threads
-    if (rnn_x3_usable(a)) return launch_rnn_x3(a, 4, s);
-    if (a.xg2) return hipErrorInvalidValue;                           // only rnn_x3 folds the opposite direction's step
-    if ((a.H == 32 || a.H == 64 || a.H == 128) && (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0) {
-        const size_t lds16 = (size_t)16 * (a.H + 4) * sizeof(float);
-        const dim3 grid((a.B + 15) / 16);
-        switch (a.H) {
-            case 32: hipLaunchKernelGGL(lstm16_kernel<32>, grid, dim3(128), lds16, s, a); break;
-            case 64: hipLaunchKernelGGL(lstm16_kernel<64>, grid, dim3(256), lds16, s, a); break;
-            default: hipLaunchKernelGGL(lstm16_kernel<128>, grid, dim3(512), lds16, s, a); break;
-        }
-        return hipGetLastError();
-    }
-    const int waves = (a.H + 31) / 32;
-    const size_t lds = (size_t)32 * (a.H + 4) * sizeof(float);
-    {
-        hipError_t ea = nww_allow_lds(reinterpret_cast<const void*>(lstm_kernel), lds);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(lstm_kernel, dim3((a.B + 31) / 32), dim3(waves * 64), lds, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_gru(const GruArgs& a, hipStream_t s) {
-    if (a.w_packed) return launch_rnn_stream(a, 3, s);
-    if (a.ldw) return launch_rnn_wide(a, 3, s);
-    if (a.H % 4 != 0 || a.H > 256) return hipErrorInvalidValue;      // a wave per 32 hidden units, 512 threads
-    if (rnn_x3_usable(a)) return launch_rnn_x3(a, 3, s);
-    if (a.xg2) return hipErrorInvalidValue;                           // only rnn_x3 folds the opposite direction's step
-    if ((a.H == 32 || a.H == 64 || a.H == 128) && (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0) {
-        const size_t lds16 = (size_t)16 * (a.H + 4) * sizeof(float);
-        const dim3 grid((a.B + 15) / 16);
-        switch (a.H) {
-            case 32: hipLaunchKernelGGL(gru16_kernel<32>, grid, dim3(64), lds16, s, a); break;
-            case 64: hipLaunchKernelGGL(gru16_kernel<64>, grid, dim3(128), lds16, s, a); break;
-            default: hipLaunchKernelGGL(gru16_kernel<128>, grid, dim3(256), lds16, s, a); break;
-        }
-        return hipGetLastError();
-    }
-    const int waves = (a.H + 31) / 32;
-    const size_t lds = (size_t)32 * (a.H + 4) * sizeof(float);
-    {
-        hipError_t ea = nww_allow_lds(reinterpret_cast<const void*>(gru_kernel), lds);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(gru_kernel, dim3((a.B + 31) / 32), dim3(waves * 64), lds, s, a);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------ classifier tail
 // 16 clips per workgroup pass; x, emb and hid tiles in LDS, weights through L1 (lanes of a 16-lane group share a weight
 // row -> broadcast loads).  ~10 k MACs per clip: this replaces three tiny GEMM launches and the sigmoid launch, whose

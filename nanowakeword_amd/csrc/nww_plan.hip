@@ -573,7 +573,7 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
     // the recurrent product follows the handle's arithmetic switch; NWW_ARITH_F16X3: two binary16 terms (|h| <= 1 bounds the one
     // operand, W_hh's scale comes from the weights)
     const int products = p.h->f16 ? 3 : p.h->conv_products;
-    GruArgs probe; probe.H = H; probe.products = products;
+    RnnArgs probe; probe.H = H; probe.products = products;
     probe.w_hh = p.W(prefix + ".weight_hh_l" + std::to_string(layers - 1));       // the pointer the fused launch will really get (alignment test)
     const bool streamed = rnn_stream_usable(probe);      // 128 < H <= 256: W_hh streamed from L2 (rnn_stream.hip)
     bool x3 = probe.w_hh != nullptr && (rnn_x3_usable(probe) || streamed);
@@ -618,7 +618,7 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
                     return launch_gemm(g, r.stream);
                 });
             } else if (fuse_ih && dir == 0) {
-                // (the forward direction's input projection runs inside its recurrence: GruArgs::fin)
+                // (the forward direction's input projection runs inside its recurrence: RnnArgs::fin)
             } else {
                 // short-K input projections (the GRU head's 64 mel bins) on the input-stationary kernel; the rest on the general GEMM
                 add_linear(p, prefix + ".ih" + sfx, cur_in, xg_id, T, G * H, cur_I, wih, bih);
@@ -649,8 +649,8 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
             const int fin = cur_I;
             if (fused_here) p.h->clamps_features = true;       // the fused input projection clamps the features it splits
             p.add(nm + (fused_here ? " + input projection" : "") + (products_l == 3 && x3 && ldw == 0 ? (w_packed ? " [f16x3, W_hh streamed]" : " [f16x3]") : ""), [=](Run& r) {
-                GruArgs a;
-                a.products = products_l; a.w_scale = w_scale; a.w_packed = w_packed;
+                RnnArgs a;
+                a.gates = G; a.products = products_l; a.w_scale = w_scale; a.w_packed = w_packed;
                 if (fused_here) {
                     a.x_in = r.x; a.w_ih = wih_f; a.b_ih = bih_f; a.fin = fin;
                     a.x_scale = f16_scale(F16_FEATURES.bound); a.x_clamp = (float)F16_FEATURES.bound; a.wi_scale = wi_scale;
@@ -666,7 +666,7 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
                     a.col_off = dir ? H : 0; a.reverse = dir;
                     a.steps = (last && dir) ? 1 : in_T;      // reverse half of rnn_out[:, -1] is its first step
                 }
-                return G == 4 ? launch_lstm(a, r.stream) : launch_gru(a, r.stream);
+                return launch_rnn(a, r.stream);
             });
         }
         cur_in = seq_out; cur_I = 2 * H;

@@ -1,9 +1,9 @@
 // rnn_stream.hip - GRU / LSTM recurrences wider than the register-resident ones (128 < layer_dim <= 256) on the f16 matrix cores, W_hh
 // STREAMED from L2 every step (gfx950).
 //
-// Cell semantics as rnn_x3.hip / layers.hip state them (nanowakeword/modules/architectures.py:129-145, 238-254).  rnn_x3 keeps W_hh in
+// Cell semantics as rnn_cell.h states them (nanowakeword/modules/architectures.py:129-145, 238-254).  rnn_x3 keeps W_hh in
 // registers for all steps; at H = 256 the two binary16 terms of a GRU's W_hh are 786 KB - more than the registers and LDS of a CU together
-// (512 + 160 KB) - so the general kernel of layers.hip took these widths at ~4 ms per layer (B = 2048, T = 101).  Here a workgroup owns
+// (512 + 160 KB) - so the general kernel of rnn_f32.hip took these widths at ~4 ms per layer (B = 2048, T = 101).  Here a workgroup owns
 // 16 or 32 clips x all hidden units; W_hh is packed once at plan time into the MFMA B-fragment order of the (k-block, wave, gate, column block, term)
 // loop nest, so that every fetch is one 16-byte load per lane and 1 KB contiguous per wave, and each step reads the whole pack through a
 // register ring RING units ahead of the matrix pipe.  The pack (0.8 - 1 MB) stays in each XCD's 4 MB L2; a CU takes 64 bytes per clock
@@ -17,14 +17,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "layers.h"
+#include "rnn_cell.h"
 #include "split_h2.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-__device__ __forceinline__ float sigmoid_s(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float tanh_s(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * v)); }
 
 constexpr int RS_NB = 2;                                      // 16-wide column blocks per wave and gate: a wave owns 32 hidden units of every gate
 
@@ -62,7 +61,7 @@ __global__ void __launch_bounds__(256) rnn_stream_pack_kernel(const float* __res
 // the products at these widths: 1 tile while the batch leaves compute units idle (shortest step), 2 beyond that (half the L2 traffic per clip).
 // Results do not depend on the choice: a clip's arithmetic is the same in either.
 template <int G, int HP, int RING, int RS_MT>
-__global__ void __launch_bounds__(64 * (HP / 32)) rnn_stream_kernel(GruArgs a) {
+__global__ void __launch_bounds__(64 * (HP / 32)) rnn_stream_kernel(RnnArgs a) {
     constexpr int KS = HP / 32, NWV = HP / 32;
     constexpr int LDP = HP + 16;                              // binary16 per LDS row: + 32 bytes - conflict-free fragment reads for the real ds_read_b128 lane groups (rnn_x3.hip)
     constexpr int UPK = G * RS_NB;                            // units per k-block and wave
@@ -210,17 +209,17 @@ __global__ void __launch_bounds__(64 * (HP / 32)) rnn_stream_kernel(GruArgs a) {
                         const float a0 = fmaf(acc[mt][0][bl][r], un, bh[0][bl]);
                         const float a1 = fmaf(acc[mt][1][bl][r], un, bh[1][bl]);
                         const float a2 = fmaf(acc[mt][2][bl][r], un, bh[2][bl]);
-                        const float rg = sigmoid_s(xq[mt][0][bl][r] + a0);
-                        const float zg = sigmoid_s(xq[mt][1][bl][r] + a1);
-                        const float ng = tanh_s(xq[mt][2][bl][r] + rg * a2);
+                        const float rg = rnn_sigmoid(xq[mt][0][bl][r] + a0);
+                        const float zg = rnn_sigmoid(xq[mt][1][bl][r] + a1);
+                        const float ng = rnn_tanh(xq[mt][2][bl][r] + rg * a2);
                         hn = (1.0f - zg) * ng + zg * hprev[mt][bl][r];
                     } else {
-                        const float ig = sigmoid_s(xq[mt][0][bl][r] + fmaf(acc[mt][0][bl][r], un, bh[0][bl]));
-                        const float fg = sigmoid_s(xq[mt][1][bl][r] + fmaf(acc[mt][1][bl][r], un, bh[1][bl]));
-                        const float gg = tanh_s(xq[mt][2][bl][r] + fmaf(acc[mt][2][bl][r], un, bh[2][bl]));
-                        const float og = sigmoid_s(xq[mt][G - 1][bl][r] + fmaf(acc[mt][G - 1][bl][r], un, bh[G - 1][bl]));
+                        const float ig = rnn_sigmoid(xq[mt][0][bl][r] + fmaf(acc[mt][0][bl][r], un, bh[0][bl]));
+                        const float fg = rnn_sigmoid(xq[mt][1][bl][r] + fmaf(acc[mt][1][bl][r], un, bh[1][bl]));
+                        const float gg = rnn_tanh(xq[mt][2][bl][r] + fmaf(acc[mt][2][bl][r], un, bh[2][bl]));
+                        const float og = rnn_sigmoid(xq[mt][G - 1][bl][r] + fmaf(acc[mt][G - 1][bl][r], un, bh[G - 1][bl]));
                         cn = fg * cprev[mt][bl][r] + ig * gg;
-                        hn = og * tanh_s(cn);
+                        hn = og * rnn_tanh(cn);
                     }
                     if (!jok[bl]) hn = cn = 0.0f;              // padded unit: its pre-activation loads were not its own
                     if (seq_wg && b < a.B && jok[bl]) *reinterpret_cast<float*>(seq_wg + 64 * bl + soff[mt][r]) = hn;
@@ -253,15 +252,15 @@ __global__ void __launch_bounds__(64 * (HP / 32)) rnn_stream_kernel(GruArgs a) {
                 const float* x2 = a.xg2 + (size_t)b * a.xg2_bstride + j;
                 float h2;
                 if (G == 3) {
-                    const float rg = sigmoid_s(x2[0] + a.b_hh2[j]);
-                    const float zg = sigmoid_s(x2[HR] + a.b_hh2[HR + j]);
-                    const float ng = tanh_s(x2[2 * HR] + rg * a.b_hh2[2 * HR + j]);
+                    const float rg = rnn_sigmoid(x2[0] + a.b_hh2[j]);
+                    const float zg = rnn_sigmoid(x2[HR] + a.b_hh2[HR + j]);
+                    const float ng = rnn_tanh(x2[2 * HR] + rg * a.b_hh2[2 * HR + j]);
                     h2 = (1.0f - zg) * ng;
                 } else {
-                    const float ig = sigmoid_s(x2[0] + a.b_hh2[j]);
-                    const float gg = tanh_s(x2[2 * HR] + a.b_hh2[2 * HR + j]);
-                    const float og = sigmoid_s(x2[(G - 1) * HR] + a.b_hh2[(G - 1) * HR + j]);
-                    h2 = og * tanh_s(ig * gg);
+                    const float ig = rnn_sigmoid(x2[0] + a.b_hh2[j]);
+                    const float gg = rnn_tanh(x2[2 * HR] + a.b_hh2[2 * HR + j]);
+                    const float og = rnn_sigmoid(x2[(G - 1) * HR] + a.b_hh2[(G - 1) * HR + j]);
+                    h2 = og * rnn_tanh(ig * gg);
                 }
                 a.last_out[(size_t)b * a.ld_last + a.col_off2 + j] = h2;
             }
@@ -272,7 +271,7 @@ __global__ void __launch_bounds__(64 * (HP / 32)) rnn_stream_kernel(GruArgs a) {
 static int rnn_stream_width(int H) { return H <= 192 ? 192 : 256; }
 
 // 128 < H <= 256, a multiple of 4 (the xg rows' alignment), two-term form
-bool rnn_stream_usable(const GruArgs& a) {
+bool rnn_stream_usable(const RnnArgs& a) {
     return a.products == 3 && a.H > 128 && a.H <= 256 && a.H % 4 == 0 && a.fin == 0;
 }
 
@@ -288,14 +287,14 @@ hipError_t launch_rnn_stream_pack(const float* w_hh, void* packed, int gates, in
     return hipGetLastError();
 }
 
-hipError_t launch_rnn_stream(const GruArgs& a, int gates, hipStream_t s) {
-    if (!rnn_stream_usable(a) || !a.w_packed || (gates != 3 && gates != 4) || !(a.w_scale > 0.0f)) return hipErrorInvalidValue;
+hipError_t launch_rnn_stream(const RnnArgs& a, hipStream_t s) {
+    if (!rnn_stream_usable(a) || !a.w_packed || (a.gates != 3 && a.gates != 4) || !(a.w_scale > 0.0f)) return hipErrorInvalidValue;
     const int HP = rnn_stream_width(a.H);
     const int mt = a.B <= 16 * a.cu_count ? 1 : 2;
     const dim3 grid((a.B + 16 * mt - 1) / (16 * mt)), block(64 * (HP / 32));
     const size_t lds = (size_t)2 * 2 * 16 * mt * (HP + 16) * sizeof(uint16_t);     // two sets of two term planes
 #ifdef NWW_ABLATION
-    GruArgs ad = a;
+    RnnArgs ad = a;
     { const char* e = getenv("NWW_RNN_DBG"); ad.dbg = e ? atoi(e) : 0; }
 #define a ad
 #endif
@@ -309,7 +308,7 @@ hipError_t launch_rnn_stream(const GruArgs& a, int gates, hipStream_t s) {
         if (mt == 1) hipLaunchKernelGGL((rnn_stream_kernel<GV, HV, R1, 1>), grid, block, lds, s, a);     \
         else hipLaunchKernelGGL((rnn_stream_kernel<GV, HV, R2, 2>), grid, block, lds, s, a);             \
     }
-    if (gates == 3) {
+    if (a.gates == 3) {
         if (HP == 192) { RS_GO(3, 192, 12, 4) } else { RS_GO(3, 256, 12, 4) }
     } else {
         if (HP == 192) { RS_GO(4, 192, 8, 2) } else { RS_GO(4, 256, 8, 2) }

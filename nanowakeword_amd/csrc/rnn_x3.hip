@@ -1,6 +1,6 @@
 // rnn_x3.hip - GRU / LSTM recurrences with the recurrent product h W_hh^T on the bf16 matrix cores (gfx950).
 //
-// nn.GRU / nn.LSTM cell semantics as layers.hip states them (CRNNModel / GRU head: nanowakeword/modules/architectures.py:
+// nn.GRU / nn.LSTM cell semantics as rnn_cell.h states them (CRNNModel / GRU head: nanowakeword/modules/architectures.py:
 // 238-254, 731-760): xg = x W_ih^T + b_ih is precomputed for every frame, the kernel walks the T steps of one direction.
 //
 // One workgroup = 16 clips x all H hidden units for all T steps; wave w owns 16 (H = 128: 32) hidden units of every gate.
@@ -9,9 +9,9 @@
 // per step by the lane that produced it, into three bf16 planes in LDS that every wave reads back as A fragments (three
 // 16-byte reads per k-block, shared by the gates).  The 6 (or 9) partial products of a k-block go to
 // v_mfma_f32_16x16x32_bf16 - 16 matrix-pipe clocks for K = 32 against 8 x 32 for the same K on v_mfma_f32_16x16x4_f32,
-// which is what the float32 instances in layers.hip spend: 6144 of their ~11 000 clocks per step at H = 128.
+// which is what the float32 instances in rnn_f32.hip spend: 6144 of their ~11 000 clocks per step at H = 128.
 // C layout = column: hidden unit, rows 4g .. 4g + 3: clips, so xg loads and h stores are coalesced along the hidden dimension.
-// xg rows are requested two steps ahead; gate functions on the hardware exp2 / reciprocal (layers.hip: rnn_sigmoid).
+// xg rows are requested two steps ahead; gate functions on the hardware exp2 / reciprocal (rnn_cell.h).
 // Clips are independent rows of every product: results do not depend on batch size or position.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +19,7 @@
 // plan) as TWO binary16 terms each (split_h2.h), three partial products per k-block on v_mfma_f32_16x16x32_f16 - 72 instead of
 // 144 MFMAs per step at H = 128, two term planes of h instead of three, and the scaling back is the fma that adds b_hh.
 #include "layers.h"
+#include "rnn_cell.h"
 #include "split_h2.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -40,18 +41,16 @@ __device__ __forceinline__ void split3r(float x, uint32_t& hi, uint32_t& mid, ui
     lo = __float_as_uint(r - __uint_as_float(mid));
 }
 __device__ __forceinline__ uint32_t pack_hi16r(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-__device__ __forceinline__ float sigmoid_r(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float tanh_r(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * v)); }
 
 // G = 3: GRU (r, z, n), G = 4: LSTM (i, f, g, o); NP = 6 or 9 partial products per operand pair; NB = 16-wide column blocks per
 // wave (2 at H = 128: four waves, one per SIMD, so that each has the whole 512-register file - 288 of them weight fragments)
-// FIN = 32 / 64 (GRU, NP = 3): the input projection of the step fused in (GruArgs::fin); 0: xg precomputed
+// FIN = 32 / 64 (GRU, NP = 3): the input projection of the step fused in (RnnArgs::fin); 0: xg precomputed
 // PAD (NP = 3): the layer's real width a.H < H, a multiple of 4 (layer_dim = 48, 96, 100 ...): the instance of the next width with the rows
 // and columns beyond a.H read as zeros - a padded unit has zero weights, biases and input pre-activations, so its gates are 1/2, 1/2,
 // tanh(0) and its state stays 0 for ever (GRU: h' = h / 2; LSTM: c' = c / 2, h' = tanh(c') / 2), which adds nothing to the real units'
 // products; all global addressing uses the real width and nothing is stored for the padded units
 template <int G, int H, int NP, int NB, int FIN = 0, bool PAD = false>
-__global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(GruArgs a) {
+__global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(RnnArgs a) {
     static_assert(FIN == 0 || (G == 3 && NP == 3 && FIN % 32 == 0), "fused input projection: GRU, two-term form");
     static_assert(!PAD || (FIN == 0 && NP == 3), "padded widths: two-term form, xg precomputed");
     const int HR = PAD ? a.H : H;                             // real width (global addressing)
@@ -275,17 +274,17 @@ __global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(GruArgs a)
                     const float a0 = H2 ? fmaf(acc[0][bl][r], un, bh[0][bl]) : acc[0][bl][r] + bh[0][bl];
                     const float a1 = H2 ? fmaf(acc[1][bl][r], un, bh[1][bl]) : acc[1][bl][r] + bh[1][bl];
                     const float a2 = H2 ? fmaf(acc[2][bl][r], un, bh[2][bl]) : acc[2][bl][r] + bh[2][bl];
-                    const float rg = sigmoid_r(H2 ? xq[0] + a0 : xq[0] + acc[0][bl][r] + bh[0][bl]);
-                    const float zg = sigmoid_r(H2 ? xq[1] + a1 : xq[1] + acc[1][bl][r] + bh[1][bl]);
-                    const float ng = tanh_r(xq[2] + rg * a2);
+                    const float rg = rnn_sigmoid(H2 ? xq[0] + a0 : xq[0] + acc[0][bl][r] + bh[0][bl]);
+                    const float zg = rnn_sigmoid(H2 ? xq[1] + a1 : xq[1] + acc[1][bl][r] + bh[1][bl]);
+                    const float ng = rnn_tanh(xq[2] + rg * a2);
                     hn = (1.0f - zg) * ng + zg * hprev[bl][r];
                 } else {
-                    const float ig = sigmoid_r(H2 ? xpf[0][0][bl][r] + fmaf(acc[0][bl][r], un, bh[0][bl]) : xpf[0][0][bl][r] + acc[0][bl][r] + bh[0][bl]);
-                    const float fg = sigmoid_r(H2 ? xpf[0][1][bl][r] + fmaf(acc[1][bl][r], un, bh[1][bl]) : xpf[0][1][bl][r] + acc[1][bl][r] + bh[1][bl]);
-                    const float gg = tanh_r(H2 ? xpf[0][2][bl][r] + fmaf(acc[2][bl][r], un, bh[2][bl]) : xpf[0][2][bl][r] + acc[2][bl][r] + bh[2][bl]);
-                    const float og = sigmoid_r(H2 ? xpf[0][G - 1][bl][r] + fmaf(acc[G - 1][bl][r], un, bh[G - 1][bl]) : xpf[0][G - 1][bl][r] + acc[G - 1][bl][r] + bh[G - 1][bl]);
+                    const float ig = rnn_sigmoid(H2 ? xpf[0][0][bl][r] + fmaf(acc[0][bl][r], un, bh[0][bl]) : xpf[0][0][bl][r] + acc[0][bl][r] + bh[0][bl]);
+                    const float fg = rnn_sigmoid(H2 ? xpf[0][1][bl][r] + fmaf(acc[1][bl][r], un, bh[1][bl]) : xpf[0][1][bl][r] + acc[1][bl][r] + bh[1][bl]);
+                    const float gg = rnn_tanh(H2 ? xpf[0][2][bl][r] + fmaf(acc[2][bl][r], un, bh[2][bl]) : xpf[0][2][bl][r] + acc[2][bl][r] + bh[2][bl]);
+                    const float og = rnn_sigmoid(H2 ? xpf[0][G - 1][bl][r] + fmaf(acc[G - 1][bl][r], un, bh[G - 1][bl]) : xpf[0][G - 1][bl][r] + acc[G - 1][bl][r] + bh[G - 1][bl]);
                     cn = fg * cprev[bl][r] + ig * gg;
-                    hn = og * tanh_r(cn);
+                    hn = og * rnn_tanh(cn);
                 }
                 if (b < a.B && (!PAD || j < HR)) {
                     if (a.seq_out) a.seq_out[((size_t)b * a.T + t) * a.ld_seq + a.col_off + j] = hn;
@@ -295,15 +294,15 @@ __global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(GruArgs a)
                             const float* x2 = a.xg2 + (size_t)b * a.xg2_bstride + j;
                             float h2;
                             if (G == 3) {
-                                const float rg = sigmoid_r(x2[0] + a.b_hh2[j]);
-                                const float zg = sigmoid_r(x2[HR] + a.b_hh2[HR + j]);
-                                const float ng = tanh_r(x2[2 * HR] + rg * a.b_hh2[2 * HR + j]);
+                                const float rg = rnn_sigmoid(x2[0] + a.b_hh2[j]);
+                                const float zg = rnn_sigmoid(x2[HR] + a.b_hh2[HR + j]);
+                                const float ng = rnn_tanh(x2[2 * HR] + rg * a.b_hh2[2 * HR + j]);
                                 h2 = (1.0f - zg) * ng;
                             } else {
-                                const float ig = sigmoid_r(x2[0] + a.b_hh2[j]);
-                                const float gg = tanh_r(x2[2 * HR] + a.b_hh2[2 * HR + j]);
-                                const float og = sigmoid_r(x2[(G - 1) * HR] + a.b_hh2[(G - 1) * HR + j]);
-                                h2 = og * tanh_r(ig * gg);
+                                const float ig = rnn_sigmoid(x2[0] + a.b_hh2[j]);
+                                const float gg = rnn_tanh(x2[2 * HR] + a.b_hh2[2 * HR + j]);
+                                const float og = rnn_sigmoid(x2[(G - 1) * HR] + a.b_hh2[(G - 1) * HR + j]);
+                                h2 = og * rnn_tanh(ig * gg);
                             }
                             a.last_out[(size_t)b * a.ld_last + a.col_off2 + j] = h2;
                         }
@@ -335,17 +334,17 @@ __global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(GruArgs a)
 }  // namespace
 
 // widths 32 / 64 / 128 in every arithmetic; any other multiple of 4 below 128 as a zero-padded instance of the next width (two-term form)
-static bool rnn_x3_padded(const GruArgs& a) {
+static bool rnn_x3_padded(const RnnArgs& a) {
     return a.products == 3 && a.H >= 4 && a.H < 128 && a.H % 4 == 0 && a.H != 32 && a.H != 64 && a.fin == 0;
 }
-bool rnn_x3_usable(const GruArgs& a) {
+bool rnn_x3_usable(const RnnArgs& a) {
     return (a.products == 3 || a.products == 6 || a.products == 9) && (a.H == 32 || a.H == 64 || a.H == 128 || rnn_x3_padded(a)) &&
            (reinterpret_cast<uintptr_t>(a.w_hh) & 15) == 0;
 }
 
-hipError_t launch_rnn_x3(const GruArgs& a, int gates, hipStream_t s) {
-    if (!rnn_x3_usable(a) || (gates != 3 && gates != 4)) return hipErrorInvalidValue;
-    if (gates == 3 && a.fin > 0 && (a.products != 3 || (a.fin != 32 && a.fin != 64) || !a.x_in || !a.w_ih || !a.b_ih || a.reverse))
+hipError_t launch_rnn_x3(const RnnArgs& a, hipStream_t s) {
+    if (!rnn_x3_usable(a) || (a.gates != 3 && a.gates != 4)) return hipErrorInvalidValue;
+    if (a.gates == 3 && a.fin > 0 && (a.products != 3 || (a.fin != 32 && a.fin != 64) || !a.x_in || !a.w_ih || !a.b_ih || a.reverse))
         return hipErrorInvalidValue;                          // fused input projection (GRU, two-term form)
     const bool pad = rnn_x3_padded(a);
     const int HP = a.H <= 32 ? 32 : a.H <= 64 ? 64 : 128;     // the instance's width
@@ -370,7 +369,7 @@ hipError_t launch_rnn_x3(const GruArgs& a, int gates, hipStream_t s) {
     else if (a.products == 6) RNN_H(GV, 6, 0, false)                                                                 \
     else if (pad) RNN_H(GV, 3, 0, true)                                                                              \
     else RNN_H(GV, 3, 0, false)
-    if (gates == 4) { RNN_P(4) }
+    if (a.gates == 4) { RNN_P(4) }
     else if (a.fin == 32) { RNN_H(3, 3, 32, false) }
     else if (a.fin == 64) { RNN_H(3, 3, 64, false) }
     else { RNN_P(3) }

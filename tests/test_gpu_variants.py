@@ -359,6 +359,32 @@ def test_recurrent_kernels_every_size_and_arithmetic(HipModel):
     print("worst |dlogit| over recurrent instances:", worst)
 
 
+def test_float32_recurrence_edge_widths(HipModel):
+    """The 32-clip float32-MFMA recurrence (rnn_f32.hip: rnn32_kernel, W_hh from L2), GRU and LSTM, at the edges of its widths:
+    4 (one wave, 28 idle columns, the upper half-lanes of the k-loop all masked), 36 (a second wave with four live units, a ragged
+    last 8-k slice), 96 and 256 (eight waves), two layers so that the sequence output and both full directions run; B = 37 is one
+    full and one ragged workgroup.  bf16x6 reaches the same kernel at the widths rnn_x3 does not take.  Against the oracle."""
+    worst = 0.0
+    for H in (4, 36, 96, 256):
+        for cfg in (HeadConfig("gru", (12, 64), layer_dim=H, n_blocks=2),
+                    HeadConfig("crnn", (16, 96), layer_dim=H, n_blocks=2, crnn_rnn_type="lstm")):
+            sd = synth_state_dict(cfg)
+            x = synth_features(37, cfg.input_shape, seed=H)
+            want = oracle.model_forward(x, sd, cfg).ravel()
+            for arith in ("f32", "bf16x6") if H == 36 else ("f32",):
+                m = HipModel(cfg, FrontendConfig(), state_dict=sd, conv_arith=arith)
+                names = m.describe_plan()
+                assert ("gru:" in names) or ("lstm:" in names), names
+                assert "[f16x3" not in names, names
+                lg, _ = m.forward_features(x)
+                worst = max(worst, float(np.abs(lg - want).max()))
+                assert np.abs(lg - want).max() <= 1e-4, (H, cfg.model_type, arith, float(np.abs(lg - want).max()))
+                l5, _ = m.forward_features(x[:5])
+                assert np.array_equal(l5, lg[:5]), (H, cfg.model_type, arith)
+                m.close()
+    print("worst |dlogit| over the 32-clip float32 recurrences:", worst)
+
+
 def test_bcresnet_front_kernel_odd_shapes(HipModel):
     """bc_front_b_kernel away from (101, 64): widths that are not multiples of four (scalar staging path), more than 32 pooled
     columns (two 32-pixel conv groups per row), planes smaller than one strip; six and nine partial products; against the oracle."""

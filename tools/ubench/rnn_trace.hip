@@ -23,16 +23,16 @@ int main(int argc, char** argv) {
     hipMemcpy(dwhh, whh.data(), whh.size() * 4, hipMemcpyHostToDevice); hipMemcpy(dwih, wih.data(), wih.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(db, b.data(), b.size() * 4, hipMemcpyHostToDevice); hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(dxg, xg.data(), xg.size() * 4, hipMemcpyHostToDevice);
-    GruArgs a;
+    RnnArgs a;
     a.xg = dxg; a.w_hh = dwhh; a.b_hh = db; a.seq_out = nullptr; a.ld_seq = 2 * H; a.last_out = dlast; a.ld_last = 2 * H; a.col_off = 0;
-    a.B = B; a.T = T; a.H = H; a.reverse = 0; a.steps = T; a.products = 3; a.w_scale = 32768.0f;
+    a.B = B; a.T = T; a.H = H; a.reverse = 0; a.steps = T; a.products = 3; a.w_scale = 32768.0f; a.gates = G;
     if (fin) { a.x_in = dx; a.w_ih = dwih; a.b_ih = db; a.fin = fin; a.x_scale = 4.0f; a.x_clamp = 8192.0f; a.wi_scale = 32768.0f; }
     hipStream_t s; hipStreamCreate(&s);
-    for (int i = 0; i < 5; ++i) launch_rnn_x3(a, 3, s);
+    for (int i = 0; i < 5; ++i) launch_rnn_x3(a, s);
     hipStreamSynchronize(s);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, s);
-    for (int i = 0; i < 20; ++i) launch_rnn_x3(a, 3, s);
+    for (int i = 0; i < 20; ++i) launch_rnn_x3(a, s);
     hipEventRecord(e1, s); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("gru H=%d B=%d T=%d fin=%d: %.4f ms per launch = %.0f ns per step (%s)\n", H, B, T, fin, ms / 20, ms / 20 / T * 1e6, hipGetErrorString(hipGetLastError()));
