@@ -47,6 +47,7 @@ extern "C" {
 #define NWW_HEAD_E_BRANCHFORMER 9 /* EBranchformerModel   architectures.py:546-616 */
 #define NWW_HEAD_QUARTZNET 10  /* QuartzNetModel          architectures.py:370-437 */
 #define NWW_HEAD_E2E_QUARTZNET 11 /* E2ERawQuartzNet      architectures.py:798-817; model.py:119-132 (learned filters on raw PCM, no STFT) */
+#define NWW_HEAD_RNN 12        /* RNNModel (bi-LSTM, hidden size 64; layer_dim is not read)  architectures.py:149-161 */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from .config import FrontendConfig, HeadConfig, HEAD_CODE, ACT_CODE, raw_frontend_depth
+from .config import FrontendConfig, HeadConfig, HEAD_CODE, ACT_CODE, RNN_HIDDEN, raw_frontend_depth
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NWW_LIB_PATH") or os.path.join(_PKG, "libnwwhip.so")   # override: A/B builds only
@@ -163,6 +163,8 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
     c.in_rows, c.in_cols = head.input_shape
     c.layer_dim, c.n_blocks, c.embedding_dim = head.layer_dim, head.n_blocks, head.embedding_dim
     c.activation = ACT_CODE[head.activation]
+    if head.model_type == "rnn":
+        c.layer_dim = RNN_HIDDEN          # RNNModel reads no layer_dim: its LSTM's hidden size is fixed
     if head.model_type in ("quartznet", "e2e_quartznet"):
         # [channels, kernel, repetitions] entries: channels in the CRNN's channel slots, kernel + 65536 * repetitions beside them; the
         # entry count goes over as it is, so that nww_create refuses more than four instead of a truncated list running

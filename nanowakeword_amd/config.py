@@ -16,12 +16,14 @@ from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Optional, Tuple
 
 HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn", "e_branchformer",
-              "quartznet", "e2e_quartznet")
+              "quartznet", "e2e_quartznet", "rnn")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
 HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8,
-             "e_branchformer": 9, "quartznet": 10, "e2e_quartznet": 11}
+             "e_branchformer": 9, "quartznet": 10, "e2e_quartznet": 11, "rnn": 12}
+# RNNModel's nn.LSTM has a fixed hidden size (architectures.py:152-154); layer_dim is not read
+RNN_HIDDEN = 64
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
 # nww_config carries at most 4 [channels, kernel, repetitions] entries of a QuartzNet and the planner at most 16 blocks
 QUARTZNET_MAX_ENTRIES, QUARTZNET_MAX_BLOCKS = 4, 16
@@ -264,6 +266,9 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     elif mt == "gru":                     # architectures.py:129-145
         _gru(s, "model.gru", F, L, nb)
         _lin(s, "model.fc", E, 2 * L)
+    elif mt == "rnn":                     # architectures.py:149-161 (RNNModel: bi-LSTM of hidden size 64, layer_dim ignored)
+        _gru(s, "model.layer1", F, RNN_HIDDEN, nb, gates=4)
+        _lin(s, "model.layer2", E, 2 * RNN_HIDDEN)
     elif mt == "bcresnet":                # architectures.py:620-687
         s["model.init_conv.0.weight"] = (32, 1, 3, 3)
         _bn(s, "model.init_conv.1", 32)
@@ -399,6 +404,14 @@ def head_macs(cfg: HeadConfig) -> int:
             steps_rev = T if l < nb - 1 else 1
             m += T * 3 * L * (isz + L) + steps_rev * 3 * L * (isz + L)
         m += 2 * L * E
+    elif mt == "rnn":
+        # the same T + 1-cell count as the GRU head, four gates, hidden size 64
+        H = RNN_HIDDEN
+        for l in range(nb):
+            isz = F if l == 0 else 2 * H
+            steps_rev = T if l < nb - 1 else 1
+            m += (T + steps_rev) * 4 * H * (isz + H)
+        m += 2 * H * E
     elif mt == "bcresnet":
         h, w = T, F
         m += 9 * 32 * h * w

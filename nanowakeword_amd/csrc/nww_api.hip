@@ -62,7 +62,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_E2E_QUARTZNET) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_RNN) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)

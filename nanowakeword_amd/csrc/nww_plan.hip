@@ -8,7 +8,7 @@ const Knobs& nww_knobs() {
         Knobs r;
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
-        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
+        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.rnn_ih_fused = env("NWW_RNN_IH_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
         r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
@@ -590,11 +590,14 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
         // strided GEMM over M = B rows instead of B*T, into the row behind the forward direction's xg) - and with h = 0 that
         // step has no recurrent product: rnn_x3 computes it in the forward direction's launch.
         const bool fold = last && x3;
-        // GRU head, first layer fed by the head's own input features (<= 64 per frame), two-term arithmetic: the forward direction's input
+        // GRU / RNN head, first layer fed by the head's own input features (GRU: 32 / 64 per frame; LSTM at H = 32 / 64: 32 / 64 / 96), two-term arithmetic: the forward direction's input
         // projection is computed inside the recurrence kernel - x_t W_ih^T on the matrix pipe beside h W_hh^T - instead of a GEMM that
         // writes T x 3H gate pre-activations per clip to HBM for the recurrence to read back (635 MB each way at B = 4096, T = 101, H = 128).
         const float* wih_f = p.W(prefix + ".weight_ih_l" + std::to_string(l));
-        const float wi_scale = (fold && l == 0 && in_id == BUF_X && G == 3 && products == 3 && (cur_I == 32 || cur_I == 64) && (H == 32 || H == 64 || H == 128) &&
+        // (the LSTM's 101 x 256 pre-activations per clip at H = 64: 423 MB each way at B = 4096); NWW_RNN_IH_FUSED = 0 keeps the GEMM for both cells
+        const bool fin_shape = G == 3 ? (cur_I == 32 || cur_I == 64) && (H == 32 || H == 64 || H == 128)
+                                      : (cur_I == 32 || cur_I == 64 || cur_I == 96) && (H == 32 || H == 64);
+        const float wi_scale = (nww_knobs().rnn_ih_fused && fold && l == 0 && in_id == BUF_X && products == 3 && fin_shape &&
                                 wih_f && (reinterpret_cast<uintptr_t>(wih_f) & 15) == 0)
                                    ? f16_wscale(f16_fetch(p.h, wih_f, (size_t)G * H * cur_I)) : 0.0f;
         const float* whh_fwd = p.W(prefix + ".weight_hh_l" + std::to_string(l));
@@ -1102,6 +1105,13 @@ int plan_gru(PlanCtx& p) {                          // GRUModel: architectures.p
     const nww_config& c = p.h->cfg;
     add_bigru_last(p, "model.gru", BUF_X, c.in_rows, c.in_cols, c.layer_dim, c.n_blocks, 2, 0, 1, 4);
     set_tail(p, "fc", 4, 2 * c.layer_dim, p.W("model.fc.weight"), p.W("model.fc.bias"));
+    return NWW_OK;
+}
+
+int plan_rnn(PlanCtx& p) {                          // RNNModel: architectures.py:149-161 (bidirectional nn.LSTM, hidden size 64 whatever layer_dim says)
+    const nww_config& c = p.h->cfg;
+    add_bigru_last(p, "model.layer1", BUF_X, c.in_rows, c.in_cols, 64, c.n_blocks, 2, 0, 1, 4, 4);
+    set_tail(p, "layer2", 4, 128, p.W("model.layer2.weight"), p.W("model.layer2.bias"));
     return NWW_OK;
 }
 
@@ -1832,6 +1842,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         case NWW_HEAD_E_BRANCHFORMER: rc = plan_e_branchformer(p); break;
         case NWW_HEAD_QUARTZNET: rc = plan_quartznet(p); break;
         case NWW_HEAD_E2E_QUARTZNET: plan_raw_frontend(p); rc = plan_quartznet(p); break;
+        case NWW_HEAD_RNN: rc = plan_rnn(p); break;
     }
     if (rc != NWW_OK) return rc;
     plan_tail(p);

@@ -69,6 +69,9 @@ void nww_build_spec(nww_handle* h) {
         case NWW_HEAD_GRU:
             s.gru("model.gru", F, L, nb); s.lin("model.fc", E, 2 * L);
             break;
+        case NWW_HEAD_RNN:                        // RNNModel (architectures.py:149-161): nn.LSTM(F, 64, n_blocks), Linear(128, E)
+            s.gru("model.layer1", F, 64, nb, 4); s.lin("model.layer2", E, 128);
+            break;
         case NWW_HEAD_BCRESNET: {
             s.add("model.init_conv.0.weight", {32, 1, 3, 3}); s.bn("model.init_conv.1", 32);
             const int ch[4] = {32, 64, 128, 256};

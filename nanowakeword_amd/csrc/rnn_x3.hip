@@ -44,14 +44,14 @@ __device__ __forceinline__ uint32_t pack_hi16r(uint32_t a, uint32_t b) { return 
 
 // G = 3: GRU (r, z, n), G = 4: LSTM (i, f, g, o); NP = 6 or 9 partial products per operand pair; NB = 16-wide column blocks per
 // wave (2 at H = 128: four waves, one per SIMD, so that each has the whole 512-register file - 288 of them weight fragments)
-// FIN = 32 / 64 (GRU, NP = 3): the input projection of the step fused in (RnnArgs::fin); 0: xg precomputed
+// FIN = 32 / 64 (GRU), 32 / 64 / 96 (LSTM at H = 32 / 64), NP = 3: the input projection of the step fused in (RnnArgs::fin); 0: xg precomputed
 // PAD (NP = 3): the layer's real width a.H < H, a multiple of 4 (layer_dim = 48, 96, 100 ...): the instance of the next width with the rows
 // and columns beyond a.H read as zeros - a padded unit has zero weights, biases and input pre-activations, so its gates are 1/2, 1/2,
 // tanh(0) and its state stays 0 for ever (GRU: h' = h / 2; LSTM: c' = c / 2, h' = tanh(c') / 2), which adds nothing to the real units'
 // products; all global addressing uses the real width and nothing is stored for the padded units
 template <int G, int H, int NP, int NB, int FIN = 0, bool PAD = false>
 __global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(RnnArgs a) {
-    static_assert(FIN == 0 || (G == 3 && NP == 3 && FIN % 32 == 0), "fused input projection: GRU, two-term form");
+    static_assert(FIN == 0 || (NP == 3 && FIN % 32 == 0 && (G == 3 || (H <= 64 && NB == 1))), "fused input projection: two-term form; LSTM at H = 32 / 64");
     static_assert(!PAD || (FIN == 0 && NP == 3), "padded widths: two-term form, xg precomputed");
     const int HR = PAD ? a.H : H;                             // real width (global addressing)
     constexpr int KSI = FIN / 32;                             // k-blocks of the input product
@@ -279,10 +279,22 @@ __global__ void __launch_bounds__(64 * (H / (16 * NB))) rnn_x3_kernel(RnnArgs a)
                     const float ng = rnn_tanh(xq[2] + rg * a2);
                     hn = (1.0f - zg) * ng + zg * hprev[bl][r];
                 } else {
-                    const float ig = rnn_sigmoid(H2 ? xpf[0][0][bl][r] + fmaf(acc[0][bl][r], un, bh[0][bl]) : xpf[0][0][bl][r] + acc[0][bl][r] + bh[0][bl]);
-                    const float fg = rnn_sigmoid(H2 ? xpf[0][1][bl][r] + fmaf(acc[1][bl][r], un, bh[1][bl]) : xpf[0][1][bl][r] + acc[1][bl][r] + bh[1][bl]);
-                    const float gg = rnn_tanh(H2 ? xpf[0][2][bl][r] + fmaf(acc[2][bl][r], un, bh[2][bl]) : xpf[0][2][bl][r] + acc[2][bl][r] + bh[2][bl]);
-                    const float og = rnn_sigmoid(H2 ? xpf[0][G - 1][bl][r] + fmaf(acc[G - 1][bl][r], un, bh[G - 1][bl]) : xpf[0][G - 1][bl][r] + acc[G - 1][bl][r] + bh[G - 1][bl]);
+                    float ig, fg, gg, og;
+                    if constexpr (FIN > 0) {
+                        // the fused input product back at the true scale plus b_ih (two-term form)
+                        float xq[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) xq[q] = fmaf(accx[q][bl][r], unx, bi[q][bl]);
+                        ig = rnn_sigmoid(xq[0] + fmaf(acc[0][bl][r], un, bh[0][bl]));
+                        fg = rnn_sigmoid(xq[1] + fmaf(acc[1][bl][r], un, bh[1][bl]));
+                        gg = rnn_tanh(xq[2] + fmaf(acc[2][bl][r], un, bh[2][bl]));
+                        og = rnn_sigmoid(xq[3] + fmaf(acc[3][bl][r], un, bh[3][bl]));
+                    } else {
+                        ig = rnn_sigmoid(H2 ? xpf[0][0][bl][r] + fmaf(acc[0][bl][r], un, bh[0][bl]) : xpf[0][0][bl][r] + acc[0][bl][r] + bh[0][bl]);
+                        fg = rnn_sigmoid(H2 ? xpf[0][1][bl][r] + fmaf(acc[1][bl][r], un, bh[1][bl]) : xpf[0][1][bl][r] + acc[1][bl][r] + bh[1][bl]);
+                        gg = rnn_tanh(H2 ? xpf[0][2][bl][r] + fmaf(acc[2][bl][r], un, bh[2][bl]) : xpf[0][2][bl][r] + acc[2][bl][r] + bh[2][bl]);
+                        og = rnn_sigmoid(H2 ? xpf[0][G - 1][bl][r] + fmaf(acc[G - 1][bl][r], un, bh[G - 1][bl]) : xpf[0][G - 1][bl][r] + acc[G - 1][bl][r] + bh[G - 1][bl]);
+                    }
                     cn = fg * cprev[bl][r] + ig * gg;
                     hn = og * rnn_tanh(cn);
                 }
@@ -344,8 +356,10 @@ bool rnn_x3_usable(const RnnArgs& a) {
 
 hipError_t launch_rnn_x3(const RnnArgs& a, hipStream_t s) {
     if (!rnn_x3_usable(a) || (a.gates != 3 && a.gates != 4)) return hipErrorInvalidValue;
-    if (a.gates == 3 && a.fin > 0 && (a.products != 3 || (a.fin != 32 && a.fin != 64) || !a.x_in || !a.w_ih || !a.b_ih || a.reverse))
-        return hipErrorInvalidValue;                          // fused input projection (GRU, two-term form)
+    // fused input projection: two-term form, forward direction; GRU from 32 / 64 features, LSTM at H = 32 / 64 from 32 / 64 / 96
+    const bool fin_ok = a.gates == 3 ? (a.fin == 32 || a.fin == 64) : ((a.fin == 32 || a.fin == 64 || a.fin == 96) && (a.H == 32 || a.H == 64));
+    if (a.fin != 0 && (!fin_ok || a.products != 3 || !a.x_in || !a.w_ih || !a.b_ih || a.reverse || (reinterpret_cast<uintptr_t>(a.w_ih) & 15) != 0))
+        return hipErrorInvalidValue;
     const bool pad = rnn_x3_padded(a);
     const int HP = a.H <= 32 ? 32 : a.H <= 64 ? 64 : 128;     // the instance's width
     const dim3 grid((a.B + 15) / 16);
@@ -369,10 +383,16 @@ hipError_t launch_rnn_x3(const RnnArgs& a, hipStream_t s) {
     else if (a.products == 6) RNN_H(GV, 6, 0, false)                                                                 \
     else if (pad) RNN_H(GV, 3, 0, true)                                                                              \
     else RNN_H(GV, 3, 0, false)
-    if (a.gates == 4) { RNN_P(4) }
+#define RNN_F4(FV)                                                                                                   \
+    if (HP == 32) RNN_L(4, 32, 3, FV, false) else RNN_L(4, 64, 3, FV, false)
+    if (a.gates == 4 && a.fin == 32) { RNN_F4(32) }
+    else if (a.gates == 4 && a.fin == 64) { RNN_F4(64) }
+    else if (a.gates == 4 && a.fin == 96) { RNN_F4(96) }
+    else if (a.gates == 4) { RNN_P(4) }
     else if (a.fin == 32) { RNN_H(3, 3, 32, false) }
     else if (a.fin == 64) { RNN_H(3, 3, 64, false) }
     else { RNN_P(3) }
+#undef RNN_F4
 #undef RNN_P
 #undef RNN_H
 #undef RNN_L

@@ -90,7 +90,7 @@ def _tensor_for(key: str, shape, seed: int) -> np.ndarray:
 
 _FIRST_LAYER_KEYS = {
     "model.layer1.weight", "model.conv1.weight", "model.cnn.0.weight", "model.gru.weight_ih_l0",
-    "model.gru.weight_ih_l0_reverse", "model.init_conv.0.weight", "model.input_proj.weight",
+    "model.gru.weight_ih_l0_reverse", "model.layer1.weight_ih_l0", "model.layer1.weight_ih_l0_reverse", "model.init_conv.0.weight", "model.input_proj.weight",
     "model.conv_block.0.weight", "model.tcn_blocks.0.conv1.weight", "model.tcn_blocks.0.downsample.weight",
     "model.quartznet_blocks.0.depthwise_conv.weight", "model.quartznet_blocks.0.residual_connector.0.weight",
 }

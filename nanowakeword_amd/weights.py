@@ -20,7 +20,7 @@ from typing import Mapping, Optional, Tuple
 
 import numpy as np
 
-from .config import FrontendConfig, HeadConfig, param_spec, raw_frontend_frames
+from .config import FrontendConfig, HeadConfig, RNN_HIDDEN, param_spec, raw_frontend_frames
 
 
 def state_dict_from_pt(path: str) -> dict:
@@ -49,7 +49,16 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
         idx = [int(m.group(1)) for k in keys for m in [re.match(pattern, k)] if m]
         return max(idx) + 1 if idx else 0
 
-    if "model.layer1.weight" in keys:
+    if "model.layer1.weight_hh_l0" in keys and "model.layer2.weight" in keys:      # RNNModel (architectures.py:149-161)
+        F = shp("model.layer1.weight_ih_l0")[1]
+        if shp("model.layer1.weight_hh_l0") != (4 * RNN_HIDDEN, RNN_HIDDEN):
+            raise ValueError(f"rnn: unexpected recurrent weight shape {shp('model.layer1.weight_hh_l0')} (an nn.LSTM of hidden size {RNN_HIDDEN})")
+        if input_shape is None:
+            raise ValueError("rnn: the sequence length is not in the weights; pass input_shape=(T, F)")
+        if input_shape[1] != F:
+            raise ValueError(f"input_shape F={input_shape[1]} but the LSTM expects {F} features")
+        cfg = HeadConfig("rnn", input_shape, n_blocks=n_indexed(r"model\.layer1\.weight_hh_l(\d+)$"), **kw)
+    elif "model.layer1.weight" in keys:
         L, TF = shp("model.layer1.weight")
         if input_shape is None:
             raise ValueError(f"dnn weights fix T*F={TF} only: pass input_shape=(T, F)")
@@ -134,7 +143,7 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn/e2e_quartznet)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/rnn/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn/e2e_quartznet)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:
@@ -240,7 +249,9 @@ def state_dict_from_onnx(path_or_bytes):
     convs = [n for n in g.nodes if n.op_type == "Conv" and anon(n.inputs[1])]
     grus = [n for n in g.nodes if n.op_type == "GRU"]
     lstms = [n for n in g.nodes if n.op_type == "LSTM"]
-    if lstms and not any(n.op_type == "Conv" and anon(n.inputs[1]) for n in g.nodes):
+    # a bare LSTM graph is the RNN head where its last Linear is named model.layer2 (RNNModel, architectures.py:149-161); LSTMModel's is not
+    rnn_head = bool(lstms) and not convs and "model.layer2.weight" in named and "model.layer2.bias" in named
+    if lstms and not rnn_head and not any(n.op_type == "Conv" and anon(n.inputs[1]) for n in g.nodes):
         raise NotImplementedError("model_type='lstm' (LSTMModel) is out of scope; the CRNN's LSTM backend is supported")
 
     def folded(node, wkey, bias_key, bn_prefix):
@@ -353,6 +364,8 @@ def state_dict_from_onnx(path_or_bytes):
             gru_layers("model.rnn") if grus else lstm_layers("model.rnn")
         elif grus:                                                                  # GRU
             gru_layers("model.gru")
+        elif rnn_head:                                                              # RNN (bi-LSTM)
+            lstm_layers("model.layer1")
 
     cls = [n for n in g.nodes if n.op_type == "Gemm" and len(n.inputs) > 1 and n.inputs[1] == _WRAP + "classifier.0.weight"]
     if len(cls) != 1:

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Measure every BASELINE.json config on ONE MI355X (the multi-GPU ones at their per-GPU batch):
 clips/s PCM->logit with PCM resident in HBM, per-launch times, max |dlogit| vs the oracle on a few clips.
-Prints one JSON line per config.  (bench.py remains the contract benchmark for configs[1].)"""
+Prints one JSON line per config.  (bench.py remains the contract benchmark for configs[1].)
+--rnn [out]: the RNN head's fused / unfused input projection A/B (rnn_main) -> profiles/rnn_bench_configs.jsonl."""
 import json
 import os
+import re
 import sys
 import time
 
@@ -84,7 +86,107 @@ def raw_frontend_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps):
             "cpu_oracle_clips_per_s": round(k / (time.perf_counter() - t0), 1)}
 
 
+RNN_CASES = [((101, 64), "pcm", 2048), ((101, 64), "pcm", 4096), ((16, 96), "features", 2048), ((16, 96), "features", 4096)]
+RNN_WARMUP, RNN_STEPS, RNN_REPEATS = 20, 100, 3
+
+
+def rnn_child():
+    """One process = one setting of NWW_RNN_IH_FUSED (the knob is read once): every RNN_CASES row, ms per step as the median of RNN_STEPS
+    device-event timings behind RNN_WARMUP warm-up steps, and max |dlogit| of 8 clips against the float64 restatement of the tests."""
+    import torch
+    import oracle
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rnn_oracle
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig, head_macs
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_features, synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    for shape, source, B in RNN_CASES:
+        cfg = HeadConfig("rnn", shape)
+        sd = synth_state_dict(cfg)
+        m = HipModel(cfg, fe, device=0, state_dict=sd, window=window, mel_fb=fb)
+        ts = torch.cuda.Stream(dev)                   # the launches and the events that time them go to this one stream
+        stream = ts.cuda_stream
+        logits = torch.empty(B, dtype=torch.float32, device=dev)
+        if source == "pcm":
+            host = synth_pcm("noise", B, 16000, seed=10)
+            x = torch.from_numpy(host).to(dev)
+            m.reserve(B, 16000)
+            step = lambda: m.forward_pcm_dev(x.data_ptr(), B, 16000, logits.data_ptr(), 0, stream)
+            lm = oracle.frontend_logmel(host[:8], window, fb, n_mels=fe.n_mels, center=fe.center).transpose(0, 2, 1)
+            ref = rnn_oracle.model_forward(np.ascontiguousarray(lm), sd, cfg, dtype=np.float64).ravel()
+        else:
+            host = synth_features(B, shape, seed=10)
+            x = torch.from_numpy(host).to(dev)
+            m.reserve(B, 0)
+            step = lambda: m.forward_features_dev(x.data_ptr(), B, logits.data_ptr(), 0, stream)
+            ref = rnn_oracle.model_forward(host[:8], sd, cfg, dtype=np.float64).ravel()
+        for _ in range(RNN_WARMUP):
+            step()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for e0, e1 in ev:
+            e0.record(ts); step(); e1.record(ts)
+        torch.cuda.synchronize()
+        ms = float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+        plan = [l for l in m.describe_plan().split("\n") if l.startswith(("lstm:", "lin_x3:model.layer1", "gemm:model.layer1"))]
+        print(json.dumps({"shape": list(shape), "source": source, "batch": B, "ms_per_step": round(ms, 4), "plan": plan,
+                          "mmac_per_clip": round(head_macs(cfg) / 1e6, 3),
+                          "max_abs_dlogit_vs_float64": float(np.abs(logits[:8].cpu().numpy() - ref).max())}), flush=True)
+        m.close()
+
+
+def rnn_main(out_path):
+    """The RNN head's A/B: NWW_RNN_IH_FUSED = 1 and 0 alternated, RNN_REPEATS fresh processes each, one after another; per row the median
+    of the repeats, their spread (max - min), and whether the fused route wins by more than the larger spread.  Then the per-launch breakdown
+    of tools/profile_head.py under each setting, in runs of their own."""
+    import subprocess
+
+    def run(args, knob):
+        env = dict(os.environ, NWW_RNN_IH_FUSED=knob)
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable] + args, env=env, cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"child {args} (NWW_RNN_IH_FUSED={knob}) exited {r.returncode}")
+        return r.stdout
+    runs = {"1": [], "0": []}
+    for _ in range(RNN_REPEATS):
+        for knob in ("1", "0"):
+            runs[knob].append([json.loads(l) for l in run([os.path.abspath(__file__), "--rnn-child"], knob).splitlines() if l.startswith("{")])
+    lines = []
+    for i, (shape, source, B) in enumerate(RNN_CASES):
+        T, F = shape
+        f = [r[i]["ms_per_step"] for r in runs["1"]]
+        u = [r[i]["ms_per_step"] for r in runs["0"]]
+        fm, um = float(np.median(f)), float(np.median(u))
+        spread = max(max(f) - min(f), max(u) - min(u))
+        lines.append({"config": f"rnn {T}x{F} from {source} B={B}", "head": "rnn", "batch": B, "warmup": RNN_WARMUP, "steps": RNN_STEPS,
+                      "fused_ms_repeats": f, "unfused_ms_repeats": u, "fused_ms_per_step": round(fm, 4), "unfused_ms_per_step": round(um, 4),
+                      "spread_ms": round(spread, 4), "fused_faster_by_ms": round(um - fm, 4), "fused_wins": bool(um - fm > spread),
+                      "fused_clips_per_s": round(B / fm * 1e3, 1), "unfused_clips_per_s": round(B / um * 1e3, 1),
+                      "xg_bytes_each_way": B * T * 4 * 64 * 4,          # T x 4H float32 gate pre-activations per clip, written then read
+                      "mmac_per_clip": runs["1"][0][i]["mmac_per_clip"],
+                      "max_abs_dlogit_vs_float64": {"fused": max(r[i]["max_abs_dlogit_vs_float64"] for r in runs["1"]),
+                                                    "unfused": max(r[i]["max_abs_dlogit_vs_float64"] for r in runs["0"])},
+                      "fused_plan": runs["1"][0][i]["plan"], "unfused_plan": runs["0"][0][i]["plan"]})
+    for knob in ("1", "0"):
+        txt = run([os.path.join(ROOT, "tools", "profile_head.py"), "rnn", "4096"], knob)
+        lines.append({"config": "rnn 101x64 from pcm B=4096 per-launch (tools/profile_head.py)", "NWW_RNN_IH_FUSED": int(knob),
+                      "launch_ms": {m.group(1): float(m.group(2)) for m in (re.match(r"(.*?\S)\s+([0-9.]+) ms", l) for l in txt.splitlines()) if m}})
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--rnn-child" in sys.argv[1:]:
+        return rnn_child()
+    if "--rnn" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--rnn"]
+        return rnn_main(rest[0] if rest else os.path.join(ROOT, "profiles", "rnn_bench_configs.jsonl"))
     import torch
     import oracle
     from nanowakeword_amd.config import FrontendConfig, HeadConfig, head_macs

@@ -294,6 +294,7 @@ def main():
     make_transformer_goldens(args.out)
     make_ebranchformer_goldens(args.out)
     make_tcn_goldens(args.out)
+    make_rnn_goldens(args.out)
     print("done ->", args.out)
 
 
@@ -764,6 +765,88 @@ def make_tcn_goldens(out_dir):
     print("onnx fixture tcn", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
 
 
+def rnn_cases():
+    """RNN head cases of heads_rnn.npz (name, HeadConfig): the reference's default feature shape, the mel shape, a width the fused input
+    projection does not take, two stacked layers, and the GELU classifier on a narrow embedding."""
+    from nanowakeword_amd.config import HeadConfig
+    return [
+        ("rnn_16x96", HeadConfig("rnn", (16, 96))),
+        ("rnn_101x64", HeadConfig("rnn", (101, 64))),
+        ("rnn_98x40", HeadConfig("rnn", (98, 40))),
+        ("rnn_12x32_nb2", HeadConfig("rnn", (12, 32), n_blocks=2)),
+        ("rnn_7x64_gelu", HeadConfig("rnn", (7, 64), activation="gelu", embedding_dim=16)),
+    ]
+
+
+def rnn_ref_model(Model, cfg, sd):
+    """The reference's own Model(model_type="rnn") with the synthetic weights loaded; its state_dict keys / shapes must equal param_spec
+    (model.py:191-197, architectures.py:149-161)."""
+    from nanowakeword_amd.config import param_spec
+    conf = {"activation_function": cfg.activation, "embedding_dim": cfg.embedding_dim}
+    m = Model(conf, "g", input_shape=cfg.input_shape, model_type=cfg.model_type, layer_dim=cfg.layer_dim, n_blocks=cfg.n_blocks)
+    ref_keys = {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.endswith("num_batches_tracked")}
+    spec = dict(param_spec(cfg))
+    assert ref_keys == spec, (set(ref_keys) ^ set(spec), {k: (ref_keys[k], spec[k]) for k in set(ref_keys) & set(spec) if ref_keys[k] != spec[k]})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.eval()
+
+
+def make_rnn_goldens(out_dir):
+    """RNN head (own files: earlier fixtures stay byte-identical): logits and embeddings of the reference's Model on seeded synthetic
+    weights -> heads_rnn.npz, and a reference export (opset 17) with its probabilities -> onnx/rnn.onnx + expected_rnn.npz."""
+    install_stubs()
+    torch.set_num_threads(1)
+    from nanowakeword.modules.model import Model
+    from nanowakeword._export import onnx as ref_onnx
+    from nanowakeword_amd.config import HeadConfig
+    from nanowakeword_amd.synth import synth_features, synth_state_dict, state_dict_checksum
+    fr = dict(np.load(os.path.join(out_dir, "frontend.npz"), allow_pickle=False))
+    db64 = fr["db64"]
+    heads, meta = {}, {}
+    for name, cfg in rnn_cases():
+        sd = synth_state_dict(cfg)
+        m = rnn_ref_model(Model, cfg, sd)
+        feats = synth_features(4, cfg.input_shape)
+        with torch.no_grad():
+            out = {"feats": feats, "logits_feat": m(torch.from_numpy(feats)).numpy(), "emb_feat": m.model(torch.from_numpy(feats)).numpy()}
+            if cfg.input_shape == (101, 64):
+                out["logits_pcm"] = m(torch.from_numpy(np.ascontiguousarray(db64.transpose(0, 2, 1)))).numpy()
+        out["sd_checksum"] = np.array(state_dict_checksum(sd))
+        out["ref_spec_json"] = np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))
+        meta[name] = cfg.to_dict()
+        for k, v in out.items():
+            heads[f"{name}/{k}"] = v
+        print("rnn", name, {k: getattr(v, "shape", v) for k, v in out.items()}, "logits", out["logits_feat"].ravel())
+    heads["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(out_dir, "heads_rnn.npz"), **heads)
+
+    # the reference's own export of a small RNN head (recipe of make_onnx_fixtures)
+    onnx_dir = os.path.join(out_dir, "onnx")
+    from torch.onnx._internal.torchscript_exporter import onnx_proto_utils
+    onnx_proto_utils._add_onnxscript_fn = lambda model_bytes, custom_opsets: model_bytes
+    orig_export = torch.onnx.export
+
+    def export_torchscript(*a, **k):
+        k.setdefault("dynamo", False)
+        return orig_export(*a, **k)
+    torch.onnx.export = export_torchscript
+    cfg = HeadConfig("rnn", (6, 32), embedding_dim=16)
+    sd = synth_state_dict(cfg)
+    m = rnn_ref_model(Model, cfg, sd)
+    ref_onnx.export_onnx_model(m, cfg.input_shape, {}, "rnn", onnx_dir)
+    path = os.path.join(onnx_dir, "rnn.onnx")
+    assert os.path.exists(path), "export of the rnn failed"
+    feats = synth_features(4, cfg.input_shape)
+    with torch.no_grad():
+        logits = m(torch.from_numpy(feats)).numpy()
+    arrays = {"rnn/feats": feats, "rnn/logits": logits.reshape(-1).astype(np.float32),
+              "rnn/probs": (1.0 / (1.0 + np.exp(-logits.astype(np.float64)))).reshape(-1).astype(np.float32),
+              "meta_json": np.array(json.dumps({"rnn": cfg.to_dict()}))}
+    np.savez_compressed(os.path.join(onnx_dir, "expected_rnn.npz"), **arrays)
+    torch.onnx.export = orig_export
+    print("onnx fixture rnn", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
+
+
 def ebranchformer_cases():
     """E-Branchformer cases of heads_ebranchformer.npz (name, HeadConfig): the reference defaults (d_model 144, 4 heads) at both feature shapes,
     two blocks, and d_model 48 (a width without fused instances).  Few clips per case: the default width is 0.35 M parameters, the file stays small."""
@@ -1193,6 +1276,8 @@ if __name__ == "__main__":
         make_round6_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--transformer-only":
         make_transformer_goldens(os.path.join(REPO, "tests", "golden"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--rnn-only":
+        make_rnn_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--ebranchformer-only":
         make_ebranchformer_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--quartznet-only":
