@@ -48,6 +48,7 @@ extern "C" {
 #define NWW_HEAD_QUARTZNET 10  /* QuartzNetModel          architectures.py:370-437 */
 #define NWW_HEAD_E2E_QUARTZNET 11 /* E2ERawQuartzNet      architectures.py:798-817; model.py:119-132 (learned filters on raw PCM, no STFT) */
 #define NWW_HEAD_RNN 12        /* RNNModel (bi-LSTM, hidden size 64; layer_dim is not read)  architectures.py:149-161 */
+#define NWW_HEAD_E2E_CNN 13    /* E2ERawCNN               architectures.py:739-795; model.py:109-117 (the raw-PCM frontend, then strided 3x3 convs) */
 
 #define NWW_ACT_RELU 0         /* model.py:81-87 activation_function */
 #define NWW_ACT_GELU 1
@@ -78,7 +79,9 @@ typedef struct nww_config {
        in_rows the raw frontend's rows for the clip length: per stage L' = (L - 1) / stride + 1 with strides 16, 4, 4, ...; its
        e2e_quartznet_config travels as NWW_HEAD_QUARTZNET's entries do; mel_major_features = 0 and the mel fields are ignored.
        For this head nww_num_frames is that frame law, nww_frontend* return the learned frontend's output ([B][in_cols][rows], or
-       [B][rows][in_cols] with frames_major; melpower_out must be NULL), nww_forward_features* run the backbone alone */
+       [B][rows][in_cols] with frames_major; melpower_out must be NULL), nww_forward_features* run the backbone alone.
+       NWW_HEAD_E2E_CNN: the same frontend fields (its depth defaults to 2 in the reference); the backbone's channel counts are fixed by
+       the architecture, the image it sees is in_cols high and in_rows wide */
     int32_t layer_dim, n_blocks, embedding_dim, activation;
     /* crnn_cnn_channels (<= 4 stages) for NWW_HEAD_CRNN; tcn_channels (1..4 levels, model.py:228) for NWW_HEAD_TCN, whose
        tcn_kernel_size (>= 2) travels in layer_dim (TCNModel reads no layer_dim); quartznet_config (model.py:239-248) for

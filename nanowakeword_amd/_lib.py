@@ -176,6 +176,9 @@ def make_config(head: HeadConfig, fe: FrontendConfig, device: int = 0, mel_major
         if head.model_type == "e2e_quartznet":
             # the raw frontend's width and depth travel in layer_dim / n_blocks, which E2ERawQuartzNet does not read (include/nww.h)
             c.layer_dim, c.n_blocks = head.e2e_frontend_channels, raw_frontend_depth(head)
+    elif head.model_type == "e2e_cnn":
+        # as for e2e_quartznet: the raw frontend's width and depth in layer_dim / n_blocks, which E2ERawCNN does not read
+        c.layer_dim, c.n_blocks = head.e2e_frontend_channels, raw_frontend_depth(head)
     else:
         # the TCN's channel list travels in the CRNN's channel slots and its kernel size in layer_dim (include/nww.h)
         ch = list(head.tcn_channels if head.model_type == "tcn" else head.crnn_cnn_channels)

@@ -16,12 +16,12 @@ from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Optional, Tuple
 
 HEAD_TYPES = ("dnn", "cnn", "crnn", "gru", "bcresnet", "conformer", "e2e_dnn", "transformer", "tcn", "e_branchformer",
-              "quartznet", "e2e_quartznet", "rnn")
+              "quartznet", "e2e_quartznet", "rnn", "e2e_cnn")
 ACTIVATIONS = ("relu", "gelu", "silu")
 
 # integer codes shared with include/nww.h
 HEAD_CODE = {"dnn": 0, "cnn": 1, "crnn": 2, "gru": 3, "bcresnet": 4, "conformer": 5, "e2e_dnn": 6, "transformer": 7, "tcn": 8,
-             "e_branchformer": 9, "quartznet": 10, "e2e_quartznet": 11, "rnn": 12}
+             "e_branchformer": 9, "quartznet": 10, "e2e_quartznet": 11, "rnn": 12, "e2e_cnn": 13}
 # RNNModel's nn.LSTM has a fixed hidden size (architectures.py:152-154); layer_dim is not read
 RNN_HIDDEN = 64
 ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
@@ -29,6 +29,11 @@ ACT_CODE = {"relu": 0, "gelu": 1, "silu": 2}
 QUARTZNET_MAX_ENTRIES, QUARTZNET_MAX_BLOCKS = 4, 16
 # RawAudioFrontend (architectures.py:692-710): stage 0 is Conv1d(k 41, stride 16, pad 20), every later stage Conv1d(k 13, stride 4, pad 6)
 RAW_FRONTEND_MAX_DEPTH, RAW_FRONTEND_MAX_WIDTH = 4, 512
+# the raw-PCM heads (mode="e2e" on learned filters): RawAudioFrontend, then a backbone on its output
+RAW_HEADS = ("e2e_quartznet", "e2e_cnn")
+# RawAudioBackbone (architectures.py:739-762): (Cin, Cout, stride over the image's H, stride over its W) of conv1..conv4; each is
+# Conv2d(3x3, pad 1, no bias) + BatchNorm2d + the activation, then the global mean and Linear(96, E)
+RAW_CNN_LAYERS = ((1, 24, 1, 2), (24, 48, 2, 2), (48, 64, 2, 2), (64, 96, 1, 1))
 # rows of the Transformer's positional-encoding buffer (PositionalEncoding(max_len=5000), architectures.py:31)
 PE_MAX_LEN = 5000
 
@@ -79,7 +84,7 @@ class HeadConfig:
     branchformer_n_head: int = 4
     # model.py:239-248 config key of the QuartzNet head: [[channels, kernel, repetitions], ...]
     quartznet_config: List[List[int]] = field(default_factory=lambda: [[256, 33, 1], [256, 33, 1], [512, 39, 1]])
-    # model.py:99-100,119-132 config keys of the raw-PCM heads (mode="e2e"); depth None is the model type's own default (3 for e2e_quartznet)
+    # model.py:99-100,119-132 config keys of the raw-PCM heads (mode="e2e"); depth None is the model type's own default (3 for e2e_quartznet, 2 for e2e_cnn)
     e2e_frontend_channels: int = 32
     e2e_frontend_depth: Optional[int] = None
     e2e_quartznet_config: List[List[int]] = field(default_factory=lambda: [[64, 11, 1], [64, 13, 1], [64, 17, 1]])
@@ -118,7 +123,7 @@ class HeadConfig:
         self.e2e_quartznet_config = self._quartznet_entries("e2e_quartznet_config", self.e2e_quartznet_config, self.model_type == "e2e_quartznet")
         self.e2e_frontend_channels = int(self.e2e_frontend_channels)
         self.e2e_frontend_depth = None if self.e2e_frontend_depth is None else int(self.e2e_frontend_depth)
-        if self.model_type == "e2e_quartznet":
+        if self.model_type in RAW_HEADS:
             depth = raw_frontend_depth(self)
             if not 1 <= depth <= RAW_FRONTEND_MAX_DEPTH:
                 raise ValueError(f"e2e_frontend_depth must be 1..{RAW_FRONTEND_MAX_DEPTH} (got {depth})")
@@ -167,8 +172,20 @@ def quartznet_blocks(cfg: "HeadConfig"):
 
 
 def raw_frontend_depth(cfg: "HeadConfig") -> int:
-    """Stages of the raw-PCM frontend: e2e_frontend_depth, or the model type's default (model.py:121)."""
-    return 3 if cfg.e2e_frontend_depth is None else cfg.e2e_frontend_depth
+    """Stages of the raw-PCM frontend: e2e_frontend_depth, or the model type's default (model.py:111, 121)."""
+    if cfg.e2e_frontend_depth is None:
+        return 2 if cfg.model_type == "e2e_cnn" else 3
+    return cfg.e2e_frontend_depth
+
+
+def raw_cnn_planes(cfg: "HeadConfig"):
+    """(H, W) of the RawAudioBackbone's image and of every conv's output: per axis (n - 1) // stride + 1 (3x3, pad 1)."""
+    h, w = cfg.input_shape[1], cfg.input_shape[0]        # the image is the frontend's output: channels high, rows wide
+    out = [(h, w)]
+    for _, _, sh, sw in RAW_CNN_LAYERS:
+        h, w = (h - 1) // sh + 1, (w - 1) // sw + 1
+        out.append((h, w))
+    return out
 
 
 def raw_frontend_stages(cfg: "HeadConfig"):
@@ -189,6 +206,17 @@ def raw_frontend_frames(cfg: "HeadConfig", n_samples: int) -> int:
     for _, _, _, s in raw_frontend_stages(cfg):
         n = (n - 1) // s + 1
     return n
+
+
+def raw_frontend_macs_upper(cfg: "HeadConfig") -> int:
+    """An UPPER estimate of the raw frontend's multiply-accumulates from the config alone: the clip length is not in it, so rows of a stage
+    are taken as rows of the next x its stride (1008 and 252 for e2e_quartznet's defaults where a 1 s clip has 1000 and 250: 14.74 against
+    14.68 MMAC); raw_frontend_macs(cfg, n_samples) is the exact count for a clip length."""
+    m, rows = 0, cfg.input_shape[0]
+    for cin, co, k, stride in reversed(raw_frontend_stages(cfg)):
+        m += rows * k * cin * co
+        rows *= stride
+    return m
 
 
 def raw_frontend_macs(cfg: "HeadConfig", n_samples: int) -> int:
@@ -215,6 +243,13 @@ def _lin(spec, prefix, out_f, in_f):
 def _ln(spec, prefix, d):
     spec[prefix + ".weight"] = (d,)
     spec[prefix + ".bias"] = (d,)
+
+
+def _raw_frontend(spec, cfg):
+    """RawAudioFrontend's nn.Sequential: Conv1d (no bias), BatchNorm1d, ReLU per stage."""
+    for i, (cin, co, k, _) in enumerate(raw_frontend_stages(cfg)):
+        spec[f"model.frontend.conv_blocks.{3*i}.weight"] = (co, cin, k)
+        _bn(spec, f"model.frontend.conv_blocks.{3*i+1}", co)
 
 
 def _gru(spec, prefix, input_size, hidden, n_layers, gates=3):
@@ -344,11 +379,9 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
         _lin(s, "model.fc", E, cin)
     elif mt in ("quartznet", "e2e_quartznet"):   # architectures.py:370-437 (QuartzNetBlock, QuartzNetModel); :798-817 E2ERawQuartzNet
         qp = "model."
-        if mt == "e2e_quartznet":         # RawAudioFrontend's nn.Sequential: Conv1d (no bias), BatchNorm1d, ReLU per stage
+        if mt == "e2e_quartznet":
             qp = "model.backbone."
-            for i, (cin, co, k, _) in enumerate(raw_frontend_stages(cfg)):
-                s[f"model.frontend.conv_blocks.{3*i}.weight"] = (co, cin, k)
-                _bn(s, f"model.frontend.conv_blocks.{3*i+1}", co)
+            _raw_frontend(s, cfg)
         for i, (cin, co, k) in enumerate(quartznet_blocks(cfg)):
             p = f"{qp}quartznet_blocks.{i}"
             s[f"{p}.depthwise_conv.weight"] = (cin, 1, k); s[f"{p}.depthwise_conv.bias"] = (cin,)
@@ -358,6 +391,12 @@ def param_spec(cfg: HeadConfig) -> "OrderedDict[str, Tuple[int, ...]]":
                 s[f"{p}.residual_connector.0.weight"] = (co, cin, 1); s[f"{p}.residual_connector.0.bias"] = (co,)
                 _bn(s, f"{p}.residual_connector.1", co)
         _lin(s, f"{qp}fc", E, quartznet_blocks(cfg)[-1][1])
+    elif mt == "e2e_cnn":                 # architectures.py:739-795 (RawAudioBackbone, E2ERawCNN)
+        _raw_frontend(s, cfg)
+        for i, (cin, co, _, _) in enumerate(RAW_CNN_LAYERS, start=1):
+            s[f"model.backbone.conv{i}.0.weight"] = (co, cin, 3, 3)
+            _bn(s, f"model.backbone.conv{i}.1", co)
+        _lin(s, "model.backbone.fc", E, 96)
     elif mt == "e2e_dnn":                 # architectures.py:840-865 (E2E_MelSpectrogram_CNN body)
         cin = 1
         for i, c in enumerate((16, 32, 64)):
@@ -447,15 +486,16 @@ def head_macs(cfg: HeadConfig) -> int:
         m += cin * E
     elif mt in ("quartznet", "e2e_quartznet"):
         if mt == "e2e_quartznet":
-            # an UPPER estimate for the raw frontend: the clip length is not in the config, so rows of a stage are taken as rows of the
-            # next x its stride (1008 and 252 at the defaults where a 1 s clip has 1000 and 250: 14.74 against 14.68 MMAC);
-            # raw_frontend_macs(cfg, n_samples) is the exact count for a clip length
-            rows = T
-            for cin, co, k, stride in reversed(raw_frontend_stages(cfg)):
-                m += rows * k * cin * co
-                rows *= stride
+            m += raw_frontend_macs_upper(cfg)
         # per step: depthwise k Cin, pointwise Cin Cout, the projected residual Cin Cout where the widths differ; then fc
         for cin, co, k in quartznet_blocks(cfg):
             m += T * (k * cin + cin * co + (cin * co if cin != co else 0))
         m += quartznet_blocks(cfg)[-1][1] * E
+    elif mt == "e2e_cnn":
+        # the raw frontend by the same upper estimate as e2e_quartznet's; the backbone exactly: every output pixel of a conv counts all
+        # nine taps, as the reference's zero-padded Conv2d does, then fc
+        m += raw_frontend_macs_upper(cfg)
+        for (cin, co, _, _), (h, w) in zip(RAW_CNN_LAYERS, raw_cnn_planes(cfg)[1:]):
+            m += 9 * cin * co * h * w
+        m += 96 * E
     return int(m)

@@ -62,7 +62,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
     if (!cfg || !out) return fail(nullptr, NWW_ERR_INVALID, "nww_create: null argument");
     *out = nullptr;
     const nww_config& c = *cfg;
-    if (c.head_type < 0 || c.head_type > NWW_HEAD_RNN) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
+    if (c.head_type < 0 || c.head_type > NWW_HEAD_E2E_CNN) return fail(nullptr, NWW_ERR_INVALID, "Unsupported model_type code %d", c.head_type);
     if (c.activation < 0 || c.activation > 2) return fail(nullptr, NWW_ERR_INVALID, "bad activation code %d", c.activation);
     if (c.conv_arith != NWW_ARITH_DEFAULT && c.conv_arith != NWW_ARITH_F32 && c.conv_arith != NWW_ARITH_BF16X6 && c.conv_arith != NWW_ARITH_BF16X9 &&
         c.conv_arith != NWW_ARITH_F16X3)
@@ -98,7 +98,7 @@ extern "C" int nww_create(const nww_config* cfg, nww_handle** out) {
         if (blocks > 16) return fail(nullptr, NWW_ERR_UNSUPPORTED, "quartznet_config expands to %d blocks; at most 16 are supported", blocks);
     }
     // the raw-PCM frontend's channels / depth travel in layer_dim / n_blocks (include/nww.h)
-    if (c.head_type == NWW_HEAD_E2E_QUARTZNET) {
+    if (nww_raw_head(c)) {
         if (c.n_blocks < 1 || c.n_blocks > 4) return fail(nullptr, NWW_ERR_INVALID, "e2e_frontend_depth must be 1..4 (got %d)", c.n_blocks);
         if (c.layer_dim > 512 || (c.layer_dim << (c.n_blocks - 1)) > 512)
             return fail(nullptr, NWW_ERR_INVALID, "the raw frontend's final width e2e_frontend_channels * 2^(depth - 1) must be <= 512 (got %d at depth %d)", c.layer_dim, c.n_blocks);

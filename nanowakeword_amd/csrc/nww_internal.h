@@ -31,6 +31,7 @@
 #include "qn_x3.h"
 #include "raw_conv.h"
 #include "raw_x3.h"
+#include "conv2s_x3.h"
 
 // rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
 // architectures.py:31)
@@ -102,7 +103,7 @@ struct nww_handle {
     int cap_rows = 0;              // cap_B rounded up to 128: the blocked trunk -> fc1 buffer is written in 128-clip row blocks
     float* d_ws = nullptr;
     int16_t* d_pcm = nullptr;
-    // NWW_HEAD_E2E_QUARTZNET: the stages of the learned raw-PCM frontend (planned at nww_finalize) and the two buffers its
+    // the raw-PCM heads (nww_raw_head): the stages of the learned raw-PCM frontend (planned at nww_finalize) and the two buffers its
     // intermediate rows alternate between; its last stage writes d_logmel (time-major, what the backbone reads)
     struct RawStage { std::string name; int cin, cout, k, stride; const float *w, *b; };
     std::vector<RawStage> raw;
@@ -185,9 +186,10 @@ void fold_batchnorms(nww_handle* h);
 void transpose_depthwise(nww_handle* h);
 void fold_quartznet(nww_handle* h);
 void fold_raw_frontend(nww_handle* h);
+void fold_raw_backbone(nww_handle* h);
 int upload_weight_arena(nww_handle* h);
 int build_frontend_tables(nww_handle* h);
-inline bool nww_raw_head(const nww_config& c) { return c.head_type == NWW_HEAD_E2E_QUARTZNET; }
+inline bool nww_raw_head(const nww_config& c) { return c.head_type == NWW_HEAD_E2E_QUARTZNET || c.head_type == NWW_HEAD_E2E_CNN; }
 // rows the head's frontend yields for N samples: the STFT's frame count, or for the raw-PCM heads the strided convs' frame law
 // (stage 0 stride 16, every later stage 4; zero padding, so any N >= 1 has rows)
 inline int nww_pcm_rows(const nww_handle* h, int N) {
@@ -197,6 +199,12 @@ inline int nww_pcm_rows(const nww_handle* h, int N) {
     return L < 1 ? -1 : L;
 }
 // the QuartzNet blocks' and fc's key prefix: the raw-PCM head holds them under model.backbone
+// NWW_HEAD_E2E_CNN: RawAudioBackbone's four conv stages (architectures.py:739-762) on the channels-last plane [A = image W][Bd = image H]
+struct RawCnnLayer { int cin, cout, sA, sB; };
+inline const RawCnnLayer* nww_raw_cnn_layers() {
+    static const RawCnnLayer L[4] = {{1, 24, 2, 1}, {24, 48, 2, 2}, {48, 64, 2, 2}, {64, 96, 1, 1}};
+    return L;
+}
 inline std::string nww_quartznet_prefix(const nww_config& c) { return nww_raw_head(c) ? "model.backbone." : "model."; }
 // NWW_HEAD_QUARTZNET: (Cin, Cout, k) of every block from the packed [channels, kernel, repetitions] entries (include/nww.h)
 struct QnBlock { int cin, cout, k; };
@@ -211,7 +219,7 @@ inline std::vector<QnBlock> nww_quartznet_blocks(const nww_config& c) {
 // The run-time knobs, read from the environment on the first call (nww_plan.hip).  Each selection knob defaults to the
 // specialised kernel; setting it picks a general one.
 struct Knobs {
-    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, raw_fused, rnn_ih_fused, mha_mfma, bc_front, bc_chain, tail;
+    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, raw_fused, conv2s_x3, rnn_ih_fused, mha_mfma, bc_front, bc_chain, tail;
     int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
     int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2
 };

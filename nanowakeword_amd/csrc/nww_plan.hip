@@ -8,7 +8,7 @@ const Knobs& nww_knobs() {
         Knobs r;
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
-        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.rnn_ih_fused = env("NWW_RNN_IH_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
+        r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.conv2s_x3 = env("NWW_CONV2S_X3", 1); r.rnn_ih_fused = env("NWW_RNN_IH_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
         r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
@@ -1625,6 +1625,55 @@ void plan_raw_frontend(PlanCtx& p) {
                         ", conv+bn+relu) [f16x3]";
 }
 
+// E2ERawCNN's RawAudioBackbone (architectures.py:739-776) behind the raw frontend: four conv + BatchNorm + activation stages on the
+// channels-last plane the frontend writes ([rows][width] = the reference's image transposed; the 3x3 weights were transposed at
+// nww_finalize, not the data), one launch each, then the mean over the plane and the Linear in the tail.  conv1 (one input channel, nine
+// taps: VALU work) is a conv2d_strided launch; conv2 .. conv4 run on conv2s_x3 under the default arithmetic - the tile's power of two
+// comes from the tile's data and the weights' from each output channel, so there is no bound to compound over the layers, no range
+// window to guard and no clamp - and on conv2d_strided (float32) under every other arithmetic, with NWW_CONV2S_X3=0, or for a weight
+// tensor whose per-row scale could not be formed.  DESIGN.md 4.4h
+int plan_e2e_cnn(PlanCtx& p) {
+    const nww_config& c = p.h->cfg;
+    const RawCnnLayer* ly = nww_raw_cnn_layers();
+    const int act = c.activation, mbuf = 2;
+    const char* an = act == ACT_GELU ? "gelu" : act == ACT_SILU ? "silu" : "relu";
+    int A = c.in_rows, Bd = c.in_cols, in = BUF_X;
+    for (int i = 0; i < 4; ++i) {
+        const int Cin = ly[i].cin, Cout = ly[i].cout, sA = ly[i].sA, sB = ly[i].sB, Ao = conv2s_out(A, sA), Bo = conv2s_out(Bd, sB), out = i % 2;
+        const std::string q = "model.backbone.conv" + std::to_string(i + 1), conv = q + ".0";
+        const std::string what = q + " (3x3 stride " + std::to_string(sB) + "x" + std::to_string(sA) + " " + std::to_string(Cin) + "->" + std::to_string(Cout) + ", " +
+                                 std::to_string(Bd) + "x" + std::to_string(A) + "->" + std::to_string(Bo) + "x" + std::to_string(Ao) + ")+bn+" + an;
+        const float *w = p.W(conv + ".c2.w"), *bias = p.W(conv + ".c2.b"), *wk = p.W(conv + ".c2.wk"), *un = p.W(conv + ".c2.un");
+        p.need(out, (size_t)Ao * Bo * Cout);
+        const void* packed = nullptr;
+        if (nww_knobs().conv2s_x3 && p.h->f16 && p.h->conv_products == 6 && conv2s_x3_supported(Cin, Cout, sA, sB) && wk && un)
+            packed = p.pack_one(conv2s_x3_packed_bytes(Cin, Cout), [&](void* d) {
+                return launch_qn_x3_pack(wk, d, conv2s_x3_coutp(Cout), 9 * conv2s_x3_cp(Cin), 1.0f, p.h->own_stream);
+            });
+        const int Ai = A, Bi = Bd;
+        if (packed)
+            p.add("conv2s_x3:" + what + " [f16x3]", [=](Run& r) {
+                Conv2sX3Args a;
+                a.x = src(r, in); a.y = r.buf[out]; a.packed = static_cast<const unsigned char*>(packed); a.w_un = un; a.bias = bias;
+                a.B = r.B; a.A = Ai; a.Bd = Bi; a.Cin = Cin; a.Cout = Cout; a.stride = sA; a.act = act;
+                return launch_conv2s_x3(a, r.stream);
+            });
+        else
+            p.add("conv2d_strided:" + what + " [f32]", [=](Run& r) {
+                Conv2sArgs a;
+                a.x = src(r, in); a.y = r.buf[out]; a.w = w; a.bias = bias;
+                a.B = r.B; a.A = Ai; a.Bd = Bi; a.Cin = Cin; a.Cout = Cout; a.sA = sA; a.sB = sB; a.act = act;
+                return launch_conv2d_strided(a, r.stream);
+            });
+        in = out; A = Ao; Bd = Bo;
+    }
+    const int fin = in, L = A * Bd;
+    p.need(mbuf, 96);
+    p.add("mean:plane", [=](Run& r) { return launch_mean_mid(r.buf[fin], r.buf[mbuf], r.B, L, 96, r.stream); });
+    set_tail(p, "fc", mbuf, 96, p.W("model.backbone.fc.weight"), p.W("model.backbone.fc.bias"));
+    return NWW_OK;
+}
+
 int plan_quartznet(PlanCtx& p) {                    // QuartzNetModel: architectures.py:370-437; time-major rows [T][C], as the head input is
     const nww_config& c = p.h->cfg;
     const std::string qp = nww_quartznet_prefix(c);
@@ -1825,6 +1874,7 @@ extern "C" int nww_finalize(nww_handle* h) {
     if (h->cfg.head_type == NWW_HEAD_BCRESNET) transpose_depthwise(h);
     if (h->cfg.head_type == NWW_HEAD_QUARTZNET || h->cfg.head_type == NWW_HEAD_E2E_QUARTZNET) fold_quartznet(h);
     if (nww_raw_head(h->cfg)) fold_raw_frontend(h);
+    if (h->cfg.head_type == NWW_HEAD_E2E_CNN) fold_raw_backbone(h);
     int rc = upload_weight_arena(h);
     if (rc == NWW_OK) rc = build_frontend_tables(h);
     if (rc != NWW_OK) return rc;
@@ -1843,6 +1893,7 @@ extern "C" int nww_finalize(nww_handle* h) {
         case NWW_HEAD_QUARTZNET: rc = plan_quartznet(p); break;
         case NWW_HEAD_E2E_QUARTZNET: plan_raw_frontend(p); rc = plan_quartznet(p); break;
         case NWW_HEAD_RNN: rc = plan_rnn(p); break;
+        case NWW_HEAD_E2E_CNN: plan_raw_frontend(p); rc = plan_e2e_cnn(p); break;
     }
     if (rc != NWW_OK) return rc;
     plan_tail(p);

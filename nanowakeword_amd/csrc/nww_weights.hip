@@ -39,6 +39,15 @@ void nww_build_spec(nww_handle* h) {
     const nww_config& c = h->cfg;
     SpecBuilder s{h->keys, h->tensors};
     const int T = c.in_rows, F = c.in_cols, L = c.layer_dim, E = c.embedding_dim, nb = c.n_blocks;
+    // the raw-PCM heads: RawAudioFrontend's Conv1d (no bias) + BatchNorm1d per stage (channels in layer_dim, depth in n_blocks)
+    auto raw_frontend = [&] {
+        for (int i = 0, cin = 1; i < nb; ++i) {
+            const int co = L << i;
+            s.add("model.frontend.conv_blocks." + std::to_string(3 * i) + ".weight", {co, cin, i == 0 ? 41 : 13});
+            s.bn("model.frontend.conv_blocks." + std::to_string(3 * i + 1), co);
+            cin = co;
+        }
+    };
     switch (c.head_type) {
         case NWW_HEAD_DNN:
             s.lin("model.layer1", L, T * F); s.ln("model.layernorm1", L);
@@ -152,13 +161,8 @@ void nww_build_spec(nww_handle* h) {
             s.lin("model.fc", E, cin);
             break;
         }
-        case NWW_HEAD_E2E_QUARTZNET:              // E2ERawQuartzNet (architectures.py:798-817): RawAudioFrontend's Conv1d (no bias) + BatchNorm1d
-            for (int i = 0, cin = 1; i < nb; ++i) {   // per stage (channels in layer_dim, depth in n_blocks), then the QuartzNet under model.backbone
-                const int co = L << i;
-                s.add("model.frontend.conv_blocks." + std::to_string(3 * i) + ".weight", {co, cin, i == 0 ? 41 : 13});
-                s.bn("model.frontend.conv_blocks." + std::to_string(3 * i + 1), co);
-                cin = co;
-            }
+        case NWW_HEAD_E2E_QUARTZNET:              // E2ERawQuartzNet (architectures.py:798-817): the frontend, then the QuartzNet under model.backbone
+            raw_frontend();
             [[fallthrough]];
         case NWW_HEAD_QUARTZNET: {                // QuartzNetModel (architectures.py:370-437); the entries as include/nww.h packs them
             const auto blocks = nww_quartznet_blocks(c);
@@ -175,6 +179,16 @@ void nww_build_spec(nww_handle* h) {
                 }
             }
             s.lin(qp + "fc", E, blocks.back().cout);
+            break;
+        }
+        case NWW_HEAD_E2E_CNN: {                  // E2ERawCNN (architectures.py:779-795): the frontend, then RawAudioBackbone's Conv2d (no bias) +
+            raw_frontend();                       // BatchNorm2d stages and its Linear
+            const RawCnnLayer* ly = nww_raw_cnn_layers();
+            for (int i = 0; i < 4; ++i) {
+                const std::string p = "model.backbone.conv" + std::to_string(i + 1);
+                s.add(p + ".0.weight", {ly[i].cout, ly[i].cin, 3, 3}); s.bn(p + ".1", ly[i].cout);
+            }
+            s.lin("model.backbone.fc", E, 96);
             break;
         }
         case NWW_HEAD_E2E_DNN: {
@@ -328,6 +342,57 @@ void fold_raw_frontend(nww_handle* h) {
             h->tensors[conv + ".raw.wk"] = tk;
         }
         Cin = Cout;
+    }
+}
+
+// RawAudioBackbone: each stage's BatchNorm2d folded into its conv ONCE in float64, and the 3x3 taps transposed to the channels-last plane
+// the frontend writes ([A = image W][Bd = image H][C]: the A tap is the weight's kw, the Bd tap its kh).  Derived tensors "<conv>.c2.*":
+//   w [3 (A)][3 (Bd)][Cin][Cout] = alpha weight, tap-major for conv2d_strided; b [Cout] = beta (the convs have no bias of their own);
+//   where conv2s_x3 has the shape, its operand: wk [CoutP][9 Cp] the same weights as rows with tap-major columns (Cin padded to Cp, Cout to
+//   CoutP with zeros), every row times its own power of two - the row's largest magnitude lands in [2^14, 2^15), a zero row takes 1 - and
+//   un [CoutP] the reciprocals.  A row whose scale cannot be formed (a value that is not finite, a power of two outside float32) leaves
+//   wk out, and the planner takes conv2d_strided
+void fold_raw_backbone(nww_handle* h) {
+    const RawCnnLayer* ly = nww_raw_cnn_layers();
+    for (int i = 0; i < 4; ++i) {
+        const int Cin = ly[i].cin, Cout = ly[i].cout;
+        const std::string conv = "model.backbone.conv" + std::to_string(i + 1) + ".0", bn = "model.backbone.conv" + std::to_string(i + 1) + ".1";
+        const auto &w = h->tensors[conv + ".weight"].data, &g = h->tensors[bn + ".weight"].data, &b = h->tensors[bn + ".bias"].data,
+                   &mu = h->tensors[bn + ".running_mean"].data, &var = h->tensors[bn + ".running_var"].data;
+        HostTensor tw, tb;
+        tw.shape = {3, 3, Cin, Cout}; tw.data.resize((size_t)9 * Cin * Cout);
+        tb.shape = {Cout}; tb.data.resize(Cout);
+        for (int co = 0; co < Cout; ++co) {
+            const double al = (double)g[co] / std::sqrt((double)var[co] + 1e-5);
+            tb.data[co] = (float)((double)b[co] - (double)mu[co] * al);
+            for (int ci = 0; ci < Cin; ++ci)
+                for (int kh = 0; kh < 3; ++kh)
+                    for (int kw = 0; kw < 3; ++kw)
+                        tw.data[((size_t)(kw * 3 + kh) * Cin + ci) * Cout + co] = (float)(al * (double)w[(((size_t)co * Cin + ci) * 3 + kh) * 3 + kw]);
+        }
+        tw.loaded = tb.loaded = true;
+        h->tensors[conv + ".c2.w"] = tw; h->tensors[conv + ".c2.b"] = tb;
+        if (!conv2s_x3_supported(Cin, Cout, ly[i].sA, ly[i].sB)) continue;
+        const int Cp = conv2s_x3_cp(Cin), CoutP = conv2s_x3_coutp(Cout), K = 9 * Cp;
+        HostTensor tk, tu;
+        tk.shape = {CoutP, K}; tk.data.assign((size_t)CoutP * K, 0.0f);
+        tu.shape = {CoutP}; tu.data.assign(CoutP, 1.0f);
+        bool ok = true;
+        for (int co = 0; co < Cout && ok; ++co) {
+            float m = 0.0f;
+            for (int q = 0; q < 9 * Cin; ++q) { const float v = std::fabs(tw.data[(size_t)q * Cout + co]); if (!(v <= m)) m = v; }   // a NaN sticks
+            if (!std::isfinite(m) || !std::isfinite(tb.data[co])) { ok = false; break; }
+            int e = 0;
+            if (m > 0.0f) e = 14 - std::ilogb(m);
+            if (e > 120 || e < -120) { ok = false; break; }
+            const float ws = std::ldexp(1.0f, e);
+            tu.data[co] = std::ldexp(1.0f, -e);
+            for (int t = 0; t < 9; ++t)
+                for (int ci = 0; ci < Cin; ++ci) tk.data[(size_t)co * K + t * Cp + ci] = tw.data[((size_t)t * Cin + ci) * Cout + co] * ws;
+        }
+        if (!ok) continue;
+        tk.loaded = tu.loaded = true;
+        h->tensors[conv + ".c2.wk"] = tk; h->tensors[conv + ".c2.un"] = tu;
     }
 }
 

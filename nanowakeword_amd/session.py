@@ -17,7 +17,7 @@ from typing import Mapping, Optional
 import numpy as np
 
 from . import _lib
-from .config import FrontendConfig, HeadConfig, param_spec
+from .config import FrontendConfig, HeadConfig, RAW_HEADS, param_spec
 
 
 class NwwError(RuntimeError):
@@ -165,12 +165,12 @@ class HipModel:
         return np.ascontiguousarray(pcm)
 
     def frontend(self, pcm, return_power: bool = False):
-        """int16 [B,N] -> log-mel dB float32 [B, n_mels, frames] (+ mel power); for model_type="e2e_quartznet" the learned raw-PCM
+        """int16 [B,N] -> log-mel dB float32 [B, n_mels, frames] (+ mel power); for the raw-PCM heads (e2e_quartznet, e2e_cnn) the learned raw-PCM
         frontend's output [B, channels, rows] (no mel power there)."""
         pcm = self._pcm(pcm)
         B, N = pcm.shape
         T = self.num_frames(N)
-        raw = self.head.model_type == "e2e_quartznet"
+        raw = self.head.model_type in RAW_HEADS
         if T <= 0 and raw:
             raise ValueError(f"a clip needs at least one sample (got {N})")
         if T <= 0:
@@ -444,7 +444,7 @@ class HipSession:
         self.accepts_int16 = True       # HipInterpreter then skips the float32 round trip of nanointerpreter.py:750
         if mode == "e2e":
             T = model.num_frames(self.clip_samples)
-            if model.head.model_type == "e2e_quartznet":      # learned filters on raw PCM: num_frames is the raw frontend's frame law
+            if model.head.model_type in RAW_HEADS:      # learned filters on raw PCM: num_frames is the raw frontend's frame law
                 rows, cols = T, model.head.input_shape[1]
             else:
                 rows, cols = (model.fe.n_mels, T) if model.head.model_type == "e2e_dnn" else (T, model.fe.n_mels)

@@ -115,6 +115,8 @@ def _is_seq_bn(key: str) -> bool:
         return n == 1
     if cont == "conv_blocks":
         return n % 3 == 1
+    if len(parts) >= 4 and parts[-4] == "backbone" and cont in ("conv1", "conv2", "conv3", "conv4"):   # RawAudioBackbone: Conv2d, BatchNorm2d, activation
+        return n == 1
     return False
 
 

@@ -20,7 +20,7 @@ from typing import Mapping, Optional, Tuple
 
 import numpy as np
 
-from .config import FrontendConfig, HeadConfig, RNN_HIDDEN, param_spec, raw_frontend_frames
+from .config import FrontendConfig, HeadConfig, RAW_HEADS, RNN_HIDDEN, param_spec, raw_frontend_frames
 
 
 def state_dict_from_pt(path: str) -> dict:
@@ -48,6 +48,16 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
     def n_indexed(pattern):
         idx = [int(m.group(1)) for k in keys for m in [re.match(pattern, k)] if m]
         return max(idx) + 1 if idx else 0
+
+    def raw_frontend_shape(what):
+        """(channels, depth) of the raw-PCM heads' frontend from its weights; input_shape must be what the backbone sees"""
+        if input_shape is None:
+            raise ValueError(f"{what}: the clip length is not in the weights; pass input_shape=(rows, channels) as the backbone sees it")
+        depth = n_indexed(r"model\.frontend\.conv_blocks\.(\d+)\.running_var") // 3 + 1
+        ch = shp("model.frontend.conv_blocks.0.weight")[0]
+        if input_shape[1] != ch * 2 ** (depth - 1):
+            raise ValueError(f"input_shape F={input_shape[1]} but the raw frontend gives {ch * 2 ** (depth - 1)} channels")
+        return ch, depth
 
     if "model.layer1.weight_hh_l0" in keys and "model.layer2.weight" in keys:      # RNNModel (architectures.py:149-161)
         F = shp("model.layer1.weight_ih_l0")[1]
@@ -123,15 +133,12 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
             raise ValueError(f"input_shape F={input_shape[1]} but the TCN expects {F} features")
         cfg = HeadConfig("tcn", input_shape, tcn_channels=chans, tcn_kernel_size=k, **kw)
     elif "model.frontend.conv_blocks.0.weight" in keys and any(k.startswith("model.backbone.quartznet_blocks.") for k in keys):
-        if input_shape is None:
-            raise ValueError("e2e_quartznet: the clip length is not in the weights; pass input_shape=(rows, channels) as the backbone sees it")
-        depth = n_indexed(r"model\.frontend\.conv_blocks\.(\d+)\.running_var") // 3 + 1
-        ch = shp("model.frontend.conv_blocks.0.weight")[0]
-        F = ch * 2 ** (depth - 1)
-        if input_shape[1] != F:
-            raise ValueError(f"input_shape F={input_shape[1]} but the raw frontend gives {F} channels")
+        ch, depth = raw_frontend_shape("e2e_quartznet")
         cfg = HeadConfig("e2e_quartznet", input_shape, e2e_frontend_channels=ch, e2e_frontend_depth=depth,
                          e2e_quartznet_config=_quartznet_entries(shp, n_indexed, "model.backbone."), **kw)
+    elif "model.frontend.conv_blocks.0.weight" in keys and "model.backbone.conv1.0.weight" in keys:
+        ch, depth = raw_frontend_shape("e2e_cnn")
+        cfg = HeadConfig("e2e_cnn", input_shape, e2e_frontend_channels=ch, e2e_frontend_depth=depth, **kw)
     elif any(k.startswith("model.quartznet_blocks.") for k in keys):
         if input_shape is None:
             raise ValueError("quartznet: the sequence length is not in the weights; pass input_shape=(T, F)")
@@ -143,7 +150,7 @@ def infer_head_config(sd: Mapping, input_shape: Optional[Tuple[int, int]] = None
     elif "model.conv_block.0.weight" in keys:
         cfg = HeadConfig("e2e_dnn", input_shape or (64, 101), **kw)
     else:
-        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/rnn/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn/e2e_quartznet)")
+        raise ValueError("state_dict does not belong to an in-scope head (dnn/cnn/crnn-gru/gru/rnn/bcresnet/conformer/transformer/tcn/e_branchformer/quartznet/e2e_dnn/e2e_quartznet/e2e_cnn)")
     spec = param_spec(cfg)
     for k, s in spec.items():
         if k not in keys:
@@ -298,15 +305,12 @@ def state_dict_from_onnx(path_or_bytes):
                 raise ValueError(f"quartznet block {i}: widths differ but no projection was found")
             i += 1
 
-    mode, clip_samples, fe = "features", 16000, None
-    if any(k.startswith("model.backbone.quartznet_blocks.") for k in named):        # E2ERawQuartzNet: learned filters on raw PCM, no STFT
-        mode = "e2e"
-        if len(in_shape) not in (2, 3):
-            raise ValueError(f"e2e_quartznet model with input shape {in_shape}: expected [batch, 1, samples]")
-        clip_samples = int(in_shape[-1])
+    def raw_frontend_chain(what):
         # RawAudioFrontend: the chain of strided convs from the graph input, each folded with its BatchNorm (the convs have no bias of
-        # their own, so the folded bias is the BatchNorm's beta)
-        t, stage, cfg_probe = g.inputs[0][0], 0, None
+        # their own, so the folded bias is the BatchNorm's beta) -> (the last stage's output tensor, the number of stages)
+        if len(in_shape) not in (2, 3):
+            raise ValueError(f"{what} model with input shape {in_shape}: expected [batch, 1, samples]")
+        t, stage = g.inputs[0][0], 0
         while True:
             nxt = [n for n in convs if n.inputs[0] == t and int(n.attrs.get("strides", [1])[0]) > 1]
             if len(nxt) != 1:
@@ -314,14 +318,42 @@ def state_dict_from_onnx(path_or_bytes):
             folded(nxt[0], f"model.frontend.conv_blocks.{3*stage}.weight", None, f"model.frontend.conv_blocks.{3*stage+1}")
             relu = [n for n in _consumers(g, nxt[0].outputs[0]) if n.op_type == "Relu"]
             if len(relu) != 1:
-                raise ValueError(f"e2e_quartznet frontend stage {stage}: expected Conv -> Relu")
+                raise ValueError(f"{what} frontend stage {stage}: expected Conv -> Relu")
             t, stage = relu[0].outputs[0], stage + 1
         if stage == 0:
-            raise ValueError("e2e_quartznet: no strided frontend conv reads the graph input")
-        quartznet_blocks("model.backbone.")
+            raise ValueError(f"{what}: no strided frontend conv reads the graph input")
+        return t, stage
+
+    def raw_input_shape(model_type, stage):
         width = sd[f"model.frontend.conv_blocks.{3*(stage-1)}.weight"].shape[0]
-        cfg_probe = HeadConfig("e2e_quartznet", (1, width), e2e_frontend_channels=int(sd["model.frontend.conv_blocks.0.weight"].shape[0]), e2e_frontend_depth=stage)
-        input_shape = (raw_frontend_frames(cfg_probe, clip_samples), width)
+        probe = HeadConfig(model_type, (1, width), e2e_frontend_channels=int(sd["model.frontend.conv_blocks.0.weight"].shape[0]), e2e_frontend_depth=stage)
+        return (raw_frontend_frames(probe, clip_samples), width)
+
+    mode, clip_samples, fe = "features", 16000, None
+    if any(k.startswith("model.backbone.quartznet_blocks.") for k in named):        # E2ERawQuartzNet: learned filters on raw PCM, no STFT
+        mode = "e2e"
+        _, stage = raw_frontend_chain("e2e_quartznet")
+        clip_samples = int(in_shape[-1])
+        quartznet_blocks("model.backbone.")
+        input_shape = raw_input_shape("e2e_quartznet", stage)
+    elif "model.backbone.fc.weight" in named and any(g.initializers[n.inputs[1]].ndim == 4 for n in convs):   # E2ERawCNN: the same frontend, then
+        mode = "e2e"                                                                # RawAudioBackbone's four Conv2d, each folded with its BatchNorm2d
+        t, stage = raw_frontend_chain("e2e_cnn")
+        clip_samples = int(in_shape[-1])
+        from .config import RAW_CNN_LAYERS
+        unsq = [n for n in _consumers(g, t) if n.op_type == "Unsqueeze"]
+        if len(unsq) != 1:
+            raise ValueError("e2e_cnn: expected the frontend's output to be unsqueezed into a one-channel image")
+        conv2d = [n for n in convs if g.initializers[n.inputs[1]].ndim == 4]          # in graph order: conv1 .. conv4
+        if len(conv2d) != len(RAW_CNN_LAYERS) or conv2d[0].inputs[0] != unsq[0].outputs[0]:
+            raise ValueError(f"e2e_cnn: expected {len(RAW_CNN_LAYERS)} Conv2d behind the unsqueezed frontend output, found {len(conv2d)}")
+        for i, (n, (cin, co, sh, sw)) in enumerate(zip(conv2d, RAW_CNN_LAYERS), start=1):
+            W = g.initializers[n.inputs[1]]
+            if tuple(W.shape) != (co, cin, 3, 3) or [int(v) for v in n.attrs.get("strides", [1, 1])] != [sh, sw] \
+                    or [int(v) for v in n.attrs.get("pads", [0, 0, 0, 0])] != [1, 1, 1, 1]:
+                raise ValueError(f"e2e_cnn backbone conv{i}: expected Conv2d({cin}, {co}, 3, stride ({sh}, {sw}), padding 1), got weights {tuple(W.shape)}")
+            folded(n, f"model.backbone.conv{i}.0.weight", None, f"model.backbone.conv{i}.1")
+        input_shape = raw_input_shape("e2e_cnn", stage)
     elif "model.mel_spec.real_basis" in named:                                        # E2E_MelSpectrogram_CNN
         mode = "e2e"
         clip_samples = int(in_shape[-1])
@@ -461,7 +493,7 @@ def load_session(path: str, device: int = 0):
         head, fe, sd, extras, meta = load_bundle(path)
     # feature-mode heads never run the frontend and e2e exports carry their own tables (model.mel_spec.*): neither
     # needs torch to rebuild torchaudio's float32 tables
-    feature_mode = meta.get("mode", "e2e") == "features" or head.model_type == "e2e_quartznet"       # (learned filters: no mel tables at all)
+    feature_mode = meta.get("mode", "e2e") == "features" or head.model_type in RAW_HEADS       # (learned filters: no mel tables at all)
     own_tables = "frontend.window" in extras or any(k.startswith("model.mel_spec.") for k in sd)
     model = HipModel(head, fe, device=device, state_dict=sd, window=extras.get("frontend.window"),
                      mel_fb=extras.get("frontend.mel_fb"), tables="builtin" if (feature_mode or own_tables) else "torchaudio")

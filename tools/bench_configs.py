@@ -86,6 +86,88 @@ def raw_frontend_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps):
             "cpu_oracle_clips_per_s": round(k / (time.perf_counter() - t0), 1)}
 
 
+def raw_cnn_backbone_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps):
+    """The raw-PCM CNN head's extra legs: the backbone alone (nww_forward_features_dev on the frontend's resident output) three ways,
+    alternating three times in this session - the default plan, the generic plan (conv_arith = "f32" takes the very launches
+    NWW_CONV2S_X3=0 takes for the backbone: conv2d_strided for every conv) and an outside yardstick that is not code under test, the same
+    folded four-stage chain as torch.nn.functional.conv2d + the activation + the mean in float32 on the same device tensors (MIOpen) -,
+    the MFMA time of the three-product work at peak, the HBM time of the bytes the layers move, and the oracle leg on the tests'
+    restatement."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import e2e_cnn_oracle
+    from nanowakeword_amd.config import RAW_CNN_LAYERS, raw_cnn_planes
+    from nanowakeword_amd.session import HipModel
+    B, N = pcm_h.shape
+    T, C = cfg.input_shape
+    fe_out = torch.empty((B, T, C), dtype=torch.float32, device=pcm.device)
+    m.frontend_dev(pcm.data_ptr(), B, N, fe_out.data_ptr(), True, stream)
+    torch.cuda.synchronize()
+    image = fe_out.transpose(1, 2).unsqueeze(1).contiguous()                      # [B, 1, H, W], as the reference's backbone sees it
+    ws, bs = [], []
+    for i in range(1, 5):
+        w, p = sd[f"model.backbone.conv{i}.0.weight"].astype(np.float64), f"model.backbone.conv{i}.1"
+        al = sd[p + ".weight"].astype(np.float64) / np.sqrt(sd[p + ".running_var"].astype(np.float64) + 1e-5)
+        ws.append(torch.from_numpy((w * al[:, None, None, None]).astype(np.float32)).to(pcm.device))
+        bs.append(torch.from_numpy((sd[p + ".bias"] - sd[p + ".running_mean"] * al).astype(np.float32)).to(pcm.device))
+    act = {"relu": torch.relu, "gelu": torch.nn.functional.gelu, "silu": torch.nn.functional.silu}[cfg.activation]
+    lg_def, lg_gen = torch.empty(B, dtype=torch.float32, device=pcm.device), torch.empty(B, dtype=torch.float32, device=pcm.device)
+    mg = HipModel(cfg, m.fe, device=0, state_dict=sd, conv_arith="f32")
+    mg.reserve(B, N)
+
+    def ours():
+        m.forward_features_dev(fe_out.data_ptr(), B, lg_def.data_ptr(), 0, stream)
+
+    def generic():
+        mg.forward_features_dev(fe_out.data_ptr(), B, lg_gen.data_ptr(), 0, stream)
+
+    def chain():
+        h = image
+        for (w, b), (_, _, sh, sw) in zip(zip(ws, bs), RAW_CNN_LAYERS):
+            h = act(torch.nn.functional.conv2d(h, w, b, stride=(sh, sw), padding=1))
+        return h.mean(dim=(2, 3))
+
+    def timed(fn, k):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / k * 1e3
+    runs = [(round(timed(ours, steps), 4), round(timed(chain, steps), 4), round(timed(generic, max(2, steps // 10)), 4)) for _ in range(3)]
+    ours_ms, chain_ms, generic_ms = (min(r[q] for r in runs) for q in range(3))
+    # the generic plan's per-launch times (conv1's cost as a launch of its own is the same launch in both plans)
+    mg.set_profiling(True)
+    for _ in range(3):
+        generic()
+    torch.cuda.synchronize()
+    gprof = {n: round(ms / max(c, 1), 4) for n, ms, c in mg.get_profile() if c > 0}
+    generic_plan = [l for l in mg.describe_plan().split("\n") if l.startswith(("conv2d_strided:", "conv2s_x3:", "mean:"))]
+    mg.close()
+    planes = raw_cnn_planes(cfg)
+    macs3 = sum(9 * cin * co * h * w for (cin, co, _, _), (h, w) in list(zip(RAW_CNN_LAYERS, planes[1:]))[1:])      # conv2 .. conv4
+    mfma_ms = 3 * 2 * macs3 * B / 2.5e15 * 1e3                  # three products per operand pair at the card's 2.5 PFLOP/s (binary16, dense)
+    moved = planes[0][0] * planes[0][1] + sum(2 * co * h * w for (_, co, _, _), (h, w) in zip(RAW_CNN_LAYERS, planes[1:]))
+    hbm_ms = B * moved * 4 / 8e12 * 1e3                          # every plane written once and read once (conv4's by the mean), float32, at 8 TB/s
+    ref = e2e_cnn_oracle.forward(pcm_h[:8], sd, cfg)[2].ravel()
+    t0 = time.perf_counter(); k = 0
+    while time.perf_counter() - t0 < 3.0:
+        e2e_cnn_oracle.forward(pcm_h[:8], sd, cfg); k += 8
+    return {"backbone_plan": [l for l in m.describe_plan().split("\n") if l.startswith(("conv2d_strided:", "conv2s_x3:", "mean:"))],
+            "backbone_ms_alternating": [r[0] for r in runs], "backbone_ms": ours_ms,
+            "generic_backbone_plan": generic_plan, "generic_backbone_ms_alternating": [r[2] for r in runs], "generic_backbone_ms": generic_ms,
+            "generic_backbone_kernel_ms": gprof,
+            "torch_conv2d_chain_ms_alternating": [r[1] for r in runs], "torch_conv2d_chain_ms": chain_ms,
+            "backbone_over_generic": round(ours_ms / generic_ms, 3), "backbone_over_torch_chain": round(ours_ms / chain_ms, 3),
+            "max_abs_dlogit_default_vs_generic": float((lg_def - lg_gen).abs().max()),
+            "backbone_mmac_per_clip_conv2_4": round(macs3 / 1e6, 2), "backbone_mfma_x3_at_peak_ms": round(mfma_ms, 4),
+            "backbone_hbm_bytes_per_clip": moved * 4, "backbone_hbm_bound_ms": round(hbm_ms, 4),
+            "backbone_over_mfma_x3_at_peak": round(ours_ms / mfma_ms, 1), "backbone_over_hbm_bound": round(ours_ms / hbm_ms, 1),
+            "max_abs_dlogit_vs_oracle": float(np.abs(logits[:8].cpu().numpy() - ref).max()),
+            "cpu_oracle_clips_per_s": round(k / (time.perf_counter() - t0), 1)}
+
+
 RNN_CASES = [((101, 64), "pcm", 2048), ((101, 64), "pcm", 4096), ((16, 96), "features", 2048), ((16, 96), "features", 4096)]
 RNN_WARMUP, RNN_STEPS, RNN_REPEATS = 20, 100, 3
 
@@ -210,6 +292,7 @@ def main():
         ("e_branchformer 64-mel B=2048", HeadConfig("e_branchformer", (101, 64)), FrontendConfig(), 2048, 10),
         ("quartznet 64-mel B=2048", HeadConfig("quartznet", (101, 64)), FrontendConfig(), 2048, 30),
         ("e2e_quartznet 1 s B=2048", HeadConfig("e2e_quartznet", (63, 128)), FrontendConfig(), 2048, 30),
+        ("e2e_cnn 1 s B=2048", HeadConfig("e2e_cnn", (250, 64)), FrontendConfig(), 2048, 20),
         # the reference's other activations (model.py:81-87) at speed: each within 1.15 x of its ReLU row
         ("C2-gelu cnn 64-mel B=4096 activation=gelu", HeadConfig("cnn", (101, 64), activation="gelu"), FrontendConfig(), 4096, 30),
         ("C2-silu cnn 64-mel B=4096 activation=silu", HeadConfig("cnn", (101, 64), activation="silu"), FrontendConfig(), 4096, 30),
@@ -261,6 +344,11 @@ def main():
                         "kernel_ms": {n: round(ms / max(c, 1), 4) for n, ms, c in prof if c > 0}})
             if cfg.model_type == "e2e_quartznet":
                 out.update(raw_frontend_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps))
+                print(json.dumps(out), flush=True)
+                m.close()
+                continue
+            if cfg.model_type == "e2e_cnn":
+                out.update(raw_cnn_backbone_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps))
                 print(json.dumps(out), flush=True)
                 m.close()
                 continue

@@ -1125,6 +1125,100 @@ def make_e2e_quartznet_goldens(out_dir):
     print("onnx fixture e2e_quartznet", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
 
 
+def e2e_cnn_cases():
+    """e2e_cnn cases of heads_e2e_cnn.npz (name, HeadConfig, samples per clip): the reference defaults (channels 32, depth 2) at 1 s and at
+    0.25 s, a 16-channel frontend, depth 3, the GELU stack, and a 65 ms clip (W = 17: odd at conv1, odd again behind it) with SiLU and E = 32."""
+    from nanowakeword_amd.config import HeadConfig, raw_frontend_frames
+
+    def e2e(n, channels=32, depth=None, **kw):
+        probe = HeadConfig("e2e_cnn", (1, channels * 2 ** ((2 if depth is None else depth) - 1)), e2e_frontend_channels=channels, e2e_frontend_depth=depth)
+        return HeadConfig("e2e_cnn", (raw_frontend_frames(probe, n), probe.input_shape[1]), e2e_frontend_channels=channels, e2e_frontend_depth=depth, **kw)
+    return [
+        ("e2e_cnn_16000", e2e(16000), 16000),
+        ("e2e_cnn_4000", e2e(4000), 4000),
+        ("e2e_cnn_4000_c16", e2e(4000, 16), 4000),
+        ("e2e_cnn_4000_d3", e2e(4000, 32, 3), 4000),
+        ("e2e_cnn_4000_gelu", e2e(4000, activation="gelu"), 4000),
+        ("e2e_cnn_1040_silu_e32", e2e(1040, activation="silu", embedding_dim=32), 1040),
+    ]
+
+
+def e2e_cnn_ref_model(Model, cfg, sd, n_samples):
+    """The reference's own Model(model_type="e2e_cnn", mode="e2e") with the synthetic weights loaded; its state_dict keys / shapes must
+    equal param_spec (model.py:109-117, architectures.py:692-710, 739-795)."""
+    from nanowakeword_amd.config import param_spec
+    conf = {"activation_function": cfg.activation, "embedding_dim": cfg.embedding_dim, "e2e_frontend_channels": cfg.e2e_frontend_channels,
+            "e2e_frontend_depth": cfg.e2e_frontend_depth}
+    m = Model(conf, "g", input_shape=(n_samples,), model_type=cfg.model_type, mode="e2e")
+    ref_keys = {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.endswith("num_batches_tracked")}
+    spec = dict(param_spec(cfg))
+    assert ref_keys == spec, (set(ref_keys) ^ set(spec), {k: (ref_keys[k], spec[k]) for k in set(ref_keys) & set(spec) if ref_keys[k] != spec[k]})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.eval()
+
+
+def make_e2e_cnn_goldens(out_dir):
+    """e2e_cnn head (own files: earlier fixtures stay byte-identical): frontend output [B, C, rows], embedding and logits of the reference's
+    Model(mode="e2e") on seeded synthetic weights and PCM / 32768 -> heads_e2e_cnn.npz, and a reference export of a reduced config with
+    its probabilities -> onnx/e2e_cnn.onnx + expected_e2e_cnn.npz."""
+    install_stubs()
+    torch.set_num_threads(1)
+    from nanowakeword.modules.model import Model
+    from nanowakeword._export import onnx as ref_onnx
+    from nanowakeword_amd.config import HeadConfig, raw_frontend_frames
+    from nanowakeword_amd.synth import synth_state_dict, state_dict_checksum
+    heads, meta = {}, {}
+    for name, cfg, n in e2e_cnn_cases():
+        sd = synth_state_dict(cfg)
+        m = e2e_cnn_ref_model(Model, cfg, sd, n)
+        pcm = e2e_quartznet_pcm(n)
+        x = torch.from_numpy(pcm.astype(np.float32) / np.float32(32768.0))
+        with torch.no_grad():
+            fe = m.model.frontend(x.unsqueeze(1)).numpy()
+            out = {"pcm": pcm, "frontend": fe, "emb": m.model(x).numpy(), "logits": m(x).numpy()}
+        assert fe.shape[1:] == (cfg.input_shape[1], cfg.input_shape[0]), (fe.shape, cfg.input_shape)
+        lens = [1, 16, 17, 8193, 16000, 16384, 16385, 32769]
+        with torch.no_grad():
+            out["law_samples"] = np.array(lens)
+            out["law_rows"] = np.array([m.model.frontend(torch.zeros(1, 1, L)).shape[2] for L in lens])
+        out["sd_checksum"] = np.array(state_dict_checksum(sd))
+        out["ref_spec_json"] = np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))
+        meta[name] = cfg.to_dict()
+        for k, v in out.items():
+            heads[f"{name}/{k}"] = v
+        print("e2e_cnn", name, {k: getattr(v, "shape", v) for k, v in out.items()}, "logits", out["logits"].ravel(), "|fe|max", np.abs(fe).max())
+    heads["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(out_dir, "heads_e2e_cnn.npz"), **heads)
+
+    # the reference's own export of a small model (recipe of make_onnx_fixtures): every BatchNorm is folded into the conv in front of it
+    onnx_dir = os.path.join(out_dir, "onnx")
+    from torch.onnx._internal.torchscript_exporter import onnx_proto_utils
+    onnx_proto_utils._add_onnxscript_fn = lambda model_bytes, custom_opsets: model_bytes
+    orig_export = torch.onnx.export
+
+    def export_torchscript(*a, **k):
+        k.setdefault("dynamo", False)
+        return orig_export(*a, **k)
+    torch.onnx.export = export_torchscript
+    n = 2000
+    probe = HeadConfig("e2e_cnn", (1, 16), e2e_frontend_channels=8, e2e_frontend_depth=2)
+    cfg = HeadConfig("e2e_cnn", (raw_frontend_frames(probe, n), 16), embedding_dim=16, e2e_frontend_channels=8, e2e_frontend_depth=2)
+    sd = synth_state_dict(cfg)
+    m = e2e_cnn_ref_model(Model, cfg, sd, n)
+    pcm = np.concatenate([e2e_quartznet_pcm(n), e2e_quartznet_pcm(n)[:, ::-1]], 0)
+    with torch.no_grad():
+        logits = m(torch.from_numpy(pcm.astype(np.float32) / np.float32(32768.0))).numpy()
+    ref_onnx.export_onnx_model(m, (n,), {}, "e2e_cnn", onnx_dir)
+    path = os.path.join(onnx_dir, "e2e_cnn.onnx")
+    assert os.path.exists(path), "export of the e2e_cnn failed"
+    arrays = {"e2e_cnn/pcm": np.ascontiguousarray(pcm), "e2e_cnn/logits": logits.reshape(-1).astype(np.float32),
+              "e2e_cnn/probs": (1.0 / (1.0 + np.exp(-logits.astype(np.float64)))).reshape(-1).astype(np.float32),
+              "meta_json": np.array(json.dumps({"e2e_cnn": cfg.to_dict()}))}
+    np.savez_compressed(os.path.join(onnx_dir, "expected_e2e_cnn.npz"), **arrays)
+    torch.onnx.export = orig_export
+    print("onnx fixture e2e_cnn", os.path.getsize(path), "bytes; logits", logits.reshape(-1))
+
+
 def make_wire_fixtures(path):
     """Messages produced by the reference's own encoders (remote_verifier.py:147-158) for tests/test_wire.py."""
     from nanowakeword.interpreter import remote_verifier as rv
@@ -1284,6 +1378,8 @@ if __name__ == "__main__":
         make_quartznet_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--e2e-quartznet-only":
         make_e2e_quartznet_goldens(os.path.join(REPO, "tests", "golden"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--e2e-cnn-only":
+        make_e2e_cnn_goldens(os.path.join(REPO, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "--r02-only":
         make_round2_goldens(os.path.join(REPO, "tests", "golden"))
     else:
