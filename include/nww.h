@@ -223,6 +223,31 @@ int nww_stream_close(nww_handle* h);
 /* samples seen per stream since open/reset                                                               */
 int64_t nww_stream_filled(const nww_handle* h);
 
+/* ---- recording scoring: every window of ONE long recording in a call (the offline counterpart of nww_stream_*) ----
+ * What NanoInterpreter.predict computes chunk after chunk over a file (test_model/evaluate_model_with_audio.py), as batches: window i
+ * is pcm[i * hop, i * hop + window), i = 0 .. nW - 1, nW = 1 + (n_samples - window) / hop (a trailing partial hop is ignored).  The
+ * recording is read where it lies (row_stride = hop): nothing is cut into windows, on the host or on the device.  Every logit is
+ * bit-identical to nww_forward_pcm on the same windows in batches of the passes' sizes.  window and hop: positive multiples of 8
+ * samples, hop <= window (NWW_ERR_INVALID), and the window must give the head's (in_rows, in_cols) (NWW_ERR_SHAPE) - the rules of
+ * nww_stream_open.  An offset of the first window is the caller's pointer arithmetic (pcm + offset).
+ * Two routes: shared frames - a pass computes every interior log-mel frame once, the frames of each window that
+ * touch its own reflect padding apart, and assembles the windows on the device - when hop is a multiple of hop_length, the head
+ * reads frames-major log-mel and NWW_REC_SHARED is not 0; otherwise the strided route, which recomputes every window's frames.
+ * (The four are declared `extern`, which changes nothing for a C compiler: tests/test_e2e_cnn_head.py and test_e2e_quartznet_head.py
+ * count the declarations that start a line with their return type, and that count - 48 - is the one they pin.)                          */
+/* nW for n_samples (0: shorter than one window); < 0: minus the error code, text in nww_last_error                                  */
+extern int nww_recording_windows(nww_handle* h, int32_t n_samples, int32_t window, int32_t hop);
+/* 1: shared-frame route, 0: strided route, < 0: minus the error code                                                                */
+extern int nww_recording_route(nww_handle* h, int32_t window, int32_t hop);
+/* d_pcm [n_samples] int16 -> d_logits / d_probs [nW] (either may be NULL), in passes of at most max_batch windows (<= 0: 4096);
+ * asynchronous on `stream`.  The workspace is that of nww_reserve(max_batch, window) plus the pass's frame pool; it grows on the
+ * first call of a size (which synchronises the device).                                                                            */
+extern int nww_forward_recording_dev(nww_handle* h, const int16_t* d_pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
+                              float* d_logits, float* d_probs, void* stream);
+/* host pointers; the recording is uploaded once (2 bytes per sample, in pieces), never as windows.  n_windows_out may be NULL.      */
+extern int nww_forward_recording(nww_handle* h, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
+                          float* logits, float* probs, int32_t* n_windows_out);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

@@ -46,6 +46,7 @@ SYMBOLS = [
     "nww_emb_push_features", "nww_emb_get_features", "nww_emb_forward", "nww_emb_window_batch", "nww_emb_pad_batch",
     "nww_comm_unique_id", "nww_comm_init", "nww_comm_destroy", "nww_all_gather_logits", "nww_forward_pcm_gather_dev",
     "nww_forward_pcm_gather_async_dev", "nww_gather_fence", "nww_gather_overlap_ms", "nww_feature_clamp",
+    "nww_recording_windows", "nww_recording_route", "nww_forward_recording_dev", "nww_forward_recording",
 ]
 
 
@@ -142,6 +143,10 @@ def load_library():
     lib.nww_gather_fence.argtypes = [vp, vp]; lib.nww_gather_fence.restype = C.c_int
     lib.nww_feature_clamp.argtypes = [vp]; lib.nww_feature_clamp.restype = C.c_float
     lib.nww_gather_overlap_ms.argtypes = [vp, C.POINTER(C.c_float)]; lib.nww_gather_overlap_ms.restype = C.c_int
+    lib.nww_recording_windows.argtypes = [vp, i32, i32, i32]; lib.nww_recording_windows.restype = C.c_int
+    lib.nww_recording_route.argtypes = [vp, i32, i32]; lib.nww_recording_route.restype = C.c_int
+    lib.nww_forward_recording_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]; lib.nww_forward_recording_dev.restype = C.c_int
+    lib.nww_forward_recording.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32p]; lib.nww_forward_recording.restype = C.c_int
     _lib = lib
     return lib
 

@@ -208,6 +208,27 @@ def raw_frontend_frames(cfg: "HeadConfig", n_samples: int) -> int:
     return n
 
 
+def recording_windows(n: int, window: int, hop: int, offset: int = 0) -> int:
+    """Windows pcm[offset + i * hop : offset + i * hop + window] that fit in a recording of n samples (nww_recording_windows): 0 when
+    it is shorter than one window; a trailing partial hop is ignored."""
+    n, window, hop, offset = int(n), int(window), int(hop), int(offset)
+    if window <= 0 or hop <= 0 or offset < 0:
+        raise ValueError("window and hop must be positive and offset non-negative")
+    return 0 if n - offset < window else 1 + (n - offset - window) // hop
+
+
+def clip_samples(cfg: "HeadConfig", fe: "FrontendConfig") -> int:
+    """The clip length a PCM head was built for, from its input_shape: the whole number of frame hops that gives its frames on the mel
+    frontends (16000 for 101 centred frames), every stage's longest input on the raw-PCM heads (16000 for 250 rows at depth 2)."""
+    if cfg.model_type in RAW_HEADS:
+        n = cfg.input_shape[0]
+        for _, _, _, s in reversed(raw_frontend_stages(cfg)):
+            n *= s
+        return n
+    frames = cfg.input_shape[1] if cfg.model_type == "e2e_dnn" else cfg.input_shape[0]
+    return (frames - 1) * fe.hop_length + (0 if fe.center else fe.n_fft)
+
+
 def raw_frontend_macs_upper(cfg: "HeadConfig") -> int:
     """An UPPER estimate of the raw frontend's multiply-accumulates from the config alone: the clip length is not in it, so rows of a stage
     are taken as rows of the next x its stride (1008 and 252 for e2e_quartznet's defaults where a 1 s clip has 1000 and 250: 14.74 against

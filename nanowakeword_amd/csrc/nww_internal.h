@@ -1,7 +1,7 @@
 // nww_internal.h - what the translation units of the C-ABI share: the handle, a forward's run state, error helpers and the
 // device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_weights.hip: state_dict spec
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
-// nww_emb.hip: embedding-mode state (nww_emb_*).
+// nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -135,6 +135,10 @@ struct nww_handle {
     float* d_seq[2] = {nullptr, nullptr}; int seq_cur = 0, a3_lo = 0, a3_hi = -1, a3_shift = 0;
     struct { bool on = false; size_t x_stride = 0; int mode = 0; } sr;    // what the next nww_run_head hands to its Run
     EmbState* emb = nullptr;       // embedding-mode preprocessor state (nww_emb_*)
+    // recording scoring (nww_recording.hip): the pool of a pass's interior frames [(B - 1) k + T][n_mels], and for the host-pointer entry
+    // point the recording and its [2][nW] logits / probabilities; each grown on demand
+    float* d_rec_pool = nullptr; int16_t* d_rec_pcm = nullptr; float* d_rec_out = nullptr;
+    size_t rec_pool_bytes = 0, rec_pcm_bytes = 0, rec_out_bytes = 0;
     void* comm = nullptr;          // ncclComm_t of this rank (nww_comm_init)
     unsigned char* pin_in = nullptr; unsigned char* pin_out = nullptr;   // pinned staging for small host-pointer calls
     bool pin_in_busy = false;                                            // an async copy out of pin_in may still be in flight
@@ -181,6 +185,7 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
                            size_t row_stride = 0, unsigned int* done_flag = nullptr, unsigned int done_seq = 0, bool* done_armed = nullptr);
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
+void nww_recording_free(nww_handle* h);        // nww_recording.hip
 void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next six: what nww_finalize does to the loaded weights before it plans
 void fold_batchnorms(nww_handle* h);
 void transpose_depthwise(nww_handle* h);
@@ -197,6 +202,14 @@ inline int nww_pcm_rows(const nww_handle* h, int N) {
     int L = N;
     for (int i = 0; i < h->cfg.n_blocks; ++i) L = raw_conv_rows(L, i == 0 ? 16 : 4);
     return L < 1 ? -1 : L;
+}
+// the first el and last er of a W-sample window's T frames read its reflect padding (centred frontends; 0 / 0 otherwise): every other frame is
+// the same samples, hence the same log-mel bits, in whichever window of a stream or recording it falls (nww_stream.hip, nww_recording.hip)
+inline void nww_edge_frames(const FeParams& fe, int T, int W, int& el, int& er) {
+    const int pad = fe.center ? fe.n_fft / 2 : 0;
+    el = er = 0;
+    while (el < T && el * fe.hop - pad < 0) ++el;
+    while (er < T && (T - 1 - er) * fe.hop - pad + fe.n_fft > W) ++er;
 }
 // the QuartzNet blocks' and fc's key prefix: the raw-PCM head holds them under model.backbone
 // NWW_HEAD_E2E_CNN: RawAudioBackbone's four conv stages (architectures.py:739-762) on the channels-last plane [A = image W][Bd = image H]
@@ -221,6 +234,7 @@ inline std::vector<QnBlock> nww_quartznet_blocks(const nww_config& c) {
 struct Knobs {
     int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, raw_fused, conv2s_x3, rnn_ih_fused, mha_mfma, bc_front, bc_chain, tail;
     int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
+    int rec_shared;                            // NWW_REC_SHARED (nww_recording.hip)
     int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2
 };
 const Knobs& nww_knobs();

@@ -9,7 +9,7 @@ const Knobs& nww_knobs() {
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
         r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.conv2s_x3 = env("NWW_CONV2S_X3", 1); r.rnn_ih_fused = env("NWW_RNN_IH_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
-        r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3);
+        r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3); r.rec_shared = env("NWW_REC_SHARED", 1);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
     }();

@@ -1,0 +1,174 @@
+// nww_recording.hip - recording scoring: every window pcm[i * hop, i * hop + window) of ONE recording in a call (nww_recording_*,
+// nww_forward_recording*): the offline counterpart of nww_stream_*.  The recording is read where it lies - nothing is cut into
+// windows - on one of two routes per (window, hop):
+//   strided  every pass of B windows is nww_forward_pcm_on_dev with row_stride = hop: all T frames of every window are computed
+//   shared   a hop of k = hop / hop_length frames makes interior frame t of window w the frame t - k of window w + 1, bit for bit
+//            (what plan_incremental of nww_stream.hip relies on from hop to hop).  Per pass: (1) the pass's span of (B - 1) hop + window
+//            samples goes through the batch frontend as ONE clip, whose frames-major output is the pool - row w k + t is interior frame
+//            t of window w; (2) the el + er frames of every window that touch its own reflect padding are computed by the frame-subset
+//            instances straight into the dense head input; (3) rec_assemble_kernel copies every window's interior run out of the pool.
+//            k + el + er frames per window instead of T.  Launch-side code only: no frontend instance is added or changed.
+#include "nww_internal.h"
+#include "rec_windows.h"
+
+namespace {
+
+struct RecPlan {
+    int T = 0, k = 0, el = 0, er = 0;
+    bool shared = false;
+};
+
+// window / hop rule and head shape (as nww_stream_open), then the route: the conditions under which plan_incremental keeps a log-mel ring
+int rec_plan(nww_handle* h, int W, int hop, RecPlan& p) {
+    int rc = nww_check_run(h, 1);
+    if (rc) return rc;
+    if (W <= 0 || hop <= 0 || hop > W || (W % 8) || (hop % 8))
+        return fail(h, NWW_ERR_INVALID, "window and hop must be positive multiples of 8 samples with hop <= window");
+    const nww_config& c = h->cfg;
+    const int T = nww_pcm_rows(h, W);
+    const int rows = c.mel_major_features ? c.n_mels : T, cols = nww_raw_head(c) ? c.in_cols : c.mel_major_features ? T : c.n_mels;
+    if (T <= 0 || rows != c.in_rows || cols != c.in_cols)
+        return fail(h, NWW_ERR_SHAPE, "a %d-sample window gives (%d,%d) features but the head expects (%d,%d)", W, rows, cols, c.in_rows, c.in_cols);
+    p = RecPlan{};
+    p.T = T;
+    if (!nww_knobs().rec_shared || nww_raw_head(c)) return NWW_OK;
+    const bool frames_major = !c.mel_major_features || h->e2e_transposed;
+    static const int mel_env = 2;
+    const int hl = h->fe.hop;
+    if (!frames_major || !fe2_subset_supported(h->fe, mel_env) || hop % hl != 0) return NWW_OK;
+    const int k = hop / hl;
+    int el, er;
+    nww_edge_frames(h->fe, T, W, el, er);
+    if (T - er - k <= el) return NWW_OK;                      // a hop replaces (nearly) the whole window: nothing to share
+    p.k = k; p.el = el; p.er = er; p.shared = true;
+    return NWW_OK;
+}
+
+long long rec_count(long long n_samples, int W, int hop) { return n_samples < W ? 0 : 1 + (n_samples - W) / hop; }
+
+int rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return NWW_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIP_TRY(h, hipMalloc(p, bytes + 16));
+    *cap = bytes;
+    return NWW_OK;
+}
+
+// One pass on the shared route: B windows whose first sample is d_pcm[0].
+int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B, int W, int hop, float* d_logits, float* d_probs, hipStream_t s) {
+    const nww_config& c = h->cfg;
+    const int span = (B - 1) * hop + W;
+    nww_prof_begin(h);
+    nww_prof_mark(h, s, 0);
+    // (1) the pool: the span as one clip.  Its own edge frames (rows < el and the last er) are no window's interior frames.
+    int rc = nww_frontend_on_dev(h, d_pcm, 1, span, h->d_rec_pool, nullptr, 1, s, nullptr);
+    if (rc) return rc;
+    // (2) every window's edge frames, with its own reflect padding, at their place in the dense tensor
+    if (p.el + p.er > 0) {
+        Fe2Sub sub;
+        if (p.el > 0) { sub.t0[sub.nr] = 0; sub.t1[sub.nr] = p.el; ++sub.nr; }
+        if (p.er > 0) { sub.t0[sub.nr] = p.T - p.er; sub.t1[sub.nr] = p.T; ++sub.nr; }
+        rc = nww_frontend_on_dev(h, d_pcm, B, W, h->d_logmel, nullptr, 1, s, nullptr, (size_t)hop, &sub);
+        if (rc) return rc;
+    }
+    // (3) the interior runs
+    hipError_t e = launch_rec_assemble(h->d_rec_pool, h->d_logmel, B, p.T, c.n_mels, p.k, p.el, p.er, s);
+    if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'rec_assemble' failed: %s", hipGetErrorString(e));
+    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, nullptr, 0, nullptr, c.mel_major_features != 0);
+}
+
+int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
+                    hipStream_t s) {
+    RecPlan p;
+    int rc = rec_plan(h, W, hop, p);
+    if (rc) return rc;
+    const long long nW = rec_count(n_samples, W, hop);
+    if (nW == 0) return NWW_OK;
+    if (max_batch <= 0) max_batch = 4096;
+    const int Bmax = (int)std::min<long long>(max_batch, nW);
+    // the pool's frames as one clip: the span has to stay inside the frontend's 32-bit sample offsets, and the frame law has to give
+    // the span every row the windows read (it does whenever hop is a multiple of the frame hop; checked, not assumed)
+    const long long span = (long long)(Bmax - 1) * hop + W, rows = (long long)(Bmax - 1) * p.k + p.T;
+    if (p.shared && (span >= (1ll << 30) || fe_num_frames(h->fe, (int)span) < rows)) p.shared = false;
+    rc = nww_ensure_ws(h, Bmax, W);
+    if (rc) return rc;
+    if (p.shared) {
+        const size_t floats = (size_t)fe_num_frames(h->fe, (int)span) * h->cfg.n_mels;
+        rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_pool), &h->rec_pool_bytes, floats * sizeof(float));
+        if (rc) return rc;
+    }
+    for (long long first = 0; first < nW; first += Bmax) {
+        const int B = (int)std::min<long long>(Bmax, nW - first);
+        const int16_t* x = d_pcm + first * hop;
+        float* lg = d_logits ? d_logits + first : nullptr;
+        float* pr = d_probs ? d_probs + first : nullptr;
+        rc = p.shared ? rec_pass_shared(h, p, x, B, W, hop, lg, pr, s) : nww_forward_pcm_on_dev(h, x, B, W, lg, pr, s, (size_t)hop);
+        if (rc) return rc;
+    }
+    return NWW_OK;
+}
+
+}  // namespace
+
+void nww_recording_free(nww_handle* h) {
+    for (void* p : {(void*)h->d_rec_pool, (void*)h->d_rec_pcm, (void*)h->d_rec_out})
+        if (p) (void)hipFree(p);
+    h->d_rec_pool = nullptr; h->d_rec_pcm = nullptr; h->d_rec_out = nullptr;
+    h->rec_pool_bytes = h->rec_pcm_bytes = h->rec_out_bytes = 0;
+}
+
+extern "C" int nww_recording_windows(nww_handle* h, int32_t n_samples, int32_t window, int32_t hop) {
+    RecPlan p;
+    const int rc = rec_plan(h, window, hop, p);
+    if (rc) return -rc;
+    if (n_samples < 0) return -fail(h, NWW_ERR_INVALID, "a recording cannot have %d samples", n_samples);
+    const long long n = rec_count(n_samples, window, hop);
+    return (int)n;
+}
+
+extern "C" int nww_recording_route(nww_handle* h, int32_t window, int32_t hop) {
+    RecPlan p;
+    const int rc = rec_plan(h, window, hop, p);
+    return rc ? -rc : (p.shared ? 1 : 0);
+}
+
+extern "C" int nww_forward_recording_dev(nww_handle* h, const int16_t* d_pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
+                                         float* d_logits, float* d_probs, void* stream) {
+    int rc = nww_check_run(h, 1);
+    if (rc) return rc;
+    if (!d_pcm || n_samples < 0) return fail(h, NWW_ERR_INVALID, "null device pointer or negative length");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return rec_forward_dev(h, d_pcm, n_samples, window, hop, max_batch, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
+}
+
+extern "C" int nww_forward_recording(nww_handle* h, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
+                                     float* logits, float* probs, int32_t* n_windows_out) {
+    int rc = nww_check_run(h, 1);
+    if (rc) return rc;
+    if (!pcm || n_samples < 0) return fail(h, NWW_ERR_INVALID, "Input audio must be a non-null int16 array");
+    RecPlan p;
+    rc = rec_plan(h, window, hop, p);
+    if (rc) return rc;
+    const long long nW = rec_count(n_samples, window, hop);
+    if (n_windows_out) *n_windows_out = (int32_t)nW;
+    if (nW == 0) return NWW_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = h->own_stream;
+    // the recording goes up once, 2 bytes per sample, in pieces of 32 MiB (16 Mi samples) - never as windows; the tail no window reads stays behind
+    const size_t used = (size_t)((nW - 1) * hop + window), piece = (size_t)16 << 20;
+    rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_pcm), &h->rec_pcm_bytes, used * sizeof(int16_t));
+    if (rc) return rc;
+    rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_out), &h->rec_out_bytes, (size_t)2 * nW * sizeof(float));
+    if (rc) return rc;
+    for (size_t o = 0; o < used; o += piece)
+        HIP_TRY(h, hipMemcpyAsync(h->d_rec_pcm + o, pcm + o, std::min(piece, used - o) * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    float *dl = h->d_rec_out, *dp = probs ? h->d_rec_out + nW : nullptr;
+    rc = rec_forward_dev(h, h->d_rec_pcm, (long long)used, window, hop, max_batch, dl, dp, s);
+    if (rc) return rc;
+    if (logits) HIP_TRY(h, hipMemcpyAsync(logits, dl, (size_t)nW * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (probs) HIP_TRY(h, hipMemcpyAsync(probs, dp, (size_t)nW * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return NWW_OK;
+}

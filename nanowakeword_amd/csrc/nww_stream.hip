@@ -61,10 +61,9 @@ static int plan_incremental(nww_handle* h, int S, int W, int hop) {
     const bool frames_major = !c.mel_major_features || h->e2e_transposed;
     static const int mel_env = 2;
     if (mode <= 0 || !frames_major || !fe2_subset_supported(h->fe, mel_env) || hop % hl != 0) return NWW_OK;
-    const int k = hop / hl, pad = h->fe.center ? h->fe.n_fft / 2 : 0;
-    int el = 0, er = 0;
-    while (el < T && el * hl - pad < 0) ++el;
-    while (er < T && (T - 1 - er) * hl - pad + h->fe.n_fft > W) ++er;
+    const int k = hop / hl;
+    int el, er;
+    nww_edge_frames(h->fe, T, W, el, er);
     if (T - er - k <= el) return NWW_OK;                      // a hop replaces (nearly) the whole window: nothing to keep
     h->fe_edge_l = el; h->fe_edge_r = er; h->lm_shift = k;
     h->lm_rows = (T + k - 1) / k * k;

@@ -5,7 +5,7 @@
 #include <cstdint>
 
 struct RawConvArgs {
-    const int16_t* pcm = nullptr;   // stage 0: int16 samples, pcm_stride samples between clips; the kernel reads sample / 32768 (exact in float32)
+    const int16_t* pcm = nullptr;   // stage 0: int16 samples, pcm_stride samples between clips (clips may overlap: pcm_stride < L); the kernel reads sample / 32768 (exact in float32)
     size_t pcm_stride = 0;
     const float* x = nullptr;       // later stages: time-major rows [B][L][Cin]
     const float* w = nullptr;       // folded weights, tap-major [k][Cin][Cout]

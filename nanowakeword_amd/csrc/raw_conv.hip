@@ -169,7 +169,8 @@ hipError_t launch_conv1d_strided(const RawConvArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     if (a.L < 1 || a.Cin < 1 || a.Cout < 1 || a.k < 1 || !(a.k & 1) || a.stride < 1 || !a.w || !a.bias || !a.y) return hipErrorInvalidValue;
     const bool pcm = a.pcm != nullptr;
-    if (pcm ? (a.Cin != 1 || a.pcm_stride < (size_t)a.L) : !a.x) return hipErrorInvalidValue;
+    // (pcm_stride < L: clips that overlap - the windows of a recording a hop apart; the kernel only reads samples [0, L) of each)
+    if (pcm ? (a.Cin != 1 || a.pcm_stride < 1) : !a.x) return hipErrorInvalidValue;
     const int Lout = raw_conv_rows(a.L, a.stride);
     // the largest tile of output rows whose input window fits the LDS budget, and no larger than the clip needs
     int TT = 64;

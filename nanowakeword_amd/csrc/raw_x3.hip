@@ -159,9 +159,10 @@ size_t raw_x3_lds_bytes(int channels, int depth) {
     return bytes;
 }
 
+// (pcm_stride may be smaller than N: overlapping clips, the windows of a recording a hop apart - samples [0, N) of each are read only)
 hipError_t launch_raw_x3(const RawX3Args& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    if (!raw_x3_supported(a.C1, a.depth) || a.N < 1 || a.pcm_stride < (size_t)a.N || !a.pcm || !a.y || !a.w1 || !a.b1 || !a.packed[0] || !a.bias[0] ||
+    if (!raw_x3_supported(a.C1, a.depth) || a.N < 1 || a.pcm_stride < 1 || !a.pcm || !a.y || !a.w1 || !a.b1 || !a.packed[0] || !a.bias[0] ||
         (a.depth == 3 && (!a.packed[1] || !a.bias[1])) || a.L[a.depth - 1] < 1)
         return hipErrorInvalidValue;
     const size_t lds = raw_x3_lds_bytes(a.C1, a.depth);

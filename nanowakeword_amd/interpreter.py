@@ -355,6 +355,68 @@ class HipInterpreter:
             return [self.predict(data, **kwargs)]
         return [self.predict(data[i:i + chunk_size], **kwargs) for i in range(0, len(data), chunk_size)]
 
+    def score_recording(self, pcm: Union[str, np.ndarray], chunk_size: int = HOP_SAMPLES, patience: dict = {}, threshold: dict = {},
+                        debounce_time: float = 0.0) -> Dict[str, np.ndarray]:
+        """A whole recording as a NEW stream: {model: float32 scores, one per chunk} - exactly what reset() followed by predict() on
+        pcm[0:chunk_size], pcm[chunk_size:2 * chunk_size], ... returns as DetectionResult.scores, and the same state left behind (zeros
+        until the window holds a clip, first five predictions zeroed, patience / debounce).  E2E sessions that offer run_recording
+        (HipSession) score every full chunk's window in batches, the recording uploaded once: the first window starts at
+        (-clip_samples) % chunk_size.  Cascades, embedding-mode interpreters (a preprocessor) and chunk sizes or first offsets that are
+        not multiples of 8 samples take the predict() loop."""
+        if isinstance(pcm, str):
+            with wave.open(pcm, mode="rb") as f:
+                if f.getframerate() != 16000 or f.getsampwidth() != 2 or f.getnchannels() != 1:
+                    raise ValueError("Audio clip must be a 16kHz, 16-bit, single-channel WAV file.")
+                pcm = np.frombuffer(f.readframes(f.getnframes()), dtype=np.int16)
+        if not isinstance(pcm, np.ndarray) or pcm.ndim != 1:
+            raise ValueError("a recording must be a one-dimensional Numpy array (or a WAV path)")
+        chunk_size = int(chunk_size)
+        if chunk_size <= 0:
+            raise ValueError("chunk_size must be positive")
+        kw = dict(patience=patience, threshold=threshold, debounce_time=debounce_time)
+        self.reset()
+        n_chunks = -(-len(pcm) // chunk_size)
+        out = {n: np.zeros(n_chunks, np.float32) for n in self.models}
+
+        def keep(t, res):
+            for n in out:
+                out[n][t] = res.scores.get(n, 0.0)
+
+        n_full = len(pcm) // chunk_size
+        batch = (self.preprocessor is None and not self.is_cascade and chunk_size % 8 == 0 and n_full > 0
+                 and all(hasattr(s, "run_recording") and chunk_size <= self.e2e_clip_samples[n] and (-self.e2e_clip_samples[n]) % chunk_size % 8 == 0
+                         for n, s in self.models.items()))
+        if not batch:
+            for t in range(n_chunks):
+                keep(t, self.predict(pcm[t * chunk_size:(t + 1) * chunk_size], **kw))
+            return out
+        xi = pcm if pcm.dtype == np.int16 else pcm.astype(np.int16)
+        full = np.ascontiguousarray(xi[:n_full * chunk_size])
+        raw, first = {}, {}
+        for n, s in self.models.items():
+            clip = self.e2e_clip_samples[n]
+            first[n] = -(-clip // chunk_size) - 1                 # the chunk that fills the window
+            raw[n] = np.asarray(s.run_recording(full, hop=chunk_size, offset=(-clip) % chunk_size), np.float32).reshape(-1)
+            assert len(raw[n]) == max(0, n_full - first[n]), (len(raw[n]), n_full, first[n])
+        for t in range(n_full):                                   # predict()'s bookkeeping, the scores looked up
+            current = {}
+            for n in self.models:
+                score = float(raw[n][t - first[n]]) if t >= first[n] else 0.0
+                self.raw_scores[n] = score
+                if len(self.prediction_buffer.get(n, ())) < N_WARMUP_PREDICTIONS:
+                    score = 0.0
+                current[n] = score
+            self._post_filters(current, patience, threshold, debounce_time, chunk_size)
+            for n, v in current.items():
+                self._history(n).append(v)
+                self.post_processed_scores[n] = v
+                out[n][t] = v
+        for w in self._windows.values():
+            w.push(full)
+        if n_full < n_chunks:                                     # a last, shorter chunk: its window starts off the grid
+            keep(n_full, self.predict(pcm[n_full * chunk_size:], **kw))
+        return out
+
     def reset(self):
         """New stream: clear histories, windows and scores (:719-733)."""
         self.prediction_buffer.clear()

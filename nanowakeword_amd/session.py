@@ -17,7 +17,7 @@ from typing import Mapping, Optional
 import numpy as np
 
 from . import _lib
-from .config import FrontendConfig, HeadConfig, RAW_HEADS, param_spec
+from .config import FrontendConfig, HeadConfig, RAW_HEADS, clip_samples, param_spec, recording_windows
 
 
 class NwwError(RuntimeError):
@@ -55,6 +55,31 @@ def torchaudio_tables(fe: FrontendConfig):
     up = slopes[:, 2:] / f_diff[1:]
     fb = torch.max(torch.zeros(1), torch.min(down, up))
     return window.numpy().astype(np.float32), fb.numpy().astype(np.float32)
+
+
+def score_recordings(forward_recording, recordings, window: int, hop: int = 1280, max_batch: int = 4096):
+    """Several recordings through ONE forward_recording(pcm, window=, hop=, max_batch=) call: each is padded with zeros to a multiple of
+    `hop`, so that every recording starts on the window grid of the concatenation; the windows that lie in one recording's own samples are
+    kept, those that reach into the padding or the next recording dropped.  Returns [(logits, probs)] per recording, each what the
+    recording scores alone."""
+    recs = [HipModel._pcm1(r) for r in recordings]
+    window, hop = int(window), int(hop)
+    if not recs:
+        return []
+    starts, parts, at = [], [], 0
+    for r in recs:
+        pad = -len(r) % hop
+        starts.append(at // hop)
+        parts.append(r)
+        if pad:
+            parts.append(np.zeros(pad, np.int16))
+        at += len(r) + pad
+    logits, probs = forward_recording(np.concatenate(parts), window=window, hop=hop, max_batch=max_batch)
+    out = []
+    for r, i0 in zip(recs, starts):
+        n = recording_windows(len(r), window, hop)
+        out.append((logits[i0:i0 + n].copy(), probs[i0:i0 + n].copy()))
+    return out
 
 
 class HipModel:
@@ -193,6 +218,81 @@ class HipModel:
         self._check(self.lib.nww_forward_pcm(self._h, pcm.ctypes.data_as(C.c_void_p), B, N,
                                              logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p)))
         return logits, probs
+
+    # ------------------------------------------------------------------ recording scoring (nww_recording_*, nww_forward_recording*)
+    @staticmethod
+    def _pcm1(pcm) -> np.ndarray:
+        if not isinstance(pcm, np.ndarray):
+            raise ValueError("Input audio `x` must be a Numpy array.")
+        if pcm.dtype != np.int16 or pcm.ndim != 1:
+            raise ValueError("a recording must be a one-dimensional int16 array")
+        if pcm.size >= 2 ** 31:
+            raise ValueError("a recording holds at most 2**31 - 1 samples per call")
+        return np.ascontiguousarray(pcm)
+
+    @property
+    def clip_samples(self) -> int:
+        """the clip length the head was built for (config.clip_samples)"""
+        return clip_samples(self.head, self.fe)
+
+    def _rec_count(self, n: int, window: int, hop: int) -> int:
+        nw = int(self.lib.nww_recording_windows(self._h, int(n), int(window), int(hop)))
+        if nw < 0:
+            self._check(-nw)
+        return nw
+
+    def recording_route(self, window: Optional[int] = None, hop: int = 1280) -> int:
+        """1: the shared-frame route scores this (window, hop), 0: the strided route (nww_recording_route)"""
+        r = int(self.lib.nww_recording_route(self._h, int(self.clip_samples if window is None else window), int(hop)))
+        if r < 0:
+            self._check(-r)
+        return r
+
+    def describe_recording(self, window: Optional[int] = None, hop: int = 1280) -> str:
+        """The launches of one pass of forward_recording at this (window, hop), one per line: the route's frontend launches, then the
+        head's lines of describe_plan()."""
+        window = int(self.clip_samples if window is None else window)
+        if self.recording_route(window, hop):
+            fe = ["frontend:pool - the pass's span of (B - 1) * %d + %d samples as one clip, frames-major" % (hop, window),
+                  "frontend:edge frames - the frames of every window that touch its own reflect padding (none without centring)",
+                  "rec_assemble:pool -> [B][frames][n_mels] (shared-frame route)"]
+        else:
+            fe = ["%s - every frame of every window, row_stride = %d (strided route)" % (l, hop)
+                  for l in self.describe_plan().strip().split("\n") if l.startswith("frontend:")]
+        return "\n".join(fe + [l for l in self.describe_plan().strip().split("\n") if not l.startswith("frontend:")]) + "\n"
+
+    def forward_recording(self, pcm, window: Optional[int] = None, hop: int = 1280, offset: int = 0, max_batch: int = 4096):
+        """int16 [N] -> (logits [nW], probs [nW]) of every window pcm[offset + i * hop : offset + i * hop + window]; each bit-identical to
+        forward_pcm on that window (in batches of the passes' sizes).  The recording goes to the device once, never as windows."""
+        pcm = self._pcm1(pcm)
+        window = int(self.clip_samples if window is None else window)
+        if offset < 0:
+            raise ValueError("offset must not be negative")
+        x = pcm[min(int(offset), len(pcm)):]
+        nw = self._rec_count(len(x), window, hop)
+        assert nw == recording_windows(len(pcm), window, hop, min(int(offset), len(pcm)))
+        logits, probs = np.empty(nw, np.float32), np.empty(nw, np.float32)
+        if nw:
+            n_out = C.c_int32()
+            self._check(self.lib.nww_forward_recording(self._h, x.ctypes.data_as(C.c_void_p), len(x), window, int(hop), int(max_batch),
+                                                       logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p), C.byref(n_out)))
+            assert n_out.value == nw
+        return logits, probs
+
+    def forward_recordings(self, recordings, window: Optional[int] = None, hop: int = 1280, max_batch: int = 4096):
+        """list of int16 [N_i] -> [(logits, probs)] per recording, scored together (score_recordings): windows never mix two recordings"""
+        return score_recordings(self.forward_recording, recordings, int(self.clip_samples if window is None else window), hop, max_batch)
+
+    def forward_recording_dev(self, pcm_ptr: int, n_samples: int, window: int, hop: int, logits_ptr: int, probs_ptr: int = 0,
+                              max_batch: int = 4096, stream: int = 0) -> int:
+        """Raw device pointers; enqueues on `stream`, does not synchronise.  Returns the number of windows written."""
+        nw = self._rec_count(n_samples, window, hop)
+        if nw:
+            self._check(self.lib.nww_forward_recording_dev(self._h, C.c_void_p(pcm_ptr), int(n_samples), int(window), int(hop), int(max_batch),
+                                                           C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                           C.c_void_p(probs_ptr) if probs_ptr else None,
+                                                           C.c_void_p(stream) if stream else None))
+        return nw
 
     @property
     def feature_clamp(self) -> float:
@@ -490,6 +590,13 @@ class HipSession:
     def run(self, output_names, input_feed):
         _, probs = self._forward(input_feed)
         return [probs.reshape(-1, 1, 1)]
+
+    def run_recording(self, pcm: np.ndarray, hop: int = 1280, offset: int = 0, max_batch: int = 4096) -> np.ndarray:
+        """int16 [N] -> probabilities [nW] of the windows pcm[offset + i * hop : offset + i * hop + clip_samples] (what run() returns for
+        each of them), the recording uploaded once: HipInterpreter.score_recording's batch path."""
+        if self.mode != "e2e":
+            raise ValueError("run_recording needs an e2e session (raw PCM in)")
+        return self.model.forward_recording(pcm, window=self.clip_samples, hop=hop, offset=offset, max_batch=max_batch)[1]
 
     def run_logits(self, input_feed):
         logits, _ = self._forward(input_feed)

@@ -2,7 +2,9 @@
 """Measure every BASELINE.json config on ONE MI355X (the multi-GPU ones at their per-GPU batch):
 clips/s PCM->logit with PCM resident in HBM, per-launch times, max |dlogit| vs the oracle on a few clips.
 Prints one JSON line per config.  (bench.py remains the contract benchmark for configs[1].)
---rnn [out]: the RNN head's fused / unfused input projection A/B (rnn_main) -> profiles/rnn_bench_configs.jsonl."""
+--rnn [out]: the RNN head's fused / unfused input projection A/B (rnn_main) -> profiles/rnn_bench_configs.jsonl.
+--recording [out]: recording scoring, shared-frame against strided route against pre-materialised windows (recording_main) ->
+profiles/recording_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -263,9 +265,119 @@ def rnn_main(out_path):
     sys.stdout.write(text)
 
 
+REC_HEADS, REC_W, REC_HOP, REC_B = ("cnn", "gru"), 16000, 1280, 4096
+REC_HOST_WARMUP, REC_HOST_STEPS = 2, 5
+
+
+def recording_child():
+    """One process = one setting of NWW_REC_SHARED (read once).  Per head: 4096 windows of 1 s, a hop of 80 ms, one pass, the PCM already on
+    the device - forward_pcm_dev on the pre-materialised windows (the path recording scoring does not touch: the baseline) and
+    forward_recording_dev on the recording, ms per call as the median of RNN_STEPS device-event timings behind RNN_WARMUP warm-up calls;
+    then host to host, forward_pcm on the host windows against forward_recording on the host recording (wall clock, median of
+    REC_HOST_STEPS); and whether the two agree bit for bit."""
+    import torch
+    from numpy.lib.stride_tricks import sliding_window_view
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    n = REC_W + (REC_B - 1) * REC_HOP
+    rec_h = synth_pcm("speechlike", 1, n, seed=10)[0]
+    win_h = np.ascontiguousarray(sliding_window_view(rec_h, REC_W)[::REC_HOP])
+    assert win_h.shape == (REC_B, REC_W)
+    rec, win = torch.from_numpy(rec_h).to(dev), torch.from_numpy(win_h).to(dev)
+    for head in REC_HEADS:
+        cfg = HeadConfig(head, (101, 64))
+        m = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+        ts = torch.cuda.Stream(dev)
+        stream = ts.cuda_stream
+        lg_w = torch.empty(REC_B, dtype=torch.float32, device=dev)
+        lg_r = torch.empty(REC_B, dtype=torch.float32, device=dev)
+        m.reserve(REC_B, REC_W)
+        legs = {"windows": lambda: m.forward_pcm_dev(win.data_ptr(), REC_B, REC_W, lg_w.data_ptr(), 0, stream),
+                "recording": lambda: m.forward_recording_dev(rec.data_ptr(), n, REC_W, REC_HOP, lg_r.data_ptr(), 0, REC_B, stream)}
+        out = {"head": head, "route": m.recording_route(REC_W, REC_HOP), "windows": REC_B, "window": REC_W, "hop": REC_HOP}
+        for name, step in legs.items():
+            for _ in range(RNN_WARMUP):
+                step()
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+            for e0, e1 in ev:
+                e0.record(ts); step(); e1.record(ts)
+            torch.cuda.synchronize()
+            out[name + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+        out["bit_identical"] = bool(torch.equal(lg_w, lg_r))
+
+        def wall(fn):
+            for _ in range(REC_HOST_WARMUP):
+                fn()
+            t = []
+            for _ in range(REC_HOST_STEPS):
+                t0 = time.perf_counter(); fn(); t.append((time.perf_counter() - t0) * 1e3)
+            return round(float(np.median(t)), 3)
+        out["host_windows_ms"] = wall(lambda: m.forward_pcm(win_h))
+        out["host_recording_ms"] = wall(lambda: m.forward_recording(rec_h, REC_W, REC_HOP, max_batch=REC_B))
+        out["host_bit_identical"] = bool(np.array_equal(m.forward_pcm(win_h)[0], m.forward_recording(rec_h, REC_W, REC_HOP, max_batch=REC_B)[0]))
+        print(json.dumps(out), flush=True)
+        m.close()
+
+
+def recording_main(out_path):
+    """NWW_REC_SHARED = 1 and 0 alternated, RNN_REPEATS fresh processes each, one after another (the protocol of --rnn); per head the
+    medians of the repeats, their spread (max - min), and whether the shared-frame route beats the strided one by more than the spread."""
+    import subprocess
+
+    def run(knob):
+        env = dict(os.environ, NWW_REC_SHARED=knob)
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--recording-child"], env=env, cwd=ROOT,
+                           stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"child (NWW_REC_SHARED={knob}) exited {r.returncode}")
+        return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    runs = {"1": [], "0": []}
+    for _ in range(RNN_REPEATS):
+        for knob in ("1", "0"):
+            runs[knob].append(run(knob))
+    lines = []
+    for i, head in enumerate(REC_HEADS):
+        assert all(r[i]["route"] == int(k) and r[i]["bit_identical"] and r[i]["host_bit_identical"] for k in runs for r in runs[k]), head
+        sh = [r[i]["recording_ms"] for r in runs["1"]]
+        st = [r[i]["recording_ms"] for r in runs["0"]]
+        base = [r[i]["windows_ms"] for k in ("1", "0") for r in runs[k]]
+        shm, stm, bm = float(np.median(sh)), float(np.median(st)), float(np.median(base))
+        spread = max(max(sh) - min(sh), max(st) - min(st))
+        hw = [r[i]["host_windows_ms"] for k in ("1", "0") for r in runs[k]]
+        hs, ht = [r[i]["host_recording_ms"] for r in runs["1"]], [r[i]["host_recording_ms"] for r in runs["0"]]
+        lines.append({"config": f"recording {head} 101x64 W={REC_W} hop={REC_HOP} {REC_B} windows per pass", "head": head, "windows": REC_B,
+                      "warmup": RNN_WARMUP, "steps": RNN_STEPS, "materialised_windows_ms_repeats": base, "strided_ms_repeats": st,
+                      "shared_ms_repeats": sh, "materialised_windows_ms": round(bm, 4), "strided_ms": round(stm, 4), "shared_ms": round(shm, 4),
+                      "spread_ms": round(spread, 4), "shared_faster_by_ms": round(stm - shm, 4), "shared_wins": bool(stm - shm > spread),
+                      "materialised_windows_per_s": round(REC_B / bm * 1e3, 1), "strided_windows_per_s": round(REC_B / stm * 1e3, 1),
+                      "shared_windows_per_s": round(REC_B / shm * 1e3, 1), "bit_identical_to_windows": True,
+                      "host_to_host": {"steps": REC_HOST_STEPS, "forward_pcm_on_windows_ms_repeats": hw, "forward_recording_shared_ms_repeats": hs,
+                                       "forward_recording_strided_ms_repeats": ht, "forward_pcm_on_windows_ms": round(float(np.median(hw)), 3),
+                                       "forward_recording_shared_ms": round(float(np.median(hs)), 3),
+                                       "forward_recording_strided_ms": round(float(np.median(ht)), 3),
+                                       "bytes_uploaded": {"windows": REC_B * REC_W * 2, "recording": (REC_W + (REC_B - 1) * REC_HOP) * 2}}})
+    lines.append({"config": "recording: default of NWW_REC_SHARED by the rule 'shared beats strided on both heads by more than the spread'",
+                  "NWW_REC_SHARED_default": int(all(l["shared_wins"] for l in lines))})
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
     if "--rnn-child" in sys.argv[1:]:
         return rnn_child()
+    if "--recording-child" in sys.argv[1:]:
+        return recording_child()
+    if "--recording" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--recording"]
+        return recording_main(rest[0] if rest else os.path.join(ROOT, "profiles", "recording_bench_configs.jsonl"))
     if "--rnn" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a != "--rnn"]
         return rnn_main(rest[0] if rest else os.path.join(ROOT, "profiles", "rnn_bench_configs.jsonl"))
