@@ -9,8 +9,8 @@
 //   S2  lane = (frame 0..7, row k1 0..7): 25-point DFT in registers, written back in natural bin order
 //   S3  lane = bin (k and 64 + k): split + |X|^2, twiddles in registers, powers written in place
 //   S4  mel contraction on v_mfma_f32_16x16x4_f32 (M = frames, N = 16 filters, K = the tile's own bin range; the
-//       matrix pipe is otherwise idle in this kernel and runs beside the other waves' VALU work) or, for A/B
-//       measurements, the sparse VALU loop of the first kernel; 10 log10 on the accumulator layout
+//       matrix pipe is otherwise idle in this kernel and runs beside the other waves' VALU work) or on register-resident
+//       filters, lane = filter (the default); 10 log10 on the accumulator layout
 //   out the wave's 8 x n_mels block leaves through a small LDS stage as 16-byte coalesced stores
 // LDS: 12.8 KB per wave (400 dwords per frame, reused in place by every stage) -> 12 waves per CU.
 // HBM traffic per clip: 2*N bytes read + 4*n_mels*frames written; nothing else leaves the CU.
@@ -21,11 +21,6 @@
 #include "layers.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Fe2MelLds {                 // sparse-mel tables of the VALU variant (packed: 3 KB)
-    uint32_t desc[FE_MAX_MELS];    // lo | cnt << 8 | off << 16
-    float w[FE_MAX_MELW];
-};
 
 // LDS traffic inside one wave is ordered by the hardware; these fences only stop the compiler from moving LDS
 // accesses across a stage boundary (no instruction is emitted for wavefront scope).
@@ -52,13 +47,12 @@ __device__ __forceinline__ float fe2_db(float mel, float amin, float mult, float
 // MEL: how S4 contracts the powers with the filterbank
 //   2  lane = filter (n_mels <= 64, every filter <= MAXT taps): the lane's weights stay in MAXT registers for the whole
 //      launch, one fmaf per tap and one 16-byte LDS read per four taps (the taps start at a multiple of four bins, zero weights
-//      in front), zero-padded to MAXT - same summation order as the sparse loop.
+//      in front), zero-padded to MAXT - the summation order of fe_steps.h's sparse loop.
 //      The default: on gfx950 the float32 MFMA runs at the VALU rate AND blocks the SIMD's VALU while it runs
 //      (tools/ubench/mfma_valu_overlap.hip: a v_mfma_f32_16x16x4_f32 wave and a VALU wave on one SIMD take a + b,
 //      AGPR accumulators or not), so the dense 16 x 16 x K tiles with half their rows empty cost 2048 matrix-pipe
 //      clocks per item against ~900 for these 370 VALU instructions.
 //   1  v_mfma_f32_16x16x4_f32 tiles (any n_mels <= 128, any filterbank)
-//   0  sparse loop over LDS tables (any filterbank; A/B reference)
 // FAST_OUT: frames-major log-mel only (the PCM -> logit path): branch-free S4 epilogue
 #define FE2_PARAMS                                                                                                      \
     const int16_t *__restrict__ pcm, size_t row_stride, int B, int N, int T, int ngroups, int hop, int pad, int n_mels,    \
@@ -76,6 +70,7 @@ __device__ __forceinline__ float fe2_db(float mel, float amin, float mult, float
 // nine in ten) runs S1 without any test: trip k + 1's loads are issued unconditionally and stay in flight under trip k's arithmetic.
 template <int MEL, int FAST_OUT, int MAXT, bool RING, bool FLAT>
 __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
+    static_assert(MEL == 1 || MEL == 2, "the mel stage runs on MFMA tiles or on register filters");
     static_assert(!FLAT || (FAST_OUT && !RING && MEL == 2), "flat items: frames-major fast output, register filters, no frame subsets");
 #ifndef NWW_ABLATION
     if (FLAT) dbg = 0;      // the stage switches are compiled out: a branch between a trip's loads and their use costs the overlap (S1)
@@ -85,15 +80,7 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nwv = blockDim.x >> 6;
-    const int tb_bytes = MEL == 0 ? (int)sizeof(Fe2MelLds) : 0;
-    Fe2MelLds* mt = reinterpret_cast<Fe2MelLds*>(smem);
-    float* slab = reinterpret_cast<float*>(smem + tb_bytes) + wv * (FE2_G * FE2_FRAME_DW);
-    if (MEL == 0) {       // the only workgroup barrier of the kernel: sparse-mel tables -> LDS, once
-        for (int i = threadIdx.x; i < FE_MAX_MELS; i += blockDim.x)
-            mt->desc[i] = (uint32_t)gtb->mel_lo[i] | ((uint32_t)gtb->mel_cnt[i] << 8) | ((uint32_t)gtb->mel_off[i] << 16);
-        for (int i = threadIdx.x; i < FE_MAX_MELW; i += blockDim.x) mt->w[i] = gtb->melw[i];
-        __syncthreads();
-    }
+    float* slab = reinterpret_cast<float*>(smem) + wv * (FE2_G * FE2_FRAME_DW);
     // ---- per-lane constants, resident in registers for the whole launch
     const int n2 = lane % 25, slot = lane / 25;             // S1: lanes 50..63 idle
     nww_c32 win[8], tw[7];
@@ -431,7 +418,7 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
                     load_chunk(min(c + 2, last), a0, b0);
                     if (c + 1 < mel_nchunks) run_chunk(c + 1, a1, b1);
                 }
-            } else if (MEL == 2) {
+            } else {
                 // two frames per trip: two independent fmaf chains; rows of frames >= nf hold stale (finite) data and
                 // are staged too - the copy-out takes nf rows only
                 const float* p0 = slab + mel_lo_lane;
@@ -471,28 +458,6 @@ __device__ __forceinline__ void fe2_wave_body(FE2_PARAMS) {
                                     }
                                 }
                             }
-                        }
-                    }
-                }
-            } else {
-                const int f = lane & 7;
-                if (f < nf) {
-                    const float* prow = slab + f * FE2_FRAME_DW + FE2_PSHIFT(f);
-                    for (int j = lane >> 3; j < n_mels; j += 8) {
-                        const uint32_t d = mt->desc[j];
-                        const float* p = prow + (d & 0xffu);
-                        const float* w = mt->w + (d >> 16);
-                        const int n = (d >> 8) & 0xffu;
-                        float m = 0.0f;
-                        for (int i = 0; i < n; ++i) m = fmaf(p[i], w[i], m);
-                        const float db = fe2_db(m, amin, db_mult, floor_db);
-                        if (frames_major) {
-                            slab[f * FE2_FRAME_DW + FE2_STAGE_OFF + FE2_PSHIFT(f) + j] = db;
-                            if (out_mel) out_mel[((size_t)b * T + t0 + f) * n_mels + j] = m;
-                        } else {
-                            const size_t o = ((size_t)b * n_mels + j) * T + t0 + f;
-                            if (out_db) out_db[o] = db;
-                            if (out_mel) out_mel[o] = m;
                         }
                     }
                 }
@@ -536,15 +501,13 @@ template <int MEL, int FAST_OUT, int MAXT, bool RING = false, bool FLAT = false>
 __global__ void __launch_bounds__(256, 3) fe2_wave_kernel(FE2_PARAMS) { fe2_wave_body<MEL, FAST_OUT, MAXT, RING, FLAT>(FE2_ARGS); }
 
 // the streaming instances exist for the frames-major fast output with the mel stage on register filters or MFMA tiles
-bool fe2_subset_supported(const FeParams& p, int mel_mode) { return mel_mode != 0 && (p.n_mels & 3) == 0; }
+bool fe2_subset_supported(const FeParams& p) { return (p.n_mels & 3) == 0; }
 
-int fe2_lds_bytes(int waves, int mel_mode) {
-    return waves * FE2_G * FE2_FRAME_DW * 4 + (mel_mode == 0 ? (int)sizeof(Fe2MelLds) : 0);
-}
+int fe2_lds_bytes(int waves) { return waves * FE2_G * FE2_FRAME_DW * 4; }
 
 hipError_t fe2_launch(const int16_t* d_pcm, size_t row_stride, int B, int N, int T, const FeParams& p,
                       const FeTables* d_tables, const Fe2MelPlan* d_plan, float* d_db, float* d_mel, int frames_major,
-                      int mel_mode, int max_taps, int block, int max_grid, hipStream_t stream, const Fe2Sub* subset) {
+                      int max_taps, int block, int max_grid, hipStream_t stream, const Fe2Sub* subset) {
     if (block < 64 || block > 1024 || (block & 63)) return hipErrorInvalidValue;
     const int nwv = block / 64;
     Fe2Sub sub = subset ? *subset : Fe2Sub{};
@@ -560,13 +523,12 @@ hipError_t fe2_launch(const int16_t* d_pcm, size_t row_stride, int B, int N, int
     for (int r = 0; r < sub.nr; ++r)
         if (sub.t0[r] < 0 || sub.t1[r] <= sub.t0[r] || sub.t1[r] > T) return hipErrorInvalidValue;
     int ngroups = count_groups(FE2_G);
-    // mel_mode: 2 = register-resident filters (falls back to the MFMA tiles when the filterbank does not fit), 1, 0
-    int mode = mel_mode;
-    if (mode == 2 && (p.n_mels > 64 || max_taps > 25)) mode = 1;      // (up to three more taps than the longest filter: the 16-byte alignment)
-    const int lds = fe2_lds_bytes(nwv, mode);
+    // the mel stage (MEL): 2 = register-resident filters, 1 = the MFMA tiles when the filterbank does not fit the registers
+    const int mode = (p.n_mels > 64 || max_taps > 25) ? 1 : 2;         // (up to three more taps than the longest filter: the 16-byte alignment)
+    const int lds = fe2_lds_bytes(nwv);
     const int fast = (frames_major && d_db && !d_mel) ? 1 : 0;
     const bool ring = sub.nr > 0 || sub.ring_rows > 0;
-    if (ring && (mode == 0 || !fast)) return hipErrorInvalidValue;
+    if (ring && !fast) return hipErrorInvalidValue;
 #ifdef NWW_ABLATION      // stage-skipping builds for phase timing (results are garbage): never in the shipped library
     static const int dbg = [] { const char* e = getenv("NWW_FE_DBG"); return e ? atoi(e) : 0; }();
 #else
@@ -586,8 +548,7 @@ hipError_t fe2_launch(const int16_t* d_pcm, size_t row_stride, int B, int N, int
     // both ends, and the per-clip map's staged span is the faster of the two (0.0184 against 0.0189 ms for 4096 clips).
     const bool flat = fast && !ring && mode == 2 && gsz == FE2_G && T != FE2_G && (long long)B * T <= 0x7fffffffLL - FE2_G &&
                       (unsigned long long)row_stride * FE2_G + (unsigned long long)N < (1ull << 31);     // (32-bit byte offsets inside an item)
-    auto kern = mode == 0 ? fe2_wave_kernel<0, 0, 1>
-              : mode == 1 ? (ring ? fe2_wave_kernel<1, 1, 1, true> : fast ? fe2_wave_kernel<1, 1, 1> : fe2_wave_kernel<1, 0, 1>)
+    auto kern = mode == 1 ? (ring ? fe2_wave_kernel<1, 1, 1, true> : fast ? fe2_wave_kernel<1, 1, 1> : fe2_wave_kernel<1, 0, 1>)
               : max_taps <= 17 ? (ring ? fe2_wave_kernel<2, 1, 20, true> : flat ? fe2_wave_kernel<2, 1, 20, false, true> : fast ? fe2_wave_kernel<2, 1, 20> : fe2_wave_kernel<2, 0, 20>)
                                : (ring ? fe2_wave_kernel<2, 1, 28, true> : flat ? fe2_wave_kernel<2, 1, 28, false, true> : fast ? fe2_wave_kernel<2, 1, 28> : fe2_wave_kernel<2, 0, 28>);
     const void* fn = reinterpret_cast<const void*>(kern);

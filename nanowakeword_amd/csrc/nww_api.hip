@@ -329,32 +329,14 @@ extern "C" int nww_reserve(nww_handle* h, int32_t B, int32_t N) {
     return nww_ensure_ws(h, B, N);
 }
 
-int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, unsigned int* done_flag,
-                 unsigned int done_seq, bool* done_armed, bool x_frames_major) {
+int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, const RunOpts& o) {
     Run r;
-    r.x_frames_major = x_frames_major;
-    r.done_flag = done_flag; r.done_seq = done_seq;
+    r.x_frames_major = o.x_frames_major;
+    r.done_flag = o.done_flag; r.done_seq = o.done_seq;
+    if (o.hop) r.hop = *o.hop;
     r.B = B; r.stream = s; r.x = d_x; r.emb = h->d_emb; r.hid = h->d_hid; r.logits = d_logits ? d_logits : h->d_logits;
     r.probs = d_probs;
     r.splitk_ws = h->d_splitk; r.splitk_floats = h->splitk_per_clip * (size_t)h->cap_B; r.cu_count = h->cu_count;
-    if (h->sr.on) {                                    // a streaming hop (nww_stream.hip) configured this forward
-        h->sr.on = false;
-        r.x_stride = h->sr.x_stride;
-        r.stream_mode = h->sr.mode;
-        if (r.stream_mode) {
-            const int W2 = h->stream_W / 4;
-            r.a2_ring = h->d_a2_ring; r.a2_rows = h->a2_rows; r.a2_row0 = h->a2_pos;
-            r.a2_ch_stride = (size_t)h->a2_rows * W2; r.a2_clip_stride = 32 * r.a2_ch_stride;
-            if (h->d_seq[0]) {
-                r.seq_new = h->d_seq[h->seq_cur];
-                if (r.stream_mode == 2) { r.seq_prev = h->d_seq[h->seq_cur ^ 1]; r.a3_lo = h->a3_lo; r.a3_hi = h->a3_hi; r.a3_shift = h->a3_shift; }
-            }
-            if (r.stream_mode == 2) {
-                r.a2_nsub = h->a2_nsub;
-                for (int q = 0; q < h->a2_nsub; ++q) { r.a2_sub_a[q] = h->a2_sub_a[q]; r.a2_sub_b[q] = h->a2_sub_b[q]; }
-            }
-        }
-    }
     size_t off = 0;
     for (int i = 0; i < 6; ++i) {
         r.buf[i] = h->d_ws + off;
@@ -372,7 +354,7 @@ int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float*
         if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'sigmoid' failed: %s", hipGetErrorString(e));
     }
     nww_prof_mark(h, s, -1);
-    if (done_armed) *done_armed = r.done_armed;
+    if (o.done_armed) *o.done_armed = r.done_armed;
     return NWW_OK;
 }
 
@@ -388,7 +370,7 @@ int nww_check_run(nww_handle* h, int B) {
 static int nww_raw_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_out, int frames_major, hipStream_t s,
                                    int* frames_out, size_t row_stride) {
     const int T = nww_pcm_rows(h, N);
-    if (T <= 0) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
+    if (T <= 0) return nww_fail_short_clip(h, N);
     if (frames_out) *frames_out = T;
     int rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
@@ -423,11 +405,10 @@ int nww_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float
         if (d_mel || sub) return fail(h, NWW_ERR_INVALID, "the raw-PCM frontend has no mel power and no frame subsets");
         return nww_raw_frontend_on_dev(h, d_pcm, B, N, d_db, frames_major, s, frames_out, row_stride);
     }
-    const int T = fe_num_frames(h->fe, N);
-    if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
+    const int T = nww_pcm_rows(h, N);
+    if (T <= 0) return nww_fail_short_clip(h, N);
     if (frames_out) *frames_out = T;
-    static const int mel_env = 2;    // 2: register filters, 1: MFMA tiles, 0: sparse LDS loop
-    hipError_t e = fe2_launch(d_pcm, row_stride ? row_stride : (size_t)N, B, N, T, h->fe, h->d_tables, h->d_melplan, d_db, d_mel, frames_major, mel_env, h->mel_max_taps, 256, h->cu_count * 3, s, sub);
+    hipError_t e = fe2_launch(d_pcm, row_stride ? row_stride : (size_t)N, B, N, T, h->fe, h->d_tables, h->d_melplan, d_db, d_mel, frames_major, h->mel_max_taps, 256, h->cu_count * 3, s, sub);
     if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "frontend launch failed: %s", hipGetErrorString(e));
     return NWW_OK;
 }
@@ -442,15 +423,13 @@ extern "C" int nww_frontend_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, 
 }
 
 int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_logits, float* d_probs, hipStream_t s,
-                           size_t row_stride, unsigned int* done_flag, unsigned int done_seq, bool* done_armed) {
+                           size_t row_stride, const RunOpts& o) {
     const nww_config& c = h->cfg;
-    const int T = nww_pcm_rows(h, N);
-    if (T <= 0 && nww_raw_head(c)) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
-    if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
-    const int rows = c.mel_major_features ? c.n_mels : T, cols = nww_raw_head(c) ? c.in_cols : c.mel_major_features ? T : c.n_mels;
-    if (rows != c.in_rows || cols != c.in_cols)
+    const ClipRows cr = nww_clip_rows(h, N);
+    if (cr.T <= 0) return nww_fail_short_clip(h, N);
+    if (!cr.fits)
         return fail(h, NWW_ERR_SHAPE, "frontend yields (%d,%d) features for %d samples but the head was built for input_shape=(%d,%d)",
-                    rows, cols, N, c.in_rows, c.in_cols);
+                    cr.rows, cr.cols, N, c.in_rows, c.in_cols);
     int rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
     nww_prof_begin(h);
@@ -458,7 +437,9 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
     const bool fm = !c.mel_major_features || h->e2e_transposed;
     rc = nww_frontend_on_dev(h, d_pcm, B, N, h->d_logmel, nullptr, fm ? 1 : 0, s, nullptr, row_stride);
     if (rc) return rc;
-    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, done_flag, done_seq, done_armed, fm && c.mel_major_features);
+    RunOpts ro = o;
+    ro.x_frames_major = fm && c.mel_major_features;
+    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, ro);
 }
 
 extern "C" int nww_forward_pcm_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, int32_t N, float* d_logits,
@@ -490,8 +471,7 @@ extern "C" int nww_frontend_ex(nww_handle* h, const int16_t* pcm, int32_t B, int
     if (!pcm) return fail(h, NWW_ERR_INVALID, "Input audio must be a non-null int16 array");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int T = nww_pcm_rows(h, N);
-    if (T <= 0 && nww_raw_head(h->cfg)) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
-    if (T <= 0) return fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
+    if (T <= 0) return nww_fail_short_clip(h, N);
     if (nww_raw_head(h->cfg) && melpower_out) return fail(h, NWW_ERR_INVALID, "melpower_out must be NULL: the raw-PCM frontend has no mel power");
     rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
@@ -567,6 +547,31 @@ static int zero_copy_wait(nww_handle* h, hipStream_t s, bool armed, volatile uns
     return NWW_OK;
 }
 
+// One zero-copy small call: `bytes` of src staged, fwd(d_in, d_logits, d_probs, opts) run on the staging buffers' device addresses,
+// B logits / probabilities copied out.  *taken = false (and nothing done) when the call does not fit the staging area.
+template <class Fwd>
+static int zero_copy_call(nww_handle* h, const void* src, size_t bytes, int B, float* logits, float* probs, hipStream_t s, bool* taken, Fwd fwd) {
+    void* d_in = nullptr; float *zl = nullptr, *zp = nullptr;
+    *taken = zero_copy_ptrs(h, bytes, B, &d_in, &zl, &zp);
+    if (!*taken) return NWW_OK;
+    // the order matters from here on.  (1) a failed call may have left a copy out of pin_in in flight: wait before overwriting it
+    if (h->pin_in_busy) { HIP_TRY(h, hipStreamSynchronize(s)); h->pin_in_busy = false; }
+    std::memcpy(h->pin_in, src, bytes);                          // (2)
+    h->pin_in_busy = true;                                       // (3) busy until this call's kernels are known to have finished
+    RunOpts o;
+    bool armed = false;
+    o.done_flag = reinterpret_cast<unsigned int*>(zl) + (PIN_BYTES / sizeof(float) - 4);     // last words of the pinned output buffer
+    if (++h->done_seq == 0) ++h->done_seq;                       // (4) 0 is the word's initial value, never a sequence number
+    o.done_seq = h->done_seq; o.done_armed = &armed;
+    int rc = fwd(d_in, zl, zp, o);                               // (5)
+    if (rc) return rc;
+    rc = zero_copy_wait(h, s, armed, reinterpret_cast<volatile unsigned int*>(h->pin_out + PIN_BYTES - 16), o.done_seq);   // (6) poll or sync
+    if (rc) return rc;
+    if (logits) std::memcpy(logits, h->pin_out, (size_t)B * sizeof(float));                  // (7) only after the wait
+    if (probs) std::memcpy(probs, h->pin_out + (size_t)B * sizeof(float), (size_t)B * sizeof(float));
+    return NWW_OK;
+}
+
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s) {
     const size_t nb = (size_t)B * sizeof(float), ne = (size_t)B * h->cfg.embedding_dim * sizeof(float);
     const size_t need = (logits ? nb : 0) + (probs ? nb : 0) + (emb ? ne : 0);
@@ -603,26 +608,11 @@ extern "C" int nww_forward_pcm(nww_handle* h, const int16_t* pcm, int32_t B, int
     rc = nww_ensure_ws(h, B, N);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
-    {
-        void* d_in = nullptr; float *zl = nullptr, *zp = nullptr;
-        const size_t bytes = (size_t)B * N * sizeof(int16_t);
-        if (zero_copy_ptrs(h, bytes, B, &d_in, &zl, &zp)) {
-            if (h->pin_in_busy) { HIP_TRY(h, hipStreamSynchronize(s)); h->pin_in_busy = false; }
-            std::memcpy(h->pin_in, pcm, bytes);
-            h->pin_in_busy = true;
-            unsigned int* flag = reinterpret_cast<unsigned int*>(zl) + (PIN_BYTES / sizeof(float) - 4);     // last words of the pinned output buffer
-            if (++h->done_seq == 0) ++h->done_seq;                   // 0 is the word's initial value, never a sequence number
-            const unsigned int seq = h->done_seq;
-            bool armed = false;
-            rc = nww_forward_pcm_on_dev(h, static_cast<const int16_t*>(d_in), B, N, zl, zp, s, 0, flag, seq, &armed);
-            if (rc) return rc;
-            rc = zero_copy_wait(h, s, armed, reinterpret_cast<volatile unsigned int*>(h->pin_out + PIN_BYTES - 16), seq);
-            if (rc) return rc;
-            if (logits) std::memcpy(logits, h->pin_out, (size_t)B * sizeof(float));
-            if (probs) std::memcpy(probs, h->pin_out + (size_t)B * sizeof(float), (size_t)B * sizeof(float));
-            return NWW_OK;
-        }
-    }
+    bool taken = false;
+    rc = zero_copy_call(h, pcm, (size_t)B * N * sizeof(int16_t), B, logits, probs, s, &taken, [&](const void* d_in, float* zl, float* zp, const RunOpts& o) {
+        return nww_forward_pcm_on_dev(h, static_cast<const int16_t*>(d_in), B, N, zl, zp, s, 0, o);
+    });
+    if (rc || taken) return rc;
     rc = nww_h2d_small(h, h->d_pcm, pcm, (size_t)B * N * sizeof(int16_t), s);
     if (rc) return rc;
     rc = nww_forward_pcm_on_dev(h, h->d_pcm, B, N, h->d_logits, h->d_probs, s);
@@ -638,28 +628,16 @@ extern "C" int nww_forward_features_ex(nww_handle* h, const float* feats, int32_
     rc = nww_ensure_ws(h, B, 0);
     if (rc) return rc;
     hipStream_t s = h->own_stream;
+    const size_t bytes = (size_t)B * h->cfg.in_rows * h->cfg.in_cols * sizeof(float);
     if (!emb) {
-        void* d_in = nullptr; float *zl = nullptr, *zp = nullptr;
-        const size_t bytes = (size_t)B * h->cfg.in_rows * h->cfg.in_cols * sizeof(float);
-        if (zero_copy_ptrs(h, bytes, B, &d_in, &zl, &zp)) {
-            if (h->pin_in_busy) { HIP_TRY(h, hipStreamSynchronize(s)); h->pin_in_busy = false; }
-            std::memcpy(h->pin_in, feats, bytes);
-            h->pin_in_busy = true;
+        bool taken = false;
+        rc = zero_copy_call(h, feats, bytes, B, logits, probs, s, &taken, [&](const void* d_in, float* zl, float* zp, const RunOpts& o) {
             nww_prof_begin(h);
-            unsigned int* flag = reinterpret_cast<unsigned int*>(zl) + (PIN_BYTES / sizeof(float) - 4);
-            if (++h->done_seq == 0) ++h->done_seq;
-            const unsigned int seq = h->done_seq;
-            bool armed = false;
-            rc = nww_run_head(h, static_cast<const float*>(d_in), B, zl, zp, s, flag, seq, &armed);
-            if (rc) return rc;
-            rc = zero_copy_wait(h, s, armed, reinterpret_cast<volatile unsigned int*>(h->pin_out + PIN_BYTES - 16), seq);
-            if (rc) return rc;
-            if (logits) std::memcpy(logits, h->pin_out, (size_t)B * sizeof(float));
-            if (probs) std::memcpy(probs, h->pin_out + (size_t)B * sizeof(float), (size_t)B * sizeof(float));
-            return NWW_OK;
-        }
+            return nww_run_head(h, static_cast<const float*>(d_in), B, zl, zp, s, o);
+        });
+        if (rc || taken) return rc;
     }
-    rc = nww_h2d_small(h, h->d_feats, feats, (size_t)B * h->cfg.in_rows * h->cfg.in_cols * sizeof(float), s);
+    rc = nww_h2d_small(h, h->d_feats, feats, bytes, s);
     if (rc) return rc;
     nww_prof_begin(h);
     rc = nww_run_head(h, h->d_feats, B, h->d_logits, h->d_probs, s);

@@ -1,7 +1,8 @@
 // nww_internal.h - what the translation units of the C-ABI share: the handle, a forward's run state, error helpers and the
 // device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_weights.hip: state_dict spec
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
-// nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*).
+// nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
+// stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -18,6 +19,7 @@
 
 #include "../../include/nww.h"
 #include "fe_tables.h"
+#include "stream_plan.h"
 #include "frontend.h"
 #include "layers.h"
 #include "trunk.h"
@@ -49,19 +51,39 @@ struct Step {
     std::function<hipError_t(struct Run&)> fn;
 };
 
+// What a streaming hop hands to the plan's steps (built by nww_stream.hip, which alone knows the rings' geometry; read by add_trunk and
+// add_conv_mfma).  The default is no hop: a dense x, every row computed into the plan's workspace.
+struct HopView {
+    size_t x_stride = 0;        // floats between consecutive clips of x; 0 = dense (only first steps that say so at plan time take a stride)
+    // set only for plans with nww_handle::stream_conv: 1 = the fused trunk writes its pooled rows into per-stream rings and the third
+    // conv reads them there, 2 = and only the strips of rows a hop invalidates are computed
+    int mode = 0;
+    float* a2_ring = nullptr; int a2_rows = 0, a2_row0 = 0; size_t a2_ch_stride = 0, a2_clip_stride = 0;
+    int a2_nsub = 0, a2_sub_a[4] = {0, 0, 0, 0}, a2_sub_b[4] = {0, 0, 0, 0};
+    // the third conv's sequence output lives in two per-stream buffers that alternate from hop to hop: rows [a3_lo, a3_hi] of the new
+    // one are rows + a3_shift of the previous one, the others are computed (mode 2); null: the plan's workspace buffer
+    float* seq_new = nullptr; const float* seq_prev = nullptr; int a3_lo = 0, a3_hi = -1, a3_shift = 0;
+};
+
+// An open stream batch: S lock-step streams, a window of W samples, a score per hop.  nww_stream_open creates it, nww_stream_close frees
+// its device memory and deletes it, nww_stream_reset rewinds it.
+struct StreamState {
+    int S = 0, W = 0, hop = 0, pos = 0; long long filled = 0;
+    int16_t* d_ring = nullptr; int16_t* d_chunk = nullptr;   // [S][2 * W]: sample p of a stream lives at p and p + W; a host chunk's staging [S][hop]
+    HopPlan plan;                  // what a hop keeps; each kept level has its buffers below
+    bool primed = false;           // the rings hold the previous window (false: the next full window is computed whole)
+    // log-mel ring [S][2 * lm_rows][n_mels]: frame t of the current window at row lm_pos + t and lm_rows away; a hop shifts it by plan.k
+    float* d_lm_ring = nullptr; int lm_rows = 0, lm_pos = 0;
+    // pooled conv rows [S][32][plan.a2_rows][stream_W / 4]: row R at (a2_pos + R) % a2_rows; a hop shifts them by plan.a2_shift
+    float* d_a2_ring = nullptr; int a2_pos = 0;
+    float* d_seq[2] = {nullptr, nullptr}; int seq_cur = 0;   // the third conv's sequence output, alternating from hop to hop (HopView::seq_new)
+};
+
 struct Run {
     int B = 0;
     hipStream_t stream = nullptr;
     const float* x = nullptr;   // head input [B][in_rows*in_cols]
-    size_t x_stride = 0;        // floats between consecutive clips of x; 0 = dense (only first steps that say so at plan time take a stride)
-    // streaming hop (nww_stream.hip; set only for plans with nww_handle::stream_conv): 1 = the fused trunk writes its pooled rows
-    // into per-stream rings and the third conv reads them there, 2 = and only the rows a hop invalidates are computed
-    int stream_mode = 0;
-    float* a2_ring = nullptr; int a2_rows = 0, a2_row0 = 0; size_t a2_ch_stride = 0, a2_clip_stride = 0;
-    int a2_nsub = 0, a2_sub_a[4] = {0, 0, 0, 0}, a2_sub_b[4] = {0, 0, 0, 0};
-    // the third conv's sequence output lives in two per-stream buffers that alternate from hop to hop: rows [a3_lo, a3_hi] of the new
-    // one are rows + a3_shift of the previous one, the others are computed (stream_mode 2); null: the plan's workspace buffer
-    float* seq_new = nullptr; const float* seq_prev = nullptr; int a3_lo = 0, a3_hi = -1, a3_shift = 0;
+    HopView hop;
     bool x_frames_major = false; // E2E head on the transposed plane: x came from the frontend as [B][frames][n_mels] already
     float* buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float* emb = nullptr;       // [B][E]
@@ -117,23 +139,15 @@ struct nww_handle {
     float* d_logits = nullptr;
     float* d_probs = nullptr;
     float* d_splitk = nullptr;     // split-K partials
-    // streaming rings: [S][2*W] int16, sample p of a stream lives at p and p+W
-    int16_t* d_ring = nullptr; int16_t* d_chunk = nullptr;
-    // incremental hops (nww_stream.hip): log-mel ring [S][2 * lm_rows][n_mels] (frame t of the current window at row lm_pos + t and
-    // lm_rows away), pooled conv rows [S][32][a2_rows][W / 4] (row R at (a2_pos + R) % a2_rows); a hop shifts them by lm_shift / a2_shift
     std::string plan_error;        // plan time: a step that cannot be planned in ANY form (nww_finalize fails with it)
     bool clamps_features = false;  // plan time: a step that reads the head input clamps it to +-NWW_F16_FEATURE_BOUND (nww_feature_clamp)
-    bool x_stride_ok = false;      // plan time: the first step takes Run::x_stride (fused split-operand trunk, DNN layer1)
-    bool stream_conv = false;      // plan time: fused trunk -> conv3_x3 pair that takes Run::stream_mode (CRNN)
+    // plan-time capabilities: what the plan can take from a streaming hop (HopView)
+    bool x_stride_ok = false;      // the first step takes HopView::x_stride (fused split-operand trunk)
+    bool stream_conv = false;      // fused trunk -> conv3_x3 pair that takes HopView::mode (CRNN)
     int stream_H = 0, stream_W = 0;   // the plane that pair works on
-    bool inc_fe = false, inc_conv = false, primed = false;
-    float* d_lm_ring = nullptr; int lm_rows = 0, lm_pos = 0, lm_shift = 0, fe_edge_l = 0, fe_edge_r = 0;
-    float* d_a2_ring = nullptr; int a2_rows = 0, a2_pos = 0, a2_shift = 0, a2_lo = 0, a2_hi = 0;
-    int a2_nsub = 0, a2_sub_a[4] = {0, 0, 0, 0}, a2_sub_b[4] = {0, 0, 0, 0};   // the strips of pooled rows a hop recomputes, each cut to fit in LDS (plan_incremental)
-    bool stream_seq = false;       // plan time: that third conv writes the recurrent layers' sequence layout (its rows can be carried over)
+    bool stream_seq = false;       // that third conv writes the recurrent layers' sequence layout (its rows can be carried over)
     size_t seq_floats = 0;         // ... floats per clip of it
-    float* d_seq[2] = {nullptr, nullptr}; int seq_cur = 0, a3_lo = 0, a3_hi = -1, a3_shift = 0;
-    struct { bool on = false; size_t x_stride = 0; int mode = 0; } sr;    // what the next nww_run_head hands to its Run
+    StreamState* stream = nullptr; // the open stream batch (nww_stream_*)
     EmbState* emb = nullptr;       // embedding-mode preprocessor state (nww_emb_*)
     // recording scoring (nww_recording.hip): the pool of a pass's interior frames [(B - 1) k + T][n_mels], and for the host-pointer entry
     // point the recording and its [2][nW] logits / probabilities; each grown on demand
@@ -151,7 +165,6 @@ struct nww_handle {
     unsigned long long gather_seq = 0;
     const float* gather_buf[2] = {nullptr, nullptr};   // the d_all_logits each slot's gather last wrote
     long long gather_test_delay_us = 0;                // test hook, read ONCE at nww_comm_init (NWW_GATHER_TEST_DELAY_US)
-    int ring_S = 0, ring_W = 0, ring_hop = 0, ring_pos = 0; long long ring_filled = 0;
     size_t splitk_per_clip = 0;    // floats per clip (max over the plan's split GEMMs)
     std::map<X3Key, void*> x3_weights;             // GEMM weights pre-split into bf16 terms / scaled binary16 terms (gemm_x3.hip)
     std::vector<void*> packed_weights;             // other plan-time weight packings (ffn_x3.hip)
@@ -177,12 +190,19 @@ void nww_prof_mark(nww_handle* h, hipStream_t s, int id_of_next);
 void nww_prof_begin(nww_handle* h);
 int nww_check_run(nww_handle* h, int B);
 int nww_ensure_ws(nww_handle* h, int B, int N);
-int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, unsigned int* done_flag = nullptr,
-                 unsigned int done_seq = 0, bool* done_armed = nullptr, bool x_frames_major = false);
+// a forward's optional inputs
+struct RunOpts {
+    bool x_frames_major = false;           // Run::x_frames_major
+    unsigned int* done_flag = nullptr;     // zero-copy small calls: the completion word, its sequence number, and whether a step was armed to write it
+    unsigned int done_seq = 0;
+    bool* done_armed = nullptr;
+    const HopView* hop = nullptr;          // a streaming hop
+};
+int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, const RunOpts& o = RunOpts());
 int nww_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_db, float* d_mel, int frames_major, hipStream_t s,
                         int* frames_out, size_t row_stride = 0, const Fe2Sub* sub = nullptr);
 int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_logits, float* d_probs, hipStream_t s,
-                           size_t row_stride = 0, unsigned int* done_flag = nullptr, unsigned int done_seq = 0, bool* done_armed = nullptr);
+                           size_t row_stride = 0, const RunOpts& o = RunOpts());
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
 void nww_recording_free(nww_handle* h);        // nww_recording.hip
@@ -203,14 +223,21 @@ inline int nww_pcm_rows(const nww_handle* h, int N) {
     for (int i = 0; i < h->cfg.n_blocks; ++i) L = raw_conv_rows(L, i == 0 ? 16 : 4);
     return L < 1 ? -1 : L;
 }
-// the first el and last er of a W-sample window's T frames read its reflect padding (centred frontends; 0 / 0 otherwise): every other frame is
-// the same samples, hence the same log-mel bits, in whichever window of a stream or recording it falls (nww_stream.hip, nww_recording.hip)
-inline void nww_edge_frames(const FeParams& fe, int T, int W, int& el, int& er) {
-    const int pad = fe.center ? fe.n_fft / 2 : 0;
-    el = er = 0;
-    while (el < T && el * fe.hop - pad < 0) ++el;
-    while (er < T && (T - 1 - er) * fe.hop - pad + fe.n_fft > W) ++er;
+// a clip of N samples against the head: its rows T, the (rows, cols) feature shape they give, and whether that is the head's
+struct ClipRows { int T, rows, cols; bool fits; };
+inline ClipRows nww_clip_rows(const nww_handle* h, int N) {
+    const nww_config& c = h->cfg;
+    const int T = nww_pcm_rows(h, N);
+    const int rows = c.mel_major_features ? c.n_mels : T, cols = nww_raw_head(c) ? c.in_cols : c.mel_major_features ? T : c.n_mels;
+    return {T, rows, cols, T > 0 && rows == c.in_rows && cols == c.in_cols};
 }
+// ... and the error of a clip that has no rows, in the wording of its frontend
+inline int nww_fail_short_clip(nww_handle* h, int N) {
+    if (nww_raw_head(h->cfg)) return nww_fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
+    return nww_fail(h, NWW_ERR_INVALID, "clip of %d samples is too short for n_fft=%d (center=%d)", N, h->fe.n_fft, h->fe.center);
+}
+// window / hop rule and head shape of a stream batch or a recording, then what its hops share at NWW_STREAM_INC `level` (nww_stream.hip)
+int nww_window_plan(nww_handle* h, int W, int hop, int level, HopPlan& p);
 // the QuartzNet blocks' and fc's key prefix: the raw-PCM head holds them under model.backbone
 // NWW_HEAD_E2E_CNN: RawAudioBackbone's four conv stages (architectures.py:739-762) on the channels-last plane [A = image W][Bd = image H]
 struct RawCnnLayer { int cin, cout, sA, sB; };

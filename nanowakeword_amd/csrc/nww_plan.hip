@@ -417,12 +417,13 @@ bool add_trunk(PlanCtx& p, const std::string& name, int in_id, int out_id, int C
             a.wpack = static_cast<const unsigned char*>(packed);
             if (f16) { a.f16_in = f_in; a.f16_k1 = f_in * f_w1; a.f16_s1 = f_s1; a.f16_k2 = f_s1 * f_w2; a.f16_so = 1.0f; a.f16_clamp = (float)in_bound; }
             a.bn_pos = bn_pos;
-            if (in_id == BUF_X) a.in_clip_stride = r.x_stride;
-            if (r.stream_mode) {                        // streaming hop: pooled rows into the per-stream rings, all of them or the invalidated ones
-                a.out = r.a2_ring; a.out_ring_rows = r.a2_rows; a.out_row0 = r.a2_row0;
-                a.out_ch_stride = r.a2_ch_stride; a.out_clip_stride = r.a2_clip_stride;
-                a.n_sub = r.stream_mode == 2 ? r.a2_nsub : 0;
-                for (int q = 0; q < a.n_sub; ++q) { a.sub_a[q] = r.a2_sub_a[q]; a.sub_b[q] = r.a2_sub_b[q]; }
+            const HopView& v = r.hop;
+            if (in_id == BUF_X) a.in_clip_stride = v.x_stride;
+            if (v.mode) {                               // streaming hop: pooled rows into the per-stream rings, all of them or the invalidated ones
+                a.out = v.a2_ring; a.out_ring_rows = v.a2_rows; a.out_row0 = v.a2_row0;
+                a.out_ch_stride = v.a2_ch_stride; a.out_clip_stride = v.a2_clip_stride;
+                a.n_sub = v.a2_nsub;
+                for (int q = 0; q < a.n_sub; ++q) { a.sub_a[q] = v.a2_sub_a[q]; a.sub_b[q] = v.a2_sub_b[q]; }
             }
             return launch_cnn_trunk_b(a, products, max_grid, r.stream);
         });
@@ -530,13 +531,14 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
             a.Cin = Cin; a.w_cin = Cin; a.strip_h = strip_h;
             a.avg_kw = o.avg_kw; a.avg_sw = o.avg_sw; a.avg_ow = o.avg_ow; a.seq_out = seq_out; a.avg_y = o.avg_y;
             if (h2) { a.h2_in = h2_in; a.h2_w = h2_w; }
-            if (ring_ok && r.stream_mode) {             // streaming hop: the fused trunk's pooled rows are read from their rings
-                a.in = r.a2_ring; a.in_ring_rows = r.a2_rows; a.in_row0 = r.a2_row0;
-                a.in_ch_stride = r.a2_ch_stride; a.in_clip_stride = r.a2_clip_stride;
-                if (seq_out && r.seq_new) {             // ... and the sequence rows a hop does not invalidate are carried over from the previous hop's buffer
-                    r.buf[out_id] = r.seq_new;          // (the recurrent layers planned behind this step read r.buf[out_id])
-                    a.out = r.seq_new;
-                    a.seq_prev = r.seq_prev; a.keep_lo = r.a3_lo; a.keep_hi = r.a3_hi; a.keep_shift = r.a3_shift;
+            const HopView& v = r.hop;
+            if (ring_ok && v.mode) {                    // streaming hop: the fused trunk's pooled rows are read from their rings
+                a.in = v.a2_ring; a.in_ring_rows = v.a2_rows; a.in_row0 = v.a2_row0;
+                a.in_ch_stride = v.a2_ch_stride; a.in_clip_stride = v.a2_clip_stride;
+                if (seq_out && v.seq_new) {             // ... and the sequence rows a hop does not invalidate are carried over from the previous hop's buffer
+                    r.buf[out_id] = v.seq_new;          // (the recurrent layers planned behind this step read r.buf[out_id])
+                    a.out = v.seq_new;
+                    a.seq_prev = v.seq_prev; a.keep_lo = v.a3_lo; a.keep_hi = v.a3_hi; a.keep_shift = v.a3_shift;
                 }
             }
             return launch_conv3_x3(a, max_grid * per_cu, r.stream);

@@ -3,7 +3,7 @@
 // windows - on one of two routes per (window, hop):
 //   strided  every pass of B windows is nww_forward_pcm_on_dev with row_stride = hop: all T frames of every window are computed
 //   shared   a hop of k = hop / hop_length frames makes interior frame t of window w the frame t - k of window w + 1, bit for bit
-//            (what plan_incremental of nww_stream.hip relies on from hop to hop).  Per pass: (1) the pass's span of (B - 1) hop + window
+//            (what a stream's log-mel ring relies on from hop to hop; HopPlan, stream_plan.h). Per pass: (1) the pass's span of (B - 1) hop + window
 //            samples goes through the batch frontend as ONE clip, whose frames-major output is the pool - row w k + t is interior frame
 //            t of window w; (2) the el + er frames of every window that touch its own reflect padding are computed by the frame-subset
 //            instances straight into the dense head input; (3) rec_assemble_kernel copies every window's interior run out of the pool.
@@ -13,35 +13,12 @@
 
 namespace {
 
-struct RecPlan {
-    int T = 0, k = 0, el = 0, er = 0;
-    bool shared = false;
-};
+using RecPlan = HopPlan;
 
-// window / hop rule and head shape (as nww_stream_open), then the route: the conditions under which plan_incremental keeps a log-mel ring
+// the rules of nww_stream_open; the route is shared exactly where a stream would keep a log-mel ring (NWW_STREAM_INC level 1)
 int rec_plan(nww_handle* h, int W, int hop, RecPlan& p) {
-    int rc = nww_check_run(h, 1);
-    if (rc) return rc;
-    if (W <= 0 || hop <= 0 || hop > W || (W % 8) || (hop % 8))
-        return fail(h, NWW_ERR_INVALID, "window and hop must be positive multiples of 8 samples with hop <= window");
-    const nww_config& c = h->cfg;
-    const int T = nww_pcm_rows(h, W);
-    const int rows = c.mel_major_features ? c.n_mels : T, cols = nww_raw_head(c) ? c.in_cols : c.mel_major_features ? T : c.n_mels;
-    if (T <= 0 || rows != c.in_rows || cols != c.in_cols)
-        return fail(h, NWW_ERR_SHAPE, "a %d-sample window gives (%d,%d) features but the head expects (%d,%d)", W, rows, cols, c.in_rows, c.in_cols);
-    p = RecPlan{};
-    p.T = T;
-    if (!nww_knobs().rec_shared || nww_raw_head(c)) return NWW_OK;
-    const bool frames_major = !c.mel_major_features || h->e2e_transposed;
-    static const int mel_env = 2;
-    const int hl = h->fe.hop;
-    if (!frames_major || !fe2_subset_supported(h->fe, mel_env) || hop % hl != 0) return NWW_OK;
-    const int k = hop / hl;
-    int el, er;
-    nww_edge_frames(h->fe, T, W, el, er);
-    if (T - er - k <= el) return NWW_OK;                      // a hop replaces (nearly) the whole window: nothing to share
-    p.k = k; p.el = el; p.er = er; p.shared = true;
-    return NWW_OK;
+    const int rc = nww_check_run(h, 1);
+    return rc ? rc : nww_window_plan(h, W, hop, nww_knobs().rec_shared ? 1 : 0, p);
 }
 
 long long rec_count(long long n_samples, int W, int hop) { return n_samples < W ? 0 : 1 + (n_samples - W) / hop; }
@@ -76,7 +53,9 @@ int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B
     // (3) the interior runs
     hipError_t e = launch_rec_assemble(h->d_rec_pool, h->d_logmel, B, p.T, c.n_mels, p.k, p.el, p.er, s);
     if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'rec_assemble' failed: %s", hipGetErrorString(e));
-    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, nullptr, 0, nullptr, c.mel_major_features != 0);
+    RunOpts o;
+    o.x_frames_major = c.mel_major_features != 0;
+    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, o);
 }
 
 int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,

@@ -143,3 +143,41 @@ def test_incremental_hops_equal_window_rescoring(golden_frontend, case):
             assert np.array_equal(pr, wantp)
         m.stream_reset()
     m.stream_close(); m.close()
+
+
+@pytest.mark.gpu
+def test_stream_reopen_on_one_handle(golden_frontend):
+    """The life cycle of a handle's stream batch: opened, opened again WITHOUT a close (other stream count, other hop: other rings and
+    kept rows), closed.  Every full-window hop of either batch is bit-identical to `forward_pcm` on that stream's last window (the
+    contract of test_incremental_hops_equal_window_rescoring); after the close a push fails and a plain forward still scores."""
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel
+    from nanowakeword_amd.synth import synth_state_dict
+    g = golden_frontend
+    cfg = HeadConfig("crnn", (101, 64))
+    m = HipModel(cfg, FrontendConfig(), state_dict=synth_state_dict(cfg), window=g["window"], mel_fb=g["fb64"])
+    W, full = 16000, 0
+    for S, hop, n_hops in ((3, 1280, 16), (2, 640, 30)):
+        streams = np.stack([synth_pcm("speechlike" if s % 2 else "noise", 1, hop * n_hops, seed=900 + 11 * s + hop)[0] for s in range(S)])
+        m.stream_open(S, W, hop)
+        assert m.stream_filled() == 0
+        hist = np.zeros((S, 0), np.int16)
+        for i in range(n_hops):
+            chunk = np.ascontiguousarray(streams[:, i * hop:(i + 1) * hop])
+            hist = np.concatenate([hist, chunk], axis=1)[:, -W:]
+            lg, pr = m.stream_push(chunk)
+            if hist.shape[1] < W:
+                assert not lg.any() and not pr.any()
+                continue
+            want, wantp = m.forward_pcm(np.ascontiguousarray(hist))
+            assert np.array_equal(lg, want), (S, hop, i, np.abs(lg - want).max())
+            assert np.array_equal(pr, wantp)
+            full += 1
+    assert full == 4 + 6                                      # 13 of 16 and 25 of 30 hops fill the window
+    m.stream_close()
+    assert m.stream_filled() == 0
+    with pytest.raises(RuntimeError, match="no open stream batch"):
+        m.stream_push(chunk)
+    lg, pr = m.forward_pcm(np.ascontiguousarray(hist))
+    assert np.array_equal(lg, want) and np.array_equal(pr, wantp) and np.isfinite(lg).all()
+    m.close()
