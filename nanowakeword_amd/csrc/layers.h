@@ -154,8 +154,7 @@ bool mha_h2_supported(int T, int D, int n_head);
 hipError_t launch_mha_h2(const float* qkv, float* out, int B, int T, int D, int n_head, int cus, hipStream_t s, int head_major = 0);
 // [B][C][H][W] -> [B][W][C*H]  (CRNN: sequence over W, features C*H; architectures.py:272-276)
 hipError_t launch_crnn_seq(const float* in, float* out, int B, int C, int H, int W, hipStream_t s);
-// out[f][kx][ky] = w[f][ky][kx] for nfilters 3x3 filters; [B][R][C] -> [B][C][R]
-hipError_t launch_transpose3x3(const float* w, float* out, int nfilters, hipStream_t s);
+// [B][R][C] -> [B][C][R]
 hipError_t launch_transpose_planes(const float* in, float* out, int B, int R, int C, hipStream_t s);
 
 // Tail of every head in ONE launch: emb = x We^T + be  (the head's last Linear, written to `emb`),

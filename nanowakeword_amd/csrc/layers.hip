@@ -683,20 +683,7 @@ hipError_t launch_layernorm_parts(const float* parts, int nparts, size_t part_st
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------ transposes (E2E head on the transposed plane)
-// 3x3 filters with their taps transposed: out[f][kx][ky] = w[f][ky][kx] (a convolution of the transposed plane with these
-// gives the transposed result of the original convolution)
-__global__ void __launch_bounds__(256) transpose3x3_kernel(const float* __restrict__ w, float* __restrict__ out, int n9) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n9) return;
-    const int f = idx / 9, t = idx - f * 9, ky = t / 3, kx = t - ky * 3;
-    out[f * 9 + kx * 3 + ky] = w[idx];
-}
-hipError_t launch_transpose3x3(const float* w, float* out, int nfilters, hipStream_t s) {
-    const int n9 = nfilters * 9;
-    hipLaunchKernelGGL(transpose3x3_kernel, dim3((n9 + 255) / 256), dim3(256), 0, s, w, out, n9);
-    return hipGetLastError();
-}
+// ------------------------------------------------------------------------------------------ transpose (E2E head on the transposed plane)
 // [B][R][C] -> [B][C][R] through a 32 x 33 LDS tile
 __global__ void __launch_bounds__(256) transpose_planes_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int C) {
     __shared__ float tile[32][33];

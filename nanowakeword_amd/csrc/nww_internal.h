@@ -2,7 +2,8 @@
 // device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_weights.hip: state_dict spec
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
 // nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
-// stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two).
+// stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); plan_host.h: the
+// planner's arithmetic on the weights' values (host-only too, used by nww_plan.hip and nww_weights.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "../../include/nww.h"
 #include "fe_tables.h"
 #include "stream_plan.h"
+#include "plan_host.h"
 #include "frontend.h"
 #include "layers.h"
 #include "trunk.h"
@@ -38,13 +40,6 @@
 // rows of the Transformer's positional-encoding buffer model.pos_encoder.pe [5000][1][d_model] (PositionalEncoding max_len,
 // architectures.py:31)
 #define NWW_PE_MAX_LEN 5000
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-    bool loaded = false;
-    size_t dev_off = 0;     // float offset in the weight arena
-};
 
 struct Step {
     std::string name;
@@ -113,6 +108,7 @@ struct nww_handle {
     std::map<std::string, HostTensor> tensors;     // required + optional + derived
     bool finalized = false;
     float* d_weights = nullptr;
+    std::vector<float> h_weights;  // the arena's host image, offset for offset: what the planner reads weight values from; held while nww_finalize runs
     FeTables* d_tables = nullptr;
     Fe2MelPlan* d_melplan = nullptr;
     int mel_max_taps = 0;          // longest filter support of the mel filterbank
@@ -206,9 +202,11 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
 void nww_recording_free(nww_handle* h);        // nww_recording.hip
-void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next six: what nww_finalize does to the loaded weights before it plans
+void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next eight: what nww_finalize does to the loaded weights before it plans
+void balance_channel_gains(nww_handle* h);
 void fold_batchnorms(nww_handle* h);
 void transpose_depthwise(nww_handle* h);
+void transpose_e2e_filters(nww_handle* h);
 void fold_quartznet(nww_handle* h);
 void fold_raw_frontend(nww_handle* h);
 void fold_raw_backbone(nww_handle* h);

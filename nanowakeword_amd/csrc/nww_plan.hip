@@ -15,6 +15,7 @@ const Knobs& nww_knobs() {
     }();
     return k;
 }
+double f16_range_factor() { return std::ldexp(1.0, nww_knobs().f16_range_log2); }      // plan_host.h: F16Range's window, from its knob
 
 // ------------------------------------------------------------------------------------------ plan helpers
 namespace {
@@ -58,42 +59,19 @@ struct PlanCtx {
     template <class Launch> void* pack_one(size_t bytes, Launch&& launch) { Packs pk(*this); void* d = pk.pack(bytes, launch); pk.commit(); return d; }
 };
 
-// ---- two-term binary16 arithmetic (NWW_ARITH_F16X3): plan-time bounds and power-of-two scales
-// device array -> host (plan time only; pack kernels of own_stream may still be writing derived arrays)
+// ---- two-term binary16 arithmetic (NWW_ARITH_F16X3): plan-time bounds and power-of-two scales (the arithmetic itself: plan_host.h)
+// n values of the weight arena at device pointer d, read from the arena's host image (nww_handle::h_weights; no HIP call); an absent
+// tensor (d = nullptr: a bias or BatchNorm a layer does not have) reads as zeros.  A pointer that is not the arena's is a programming
+// error: nww_finalize fails with it
 std::vector<float> f16_fetch(nww_handle* h, const float* d, size_t n) {
-    std::vector<float> v(n, 0.0f);
-    if (d && n) {
-        (void)hipStreamSynchronize(h->own_stream);
-        if (hipMemcpy(v.data(), d, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) v.assign(n, INFINITY);
+    if (!d) return std::vector<float>(n, 0.0f);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d), a0 = reinterpret_cast<uintptr_t>(h->d_weights);
+    const size_t size = h->h_weights.size(), off = a >= a0 ? (size_t)(a - a0) / sizeof(float) : size + 1;
+    if ((a - a0) % sizeof(float) != 0 || off > size || n > size - off) {
+        if (h->plan_error.empty()) h->plan_error = "plan-time read of " + std::to_string(n) + " weights outside the weight arena";
+        return std::vector<float>(n, 0.0f);
     }
-    return v;
-}
-double f16_pow2_floor(double x) { int e; (void)std::frexp(x, &e); return std::ldexp(1.0, e - 1); }      // largest power of two <= x
-// scale that keeps |v| <= bound inside the binary16 range (65504), with 2 % to spare for the host / device difference of the bound
-float f16_scale(double bound) {
-    if (!(bound > 1e-30)) bound = 1e-30;
-    if (!(bound < 1e30)) return 0.0f;                             // no usable bound
-    double s = f16_pow2_floor(65504.0 / (bound * 1.02));
-    if (s > 1099511627776.0) s = 1099511627776.0;                // 2^40
-    return (float)s;
-}
-float f16_wscale(const std::vector<float>& w) {                   // the largest weight lands in [2^14, 2^15)
-    double m = 0;
-    for (float x : w) m = std::fmax(m, std::fabs((double)x));
-    return f16_scale(m * 2.0);
-}
-// |act((sum_k w[c][k] x[k] + b[c]) al[c] + be[c])| <= max_c (sum_k |w[c][k]| bound + |b[c]|) |al[c]| + |be[c]| for ReLU / GELU / SiLU
-double f16_layer_bound(const std::vector<float>& w, int Cout, int K, const std::vector<float>& b, bool has_b,
-                       const std::vector<float>& al, const std::vector<float>& be, bool has_bn, double in_bound) {
-    double worst = 0;
-    for (int c = 0; c < Cout; ++c) {
-        double t = 0;
-        for (int k = 0; k < K; ++k) t += std::fabs((double)w[(size_t)c * K + k]);
-        t = t * in_bound + (has_b ? std::fabs((double)b[c]) : 0.0);
-        if (has_bn) t = t * std::fabs((double)al[c]) + std::fabs((double)be[c]);
-        worst = std::fmax(worst, t);
-    }
-    return worst;
+    return std::vector<float>(h->h_weights.begin() + off, h->h_weights.begin() + off + n);
 }
 // |LayerNorm(x)_k| <= sqrt(D) |w_k| + |b_k| whatever x holds: a bound on a LayerNorm's output from its weights alone
 double f16_ln_bound(nww_handle* h, const float* w, const float* b, int D) {
@@ -106,92 +84,8 @@ bool f16_all_nonneg(nww_handle* h, const float* d, int n) {      // folded-BN fa
     for (float v : f16_fetch(h, d, n)) if (!(v >= 0.0f)) return false;
     return true;
 }
-// scale of the LayerNorm'd rows that the ffn_x3 epilogues sum exactly over time: |LayerNorm| x scale <= 2^36; 0 = no usable bound
-float f16_mean_scale(double bound) {
-    const float s = bound < 1e30 ? (float)f16_pow2_floor(68719476736.0 / std::fmax(bound, 1e-30)) : 0.0f;
-    return s > 0.0f && std::isfinite(s) ? s : 0.0f;
-}
 
-// A tensor's plan-time range: a BOUND on its magnitude (what the scale is derived from) and a rough TYPICAL magnitude.  Two binary16
-// terms hold 22-23 bits of a value down to 2^-17 of the scaled bound; a bound that is more pessimistic than that against the values
-// that matter would cost precision silently - so a layer takes the two-term form only when bound <= 2^16 typ (typ-sized values then
-// sit at >= 2^-1 after scaling, one bit above where `lo` starts to lose bits), and otherwise stays on
-// the three-term bf16 form (which has float32's range and needs no bound).  typ: the head's features ~ 32 (dB values), a layer's
-// output ~ sqrt(sum_k w^2) typ_in (uncorrelated terms; |folded-BN alpha| applied) - order-of-magnitude, which is all the guard needs.
-// how far above the typical magnitude a worst-case bound may lie: 2^16 leaves typical values 22+ significant bits in two binary16 terms.
-// NWW_F16_RANGE_LOG2 (A/B and test knob): a larger exponent lets deeper stages take the two-term kernels at reduced precision of small values
-inline double f16_range_factor() {
-    return std::ldexp(1.0, nww_knobs().f16_range_log2);
-}
-struct F16Range {
-    double bound = 0.0, typ = 0.0;
-    std::vector<double> ch;                               // the typical magnitude per channel (f16_rows_typ); empty: only the mean is known
-    bool ok() const { return bound > 0.0 && typ > 0.0 && bound <= typ * f16_range_factor(); }
-};
-// The mean over the channels (f16_layer_typ) cannot see a model whose channel gains spread: a channel whose gain is G times the others' (and
-// whose weights in the next layer are 1 / G) puts G / Cout into the mean and hides the others, which then sit G below the bound.  So a
-// plan-time-scaled operand is also held against what each CONSUMER ROW sees of it.  Per row co of the layer that reads the operand:
-// sig2 = sum_q w_q^2 typ_q^2 over the contraction (typ_q: the typical magnitude of the input channel of index q) and norm2 = sum_q w_q^2.
-// The operand's absolute error (2^-25 / scale on a value far below the bound) reaches row co through the row's 2-norm, so the operand's
-// magnitude as co sees it is sqrt(sig2 / norm2); a row with no weight reads nothing and a channel no row reads weighs nothing.  The
-// smallest of those is held against the bound: within 2^4 f16_range_factor() (2^20: the quietest row keeps 20 bits, 1e-6; taken against
-// the quietest row and not a mean, hence the 2^4).  Used by the raw frontend's planes, add_trunk, add_conv_mfma and fc1's operand.
-struct F16Rows { std::vector<double> sig2, norm2; double wmax = 0.0; };
-// w_at(q, co): the weight of row co at contraction index q; ch_of(q): the input channel of index q
-template <class WAt, class ChOf>
-F16Rows f16_rows_moments(int Cout, int K, WAt&& w_at, ChOf&& ch_of, const std::vector<double>& typ_in) {
-    F16Rows m;
-    m.sig2.assign(Cout, 0.0); m.norm2.assign(Cout, 0.0);
-    for (int q = 0; q < K; ++q) {
-        const double t = typ_in[ch_of(q)];
-        for (int co = 0; co < Cout; ++co) {
-            const double w = (double)w_at(q, co), w2 = w * w;
-            m.norm2[co] += w2; m.sig2[co] += w2 * t * t;
-            m.wmax = std::fmax(m.wmax, std::fabs(w));
-        }
-    }
-    return m;
-}
-double f16_rows_seen(const F16Rows& m) {                 // the operand as its quietest consumer row sees it; INFINITY: no row reads it
-    double seen = INFINITY;
-    for (size_t co = 0; co < m.norm2.size(); ++co) if (m.norm2[co] > 0.0) seen = std::fmin(seen, std::sqrt(m.sig2[co] / m.norm2[co]));
-    return seen;
-}
-bool f16_rows_ok(double bound, const F16Rows& m) {
-    const double seen = f16_rows_seen(m);
-    return seen < INFINITY && bound <= seen * std::ldexp(f16_range_factor(), 4);
-}
-// The weights' side of the same thing: one power of two per tensor puts its largest weight in [2^14, 2^15), and a weight's `lo` term keeps
-// its 11 bits down to 2^-3 - so every row's RMS weight has to lie within 2^17 of the largest weight (a convolution without a BatchNorm whose
-// one output channel is G times the others' carries G in its own rows).  Conservative on purpose: one nearly dead row (pruned to 2^-17 of
-// the largest weight but not to zero) sends the layer to three terms although its lost bits cannot matter - the result stays right, the
-// step is slower; a row of exact zeros is exempt
-bool f16_rows_weights_ok(const F16Rows& m, int K) {
-    for (size_t co = 0; co < m.norm2.size(); ++co)
-        if (m.norm2[co] > 0.0 && m.wmax > std::sqrt(m.norm2[co] / K) * 131072.0) return false;
-    return true;
-}
-// the rows' outputs, per channel: typ_co = sqrt(sig2 + b^2), through a folded BatchNorm sqrt(sig2 al^2 + (b al + be)^2)
-std::vector<double> f16_rows_typ(const F16Rows& m, const std::vector<float>& b, bool has_b, const std::vector<float>& al,
-                                 const std::vector<float>& be, bool has_bn) {
-    std::vector<double> typ(m.sig2.size(), 0.0);
-    for (size_t co = 0; co < typ.size(); ++co) {
-        const double bb = has_b ? (double)b[co] : 0.0;
-        typ[co] = has_bn ? std::sqrt(m.sig2[co] * (double)al[co] * (double)al[co] + (bb * (double)al[co] + (double)be[co]) * (bb * (double)al[co] + (double)be[co]))
-                         : std::sqrt(m.sig2[co] + bb * bb);
-    }
-    return typ;
-}
 const F16Range F16_FEATURES{NWW_F16_FEATURE_BOUND, 32.0};
-double f16_layer_typ(const std::vector<float>& w, int Cout, int K, const std::vector<float>& al, bool has_bn, double typ_in) {
-    double acc = 0;
-    for (int c = 0; c < Cout; ++c) {
-        double q = 0;
-        for (int k = 0; k < K; ++k) q += (double)w[(size_t)c * K + k] * (double)w[(size_t)c * K + k];
-        acc += std::sqrt(q) * (has_bn ? std::fabs((double)al[c]) : 1.0);
-    }
-    return acc / (Cout > 0 ? Cout : 1) * typ_in;
-}
 
 // a step's input / output: one of the named selectors above or a workspace buffer
 inline const float* src(Run& r, int id) { return id == BUF_X ? r.x : id == BUF_EMB ? r.emb : id == BUF_HID ? r.hid : r.buf[id]; }
@@ -452,18 +346,15 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
     const int enabled = nww_knobs().conv_mfma, x3_enabled = nww_knobs().conv3_x3;
     // the input's bound against what this stage's quietest row sees of its channels (f16_rows_ok), the rows against their largest weight
     F16Rows rows;
+    const auto hw = p.h->f16 && in_bound > 0.0 ? f16_fetch(p.h, w, (size_t)Cout * Cin * 9) : std::vector<float>();
     if (p.h->f16 && in_bound > 0.0 && (int)o.in_range.ch.size() == Cin) {
-        const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
         rows = f16_rows_moments(Cout, Cin * 9, [&](int q, int co) { return hw[(size_t)co * Cin * 9 + q]; }, [](int q) { return q / 9; }, o.in_range.ch);
         if (!(f16_rows_ok(in_bound, rows) && f16_rows_weights_ok(rows, Cin * 9))) in_bound = 0.0;
     }
     // 64 input channels (a fourth CRNN stage): conv3_x3's wide instance - two-term arithmetic on a bounded input only
     bool wide = Cin == 64 && enabled && x3_enabled && pool && o.avg_ow == 0 && !o.avg_y && p.h->conv_products == 6 && p.h->f16 && in_bound > 0.0 &&
                 Cout % 32 == 0 && conv3_x3_wide_fits(Cin, H, W, Cout);
-    if (wide) {
-        const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
-        if (f16_scale(in_bound) <= 0.0f || f16_wscale(hw) <= 0.0f) wide = false;
-    }
+    if (wide && (f16_scale(in_bound) <= 0.0f || f16_wscale(hw) <= 0.0f)) wide = false;
     // more than 32 input channels without a usable bound (the worst-case bound of a fourth stage is usually too loose for two terms): the
     // 32-channel three-term instance once per 32 input channels - every pass but the last leaves raw, un-pooled sums in a scratch buffer, the
     // next one starts its accumulators from them (k-split; the planes of such stages are a few hundred pixels)
@@ -516,7 +407,6 @@ bool add_conv_mfma(PlanCtx& p, const std::string& name, int in_id, int out_id, i
         // NWW_ARITH_F16X3: two binary16 terms when the input is bounded (the fused trunk's plan-time bound)
         float h2_in = 0.0f, h2_w = 0.0f;
         if (p.h->f16 && in_bound > 0.0) {
-            const auto hw = f16_fetch(p.h, w, (size_t)Cout * Cin * 9);
             h2_in = f16_scale(in_bound); h2_w = f16_wscale(hw);
             if (o.out_range && h2_in > 0.0f && h2_w > 0.0f) {
                 const auto hal = f16_fetch(p.h, alpha, Cout), hbe = f16_fetch(p.h, beta, Cout), hbi = f16_fetch(p.h, bias, Cout);
@@ -631,6 +521,8 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
             if (fold && dir == 0) continue;                  // the forward recurrence is launched after the reverse projection
             const int in_T = T;
             const float* whh_f = fold ? p.W(prefix + ".weight_hh_l" + std::to_string(l)) : whh;
+            // (from the tensor itself, before the padded image takes its place: the any-width kernel reads neither w_scale nor products)
+            const float w_scale = products == 3 ? f16_wscale(f16_fetch(p.h, whh_f, (size_t)G * H * H)) : 1.0f;
             // widths the register-resident / 32-units-per-wave kernels do not take: zero-padded weight rows for the any-width kernel
             int ldw = 0;
             if (H % 4 != 0 || H > 256) {
@@ -640,7 +532,6 @@ void add_bigru_last(PlanCtx& p, const std::string& prefix, int in_id, int T, int
             const float* bhh_f = fold ? p.W(prefix + ".bias_hh_l" + std::to_string(l)) : bhh;
             const std::string nm = fold ? (G == 4 ? "lstm:" : "gru:") + prefix + "_l" + std::to_string(l) + " + first reverse step"
                                         : (G == 4 ? "lstm:" : "gru:") + prefix + sfx;
-            const float w_scale = products == 3 ? f16_wscale(f16_fetch(p.h, whh_f, (size_t)G * H * H)) : 1.0f;
             const int products_l = (products == 3 && !(w_scale > 0.0f)) ? p.h->conv_products : products;
             const void* w_packed = nullptr;
             if (streamed && products_l == 3 && ldw == 0) {
@@ -965,14 +856,9 @@ bool plan_e2e_dnn_transposed(PlanCtx& p) {
     if (!e2e_transposed_ok(p, Hh, Ww)) return false;
     const size_t steps_before = h->plan.size();
     const int Ht = Ww, Wt = Hh;       // the plane the kernels see: (frames, n_mels)
-    const int nf[3] = {16, 32 * 16, 64 * 32};
-    PlanCtx::Packs pk(p);                         // the three transposed weights in one allocation, kept only with the plan
-    float* wt = static_cast<float*>(pk.alloc((size_t)(nf[0] + nf[1] + nf[2]) * 9 * sizeof(float)));
-    if (!wt) return false;
-    float* wts[3] = {wt, wt + (size_t)nf[0] * 9, wt + (size_t)(nf[0] + nf[1]) * 9};
-    for (int i = 0; i < 3; ++i)
-        if (launch_transpose3x3(p.W("model.conv_block." + std::to_string(4 * i) + ".weight"), wts[i], nf[i], h->own_stream) != hipSuccess)
-            return false;
+    // the three filters with their taps transposed (transpose_e2e_filters, nww_weights.hip)
+    const float* wts[3] = {p.W("model.conv_block.0.weight_t"), p.W("model.conv_block.4.weight_t"), p.W("model.conv_block.8.weight_t")};
+    if (!wts[0] || !wts[1] || !wts[2]) return false;
     h->e2e_transposed = true;
     p.need(2, (size_t)Hh * Ww);
     p.add("transpose:mel-major features -> frames-major (skipped after the frontend)", [=](Run& r) {
@@ -993,7 +879,6 @@ bool plan_e2e_dnn_transposed(PlanCtx& p) {
     ConvMfmaOpts co; co.avg_kw = kw4; co.avg_sw = sw4; co.avg_ow = 4; co.avg_y = 1; co.in_range = tbound;
     if (!add_conv_mfma(p, "model.conv_block.8 (transposed plane)", 1, 0, 32, 64, h3, w3, wts[2], p.W("model.conv_block.8.bias"),
                        p.W("model.conv_block.9.alpha"), p.W("model.conv_block.9.beta"), act, 0, co)) return undo();
-    pk.commit();
     GemmOpts bn1; bn1.alpha = p.W("model.bn1.alpha"); bn1.beta = p.W("model.bn1.beta");
     add_gemm(p, "fc1+bn1", 0, 1, 1, 128, 256, p.W("model.fc1.weight"), p.W("model.fc1.bias"), act, bn1);
     set_tail(p, "out", 1, 128, p.W("model.out.weight"), p.W("model.out.bias"));
@@ -1772,96 +1657,6 @@ void plan_tail(PlanCtx& p) {
     }
 }
 
-// ---- channel gains balanced at load time (two-term arithmetic, ReLU heads with a plan-time-scaled conv trunk: cnn, crnn, e2e_dnn)
-// One power of two per TENSOR serves conv1's and conv2's outputs, so a channel whose gain is G times the others' pushes them log2 G bits
-// down the operand, and the range guard (F16Range, f16_rows_ok) then has to send the layer that reads it to three terms.  ReLU and the
-// pools are positively homogeneous: channel c of a layer x s_c and the next layer's weights on c / s_c, s_c a power of two, is the same
-// function with the same float32 bits.  So a channel whose worst-case bound lies 2^4 or more off the layer's median channel (the upper
-// median over the channels that count, see below) is given the
-// power of two that brings it next to the median - through the BatchNorm's weight and bias where the layer has one (the fold sees them),
-// else through the convolution's row and bias - before the BatchNorms are folded and the arena is uploaded.  Ordinary models (channel
-// bounds within a few x of each other) are not touched; GELU / SiLU heads cannot be (the guard decides for them).  -> the layer's bound after
-struct BalanceLayer { HostTensor *w = nullptr, *b = nullptr, *g = nullptr, *beta = nullptr, *mean = nullptr, *var = nullptr; };
-double balance_channels(const BalanceLayer& L, const std::vector<HostTensor*>& consumers, double in_bound) {
-    const int Cout = (int)L.w->shape[0], K = (int)(L.w->data.size() / Cout);
-    std::vector<double> bound(Cout, 0.0);
-    for (int c = 0; c < Cout; ++c) {
-        double t = 0.0;
-        for (int k = 0; k < K; ++k) t += std::fabs((double)L.w->data[(size_t)c * K + k]);
-        t = t * in_bound + (L.b ? std::fabs((double)L.b->data[c]) : 0.0);
-        if (L.g) {
-            const double al = (double)L.g->data[c] / std::sqrt((double)L.var->data[c] + 1e-5), be = (double)L.beta->data[c] - (double)L.mean->data[c] * al;
-            t = t * std::fabs(al) + std::fabs(be);
-        }
-        bound[c] = t;
-    }
-    // what a channel is worth to the layer behind it: its bound times the 2-norm of the weights that read it.  A channel worth less than 2^-8
-    // of the layer's best (a nearly dead BatchNorm channel, a pruned column) is neither moved nor counted: the median is taken over the rest
-    std::vector<double> worth(Cout, 0.0);
-    double best = 0.0;
-    for (int c = 0; c < Cout; ++c) {
-        double q = 0.0;
-        for (HostTensor* W : consumers) {
-            const size_t N = (size_t)W->shape[0], Kc = W->data.size() / N, per = Kc / Cout;
-            for (size_t n = 0; n < N; ++n)
-                for (size_t j = 0; j < per; ++j) { const double v = (double)W->data[n * Kc + (size_t)c * per + j]; q += v * v; }
-        }
-        worth[c] = bound[c] * std::sqrt(q);
-        if (std::isfinite(worth[c])) best = std::fmax(best, worth[c]);
-    }
-    std::vector<double> sorted;
-    for (int c = 0; c < Cout; ++c) if (worth[c] > 0.0 && worth[c] >= best * 0.00390625) sorted.push_back(bound[c]);
-    std::sort(sorted.begin(), sorted.end());
-    const double med = sorted.empty() ? 0.0 : sorted[sorted.size() / 2];
-    double worst = 0.0;
-    for (int c = 0; c < Cout; ++c) {
-        int e = 0;
-        if (med > 0.0 && worth[c] > 0.0 && worth[c] >= best * 0.00390625 && std::isfinite(bound[c]) && std::isfinite(med)) {
-            const double l = std::log2(bound[c] / med);
-            if (std::fabs(l) >= 4.0 && std::fabs(l) <= 40.0) e = -(int)std::lround(l);
-        }
-        if (e != 0) {
-            const float s = std::ldexp(1.0f, e), r = std::ldexp(1.0f, -e);
-            if (L.g) { L.g->data[c] *= s; L.beta->data[c] *= s; }
-            else { for (int k = 0; k < K; ++k) L.w->data[(size_t)c * K + k] *= s; if (L.b) L.b->data[c] *= s; }
-            for (HostTensor* W : consumers) {                   // [N][Cout * per]: channel c is columns c per .. c per + per - 1
-                const size_t N = (size_t)W->shape[0], Kc = W->data.size() / N, per = Kc / Cout;
-                for (size_t n = 0; n < N; ++n)
-                    for (size_t j = 0; j < per; ++j) W->data[n * Kc + (size_t)c * per + j] *= r;
-            }
-        }
-        worst = std::fmax(worst, std::ldexp(bound[c], e));
-    }
-    return worst;
-}
-void balance_channel_gains(nww_handle* h) {
-    const nww_config& c = h->cfg;
-    if (!(h->f16 && h->conv_products == 6 && c.activation == ACT_RELU)) return;
-    auto T = [&](const std::string& k) -> HostTensor* { auto it = h->tensors.find(k); return it == h->tensors.end() || !it->second.loaded ? nullptr : &it->second; };
-    auto layer = [&](const std::string& conv, const std::string& bn) {
-        BalanceLayer L; L.w = T(conv + ".weight"); L.b = T(conv + ".bias");
-        if (!bn.empty()) { L.g = T(bn + ".weight"); L.beta = T(bn + ".bias"); L.mean = T(bn + ".running_mean"); L.var = T(bn + ".running_var"); }
-        return L;
-    };
-    std::vector<std::pair<BalanceLayer, HostTensor*>> links;      // a layer and the weight that reads its channels
-    if (c.head_type == NWW_HEAD_CNN) {
-        links = {{layer("model.conv1", ""), T("model.conv2.weight")}, {layer("model.conv2", ""), T("model.fc1.weight")}};
-    } else if (c.head_type == NWW_HEAD_CRNN && c.n_crnn_channels >= 3 && c.crnn_channels[0] == 16 && c.crnn_channels[1] == 32) {
-        links = {{layer("model.cnn.0", "model.cnn.1"), T("model.cnn.4.weight")}, {layer("model.cnn.4", "model.cnn.5"), T("model.cnn.8.weight")}};
-    } else if (c.head_type == NWW_HEAD_E2E_DNN) {
-        links = {{layer("model.conv_block.0", "model.conv_block.1"), T("model.conv_block.4.weight")},
-                 {layer("model.conv_block.4", "model.conv_block.5"), T("model.conv_block.8.weight")}};
-    }
-    double bound = NWW_F16_FEATURE_BOUND;
-    for (auto& lk : links) {
-        const BalanceLayer& L = lk.first;
-        if (!L.w || !lk.second || L.w->shape.empty() || (L.g && !(L.beta && L.mean && L.var))) return;
-        const size_t Cout = (size_t)L.w->shape[0], N = (size_t)lk.second->shape[0];
-        if (Cout == 0 || N == 0 || L.w->data.size() % Cout || (lk.second->data.size() / N) % Cout) return;
-        bound = balance_channels(L, {lk.second}, bound);
-    }
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ finalize
@@ -1874,9 +1669,11 @@ extern "C" int nww_finalize(nww_handle* h) {
     balance_channel_gains(h);
     fold_batchnorms(h);
     if (h->cfg.head_type == NWW_HEAD_BCRESNET) transpose_depthwise(h);
+    if (h->cfg.head_type == NWW_HEAD_E2E_DNN) transpose_e2e_filters(h);
     if (h->cfg.head_type == NWW_HEAD_QUARTZNET || h->cfg.head_type == NWW_HEAD_E2E_QUARTZNET) fold_quartznet(h);
     if (nww_raw_head(h->cfg)) fold_raw_frontend(h);
     if (h->cfg.head_type == NWW_HEAD_E2E_CNN) fold_raw_backbone(h);
+    struct ArenaImage { nww_handle* h; ~ArenaImage() { std::vector<float>().swap(h->h_weights); } } image{h};      // held until this returns
     int rc = upload_weight_arena(h);
     if (rc == NWW_OK) rc = build_frontend_tables(h);
     if (rc != NWW_OK) return rc;

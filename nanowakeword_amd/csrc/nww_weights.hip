@@ -209,6 +209,35 @@ void nww_build_spec(nww_handle* h) {
 }
 
 // ------------------------------------------------------------------------------------------ weights and frontend tables
+// channel gains balanced at load time (balance_channels, plan_host.h), before the BatchNorms are folded: the conv trunks of the ReLU heads
+void balance_channel_gains(nww_handle* h) {
+    const nww_config& c = h->cfg;
+    if (!(h->f16 && h->conv_products == 6 && c.activation == ACT_RELU)) return;
+    auto T = [&](const std::string& k) -> HostTensor* { auto it = h->tensors.find(k); return it == h->tensors.end() || !it->second.loaded ? nullptr : &it->second; };
+    auto layer = [&](const std::string& conv, const std::string& bn) {
+        BalanceLayer L; L.w = T(conv + ".weight"); L.b = T(conv + ".bias");
+        if (!bn.empty()) { L.g = T(bn + ".weight"); L.beta = T(bn + ".bias"); L.mean = T(bn + ".running_mean"); L.var = T(bn + ".running_var"); }
+        return L;
+    };
+    std::vector<std::pair<BalanceLayer, HostTensor*>> links;      // a layer and the weight that reads its channels
+    if (c.head_type == NWW_HEAD_CNN) {
+        links = {{layer("model.conv1", ""), T("model.conv2.weight")}, {layer("model.conv2", ""), T("model.fc1.weight")}};
+    } else if (c.head_type == NWW_HEAD_CRNN && c.n_crnn_channels >= 3 && c.crnn_channels[0] == 16 && c.crnn_channels[1] == 32) {
+        links = {{layer("model.cnn.0", "model.cnn.1"), T("model.cnn.4.weight")}, {layer("model.cnn.4", "model.cnn.5"), T("model.cnn.8.weight")}};
+    } else if (c.head_type == NWW_HEAD_E2E_DNN) {
+        links = {{layer("model.conv_block.0", "model.conv_block.1"), T("model.conv_block.4.weight")},
+                 {layer("model.conv_block.4", "model.conv_block.5"), T("model.conv_block.8.weight")}};
+    }
+    double bound = NWW_F16_FEATURE_BOUND;
+    for (auto& lk : links) {
+        const BalanceLayer& L = lk.first;
+        if (!L.w || !lk.second || L.w->shape.empty() || (L.g && !(L.beta && L.mean && L.var))) return;
+        const size_t Cout = (size_t)L.w->shape[0], N = (size_t)lk.second->shape[0];
+        if (Cout == 0 || N == 0 || L.w->data.size() % Cout || (lk.second->data.size() / N) % Cout) return;
+        bound = balance_channels(L, {lk.second}, bound);
+    }
+}
+
 // every BatchNorm folded (eval): alpha = w/sqrt(var+eps), beta = b - mean*alpha (PyTorch CPU kernel form)
 void fold_batchnorms(nww_handle* h) {
     std::vector<std::string> bn_prefixes;
@@ -245,6 +274,23 @@ void transpose_depthwise(nww_handle* h) {
         wt.data.resize((size_t)9 * C);
         for (int ch = 0; ch < C; ++ch)
             for (int tap = 0; tap < 9; ++tap) wt.data[(size_t)tap * C + ch] = w.data[(size_t)ch * 9 + tap];
+        wt.loaded = true;
+        h->tensors[k + "_t"] = wt;
+    }
+}
+
+// E2E head on the transposed plane: the three 3x3 filters with their taps transposed, out[f][kx][ky] = w[f][ky][kx] (a convolution of
+// the transposed plane with these gives the transposed result of the original convolution)
+void transpose_e2e_filters(nww_handle* h) {
+    for (int i = 0; i < 3; ++i) {
+        const std::string k = "model.conv_block." + std::to_string(4 * i) + ".weight";
+        const HostTensor& w = h->tensors[k];
+        HostTensor wt;
+        wt.shape = w.shape;
+        wt.data.resize(w.data.size());
+        for (size_t f = 0; f + 9 <= w.data.size(); f += 9)
+            for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx) wt.data[f + kx * 3 + ky] = w.data[f + ky * 3 + kx];
         wt.loaded = true;
         h->tensors[k + "_t"] = wt;
     }
@@ -396,7 +442,8 @@ void fold_raw_backbone(nww_handle* h) {
     }
 }
 
-// every loaded tensor but the frontend's in one device arena, each 16-byte aligned
+// every loaded tensor but the frontend's in one device arena, each 16-byte aligned: assembled in its host image (nww_handle::h_weights,
+// which the planner reads the weights' values from and nww_finalize releases) and uploaded in one copy
 int upload_weight_arena(nww_handle* h) {
     size_t total = 0;
     for (auto& kv : h->tensors) {
@@ -404,12 +451,16 @@ int upload_weight_arena(nww_handle* h) {
         kv.second.dev_off = total;
         total += (kv.second.data.size() + 3) & ~(size_t)3;
     }
-    HIP_TRY(h, hipMalloc(&h->d_weights, (total + 4) * sizeof(float)));
-    for (auto& kv : h->tensors) {
+    h->h_weights.clear();
+    h->h_weights.reserve(total + 4);
+    for (const auto& kv : h->tensors) {                              // in offset order: each tensor, then zeros up to the next one
         if (!kv.second.loaded || kv.first.rfind("frontend.", 0) == 0) continue;
-        HIP_TRY(h, hipMemcpy(h->d_weights + kv.second.dev_off, kv.second.data.data(), kv.second.data.size() * sizeof(float),
-                             hipMemcpyHostToDevice));
+        h->h_weights.resize(kv.second.dev_off, 0.0f);
+        h->h_weights.insert(h->h_weights.end(), kv.second.data.begin(), kv.second.data.end());
     }
+    h->h_weights.resize(total + 4, 0.0f);
+    HIP_TRY(h, hipMalloc(&h->d_weights, h->h_weights.size() * sizeof(float)));
+    HIP_TRY(h, hipMemcpy(h->d_weights, h->h_weights.data(), h->h_weights.size() * sizeof(float), hipMemcpyHostToDevice));
     return NWW_OK;
 }
 

@@ -7,9 +7,9 @@ and `cmp` the two files.  profiles/plan_dump.txt holds the last recorded dump (w
 
     python tools/dump_plans.py --stream --out profiles/plan_dump.txt
 
-For each row of tests/test_gpu_parity.py:_F64_HEADS and each conv_arith in (default, f32, bf16x6, bf16x9) a child prints
+For each row of tests/test_gpu_parity.py:_F64_HEADS and of EXTRA_HEADS and each conv_arith in (default, f32, bf16x6, bf16x9) a child prints
 describe_plan() and one SHA-256 over the float32 logits and embedding bytes of synth_features at B = 1, 3 and 64; a combination
-the library refuses prints the refusal; the e2e_quartznet head follows on PCM.  --stream adds the CRNN head scoring a few
+the library refuses prints the refusal; the raw-PCM heads (PCM_HEADS) follow on PCM.  --stream adds the CRNN head scoring a few
 streaming hops (the ring / sequence captures of the conv stem run only there).  The knobs are read once per process, so every
 setting is a fresh child, one after another, each under its own time limit; the first child that fails ends the run.
 
@@ -31,11 +31,16 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 KNOBS = ("NWW_TRUNK", "NWW_CONV_MFMA", "NWW_CONV3_X3", "NWW_GEMM_X3", "NWW_LIN_X3", "NWW_FFN_FUSED", "NWW_ATTN_FUSED",
-         "NWW_MERGE_FUSED", "NWW_QN_FUSED", "NWW_RAW_FUSED", "NWW_MHA_MFMA", "NWW_BC_FRONT", "NWW_BC_CHAIN", "NWW_TAIL")
+         "NWW_MERGE_FUSED", "NWW_QN_FUSED", "NWW_RAW_FUSED", "NWW_CONV2S_X3", "NWW_RNN_IH_FUSED", "NWW_MHA_MFMA", "NWW_BC_FRONT", "NWW_BC_CHAIN",
+         "NWW_TAIL")
 SETTINGS = [()] + [((k, "0"),) for k in KNOBS] + [(("NWW_GEMM_X3", "2"),), (("NWW_BC_FRONT", "2"),)]
 ARITHS = ("default", "f32", "bf16x6", "bf16x9")
 BATCHES = (1, 3, 64)
 CHILD_SECONDS = 600
+# feature-path rows beside _F64_HEADS: the bi-LSTM head has no oracle.heads._NETS entry, so that test's list cannot carry it
+EXTRA_HEADS = (("rnn", (101, 64), {}, "rnn"), ("rnn", (16, 96), {}, "rnn-16x96"))
+# the raw-PCM heads: (head, what the backbone sees of a clip under the default frontend, the clip's length in samples)
+PCM_HEADS = (("e2e_quartznet", (33, 128), 8193), ("e2e_cnn", (63, 64), 4000))
 
 
 def _sha(arrays) -> str:
@@ -53,7 +58,7 @@ def child(stream: bool) -> int:
     from test_gpu_parity import _F64_HEADS, _F64_IDS
 
     feats = {}
-    for (head, shape, kw), rid in zip(_F64_HEADS, _F64_IDS):
+    for head, shape, kw, rid in [(*r, i) for r, i in zip(_F64_HEADS, _F64_IDS)] + list(EXTRA_HEADS):
         cfg = HeadConfig(head, shape, **kw)
         sd = synth_state_dict(cfg)
         for B in BATCHES:
@@ -71,19 +76,20 @@ def child(stream: bool) -> int:
             print("sha256 " + _sha(a for lg, _, emb in outs for a in (lg, emb)))
             m.close()
             sys.stdout.flush()
-    # the eleventh head reads PCM: its raw frontend's plan (frontend:* lines) and the logits of the whole model
-    cfg = HeadConfig("e2e_quartznet", (33, 128))
-    sd, pcm = synth_state_dict(cfg), synth_pcm("noise", 3, 8193)
-    for arith in ARITHS:
-        print(f"--- e2e_quartznet 33x128 conv_arith={arith}")
-        try:
-            m = HipModel(cfg, FrontendConfig(), state_dict=sd, tables="builtin", conv_arith=arith)
-        except NwwError as e:
-            print(f"refused: {e}")
-            continue
-        print(m.describe_plan().rstrip("\n"))
-        print("sha256 " + _sha((m.forward_pcm(pcm)[0], m.frontend(pcm))))
-        m.close()
+    # the raw-PCM heads: the raw frontend's plan (frontend:* lines) and the logits of the whole model
+    for head, shape, n in PCM_HEADS:
+        cfg = HeadConfig(head, shape)
+        sd, pcm = synth_state_dict(cfg), synth_pcm("noise", 3, n)
+        for arith in ARITHS:
+            print(f"--- {head} {shape[0]}x{shape[1]} conv_arith={arith}")
+            try:
+                m = HipModel(cfg, FrontendConfig(), state_dict=sd, tables="builtin", conv_arith=arith)
+            except NwwError as e:
+                print(f"refused: {e}")
+                continue
+            print(m.describe_plan().rstrip("\n"))
+            print("sha256 " + _sha((m.forward_pcm(pcm)[0], m.frontend(pcm))))
+            m.close()
     if stream:
         # the CRNN stem's third stage reads the fused trunk's rings and writes the recurrent layers' sequence rows only on this path
         S, W, hop, n_hops = 3, 16000, 1280, 18
