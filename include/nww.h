@@ -248,6 +248,49 @@ extern int nww_forward_recording_dev(nww_handle* h, const int16_t* d_pcm, int32_
 extern int nww_forward_recording(nww_handle* h, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
                           float* logits, float* probs, int32_t* n_windows_out);
 
+/* ---- gate + verifier cascades: the verifier runs on the windows the gate opens (NanoInterpreter.load_model(cascade=True)) ----
+ * Two finalized handles on one device, a small gate and the verifier, and a threshold.  The gate scores every window; a window is
+ * CLOSED exactly when (double)gate_prob < gate_threshold (nanointerpreter.py:660-669, 758-769 on float(np.float32): a NaN probability
+ * leaves the window open, a threshold <= 0 opens all, one > 1 closes all); the open windows' indices are compacted on the device in
+ * ascending order (block counts, a prefix sum, a placement pass: no atomic counter), their samples gathered into the verifier's PCM
+ * staging, the verifier run by nww_forward_pcm's own path on consecutive chunks of at most max_batch survivors (the batch entry point
+ * and the stream push: all survivors of the call as one batch), and its outputs scattered back.  Outputs are dense, one per window:
+ * the gate's probabilities bit-identical to the gate handle alone on the same input, the verifier's logits / probabilities
+ * bit-identical to nww_forward_pcm on the open windows stacked in ascending order in those chunks, and 0.0f / -INFINITY on closed
+ * windows.  With no window open the verifier is not launched.  The two handles may differ in everything but the device; the window
+ * must give each its own (in_rows, in_cols) (NWW_ERR_SHAPE, the text naming which of the two).  Handles that are not finalized, not
+ * distinct or on two devices: NWW_ERR_INVALID.  Errors go to nww_last_error(verifier); the index list, the dense outputs of the
+ * host-pointer variants and the pinned count live on the verifier's handle and grow on demand.
+ * The count of open windows is read back through one pinned 4-byte copy: every entry point synchronises `stream` ONCE, behind the
+ * gate's last pass and the select (never once per pass), and checks 0 <= n_open <= n before it sizes anything (NWW_ERR_HIP
+ * otherwise).  The verifier's launches are asynchronous on `stream` in the _dev variants; the host-pointer variants synchronise a
+ * second time before they return.  stream NULL: the verifier's own stream.  n_open_out may be NULL.  DESIGN.md 4.8c.
+ * (Declared `extern` like the recording block above: the pinned count of declarations that start a line with their return type
+ * stays 48.)                                                                                                                        */
+/* The select alone, on the caller's scores: probs [n] host -> idx_out [n_open] host (room for n entries), ascending.                  */
+extern int nww_cascade_select(nww_handle* verifier, const float* probs, int32_t n, double gate_threshold, int32_t* idx_out, int32_t* n_open_out);
+/* d_pcm [B][N] -> d_gate_probs / d_logits / d_probs [B] (d_gate_probs may be NULL; d_logits or d_probs may be NULL)                    */
+extern int nww_cascade_forward_pcm_dev(nww_handle* gate, nww_handle* verifier, const int16_t* d_pcm, int32_t B, int32_t N, double gate_threshold,
+                                float* d_gate_probs, float* d_logits, float* d_probs, int32_t* n_open_out, void* stream);
+extern int nww_cascade_forward_pcm(nww_handle* gate, nww_handle* verifier, const int16_t* pcm, int32_t B, int32_t N, double gate_threshold,
+                            float* gate_probs, float* logits, float* probs, int32_t* n_open_out);
+/* every window of a recording (the rules of nww_forward_recording*): the gate scores ALL passes first, on whichever route it plans,
+ * then one select over the nW windows, then the verifier's chunks, gathered from the recording where it lies (row_stride = hop)      */
+extern int nww_cascade_forward_recording_dev(nww_handle* gate, nww_handle* verifier, const int16_t* d_pcm, int32_t n_samples, int32_t window, int32_t hop,
+                                      int32_t max_batch, double gate_threshold, float* d_gate_probs, float* d_logits, float* d_probs,
+                                      int32_t* n_open_out, void* stream);
+/* host pointers; the recording is uploaded once, as nww_forward_recording does.  n_windows_out may be NULL.                           */
+extern int nww_cascade_forward_recording(nww_handle* gate, nww_handle* verifier, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop,
+                                  int32_t max_batch, double gate_threshold, float* gate_probs, float* logits, float* probs,
+                                  int32_t* n_windows_out, int32_t* n_open_out);
+/* S lock-step streams: only the GATE has a stream open (nww_stream_open on it, at whatever incremental level it plans); the verifier
+ * keeps no ring and scores the full windows of the open streams out of the gate's PCM ring.  Until the ring holds a window every
+ * output is 0 and the verifier is not run, as in nww_stream_push.  chunk [S][hop]; outputs [S].                                       */
+extern int nww_cascade_stream_push(nww_handle* gate, nww_handle* verifier, const int16_t* chunk, double gate_threshold, float* gate_probs,
+                            float* logits, float* probs, int32_t* n_open_out);
+extern int nww_cascade_stream_push_dev(nww_handle* gate, nww_handle* verifier, const int16_t* d_chunk, double gate_threshold, float* d_gate_probs,
+                                float* d_logits, float* d_probs, int32_t* n_open_out, void* stream);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

@@ -217,6 +217,17 @@ def recording_windows(n: int, window: int, hop: int, offset: int = 0) -> int:
     return 0 if n - offset < window else 1 + (n - offset - window) // hop
 
 
+def cascade_open(gate_probs, gate_threshold: float):
+    """Which windows a cascade's gate opens: bool array, False exactly where float(p) < gate_threshold for the float32 probability p
+    the gate wrote (the reference's `gate_score_ < gate_threshold`, nanointerpreter.py:660-669, 758-769).  The comparison is made in
+    double precision, so a probability equal to the threshold is open, a NaN is open, a threshold <= 0 opens every window and one > 1
+    closes every window.  The device's select (cascade.hip) applies the same rule."""
+    import numpy as np
+    p = np.asarray(gate_probs, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return ~(p < float(gate_threshold))
+
+
 def clip_samples(cfg: "HeadConfig", fe: "FrontendConfig") -> int:
     """The clip length a PCM head was built for, from its input_shape: the whole number of frame hops that gives its frames on the mel
     frontends (16000 for 101 centred frames), every stage's longest input on the raw-PCM heads (16000 for 250 rows at depth 2)."""

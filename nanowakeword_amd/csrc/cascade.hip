@@ -1,0 +1,132 @@
+// cascade.hip - select / gather / scatter of a gate + verifier cascade (cascade.h).  All three are small and memory-bound: a window costs
+// the select 4 bytes read and 8 written, the gather moves a survivor's window once, the scatter 8 bytes per survivor.
+#include "cascade.h"
+#include <cmath>
+
+namespace {
+
+// the reference's gate rule on float(np.float32): closed exactly when (double)p < thr, so a NaN probability is open
+__device__ __forceinline__ bool cascade_is_open(float p, double thr) { return !((double)p < thr); }
+
+// sum of v over the block's 256 threads (four waves), returned to every thread
+__device__ __forceinline__ int block_sum(int v, int* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int t = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return t;
+}
+
+// pass 1: counts[b] = open windows among block b's [b * per, min(n, (b + 1) * per))
+__global__ void __launch_bounds__(256) cascade_count_kernel(const float* __restrict__ probs, long long n, double thr, long long per,
+                                                            int32_t* __restrict__ counts) {
+    __shared__ int red[4];
+    const long long lo = (long long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    int c = 0;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) c += cascade_is_open(probs[i], thr) ? 1 : 0;
+    c = block_sum(c, red);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// pass 2: block b starts at the sum of the counts before it (every block adds them up itself: at most CASCADE_MAX_BLOCKS ints) and
+// walks its windows again, 256 at a time; a window's place is that base + the open windows of the waves before its own + those of the
+// lanes before its own (ballot + popcount).  Ascending and the same on every run: nothing depends on arrival order.
+__global__ void __launch_bounds__(256) cascade_place_kernel(const float* __restrict__ probs, long long n, double thr, long long per,
+                                                            int32_t* __restrict__ counts, int32_t* __restrict__ idx,
+                                                            float* __restrict__ fill_logits, float* __restrict__ fill_probs) {
+    __shared__ int red[4];
+    __shared__ int wcnt[4];
+    int part = 0;
+    for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) part += counts[j];
+    int base = block_sum(part, red);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) counts[CASCADE_MAX_BLOCKS] = base + counts[blockIdx.x];
+    const long long lo = (long long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long long i0 = lo; i0 < hi; i0 += 256) {       // the same trip count for the whole block
+        const long long i = i0 + threadIdx.x;
+        const bool in = i < hi;
+        const bool open = in && cascade_is_open(probs[i], thr);
+        const unsigned long long m = __ballot(open);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            const int c = wcnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (open) idx[base + before + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
+        if (in) {
+            if (fill_logits) fill_logits[i] = -INFINITY;
+            if (fill_probs) fill_probs[i] = 0.0f;
+        }
+        base += total;
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) cascade_gather16_kernel(const int16_t* __restrict__ src, const int32_t* __restrict__ idx, size_t row_stride,
+                                                               int n8, size_t total, uint4* __restrict__ dst) {
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t j = t / (size_t)n8, i = t - j * (size_t)n8;
+        dst[t] = *reinterpret_cast<const uint4*>(src + (size_t)idx[j] * row_stride + i * 8);
+    }
+}
+
+__global__ void __launch_bounds__(256) cascade_gather2_kernel(const int16_t* __restrict__ src, const int32_t* __restrict__ idx, size_t row_stride,
+                                                              int N, size_t total, int16_t* __restrict__ dst) {
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t j = t / (size_t)N, i = t - j * (size_t)N;
+        dst[t] = src[(size_t)idx[j] * row_stride + i];
+    }
+}
+
+__global__ void __launch_bounds__(256) cascade_scatter_kernel(const int32_t* __restrict__ idx, int rows, const float* __restrict__ logits,
+                                                              const float* __restrict__ probs, float* __restrict__ out_logits,
+                                                              float* __restrict__ out_probs) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= rows) return;
+    const size_t w = (size_t)idx[j];
+    if (out_logits) out_logits[w] = logits[j];
+    if (out_probs) out_probs[w] = probs[j];
+}
+
+unsigned capped_blocks(size_t total) {
+    const size_t b = (total + 255) / 256;
+    return (unsigned)(b < (size_t)1 << 20 ? b : (size_t)1 << 20);      // the gathers stride over the grid beyond 2^28 elements
+}
+
+}  // namespace
+
+hipError_t launch_cascade_select(const float* d_probs, long long n, double thr, int32_t* d_idx, int32_t* d_counts, float* fill_logits,
+                                 float* fill_probs, hipStream_t s) {
+    if (n < 1 || n > 0x7fffffffll || !d_probs || !d_idx || !d_counts) return hipErrorInvalidValue;
+    const CascadeGrid g = cascade_grid(n);
+    hipLaunchKernelGGL(cascade_count_kernel, dim3((unsigned)g.blocks), dim3(256), 0, s, d_probs, n, thr, g.per, d_counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cascade_place_kernel, dim3((unsigned)g.blocks), dim3(256), 0, s, d_probs, n, thr, g.per, d_counts, d_idx, fill_logits, fill_probs);
+    return hipGetLastError();
+}
+
+hipError_t launch_cascade_gather(const int16_t* src, const int32_t* d_idx, size_t row_stride, int N, int rows, int16_t* dst, hipStream_t s) {
+    if (N < 1 || rows < 1 || row_stride < 1 || !src || !d_idx || !dst) return hipErrorInvalidValue;
+    const bool wide = ((uintptr_t)src | (uintptr_t)dst) % 16 == 0 && row_stride % 8 == 0 && N % 8 == 0;
+    if (wide) {
+        const size_t total = (size_t)rows * (N / 8);
+        hipLaunchKernelGGL(cascade_gather16_kernel, dim3(capped_blocks(total)), dim3(256), 0, s, src, d_idx, row_stride, N / 8, total,
+                           reinterpret_cast<uint4*>(dst));
+    } else {
+        const size_t total = (size_t)rows * N;
+        hipLaunchKernelGGL(cascade_gather2_kernel, dim3(capped_blocks(total)), dim3(256), 0, s, src, d_idx, row_stride, N, total, dst);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cascade_scatter(const int32_t* d_idx, int rows, const float* logits, const float* probs, float* out_logits, float* out_probs,
+                                  hipStream_t s) {
+    if (rows < 1 || !d_idx || (out_logits && !logits) || (out_probs && !probs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cascade_scatter_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_idx, rows, logits, probs, out_logits, out_probs);
+    return hipGetLastError();
+}

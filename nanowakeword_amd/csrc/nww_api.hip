@@ -169,6 +169,7 @@ extern "C" int nww_destroy(nww_handle* h) {
     nww_stream_close(h);
     nww_emb_close(h);
     nww_recording_free(h);
+    nww_cascade_free(h);
     nww_comm_destroy(h);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);

@@ -2,6 +2,7 @@
 // device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_weights.hip: state_dict spec
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
 // nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
+// nww_cascade.hip: gate + verifier cascades (nww_cascade_*);
 // stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); plan_host.h: the
 // planner's arithmetic on the weights' values (host-only too, used by nww_plan.hip and nww_weights.hip).
 #pragma once
@@ -149,6 +150,11 @@ struct nww_handle {
     // point the recording and its [2][nW] logits / probabilities; each grown on demand
     float* d_rec_pool = nullptr; int16_t* d_rec_pcm = nullptr; float* d_rec_out = nullptr;
     size_t rec_pool_bytes = 0, rec_pcm_bytes = 0, rec_out_bytes = 0;
+    // cascade scoring (nww_cascade.hip), held by the VERIFIER's handle: the open windows' ascending indices [n], the dense [3][n] gate
+    // probabilities / logits / probabilities of the host-pointer entry points, the select's per-block counts and total, and the pinned
+    // word the count is read back through; the first two grown on demand
+    int32_t* d_cas_idx = nullptr; float* d_cas_out = nullptr; int32_t* d_cas_counts = nullptr; int32_t* pin_cas_count = nullptr;
+    size_t cas_idx_bytes = 0, cas_out_bytes = 0;
     void* comm = nullptr;          // ncclComm_t of this rank (nww_comm_init)
     unsigned char* pin_in = nullptr; unsigned char* pin_out = nullptr;   // pinned staging for small host-pointer calls
     bool pin_in_busy = false;                                            // an async copy out of pin_in may still be in flight
@@ -201,7 +207,12 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
                            size_t row_stride = 0, const RunOpts& o = RunOpts());
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
-void nww_recording_free(nww_handle* h);        // nww_recording.hip
+void nww_recording_free(nww_handle* h);        // nww_recording.hip, as the next three: what nww_cascade.hip scores a gate's recording with
+long long nww_rec_count(long long n_samples, int W, int hop);
+int nww_rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes);
+int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
+                           hipStream_t s);
+void nww_cascade_free(nww_handle* h);          // nww_cascade.hip
 void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next eight: what nww_finalize does to the loaded weights before it plans
 void balance_channel_gains(nww_handle* h);
 void fold_batchnorms(nww_handle* h);

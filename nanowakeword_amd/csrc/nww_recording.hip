@@ -91,6 +91,13 @@ int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, in
 
 }  // namespace
 
+long long nww_rec_count(long long n_samples, int W, int hop) { return rec_count(n_samples, W, hop); }
+int nww_rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes) { return rec_grow(h, p, cap, bytes); }
+int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
+                           hipStream_t s) {
+    return rec_forward_dev(h, d_pcm, n_samples, W, hop, max_batch, d_logits, d_probs, s);
+}
+
 void nww_recording_free(nww_handle* h) {
     for (void* p : {(void*)h->d_rec_pool, (void*)h->d_rec_pcm, (void*)h->d_rec_out})
         if (p) (void)hipFree(p);

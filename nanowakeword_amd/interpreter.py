@@ -22,6 +22,8 @@ from typing import Dict, List, Mapping, Optional, Union
 
 import numpy as np
 
+from .config import cascade_open
+
 N_WARMUP_PREDICTIONS = 5        # nanointerpreter.py:690,789
 PREDICTION_HISTORY = 30         # nanointerpreter.py:1002
 HOP_SAMPLES = 1280              # 80 ms @ 16 kHz (AudioFeatures.py:414)
@@ -361,8 +363,10 @@ class HipInterpreter:
         pcm[0:chunk_size], pcm[chunk_size:2 * chunk_size], ... returns as DetectionResult.scores, and the same state left behind (zeros
         until the window holds a clip, first five predictions zeroed, patience / debounce).  E2E sessions that offer run_recording
         (HipSession) score every full chunk's window in batches, the recording uploaded once: the first window starts at
-        (-clip_samples) % chunk_size.  Cascades, embedding-mode interpreters (a preprocessor) and chunk sizes or first offsets that are
-        not multiples of 8 samples take the predict() loop."""
+        (-clip_samples) % chunk_size.  A cascade takes the batch path when it is exactly a gate and a verifier whose session offers
+        run_recording_cascade and accepts the gate's session (two HipSessions on one device with the same clip length): the verifier
+        then runs only on the windows the gate opens.  Other cascades, embedding-mode interpreters (a preprocessor) and chunk sizes or
+        first offsets that are not multiples of 8 samples take the predict() loop."""
         if isinstance(pcm, str):
             with wave.open(pcm, mode="rb") as f:
                 if f.getframerate() != 16000 or f.getsampwidth() != 2 or f.getnchannels() != 1:
@@ -383,9 +387,15 @@ class HipInterpreter:
                 out[n][t] = res.scores.get(n, 0.0)
 
         n_full = len(pcm) // chunk_size
-        batch = (self.preprocessor is None and not self.is_cascade and chunk_size % 8 == 0 and n_full > 0
-                 and all(hasattr(s, "run_recording") and chunk_size <= self.e2e_clip_samples[n] and (-self.e2e_clip_samples[n]) % chunk_size % 8 == 0
-                         for n, s in self.models.items()))
+        grid = (self.preprocessor is None and chunk_size % 8 == 0 and n_full > 0
+                and all(chunk_size <= self.e2e_clip_samples[n] and (-self.e2e_clip_samples[n]) % chunk_size % 8 == 0 for n in self.models))
+        if self.is_cascade:
+            # a gate + verifier pair whose verifier session scores only the windows the gate opens (HipSession.run_recording_cascade)
+            gate_s, ver_s = self.models.get(self.gate_name), self.models.get(self.model_name)
+            batch = bool(grid and len(self.models) == 2 and gate_s is not None and ver_s is not None
+                         and hasattr(ver_s, "run_recording_cascade") and hasattr(ver_s, "cascade_accepts") and ver_s.cascade_accepts(gate_s))
+        else:
+            batch = grid and all(hasattr(s, "run_recording") for s in self.models.values())
         if not batch:
             for t in range(n_chunks):
                 keep(t, self.predict(pcm[t * chunk_size:(t + 1) * chunk_size], **kw))
@@ -393,14 +403,28 @@ class HipInterpreter:
         xi = pcm if pcm.dtype == np.int16 else pcm.astype(np.int16)
         full = np.ascontiguousarray(xi[:n_full * chunk_size])
         raw, first = {}, {}
+        if self.is_cascade:
+            # the device opens a superset of what predict() would: every window whose RAW gate probability reaches the threshold.  The
+            # loop below still gates on the gate's post-warm-up score (_gate_closed) and zeroes the verifier wherever that says closed.
+            clip = self.e2e_clip_samples[self.model_name]
+            pair = ver_s.run_recording_cascade(gate_s, full, hop=chunk_size, offset=(-clip) % chunk_size,
+                                               gate_threshold=self.cascade_config["gate_threshold"])
+            got = dict(zip((self.gate_name, self.model_name), pair))
         for n, s in self.models.items():
             clip = self.e2e_clip_samples[n]
             first[n] = -(-clip // chunk_size) - 1                 # the chunk that fills the window
-            raw[n] = np.asarray(s.run_recording(full, hop=chunk_size, offset=(-clip) % chunk_size), np.float32).reshape(-1)
+            if self.is_cascade:
+                raw[n] = np.asarray(got[n], np.float32).reshape(-1)
+            else:
+                raw[n] = np.asarray(s.run_recording(full, hop=chunk_size, offset=(-clip) % chunk_size), np.float32).reshape(-1)
             assert len(raw[n]) == max(0, n_full - first[n]), (len(raw[n]), n_full, first[n])
         for t in range(n_full):                                   # predict()'s bookkeeping, the scores looked up
             current = {}
             for n in self.models:
+                if t >= first[n] and self._gate_closed(n, current):
+                    current[n] = 0.0
+                    self.raw_scores[n] = 0.0
+                    continue
                 score = float(raw[n][t - first[n]]) if t >= first[n] else 0.0
                 self.raw_scores[n] = score
                 if len(self.prediction_buffer.get(n, ())) < N_WARMUP_PREDICTIONS:
@@ -432,6 +456,22 @@ class HipInterpreter:
     @property
     def e2e_buffer_samples(self) -> Dict[str, int]:
         return {n: w.filled for n, w in self._windows.items()}
+
+
+def _filter_streams(score: np.ndarray, history: np.ndarray, patience: int, threshold: float, debounce_time: float, hop: int):
+    """Patience or debounce (:1034-1064) on one model's scores [S] in place, against its history [rows][S] (most recent last)."""
+    nz = score != 0.0
+    if patience:
+        if history.shape[0] < patience:
+            score[nz] = 0.0
+        else:
+            tail = history[-(patience - 1):] if patience > 1 else history
+            hits = (tail >= threshold).sum(axis=0) + (score >= threshold)
+            score[nz & (hits < patience)] = 0.0
+    else:
+        k = int(math.ceil(debounce_time / (hop / 16000.0)))
+        recent = (history[-k:] >= threshold).any(axis=0) if history.shape[0] else np.zeros(len(score), bool)
+        score[nz & (score >= threshold) & recent] = 0.0
 
 
 class StreamBatch:
@@ -470,21 +510,71 @@ class StreamBatch:
                 raise ValueError("`threshold` must be provided when using `patience` or `debounce_time`.")
             if patience and debounce_time > 0:
                 raise ValueError("`patience` and `debounce_time` cannot be used together.")
-            nz = score != 0.0
-            if patience:
-                if self.history.shape[0] < patience:
-                    score[nz] = 0.0
-                else:
-                    tail = self.history[-(patience - 1):] if patience > 1 else self.history
-                    hits = (tail >= threshold).sum(axis=0) + (score >= threshold)
-                    score[nz & (hits < patience)] = 0.0
-            else:
-                k = int(math.ceil(debounce_time / (self.hop / 16000.0)))
-                recent = (self.history[-k:] >= threshold).any(axis=0) if self.history.shape[0] else np.zeros(self.S, bool)
-                score[nz & (score >= threshold) & recent] = 0.0
+            _filter_streams(score, self.history, patience, threshold, debounce_time, self.hop)
         self.history = np.vstack([self.history, score[None]])[-PREDICTION_HISTORY:]
         self.post_processed_scores = score
         return score
 
     def close(self):
         self.backend.stream_close()
+
+
+class CascadeStreamBatch:
+    """S lock-step streams through a gate + verifier pair (session.HipCascade): StreamBatch's filter state once per model, and the
+    cascade rule of ``HipInterpreter.predict`` vectorised over streams.  Only the gate keeps a device ring; the verifier scores the
+    windows of the streams whose RAW gate probability reaches the threshold (the device's select), and the host zeroes it wherever the
+    gate's post-warm-up score is below the threshold (:660-669, 758-769) - so during the gate's first five predictions the verifier
+    reports 0 for any positive threshold, as it does in the reference.  ``push`` returns {gate_name: scores [S], name: scores [S]},
+    per stream what ``DetectionResult.scores`` holds."""
+
+    def __init__(self, cascade, n_streams: int, window_samples: int = 16000, hop_samples: int = HOP_SAMPLES, gate_name: str = "gate",
+                 name: str = "model"):
+        if gate_name == name:
+            raise ValueError("the gate and the verifier need two names")
+        self.cascade, self.S, self.window, self.hop = cascade, int(n_streams), int(window_samples), int(hop_samples)
+        self.gate_name, self.name = gate_name, name
+        cascade.stream_open(self.S, self.window, self.hop)
+        self.reset(_device=False)
+
+    def reset(self, _device: bool = True):
+        if _device:
+            self.cascade.stream_reset()
+        self.filled = 0
+        self.history = {n: np.zeros((0, self.S), np.float32) for n in (self.gate_name, self.name)}
+        self.raw_scores = {n: np.zeros(self.S, np.float32) for n in (self.gate_name, self.name)}
+        self.post_processed_scores = {n: np.zeros(self.S, np.float32) for n in (self.gate_name, self.name)}
+        self.n_open = 0
+
+    def push(self, chunk: np.ndarray, patience: dict = {}, threshold: dict = {}, debounce_time: float = 0.0) -> Dict[str, np.ndarray]:
+        """chunk int16 [S, hop] -> {name: post-processed scores [S]}; patience / threshold are keyed by model name, as in predict()"""
+        if not isinstance(chunk, np.ndarray):
+            raise ValueError("Input audio `x` must be a Numpy array.")
+        if (patience or debounce_time > 0) and not threshold:
+            raise ValueError("`threshold` must be provided when using `patience` or `debounce_time`.")
+        if patience and debounce_time > 0:
+            raise ValueError("`patience` and `debounce_time` cannot be used together.")
+        gate_probs, _, probs, self.n_open = self.cascade.stream_push(chunk)
+        self.filled += self.hop
+        full = self.filled >= self.window
+        out = {}
+        for n, raw in ((self.gate_name, gate_probs), (self.name, probs)):
+            raw = raw.astype(np.float32)
+            if n == self.name and full:
+                raw[~cascade_open(out[self.gate_name], self.cascade.gate_threshold)] = 0.0     # the gate's post-warm-up score decides
+            self.raw_scores[n] = raw
+            score = raw.copy()
+            if self.history[n].shape[0] < N_WARMUP_PREDICTIONS:
+                score[:] = 0.0
+            out[n] = score
+        final = {n: v.copy() for n, v in out.items()}
+        for n, score in final.items():
+            if n in patience:
+                _filter_streams(score, self.history[n], int(patience[n]), threshold[n], 0.0, self.hop)
+            elif debounce_time > 0 and n in threshold:
+                _filter_streams(score, self.history[n], 0, threshold[n], debounce_time, self.hop)
+            self.history[n] = np.vstack([self.history[n], score[None]])[-PREDICTION_HISTORY:]
+            self.post_processed_scores[n] = score
+        return final
+
+    def close(self):
+        self.cascade.stream_close()

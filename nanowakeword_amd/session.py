@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's session boundary, on top of the libnwwhip C-ABI.
 
 ``HipModel``   : create / load_state_dict / finalize / forward - one handle on one GPU.
+``HipCascade`` : a gate and a verifier HipModel as a pair - the verifier runs on the windows the gate opens (nww_cascade_*).
 ``HipSession`` : duck-types ``onnxruntime.InferenceSession`` exactly as the reference uses it
                  (``get_inputs()[0].name/.shape`` and ``run(None, {"input": x}) -> [probs (B,1,1)]``;
                  reference: nanowakeword/interpreter/nanointerpreter.py:165-167,177-178,677,681,783;
@@ -515,6 +516,148 @@ class HipModel:
         return buf.value.decode()
 
 
+class HipCascade:
+    """A gate and a verifier as a pair on one GPU (nww_cascade_*): the gate scores every window, the verifier only those the gate opens
+    (config.cascade_open: closed exactly where float(gate_prob) < gate_threshold), selected, gathered and scattered on the device.
+    Every entry point returns dense per-window outputs: the gate's probabilities as the gate alone gives them, the verifier's logits /
+    probabilities as verifier.forward_pcm gives them on the open windows stacked in ascending order (in chunks of max_batch), and
+    -inf / 0.0 on closed windows.  With no window open the verifier is not launched."""
+
+    def __init__(self, gate: HipModel, verifier: HipModel, gate_threshold: float = 0.3):
+        if not isinstance(gate, HipModel) or not isinstance(verifier, HipModel):
+            raise TypeError("HipCascade needs two HipModel objects: the gate and the verifier")
+        if gate is verifier:
+            raise ValueError("a cascade needs two distinct models: the gate and the verifier are the same one")
+        if not gate.finalized or not verifier.finalized:
+            raise NwwError("HipCascade needs finalized HipModels")
+        self.gate, self.verifier, self.gate_threshold = gate, verifier, float(gate_threshold)
+        self.lib = verifier.lib
+
+    def _check(self, rc: int):
+        self.verifier._check(rc)              # a cascade's errors go to the verifier's handle
+
+    @property
+    def clip_samples(self) -> int:
+        a, b = self.gate.clip_samples, self.verifier.clip_samples
+        if a != b:
+            raise ValueError(f"the gate was built for clips of {a} samples and the verifier for {b}: pass `window`")
+        return a
+
+    def _thr(self, thr) -> float:
+        return self.gate_threshold if thr is None else float(thr)
+
+    def select(self, probs, thr: Optional[float] = None) -> np.ndarray:
+        """float32 [n] scores -> the ascending int32 indices of the open ones (nww_cascade_select: the device's select alone)"""
+        p = np.ascontiguousarray(np.asarray(probs), dtype=np.float32).reshape(-1)
+        if p.size == 0:
+            return np.empty(0, np.int32)
+        if p.size >= 2 ** 31:
+            raise ValueError("at most 2**31 - 1 scores per call")
+        idx, n_open = np.empty(p.size, np.int32), C.c_int32()
+        self._check(self.lib.nww_cascade_select(self.verifier._h, p.ctypes.data_as(C.c_void_p), p.size, self._thr(thr),
+                                                idx.ctypes.data_as(C.c_void_p), C.byref(n_open)))
+        return idx[:n_open.value].copy()
+
+    def forward_pcm(self, pcm, gate_threshold: Optional[float] = None):
+        """int16 [B,N] -> (gate_probs [B], logits [B], probs [B], n_open); the verifier runs the open clips as one batch"""
+        pcm = HipModel._pcm(pcm)
+        B, N = pcm.shape
+        gp, logits, probs = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.float32)
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_forward_pcm(self.gate._h, self.verifier._h, pcm.ctypes.data_as(C.c_void_p), B, N, self._thr(gate_threshold),
+                                                     gp.ctypes.data_as(C.c_void_p), logits.ctypes.data_as(C.c_void_p),
+                                                     probs.ctypes.data_as(C.c_void_p), C.byref(n_open)))
+        return gp, logits, probs, int(n_open.value)
+
+    def forward_pcm_dev(self, pcm_ptr: int, B: int, N: int, gate_probs_ptr: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0,
+                        gate_threshold: Optional[float] = None) -> int:
+        """Raw device pointers; enqueues on `stream`, which it synchronises once (the count of open clips).  Returns n_open."""
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_forward_pcm_dev(self.gate._h, self.verifier._h, C.c_void_p(pcm_ptr), int(B), int(N), self._thr(gate_threshold),
+                                                         C.c_void_p(gate_probs_ptr) if gate_probs_ptr else None,
+                                                         C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                         C.c_void_p(probs_ptr) if probs_ptr else None, C.byref(n_open),
+                                                         C.c_void_p(stream) if stream else None))
+        return int(n_open.value)
+
+    def forward_recording(self, pcm, window: Optional[int] = None, hop: int = 1280, offset: int = 0, max_batch: int = 4096,
+                          gate_threshold: Optional[float] = None):
+        """int16 [N] -> (gate_probs [nW], logits [nW], probs [nW], n_open) over the windows pcm[offset + i * hop : offset + i * hop + window]:
+        the gate scores all passes, one select, then the verifier in chunks of at most max_batch open windows.  The recording goes up once."""
+        pcm = HipModel._pcm1(pcm)
+        window = int(self.clip_samples if window is None else window)
+        if offset < 0:
+            raise ValueError("offset must not be negative")
+        x = pcm[min(int(offset), len(pcm)):]
+        gp = np.empty(max(0, recording_windows(len(x), window, hop)) if window > 0 and hop > 0 else 0, np.float32)
+        logits, probs = np.empty_like(gp), np.empty_like(gp)
+        nw, n_open = C.c_int32(), C.c_int32()
+        keep = x if len(x) else np.zeros(1, np.int16)               # a valid pointer for an empty recording
+        self._check(self.lib.nww_cascade_forward_recording(self.gate._h, self.verifier._h, keep.ctypes.data_as(C.c_void_p), len(x), window, int(hop),
+                                                           int(max_batch), self._thr(gate_threshold), gp.ctypes.data_as(C.c_void_p),
+                                                           logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p),
+                                                           C.byref(nw), C.byref(n_open)))
+        assert nw.value == len(gp), (nw.value, len(gp))
+        return gp, logits, probs, int(n_open.value)
+
+    def forward_recording_dev(self, pcm_ptr: int, n_samples: int, window: int, hop: int, gate_probs_ptr: int, logits_ptr: int, probs_ptr: int = 0,
+                              max_batch: int = 4096, stream: int = 0, gate_threshold: Optional[float] = None):
+        """Raw device pointers; enqueues on `stream`, which it synchronises once.  Returns (windows written, n_open)."""
+        nw = self.gate._rec_count(n_samples, window, hop)
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_forward_recording_dev(self.gate._h, self.verifier._h, C.c_void_p(pcm_ptr), int(n_samples), int(window), int(hop),
+                                                               int(max_batch), self._thr(gate_threshold),
+                                                               C.c_void_p(gate_probs_ptr) if gate_probs_ptr else None,
+                                                               C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                               C.c_void_p(probs_ptr) if probs_ptr else None, C.byref(n_open),
+                                                               C.c_void_p(stream) if stream else None))
+        return nw, int(n_open.value)
+
+    # ------------------------------------------------------------------ S lock-step streams: the ring is the gate's
+    def stream_open(self, n_streams: int, window_samples: Optional[int] = None, hop_samples: int = 1280):
+        self.gate.stream_open(n_streams, int(self.clip_samples if window_samples is None else window_samples), hop_samples)
+
+    def stream_push(self, chunk, gate_threshold: Optional[float] = None):
+        """chunk int16 [S, hop] -> (gate_probs [S], logits [S], probs [S], n_open); zeros until every stream has a full window"""
+        S, W, hop = self.gate._stream
+        chunk = HipModel._pcm(chunk)
+        if chunk.shape != (S, hop):
+            raise ValueError(f"chunk must have shape ({S}, {hop}), got {chunk.shape}")
+        gp, logits, probs = np.empty(S, np.float32), np.empty(S, np.float32), np.empty(S, np.float32)
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_stream_push(self.gate._h, self.verifier._h, chunk.ctypes.data_as(C.c_void_p), self._thr(gate_threshold),
+                                                     gp.ctypes.data_as(C.c_void_p), logits.ctypes.data_as(C.c_void_p),
+                                                     probs.ctypes.data_as(C.c_void_p), C.byref(n_open)))
+        return gp, logits, probs, int(n_open.value)
+
+    def stream_push_dev(self, chunk_ptr: int, gate_probs_ptr: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0,
+                        gate_threshold: Optional[float] = None) -> int:
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_stream_push_dev(self.gate._h, self.verifier._h, C.c_void_p(chunk_ptr), self._thr(gate_threshold),
+                                                         C.c_void_p(gate_probs_ptr) if gate_probs_ptr else None,
+                                                         C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                         C.c_void_p(probs_ptr) if probs_ptr else None, C.byref(n_open),
+                                                         C.c_void_p(stream) if stream else None))
+        return int(n_open.value)
+
+    def stream_reset(self):
+        self.gate.stream_reset()
+
+    def stream_filled(self) -> int:
+        return self.gate.stream_filled()
+
+    def stream_close(self):
+        self.gate.stream_close()
+
+    def describe(self) -> str:
+        """The launches of one cascade call, one per line: the gate's plan, the select, the gather, the verifier's plan, the scatter"""
+        g = self.gate.describe_plan().strip().split("\n")
+        v = self.verifier.describe_plan().strip().split("\n")
+        return "\n".join(g + ["cascade_select:count + place - ascending indices of the windows with float(gate_prob) >= threshold, closed fill",
+                              "cascade_gather:open windows -> the verifier's PCM staging"] + v +
+                         ["cascade_scatter:the verifier's logits / probabilities -> their windows"]) + "\n"
+
+
 class _Input:
     """Stand-in for onnxruntime NodeArg (cf. _FakeInput, remote_verifier.py:595-603)."""
 
@@ -597,6 +740,28 @@ class HipSession:
         if self.mode != "e2e":
             raise ValueError("run_recording needs an e2e session (raw PCM in)")
         return self.model.forward_recording(pcm, window=self.clip_samples, hop=hop, offset=offset, max_batch=max_batch)[1]
+
+    def cascade_accepts(self, gate_session) -> bool:
+        """Whether run_recording_cascade can take `gate_session` as this session's gate: both e2e HipSessions on two models of one
+        device, built for the same clip length (cheap: no device call)."""
+        return (isinstance(gate_session, HipSession) and gate_session is not self and self.mode == "e2e" and gate_session.mode == "e2e"
+                and gate_session.model is not self.model and gate_session.model.device == self.model.device
+                and gate_session.clip_samples == self.clip_samples)
+
+    def run_recording_cascade(self, gate_session, pcm: np.ndarray, hop: int = 1280, offset: int = 0, gate_threshold: float = 0.3,
+                              max_batch: int = 4096):
+        """int16 [N] -> (gate probabilities [nW], this session's probabilities [nW]) over the windows of run_recording, this session's model
+        run only on the windows whose raw gate probability reaches gate_threshold (0.0 elsewhere): HipInterpreter.score_recording's batch
+        path for a cascade.  last_cascade keeps (windows, open windows) of the latest call."""
+        if not self.cascade_accepts(gate_session):
+            raise ValueError("run_recording_cascade needs two e2e HipSessions on one device with the same clip_samples")
+        cas = getattr(self, "_cascade", None)
+        if cas is None or cas.gate is not gate_session.model:
+            cas = self._cascade = HipCascade(gate_session.model, self.model, gate_threshold)
+        gp, _, probs, n_open = cas.forward_recording(pcm, window=self.clip_samples, hop=hop, offset=offset, max_batch=max_batch,
+                                                     gate_threshold=gate_threshold)
+        self.last_cascade = (len(gp), n_open)
+        return gp, probs
 
     def run_logits(self, input_feed):
         logits, _ = self._forward(input_feed)

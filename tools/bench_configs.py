@@ -4,7 +4,8 @@ clips/s PCM->logit with PCM resident in HBM, per-launch times, max |dlogit| vs t
 Prints one JSON line per config.  (bench.py remains the contract benchmark for configs[1].)
 --rnn [out]: the RNN head's fused / unfused input projection A/B (rnn_main) -> profiles/rnn_bench_configs.jsonl.
 --recording [out]: recording scoring, shared-frame against strided route against pre-materialised windows (recording_main) ->
-profiles/recording_bench_configs.jsonl."""
+profiles/recording_bench_configs.jsonl.
+--cascade [out]: a gate + verifier cascade against the gate alone and the verifier alone (cascade_main) -> profiles/cascade_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -370,7 +371,130 @@ def recording_main(out_path):
     sys.stdout.write(text)
 
 
+CAS_VERIFIERS = (("cnn", (101, 64)), ("e2e_cnn", (250, 64)))
+CAS_GATE = ("e2e_dnn", (64, 101))
+CAS_HOST_WINDOWS = 200                 # host to host: a recording of 16000 + 199 * 1280 samples (about 17 s), every chunk through predict()
+
+
+def cascade_child():
+    """One process: per verifier, REC_B windows of 1 s every 80 ms with the PCM on the device - the gate alone and the verifier alone on all
+    windows (forward_recording_dev), then the cascade at thresholds that open 0 %, about 5 % and 100 % of the windows, taken from the
+    gate's own score quantiles; ms per call as the median of RNN_STEPS device-event timings behind RNN_WARMUP warm-up calls.  Then host to
+    host on a shorter recording: HipInterpreter.score_recording of the pair on the batch path against the same interpreter's predict()
+    loop (wall clock, one pass each behind a warm-up pass), and whether the two agree."""
+    import torch
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.interpreter import HipInterpreter
+    from nanowakeword_amd.session import HipCascade, HipModel, HipSession, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    n = REC_W + (REC_B - 1) * REC_HOP
+    rec_h = synth_pcm("speechlike", 1, n, seed=10)[0]
+    rec = torch.from_numpy(rec_h).to(dev)
+    gcfg = HeadConfig(*CAS_GATE)
+    for head, shape in CAS_VERIFIERS:
+        gate = HipModel(gcfg, fe, device=0, state_dict=synth_state_dict(gcfg), window=window, mel_fb=fb)
+        cfg = HeadConfig(head, shape)
+        ver = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+        cas = HipCascade(gate, ver)
+        ts = torch.cuda.Stream(dev)
+        stream = ts.cuda_stream
+        gp, lg, pr = (torch.empty(REC_B, dtype=torch.float32, device=dev) for _ in range(3))
+        gate.reserve(REC_B, REC_W); ver.reserve(REC_B, REC_W)
+        gate.forward_recording_dev(rec.data_ptr(), n, REC_W, REC_HOP, lg.data_ptr(), gp.data_ptr(), REC_B, stream)
+        torch.cuda.synchronize()
+        q = np.sort(gp.cpu().numpy().astype(np.float64))
+        thr = {"0": float(np.nextafter(q[-1], np.inf)), "5": float(q[-(REC_B // 20)]), "100": float(q[0])}
+        casc = lambda t: (lambda: cas.forward_recording_dev(rec.data_ptr(), n, REC_W, REC_HOP, gp.data_ptr(), lg.data_ptr(), pr.data_ptr(), REC_B,
+                                                            stream, gate_threshold=t))
+        legs = {"gate": lambda: gate.forward_recording_dev(rec.data_ptr(), n, REC_W, REC_HOP, 0, gp.data_ptr(), REC_B, stream),
+                "verifier": lambda: ver.forward_recording_dev(rec.data_ptr(), n, REC_W, REC_HOP, lg.data_ptr(), pr.data_ptr(), REC_B, stream),
+                "cascade_0": casc(thr["0"]), "cascade_5": casc(thr["5"]), "cascade_100": casc(thr["100"])}
+        out = {"verifier": head, "gate": CAS_GATE[0], "windows": REC_B, "window": REC_W, "hop": REC_HOP, "thresholds": thr,
+               "gate_route": gate.recording_route(REC_W, REC_HOP), "verifier_route": ver.recording_route(REC_W, REC_HOP)}
+        for name, step in legs.items():
+            for _ in range(RNN_WARMUP):
+                got = step()
+            torch.cuda.synchronize()
+            if name.startswith("cascade"):
+                out[name + "_open"] = got[1]
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+            for e0, e1 in ev:
+                e0.record(ts); step(); e1.record(ts)
+            torch.cuda.synchronize()
+            out[name + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+        # host to host
+        short = np.ascontiguousarray(rec_h[:REC_W + (CAS_HOST_WINDOWS - 1) * REC_HOP])
+        it = HipInterpreter({"gate": HipSession(gate, name="gate"), "kw": HipSession(ver, name="kw")})
+        it.cascade_config = {"gate": "gate", "verifier": "kw", "gate_threshold": thr["5"]}
+
+        def loop():
+            it.reset()
+            return np.array([it.predict(short[i:i + REC_HOP]).scores["kw"] for i in range(0, len(short), REC_HOP)], np.float32)
+
+        def wall(fn):
+            fn()
+            t0 = time.perf_counter()
+            r = fn()
+            return round((time.perf_counter() - t0) * 1e3, 3), r
+        out["host_batch_ms"], a = wall(lambda: it.score_recording(short)["kw"])
+        out["host_open"] = list(it.models["kw"].last_cascade)
+        out["host_loop_ms"], b = wall(loop)
+        out["host_chunks"], out["host_samples"], out["host_equal"] = len(a), len(short), bool(np.array_equal(a, b))
+        print(json.dumps(out), flush=True)
+        gate.close(); ver.close()
+
+
+def cascade_main(out_path):
+    """RNN_REPEATS fresh child processes, one after another, each under its own time limit; per verifier the medians of the repeats, their
+    spread (max - min over the repeats, the largest of the legs compared), and the three written-down differences."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--cascade-child"], env=dict(os.environ),
+                           cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"cascade child exited {r.returncode}")
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")])
+    lines = []
+    for i, (head, shape) in enumerate(CAS_VERIFIERS):
+        rep = {k: [r[i][k + "_ms"] for r in runs] for k in ("gate", "verifier", "cascade_0", "cascade_5", "cascade_100", "host_batch", "host_loop")}
+        med = {k: float(np.median(v)) for k, v in rep.items()}
+        spread = max(max(v) - min(v) for k, v in rep.items() if not k.startswith("host"))
+        first = runs[0][i]
+        assert all(r[i]["host_equal"] for r in runs), head
+        lines.append({"config": f"cascade {CAS_GATE[0]} {CAS_GATE[1][0]}x{CAS_GATE[1][1]} -> {head} {shape[0]}x{shape[1]} W={REC_W} hop={REC_HOP} "
+                                f"{REC_B} windows, PCM on the device",
+                      "gate": CAS_GATE[0], "verifier": head, "windows": REC_B, "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS,
+                      "thresholds": first["thresholds"], "open_windows": {k: first[f"cascade_{k}_open"] for k in ("0", "5", "100")},
+                      "gate_route": first["gate_route"], "verifier_route": first["verifier_route"],
+                      "ms_repeats": {k: v for k, v in rep.items() if not k.startswith("host")},
+                      "gate_ms": round(med["gate"], 4), "verifier_alone_ms": round(med["verifier"], 4), "cascade_0pct_ms": round(med["cascade_0"], 4),
+                      "cascade_5pct_ms": round(med["cascade_5"], 4), "cascade_100pct_ms": round(med["cascade_100"], 4), "spread_ms": round(spread, 4),
+                      "select_and_readback_ms": round(med["cascade_0"] - med["gate"], 4),
+                      "gather_and_scatter_ms": round(med["cascade_100"] - med["gate"] - med["verifier"], 4),
+                      "cascade_5pct_faster_than_verifier_alone_by_ms": round(med["verifier"] - med["cascade_5"], 4),
+                      "cascade_5pct_wins": bool(med["verifier"] - med["cascade_5"] > spread),
+                      "verifier_alone_over_cascade_5pct": round(med["verifier"] / med["cascade_5"], 2),
+                      "host_to_host": {"samples": first["host_samples"], "chunks": first["host_chunks"], "windows_open": first["host_open"],
+                                       "score_recording_batch_ms_repeats": rep["host_batch"], "predict_loop_ms_repeats": rep["host_loop"],
+                                       "score_recording_batch_ms": round(med["host_batch"], 3), "predict_loop_ms": round(med["host_loop"], 3),
+                                       "loop_over_batch": round(med["host_loop"] / med["host_batch"], 1), "equal": True}})
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--cascade-child" in sys.argv[1:]:
+        return cascade_child()
+    if "--cascade" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--cascade"]
+        return cascade_main(rest[0] if rest else os.path.join(ROOT, "profiles", "cascade_bench_configs.jsonl"))
     if "--rnn-child" in sys.argv[1:]:
         return rnn_child()
     if "--recording-child" in sys.argv[1:]:
