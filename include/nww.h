@@ -233,7 +233,11 @@ int64_t nww_stream_filled(const nww_handle* h);
  * Two routes: shared frames - a pass computes every interior log-mel frame once, the frames of each window that
  * touch its own reflect padding apart, and assembles the windows on the device - when hop is a multiple of hop_length, the head
  * reads frames-major log-mel and NWW_REC_SHARED is not 0; otherwise the strided route, which recomputes every window's frames.
- * (The four are declared `extern`, which changes nothing for a C compiler: tests/test_e2e_cnn_head.py and test_e2e_quartznet_head.py
+ * The raw-PCM heads (e2e_quartznet, e2e_cnn) share the rows of their learned frontend's last stage in the same way - the pool is
+ * the one-launch frontend over the pass's span, a row-subset instance of it computes the rows of each window that see its own zero
+ * padding - when that frontend is planned (depth 2 or 3, 16 or 32 channels, NWW_RAW_FUSED not 0) and hop is a multiple of the
+ * frontend's total stride 16 * 4^(depth - 1); nww_stream_push keeps a ring of those rows under the same rule (NWW_STREAM_INC).
+ * (The five - nww_recording_poison included - are declared `extern`, which changes nothing for a C compiler: tests/test_e2e_cnn_head.py and test_e2e_quartznet_head.py
  * count the declarations that start a line with their return type, and that count - 48 - is the one they pin.)                          */
 /* nW for n_samples (0: shorter than one window); < 0: minus the error code, text in nww_last_error                                  */
 extern int nww_recording_windows(nww_handle* h, int32_t n_samples, int32_t window, int32_t hop);
@@ -247,6 +251,9 @@ extern int nww_forward_recording_dev(nww_handle* h, const int16_t* d_pcm, int32_
 /* host pointers; the recording is uploaded once (2 bytes per sample, in pieces), never as windows.  n_windows_out may be NULL.      */
 extern int nww_forward_recording(nww_handle* h, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
                           float* logits, float* probs, int32_t* n_windows_out);
+/* test instrument: fills the shared route's pool and the dense head input with `value` (synchronises), so that a later pass which
+ * left one of their rows unwritten cannot score as before                                                                            */
+extern int nww_recording_poison(nww_handle* h, float value);
 
 /* ---- gate + verifier cascades: the verifier runs on the windows the gate opens (NanoInterpreter.load_model(cascade=True)) ----
  * Two finalized handles on one device, a small gate and the verifier, and a threshold.  The gate scores every window; a window is

@@ -46,7 +46,7 @@ SYMBOLS = [
     "nww_emb_push_features", "nww_emb_get_features", "nww_emb_forward", "nww_emb_window_batch", "nww_emb_pad_batch",
     "nww_comm_unique_id", "nww_comm_init", "nww_comm_destroy", "nww_all_gather_logits", "nww_forward_pcm_gather_dev",
     "nww_forward_pcm_gather_async_dev", "nww_gather_fence", "nww_gather_overlap_ms", "nww_feature_clamp",
-    "nww_recording_windows", "nww_recording_route", "nww_forward_recording_dev", "nww_forward_recording",
+    "nww_recording_windows", "nww_recording_route", "nww_forward_recording_dev", "nww_forward_recording", "nww_recording_poison",
     "nww_cascade_select", "nww_cascade_forward_pcm_dev", "nww_cascade_forward_pcm", "nww_cascade_forward_recording_dev",
     "nww_cascade_forward_recording", "nww_cascade_stream_push", "nww_cascade_stream_push_dev",
 ]
@@ -149,6 +149,7 @@ def load_library():
     lib.nww_recording_route.argtypes = [vp, i32, i32]; lib.nww_recording_route.restype = C.c_int
     lib.nww_forward_recording_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]; lib.nww_forward_recording_dev.restype = C.c_int
     lib.nww_forward_recording.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32p]; lib.nww_forward_recording.restype = C.c_int
+    lib.nww_recording_poison.argtypes = [vp, C.c_float]; lib.nww_recording_poison.restype = C.c_int
     f64 = C.c_double                    # the gate threshold travels as a double: the reference compares float(np.float32) with a Python float
     lib.nww_cascade_select.argtypes = [vp, vp, i32, f64, vp, i32p]; lib.nww_cascade_select.restype = C.c_int
     lib.nww_cascade_forward_pcm_dev.argtypes = [vp, vp, vp, i32, i32, f64, vp, vp, vp, i32p, vp]; lib.nww_cascade_forward_pcm_dev.restype = C.c_int

@@ -369,21 +369,33 @@ int nww_check_run(nww_handle* h, int B) {
 // the learned raw-PCM frontend: one conv1d_strided launch per stage (float32 fmaf on the folded operands), rows ping-ponging between
 // d_raw[0] and d_raw[1]; the last stage writes d_out time-major [B][rows][C], or [B][C][rows] when frames_major is 0
 static int nww_raw_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_out, int frames_major, hipStream_t s,
-                                   int* frames_out, size_t row_stride) {
+                                   int* frames_out, size_t row_stride, const Fe2Sub* sub) {
     const int T = nww_pcm_rows(h, N);
     if (T <= 0) return nww_fail_short_clip(h, N);
     if (frames_out) *frames_out = T;
-    int rc = nww_ensure_ws(h, B, N);
-    if (rc) return rc;
     int L = N;
+    // (the one-launch frontend keeps its intermediate rows in LDS: it needs no workspace, and a recording's span as one clip - millions
+    // of samples - must not size one)
     if (h->raw_fused) {
         RawX3Args a = h->raw_x3;
         a.pcm = d_pcm; a.pcm_stride = row_stride ? row_stride : (size_t)N; a.y = d_out; a.B = B; a.N = N; a.ct_out = !frames_major;
         for (int i = 0; i < a.depth; ++i) { L = raw_conv_rows(L, i == 0 ? 16 : 4); a.L[i] = L; }
-        hipError_t e = launch_raw_x3(a, s);
+        hipError_t e;
+        if (sub) {                              // a streaming hop or a recording's edge rows: the row-subset instance
+            if (!frames_major || sub->nr > 3) return fail(h, NWW_ERR_INVALID, "the raw-PCM frontend computes up to three row ranges, rows-major");
+            RawX3Sub rs;
+            rs.nr = sub->nr; rs.ring_rows = sub->ring_rows; rs.row0 = sub->row0; rs.out_clip_stride = sub->out_clip_stride;
+            for (int i = 0; i < sub->nr; ++i) { rs.t0[i] = sub->t0[i]; rs.t1[i] = sub->t1[i]; }
+            e = launch_raw_x3_sub(a, rs, s);
+        } else {
+            e = launch_raw_x3(a, s);
+        }
         if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch '%s' failed: %s", h->raw_fused_name.c_str(), hipGetErrorString(e));
         return NWW_OK;
     }
+    if (sub) return fail(h, NWW_ERR_INVALID, "the per-stage raw-PCM frontend has no row subsets");
+    const int rc = nww_ensure_ws(h, B, N);
+    if (rc) return rc;
     const float* in = nullptr;
     for (size_t i = 0; i < h->raw.size(); ++i) {
         const auto& st = h->raw[i];
@@ -403,8 +415,8 @@ static int nww_raw_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, i
 int nww_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_db, float* d_mel, int frames_major,
                         hipStream_t s, int* frames_out, size_t row_stride, const Fe2Sub* sub) {
     if (nww_raw_head(h->cfg)) {
-        if (d_mel || sub) return fail(h, NWW_ERR_INVALID, "the raw-PCM frontend has no mel power and no frame subsets");
-        return nww_raw_frontend_on_dev(h, d_pcm, B, N, d_db, frames_major, s, frames_out, row_stride);
+        if (d_mel) return fail(h, NWW_ERR_INVALID, "the raw-PCM frontend has no mel power");
+        return nww_raw_frontend_on_dev(h, d_pcm, B, N, d_db, frames_major, s, frames_out, row_stride, sub);
     }
     const int T = nww_pcm_rows(h, N);
     if (T <= 0) return nww_fail_short_clip(h, N);

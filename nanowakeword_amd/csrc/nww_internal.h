@@ -22,6 +22,7 @@
 #include "../../include/nww.h"
 #include "fe_tables.h"
 #include "stream_plan.h"
+#include "raw_plan.h"
 #include "plan_host.h"
 #include "frontend.h"
 #include "layers.h"
@@ -146,7 +147,7 @@ struct nww_handle {
     size_t seq_floats = 0;         // ... floats per clip of it
     StreamState* stream = nullptr; // the open stream batch (nww_stream_*)
     EmbState* emb = nullptr;       // embedding-mode preprocessor state (nww_emb_*)
-    // recording scoring (nww_recording.hip): the pool of a pass's interior frames [(B - 1) k + T][n_mels], and for the host-pointer entry
+    // recording scoring (nww_recording.hip): the pool of a pass's interior frames [(B - 1) k + T][n_mels] (raw-PCM heads: rows of in_cols), and for the host-pointer entry
     // point the recording and its [2][nW] logits / probabilities; each grown on demand
     float* d_rec_pool = nullptr; int16_t* d_rec_pcm = nullptr; float* d_rec_out = nullptr;
     size_t rec_pool_bytes = 0, rec_pcm_bytes = 0, rec_out_bytes = 0;
@@ -224,6 +225,8 @@ void fold_raw_backbone(nww_handle* h);
 int upload_weight_arena(nww_handle* h);
 int build_frontend_tables(nww_handle* h);
 inline bool nww_raw_head(const nww_config& c) { return c.head_type == NWW_HEAD_E2E_QUARTZNET || c.head_type == NWW_HEAD_E2E_CNN; }
+// floats per row of the frames-major head input: mel bins, or the channels of the raw-PCM frontend's last stage
+inline int nww_row_floats(const nww_config& c) { return nww_raw_head(c) ? c.in_cols : c.n_mels; }
 // rows the head's frontend yields for N samples: the STFT's frame count, or for the raw-PCM heads the strided convs' frame law
 // (stage 0 stride 16, every later stage 4; zero padding, so any N >= 1 has rows)
 inline int nww_pcm_rows(const nww_handle* h, int N) {

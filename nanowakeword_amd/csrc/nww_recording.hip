@@ -8,6 +8,9 @@
 //            t of window w; (2) the el + er frames of every window that touch its own reflect padding are computed by the frame-subset
 //            instances straight into the dense head input; (3) rec_assemble_kernel copies every window's interior run out of the pool.
 //            k + el + er frames per window instead of T.  Launch-side code only: no frontend instance is added or changed.
+//            The raw-PCM heads take it with the rows of their learned frontend's last stage for frames (nww_plan_hop_raw, raw_plan.h):
+//            the pool is launch_raw_x3 on the span, the edge rows - those that see the window's own zero padding - the row-subset
+//            instance launch_raw_x3_sub, the assembly the same kernel on rows of in_cols floats.
 #include "nww_internal.h"
 #include "rec_windows.h"
 
@@ -51,7 +54,7 @@ int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B
         if (rc) return rc;
     }
     // (3) the interior runs
-    hipError_t e = launch_rec_assemble(h->d_rec_pool, h->d_logmel, B, p.T, c.n_mels, p.k, p.el, p.er, s);
+    hipError_t e = launch_rec_assemble(h->d_rec_pool, h->d_logmel, B, p.T, nww_row_floats(c), p.k, p.el, p.er, s);
     if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'rec_assemble' failed: %s", hipGetErrorString(e));
     RunOpts o;
     o.x_frames_major = c.mel_major_features != 0;
@@ -70,11 +73,11 @@ int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, in
     // the pool's frames as one clip: the span has to stay inside the frontend's 32-bit sample offsets, and the frame law has to give
     // the span every row the windows read (it does whenever hop is a multiple of the frame hop; checked, not assumed)
     const long long span = (long long)(Bmax - 1) * hop + W, rows = (long long)(Bmax - 1) * p.k + p.T;
-    if (p.shared && (span >= (1ll << 30) || fe_num_frames(h->fe, (int)span) < rows)) p.shared = false;
+    if (p.shared && (span >= (1ll << 30) || (nww_raw_head(h->cfg) ? nww_pcm_rows(h, (int)span) != rows : nww_pcm_rows(h, (int)span) < rows))) p.shared = false;
     rc = nww_ensure_ws(h, Bmax, W);
     if (rc) return rc;
     if (p.shared) {
-        const size_t floats = (size_t)fe_num_frames(h->fe, (int)span) * h->cfg.n_mels;
+        const size_t floats = (size_t)nww_pcm_rows(h, (int)span) * nww_row_floats(h->cfg);
         rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_pool), &h->rec_pool_bytes, floats * sizeof(float));
         if (rc) return rc;
     }
@@ -118,6 +121,19 @@ extern "C" int nww_recording_route(nww_handle* h, int32_t window, int32_t hop) {
     RecPlan p;
     const int rc = rec_plan(h, window, hop, p);
     return rc ? -rc : (p.shared ? 1 : 0);
+}
+
+// test instrument: the pool and the dense head input hold `value` everywhere, so that a pass which left a row unwritten shows
+extern "C" int nww_recording_poison(nww_handle* h, float value) {
+    const int rc = nww_check_run(h, 1);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = h->own_stream;
+    HIP_TRY(h, launch_rec_fill(h->d_rec_pool, h->rec_pool_bytes / sizeof(float), value, s));
+    const int T = h->cap_N > 0 ? nww_pcm_rows(h, h->cap_N) : 0;
+    if (T > 0 && h->d_logmel) HIP_TRY(h, launch_rec_fill(h->d_logmel, (size_t)h->cap_B * T * nww_row_floats(h->cfg), value, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return NWW_OK;
 }
 
 extern "C" int nww_forward_recording_dev(nww_handle* h, const int16_t* d_pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,

@@ -40,8 +40,10 @@ int nww_window_plan(nww_handle* h, int W, int hop, int level, HopPlan& p) {
     const nww_config& c = h->cfg;
     const ClipRows cr = nww_clip_rows(h, W);
     const bool fe_subsets = !nww_raw_head(c) && (!c.mel_major_features || h->e2e_transposed) && fe2_subset_supported(h->fe);
-    p = nww_plan_hop(h->fe, cr.T, W, hop, level, fe_subsets, h->stream_conv && h->x_stride_ok && h->stream_H == cr.T, h->stream_seq,
-                     [&](int a, int b) { return trunk_b_rows_fit(cr.T, h->stream_W, a, b); });
+    // a raw-PCM head shares the rows of its last frontend stage where the one-launch frontend (and so its row-subset instance) is planned
+    if (nww_raw_head(c)) p = nww_plan_hop_raw(c.n_blocks, W, hop, level, h->raw_fused);
+    else p = nww_plan_hop(h->fe, cr.T, W, hop, level, fe_subsets, h->stream_conv && h->x_stride_ok && h->stream_H == cr.T, h->stream_seq,
+                          [&](int a, int b) { return trunk_b_rows_fit(cr.T, h->stream_W, a, b); });
     if (!p.valid) return fail(h, NWW_ERR_INVALID, "window and hop must be positive multiples of 8 samples with hop <= window");
     if (!cr.fits)
         return fail(h, NWW_ERR_SHAPE, "a %d-sample window gives (%d,%d) features but the head expects (%d,%d)", W, cr.rows, cr.cols, c.in_rows, c.in_cols);
@@ -49,7 +51,8 @@ int nww_window_plan(nww_handle* h, int W, int hop, int level, HopPlan& p) {
 }
 
 // NWW_STREAM_INC = 0: every hop re-scores the whole window (rounds 1-3), 1: frontend only, 2: + the fused trunk's rows, 3 (default):
-// + the third conv's rows (HopPlan, stream_plan.h); the raw-PCM frontend re-scores the whole window every hop.  One buffer per kept level.
+// + the third conv's rows (HopPlan, stream_plan.h).  A raw-PCM head keeps the rows of its frontend's last stage in the same ring (rows of
+// in_cols floats, raw_plan.h) wherever the hop is a whole number of them; otherwise it re-scores the whole window every hop.  One buffer per kept level.
 static int stream_alloc(nww_handle* h, StreamState* st) {
     const int S = st->S, W = st->W;
     const HopPlan& p = st->plan;
@@ -59,7 +62,7 @@ static int stream_alloc(nww_handle* h, StreamState* st) {
     HIP_TRY(h, hipMalloc(&st->d_chunk, (size_t)S * st->hop * sizeof(int16_t) + 16));
     if (p.shared) {
         st->lm_rows = (p.T + p.k - 1) / p.k * p.k;
-        HIP_TRY(h, hipMalloc(&st->d_lm_ring, (size_t)S * 2 * st->lm_rows * h->cfg.n_mels * sizeof(float) + 16));
+        HIP_TRY(h, hipMalloc(&st->d_lm_ring, (size_t)S * 2 * st->lm_rows * nww_row_floats(h->cfg) * sizeof(float) + 16));
     }
     if (p.conv) HIP_TRY(h, hipMalloc(&st->d_a2_ring, (size_t)S * 32 * p.a2_rows * (h->stream_W / 4) * sizeof(float) + 16));
     for (int q = 0; q < 2 && p.seq; ++q) HIP_TRY(h, hipMalloc(&st->d_seq[q], (size_t)S * h->seq_floats * sizeof(float) + 16));
@@ -117,13 +120,13 @@ static int stream_hop_incremental(nww_handle* h, float* d_logits, float* d_probs
     const nww_config& c = h->cfg;
     StreamState* st = h->stream;
     const HopPlan& p = st->plan;
-    const int S = st->S, W = st->W, T = p.T, k = p.k;
+    const int S = st->S, W = st->W, T = p.T, k = p.k, cols = nww_row_floats(c);
     int rc = nww_ensure_ws(h, S, W);
     if (rc) return rc;
     nww_prof_begin(h);
     nww_prof_mark(h, s, 0);
     Fe2Sub sub;
-    sub.ring_rows = st->lm_rows; sub.row0 = st->lm_pos; sub.out_clip_stride = (size_t)2 * st->lm_rows * c.n_mels;
+    sub.ring_rows = st->lm_rows; sub.row0 = st->lm_pos; sub.out_clip_stride = (size_t)2 * st->lm_rows * cols;
     if (st->primed) {
         if (p.el > 0) { sub.t0[sub.nr] = 0; sub.t1[sub.nr] = p.el; ++sub.nr; }
         // the new interior frames, then the trailing edge frames as a group of their own (groups of up to eight frames)
@@ -132,14 +135,14 @@ static int stream_hop_incremental(nww_handle* h, float* d_logits, float* d_probs
     }
     rc = nww_frontend_on_dev(h, st->d_ring + st->pos, S, W, st->d_lm_ring, nullptr, 1, s, nullptr, (size_t)2 * W, &sub);
     if (rc) return rc;
-    const float* win = st->d_lm_ring + (size_t)st->lm_pos * c.n_mels;          // rows [lm_pos, lm_pos + T) of every stream's ring: its window
+    const float* win = st->d_lm_ring + (size_t)st->lm_pos * cols;          // rows [lm_pos, lm_pos + T) of every stream's ring: its window
     RunOpts o;
     if (h->x_stride_ok) {
         const HopView v = stream_hop_view(h, st, sub.out_clip_stride);
         o.hop = &v;
         rc = nww_run_head(h, win, S, d_logits, d_probs, s, o);
     } else {
-        const int n4 = T * c.n_mels / 4;
+        const int n4 = T * cols / 4;
         const size_t total = (size_t)S * n4;
         hipLaunchKernelGGL(stream_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(win),
                            reinterpret_cast<float4*>(h->d_logmel), S, n4, sub.out_clip_stride / 4);

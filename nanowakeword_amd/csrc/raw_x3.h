@@ -21,3 +21,14 @@ struct RawX3Args {
 bool raw_x3_supported(int channels, int depth);
 size_t raw_x3_lds_bytes(int channels, int depth);
 hipError_t launch_raw_x3(const RawX3Args& a, hipStream_t s);
+// The row-subset instance (streaming hops, recording scoring): only the rows of up to three ascending ranges [t0, t1) of every clip's
+// last stage are computed (nr = 0: all of them), each with the clip's own zero padding and bit for bit as launch_raw_x3 computes it.
+// Rows-major output only: row t of clip b at y + b * out_clip_stride + t * C (out_clip_stride = 0: dense clips), or with ring_rows > 0
+// at row row0 + t of the clip's ring of 2 * ring_rows rows, and again ring_rows rows away (Fe2Sub, frontend.h).
+struct RawX3Sub {
+    int nr = 0;
+    int t0[3] = {0, 0, 0}, t1[3] = {0, 0, 0};
+    int ring_rows = 0, row0 = 0;
+    size_t out_clip_stride = 0;
+};
+hipError_t launch_raw_x3_sub(const RawX3Args& a, const RawX3Sub& sub, hipStream_t s);

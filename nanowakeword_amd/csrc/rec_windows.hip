@@ -27,6 +27,17 @@ rec_assemble_kernel(const float4* __restrict__ pool, float4* __restrict__ dense,
     }
 }
 
+__global__ void __launch_bounds__(REC_BLOCK) rec_fill_kernel(float* __restrict__ p, size_t n, float v) {
+    for (size_t i = (size_t)blockIdx.x * REC_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * REC_BLOCK) p[i] = v;
+}
+
+hipError_t launch_rec_fill(float* p, size_t n, float v, hipStream_t stream) {
+    if (!p || n == 0) return hipSuccess;
+    const size_t blocks = (n + REC_BLOCK - 1) / REC_BLOCK;
+    hipLaunchKernelGGL(rec_fill_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(REC_BLOCK), 0, stream, p, n, v);
+    return hipGetLastError();
+}
+
 hipError_t launch_rec_assemble(const float* d_pool, float* d_dense, int B, int T, int n_mels, int k, int el, int er, hipStream_t stream) {
     if (B <= 0 || T <= 0 || k <= 0 || el < 0 || er < 0 || el + er >= T || n_mels <= 0 || (n_mels & 3)) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(d_pool) | reinterpret_cast<uintptr_t>(d_dense)) & 15) return hipErrorInvalidValue;

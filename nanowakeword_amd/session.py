@@ -253,7 +253,12 @@ class HipModel:
         """The launches of one pass of forward_recording at this (window, hop), one per line: the route's frontend launches, then the
         head's lines of describe_plan()."""
         window = int(self.clip_samples if window is None else window)
-        if self.recording_route(window, hop):
+        raw = self.head.model_type in RAW_HEADS
+        if self.recording_route(window, hop) and raw:
+            fe = ["raw_x3:pool - the pass's span of (B - 1) * %d + %d samples as one clip, rows-major" % (hop, window),
+                  "raw_x3:edge rows - the rows of every window's last frontend stage that see its own zero padding",
+                  "rec_assemble:pool -> [B][rows][channels] (shared-frame route)"]
+        elif self.recording_route(window, hop):
             fe = ["frontend:pool - the pass's span of (B - 1) * %d + %d samples as one clip, frames-major" % (hop, window),
                   "frontend:edge frames - the frames of every window that touch its own reflect padding (none without centring)",
                   "rec_assemble:pool -> [B][frames][n_mels] (shared-frame route)"]
@@ -279,6 +284,10 @@ class HipModel:
                                                        logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p), C.byref(n_out)))
             assert n_out.value == nw
         return logits, probs
+
+    def poison_recording_workspace(self, value: float = 1e30) -> None:
+        """Test instrument (nww_recording_poison): the shared route's pool and the dense head input hold `value` everywhere."""
+        self._check(self.lib.nww_recording_poison(self._h, float(value)))
 
     def forward_recordings(self, recordings, window: Optional[int] = None, hop: int = 1280, max_batch: int = 4096):
         """list of int16 [N_i] -> [(logits, probs)] per recording, scored together (score_recordings): windows never mix two recordings"""

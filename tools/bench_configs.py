@@ -5,6 +5,9 @@ Prints one JSON line per config.  (bench.py remains the contract benchmark for c
 --rnn [out]: the RNN head's fused / unfused input projection A/B (rnn_main) -> profiles/rnn_bench_configs.jsonl.
 --recording [out]: recording scoring, shared-frame against strided route against pre-materialised windows (recording_main) ->
 profiles/recording_bench_configs.jsonl.
+--recording-raw [out] [--parent DIR]: the same workload for the raw-PCM heads plus a row of 1024 streams, shared rows against
+NWW_REC_SHARED = NWW_STREAM_INC = 0 and against the package of a built checkout of the parent commit (recording_raw_main) ->
+profiles/raw_recording_bench_configs.jsonl.
 --cascade [out]: a gate + verifier cascade against the gate alone and the verifier alone (cascade_main) -> profiles/cascade_bench_configs.jsonl."""
 import json
 import os
@@ -15,7 +18,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.environ.get("NWW_BENCH_PACKAGE_ROOT") or ROOT)      # (the package of another checkout: --recording-raw --parent)
 
 
 def raw_frontend_legs(torch, m, cfg, sd, pcm, pcm_h, logits, stream, steps):
@@ -371,6 +374,110 @@ def recording_main(out_path):
     sys.stdout.write(text)
 
 
+RAW_REC_HEADS = (("e2e_quartznet", (63, 128)), ("e2e_cnn", (250, 64)))
+RAW_REC_STREAMS = 1024
+
+
+def recording_raw_child():
+    """recording_child for the raw-PCM heads, one process = one setting (NWW_REC_SHARED and NWW_STREAM_INC, read once; or the package of
+    another checkout, NWW_BENCH_PACKAGE_ROOT).  Per head: the 4096 windows of --recording through forward_pcm_dev (materialised) and
+    forward_recording_dev, device-event medians as there and whether the two agree bit for bit; then RAW_REC_STREAMS streams, ms per hop of
+    stream_push_dev behind the pushes that fill the window and RNN_WARMUP more."""
+    import torch
+    from numpy.lib.stride_tricks import sliding_window_view
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    n = REC_W + (REC_B - 1) * REC_HOP
+    rec_h = synth_pcm("speechlike", 1, n, seed=10)[0]
+    win_h = np.ascontiguousarray(sliding_window_view(rec_h, REC_W)[::REC_HOP])
+    rec, win = torch.from_numpy(rec_h).to(dev), torch.from_numpy(win_h).to(dev)
+    chunk = torch.from_numpy(synth_pcm("speechlike", RAW_REC_STREAMS, REC_HOP, seed=11)).to(dev)
+
+    def timed(ts, step):
+        for _ in range(RNN_WARMUP):
+            step()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for e0, e1 in ev:
+            e0.record(ts); step(); e1.record(ts)
+        torch.cuda.synchronize()
+        return round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+
+    for head, shape in RAW_REC_HEADS:
+        cfg = HeadConfig(head, shape)
+        m = HipModel(cfg, FrontendConfig(), device=0, state_dict=synth_state_dict(cfg))
+        ts = torch.cuda.Stream(dev)
+        stream = ts.cuda_stream
+        lg_w = torch.empty(REC_B, dtype=torch.float32, device=dev)
+        lg_r = torch.empty(REC_B, dtype=torch.float32, device=dev)
+        lg_s = torch.empty(RAW_REC_STREAMS, dtype=torch.float32, device=dev)
+        m.reserve(REC_B, REC_W)
+        out = {"head": head, "route": m.recording_route(REC_W, REC_HOP), "windows": REC_B, "window": REC_W, "hop": REC_HOP}
+        out["windows_ms"] = timed(ts, lambda: m.forward_pcm_dev(win.data_ptr(), REC_B, REC_W, lg_w.data_ptr(), 0, stream))
+        out["recording_ms"] = timed(ts, lambda: m.forward_recording_dev(rec.data_ptr(), n, REC_W, REC_HOP, lg_r.data_ptr(), 0, REC_B, stream))
+        out["bit_identical"] = bool(torch.equal(lg_w, lg_r))
+        m.stream_open(RAW_REC_STREAMS, REC_W, REC_HOP)
+        for _ in range(REC_W // REC_HOP + 1):
+            m.stream_push_dev(chunk.data_ptr(), lg_s.data_ptr(), 0, stream)
+        out["streams"] = RAW_REC_STREAMS
+        out["stream_ms_per_hop"] = timed(ts, lambda: m.stream_push_dev(chunk.data_ptr(), lg_s.data_ptr(), 0, stream))
+        m.stream_close()
+        print(json.dumps(out), flush=True)
+        m.close()
+
+
+def recording_raw_main(out_path, parent_root):
+    """The raw-PCM heads' recording and stream rows: the shared route (the default), NWW_REC_SHARED = NWW_STREAM_INC = 0 on the same build
+    and - with --parent DIR, a built checkout of the parent commit - that commit's package, alternated, RNN_REPEATS fresh processes each;
+    per head the medians of the repeats, their spread (max - min) and whether the shared route beats the strided one by more than three
+    times the spread (the rule the planner's default follows)."""
+    import subprocess
+
+    def run(setting):
+        env = dict(os.environ)
+        if setting == "parent":
+            env["NWW_BENCH_PACKAGE_ROOT"] = parent_root
+        else:
+            env.update(NWW_REC_SHARED=setting, NWW_STREAM_INC="3" if setting == "1" else "0")
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--recording-raw-child"], env=env, cwd=ROOT,
+                           stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"child ({setting}) exited {r.returncode}")
+        print(f"[{setting}] {r.stdout.strip()}", file=sys.stderr, flush=True)
+        return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    settings =("1", "0") + (("parent",) if parent_root else ())
+    runs = {s: [] for s in settings}
+    for _ in range(RNN_REPEATS):
+        for s in settings:
+            runs[s].append(run(s))
+    lines = []
+    for i, (head, shape) in enumerate(RAW_REC_HEADS):
+        assert all(r[i]["bit_identical"] for s in runs for r in runs[s]), head
+        assert all(r[i]["route"] == (1 if s == "1" else 0) for s in runs for r in runs[s]), head
+        line = {"config": f"recording {head} {shape[0]}x{shape[1]} W={REC_W} hop={REC_HOP} {REC_B} windows per pass, {RAW_REC_STREAMS} streams",
+                "head": head, "windows": REC_B, "streams": RAW_REC_STREAMS, "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS}
+        for key, name in (("recording_ms", "recording"), ("stream_ms_per_hop", "stream_hop")):
+            rep = {s: [r[i][key] for r in runs[s]] for s in settings}
+            med = {s: float(np.median(v)) for s, v in rep.items()}
+            spread = max(max(v) - min(v) for v in rep.values())
+            line[name] = {"shared_ms_repeats": rep["1"], "strided_ms_repeats": rep["0"], "shared_ms": round(med["1"], 4), "strided_ms": round(med["0"], 4),
+                          "spread_ms": round(spread, 4), "shared_faster_by_ms": round(med["0"] - med["1"], 4),
+                          "shared_wins": bool(med["0"] - med["1"] > 3 * spread)}
+            if parent_root:
+                line[name].update(parent_ms_repeats=rep["parent"], parent_ms=round(med["parent"], 4))
+        base = [r[i]["windows_ms"] for s in settings for r in runs[s]]
+        line["materialised_windows_ms"] = round(float(np.median(base)), 4)
+        line["bit_identical_to_windows"] = True
+        lines.append(line)
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 CAS_VERIFIERS = (("cnn", (101, 64)), ("e2e_cnn", (250, 64)))
 CAS_GATE = ("e2e_dnn", (64, 101))
 CAS_HOST_WINDOWS = 200                 # host to host: a recording of 16000 + 199 * 1280 samples (about 17 s), every chunk through predict()
@@ -499,6 +606,13 @@ def main():
         return rnn_child()
     if "--recording-child" in sys.argv[1:]:
         return recording_child()
+    if "--recording-raw-child" in sys.argv[1:]:
+        return recording_raw_child()
+    if "--recording-raw" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--recording-raw"]
+        parent = rest.pop(rest.index("--parent") + 1) if "--parent" in rest else None
+        rest = [a for a in rest if a != "--parent"]
+        return recording_raw_main(rest[0] if rest else os.path.join(ROOT, "profiles", "raw_recording_bench_configs.jsonl"), parent)
     if "--recording" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a != "--recording"]
         return recording_main(rest[0] if rest else os.path.join(ROOT, "profiles", "recording_bench_configs.jsonl"))
