@@ -220,8 +220,40 @@ int nww_stream_push(nww_handle* h, const int16_t* chunk, float* logits, float* p
 int nww_stream_push_dev(nww_handle* h, const int16_t* d_chunk, float* d_logits, float* d_probs, void* stream);
 int nww_stream_reset(nww_handle* h);      /* new session for every stream (NanoInterpreter.reset, :719-733)    */
 int nww_stream_close(nww_handle* h);
-/* samples seen per stream since open/reset                                                               */
+/* samples seen per stream since open/reset (of a batch whose streams share one state; nww_stream_filled_of otherwise) */
 int64_t nww_stream_filled(const nww_handle* h);
+
+/* ---- streams that push, join and reset on their own: the serving shape of the batch above ----
+ * The same open batch, every stream with a write position, fill count and log-mel ring rotation of its own, kept on the host (every
+ * push is commanded by the host: no device counter, no read-back); a call uploads one small table for its listed streams.  A client
+ * that connects takes a free stream through nww_stream_reset_some and inherits nothing; a client whose packet is late is left out of
+ * the tick.  Every score is bit-identical to nww_forward_pcm on the scored streams' last `window` samples stacked in idx order.
+ * Route 1 (shared frames), where nww_stream_push keeps a log-mel ring for a mel head: the scored windows are gathered out of the PCM
+ * rings, the frontend computes for a stream whose ring holds its previous window only the frames the hop invalidates (12 of 101 at
+ * 1 s / 80 ms), for a stream's first full window all of them; the rows are placed in each stream's own ring and each window gathered
+ * from its own rotation into the dense head input.  Route 0 (whole windows) otherwise - a raw-PCM head, a hop that is no multiple of
+ * hop_length, NWW_STREAM_INC=0, a frontend without frame subsets: nww_forward_pcm's own path on the gathered windows.
+ * While every stream shares one state (a fresh or reset batch, and as long as every call lists every stream) the batch is ALIGNED and
+ * nww_stream_push* / nww_cascade_stream_push* work as before; the first push_some / reset_some that makes the states differ ends
+ * that, and those calls return NWW_ERR_STATE until nww_stream_reset.  The pooled conv rows and sequence rows nww_stream_push keeps
+ * for the CRNN stem are not kept per stream.
+ * (Declared `extern` like the recording block below: the pinned count of declarations that start a line with their return type
+ * stays 48.)                                                                                                                        */
+/* idx: HOST pointer, n strictly ascending stream numbers in [0, n_streams).  chunk [n][hop]: row i belongs to stream idx[i].  Outputs
+ * [n], in idx order (either may be NULL); a stream whose own ring does not yet hold a window gets 0 (logit and probability).  n == 0 is
+ * NWW_OK and launches nothing.  idx not strictly ascending or out of range: NWW_ERR_INVALID, and nothing is written.                */
+extern int nww_stream_push_some(nww_handle* h, const int32_t* idx, int32_t n, const int16_t* chunk, float* logits, float* probs);
+/* device variant: d_chunk and the outputs are device pointers (idx stays a host pointer), enqueued on `stream`, no sync.  A d_chunk
+ * that is 16-byte aligned is copied 16 bytes per thread.                                                                          */
+extern int nww_stream_push_some_dev(nww_handle* h, const int32_t* idx, int32_t n, const int16_t* d_chunk, float* d_logits, float* d_probs, void* stream);
+/* New session for the listed streams only: their PCM rings are zeroed, their fill counts are 0 and their next full window is
+ * computed whole.  Synchronises the device.                                                                                       */
+extern int nww_stream_reset_some(nww_handle* h, const int32_t* idx, int32_t n);
+/* samples seen by one stream since open / its last reset                                                                          */
+extern int64_t nww_stream_filled_of(const nww_handle* h, int32_t stream);
+/* Test and tool instrument, for the latest push_some: how many streams were scored, the route taken (1 shared frames, 0 whole
+ * windows) and how many log-mel frames (rows of a raw-PCM frontend) the frontend was asked for in total.  Outputs may be NULL.      */
+extern int nww_stream_pool_stats(const nww_handle* h, int32_t* n_scored, int32_t* route, int64_t* frames_computed);
 
 /* ---- recording scoring: every window of ONE long recording in a call (the offline counterpart of nww_stream_*) ----
  * What NanoInterpreter.predict computes chunk after chunk over a file (test_model/evaluate_model_with_audio.py), as batches: window i

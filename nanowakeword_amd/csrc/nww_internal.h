@@ -3,7 +3,8 @@
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
 // nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
 // nww_cascade.hip: gate + verifier cascades (nww_cascade_*);
-// stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); plan_host.h: the
+// stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); stream_pool.h: the
+// per-stream state of a batch whose streams push and reset on their own (host-only too, used by nww_stream.hip); plan_host.h: the
 // planner's arithmetic on the weights' values (host-only too, used by nww_plan.hip and nww_weights.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,6 +23,7 @@
 #include "../../include/nww.h"
 #include "fe_tables.h"
 #include "stream_plan.h"
+#include "stream_pool.h"
 #include "raw_plan.h"
 #include "plan_host.h"
 #include "frontend.h"
@@ -74,7 +76,19 @@ struct StreamState {
     // pooled conv rows [S][32][plan.a2_rows][stream_W / 4]: row R at (a2_pos + R) % a2_rows; a hop shifts them by plan.a2_shift
     float* d_a2_ring = nullptr; int a2_pos = 0;
     float* d_seq[2] = {nullptr, nullptr}; int seq_cur = 0;   // the third conv's sequence output, alternating from hop to hop (HopView::seq_new)
+    // Streams that push, join and reset on their own (nww_stream_push_some / nww_stream_reset_some): the per-stream state.  While the
+    // batch is aligned (StreamPool::aligned) the lock-step fields above and the pool describe the same rings: pool_synced says whether
+    // the pool's copy is current (a lock-step push or reset clears it; the next pool call takes the fields over, and hands them back
+    // when it leaves the batch aligned).  The pool keeps the PCM and log-mel rings only - not the conv-row or sequence rings.
+    StreamPool pool; bool pool_synced = false;
+    // its device side, allocated by the first pool call: the frontend's scratch [S][T][row floats], POOL_TAB_SLOTS table slots on the
+    // device and in pinned host memory (a call's table is written to the next slot once the event of that slot's previous call has
+    // passed), and the dense [2][S] outputs of the host-pointer entry point
+    float* d_lm_scratch = nullptr; unsigned char* d_tab = nullptr; unsigned char* pin_tab = nullptr; float* d_pool_out = nullptr;
+    hipEvent_t ev_tab[4] = {nullptr, nullptr, nullptr, nullptr}; size_t tab_slot_bytes = 0; unsigned tab_seq = 0;
+    int stat_scored = 0; long long stat_frames = 0;                   // nww_stream_pool_stats: the latest push_some
 };
+#define POOL_TAB_SLOTS 4
 
 struct Run {
     int B = 0;

@@ -519,6 +519,87 @@ class StreamBatch:
         self.backend.stream_close()
 
 
+class StreamPool:
+    """S audio streams on one GPU that push, join and leave on their own: what a server scoring many clients needs of ``StreamBatch``.
+    A push names the streams that have a chunk this tick (``nww_stream_push_some``); a client that connects takes a free slot through
+    ``attach`` and inherits nothing of the slot's previous client - neither audio nor filter state; one whose packet is late is left out
+    of the tick.  Every slot behaves exactly like a ``StreamBatch`` of one stream fed that slot's chunks: raw score 0 until the slot's own
+    window is full, its first five predictions zeroed, patience / debounce against its own 30-entry history."""
+
+    def __init__(self, backend, n_streams: int, window_samples: int = 16000, hop_samples: int = HOP_SAMPLES, name: str = "model"):
+        self.backend, self.S, self.window, self.hop, self.name = backend, int(n_streams), int(window_samples), int(hop_samples), name
+        backend.stream_open(self.S, self.window, self.hop)
+        self.attached = np.zeros(self.S, bool)
+        self.history = np.zeros((PREDICTION_HISTORY, self.S), np.float32)      # per stream: its latest `count` scores in the last rows
+        self.count = np.zeros(self.S, np.int64)
+        self.raw_scores = np.zeros(self.S, np.float32)
+        self.post_processed_scores = np.zeros(self.S, np.float32)
+
+    def _ids(self, ids) -> np.ndarray:
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) and (ids[0] < 0 or ids[-1] >= self.S or (np.diff(ids) <= 0).any()):
+            raise ValueError(f"stream ids must be strictly ascending numbers in [0, {self.S})")
+        return ids
+
+    def attach(self) -> int:
+        """A new client: the lowest free slot, reset (device ring and filter state)."""
+        free = np.flatnonzero(~self.attached)
+        if not len(free):
+            raise RuntimeError(f"all {self.S} stream slots are taken")
+        slot = int(free[0])
+        self.reset([slot])
+        self.attached[slot] = True
+        return slot
+
+    def detach(self, slot: int):
+        if not 0 <= int(slot) < self.S or not self.attached[int(slot)]:
+            raise ValueError(f"slot {slot} is not attached")
+        self.attached[int(slot)] = False
+
+    def reset(self, ids=None):
+        """New session for the listed streams (None: every stream, which also puts the batch back in lock-step)."""
+        if ids is None:
+            self.backend.stream_reset()
+            ids = np.arange(self.S)
+        else:
+            ids = self._ids(ids)
+            self.backend.stream_reset_some(ids)
+        self.history[:, ids] = 0.0
+        self.count[ids] = 0
+        self.raw_scores[ids] = 0.0
+        self.post_processed_scores[ids] = 0.0
+
+    def push(self, ids, chunk: np.ndarray, patience: int = 0, threshold: float = 0.0, debounce_time: float = 0.0) -> np.ndarray:
+        """ids: strictly ascending stream numbers [n]; chunk int16 [n, hop], row i for stream ids[i] -> post-processed scores [n]."""
+        if not isinstance(chunk, np.ndarray):
+            raise ValueError("Input audio `x` must be a Numpy array.")
+        ids = self._ids(ids)
+        _, probs = self.backend.stream_push_some(ids, chunk)
+        raw = probs.astype(np.float32)
+        self.raw_scores[ids] = raw
+        score = raw.copy()
+        cnt = self.count[ids]
+        score[cnt < N_WARMUP_PREDICTIONS] = 0.0
+        if patience or debounce_time > 0:
+            if not threshold:
+                raise ValueError("`threshold` must be provided when using `patience` or `debounce_time`.")
+            if patience and debounce_time > 0:
+                raise ValueError("`patience` and `debounce_time` cannot be used together.")
+            for c in np.unique(cnt):                              # streams that hold equally many scores share StreamBatch's own filter
+                g = np.flatnonzero(cnt == c)
+                part = score[g]
+                _filter_streams(part, self.history[PREDICTION_HISTORY - int(c):, ids[g]], patience, threshold, debounce_time, self.hop)
+                score[g] = part
+        self.history[:-1, ids] = self.history[1:, ids]
+        self.history[-1, ids] = score
+        self.count[ids] = np.minimum(cnt + 1, PREDICTION_HISTORY)
+        self.post_processed_scores[ids] = score
+        return score
+
+    def close(self):
+        self.backend.stream_close()
+
+
 class CascadeStreamBatch:
     """S lock-step streams through a gate + verifier pair (session.HipCascade): StreamBatch's filter state once per model, and the
     cascade rule of ``HipInterpreter.predict`` vectorised over streams.  Only the gate keeps a device ring; the verifier scores the

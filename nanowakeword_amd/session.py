@@ -374,11 +374,51 @@ class HipModel:
     def stream_reset(self):
         self._check(self.lib.nww_stream_reset(self._h))
 
-    def stream_filled(self) -> int:
-        return int(self.lib.nww_stream_filled(self._h))
+    def stream_filled(self, s: Optional[int] = None) -> int:
+        """samples seen since open / reset: of the batch (streams in lock-step), or of stream `s` alone"""
+        if s is None:
+            return int(self.lib.nww_stream_filled(self._h))
+        return int(self.lib.nww_stream_filled_of(self._h, int(s)))
 
     def stream_close(self):
         self._check(self.lib.nww_stream_close(self._h))
+
+    # streams that push, join and reset on their own (nww_stream_push_some / nww_stream_reset_some)
+    @staticmethod
+    def _stream_ids(ids) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int32)
+
+    def stream_push_some(self, ids, chunk):
+        """ids: strictly ascending stream numbers [n]; chunk int16 [n, hop], row i for stream ids[i] -> (logits [n], probs [n]), 0 for a
+        stream whose own ring does not hold a window yet"""
+        S, W, hop = self._stream
+        ids = self._stream_ids(ids)
+        n = len(ids)
+        chunk = self._pcm(chunk) if n else np.zeros((0, hop), np.int16)
+        if chunk.shape != (n, hop):
+            raise ValueError(f"chunk must have shape ({n}, {hop}), got {chunk.shape}")
+        logits, probs = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._check(self.lib.nww_stream_push_some(self._h, ids.ctypes.data_as(C.c_void_p), n, chunk.ctypes.data_as(C.c_void_p),
+                                                  logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p)))
+        return logits, probs
+
+    def stream_push_some_dev(self, ids, chunk_ptr: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0):
+        ids = self._stream_ids(ids)
+        self._check(self.lib.nww_stream_push_some_dev(self._h, ids.ctypes.data_as(C.c_void_p), len(ids), C.c_void_p(chunk_ptr),
+                                                      C.c_void_p(logits_ptr), C.c_void_p(probs_ptr) if probs_ptr else None,
+                                                      C.c_void_p(stream) if stream else None))
+
+    def stream_reset_some(self, ids):
+        """a new session for the listed streams only"""
+        ids = self._stream_ids(ids)
+        self._check(self.lib.nww_stream_reset_some(self._h, ids.ctypes.data_as(C.c_void_p), len(ids)))
+
+    def stream_pool_stats(self):
+        """the latest stream_push_some: (streams scored, route: 1 shared frames / 0 whole windows, frames the frontend was asked for)"""
+        n, route, frames = C.c_int32(), C.c_int32(), C.c_int64()
+        if self.lib.nww_stream_pool_stats(self._h, C.byref(n), C.byref(route), C.byref(frames)) != 0:
+            raise NwwError("no open stream batch (nww_stream_open)")
+        return n.value, route.value, frames.value
 
     # ------------------------------------------------------------------ embedding-mode preprocessor state (nww_emb_*)
     def emb_open(self, n_streams: int = 1, mel_bins: int = 32, emb_dim: int = 96, mel_cap: int = 970, feat_cap: int = 120):
@@ -775,3 +815,24 @@ class HipSession:
     def run_logits(self, input_feed):
         logits, _ = self._forward(input_feed)
         return logits.reshape(-1, 1)
+
+    # a pool of streams on the session's model (interpreter.StreamPool takes a session as its backend): windows of clip_samples
+    def stream_open(self, n_streams: int, window_samples: Optional[int] = None, hop_samples: int = 1280):
+        if self.mode != "e2e":
+            raise ValueError("streams need an e2e session (raw PCM in)")
+        self.model.stream_open(n_streams, self.clip_samples if window_samples is None else window_samples, hop_samples)
+
+    def stream_push_some(self, ids, chunk):
+        return self.model.stream_push_some(ids, chunk)
+
+    def stream_reset_some(self, ids):
+        self.model.stream_reset_some(ids)
+
+    def stream_reset(self):
+        self.model.stream_reset()
+
+    def stream_filled(self, s: Optional[int] = None) -> int:
+        return self.model.stream_filled(s)
+
+    def stream_close(self):
+        self.model.stream_close()

@@ -8,7 +8,9 @@ profiles/recording_bench_configs.jsonl.
 --recording-raw [out] [--parent DIR]: the same workload for the raw-PCM heads plus a row of 1024 streams, shared rows against
 NWW_REC_SHARED = NWW_STREAM_INC = 0 and against the package of a built checkout of the parent commit (recording_raw_main) ->
 profiles/raw_recording_bench_configs.jsonl.
---cascade [out]: a gate + verifier cascade against the gate alone and the verifier alone (cascade_main) -> profiles/cascade_bench_configs.jsonl."""
+--cascade [out]: a gate + verifier cascade against the gate alone and the verifier alone (cascade_main) -> profiles/cascade_bench_configs.jsonl.
+--stream-pool [out]: 1024 streams per tick, lock-step against push_some (all streams, a random half) against whole-window re-scoring
+(stream_pool_main) -> profiles/stream_pool_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -596,7 +598,120 @@ def cascade_main(out_path):
     sys.stdout.write(text)
 
 
+POOL_HEADS, POOL_STREAMS = ("crnn", "cnn"), 1024
+
+
+def stream_pool_child():
+    """One process = one setting of NWW_STREAM_INC (read once).  Per head: POOL_STREAMS streams, 1 s windows, 80 ms hops, device-resident
+    chunks; ms per tick as the median of RNN_STEPS device-event timings behind the pushes that fill the windows and RNN_WARMUP more, each
+    leg on a batch of its own: lock-step stream_push_dev, push_some with every stream listed, push_some with a random half listed (eight
+    seeded halves in turn, so the streams' ring positions drift apart)."""
+    import torch
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    S = POOL_STREAMS
+    parts = [torch.from_numpy(synth_pcm("speechlike", S, REC_HOP, seed=20 + i)).to(dev) for i in range(4)]
+    rng = np.random.default_rng(5)
+    every = np.arange(S, dtype=np.int32)
+    halves = [np.sort(rng.permutation(S)[:S // 2]).astype(np.int32) for _ in range(8)]
+    half_parts = [[p[torch.from_numpy(h.astype(np.int64)).to(dev)].contiguous() for p in parts] for h in halves]
+    fill = REC_W // REC_HOP + 1
+
+    def timed(ts, step):
+        for i in range(RNN_WARMUP):
+            step(i)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for i, (e0, e1) in enumerate(ev):
+            e0.record(ts); step(RNN_WARMUP + i); e1.record(ts)
+        torch.cuda.synchronize()
+        return round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+
+    for head in POOL_HEADS:
+        cfg = HeadConfig(head, (101, 64))
+        m = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+        ts = torch.cuda.Stream(dev)
+        stream = ts.cuda_stream
+        lg = torch.empty(S, dtype=torch.float32, device=dev)
+        out = {"head": head, "streams": S, "window": REC_W, "hop": REC_HOP}
+
+        def lock(i):
+            m.stream_push_dev(parts[i % 4].data_ptr(), lg.data_ptr(), 0, stream)
+
+        def some_all(i):
+            m.stream_push_some_dev(every, parts[i % 4].data_ptr(), lg.data_ptr(), 0, stream)
+
+        def some_half(i):
+            m.stream_push_some_dev(halves[i % 8], half_parts[i % 8][i % 4].data_ptr(), lg.data_ptr(), 0, stream)
+
+        for name, step in (("lock_step", lock), ("some_all", some_all), ("some_half", some_half)):
+            m.stream_open(S, REC_W, REC_HOP)
+            for i in range(fill):
+                (lock if name == "lock_step" else some_all)(i)
+            out[name + "_ms"] = timed(ts, step)
+            if name != "lock_step":
+                out[name + "_stats"] = list(m.stream_pool_stats())
+            m.stream_close()
+        out["route"] = out["some_all_stats"][1]
+        print(json.dumps(out), flush=True)
+        m.close()
+
+
+def stream_pool_main(out_path):
+    """NWW_STREAM_INC = 3 (the default) and 0 alternated, RNN_REPEATS fresh processes each, one after another (the protocol of --recording);
+    per head the medians of the repeats and their spread (max - min) for (a) lock-step nww_stream_push_dev, (b) push_some with every
+    stream listed, (c) push_some with a random half listed, each on the shared-frame route, and (d) the same two push_some legs re-scoring
+    whole windows (NWW_STREAM_INC=0); and whether (b) beats (d) by more than the spread."""
+    import subprocess
+
+    def run(knob):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--stream-pool-child"],
+                           env=dict(os.environ, NWW_STREAM_INC=knob), cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"child (NWW_STREAM_INC={knob}) exited {r.returncode}")
+        print(f"[NWW_STREAM_INC={knob}] {r.stdout.strip()}", file=sys.stderr, flush=True)
+        return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    runs = {"3": [], "0": []}
+    for _ in range(RNN_REPEATS):
+        for knob in ("3", "0"):
+            runs[knob].append(run(knob))
+    lines = []
+    for i, head in enumerate(POOL_HEADS):
+        assert all(r[i]["route"] == (1 if k == "3" else 0) for k in runs for r in runs[k]), head
+        rep = {"a_lock_step": [r[i]["lock_step_ms"] for r in runs["3"]], "b_push_some_all": [r[i]["some_all_ms"] for r in runs["3"]],
+               "c_push_some_half": [r[i]["some_half_ms"] for r in runs["3"]], "d_whole_windows_all": [r[i]["some_all_ms"] for r in runs["0"]],
+               "d_whole_windows_half": [r[i]["some_half_ms"] for r in runs["0"]], "lock_step_whole_windows": [r[i]["lock_step_ms"] for r in runs["0"]]}
+        med = {k: float(np.median(v)) for k, v in rep.items()}
+        spread = max(max(v) - min(v) for v in rep.values())
+        line = {"config": f"stream pool {head} 101x64 W={REC_W} hop={REC_HOP} {POOL_STREAMS} streams, ms per tick", "head": head, "streams": POOL_STREAMS,
+                "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS}
+        for k in rep:
+            line[k + "_ms_repeats"] = rep[k]
+            line[k + "_ms"] = round(med[k], 4)
+        line.update(spread_ms=round(spread, 4), b_over_a_ms=round(med["b_push_some_all"] - med["a_lock_step"], 4),
+                    b_faster_than_d_by_ms=round(med["d_whole_windows_all"] - med["b_push_some_all"], 4),
+                    c_faster_than_d_by_ms=round(med["d_whole_windows_half"] - med["c_push_some_half"], 4),
+                    lock_step_wins_over_b=bool(med["b_push_some_all"] - med["a_lock_step"] > spread),
+                    shared_frames_win=bool(med["d_whole_windows_all"] - med["b_push_some_all"] > spread and
+                                           med["d_whole_windows_half"] - med["c_push_some_half"] > spread))
+        lines.append(line)
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--stream-pool-child" in sys.argv[1:]:
+        return stream_pool_child()
+    if "--stream-pool" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--stream-pool"]
+        return stream_pool_main(rest[0] if rest else os.path.join(ROOT, "profiles", "stream_pool_bench_configs.jsonl"))
     if "--cascade-child" in sys.argv[1:]:
         return cascade_child()
     if "--cascade" in sys.argv[1:]:
