@@ -235,8 +235,9 @@ int64_t nww_stream_filled(const nww_handle* h);
  * hop_length, NWW_STREAM_INC=0, a frontend without frame subsets: nww_forward_pcm's own path on the gathered windows.
  * While every stream shares one state (a fresh or reset batch, and as long as every call lists every stream) the batch is ALIGNED and
  * nww_stream_push* / nww_cascade_stream_push* work as before; the first push_some / reset_some that makes the states differ ends
- * that, and those calls return NWW_ERR_STATE until nww_stream_reset.  The pooled conv rows and sequence rows nww_stream_push keeps
- * for the CRNN stem are not kept per stream.
+ * that, and those lock-step calls return NWW_ERR_STATE until nww_stream_reset.  A cascade does not need lock-step:
+ * nww_cascade_stream_push_some / nww_cascade_stream_reset_some (the cascade block below) run a gate + verifier pair on a batch in any
+ * state.  The pooled conv rows and sequence rows nww_stream_push keeps for the CRNN stem are not kept per stream.
  * (Declared `extern` like the recording block below: the pinned count of declarations that start a line with their return type
  * stays 48.)                                                                                                                        */
 /* idx: HOST pointer, n strictly ascending stream numbers in [0, n_streams).  chunk [n][hop]: row i belongs to stream idx[i].  Outputs
@@ -329,6 +330,35 @@ extern int nww_cascade_stream_push(nww_handle* gate, nww_handle* verifier, const
                             float* logits, float* probs, int32_t* n_open_out);
 extern int nww_cascade_stream_push_dev(nww_handle* gate, nww_handle* verifier, const int16_t* d_chunk, double gate_threshold, float* d_gate_probs,
                                 float* d_logits, float* d_probs, int32_t* n_open_out, void* stream);
+/* The listed streams of a batch whose streams push, join and reset on their own (nww_stream_push_some): the gate's
+ * batch may be in any state, aligned or not.  idx and chunk follow nww_stream_push_some: idx a HOST pointer to n strictly ascending
+ * stream numbers, chunk [n][hop] with row i for stream idx[i]; only the gate has a stream batch open.  Outputs [n], in idx order, any of
+ * them NULL under the rules of nww_cascade_stream_push*:
+ *     the stream's own ring holds no window yet    gate_probs 0             logits 0            probs 0
+ *     scored, closed                               the gate alone           -INFINITY           0.0f
+ *     scored, open                                 the gate alone           the verifier        the verifier
+ * gate_probs[i] is bit-identical to what nww_stream_push_some on the gate alone writes for the same call.  A stream that holds no
+ * window is never open, whatever the threshold: gate_threshold <= 0 opens every SCORED stream.  The open streams' outputs are
+ * bit-identical to nww_forward_pcm on the verifier for those streams' last `window` samples, stacked in ascending stream order as ONE
+ * batch.  *n_open_out: the open streams; with none the verifier launches nothing.  The open entries are compacted by a select that walks
+ * the call's table on the device (count, prefix sum, placement: ascending, no atomic counter) and leaves each open stream's window
+ * offset in the gate's PCM rings for the gather and its output index for the scatter.
+ * n == 0: NWW_OK, nothing is launched, *n_open_out = 0.  Every check that needs no device runs BEFORE the gate's push touches a ring,
+ * so a call that fails one leaves every nww_stream_filled_of as it was: the handles distinct, finalized and on one device
+ * (NWW_ERR_INVALID), the gate with an open batch (NWW_ERR_STATE), idx valid (NWW_ERR_INVALID), the window giving the verifier its
+ * (in_rows, in_cols) (NWW_ERR_SHAPE, the text naming the verifier).  A failure BEHIND the gate's push - a launch, the count's
+ * read-back, the verifier's workspace - leaves the gate's listed streams advanced by the hop, as nww_cascade_stream_push leaves them.
+ * Synchronisation as above: `stream` once, behind the gate and the select, for the pinned 4-byte count (not at all when no listed
+ * stream holds a window), 0 <= n_open <= n checked before anything is sized; the host-pointer variant a second time before it returns.
+ * A call that lists every stream of an aligned batch keeps it aligned, and nww_cascade_stream_push* runs afterwards.                 */
+extern int nww_cascade_stream_push_some(nww_handle* gate, nww_handle* verifier, const int32_t* idx, int32_t n, const int16_t* chunk,
+                                 double gate_threshold, float* gate_probs, float* logits, float* probs, int32_t* n_open_out);
+/* device variant: d_chunk and the outputs are device pointers, idx stays a host pointer (as in nww_stream_push_some_dev)             */
+extern int nww_cascade_stream_push_some_dev(nww_handle* gate, nww_handle* verifier, const int32_t* idx, int32_t n, const int16_t* d_chunk,
+                                     double gate_threshold, float* d_gate_probs, float* d_logits, float* d_probs, int32_t* n_open_out,
+                                     void* stream);
+/* the gate's nww_stream_reset_some (the verifier keeps no ring); its errors are reported on the verifier's handle                  */
+extern int nww_cascade_stream_reset_some(nww_handle* gate, nww_handle* verifier, const int32_t* idx, int32_t n);
 
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models

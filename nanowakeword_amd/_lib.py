@@ -50,6 +50,7 @@ SYMBOLS = [
     "nww_cascade_select", "nww_cascade_forward_pcm_dev", "nww_cascade_forward_pcm", "nww_cascade_forward_recording_dev",
     "nww_cascade_forward_recording", "nww_cascade_stream_push", "nww_cascade_stream_push_dev",
     "nww_stream_push_some", "nww_stream_push_some_dev", "nww_stream_reset_some", "nww_stream_filled_of", "nww_stream_pool_stats",
+    "nww_cascade_stream_push_some", "nww_cascade_stream_push_some_dev", "nww_cascade_stream_reset_some",
 ]
 
 
@@ -161,6 +162,9 @@ def load_library():
     lib.nww_cascade_forward_recording.restype = C.c_int
     lib.nww_cascade_stream_push.argtypes = [vp, vp, vp, f64, vp, vp, vp, i32p]; lib.nww_cascade_stream_push.restype = C.c_int
     lib.nww_cascade_stream_push_dev.argtypes = [vp, vp, vp, f64, vp, vp, vp, i32p, vp]; lib.nww_cascade_stream_push_dev.restype = C.c_int
+    lib.nww_cascade_stream_push_some.argtypes = [vp, vp, vp, i32, vp, f64, vp, vp, vp, i32p]; lib.nww_cascade_stream_push_some.restype = C.c_int
+    lib.nww_cascade_stream_push_some_dev.argtypes = [vp, vp, vp, i32, vp, f64, vp, vp, vp, i32p, vp]; lib.nww_cascade_stream_push_some_dev.restype = C.c_int
+    lib.nww_cascade_stream_reset_some.argtypes = [vp, vp, vp, i32]; lib.nww_cascade_stream_reset_some.restype = C.c_int
     lib.nww_stream_push_some.argtypes = [vp, vp, i32, vp, vp, vp]; lib.nww_stream_push_some.restype = C.c_int
     lib.nww_stream_push_some_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp]; lib.nww_stream_push_some_dev.restype = C.c_int
     lib.nww_stream_reset_some.argtypes = [vp, vp, i32]; lib.nww_stream_reset_some.restype = C.c_int

@@ -228,6 +228,14 @@ def cascade_open(gate_probs, gate_threshold: float):
         return ~(p < float(gate_threshold))
 
 
+def cascade_pool_open(gate_probs, scored, gate_threshold: float):
+    """Which listed streams of a pool call (nww_cascade_stream_push_some) a cascade's gate opens: `scored` [n] bool says whose ring holds
+    a window, and only those are candidates for cascade_open's rule - a stream that holds no window is never open, so a threshold <= 0
+    opens exactly the scored streams.  The device's pool select (cascade.hip) applies the same rule."""
+    import numpy as np
+    return np.asarray(scored, dtype=bool) & cascade_open(gate_probs, gate_threshold)
+
+
 def clip_samples(cfg: "HeadConfig", fe: "FrontendConfig") -> int:
     """The clip length a PCM head was built for, from its input_shape: the whole number of frame hops that gives its frames on the mel
     frontends (16000 for 101 centred frames), every stage's longest input on the raw-PCM heads (16000 for 250 rows at depth 2)."""

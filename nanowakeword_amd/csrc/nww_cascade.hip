@@ -1,8 +1,10 @@
 // nww_cascade.hip - gate + verifier cascades (nww_cascade_*): the gate scores every window, cascade_select compacts the open ones on the
 // device, and the verifier runs nww_forward_pcm_on_dev on them alone - gathered into its own PCM staging, scattered back into dense
 // per-window outputs.  Three inputs share one back half (cas_verify): a batch of clips (row_stride = N), every window of a recording
-// (row_stride = hop) and S lock-step streams (the gate's PCM ring, row_stride = 2 W).  Launch-side code and the three kernels of
-// cascade.hip only: no frontend or head kernel is added or changed.  State (index list, dense outputs of the host-pointer variants,
+// (row_stride = hop) and S lock-step streams (the gate's PCM ring, row_stride = 2 W).  A fourth, the listed streams of a batch whose
+// streams push on their own (cas_pool_push_dev), shares the verifier's chunk with it (cas_verify_chunk): its select walks the table of
+// the gate's pool call and its gather follows ring offsets (row_stride = 8).  Launch-side code and the kernels of
+// cascade.hip only: no frontend or head kernel is added or changed.  State (index lists, dense outputs of the host-pointer variants,
 // block counts, the pinned count) lives on the VERIFIER's handle, and errors go to nww_last_error(verifier).
 #include "nww_internal.h"
 #include "cascade.h"
@@ -48,8 +50,9 @@ int cas_window_fits(nww_handle* v, nww_handle* h, const char* who, int W, int ho
 
 // the index list for n windows and `planes` dense [n] float outputs (3: a host-pointer call's gate probabilities, logits and probabilities;
 // 1: the gate probabilities a _dev caller did not ask for, or nww_cascade_select's uploaded scores; 0: none)
-int cas_state(nww_handle* v, long long n, int planes) {
-    int rc = nww_rec_grow(v, reinterpret_cast<void**>(&v->d_cas_idx), &v->cas_idx_bytes, (size_t)n * sizeof(int32_t));
+// (lists = 2: a pool call's two index lists, ring offsets [n] then entries [n])
+int cas_state(nww_handle* v, long long n, int planes, int lists = 1) {
+    int rc = nww_rec_grow(v, reinterpret_cast<void**>(&v->d_cas_idx), &v->cas_idx_bytes, (size_t)lists * n * sizeof(int32_t));
     if (rc) return rc;
     if (planes > 0) {
         rc = nww_rec_grow(v, reinterpret_cast<void**>(&v->d_cas_out), &v->cas_out_bytes, (size_t)planes * n * sizeof(float));
@@ -60,11 +63,9 @@ int cas_state(nww_handle* v, long long n, int planes) {
     return NWW_OK;
 }
 
-// select over n scores on the device, the count read back: ONE 4-byte copy into pinned memory behind ONE synchronisation of s.  The
-// count is checked before anything is sized by it.
-int cas_select(nww_handle* v, const float* d_gate_probs, long long n, double thr, float* fill_logits, float* fill_probs, int* n_open, hipStream_t s) {
-    hipError_t e = launch_cascade_select(d_gate_probs, n, thr, v->d_cas_idx, v->d_cas_counts, fill_logits, fill_probs, s);
-    if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_select' failed: %s", hipGetErrorString(e));
+// a select's count read back: ONE 4-byte copy into pinned memory behind ONE synchronisation of s.  The count is checked before anything
+// is sized by it.
+int cas_read_count(nww_handle* v, long long n, int* n_open, hipStream_t s) {
     *v->pin_cas_count = -1;
     HIP_TRY(v, hipMemcpyAsync(v->pin_cas_count, v->d_cas_counts + CASCADE_MAX_BLOCKS, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(v, hipStreamSynchronize(s));
@@ -74,7 +75,27 @@ int cas_select(nww_handle* v, const float* d_gate_probs, long long n, double thr
     return NWW_OK;
 }
 
-// The back half of every entry point.  d_gate_probs [n] are on the device (enqueued on s); window i is the N samples at
+// select over n scores on the device, and its count
+int cas_select(nww_handle* v, const float* d_gate_probs, long long n, double thr, float* fill_logits, float* fill_probs, int* n_open, hipStream_t s) {
+    hipError_t e = launch_cascade_select(d_gate_probs, n, thr, v->d_cas_idx, v->d_cas_counts, fill_logits, fill_probs, s);
+    if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_select' failed: %s", hipGetErrorString(e));
+    return cas_read_count(v, n, n_open, s);
+}
+
+// One chunk of the verifier: the b windows at src + from[j] * row_stride gathered into its PCM staging, nww_forward_pcm's own path on
+// them, and result j scattered to output to[j].  (v's workspace holds b clips of N samples: nww_ensure_ws is the caller's.)
+int cas_verify_chunk(nww_handle* v, const int16_t* src, const int32_t* from, size_t row_stride, int N, int b, const int32_t* to, float* d_logits,
+                     float* d_probs, hipStream_t s) {
+    hipError_t e = launch_cascade_gather(src, from, row_stride, N, b, v->d_pcm, s);
+    if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_gather' failed: %s", hipGetErrorString(e));
+    const int rc = nww_forward_pcm_on_dev(v, v->d_pcm, b, N, v->d_logits, v->d_probs, s);
+    if (rc) return rc;
+    e = launch_cascade_scatter(to, b, v->d_logits, v->d_probs, d_logits, d_probs, s);
+    if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_scatter' failed: %s", hipGetErrorString(e));
+    return NWW_OK;
+}
+
+// The back half of every entry point but the pool's.  d_gate_probs [n] are on the device (enqueued on s); window i is the N samples at
 // src + i * row_stride.  Fills the dense outputs, then runs the verifier on consecutive chunks of at most `chunk_max` open windows.
 int cas_verify(nww_handle* v, const float* d_gate_probs, long long n, double thr, const int16_t* src, size_t row_stride, int N, int chunk_max,
                float* d_logits, float* d_probs, int32_t* n_open_out, hipStream_t s) {
@@ -89,12 +110,8 @@ int cas_verify(nww_handle* v, const float* d_gate_probs, long long n, double thr
     for (int j0 = 0; j0 < n_open; j0 += chunk) {
         const int b = std::min(chunk, n_open - j0);
         const int32_t* idx = v->d_cas_idx + j0;
-        hipError_t e = launch_cascade_gather(src, idx, row_stride, N, b, v->d_pcm, s);
-        if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_gather' failed: %s", hipGetErrorString(e));
-        rc = nww_forward_pcm_on_dev(v, v->d_pcm, b, N, v->d_logits, v->d_probs, s);
+        rc = cas_verify_chunk(v, src, idx, row_stride, N, b, idx, d_logits, d_probs, s);
         if (rc) return rc;
-        e = launch_cascade_scatter(idx, b, v->d_logits, v->d_probs, d_logits, d_probs, s);
-        if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_scatter' failed: %s", hipGetErrorString(e));
     }
     return NWW_OK;
 }
@@ -147,6 +164,56 @@ int cas_stream_push_dev(nww_handle* g, nww_handle* v, const int16_t* d_chunk, do
     }
     // every stream's window is the W samples at ring + pos of its row (double-written ring), after the push has moved pos
     return cas_verify(v, d_gate_probs, S, thr, st->d_ring + st->pos, (size_t)2 * W, W, S, d_logits, d_probs, n_open_out, s);
+}
+
+// The checks of a pool call that need no device, in the order the header gives: nothing has touched a ring when one of them fails.
+// *done: n == 0, the call is complete.
+int cas_pool_check(nww_handle* g, nww_handle* v, const int32_t* idx, int32_t n, const void* chunk, int32_t* n_open_out, bool* done) {
+    *done = false;
+    int rc = cas_check(g, v);
+    if (rc) return rc;
+    rc = nww_pool_push_check(g, idx, n, chunk, done);
+    if (rc) return cas_gate_fail(g, v, rc);
+    if (*done) {
+        if (n_open_out) *n_open_out = 0;
+        return NWW_OK;
+    }
+    return cas_clip_fits(v, v, "verifier", g->stream->W);
+}
+
+// The listed streams of the gate's batch, each in its own state: the gate's pool call (either route) leaves its table on the device and
+// the listed streams' probabilities [n] in d_gate_probs; the pool select walks the table and leaves the open streams' ring offsets and
+// entries; the verifier scores their windows out of the gate's PCM rings as ONE batch.
+int cas_pool_push_dev(nww_handle* g, nww_handle* v, const int32_t* idx, int n, const int16_t* d_chunk, double thr, float* d_gate_probs, float* d_logits,
+                      float* d_probs, int32_t* n_open_out, hipStream_t s) {
+    StreamState* st = g->stream;
+    const int W = st->W;
+    int rc = cas_state(v, n, d_gate_probs ? 0 : 1, 2);
+    if (rc) return rc;
+    if (!d_gate_probs) d_gate_probs = v->d_cas_out;
+    const PoolEntry* tab = nullptr;
+    int m = 0;
+    rc = nww_pool_push_on_dev(g, idx, n, d_chunk, nullptr, d_gate_probs, s, &tab, &m);
+    if (rc) return cas_gate_fail(g, v, rc);
+    if (n_open_out) *n_open_out = 0;
+    if (m == 0) {               // no listed stream holds a window yet: 0 for both models, nothing to select
+        if (d_logits) HIP_TRY(v, hipMemsetAsync(d_logits, 0, (size_t)n * sizeof(float), s));
+        if (d_probs) HIP_TRY(v, hipMemsetAsync(d_probs, 0, (size_t)n * sizeof(float), s));
+        return NWW_OK;
+    }
+    int32_t* ring8 = v->d_cas_idx;
+    int32_t* entry = v->d_cas_idx + n;
+    hipError_t e = launch_cascade_pool_select(tab, d_gate_probs, n, thr, W, ring8, entry, v->d_cas_counts, d_logits, d_probs, s);
+    if (e != hipSuccess) return fail(v, NWW_ERR_HIP, "launch 'cascade_pool_select' failed: %s", hipGetErrorString(e));
+    int n_open = 0;
+    rc = cas_read_count(v, m, &n_open, s);
+    if (rc) return rc;
+    if (n_open_out) *n_open_out = n_open;
+    if (n_open == 0) return NWW_OK;                    // no verifier launch at all
+    rc = nww_ensure_ws(v, n_open, W);
+    if (rc) return rc;
+    // an open stream's window is the W samples at 8 * ring8[j] of the gate's double-written rings, after the push has moved its pos
+    return cas_verify_chunk(v, st->d_ring, ring8, 8, W, n_open, entry, d_logits, d_probs, s);
 }
 
 // the dense [3][n] outputs of a host-pointer call -> the caller's arrays, then the call's second synchronisation
@@ -296,4 +363,37 @@ extern "C" int nww_cascade_stream_push(nww_handle* g, nww_handle* v, const int16
     rc = cas_stream_push_dev(g, v, g->stream->d_chunk, thr, out, out + S, out + 2 * S, n_open_out, s);
     if (rc) return cas_settle(g, s, rc);
     return cas_copy_out(g, v, S, gate_probs, logits, probs, s);
+}
+
+extern "C" int nww_cascade_stream_push_some_dev(nww_handle* g, nww_handle* v, const int32_t* idx, int32_t n, const int16_t* d_chunk, double thr,
+                                                float* d_gate_probs, float* d_logits, float* d_probs, int32_t* n_open_out, void* stream) {
+    bool done;
+    const int rc = cas_pool_check(g, v, idx, n, d_chunk, n_open_out, &done);
+    if (rc || done) return rc;
+    HIP_TRY(v, hipSetDevice(v->cfg.device));
+    return cas_pool_push_dev(g, v, idx, n, d_chunk, thr, d_gate_probs, d_logits, d_probs, n_open_out, stream ? (hipStream_t)stream : v->own_stream);
+}
+
+extern "C" int nww_cascade_stream_push_some(nww_handle* g, nww_handle* v, const int32_t* idx, int32_t n, const int16_t* chunk, double thr,
+                                            float* gate_probs, float* logits, float* probs, int32_t* n_open_out) {
+    bool done;
+    int rc = cas_pool_check(g, v, idx, n, chunk, n_open_out, &done);
+    if (rc || done) return rc;
+    HIP_TRY(v, hipSetDevice(v->cfg.device));
+    hipStream_t s = v->own_stream;
+    rc = cas_state(v, n, 3, 2);
+    if (rc) return rc;
+    rc = nww_h2d_small(g, g->stream->d_chunk, chunk, (size_t)n * g->stream->hop * sizeof(int16_t), s);
+    if (rc) return cas_gate_fail(g, v, rc);
+    float* out = v->d_cas_out;
+    rc = cas_pool_push_dev(g, v, idx, n, g->stream->d_chunk, thr, out, out + n, out + 2 * n, n_open_out, s);
+    if (rc) return cas_settle(g, s, rc);
+    return cas_copy_out(g, v, n, gate_probs, logits, probs, s);
+}
+
+extern "C" int nww_cascade_stream_reset_some(nww_handle* g, nww_handle* v, const int32_t* idx, int32_t n) {
+    int rc = cas_check(g, v);
+    if (rc) return rc;
+    rc = nww_stream_reset_some(g, idx, n);
+    return rc ? cas_gate_fail(g, v, rc) : NWW_OK;
 }

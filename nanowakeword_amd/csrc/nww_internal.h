@@ -227,6 +227,11 @@ long long nww_rec_count(long long n_samples, int W, int hop);
 int nww_rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes);
 int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
                            hipStream_t s);
+// nww_stream.hip, as the next one: the checks every push_some shares (*done: n == 0, the call is complete), and the push itself on
+// device pointers - what nww_cascade.hip runs a gate's pool call with
+int nww_pool_push_check(nww_handle* h, const int32_t* idx, int32_t n, const void* chunk, bool* done);
+int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t* d_chunk, float* d_logits, float* d_probs, hipStream_t s,
+                         const PoolEntry** tab_out = nullptr, int* m_out = nullptr);
 void nww_cascade_free(nww_handle* h);          // nww_cascade.hip
 void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next eight: what nww_finalize does to the loaded weights before it plans
 void balance_channel_gains(nww_handle* h);

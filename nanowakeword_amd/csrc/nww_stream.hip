@@ -322,7 +322,10 @@ static int pool_alloc(nww_handle* h, StreamState* st) {
     return NWW_OK;
 }
 
-static int pool_push_dev(nww_handle* h, const int32_t* idx, int n, const int16_t* d_chunk, float* d_logits, float* d_probs, hipStream_t s) {
+// (tab_out / m_out: the call's table [n] on the device and its count of scored streams, for a caller that enqueues on s right behind
+// the call - nww_cascade.hip; the table's slot is rewritten POOL_TAB_SLOTS calls later at the earliest)
+int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t* d_chunk, float* d_logits, float* d_probs, hipStream_t s,
+                         const PoolEntry** tab_out, int* m_out) {
     StreamState* st = h->stream;
     StreamPool& pool = st->pool;
     const int W = st->W, hop = st->hop;
@@ -348,6 +351,8 @@ static int pool_push_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
     const PoolEntry* tab = reinterpret_cast<const PoolEntry*>(dev);
     const int32_t* d_win8 = reinterpret_cast<const int32_t*>(dev + nb_e);
     const int32_t* d_out = reinterpret_cast<const int32_t*>(dev + nb_e + nb_m);
+    if (tab_out) *tab_out = tab;
+    if (m_out) *m_out = m;
     auto launches = [&]() -> int {
         // (1) the chunk rows into the rings, each at its own position
         if ((uintptr_t)d_chunk % 16 == 0) {
@@ -431,7 +436,7 @@ static int pool_push_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
 }
 
 // the checks every push_some shares; *done: the call is complete (n == 0)
-static int pool_push_check(nww_handle* h, const int32_t* idx, int32_t n, const void* chunk, bool* done) {
+int nww_pool_push_check(nww_handle* h, const int32_t* idx, int32_t n, const void* chunk, bool* done) {
     *done = false;
     if (!h) return NWW_ERR_INVALID;
     if (!h->stream) return fail(h, NWW_ERR_STATE, "no open stream batch (nww_stream_open)");
@@ -444,15 +449,15 @@ static int pool_push_check(nww_handle* h, const int32_t* idx, int32_t n, const v
 
 extern "C" int nww_stream_push_some_dev(nww_handle* h, const int32_t* idx, int32_t n, const int16_t* d_chunk, float* d_logits, float* d_probs, void* stream) {
     bool done;
-    const int rc = pool_push_check(h, idx, n, d_chunk, &done);
+    const int rc = nww_pool_push_check(h, idx, n, d_chunk, &done);
     if (rc || done) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return pool_push_dev(h, idx, n, d_chunk, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
+    return nww_pool_push_on_dev(h, idx, n, d_chunk, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
 }
 
 extern "C" int nww_stream_push_some(nww_handle* h, const int32_t* idx, int32_t n, const int16_t* chunk, float* logits, float* probs) {
     bool done;
-    int rc = pool_push_check(h, idx, n, chunk, &done);
+    int rc = nww_pool_push_check(h, idx, n, chunk, &done);
     if (rc || done) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     StreamState* st = h->stream;
@@ -462,7 +467,7 @@ extern "C" int nww_stream_push_some(nww_handle* h, const int32_t* idx, int32_t n
     rc = nww_h2d_small(h, st->d_chunk, chunk, (size_t)n * st->hop * sizeof(int16_t), s);
     if (rc) return rc;
     float* out = st->d_pool_out;
-    rc = pool_push_dev(h, idx, n, st->d_chunk, logits ? out : nullptr, probs ? out + st->S : nullptr, s);
+    rc = nww_pool_push_on_dev(h, idx, n, st->d_chunk, logits ? out : nullptr, probs ? out + st->S : nullptr, s);
     if (!rc && logits) HIP_TRY(h, hipMemcpyAsync(logits, out, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     if (!rc && probs) HIP_TRY(h, hipMemcpyAsync(probs, out + st->S, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));

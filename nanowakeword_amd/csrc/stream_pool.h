@@ -18,6 +18,15 @@ enum { POOL_NOT_FULL = 0,    // its ring holds no window yet: the chunk is store
 // dense: its row in the head's input and output (list order).  slot and dense are -1 for POOL_NOT_FULL.
 struct PoolEntry { int32_t stream, pos, lm_row, group, slot, dense; };
 
+#ifdef __HIPCC__
+#define POOL_HD __host__ __device__
+#else
+#define POOL_HD
+#endif
+// where an entry's window starts in the PCM rings [S][2 W], in units of 8 samples (16 bytes), from the entry alone: what win8 holds in
+// slot order, and what a reader that walks the entries in list order (the cascade's pool select, cascade.hip) computes for itself
+POOL_HD inline int32_t pool_entry_win8(const PoolEntry& e, int W) { return (int32_t)(((int64_t)e.stream * 2 * W + e.pos) / 8); }
+
 struct PoolCall {
     std::vector<PoolEntry> entries;      // [n]
     std::vector<int32_t> win8;           // [m], slot order: the window's offset in the PCM rings, in units of 8 samples (16 bytes)
@@ -108,7 +117,7 @@ inline void pool_plan_push(const StreamPool& p, const int32_t* idx, int n, PoolC
         if (e.group == POOL_NOT_FULL) continue;
         e.slot = e.group == POOL_WHOLE ? whole++ : c.n_whole + primed++;
         e.dense = dense++;
-        c.win8[(size_t)e.slot] = (int32_t)(((int64_t)e.stream * 2 * p.W + e.pos) / 8);
+        c.win8[(size_t)e.slot] = pool_entry_win8(e, p.W);
         c.out[(size_t)e.dense] = i;
     }
 }

@@ -22,7 +22,7 @@ from typing import Dict, List, Mapping, Optional, Union
 
 import numpy as np
 
-from .config import cascade_open
+from .config import cascade_open, cascade_pool_open
 
 N_WARMUP_PREDICTIONS = 5        # nanointerpreter.py:690,789
 PREDICTION_HISTORY = 30         # nanointerpreter.py:1002
@@ -474,6 +474,17 @@ def _filter_streams(score: np.ndarray, history: np.ndarray, patience: int, thres
         score[nz & (score >= threshold) & recent] = 0.0
 
 
+def _filter_by_count(score: np.ndarray, history: np.ndarray, cnt: np.ndarray, ids: np.ndarray, patience: int, threshold: float,
+                     debounce_time: float, hop: int):
+    """_filter_streams for streams that each hold their own number of scores: score [n] in place for the streams ids [n], whose latest
+    cnt[i] scores are the last rows of history [PREDICTION_HISTORY][S].  Streams that hold equally many share one call of the filter."""
+    for c in np.unique(cnt):
+        g = np.flatnonzero(cnt == c)
+        part = score[g]
+        _filter_streams(part, history[PREDICTION_HISTORY - int(c):, ids[g]], patience, threshold, debounce_time, hop)
+        score[g] = part
+
+
 class StreamBatch:
     """S lock-step audio streams scored together on one GPU: the batched form of the E2E branch of
     ``NanoInterpreter.predict`` (nanointerpreter.py:735-814).  The raw-audio windows live in device rings
@@ -585,11 +596,7 @@ class StreamPool:
                 raise ValueError("`threshold` must be provided when using `patience` or `debounce_time`.")
             if patience and debounce_time > 0:
                 raise ValueError("`patience` and `debounce_time` cannot be used together.")
-            for c in np.unique(cnt):                              # streams that hold equally many scores share StreamBatch's own filter
-                g = np.flatnonzero(cnt == c)
-                part = score[g]
-                _filter_streams(part, self.history[PREDICTION_HISTORY - int(c):, ids[g]], patience, threshold, debounce_time, self.hop)
-                score[g] = part
+            _filter_by_count(score, self.history, cnt, ids, patience, threshold, debounce_time, self.hop)
         self.history[:-1, ids] = self.history[1:, ids]
         self.history[-1, ids] = score
         self.count[ids] = np.minimum(cnt + 1, PREDICTION_HISTORY)
@@ -655,6 +662,84 @@ class CascadeStreamBatch:
                 _filter_streams(score, self.history[n], 0, threshold[n], debounce_time, self.hop)
             self.history[n] = np.vstack([self.history[n], score[None]])[-PREDICTION_HISTORY:]
             self.post_processed_scores[n] = score
+        return final
+
+    def close(self):
+        self.cascade.stream_close()
+
+
+class CascadeStreamPool(StreamPool):
+    """StreamPool through a gate + verifier pair (session.HipCascade.stream_push_some): S streams that push, join and leave on their own,
+    the verifier scoring only the listed streams the gate opens.  Every slot behaves exactly like a ``CascadeStreamBatch`` of one stream
+    fed that slot's chunks: raw score 0 until the slot's own window is full, each model's first five predictions zeroed, the verifier
+    zeroed wherever the gate's post-warm-up score is below the threshold, patience / debounce per model against the slot's own 30-entry
+    history.  ``attach`` / ``detach`` are StreamPool's: a slot handed out inherits neither audio nor filter state.  ``push`` returns
+    {gate_name: scores [n], name: scores [n]}."""
+
+    def __init__(self, cascade, n_streams: int, window_samples: int = 16000, hop_samples: int = HOP_SAMPLES, gate_name: str = "gate",
+                 name: str = "model"):
+        if gate_name == name:
+            raise ValueError("the gate and the verifier need two names")
+        self.cascade, self.S, self.window, self.hop = cascade, int(n_streams), int(window_samples), int(hop_samples)
+        self.gate_name, self.name = gate_name, name
+        cascade.stream_open(self.S, self.window, self.hop)
+        self.attached = np.zeros(self.S, bool)
+        names = (gate_name, name)
+        self.history = {n: np.zeros((PREDICTION_HISTORY, self.S), np.float32) for n in names}   # per stream: its latest `count` scores in the last rows
+        self.count = np.zeros(self.S, np.int64)                 # one count for both models: every push scores both
+        self.filled = np.zeros(self.S, np.int64)
+        self.raw_scores = {n: np.zeros(self.S, np.float32) for n in names}
+        self.post_processed_scores = {n: np.zeros(self.S, np.float32) for n in names}
+        self.n_open = 0
+
+    def reset(self, ids=None):
+        """New session for the listed streams (None: every stream, which also puts the gate's batch back in lock-step)."""
+        if ids is None:
+            self.cascade.stream_reset()
+            ids = np.arange(self.S)
+        else:
+            ids = self._ids(ids)
+            self.cascade.stream_reset_some(ids)
+        self.count[ids] = 0
+        self.filled[ids] = 0
+        for n in (self.gate_name, self.name):
+            self.history[n][:, ids] = 0.0
+            self.raw_scores[n][ids] = 0.0
+            self.post_processed_scores[n][ids] = 0.0
+
+    def push(self, ids, chunk: np.ndarray, patience: dict = {}, threshold: dict = {}, debounce_time: float = 0.0) -> Dict[str, np.ndarray]:
+        """ids: strictly ascending stream numbers [n]; chunk int16 [n, hop], row i for stream ids[i] -> {name: post-processed scores [n]};
+        patience / threshold are keyed by model name, as in predict()"""
+        if not isinstance(chunk, np.ndarray):
+            raise ValueError("Input audio `x` must be a Numpy array.")
+        if (patience or debounce_time > 0) and not threshold:
+            raise ValueError("`threshold` must be provided when using `patience` or `debounce_time`.")
+        if patience and debounce_time > 0:
+            raise ValueError("`patience` and `debounce_time` cannot be used together.")
+        ids = self._ids(ids)
+        gate_probs, _, probs, self.n_open = self.cascade.stream_push_some(ids, chunk)
+        self.filled[ids] += self.hop
+        full = self.filled[ids] >= self.window
+        cnt = self.count[ids]
+        out = {}
+        for n, raw in ((self.gate_name, gate_probs), (self.name, probs)):
+            raw = raw.astype(np.float32)
+            if n == self.name:
+                raw[~cascade_pool_open(out[self.gate_name], full, self.cascade.gate_threshold)] = 0.0   # the gate's post-warm-up score decides
+            self.raw_scores[n][ids] = raw
+            score = raw.copy()
+            score[cnt < N_WARMUP_PREDICTIONS] = 0.0
+            out[n] = score
+        final = {n: v.copy() for n, v in out.items()}
+        for n, score in final.items():
+            if n in patience:
+                _filter_by_count(score, self.history[n], cnt, ids, int(patience[n]), threshold[n], 0.0, self.hop)
+            elif debounce_time > 0 and n in threshold:
+                _filter_by_count(score, self.history[n], cnt, ids, 0, threshold[n], debounce_time, self.hop)
+            self.history[n][:-1, ids] = self.history[n][1:, ids]
+            self.history[n][-1, ids] = score
+            self.post_processed_scores[n][ids] = score
+        self.count[ids] = np.minimum(cnt + 1, PREDICTION_HISTORY)
         return final
 
     def close(self):

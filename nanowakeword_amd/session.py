@@ -698,11 +698,57 @@ class HipCascade:
     def stream_close(self):
         self.gate.stream_close()
 
-    def describe(self) -> str:
-        """The launches of one cascade call, one per line: the gate's plan, the select, the gather, the verifier's plan, the scatter"""
+    # streams that push, join and reset on their own (nww_cascade_stream_push_some): the gate's batch in any state, aligned or not
+    def stream_push_some(self, ids, chunk, gate_threshold: Optional[float] = None):
+        """ids: strictly ascending stream numbers [n]; chunk int16 [n, hop], row i for stream ids[i] -> (gate_probs [n], logits [n],
+        probs [n], n_open).  A stream whose own ring holds no window yet reads 0 / 0 / 0 and is never open; a scored one that the gate
+        closes reads -inf / 0.0 (config.cascade_pool_open); the verifier runs the open streams' windows as one batch."""
+        S, W, hop = self.gate._stream
+        ids = HipModel._stream_ids(ids)
+        n = len(ids)
+        chunk = HipModel._pcm(chunk) if n else np.zeros((0, hop), np.int16)
+        if chunk.shape != (n, hop):
+            raise ValueError(f"chunk must have shape ({n}, {hop}), got {chunk.shape}")
+        gp, logits, probs = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_stream_push_some(self.gate._h, self.verifier._h, ids.ctypes.data_as(C.c_void_p), n,
+                                                          chunk.ctypes.data_as(C.c_void_p), self._thr(gate_threshold),
+                                                          gp.ctypes.data_as(C.c_void_p), logits.ctypes.data_as(C.c_void_p),
+                                                          probs.ctypes.data_as(C.c_void_p), C.byref(n_open)))
+        return gp, logits, probs, int(n_open.value)
+
+    def stream_push_some_dev(self, ids, chunk_ptr: int, gate_probs_ptr: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0,
+                             gate_threshold: Optional[float] = None) -> int:
+        """Raw device pointers (ids stays on the host); enqueues on `stream`, which it synchronises once.  Returns n_open."""
+        ids = HipModel._stream_ids(ids)
+        n_open = C.c_int32()
+        self._check(self.lib.nww_cascade_stream_push_some_dev(self.gate._h, self.verifier._h, ids.ctypes.data_as(C.c_void_p), len(ids),
+                                                              C.c_void_p(chunk_ptr), self._thr(gate_threshold),
+                                                              C.c_void_p(gate_probs_ptr) if gate_probs_ptr else None,
+                                                              C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                              C.c_void_p(probs_ptr) if probs_ptr else None, C.byref(n_open),
+                                                              C.c_void_p(stream) if stream else None))
+        return int(n_open.value)
+
+    def stream_reset_some(self, ids):
+        """a new session for the listed streams only (the ring is the gate's)"""
+        ids = HipModel._stream_ids(ids)
+        self._check(self.lib.nww_cascade_stream_reset_some(self.gate._h, self.verifier._h, ids.ctypes.data_as(C.c_void_p), len(ids)))
+
+    def stream_filled_of(self, i: int) -> int:
+        """samples stream i has seen since open / its last reset"""
+        return self.gate.stream_filled(int(i))
+
+    def describe(self, pool: bool = False) -> str:
+        """The launches of one cascade call, one per line: the gate's plan, the select, the gather, the verifier's plan, the scatter.
+        pool: of a stream_push_some call, whose select walks the table of the gate's pool call (the gate's own data movement around its
+        plan is the pool's: DESIGN.md 4.8d)"""
         g = self.gate.describe_plan().strip().split("\n")
         v = self.verifier.describe_plan().strip().split("\n")
-        return "\n".join(g + ["cascade_select:count + place - ascending indices of the windows with float(gate_prob) >= threshold, closed fill",
+        select = ("cascade_pool_select:count + place over the call's table - ring offsets and entries of the scored streams with "
+                  "float(gate_prob) >= threshold, ascending; 0 fill without a window, closed fill" if pool else
+                  "cascade_select:count + place - ascending indices of the windows with float(gate_prob) >= threshold, closed fill")
+        return "\n".join(g + [select,
                               "cascade_gather:open windows -> the verifier's PCM staging"] + v +
                          ["cascade_scatter:the verifier's logits / probabilities -> their windows"]) + "\n"
 

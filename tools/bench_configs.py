@@ -10,7 +10,9 @@ NWW_REC_SHARED = NWW_STREAM_INC = 0 and against the package of a built checkout 
 profiles/raw_recording_bench_configs.jsonl.
 --cascade [out]: a gate + verifier cascade against the gate alone and the verifier alone (cascade_main) -> profiles/cascade_bench_configs.jsonl.
 --stream-pool [out]: 1024 streams per tick, lock-step against push_some (all streams, a random half) against whole-window re-scoring
-(stream_pool_main) -> profiles/stream_pool_bench_configs.jsonl."""
+(stream_pool_main) -> profiles/stream_pool_bench_configs.jsonl.
+--cascade-pool [out]: 1024 streams per tick through a gate + verifier pair, nww_cascade_stream_push_some_dev against push_some on both
+models against the lock-step cascade (cascade_pool_main) -> profiles/cascade_pool_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -706,7 +708,164 @@ def stream_pool_main(out_path):
     sys.stdout.write(text)
 
 
+CPOOL_OPEN = ("5", "50")               # per cent of the scored streams the thresholds open, from the gate's own score quantiles
+
+
+def cascade_pool_child():
+    """One process: per verifier, POOL_STREAMS streams, 1 s windows, 80 ms hops, device-resident chunks, the CAS_GATE gate; every leg on a
+    fresh batch filled by pushes that list every stream, ms per tick as the median of RNN_STEPS device-event timings behind RNN_WARMUP
+    warm-up calls.  Settings: every stream listed / a random half listed (eight seeded halves in turn).  Legs: gate_some - the gate's
+    push_some alone; new - nww_cascade_stream_push_some_dev at thresholds that open about 5 % and 50 % of the scored streams; today - what
+    the entry points before it allow, push_some on the gate plus push_some on a verifier batch for every listed stream; lock -
+    nww_cascade_stream_push_dev with all streams; verifier_open - the verifier's forward_pcm_dev alone on as many windows as the new call
+    opened."""
+    import torch
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipCascade, HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    S = POOL_STREAMS
+    parts = [torch.from_numpy(synth_pcm("speechlike", S, REC_HOP, seed=20 + i)).to(dev) for i in range(4)]
+    clips = torch.from_numpy(synth_pcm("speechlike", S, REC_W, seed=30)).to(dev)
+    rng = np.random.default_rng(5)
+    every = np.arange(S, dtype=np.int32)
+    halves = [np.sort(rng.permutation(S)[:S // 2]).astype(np.int32) for _ in range(8)]
+    half_parts = [[p[torch.from_numpy(h.astype(np.int64)).to(dev)].contiguous() for p in parts] for h in halves]
+    listed = {"all": lambda i: (every, parts[i % 4]), "half": lambda i: (halves[i % 8], half_parts[i % 8][i % 4])}
+    fill = REC_W // REC_HOP + 1
+    gcfg = HeadConfig(*CAS_GATE)
+
+    def timed(ts, step):
+        for i in range(RNN_WARMUP):
+            step(i)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        opened = []
+        for i, (e0, e1) in enumerate(ev):
+            e0.record(ts); opened.append(step(RNN_WARMUP + i)); e1.record(ts)
+        torch.cuda.synchronize()
+        return round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4), opened
+
+    for head, shape in CAS_VERIFIERS:
+        gate = HipModel(gcfg, fe, device=0, state_dict=synth_state_dict(gcfg), window=window, mel_fb=fb)
+        cfg = HeadConfig(head, shape)
+        ver = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+        cas = HipCascade(gate, ver)
+        ts = torch.cuda.Stream(dev)
+        stream = ts.cuda_stream
+        gp, lg, pr = (torch.empty(S, dtype=torch.float32, device=dev) for _ in range(3))
+        gate.reserve(S, REC_W); ver.reserve(S, REC_W)
+        out = {"verifier": head, "gate": CAS_GATE[0], "streams": S, "window": REC_W, "hop": REC_HOP}
+
+        def fresh(with_verifier=False):
+            gate.stream_open(S, REC_W, REC_HOP)
+            if with_verifier:
+                ver.stream_open(S, REC_W, REC_HOP)
+            for i in range(fill):
+                gate.stream_push_some_dev(every, parts[i % 4].data_ptr(), lg.data_ptr(), gp.data_ptr(), stream)
+                if with_verifier:
+                    ver.stream_push_some_dev(every, parts[i % 4].data_ptr(), lg.data_ptr(), pr.data_ptr(), stream)
+            torch.cuda.synchronize()
+
+        fresh()
+        q = np.sort(gp.cpu().numpy().astype(np.float64))
+        thr = {"5": float(q[-(S // 20)]), "50": float(q[S // 2])}
+        out["thresholds"] = thr
+        out["gate_route"] = gate.stream_pool_stats()[1]
+        gate.stream_close()
+        for setting, pick in listed.items():
+            def gate_some(i):
+                ids, chunk = pick(i)
+                gate.stream_push_some_dev(ids, chunk.data_ptr(), lg.data_ptr(), gp.data_ptr(), stream)
+
+            def today(i):
+                ids, chunk = pick(i)
+                gate.stream_push_some_dev(ids, chunk.data_ptr(), 0, gp.data_ptr(), stream)
+                ver.stream_push_some_dev(ids, chunk.data_ptr(), lg.data_ptr(), pr.data_ptr(), stream)
+
+            fresh()
+            out[f"gate_some_{setting}_ms"], _ = timed(ts, gate_some)
+            gate.stream_close()
+            fresh(with_verifier=True)
+            out[f"today_{setting}_ms"], _ = timed(ts, today)
+            out["verifier_route"] = ver.stream_pool_stats()[1]
+            gate.stream_close(); ver.stream_close()
+            for pct in CPOOL_OPEN:
+                def new(i):
+                    ids, chunk = pick(i)
+                    return cas.stream_push_some_dev(ids, chunk.data_ptr(), gp.data_ptr(), lg.data_ptr(), pr.data_ptr(), stream, gate_threshold=thr[pct])
+
+                fresh()
+                out[f"new_{setting}_{pct}_ms"], opened = timed(ts, new)
+                gate.stream_close()
+                n_open = int(np.median(opened))
+                out[f"new_{setting}_{pct}_open"] = n_open
+                out[f"verifier_open_{setting}_{pct}_ms"], _ = timed(
+                    ts, lambda i: ver.forward_pcm_dev(clips.data_ptr(), max(n_open, 1), REC_W, lg.data_ptr(), pr.data_ptr(), stream))
+        for pct in CPOOL_OPEN:
+            fresh()
+            out[f"lock_{pct}_ms"], opened = timed(
+                ts, lambda i: cas.stream_push_dev(parts[i % 4].data_ptr(), gp.data_ptr(), lg.data_ptr(), pr.data_ptr(), stream, gate_threshold=thr[pct]))
+            out[f"lock_{pct}_open"] = int(np.median(opened))
+            gate.stream_close()
+        print(json.dumps(out), flush=True)
+        gate.close(); ver.close()
+
+
+def cascade_pool_main(out_path):
+    """RNN_REPEATS fresh child processes, one after another, each under its own time limit (the protocol of --cascade); per verifier and
+    setting the medians of the repeats and their spread (max - min, the largest of the legs), and per threshold (a) the new call, (b) today's
+    two push_some calls, (c) the lock-step cascade with all streams as the floor, and the share of (a) that is neither the gate's
+    push_some nor the verifier on the open windows: the select, the count's read-back, the gather and the scatter."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--cascade-pool-child"], env=dict(os.environ),
+                           cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"cascade-pool child exited {r.returncode}")
+        print(f"[cascade-pool child] {r.stdout.strip()}", file=sys.stderr, flush=True)
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")])
+    lines = []
+    for i, (head, shape) in enumerate(CAS_VERIFIERS):
+        first = runs[0][i]
+        rep = {k[:-3]: [r[i][k] for r in runs] for k in first if k.endswith("_ms")}
+        med = {k: float(np.median(v)) for k, v in rep.items()}
+        spread = max(max(v) - min(v) for v in rep.values())
+        for setting in ("all", "half"):
+            line = {"config": f"cascade pool {CAS_GATE[0]} {CAS_GATE[1][0]}x{CAS_GATE[1][1]} -> {head} {shape[0]}x{shape[1]} W={REC_W} hop={REC_HOP} "
+                              f"{POOL_STREAMS} streams, {setting} listed, ms per tick",
+                    "gate": CAS_GATE[0], "verifier": head, "streams": POOL_STREAMS, "listed": POOL_STREAMS if setting == "all" else POOL_STREAMS // 2,
+                    "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS, "thresholds": first["thresholds"],
+                    "gate_route": first["gate_route"], "verifier_route": first["verifier_route"],
+                    "ms_repeats": {k: v for k, v in rep.items() if setting in k or k.startswith("lock")},
+                    "gate_push_some_ms": round(med[f"gate_some_{setting}"], 4), "b_today_two_push_some_ms": round(med[f"today_{setting}"], 4),
+                    "spread_ms": round(spread, 4)}
+            for pct in CPOOL_OPEN:
+                a, b = med[f"new_{setting}_{pct}"], med[f"today_{setting}"]
+                line[f"open_{pct}pct"] = {
+                    "open_streams": first[f"new_{setting}_{pct}_open"], "a_new_call_ms": round(a, 4),
+                    "c_lock_step_all_streams_ms": round(med[f"lock_{pct}"], 4), "c_open_streams": first[f"lock_{pct}_open"],
+                    "verifier_on_open_windows_ms": round(med[f"verifier_open_{setting}_{pct}"], 4),
+                    "select_readback_gather_scatter_ms": round(a - med[f"gate_some_{setting}"] - med[f"verifier_open_{setting}_{pct}"], 4),
+                    "a_faster_than_b_by_ms": round(b - a, 4), "b_over_a": round(b / a, 2), "a_wins": bool(b - a > spread),
+                    "a_loses": bool(a - b > spread)}
+            lines.append(line)
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--cascade-pool-child" in sys.argv[1:]:
+        return cascade_pool_child()
+    if "--cascade-pool" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--cascade-pool"]
+        return cascade_pool_main(rest[0] if rest else os.path.join(ROOT, "profiles", "cascade_pool_bench_configs.jsonl"))
     if "--stream-pool-child" in sys.argv[1:]:
         return stream_pool_child()
     if "--stream-pool" in sys.argv[1:]:
