@@ -15,6 +15,8 @@
 // workgroups share a CU; the next k-tile's global loads travel in registers during the multiplication.  A is split
 // while it is staged into LDS (5.5 VALU ops per element, amortised over 32*CB columns); W is split once at
 // nww_finalize into the same [N][K/16][3][16] layout so its tiles are plain 16-byte copies.
+// fc1 at large M runs the PP instance instead: the CU's two workgroups as the halves of one, held in anti-phase by the barriers (below;
+// 56.4 -> 48.7 us per launch).
 // H2 instances ("f16x3", GemmArgs::h2): the operands, scaled by powers of two fixed at plan time (a_scale on load, the weights
 // at pack time; c_scale undoes both on the way out), are split into TWO binary16 terms hi = RN16(v), lo = RN16(v - hi) holding
 // 22-23 of the 24 significant bits; hi*hi, hi*lo, lo*hi go to v_mfma_f32_32x32x16_f16 - half the matrix instructions, the
@@ -44,7 +46,7 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 #ifdef X3_TRACE      // tools/ubench/gemm_x3_trace.hip: s_memtime stamps of workgroup 0's first k-tiles (phase boundaries per wave)
-__device__ unsigned long long x3_trace_buf[4 * 16 * 4];
+__device__ unsigned long long x3_trace_buf[8 * 16 * 4];      // [wave (of up to eight)][k-tile][stamp]
 #define X3_STAMP(kt_rel, ph)                                                                                        \
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && (kt_rel) < 16 && (threadIdx.x & 63) == 0)        \
         x3_trace_buf[((threadIdx.x >> 6) * 16 + (kt_rel)) * 4 + (ph)] = __builtin_readcyclecounter();
@@ -141,8 +143,15 @@ __global__ void __launch_bounds__(256) split_weights_h2_kernel(const float* __re
 // latency - 25 dependent k-tiles of ~2.4 us each - and runs 32-column tiles (4x the workgroups) with eight k-tiles in
 // flight (only rows 0..63 of A are staged, so a stage is 16 registers).  Per-output summation order is the same in every instance: same k-tile sequence, same products, same
 // split-K chunks - results stay bit-identical across batch sizes.
-template <int CB, int NST, int ACT, bool H2>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(184))) gemm_x3_kernel(GemmArgs g) {
+//
+// PP ("ping-pong", fc1 at large M: CB = 4, NST = 1, two-term, blocked A, split-K): the two 4-wave workgroups a CU holds become the
+// two halves of ONE 8-wave workgroup; half hf = wave >> 2 owns row tile 2 blockIdx.x + hf, its own LDS region and exactly the
+// per-half code below.  Half 1 executes one barrier more in front of the loop and half 0 one more behind it, so the two barriers
+// of a k-tile are the boundaries at which the halves swap roles: one multiplies tile k while the other waits for, splits and stores
+// its tile - the anti-phase that two independent workgroups do not keep.  Every wave executes 2 T + 1 barriers
+// whatever its rows: a half or a wave beyond M stages clamped rows and skips only the MFMAs and the stores.
+template <int CB, int NST, int ACT, bool H2, bool PP = false>
+__global__ void __launch_bounds__(PP ? 512 : 256) __attribute__((amdgpu_num_vgpr(184))) gemm_x3_kernel(GemmArgs g) {
     constexpr int NT = X3A<H2>::NT, X3_ROW = X3A<H2>::ROW, PB = 2 * NT;   // terms, LDS row bytes, 16-byte pieces of a row's 16-k block
     // accumulators in AGPRs: two workgroups share a CU, and one's bf16 MFMAs run beside the other's split/stage VALU
     // work only in the AGPR form (tools/ubench/mfma_valu_overlap.hip).  The empty asm flips hipcc's
@@ -153,11 +162,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(184))) gem
     constexpr int WPIECES = BN * 2 * PB;                       // 16-byte pieces of a W tile (32 k x NT terms per row)
     constexpr int WLD = (WPIECES + 255) / 256;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    auto As = [&](int) { return smem; };
-    auto Ws = [&](int) { return smem + X3_BM * X3_ROW; };
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hf = PP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;      // the half of a ping-pong workgroup
+    unsigned char* const region = smem + hf * ((X3_BM + BN) * X3_ROW);
+    auto As = [&](int) { return region; };
+    auto Ws = [&](int) { return region + X3_BM * X3_ROW; };
+    const int tid = threadIdx.x & 255, lane = tid & 63;
+    const int wave = PP ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int i = lane & 31, h = lane >> 5;
-    const int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
+    const int bxi = PP ? 2 * blockIdx.x + hf : blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
     // (an XCD-aware tile map - every XCD keeping a few W chunks in its L2 - measured no change: rocprofv3 FETCH_SIZE of fc1 is A's
     // 211 MB already, the split W is served from L2 as it is)
     const int bm = bxi * X3_BM, bn = byi * BN;
@@ -175,7 +187,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(184))) gem
     const float* arow[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-        arow[q] = g.a_blocked ? g.A + ((size_t)(bm >> 7) * g.a_blocked * 128 + lr + 32 * q) * 32 + 4 * lq
+        arow[q] = g.a_blocked ? g.A + ((size_t)min(bm >> 7, (g.M - 1) >> 7) * g.a_blocked * 128 + lr + 32 * q) * 32 + 4 * lq      // (a half beyond M: the last tile)
                               : g.A + (size_t)min(bm + lr + 32 * q, g.M - 1) * g.lda + 4 * lq;
     const int a_kstep = g.a_blocked ? 128 * 32 : 32;           // floats between consecutive k-tiles of a row
     constexpr int AQ = (NST > 1 && CB == 1) ? 2 : 4;           // the small-M instance (M <= 64) stages rows 0..63 only
@@ -270,6 +282,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(184))) gem
             }
         }
     };
+    if (PP && hf) __syncthreads();                               // half 1 runs one phase behind half 0
     for (int kt = kt_begin; kt < kt_end; kt += NST) {
 #pragma unroll
         for (int q = 0; q < NST; ++q) {
@@ -278,14 +291,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(184))) gem
                 __syncthreads();                               // everyone is done reading the previous tile
                 X3_STAMP(kt + q - kt_begin, 1)
                 lstore(0, st[q]);
+                if (PP) gload(min(kt + q + NST, kt_end - 1), st[q]);        // a phase earlier than below: it lands under the other half's MFMAs AND this half's
                 __syncthreads();
                 X3_STAMP(kt + q - kt_begin, 2)
             }
-            gload(min(kt + q + NST, kt_end - 1), st[q]);
-            if (kt + q < kt_end && (NST == 1 || has_rows)) multiply();
+            if (!PP) gload(min(kt + q + NST, kt_end - 1), st[q]);
+            if (kt + q < kt_end && ((NST == 1 && !PP) || has_rows)) multiply();
             X3_STAMP(kt + q - kt_begin, 3)
         }
     }
+    if (PP && !hf) __syncthreads();                              // ... and half 0 waits out half 1's last multiply: 2 T + 1 barriers each
 
     const int m0 = bm + wave * 32;
     if (m0 >= g.M) return;
@@ -554,6 +569,12 @@ hipError_t launch_gemm_x3(const GemmArgs& g, hipStream_t s) {
     const int bn = 32 * cb;
     dim3 grid((g.M + X3_BM - 1) / X3_BM, (g.N + bn - 1) / bn, sk);
     const size_t lds = (size_t)(X3_BM + bn) * row_b;
+    if (a.pp && h2 && a.a_blocked && cb == 4 && sk > 1) {       // fc1 at large M: two row tiles per workgroup, in anti-phase (the kernel comment)
+        hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(gemm_x3_kernel<4, 1, ACT_NONE, true, true>), 2 * lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((gemm_x3_kernel<4, 1, ACT_NONE, true, true>), dim3((grid.x + 1) / 2, grid.y, sk), dim3(512), 2 * lds, s, a);
+        return hipGetLastError();
+    }
     switch (cb) {
         case 2: X3_ACT(2, 1, grid, lds) break;
         case 3: X3_ACT(3, 1, grid, lds) break;

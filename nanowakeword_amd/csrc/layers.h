@@ -85,6 +85,9 @@ struct GemmArgs {
     // the fused conv trunk) instead of row-major - every tile load is one contiguous 16 KB block.  With row-major A
     // (row stride 51 KB for fc1) the same loads reach 2.5-2.9 TB/s (tools/ubench/strided_read.hip)
     int a_blocked = 0;
+    // != 0 (NWW_GEMM_PP, the default): the bulk two-term split-K shape with blocked A and 128-column tiles (fc1 at M > 64) runs two row
+    // tiles per 8-wave workgroup, each half staging under the other's MFMAs (gemm_x3.hip); 0: one row tile per 4-wave workgroup
+    int pp = 0;
     // dual GEMM (BcResNet block): C = (A2 W2^T * alpha2 + beta2) + rscale * act((A W^T + bias) * alpha + beta), the second
     // product (shortcut branch) computed by the same workgroup instead of a separate GEMM + a residual round trip
     const float* A2 = nullptr; int lda2 = 0; const float* W2 = nullptr; int K2 = 0;

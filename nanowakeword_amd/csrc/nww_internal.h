@@ -290,7 +290,7 @@ inline std::vector<QnBlock> nww_quartznet_blocks(const nww_config& c) {
 // The run-time knobs, read from the environment on the first call (nww_plan.hip).  Each selection knob defaults to the
 // specialised kernel; setting it picks a general one.
 struct Knobs {
-    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, raw_fused, conv2s_x3, rnn_ih_fused, mha_mfma, bc_front, bc_chain, tail;
+    int trunk, conv_mfma, conv3_x3, gemm_x3, lin_x3, ffn_fused, attn_fused, merge_fused, qn_fused, raw_fused, conv2s_x3, rnn_ih_fused, mha_mfma, bc_front, bc_chain, tail, gemm_pp;
     int stream_inc;                            // NWW_STREAM_INC (nww_stream.hip)
     int rec_shared;                            // NWW_REC_SHARED (nww_recording.hip)
     int f16_range_log2;                        // test instrument: NWW_F16_RANGE_LOG2

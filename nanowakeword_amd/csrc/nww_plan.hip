@@ -9,7 +9,7 @@ const Knobs& nww_knobs() {
         r.trunk = env("NWW_TRUNK", 1); r.conv_mfma = env("NWW_CONV_MFMA", 1); r.conv3_x3 = env("NWW_CONV3_X3", 1);
         r.gemm_x3 = env("NWW_GEMM_X3", 1); r.lin_x3 = env("NWW_LIN_X3", 1); r.ffn_fused = env("NWW_FFN_FUSED", 1);
         r.attn_fused = env("NWW_ATTN_FUSED", 1); r.merge_fused = env("NWW_MERGE_FUSED", 1); r.qn_fused = env("NWW_QN_FUSED", 1); r.raw_fused = env("NWW_RAW_FUSED", 1); r.conv2s_x3 = env("NWW_CONV2S_X3", 1); r.rnn_ih_fused = env("NWW_RNN_IH_FUSED", 1); r.mha_mfma = env("NWW_MHA_MFMA", 1); r.bc_front = env("NWW_BC_FRONT", 1);
-        r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3); r.rec_shared = env("NWW_REC_SHARED", 1);
+        r.bc_chain = env("NWW_BC_CHAIN", 1); r.tail = env("NWW_TAIL", 1); r.stream_inc = env("NWW_STREAM_INC", 3); r.rec_shared = env("NWW_REC_SHARED", 1); r.gemm_pp = env("NWW_GEMM_PP", 1);
         r.f16_range_log2 = env("NWW_F16_RANGE_LOG2", 16);
         return r;
     }();
@@ -163,6 +163,7 @@ void add_gemm(PlanCtx& p, const std::string& name, int in_id, int out_id, int ro
         g.Wx3 = wx3;
         if (h2) { g.h2 = 1; g.a_scale = h2_as; g.c_scale = 1.0f / (h2_as * h2_ws); g.a_clamp = o.a_bound_assumed ? (float)a_bound : 0.0f; }
         g.a_blocked = a_blocked;
+        g.pp = nww_knobs().gemm_pp;
         g.splitk = gemm_recommended_splitk(g.M, N, K, r.cu_count);
         // split-operand layers: chunks of ~16-25 k-tiles, so that a small batch's chunk is ONE round of gemm_x3_chain_kernel
         // (32 k-tiles in flight) on a few dozen CUs - K = 12 800: 16 chunks of 25, K = 6 464: 12 of 17, K = 3 920 (C1): 7 of 18
