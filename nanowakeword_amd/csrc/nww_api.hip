@@ -288,6 +288,17 @@ extern "C" int nww_describe_plan(const nww_handle* h, char* buf, int32_t buflen)
 }
 
 // ------------------------------------------------------------------------------------------ workspace / run
+// a device buffer that grows on demand: *p holds at least `bytes` (its contents are lost when it grows)
+int nww_grow(nww_handle* h, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return NWW_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIP_TRY(h, hipMalloc(p, bytes + 16));
+    *cap = bytes;
+    return NWW_OK;
+}
+
 int nww_ensure_ws(nww_handle* h, int B, int N) {
     if (B <= h->cap_B && N <= h->cap_N) return NWW_OK;
     const int nB = B > h->cap_B ? B : h->cap_B, nN = N > h->cap_N ? N : h->cap_N;

@@ -52,10 +52,10 @@ int cas_window_fits(nww_handle* v, nww_handle* h, const char* who, int W, int ho
 // 1: the gate probabilities a _dev caller did not ask for, or nww_cascade_select's uploaded scores; 0: none)
 // (lists = 2: a pool call's two index lists, ring offsets [n] then entries [n])
 int cas_state(nww_handle* v, long long n, int planes, int lists = 1) {
-    int rc = nww_rec_grow(v, reinterpret_cast<void**>(&v->d_cas_idx), &v->cas_idx_bytes, (size_t)lists * n * sizeof(int32_t));
+    int rc = nww_grow(v, reinterpret_cast<void**>(&v->d_cas_idx), &v->cas_idx_bytes, (size_t)lists * n * sizeof(int32_t));
     if (rc) return rc;
     if (planes > 0) {
-        rc = nww_rec_grow(v, reinterpret_cast<void**>(&v->d_cas_out), &v->cas_out_bytes, (size_t)planes * n * sizeof(float));
+        rc = nww_grow(v, reinterpret_cast<void**>(&v->d_cas_out), &v->cas_out_bytes, (size_t)planes * n * sizeof(float));
         if (rc) return rc;
     }
     if (!v->d_cas_counts) HIP_TRY(v, hipMalloc(reinterpret_cast<void**>(&v->d_cas_counts), CASCADE_COUNT_INTS * sizeof(int32_t) + 16));
@@ -157,13 +157,10 @@ int cas_stream_push_dev(nww_handle* g, nww_handle* v, const int16_t* d_chunk, do
     rc = nww_stream_push_dev(g, d_chunk, nullptr, d_gate_probs, s);
     if (rc) return cas_gate_fail(g, v, rc);
     if (n_open_out) *n_open_out = 0;
-    if (st->filled < W) {       // the ring holds no window yet: 0 for both models, as nww_stream_push reports
-        if (d_logits) HIP_TRY(v, hipMemsetAsync(d_logits, 0, (size_t)S * sizeof(float), s));
-        if (d_probs) HIP_TRY(v, hipMemsetAsync(d_probs, 0, (size_t)S * sizeof(float), s));
-        return NWW_OK;
-    }
+    const RingState& ring = st->pool.all;           // the push ran, so the batch is aligned: every stream's state
+    if (ring.filled < W) return nww_zero_scores(v, d_logits, d_probs, S, s);      // no window yet: 0 for both models, as nww_stream_push reports
     // every stream's window is the W samples at ring + pos of its row (double-written ring), after the push has moved pos
-    return cas_verify(v, d_gate_probs, S, thr, st->d_ring + st->pos, (size_t)2 * W, W, S, d_logits, d_probs, n_open_out, s);
+    return cas_verify(v, d_gate_probs, S, thr, st->d_ring + ring.pos, (size_t)2 * W, W, S, d_logits, d_probs, n_open_out, s);
 }
 
 // The checks of a pool call that need no device, in the order the header gives: nothing has touched a ring when one of them fails.
@@ -196,11 +193,7 @@ int cas_pool_push_dev(nww_handle* g, nww_handle* v, const int32_t* idx, int n, c
     rc = nww_pool_push_on_dev(g, idx, n, d_chunk, nullptr, d_gate_probs, s, &tab, &m);
     if (rc) return cas_gate_fail(g, v, rc);
     if (n_open_out) *n_open_out = 0;
-    if (m == 0) {               // no listed stream holds a window yet: 0 for both models, nothing to select
-        if (d_logits) HIP_TRY(v, hipMemsetAsync(d_logits, 0, (size_t)n * sizeof(float), s));
-        if (d_probs) HIP_TRY(v, hipMemsetAsync(d_probs, 0, (size_t)n * sizeof(float), s));
-        return NWW_OK;
-    }
+    if (m == 0) return nww_zero_scores(v, d_logits, d_probs, n, s);      // no listed stream holds a window yet: 0 for both models, nothing to select
     int32_t* ring8 = v->d_cas_idx;
     int32_t* entry = v->d_cas_idx + n;
     hipError_t e = launch_cascade_pool_select(tab, d_gate_probs, n, thr, W, ring8, entry, v->d_cas_counts, d_logits, d_probs, s);
@@ -325,7 +318,7 @@ extern "C" int nww_cascade_forward_recording(nww_handle* g, nww_handle* v, const
     hipStream_t s = v->own_stream;
     // the recording goes up once, in pieces of 32 MiB, as in nww_forward_recording; the tail no window reads stays behind
     const size_t used = (size_t)((nW - 1) * hop + window), piece = (size_t)16 << 20;
-    rc = nww_rec_grow(v, reinterpret_cast<void**>(&v->d_rec_pcm), &v->rec_pcm_bytes, used * sizeof(int16_t));
+    rc = nww_grow(v, reinterpret_cast<void**>(&v->d_rec_pcm), &v->rec_pcm_bytes, used * sizeof(int16_t));
     if (!rc) rc = cas_state(v, nW, 3);
     if (rc) return rc;
     for (size_t o = 0; o < used; o += piece)

@@ -4,7 +4,8 @@
 // nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
 // nww_cascade.hip: gate + verifier cascades (nww_cascade_*);
 // stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); stream_pool.h: the
-// per-stream state of a batch whose streams push and reset on their own (host-only too, used by nww_stream.hip); plan_host.h: the
+// one ring state of a stream batch, moved by its lock-step calls and by the calls whose streams push and reset on their own (host-only
+// too, used by nww_stream.hip and read by nww_cascade.hip); plan_host.h: the
 // planner's arithmetic on the weights' values (host-only too, used by nww_plan.hip and nww_weights.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,24 +65,24 @@ struct HopView {
     float* seq_new = nullptr; const float* seq_prev = nullptr; int a3_lo = 0, a3_hi = -1, a3_shift = 0;
 };
 
-// An open stream batch: S lock-step streams, a window of W samples, a score per hop.  nww_stream_open creates it, nww_stream_close frees
-// its device memory and deletes it, nww_stream_reset rewinds it.
+// An open stream batch: S streams, a window of W samples, a score per hop.  nww_stream_open creates it, nww_stream_close frees its device
+// memory and deletes it, nww_stream_reset rewinds it.
 struct StreamState {
-    int S = 0, W = 0, hop = 0, pos = 0; long long filled = 0;
+    int S = 0, W = 0, hop = 0;
     int16_t* d_ring = nullptr; int16_t* d_chunk = nullptr;   // [S][2 * W]: sample p of a stream lives at p and p + W; a host chunk's staging [S][hop]
-    HopPlan plan;                  // what a hop keeps; each kept level has its buffers below
-    bool primed = false;           // the rings hold the previous window (false: the next full window is computed whole)
-    // log-mel ring [S][2 * lm_rows][n_mels]: frame t of the current window at row lm_pos + t and lm_rows away; a hop shifts it by plan.k
-    float* d_lm_ring = nullptr; int lm_rows = 0, lm_pos = 0;
-    // pooled conv rows [S][32][plan.a2_rows][stream_W / 4]: row R at (a2_pos + R) % a2_rows; a hop shifts them by plan.a2_shift
+    HopPlan plan;                  // what a lock-step hop keeps; each kept level has its buffers below
+    // The state of the PCM and log-mel rings - position, fill, log-mel rotation and primed, of the batch while its streams are aligned
+    // and of every stream once they are not - for the lock-step calls and the pool calls alike (stream_pool.h).
+    StreamPool pool;
+    // log-mel ring [S][2 * lm_rows][n_mels]: frame t of a stream's current window at row lm_pos + t of its ring and lm_rows away; a hop shifts it by plan.k
+    float* d_lm_ring = nullptr; int lm_rows = 0;
+    // What the lock-step path alone keeps.  Pooled conv rows [S][32][plan.a2_rows][stream_W / 4]: row R at (a2_pos + R) % a2_rows; a hop
+    // shifts them by plan.a2_shift.  The third conv's sequence output, alternating from hop to hop (HopView::seq_new).  rows_held: both
+    // hold the previous window; any pool call, reset or failed hop clears it, and the next lock-step hop computes its window whole.
     float* d_a2_ring = nullptr; int a2_pos = 0;
-    float* d_seq[2] = {nullptr, nullptr}; int seq_cur = 0;   // the third conv's sequence output, alternating from hop to hop (HopView::seq_new)
-    // Streams that push, join and reset on their own (nww_stream_push_some / nww_stream_reset_some): the per-stream state.  While the
-    // batch is aligned (StreamPool::aligned) the lock-step fields above and the pool describe the same rings: pool_synced says whether
-    // the pool's copy is current (a lock-step push or reset clears it; the next pool call takes the fields over, and hands them back
-    // when it leaves the batch aligned).  The pool keeps the PCM and log-mel rings only - not the conv-row or sequence rings.
-    StreamPool pool; bool pool_synced = false;
-    // its device side, allocated by the first pool call: the frontend's scratch [S][T][row floats], POOL_TAB_SLOTS table slots on the
+    float* d_seq[2] = {nullptr, nullptr}; int seq_cur = 0;
+    bool rows_held = false;
+    // The pool calls' device side, allocated by the first one: the frontend's scratch [S][T][row floats], POOL_TAB_SLOTS table slots on the
     // device and in pinned host memory (a call's table is written to the next slot once the event of that slot's previous call has
     // passed), and the dense [2][S] outputs of the host-pointer entry point
     float* d_lm_scratch = nullptr; unsigned char* d_tab = nullptr; unsigned char* pin_tab = nullptr; float* d_pool_out = nullptr;
@@ -207,6 +208,7 @@ void nww_prof_mark(nww_handle* h, hipStream_t s, int id_of_next);
 void nww_prof_begin(nww_handle* h);
 int nww_check_run(nww_handle* h, int B);
 int nww_ensure_ws(nww_handle* h, int B, int N);
+int nww_grow(nww_handle* h, void** p, size_t* cap, size_t bytes);       // a device buffer grown on demand to hold `bytes`
 // a forward's optional inputs
 struct RunOpts {
     bool x_frames_major = false;           // Run::x_frames_major
@@ -222,9 +224,8 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
                            size_t row_stride = 0, const RunOpts& o = RunOpts());
 int nww_h2d_small(nww_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);
 int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, hipStream_t s);
-void nww_recording_free(nww_handle* h);        // nww_recording.hip, as the next three: what nww_cascade.hip scores a gate's recording with
+void nww_recording_free(nww_handle* h);        // nww_recording.hip, as the next two: what nww_cascade.hip scores a gate's recording with
 long long nww_rec_count(long long n_samples, int W, int hop);
-int nww_rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes);
 int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
                            hipStream_t s);
 // nww_stream.hip, as the next one: the checks every push_some shares (*done: n == 0, the call is complete), and the push itself on
@@ -303,4 +304,11 @@ const Knobs& nww_knobs();
         hipError_t e_ = (expr);                                                                      \
         if (e_ != hipSuccess) return fail(h, NWW_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// the scores of n streams that hold no window yet: both outputs are 0, as the reference reports (nanointerpreter.py:785-786)
+inline int nww_zero_scores(nww_handle* h, float* d_logits, float* d_probs, size_t n, hipStream_t s) {
+    if (d_logits) HIP_TRY(h, hipMemsetAsync(d_logits, 0, n * sizeof(float), s));
+    if (d_probs) HIP_TRY(h, hipMemsetAsync(d_probs, 0, n * sizeof(float), s));
+    return NWW_OK;
+}
 

@@ -24,18 +24,6 @@ int rec_plan(nww_handle* h, int W, int hop, RecPlan& p) {
     return rc ? rc : nww_window_plan(h, W, hop, nww_knobs().rec_shared ? 1 : 0, p);
 }
 
-long long rec_count(long long n_samples, int W, int hop) { return n_samples < W ? 0 : 1 + (n_samples - W) / hop; }
-
-int rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return NWW_OK;
-    HIP_TRY(h, hipDeviceSynchronize());
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIP_TRY(h, hipMalloc(p, bytes + 16));
-    *cap = bytes;
-    return NWW_OK;
-}
-
 // One pass on the shared route: B windows whose first sample is d_pcm[0].
 int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B, int W, int hop, float* d_logits, float* d_probs, hipStream_t s) {
     const nww_config& c = h->cfg;
@@ -48,8 +36,7 @@ int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B
     // (2) every window's edge frames, with its own reflect padding, at their place in the dense tensor
     if (p.el + p.er > 0) {
         Fe2Sub sub;
-        if (p.el > 0) { sub.t0[sub.nr] = 0; sub.t1[sub.nr] = p.el; ++sub.nr; }
-        if (p.er > 0) { sub.t0[sub.nr] = p.T - p.er; sub.t1[sub.nr] = p.T; ++sub.nr; }
+        nww_hop_ranges(p.T, 0, p.el, p.er, sub);
         rc = nww_frontend_on_dev(h, d_pcm, B, W, h->d_logmel, nullptr, 1, s, nullptr, (size_t)hop, &sub);
         if (rc) return rc;
     }
@@ -61,12 +48,16 @@ int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B
     return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, o);
 }
 
-int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
-                    hipStream_t s) {
+}  // namespace
+
+long long nww_rec_count(long long n_samples, int W, int hop) { return n_samples < W ? 0 : 1 + (n_samples - W) / hop; }
+
+int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
+                           hipStream_t s) {
     RecPlan p;
     int rc = rec_plan(h, W, hop, p);
     if (rc) return rc;
-    const long long nW = rec_count(n_samples, W, hop);
+    const long long nW = nww_rec_count(n_samples, W, hop);
     if (nW == 0) return NWW_OK;
     if (max_batch <= 0) max_batch = 4096;
     const int Bmax = (int)std::min<long long>(max_batch, nW);
@@ -78,7 +69,7 @@ int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, in
     if (rc) return rc;
     if (p.shared) {
         const size_t floats = (size_t)nww_pcm_rows(h, (int)span) * nww_row_floats(h->cfg);
-        rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_pool), &h->rec_pool_bytes, floats * sizeof(float));
+        rc = nww_grow(h, reinterpret_cast<void**>(&h->d_rec_pool), &h->rec_pool_bytes, floats * sizeof(float));
         if (rc) return rc;
     }
     for (long long first = 0; first < nW; first += Bmax) {
@@ -90,15 +81,6 @@ int rec_forward_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, in
         if (rc) return rc;
     }
     return NWW_OK;
-}
-
-}  // namespace
-
-long long nww_rec_count(long long n_samples, int W, int hop) { return rec_count(n_samples, W, hop); }
-int nww_rec_grow(nww_handle* h, void** p, size_t* cap, size_t bytes) { return rec_grow(h, p, cap, bytes); }
-int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
-                           hipStream_t s) {
-    return rec_forward_dev(h, d_pcm, n_samples, W, hop, max_batch, d_logits, d_probs, s);
 }
 
 void nww_recording_free(nww_handle* h) {
@@ -113,7 +95,7 @@ extern "C" int nww_recording_windows(nww_handle* h, int32_t n_samples, int32_t w
     const int rc = rec_plan(h, window, hop, p);
     if (rc) return -rc;
     if (n_samples < 0) return -fail(h, NWW_ERR_INVALID, "a recording cannot have %d samples", n_samples);
-    const long long n = rec_count(n_samples, window, hop);
+    const long long n = nww_rec_count(n_samples, window, hop);
     return (int)n;
 }
 
@@ -142,7 +124,7 @@ extern "C" int nww_forward_recording_dev(nww_handle* h, const int16_t* d_pcm, in
     if (rc) return rc;
     if (!d_pcm || n_samples < 0) return fail(h, NWW_ERR_INVALID, "null device pointer or negative length");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return rec_forward_dev(h, d_pcm, n_samples, window, hop, max_batch, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
+    return nww_rec_forward_on_dev(h, d_pcm, n_samples, window, hop, max_batch, d_logits, d_probs, stream ? (hipStream_t)stream : h->own_stream);
 }
 
 extern "C" int nww_forward_recording(nww_handle* h, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop, int32_t max_batch,
@@ -153,21 +135,21 @@ extern "C" int nww_forward_recording(nww_handle* h, const int16_t* pcm, int32_t 
     RecPlan p;
     rc = rec_plan(h, window, hop, p);
     if (rc) return rc;
-    const long long nW = rec_count(n_samples, window, hop);
+    const long long nW = nww_rec_count(n_samples, window, hop);
     if (n_windows_out) *n_windows_out = (int32_t)nW;
     if (nW == 0) return NWW_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = h->own_stream;
     // the recording goes up once, 2 bytes per sample, in pieces of 32 MiB (16 Mi samples) - never as windows; the tail no window reads stays behind
     const size_t used = (size_t)((nW - 1) * hop + window), piece = (size_t)16 << 20;
-    rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_pcm), &h->rec_pcm_bytes, used * sizeof(int16_t));
+    rc = nww_grow(h, reinterpret_cast<void**>(&h->d_rec_pcm), &h->rec_pcm_bytes, used * sizeof(int16_t));
     if (rc) return rc;
-    rc = rec_grow(h, reinterpret_cast<void**>(&h->d_rec_out), &h->rec_out_bytes, (size_t)2 * nW * sizeof(float));
+    rc = nww_grow(h, reinterpret_cast<void**>(&h->d_rec_out), &h->rec_out_bytes, (size_t)2 * nW * sizeof(float));
     if (rc) return rc;
     for (size_t o = 0; o < used; o += piece)
         HIP_TRY(h, hipMemcpyAsync(h->d_rec_pcm + o, pcm + o, std::min(piece, used - o) * sizeof(int16_t), hipMemcpyHostToDevice, s));
     float *dl = h->d_rec_out, *dp = probs ? h->d_rec_out + nW : nullptr;
-    rc = rec_forward_dev(h, h->d_rec_pcm, (long long)used, window, hop, max_batch, dl, dp, s);
+    rc = nww_rec_forward_on_dev(h, h->d_rec_pcm, (long long)used, window, hop, max_batch, dl, dp, s);
     if (rc) return rc;
     if (logits) HIP_TRY(h, hipMemcpyAsync(logits, dl, (size_t)nW * sizeof(float), hipMemcpyDeviceToHost, s));
     if (probs) HIP_TRY(h, hipMemcpyAsync(probs, dp, (size_t)nW * sizeof(float), hipMemcpyDeviceToHost, s));

@@ -1,4 +1,5 @@
-// nww_stream.hip - batched streaming: S lock-step device rings, one score per stream and hop (nww_stream_*).
+// nww_stream.hip - batched streaming: S device rings, one score per stream and hop (nww_stream_*).  The lock-step calls push every
+// stream, the pool calls the listed ones; both move the one ring state of stream_pool.h, which also decides what a hop may reuse.
 #include "nww_internal.h"
 #include "cascade.h"
 
@@ -153,10 +154,10 @@ extern "C" int nww_stream_open(nww_handle* h, int32_t S, int32_t W, int32_t hop)
     st->S = S; st->W = W; st->hop = hop; st->plan = p;
     rc = stream_alloc(h, st);
     if (rc) { nww_stream_close(h); return rc; }     // no half-allocated stream batch stays open
-    // the pool keeps per-stream log-mel rings where the lock-step path keeps one rotation of them, for the mel heads (a raw-PCM head
-    // re-scores whole windows in pool mode)
+    // pool calls maintain the log-mel rings for the mel heads; a raw-PCM head re-scores whole windows in pool mode
     st->pool.open(S, W, hop);
-    if (p.shared && !nww_raw_head(h->cfg)) {
+    if (p.shared && nww_raw_head(h->cfg)) st->pool.keep_ring(st->lm_rows, p.k);
+    else if (p.shared) {
         int head, tail;
         pool_primed_spans(h->fe, W, p.T, p.k, p.el, p.er, head, tail);
         st->pool.keep_frames(st->lm_rows, p.T, p.k, p.el, p.er, head, tail);
@@ -170,22 +171,22 @@ extern "C" int nww_stream_reset(nww_handle* h) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipDeviceSynchronize());
     HIP_TRY(h, hipMemset(st->d_ring, 0, (size_t)st->S * 2 * st->W * sizeof(int16_t)));
-    st->pos = 0; st->filled = 0;
-    st->primed = false; st->lm_pos = 0; st->a2_pos = 0; st->seq_cur = 0;      // the next full window is computed whole
-    st->pool.aligned = true; st->pool_synced = false;                         // every stream shares one state again
+    pool_reset_all(st->pool);                                  // every stream shares one state again; the next full window is computed whole
+    st->a2_pos = 0; st->seq_cur = 0; st->rows_held = false;
     return NWW_OK;
 }
 
-extern "C" int64_t nww_stream_filled(const nww_handle* h) { return h && h->stream ? h->stream->filled : 0; }
+// (the batch's count while its streams are aligned; afterwards what it was when alignment ended)
+extern "C" int64_t nww_stream_filled(const nww_handle* h) { return h && h->stream ? h->stream->pool.all.filled : 0; }
 
 // What this hop hands to the plan's steps: the window's clip stride in the log-mel ring, and where the plan keeps pooled rows, the rings
 // at their current rotation (mode 1: the first full window fills them, 2: a hop recomputes the plan's strips only).
-static HopView stream_hop_view(const nww_handle* h, const StreamState* st, size_t x_stride) {
+static HopView stream_hop_view(const nww_handle* h, const StreamState* st, size_t x_stride, bool primed) {
     const HopPlan& p = st->plan;
     HopView v;
     v.x_stride = x_stride;
     if (!p.conv) return v;
-    v.mode = st->primed ? 2 : 1;
+    v.mode = primed ? 2 : 1;
     v.a2_ring = st->d_a2_ring; v.a2_rows = p.a2_rows; v.a2_row0 = st->a2_pos;
     v.a2_ch_stride = (size_t)p.a2_rows * (h->stream_W / 4); v.a2_clip_stride = 32 * v.a2_ch_stride;
     if (p.seq) v.seq_new = st->d_seq[st->seq_cur];
@@ -197,30 +198,27 @@ static HopView stream_hop_view(const nww_handle* h, const StreamState* st, size_
     return v;
 }
 
-// One hop on the incremental path: the invalidated frames (all of them for the first full window) -> log-mel ring -> head.
-static int stream_hop_incremental(nww_handle* h, float* d_logits, float* d_probs, hipStream_t s) {
+// One hop on the incremental path: the invalidated frames (all of them where a ring does not hold the previous window) -> log-mel ring
+// -> head.
+static int stream_hop_incremental(nww_handle* h, const LockHop& hp, float* d_logits, float* d_probs, hipStream_t s) {
     const nww_config& c = h->cfg;
     StreamState* st = h->stream;
     const HopPlan& p = st->plan;
-    const int S = st->S, W = st->W, T = p.T, k = p.k, cols = nww_row_floats(c);
+    const int S = st->S, W = st->W, T = p.T, cols = nww_row_floats(c);
+    const bool primed = hp.primed && (!p.conv || st->rows_held);           // every ring the plan keeps holds the previous window
     int rc = nww_ensure_ws(h, S, W);
     if (rc) return rc;
     nww_prof_begin(h);
     nww_prof_mark(h, s, 0);
     Fe2Sub sub;
-    sub.ring_rows = st->lm_rows; sub.row0 = st->lm_pos; sub.out_clip_stride = (size_t)2 * st->lm_rows * cols;
-    if (st->primed) {
-        if (p.el > 0) { sub.t0[sub.nr] = 0; sub.t1[sub.nr] = p.el; ++sub.nr; }
-        // the new interior frames, then the trailing edge frames as a group of their own (groups of up to eight frames)
-        sub.t0[sub.nr] = T - p.er - k; sub.t1[sub.nr] = T - p.er; ++sub.nr;
-        if (p.er > 0) { sub.t0[sub.nr] = T - p.er; sub.t1[sub.nr] = T; ++sub.nr; }
-    }
-    rc = nww_frontend_on_dev(h, st->d_ring + st->pos, S, W, st->d_lm_ring, nullptr, 1, s, nullptr, (size_t)2 * W, &sub);
+    sub.ring_rows = st->lm_rows; sub.row0 = hp.lm_row; sub.out_clip_stride = (size_t)2 * st->lm_rows * cols;
+    if (primed) nww_hop_ranges(T, p.k, p.el, p.er, sub);
+    rc = nww_frontend_on_dev(h, st->d_ring + hp.pos, S, W, st->d_lm_ring, nullptr, 1, s, nullptr, (size_t)2 * W, &sub);
     if (rc) return rc;
-    const float* win = st->d_lm_ring + (size_t)st->lm_pos * cols;          // rows [lm_pos, lm_pos + T) of every stream's ring: its window
+    const float* win = st->d_lm_ring + (size_t)hp.lm_row * cols;           // rows [lm_row, lm_row + T) of every stream's ring: its window
     RunOpts o;
     if (h->x_stride_ok) {
-        const HopView v = stream_hop_view(h, st, sub.out_clip_stride);
+        const HopView v = stream_hop_view(h, st, sub.out_clip_stride, primed);
         o.hop = &v;
         rc = nww_run_head(h, win, S, d_logits, d_probs, s, o);
     } else {
@@ -233,42 +231,31 @@ static int stream_hop_incremental(nww_handle* h, float* d_logits, float* d_probs
         rc = nww_run_head(h, h->d_logmel, S, d_logits, d_probs, s, o);
     }
     if (rc) return rc;
-    st->lm_pos = (st->lm_pos + k) % st->lm_rows;
     if (p.conv) st->a2_pos = (st->a2_pos + p.a2_shift) % p.a2_rows;
     if (p.seq) st->seq_cur ^= 1;
-    st->primed = true;
     return NWW_OK;
 }
 
 static int stream_push_dev(nww_handle* h, const int16_t* d_chunk, float* d_logits, float* d_probs, hipStream_t s) {
     StreamState* st = h->stream;
     const int S = st->S, W = st->W, hop = st->hop;
+    const LockHop hp = pool_lock_plan(st->pool);
     const size_t total = (size_t)S * hop;
-    hipLaunchKernelGGL(stream_push_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, st->d_ring, d_chunk, S, W, hop, st->pos);
+    hipLaunchKernelGGL(stream_push_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, st->d_ring, d_chunk, S, W, hop, hp.at);
     HIP_TRY(h, hipGetLastError());
-    st->pos = (st->pos + hop) % W;
-    st->filled += hop;
     // the last W samples of every stream are contiguous at ring + pos (double-written ring)
-    if (st->filled < W) {       // window not full yet: the reference reports 0.0 (nanointerpreter.py:785-786)
-        if (d_logits) HIP_TRY(h, hipMemsetAsync(d_logits, 0, (size_t)S * sizeof(float), s));
-        if (d_probs) HIP_TRY(h, hipMemsetAsync(d_probs, 0, (size_t)S * sizeof(float), s));
-        return NWW_OK;
-    }
-    if (st->plan.shared) {
-        const int rc = stream_hop_incremental(h, d_logits, d_probs, s);
-        if (rc) st->primed = false;           // the rings may hold a half-finished hop: the next hop computes its window whole
-        return rc;
-    }
-    return nww_forward_pcm_on_dev(h, st->d_ring + st->pos, S, W, d_logits, d_probs, s, (size_t)2 * W);
+    const int rc = !hp.full ? nww_zero_scores(h, d_logits, d_probs, S, s)
+                 : st->plan.shared ? stream_hop_incremental(h, hp, d_logits, d_probs, s)
+                                   : nww_forward_pcm_on_dev(h, st->d_ring + hp.pos, S, W, d_logits, d_probs, s, (size_t)2 * W);
+    pool_lock_commit(st->pool, hp, rc == NWW_OK);      // (a failed hop may have left the rings half-finished: the next one computes its window whole)
+    st->rows_held = hp.full && rc == NWW_OK;
+    return rc;
 }
-// the lock-step entry points run while every stream shares one state; their push makes the pool's copy of it stale
+// the lock-step entry points run while every stream shares one state
 static int stream_lockstep(nww_handle* h) {
-    StreamState* st = h->stream;
-    if (!st->pool.aligned)
-        return fail(h, NWW_ERR_STATE, "the streams of this batch no longer share one state (nww_stream_push_some / nww_stream_reset_some made them "
-                                      "differ): a lock-step push needs nww_stream_reset first");
-    st->pool_synced = false;
-    return NWW_OK;
+    if (pool_lock_ok(h->stream->pool)) return NWW_OK;
+    return fail(h, NWW_ERR_STATE, "the streams of this batch no longer share one state (nww_stream_push_some / nww_stream_reset_some made them "
+                                  "differ): a lock-step push needs nww_stream_reset first");
 }
 
 extern "C" int nww_stream_push_dev(nww_handle* h, const int16_t* d_chunk, float* d_logits, float* d_probs, void* stream) {
@@ -293,22 +280,8 @@ extern "C" int nww_stream_push(nww_handle* h, const int16_t* chunk, float* logit
 }
 
 // ------------------------------------------------------------------------------------------ streams that push, join and reset on their own
-// The pool's view of the rings is the lock-step fields' while the batch is aligned: taken over before a pool call that follows a
-// lock-step one, handed back after a pool call that leaves the batch aligned.  The conv-row and sequence rings are not maintained here,
-// so a lock-step push that follows computes its window whole where it keeps them.
-static void pool_take_over(StreamState* st) {
-    if (st->pool_synced) return;
-    st->pool.set_all(st->pos, st->filled, st->lm_pos, st->primed && st->pool.frames);
-    st->pool_synced = true;
-}
-static void pool_hand_back(StreamState* st) {
-    const StreamPool& p = st->pool;
-    if (!p.aligned || p.S < 1) return;
-    st->pos = p.pos[0]; st->filled = p.filled[0];
-    if (p.frames) st->lm_pos = p.lm_pos[0];
-    st->primed = p.frames && p.primed[0] && !st->plan.conv;
-}
-
+// The pool calls maintain the PCM and (route 1) log-mel rings, not the lock-step path's conv-row and sequence rings: each clears
+// StreamState::rows_held.
 static int pool_alloc(nww_handle* h, StreamState* st) {
     if (st->d_tab) return NWW_OK;
     const size_t S = (size_t)st->S;
@@ -332,7 +305,7 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
     int rc = pool_alloc(h, st);
     if (!rc) rc = nww_ensure_ws(h, st->S, W);
     if (rc) return rc;
-    pool_take_over(st);
+    st->rows_held = false;
     PoolCall c;
     pool_plan_push(pool, idx, n, c);
     const int m = c.m();
@@ -363,10 +336,10 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
             hipLaunchKernelGGL(pool_push_kernel<int16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, st->d_ring, d_chunk, tab, n, W, hop);
         }
         HIP_TRY(h, hipGetLastError());
-        // a listed stream that holds no window yet reports 0 (nanointerpreter.py:785-786); the scored ones are scattered over that
+        // a listed stream that holds no window yet reports 0; the scored ones are scattered over that
         if (m < n) {
-            if (d_logits) HIP_TRY(h, hipMemsetAsync(d_logits, 0, (size_t)n * sizeof(float), s));
-            if (d_probs) HIP_TRY(h, hipMemsetAsync(d_probs, 0, (size_t)n * sizeof(float), s));
+            const int rcz = nww_zero_scores(h, d_logits, d_probs, n, s);
+            if (rcz) return rcz;
         }
         if (m == 0) return NWW_OK;
         hipError_t e;
@@ -399,9 +372,7 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
             }
             if (c.n_primed) {
                 Fe2Sub sub;
-                if (pool.el > 0) { sub.t0[sub.nr] = 0; sub.t1[sub.nr] = pool.el; ++sub.nr; }
-                sub.t0[sub.nr] = T - tail; sub.t1[sub.nr] = T - pool.er; ++sub.nr;
-                if (pool.er > 0) { sub.t0[sub.nr] = T - pool.er; sub.t1[sub.nr] = T; ++sub.nr; }
+                nww_hop_ranges(T, pool.k, pool.el, pool.er, sub);
                 const int rc1 = nww_frontend_on_dev(h, h->d_pcm + (size_t)c.n_whole * W, c.n_primed, W, st->d_lm_scratch + (size_t)c.n_whole * T * cols,
                                                     nullptr, 1, s, nullptr, (size_t)W, &sub);
                 if (rc1) return rc1;
@@ -431,7 +402,6 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
     rc = launches();
     (void)hipEventRecord(st->ev_tab[slot], s);
     pool_commit_push(pool, c, rc == NWW_OK);
-    pool_hand_back(st);
     return rc;
 }
 
@@ -490,16 +460,14 @@ extern "C" int nww_stream_reset_some(nww_handle* h, const int32_t* idx, int32_t 
         HIP_TRY(h, hipMemset(reinterpret_cast<unsigned char*>(st->d_ring) + (size_t)idx[i] * row, 0, (size_t)(j - i) * row));
         i = j;
     }
-    pool_take_over(st);
+    st->rows_held = false;
     pool_reset(st->pool, idx, n);
-    pool_hand_back(st);
     return NWW_OK;
 }
 
 extern "C" int64_t nww_stream_filled_of(const nww_handle* h, int32_t stream) {
     if (!h || !h->stream || stream < 0 || stream >= h->stream->S) return 0;
-    const StreamState* st = h->stream;
-    return st->pool_synced ? st->pool.filled[(size_t)stream] : st->filled;
+    return h->stream->pool.of(stream).filled;
 }
 
 extern "C" int nww_stream_pool_stats(const nww_handle* h, int32_t* n_scored, int32_t* route, int64_t* frames_computed) {

@@ -12,6 +12,21 @@ inline void nww_edge_frames(const FeParams& fe, int T, int W, int& el, int& er) 
     while (er < T && (T - 1 - er) * fe.hop - pad + fe.n_fft > W) ++er;
 }
 
+// The frames a hop of k frames computes in a window of T: the leading edge [0, el), the k new interior frames [T - er - k, T - er) and the
+// trailing edge [T - er, T) as a range of its own (the frontend groups frames range by range) - ascending, disjoint, none empty, so at
+// most three.  k = 0: a window's edge frames alone (the recording route).  Needs el <= T - er - k, which a shared HopPlan guarantees.
+// Sub: Fe2Sub (frontend.h), or anything with its nr, t0[4] and t1[4].
+template <class Sub>
+void nww_hop_ranges(int T, int k, int el, int er, Sub& sub) {
+    sub.nr = 0;
+    auto add = [&](int a, int b) {
+        if (a < b) { sub.t0[sub.nr] = a; sub.t1[sub.nr] = b; ++sub.nr; }
+    };
+    add(0, el);
+    add(T - er - k, T - er);
+    add(T - er, T);
+}
+
 // A hop of k = hop / hop_length frames turns frame t of the old window into frame t - k of the new one, bit for bit, unless the frame
 // touches the reflect padding of either window: per hop only frames [0, el) and [T - er - k, T) are computed (`shared`).
 // Likewise pooled row j of the fused trunk (input rows 4j - 3 .. 4j + 6) equals row j + k / 4 of the previous window when those rows are

@@ -1,7 +1,20 @@
-// stream_pool.h - a stream batch whose streams push, join and reset on their own (nww_stream_push_some / nww_stream_reset_some): the
-// per-stream ring state and what one call asks of the device, as host-only integer arithmetic (no HIP header; g++ compiles it for
-// tests/test_stream_pool_host.py).  Every push is commanded by the host, so the state lives here and nothing is read back: a call
-// turns its ascending stream list into one small table (PoolCall) that the data-movement kernels of nww_stream.hip follow.
+// stream_pool.h - the ring state of a stream batch, and what one call asks of the device, as host-only integer arithmetic (no HIP header;
+// g++ compiles it for tests/test_stream_pool_host.py).  Every push is commanded by the host, so the state lives here and nothing is read
+// back.  There is ONE state, whichever entry point moves it: per stream the write position of its PCM ring, its fill count, the rotation
+// of its log-mel ring and whether that ring holds the window before the next hop (primed).
+//   lock-step calls (nww_stream_push*)   every stream pushes: pool_lock_plan / pool_lock_commit, O(1) on the common state
+//   pool calls (nww_stream_push_some*, nww_stream_reset_some)   the listed streams push or reset on their own: a call turns its ascending
+//                                        stream list into one small table (PoolCall) that the data-movement kernels of nww_stream.hip follow
+//   nww_stream_reset                     pool_reset_all
+// Alignment: while `aligned`, every stream has the state `all` and the lock-step calls may run.  A pool call gives each stream its own
+// copy (`each`, O(S), made by the first such call) and works there; if it leaves them all equal - it listed every stream, or reset
+// streams that were empty anyway - the batch stays aligned.  The first call that makes states differ ends alignment, and only
+// pool_reset_all restores it.
+// Primed: a pool that keeps frames maintains the log-mel rings, so lock-step and all-stream pool hops follow one another incrementally.
+// A pool call that keeps none (raw-PCM head, route 0) clears the flag of the streams it lists: the next lock-step hop computes its window
+// whole.  (The lock-step path's conv-row and sequence rings are its own, with a flag of their own: StreamState::rows_held.)
+// A failed lock-step hop has stored its chunk: position and fill advance, primed is lost.  A failed pool call commits nothing but the
+// loss of primed.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -35,35 +48,38 @@ struct PoolCall {
     int m() const { return n_whole + n_primed; }
 };
 
+// one stream's rings
+struct RingState {
+    int32_t pos = 0, lm_pos = 0;
+    int64_t filled = 0;                  // samples since its last reset
+    bool primed = false;
+    bool operator==(const RingState& o) const { return pos == o.pos && lm_pos == o.lm_pos && filled == o.filled && primed == o.primed; }
+};
+
 struct StreamPool {
     int S = 0, W = 0, hop = 0;
-    bool frames = false;                 // log-mel rings are kept (route 1); lm_rows rows per ring, a hop shifts a window by k of T frames
-    int lm_rows = 0, k = 0, T = 0, el = 0, er = 0;
+    int lm_rows = 0, k = 0;              // a log-mel ring of lm_rows rows is kept (keep_ring); a hop shifts a window by k frames
+    bool frames = false;                 // ... and pool calls maintain it too (route 1); a window has T frames, el / er of them edge frames
+    int T = 0, el = 0, er = 0;
     int head = 0, tail = 0;              // a primed stream's hop reads samples [0, head) and [tail, W) of its window only (pool_primed_spans)
-    // every stream has the same state: the lock-step entry points may run.  Cleared by the first call that makes the states differ,
-    // set again only by a reset of the whole batch.
     bool aligned = true;
-    std::vector<int32_t> pos, lm_pos;
-    std::vector<int64_t> filled;
-    std::vector<uint8_t> primed;
+    RingState all;                       // every stream's state while aligned; afterwards what it was when alignment ended
+    std::vector<RingState> each;         // [S] while not aligned
 
-    void open(int S_, int W_, int hop_) {
-        S = S_; W = W_; hop = hop_;
-        frames = false; lm_rows = k = T = el = er = head = tail = 0;
-        aligned = true;
-        set_all(0, 0, 0, false);
-    }
+    void open(int S_, int W_, int hop_) { *this = StreamPool(); S = S_; W = W_; hop = hop_; }
+    void keep_ring(int lm_rows_, int k_) { lm_rows = lm_rows_; k = k_; }
     void keep_frames(int lm_rows_, int T_, int k_, int el_, int er_, int head_, int tail_) {
-        frames = true; lm_rows = lm_rows_; T = T_; k = k_; el = el_; er = er_; head = head_; tail = tail_;
+        keep_ring(lm_rows_, k_);
+        frames = true; T = T_; el = el_; er = er_; head = head_; tail = tail_;
     }
-    // every stream takes the lock-step batch's state
-    void set_all(int pos_, long long filled_, int lm_pos_, bool primed_) {
-        pos.assign((size_t)S, pos_); lm_pos.assign((size_t)S, lm_pos_); filled.assign((size_t)S, filled_); primed.assign((size_t)S, primed_ ? 1 : 0);
-    }
-    bool all_equal() const {
-        for (int s = 1; s < S; ++s)
-            if (pos[s] != pos[0] || lm_pos[s] != lm_pos[0] || filled[s] != filled[0] || primed[s] != primed[0]) return false;
-        return true;
+    const RingState& of(int s) const { return aligned ? all : each[(size_t)s]; }
+    // a pool call's writes: f works on the streams' own states; an aligned batch stays aligned if f leaves them all equal
+    template <class F>
+    void edit(F f) {
+        if (aligned) each.assign((size_t)S, all);
+        f(each);
+        for (int s = 1; s < S && aligned; ++s) aligned = each[(size_t)s] == each[0];
+        if (aligned && S > 0) all = each[0];
     }
     // log-mel frames the frontend computes for one stream of a group
     int frames_of(int group) const { return group == POOL_NOT_FULL ? 0 : group == POOL_PRIMED ? el + k + er : T; }
@@ -99,12 +115,12 @@ inline void pool_plan_push(const StreamPool& p, const int32_t* idx, int n, PoolC
     c.entries.assign((size_t)n, PoolEntry{});
     c.n_whole = c.n_primed = 0;
     for (int i = 0; i < n; ++i) {
-        const int s = idx[i];
+        const RingState& r = p.of(idx[i]);
         PoolEntry& e = c.entries[(size_t)i];
-        e.stream = s;
-        e.pos = (p.pos[s] + p.hop) % p.W;
-        e.lm_row = p.lm_pos[s];
-        e.group = p.filled[s] + p.hop < p.W ? POOL_NOT_FULL : (p.frames && p.primed[s]) ? POOL_PRIMED : POOL_WHOLE;
+        e.stream = idx[i];
+        e.pos = (r.pos + p.hop) % p.W;
+        e.lm_row = r.lm_pos;
+        e.group = r.filled + p.hop < p.W ? POOL_NOT_FULL : (p.frames && r.primed) ? POOL_PRIMED : POOL_WHOLE;
         e.slot = e.dense = -1;
         if (e.group == POOL_WHOLE) ++c.n_whole;
         if (e.group == POOL_PRIMED) ++c.n_primed;
@@ -125,24 +141,46 @@ inline void pool_plan_push(const StreamPool& p, const int32_t* idx, int n, PoolC
 // ok: every launch of the call went out; otherwise the listed streams' log-mel rings may hold a half-written hop and their next window
 // is computed whole
 inline void pool_commit_push(StreamPool& p, const PoolCall& c, bool ok) {
-    for (const PoolEntry& e : c.entries) {
-        const int s = e.stream;
-        if (!ok) { p.primed[s] = 0; continue; }
-        p.pos[s] = e.pos;
-        p.filled[s] += p.hop;
-        if (e.group != POOL_NOT_FULL && p.frames) {
-            p.lm_pos[s] = (p.lm_pos[s] + p.k) % p.lm_rows;
-            p.primed[s] = 1;
+    p.edit([&](std::vector<RingState>& each) {
+        for (const PoolEntry& e : c.entries) {
+            RingState& r = each[(size_t)e.stream];
+            if (!ok || !p.frames) r.primed = false;
+            if (!ok) continue;
+            r.pos = e.pos;
+            r.filled += p.hop;
+            if (e.group != POOL_NOT_FULL && p.frames) { r.lm_pos = (r.lm_pos + p.k) % p.lm_rows; r.primed = true; }
         }
-    }
-    if (p.aligned && !p.all_equal()) p.aligned = false;
+    });
 }
 
 // a new session for the listed streams
 inline void pool_reset(StreamPool& p, const int32_t* idx, int n) {
-    for (int i = 0; i < n; ++i) {
-        const int s = idx[i];
-        p.pos[s] = 0; p.lm_pos[s] = 0; p.filled[s] = 0; p.primed[s] = 0;
-    }
-    if (p.aligned && !p.all_equal()) p.aligned = false;
+    p.edit([&](std::vector<RingState>& each) {
+        for (int i = 0; i < n; ++i) each[(size_t)idx[i]] = RingState();
+    });
+}
+
+// ... and for the whole batch, which is aligned again
+inline void pool_reset_all(StreamPool& p) { p.all = RingState(); p.aligned = true; }
+
+// ---- the lock-step calls: every stream pushes one hop; they run only while the batch is aligned
+inline bool pool_lock_ok(const StreamPool& p) { return p.aligned; }
+
+// What a lock-step push reads.  at: where the chunk goes in every PCM ring; pos: where the window starts after the push (the last W
+// samples are contiguous there in the double-written ring); full: the rings hold a window; lm_row: the row of the log-mel rings that
+// frame 0 of that window takes; primed: those rings hold the previous window.
+struct LockHop { int32_t at, pos, lm_row; bool full, primed; };
+inline LockHop pool_lock_plan(const StreamPool& p) {
+    const RingState& r = p.all;
+    return {r.pos, (r.pos + p.hop) % p.W, r.lm_pos, r.filled + p.hop >= p.W, r.primed};
+}
+
+// The chunk is in the rings, so position and fill advance either way.  ok: the hop's launches went out - where a log-mel ring is kept and
+// the window was full, the ring has been rotated to it; otherwise the rings may hold a half-finished hop.
+inline void pool_lock_commit(StreamPool& p, const LockHop& hp, bool ok) {
+    RingState& r = p.all;
+    r.pos = hp.pos;
+    r.filled += p.hop;
+    if (!ok) r.primed = false;
+    else if (hp.full && p.lm_rows > 0) { r.lm_pos = (r.lm_pos + p.k) % p.lm_rows; r.primed = true; }
 }

@@ -140,7 +140,7 @@ static void run(const FeParams& fe, int W, int hop, unsigned seed, Totals& tot) 
             CHECK(ok, AT);
         }
         pool_commit_push(p, c, true);
-        for (int s = 0; s < S; ++s) CHECK(p.filled[(size_t)s] == samples[(size_t)s], AT);
+        for (int s = 0; s < S; ++s) CHECK(p.of(s).filled == samples[(size_t)s], AT);
     }
 #undef AT
 }

@@ -42,7 +42,30 @@ static int min_cover(int a, int b, Fits fits) {
     return best[b - a];
 }
 
-struct Counts { long plans = 0, shared = 0, conv = 0, seq = 0, cut = 0, gave_up = 0; };
+struct Counts { long plans = 0, shared = 0, conv = 0, seq = 0, cut = 0, gave_up = 0, ranges = 0, two = 0, three = 0; };
+
+// nww_hop_ranges: ascending, disjoint, none empty, at most four; their union is exactly [0, el) and [T - er - k, T), and the trailing er
+// frames are a range of their own
+struct Ranges { int nr = -1, t0[4] = {0, 0, 0, 0}, t1[4] = {0, 0, 0, 0}; };
+static void check_ranges(int T, int k, int el, int er, Counts& n) {
+    Ranges r;
+    nww_hop_ranges(T, k, el, er, r);
+    ++n.ranges;
+#define AT "T=%d k=%d el=%d er=%d", T, k, el, er
+    CHECK(r.nr >= 0 && r.nr <= 4, AT);
+    std::vector<int> hit(T, 0);
+    bool trailing = er == 0;
+    for (int q = 0; q < r.nr && q < 4; ++q) {
+        CHECK(r.t0[q] >= 0 && r.t0[q] < r.t1[q] && r.t1[q] <= T && (q == 0 || r.t1[q - 1] <= r.t0[q]), AT);
+        for (int t = r.t0[q]; t < r.t1[q] && t < T; ++t) ++hit[t < 0 ? 0 : t];
+        if (r.t0[q] == T - er && r.t1[q] == T) trailing = true;
+    }
+    for (int t = 0; t < T; ++t) CHECK(hit[t] == ((t < el || t >= T - er - k) ? 1 : 0), AT);
+    CHECK(trailing, AT);
+    if (r.nr == 2) ++n.two;
+    if (r.nr == 3) ++n.three;
+#undef AT
+}
 
 template <class Fits>
 static void check_pair(const FeParams& fe, int W, int hop, Fits fits, const char* pred, Counts& n) {
@@ -65,6 +88,8 @@ static void check_pair(const FeParams& fe, int W, int hop, Fits fits, const char
         if (!p.shared) { CHECK(!p.conv && !p.seq && p.nsub == 0, AT); continue; }
         ++n.shared;
         CHECK(p.k == k && p.el == el && p.er == er, AT);
+        check_ranges(T, k, el, er, n);                                                 // the frames a hop computes, and a recording window's edge frames
+        check_ranges(T, 0, el, er, n);
         // the fused trunk's pooled rows
         const int H2 = T / 4;
         int lo = -1, hi = -1, kept = 0;
@@ -121,10 +146,13 @@ int main() {
         }
     }
     for (const Counts* c : {&all, &small})
-        std::printf("plans=%ld shared=%ld conv=%ld seq=%ld cut=%ld gave_up=%ld\n", c->plans, c->shared, c->conv, c->seq, c->cut, c->gave_up);
+        std::printf("plans=%ld shared=%ld conv=%ld seq=%ld cut=%ld gave_up=%ld ranges=%ld two=%ld three=%ld\n", c->plans, c->shared, c->conv, c->seq, c->cut, c->gave_up,
+                    c->ranges, c->two, c->three);
     // both paths of the strip cutter occur: a range that goes out in several strips, and a pair that keeps the frontend ring only
     CHECK(small.cut > 0 && small.gave_up > 0, "cut=%ld gave_up=%ld", small.cut, small.gave_up);
     CHECK(all.conv > 0 && all.seq > 0 && all.gave_up == 0, "conv=%ld seq=%ld", all.conv, all.seq);
+    // a centred frontend's hop has three ranges, its recording window two
+    CHECK(all.ranges > 0 && all.two > 0 && all.three > 0, "ranges=%ld two=%ld three=%ld", all.ranges, all.two, all.three);
     if (g_fail) std::printf("FAILED %d checks\n", g_fail);
     else std::printf("ok\n");
     return g_fail ? 1 : 0;

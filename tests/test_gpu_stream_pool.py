@@ -268,6 +268,35 @@ def test_lock_step_unchanged(golden_frontend):
     m.stream_close(); m.close()
 
 
+@pytest.mark.parametrize("head,shape,kw,n_streams,window,hop,ticks", [
+    ("cnn", (T, 64), {}, S, W, 640, 14),                                             # frames kept by both paths, no conv-row rings
+    ("e2e_cnn", (17, 64), dict(e2e_frontend_channels=32), 3, 1040, 320, 12),         # the lock-step plan shares rows, the pool keeps none
+])
+def test_lock_step_and_pool_interleave(golden_frontend, head, shape, kw, n_streams, window, hop, ticks):
+    """While every call lists every stream the two kinds of push describe one state: all lock-step, all push_some and a mix of the two
+    score the same bits, and the batch's fill count is every stream's after every call."""
+    m = _model(HeadConfig(head, shape, **kw), golden_frontend if head == "cnn" else None)
+    kinds = ("speechlike", "noise", "loud", "chirp")
+    audio = np.concatenate([synth_pcm(kinds[s % 4], 1, hop * ticks, seed=31 + 3 * s) for s in range(n_streams)], 0)
+    every = list(range(n_streams))
+    chunks = [np.ascontiguousarray(audio[:, t * hop:(t + 1) * hop]) for t in range(ticks)]
+
+    def run(schedule):
+        m.stream_open(n_streams, window, hop)
+        out = []
+        for t, kind in enumerate(schedule):
+            out.append(np.stack(m.stream_push(chunks[t]) if kind == "lock" else m.stream_push_some(every, chunks[t])))
+            assert all(m.stream_filled() == m.stream_filled(s) == hop * (t + 1) for s in every), (kind, t)
+        m.stream_close()
+        return np.stack(out)
+
+    lock = run(["lock"] * ticks)
+    assert lock[-1].all() and not lock[0].any()
+    assert np.array_equal(run(["some"] * ticks), lock)
+    assert np.array_equal(run((["lock", "some", "some", "lock", "lock"] * 3)[:ticks]), lock)
+    m.close()
+
+
 # ---- errors
 def test_errors(golden_frontend):
     m = _model(HeadConfig("cnn", (T, 64)), golden_frontend)

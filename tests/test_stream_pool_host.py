@@ -1,8 +1,10 @@
-"""The per-stream state of a stream batch whose streams push, join and reset on their own (csrc/stream_pool.h: ring offsets, fill counts,
-log-mel ring rows, the not-full / whole / primed partition of a call, its table, the aligned flag) on the CPU:
+"""The one ring state of a stream batch (csrc/stream_pool.h: ring offsets, fill counts, log-mel ring rows, the not-full / whole / primed
+partition of a pool call, its table, what a lock-step push reads and commits, alignment and who ends and restores it) on the CPU:
 tests/hostemu/stream_pool_check.cpp, a stand-alone g++ program built with -fsanitize=address,undefined, checks it against brute force -
-one sample counter and one list of frame origins per stream, the rings emulated cell by cell from the table alone - over random schedules
-for windows 4800 / 16000, hops 640 / 1280 / 296 / the window itself and centre 0 / 1.  No GPU, and no library is loaded into Python."""
+one sample counter and one list of frame origins per stream, the rings emulated cell by cell from what a call hands to the device alone -
+over random schedules of pool pushes, resets, lock-step pushes (some failing) and whole-batch resets, with aligned stretches in which the
+two kinds of push hand over to one another, for windows 4800 / 16000, hops 640 / 1280 / 296 / the window itself, centre 0 / 1, and pools
+that do and do not keep frames.  No GPU, and no library is loaded into Python."""
 import os
 import subprocess
 
