@@ -360,6 +360,57 @@ extern int nww_cascade_stream_push_some_dev(nww_handle* gate, nww_handle* verifi
 /* the gate's nww_stream_reset_some (the verifier keeps no ring); its errors are reported on the verifier's handle                  */
 extern int nww_cascade_stream_reset_some(nww_handle* gate, nww_handle* verifier, const int32_t* idx, int32_t n);
 
+/* ---- model banks: several wake words on ONE frontend pass (NanoInterpreter scores every loaded model on the same audio) ----
+ * A bank is k >= 1 finalized handles on one device whose mel frontends are identical.  It is not an object: like a cascade it is the
+ * list of handles passed with each call.  members[0] is the LEADER and owns everything that is shared - PCM staging, the frontend's
+ * launches, the dense frames-major head input, the stream batch with its PCM and log-mel rings, the recording pool; the other members
+ * are FOLLOWERS: they run only their head plan, on the leader's head input, launch no frontend and hold no PCM (their workspaces are
+ * sized as nww_forward_features_dev sizes them).  A call runs exactly the frontend work the leader alone would run - one launch per
+ * batch or pass, the leader's pool / edge / assembly launches on a recording's shared route, its whole / primed launches in a pool
+ * call - then the k head plans, all on `stream` in member order.  DESIGN.md 4.8f.
+ * Outputs are member-major [k][n]: member j's value for item i at j * n + i, n being B, nW or the number of listed streams; either
+ * may be NULL.  Member j's logits and probabilities are bit-identical to the single-handle call on member j alone with the same input
+ * - nww_forward_pcm; nww_forward_recording with the same max_batch; nww_stream_push_some on a batch of its own that received the same
+ * push / reset calls (a listed stream that holds no window reads 0 / 0 for every member) - and do not depend on which member leads.
+ * k = 1 is the plain call on members[0].  Profiling works per member; a follower's entry 0 (frontend) records nothing in a bank call.
+ * Rules, checked before anything is launched or any ring is touched - a failing call writes no output and leaves every
+ * nww_stream_filled_of as it was; the text names the offending member by its index:
+ *   members non-NULL and k >= 1; every member non-NULL, finalized, distinct, on one device              NWW_ERR_INVALID
+ *   no raw-PCM head (e2e_quartznet, e2e_cnn) among k > 1 members: a learned frontend shares nothing     NWW_ERR_INVALID
+ *   identical frontends: sample_rate, n_fft, win_length, hop_length, n_mels, center, f_min, f_max, amin, db_multiplier equal, the
+ *   window and mel filterbank tables byte-equal, loaded (frontend.window / frontend.mel_fb) or built in;
+ *   the text names the first differing field                                                           NWW_ERR_INVALID
+ *   every member consumes frames-major log-mel (an e2e_dnn planned in the reference's orientation, for
+ *   instance under conv_arith = f32, does not)                                                         NWW_ERR_UNSUPPORTED
+ *   the clip or window gives every member its own (in_rows, in_cols)                                   NWW_ERR_SHAPE
+ *   the stream call: the leader has an open batch (NWW_ERR_STATE), idx as in nww_stream_push_some      NWW_ERR_INVALID
+ * Errors go to nww_last_error(members[0]) (to nww_last_error(NULL) where there is no members[0]).  The dense [2][k][n] outputs of the
+ * host-pointer variants live on the leader's handle, grow on demand and are freed by nww_destroy.
+ * Streams: only the leader has a stream batch; open, reset, close, nww_stream_reset_some, nww_stream_filled_of and
+ * nww_stream_pool_stats are the leader's existing calls.  The bank's stream entry point is the pool call, on a batch in any state; a
+ * call that lists every stream of an aligned batch keeps it aligned, and the lock-step nww_stream_push* on the leader alone runs
+ * afterwards as before.  There is no lock-step bank call: that path may keep conv rows instead of a dense window (CRNN), which leaves
+ * a follower nothing to read - clients that tick together list every stream.
+ * (Declared `extern` like the blocks above: the pinned count of declarations that start a line with their return type stays 48.)      */
+/* the rules alone, for clips or windows of `window` samples: 0 or the error code                                                     */
+extern int nww_bank_check(nww_handle* const* members, int32_t k, int32_t window);
+/* d_pcm [B][N] -> d_logits / d_probs [k][B]; asynchronous on `stream` (NULL: the leader's own)                                        */
+extern int nww_bank_forward_pcm_dev(nww_handle* const* members, int32_t k, const int16_t* d_pcm, int32_t B, int32_t N,
+                                    float* d_logits, float* d_probs, void* stream);
+/* host pointers; the clips are uploaded once, into the leader's staging; synchronises before it returns                               */
+extern int nww_bank_forward_pcm(nww_handle* const* members, int32_t k, const int16_t* pcm, int32_t B, int32_t N, float* logits, float* probs);
+/* every window of a recording (the rules of nww_forward_recording*, the route the leader plans): d_logits / d_probs [k][nW]          */
+extern int nww_bank_forward_recording_dev(nww_handle* const* members, int32_t k, const int16_t* d_pcm, int32_t n_samples, int32_t window, int32_t hop,
+                                          int32_t max_batch, float* d_logits, float* d_probs, void* stream);
+/* host pointers; the recording is uploaded once.  n_windows_out may be NULL.                                                          */
+extern int nww_bank_forward_recording(nww_handle* const* members, int32_t k, const int16_t* pcm, int32_t n_samples, int32_t window, int32_t hop,
+                                      int32_t max_batch, float* logits, float* probs, int32_t* n_windows_out);
+/* the listed streams of the leader's batch (idx, n and the chunk as in nww_stream_push_some): outputs [k][n], in idx order             */
+extern int nww_bank_stream_push_some_dev(nww_handle* const* members, int32_t k, const int32_t* idx, int32_t n, const int16_t* d_chunk,
+                                         float* d_logits, float* d_probs, void* stream);
+extern int nww_bank_stream_push_some(nww_handle* const* members, int32_t k, const int32_t* idx, int32_t n, const int16_t* chunk,
+                                     float* logits, float* probs);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

@@ -51,6 +51,8 @@ SYMBOLS = [
     "nww_cascade_forward_recording", "nww_cascade_stream_push", "nww_cascade_stream_push_dev",
     "nww_stream_push_some", "nww_stream_push_some_dev", "nww_stream_reset_some", "nww_stream_filled_of", "nww_stream_pool_stats",
     "nww_cascade_stream_push_some", "nww_cascade_stream_push_some_dev", "nww_cascade_stream_reset_some",
+    "nww_bank_check", "nww_bank_forward_pcm_dev", "nww_bank_forward_pcm", "nww_bank_forward_recording_dev", "nww_bank_forward_recording",
+    "nww_bank_stream_push_some_dev", "nww_bank_stream_push_some",
 ]
 
 
@@ -170,6 +172,14 @@ def load_library():
     lib.nww_stream_reset_some.argtypes = [vp, vp, i32]; lib.nww_stream_reset_some.restype = C.c_int
     lib.nww_stream_filled_of.argtypes = [vp, i32]; lib.nww_stream_filled_of.restype = C.c_int64
     lib.nww_stream_pool_stats.argtypes = [vp, i32p, i32p, C.POINTER(C.c_int64)]; lib.nww_stream_pool_stats.restype = C.c_int
+    # model banks: `members` is an array of k handles (nww_handle* const*), passed as a pointer
+    lib.nww_bank_check.argtypes = [vp, i32, i32]; lib.nww_bank_check.restype = C.c_int
+    lib.nww_bank_forward_pcm_dev.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]; lib.nww_bank_forward_pcm_dev.restype = C.c_int
+    lib.nww_bank_forward_pcm.argtypes = [vp, i32, vp, i32, i32, vp, vp]; lib.nww_bank_forward_pcm.restype = C.c_int
+    lib.nww_bank_forward_recording_dev.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]; lib.nww_bank_forward_recording_dev.restype = C.c_int
+    lib.nww_bank_forward_recording.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i32p]; lib.nww_bank_forward_recording.restype = C.c_int
+    lib.nww_bank_stream_push_some_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]; lib.nww_bank_stream_push_some_dev.restype = C.c_int
+    lib.nww_bank_stream_push_some.argtypes = [vp, i32, vp, i32, vp, vp, vp]; lib.nww_bank_stream_push_some.restype = C.c_int
     _lib = lib
     return lib
 

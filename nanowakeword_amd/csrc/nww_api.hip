@@ -170,6 +170,7 @@ extern "C" int nww_destroy(nww_handle* h) {
     nww_emb_close(h);
     nww_recording_free(h);
     nww_cascade_free(h);
+    nww_bank_free(h);
     nww_comm_destroy(h);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -370,6 +371,24 @@ int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float*
     return NWW_OK;
 }
 
+int nww_run_heads(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, const RunOpts& o) {
+    int rc = nww_run_head(h, d_x, B, d_logits, d_probs, s, o);
+    if (rc || !o.bank) return rc;
+    // a bank's followers: their head plans alone, on the leader's input (a follower's profile entry 0, the frontend, records nothing)
+    const BankRun& b = *o.bank;
+    for (int j = 1; j < b.k; ++j) {
+        nww_handle* f = b.members[j];
+        float* lg = b.own ? f->d_logits : b.d_logits ? b.d_logits + (size_t)j * b.stride + b.offset : nullptr;
+        float* pr = b.own ? (b.probs ? f->d_probs : nullptr) : b.d_probs ? b.d_probs + (size_t)j * b.stride + b.offset : nullptr;
+        RunOpts fo;
+        fo.x_frames_major = f->cfg.mel_major_features != 0;
+        nww_prof_begin(f);
+        rc = nww_run_head(f, d_x, B, lg, pr, s, fo);
+        if (rc) return fail(h, rc, "member %d: %s", j, f->err.c_str());
+    }
+    return NWW_OK;
+}
+
 int nww_check_run(nww_handle* h, int B) {
     if (!h) return NWW_ERR_INVALID;
     if (!h->finalized) return fail(h, NWW_ERR_STATE, "model not finalized: call nww_finalize after loading the state_dict");
@@ -463,7 +482,7 @@ int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, fl
     if (rc) return rc;
     RunOpts ro = o;
     ro.x_frames_major = fm && c.mel_major_features;
-    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, ro);
+    return nww_run_heads(h, h->d_logmel, B, d_logits, d_probs, s, ro);
 }
 
 extern "C" int nww_forward_pcm_dev(nww_handle* h, const int16_t* d_pcm, int32_t B, int32_t N, float* d_logits,

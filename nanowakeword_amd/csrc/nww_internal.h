@@ -2,7 +2,7 @@
 // device-side entry points they call on each other.  nww_api.hip: create / load / run entry points; nww_weights.hip: state_dict spec
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
 // nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
-// nww_cascade.hip: gate + verifier cascades (nww_cascade_*);
+// nww_cascade.hip: gate + verifier cascades (nww_cascade_*); nww_bank.hip: model banks (nww_bank_*: K heads on one frontend pass);
 // stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); stream_pool.h: the
 // one ring state of a stream batch, moved by its lock-step calls and by the calls whose streams push and reset on their own (host-only
 // too, used by nww_stream.hip and read by nww_cascade.hip); plan_host.h: the
@@ -127,6 +127,7 @@ struct nww_handle {
     float* d_weights = nullptr;
     std::vector<float> h_weights;  // the arena's host image, offset for offset: what the planner reads weight values from; held while nww_finalize runs
     FeTables* d_tables = nullptr;
+    std::vector<float> fe_window, fe_mel_fb;   // the window and filterbank the tables were built from, loaded or built in (what a bank compares: bank.h)
     Fe2MelPlan* d_melplan = nullptr;
     int mel_max_taps = 0;          // longest filter support of the mel filterbank
     hipStream_t own_stream = nullptr;
@@ -171,6 +172,9 @@ struct nww_handle {
     // word the count is read back through; the first two grown on demand
     int32_t* d_cas_idx = nullptr; float* d_cas_out = nullptr; int32_t* d_cas_counts = nullptr; int32_t* pin_cas_count = nullptr;
     size_t cas_idx_bytes = 0, cas_out_bytes = 0;
+    // bank scoring (nww_bank.hip), held by the LEADER's handle: the dense [2][k][n] logits / probabilities of the host-pointer entry
+    // points, grown on demand
+    float* d_bank_out = nullptr; size_t bank_out_bytes = 0;
     void* comm = nullptr;          // ncclComm_t of this rank (nww_comm_init)
     unsigned char* pin_in = nullptr; unsigned char* pin_out = nullptr;   // pinned staging for small host-pointer calls
     bool pin_in_busy = false;                                            // an async copy out of pin_in may still be in flight
@@ -209,6 +213,15 @@ void nww_prof_begin(nww_handle* h);
 int nww_check_run(nww_handle* h, int B);
 int nww_ensure_ws(nww_handle* h, int B, int N);
 int nww_grow(nww_handle* h, void** p, size_t* cap, size_t bytes);       // a device buffer grown on demand to hold `bytes`
+// The followers of a bank call (nww_bank.hip): members[1 .. k) run their head plans on the dense head input the leader (members[0])
+// has just written.  Follower j writes d_logits / d_probs + j * stride + offset (offset: the first item of a recording's pass), or with
+// `own` its own nww_handle::d_logits / d_probs (a pool call, which scatters every member's scored results afterwards).
+struct BankRun {
+    nww_handle* const* members = nullptr; int k = 0;
+    float* d_logits = nullptr; float* d_probs = nullptr;
+    size_t stride = 0, offset = 0;
+    bool own = false, probs = false;       // own: whether the followers compute probabilities
+};
 // a forward's optional inputs
 struct RunOpts {
     bool x_frames_major = false;           // Run::x_frames_major
@@ -216,8 +229,11 @@ struct RunOpts {
     unsigned int done_seq = 0;
     bool* done_armed = nullptr;
     const HopView* hop = nullptr;          // a streaming hop
+    const BankRun* bank = nullptr;         // a bank call: the followers run behind the leader's head
 };
 int nww_run_head(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, const RunOpts& o = RunOpts());
+// the head of h on the dense frames-major d_x, then (o.bank) every follower's on the same d_x, all on s in member order
+int nww_run_heads(nww_handle* h, const float* d_x, int B, float* d_logits, float* d_probs, hipStream_t s, const RunOpts& o);
 int nww_frontend_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_db, float* d_mel, int frames_major, hipStream_t s,
                         int* frames_out, size_t row_stride = 0, const Fe2Sub* sub = nullptr);
 int nww_forward_pcm_on_dev(nww_handle* h, const int16_t* d_pcm, int B, int N, float* d_logits, float* d_probs, hipStream_t s,
@@ -227,13 +243,14 @@ int nww_copy_out(nww_handle* h, int B, float* logits, float* probs, float* emb, 
 void nww_recording_free(nww_handle* h);        // nww_recording.hip, as the next two: what nww_cascade.hip scores a gate's recording with
 long long nww_rec_count(long long n_samples, int W, int hop);
 int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
-                           hipStream_t s);
+                           hipStream_t s, const BankRun* bank = nullptr);
 // nww_stream.hip, as the next one: the checks every push_some shares (*done: n == 0, the call is complete), and the push itself on
 // device pointers - what nww_cascade.hip runs a gate's pool call with
 int nww_pool_push_check(nww_handle* h, const int32_t* idx, int32_t n, const void* chunk, bool* done);
 int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t* d_chunk, float* d_logits, float* d_probs, hipStream_t s,
-                         const PoolEntry** tab_out = nullptr, int* m_out = nullptr);
+                         const PoolEntry** tab_out = nullptr, int* m_out = nullptr, const BankRun* bank = nullptr);
 void nww_cascade_free(nww_handle* h);          // nww_cascade.hip
+void nww_bank_free(nww_handle* h);             // nww_bank.hip
 void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next eight: what nww_finalize does to the loaded weights before it plans
 void balance_channel_gains(nww_handle* h);
 void fold_batchnorms(nww_handle* h);

@@ -25,7 +25,8 @@ int rec_plan(nww_handle* h, int W, int hop, RecPlan& p) {
 }
 
 // One pass on the shared route: B windows whose first sample is d_pcm[0].
-int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B, int W, int hop, float* d_logits, float* d_probs, hipStream_t s) {
+int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B, int W, int hop, float* d_logits, float* d_probs, hipStream_t s,
+                    const BankRun* bank) {
     const nww_config& c = h->cfg;
     const int span = (B - 1) * hop + W;
     nww_prof_begin(h);
@@ -45,7 +46,8 @@ int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B
     if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'rec_assemble' failed: %s", hipGetErrorString(e));
     RunOpts o;
     o.x_frames_major = c.mel_major_features != 0;
-    return nww_run_head(h, h->d_logmel, B, d_logits, d_probs, s, o);
+    o.bank = bank;
+    return nww_run_heads(h, h->d_logmel, B, d_logits, d_probs, s, o);
 }
 
 }  // namespace
@@ -53,7 +55,7 @@ int rec_pass_shared(nww_handle* h, const RecPlan& p, const int16_t* d_pcm, int B
 long long nww_rec_count(long long n_samples, int W, int hop) { return n_samples < W ? 0 : 1 + (n_samples - W) / hop; }
 
 int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samples, int W, int hop, int max_batch, float* d_logits, float* d_probs,
-                           hipStream_t s) {
+                           hipStream_t s, const BankRun* bank) {
     RecPlan p;
     int rc = rec_plan(h, W, hop, p);
     if (rc) return rc;
@@ -77,7 +79,10 @@ int nww_rec_forward_on_dev(nww_handle* h, const int16_t* d_pcm, long long n_samp
         const int16_t* x = d_pcm + first * hop;
         float* lg = d_logits ? d_logits + first : nullptr;
         float* pr = d_probs ? d_probs + first : nullptr;
-        rc = p.shared ? rec_pass_shared(h, p, x, B, W, hop, lg, pr, s) : nww_forward_pcm_on_dev(h, x, B, W, lg, pr, s, (size_t)hop);
+        BankRun pass;                                            // a bank's followers write the same pass of their own rows
+        RunOpts o;
+        if (bank) { pass = *bank; pass.offset = (size_t)first; o.bank = &pass; }
+        rc = p.shared ? rec_pass_shared(h, p, x, B, W, hop, lg, pr, s, o.bank) : nww_forward_pcm_on_dev(h, x, B, W, lg, pr, s, (size_t)hop, o);
         if (rc) return rc;
     }
     return NWW_OK;

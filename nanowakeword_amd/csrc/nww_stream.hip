@@ -298,7 +298,7 @@ static int pool_alloc(nww_handle* h, StreamState* st) {
 // (tab_out / m_out: the call's table [n] on the device and its count of scored streams, for a caller that enqueues on s right behind
 // the call - nww_cascade.hip; the table's slot is rewritten POOL_TAB_SLOTS calls later at the earliest)
 int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t* d_chunk, float* d_logits, float* d_probs, hipStream_t s,
-                         const PoolEntry** tab_out, int* m_out) {
+                         const PoolEntry** tab_out, int* m_out, const BankRun* bank) {
     StreamState* st = h->stream;
     StreamPool& pool = st->pool;
     const int W = st->W, hop = st->hop;
@@ -337,19 +337,23 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
         }
         HIP_TRY(h, hipGetLastError());
         // a listed stream that holds no window yet reports 0; the scored ones are scattered over that
+        // (a bank's outputs are [k][n]: every member's row)
+        const int k = bank ? bank->k : 1;
         if (m < n) {
-            const int rcz = nww_zero_scores(h, d_logits, d_probs, n, s);
+            const int rcz = nww_zero_scores(h, d_logits, d_probs, (size_t)n * k, s);
             if (rcz) return rcz;
         }
         if (m == 0) return NWW_OK;
         hipError_t e;
         float* lg = h->d_logits;
         float* pr = d_probs ? h->d_probs : nullptr;
+        RunOpts o;
+        o.bank = bank;
         if (!pool.frames) {                                      // route 0: whole windows (slot order is dense order)
             // (2) the scored streams' windows out of their rings into the PCM staging [m][W]
             e = launch_cascade_gather(st->d_ring, d_win8, 8, W, m, h->d_pcm, s);
             if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'cascade_gather' failed: %s", hipGetErrorString(e));
-            const int rc0 = nww_forward_pcm_on_dev(h, h->d_pcm, m, W, lg, pr, s);
+            const int rc0 = nww_forward_pcm_on_dev(h, h->d_pcm, m, W, lg, pr, s, 0, o);
             if (rc0) return rc0;
         } else {                                                 // route 1: shared frames
             const nww_config& cfg = h->cfg;
@@ -387,14 +391,15 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
             hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(st->d_lm_ring),
                                reinterpret_cast<float4*>(h->d_logmel), tab, n, T * cols4, cols4, pool.lm_rows);
             HIP_TRY(h, hipGetLastError());
-            RunOpts o;
             o.x_frames_major = cfg.mel_major_features != 0;
-            const int rc1 = nww_run_head(h, h->d_logmel, m, lg, pr, s, o);
+            const int rc1 = nww_run_heads(h, h->d_logmel, m, lg, pr, s, o);
             if (rc1) return rc1;
         }
         // (6) the m results into the [n] outputs
-        if (d_logits || d_probs) {
-            e = launch_cascade_scatter(d_out, m, lg, pr, d_logits, d_probs, s);
+        for (int j = 0; j < k && (d_logits || d_probs); ++j) {        // (a follower's results lie in its own d_logits / d_probs)
+            const nww_handle* f = j ? bank->members[j] : h;
+            e = launch_cascade_scatter(d_out, m, j ? f->d_logits : lg, !pr ? nullptr : j ? f->d_probs : pr, d_logits ? d_logits + (size_t)j * n : nullptr,
+                                       d_probs ? d_probs + (size_t)j * n : nullptr, s);
             if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'cascade_scatter' failed: %s", hipGetErrorString(e));
         }
         return NWW_OK;

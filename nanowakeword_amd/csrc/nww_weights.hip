@@ -470,6 +470,7 @@ int build_frontend_tables(nww_handle* h) {
     if (wi != h->tensors.end() && wi->second.loaded) win = wi->second.data; else fe_default_window(h->fe.win_length, win);
     auto fi = h->tensors.find("frontend.mel_fb");
     if (fi != h->tensors.end() && fi->second.loaded) fb = fi->second.data; else fe_default_melfb(h->fe, fb);
+    h->fe_window = win; h->fe_mel_fb = fb;
     FeTables tb;
     const std::string e = fe_build_tables(h->fe, win.data(), fb.data(), &tb);
     if (!e.empty()) return fail(h, NWW_ERR_INVALID, "frontend tables: %s", e.c_str());

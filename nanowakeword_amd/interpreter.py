@@ -134,16 +134,21 @@ class HipInterpreter:
         self.preprocessor = None if all_e2e else preprocessor
         self.cascade_config: dict = {}
         self.vad_threshold = 0
+        self.bank: list = []          # load_model(bank=True): the sessions that share one frontend pass, the leader first (else empty)
 
     # ------------------------------------------------------------------ construction
     @classmethod
     def load_model(cls, model: Union[str, List[str], Mapping[str, object], object, None] = None, cascade: bool = False,
-                   gate_model=None, gate_threshold: float = 0.3, device: int = 0, **kwargs) -> "HipInterpreter":
+                   gate_model=None, gate_threshold: float = 0.3, device: int = 0, bank: bool = False, **kwargs) -> "HipInterpreter":
         """Same calling convention as NanoInterpreter.load_model (:310-325).  ``model`` may be a path (or
         list of paths) to the reference's own exported ``*.onnx`` files (weights recovered by
         ``weights.state_dict_from_onnx``), to bundles written by ``weights.save_bundle`` (``*.nww.npz``),
         or ready session objects / a {name: session} mapping.  ``cascade=True`` looks for ``<name>_lite``
-        next to the main bundle; ``gate_model`` names the gate explicitly (implies cascade)."""
+        next to the main bundle; ``gate_model`` names the gate explicitly (implies cascade).  ``bank=True`` scores several wake words
+        on ONE frontend pass (session.HipBank): it applies when the interpreter is not a cascade, holds at least two e2e sessions and the
+        first one's ``bank_accepts`` takes every other - one device, one clip length, identical mel frontends; ``predict`` then keeps one
+        audio window and ``score_recording`` uploads the recording once.  Sessions that do not qualify are scored one after the other,
+        as without it; scores, histories and results are the same either way."""
         from .weights import load_session
         if model is None:
             raise ValueError("`model` is required (remote verifier mode is not part of the accelerated path)")
@@ -204,7 +209,21 @@ class HipInterpreter:
                 sessions[name] = load_session(p, device=device)
         inst = cls(sessions, **kwargs)
         inst.cascade_config = cascade_cfg
+        if bank:
+            inst._enable_bank()
         return inst
+
+    def _enable_bank(self):
+        """the sessions as a bank, when they qualify (load_model(bank=True)); otherwise nothing changes"""
+        ss = list(self.models.values())
+        lead = ss[0]
+        if (self.is_cascade or self.preprocessor is not None or len(ss) < 2 or not all(self.is_e2e.values())
+                or not all(hasattr(lead, a) for a in ("bank_accepts", "run_bank", "run_recording_bank"))
+                or len(set(self.e2e_clip_samples.values())) != 1 or not all(lead.bank_accepts(s) for s in ss[1:])):
+            return
+        self.bank = ss
+        shared = self._windows[next(iter(self.models))]            # one audio window for all models
+        self._windows = {n: shared for n in self.models}
 
     # ------------------------------------------------------------------ accessors (:196-295)
     @property
@@ -276,7 +295,17 @@ class HipInterpreter:
         current: Dict[str, float] = {}
         if self.preprocessor is None:                       # ---- E2E: raw audio windows per model
             xi = x if x.dtype == np.int16 else x.astype(np.int16)
-            for name, session in self.models.items():
+            if self.bank:                                    # one window, one upload, one frontend pass for all models
+                win = self._windows[next(iter(self.models))]
+                win.push(xi)
+                scores = ([float(p.item()) for p in self.bank[0].run_bank(self.bank, win.data.reshape(1, -1))]
+                          if win.filled >= win.size else [0.0] * len(self.models))
+                for name, score in zip(self.models, scores):
+                    self.raw_scores[name] = score
+                    if len(self.prediction_buffer.get(name, ())) < N_WARMUP_PREDICTIONS:
+                        score = 0.0
+                    current[name] = score
+            for name, session in () if self.bank else self.models.items():
                 win = self._windows[name]
                 win.push(xi)
                 if win.filled >= win.size:
@@ -403,6 +432,9 @@ class HipInterpreter:
         xi = pcm if pcm.dtype == np.int16 else pcm.astype(np.int16)
         full = np.ascontiguousarray(xi[:n_full * chunk_size])
         raw, first = {}, {}
+        if self.bank:                                             # one call: the recording uploaded once, each pass's frontend run once
+            clip = self.e2e_clip_samples[self.model_name]
+            got = dict(zip(self.models, self.bank[0].run_recording_bank(self.bank, full, hop=chunk_size, offset=(-clip) % chunk_size)))
         if self.is_cascade:
             # the device opens a superset of what predict() would: every window whose RAW gate probability reaches the threshold.  The
             # loop below still gates on the gate's post-warm-up score (_gate_closed) and zeroes the verifier wherever that says closed.
@@ -413,7 +445,7 @@ class HipInterpreter:
         for n, s in self.models.items():
             clip = self.e2e_clip_samples[n]
             first[n] = -(-clip // chunk_size) - 1                 # the chunk that fills the window
-            if self.is_cascade:
+            if self.is_cascade or self.bank:
                 raw[n] = np.asarray(got[n], np.float32).reshape(-1)
             else:
                 raw[n] = np.asarray(s.run_recording(full, hop=chunk_size, offset=(-clip) % chunk_size), np.float32).reshape(-1)
@@ -435,7 +467,7 @@ class HipInterpreter:
                 self._history(n).append(v)
                 self.post_processed_scores[n] = v
                 out[n][t] = v
-        for w in self._windows.values():
+        for w in {id(w): w for w in self._windows.values()}.values():      # (a bank's models share one window)
             w.push(full)
         if n_full < n_chunks:                                     # a last, shorter chunk: its window starts off the grid
             keep(n_full, self.predict(pcm[n_full * chunk_size:], **kw))
@@ -744,3 +776,66 @@ class CascadeStreamPool(StreamPool):
 
     def close(self):
         self.cascade.stream_close()
+
+
+class BankStreamPool(StreamPool):
+    """StreamPool through a bank (session.HipBank.stream_push_some): S streams that push, join and leave on their own, every listed
+    stream scored by all of the bank's models on one frontend pass.  Filter state is kept once per model - history, count, raw and
+    post-processed scores, ``[model][stream]`` - and every (model, slot) behaves exactly like a ``StreamPool`` of that model alone fed
+    that slot's chunks.  ``attach`` / ``detach`` are StreamPool's.  ``push`` returns {name: scores [n]}."""
+
+    def __init__(self, bank, n_streams: int, window_samples: int = 16000, hop_samples: int = HOP_SAMPLES):
+        self.bank, self.S, self.window, self.hop = bank, int(n_streams), int(window_samples), int(hop_samples)
+        self.names = list(bank.names)
+        bank.stream_open(self.S, self.window, self.hop)
+        self.attached = np.zeros(self.S, bool)
+        self.history = {n: np.zeros((PREDICTION_HISTORY, self.S), np.float32) for n in self.names}
+        self.count = {n: np.zeros(self.S, np.int64) for n in self.names}
+        self.raw_scores = {n: np.zeros(self.S, np.float32) for n in self.names}
+        self.post_processed_scores = {n: np.zeros(self.S, np.float32) for n in self.names}
+
+    def reset(self, ids=None):
+        """New session for the listed streams (None: every stream, which also puts the leader's batch back in lock-step)."""
+        if ids is None:
+            self.bank.stream_reset()
+            ids = np.arange(self.S)
+        else:
+            ids = self._ids(ids)
+            self.bank.stream_reset_some(ids)
+        for n in self.names:
+            self.history[n][:, ids] = 0.0
+            self.count[n][ids] = 0
+            self.raw_scores[n][ids] = 0.0
+            self.post_processed_scores[n][ids] = 0.0
+
+    def push(self, ids, chunk: np.ndarray, patience: dict = {}, threshold: dict = {}, debounce_time: float = 0.0) -> Dict[str, np.ndarray]:
+        """ids: strictly ascending stream numbers [n]; chunk int16 [n, hop], row i for stream ids[i] -> {name: post-processed scores [n]};
+        patience / threshold are keyed by model name, as in predict()"""
+        if not isinstance(chunk, np.ndarray):
+            raise ValueError("Input audio `x` must be a Numpy array.")
+        if (patience or debounce_time > 0) and not threshold:
+            raise ValueError("`threshold` must be provided when using `patience` or `debounce_time`.")
+        if patience and debounce_time > 0:
+            raise ValueError("`patience` and `debounce_time` cannot be used together.")
+        ids = self._ids(ids)
+        got = self.bank.stream_push_some(ids, chunk)
+        final = {}
+        for n in self.names:
+            raw = got[n][1].astype(np.float32)
+            self.raw_scores[n][ids] = raw
+            score = raw.copy()
+            cnt = self.count[n][ids]
+            score[cnt < N_WARMUP_PREDICTIONS] = 0.0
+            if n in patience:
+                _filter_by_count(score, self.history[n], cnt, ids, int(patience[n]), threshold[n], 0.0, self.hop)
+            elif debounce_time > 0 and n in threshold:
+                _filter_by_count(score, self.history[n], cnt, ids, 0, threshold[n], debounce_time, self.hop)
+            self.history[n][:-1, ids] = self.history[n][1:, ids]
+            self.history[n][-1, ids] = score
+            self.count[n][ids] = np.minimum(cnt + 1, PREDICTION_HISTORY)
+            self.post_processed_scores[n][ids] = score
+            final[n] = score
+        return final
+
+    def close(self):
+        self.bank.stream_close()

@@ -2,6 +2,7 @@
 
 ``HipModel``   : create / load_state_dict / finalize / forward - one handle on one GPU.
 ``HipCascade`` : a gate and a verifier HipModel as a pair - the verifier runs on the windows the gate opens (nww_cascade_*).
+``HipBank``    : several HipModels with identical mel frontends on ONE frontend pass - the first leads, the others run their heads (nww_bank_*).
 ``HipSession`` : duck-types ``onnxruntime.InferenceSession`` exactly as the reference uses it
                  (``get_inputs()[0].name/.shape`` and ``run(None, {"input": x}) -> [probs (B,1,1)]``;
                  reference: nanowakeword/interpreter/nanointerpreter.py:165-167,177-178,677,681,783;
@@ -380,6 +381,11 @@ class HipModel:
             return int(self.lib.nww_stream_filled(self._h))
         return int(self.lib.nww_stream_filled_of(self._h, int(s)))
 
+    def stream_filled_of(self, s: int) -> int:
+        """samples stream `s` has seen since open / its last reset; NwwError on a handle that has no open stream batch (a bank's follower)"""
+        self.stream_pool_stats()
+        return int(self.lib.nww_stream_filled_of(self._h, int(s)))
+
     def stream_close(self):
         self._check(self.lib.nww_stream_close(self._h))
 
@@ -753,6 +759,147 @@ class HipCascade:
                          ["cascade_scatter:the verifier's logits / probabilities -> their windows"]) + "\n"
 
 
+class HipBank:
+    """Several wake words on one frontend pass (nww_bank_*): finalized HipModels on one GPU whose mel frontends are identical, in
+    insertion order.  The first is the LEADER: it owns the PCM staging, the frontend's launches, the dense head input, the stream
+    batch and the recording pool; the others run only their head plans, on the leader's head input.  Every entry point returns
+    {name: (logits, probs)}, each pair bit-identical to the same call on that model alone, whichever model leads."""
+
+    def __init__(self, models: Mapping[str, HipModel]):
+        if not isinstance(models, Mapping) or not models:
+            raise ValueError("HipBank needs a non-empty {name: HipModel} mapping")
+        for m in models.values():
+            if not isinstance(m, HipModel):
+                raise TypeError("HipBank needs HipModel objects")
+            if not m.finalized:
+                raise NwwError("HipBank needs finalized HipModels")
+        self.models = dict(models)
+        self.names = list(self.models)
+        self.leader = self.models[self.names[0]]
+        self.lib = self.leader.lib
+        self.k = len(self.names)
+        self._members = (C.c_void_p * self.k)(*[m._h for m in self.models.values()])
+
+    def _check(self, rc: int):
+        self.leader._check(rc)                # a bank's errors go to the leader's handle
+
+    def check(self, window: Optional[int] = None):
+        """the bank's rules alone for clips or windows of `window` samples (nww_bank_check): raises what a call would raise"""
+        self._check(self.lib.nww_bank_check(self._members, self.k, int(self.clip_samples if window is None else window)))
+
+    @property
+    def clip_samples(self) -> int:
+        n = {name: m.clip_samples for name, m in self.models.items()}
+        if len(set(n.values())) != 1:
+            raise ValueError(f"the bank's models were built for clips of different lengths {n}: pass `window`")
+        return next(iter(n.values()))
+
+    def _split(self, logits: np.ndarray, probs: np.ndarray):
+        return {name: (logits[j].copy(), probs[j].copy()) for j, name in enumerate(self.names)}
+
+    def forward_pcm(self, pcm):
+        """int16 [B,N] -> {name: (logits [B], probs [B])}; the clips are uploaded once and the frontend runs once"""
+        pcm = HipModel._pcm(pcm)
+        B, N = pcm.shape
+        logits, probs = np.empty((self.k, B), np.float32), np.empty((self.k, B), np.float32)
+        self._check(self.lib.nww_bank_forward_pcm(self._members, self.k, pcm.ctypes.data_as(C.c_void_p), B, N,
+                                                  logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p)))
+        return self._split(logits, probs)
+
+    def forward_pcm_dev(self, pcm_ptr: int, B: int, N: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0):
+        """Raw device pointers, outputs [k][B] member-major; enqueues on `stream`, does not synchronise."""
+        self._check(self.lib.nww_bank_forward_pcm_dev(self._members, self.k, C.c_void_p(pcm_ptr), int(B), int(N),
+                                                      C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                      C.c_void_p(probs_ptr) if probs_ptr else None, C.c_void_p(stream) if stream else None))
+
+    def forward_recording(self, pcm, window: Optional[int] = None, hop: int = 1280, offset: int = 0, max_batch: int = 4096):
+        """int16 [N] -> {name: (logits [nW], probs [nW])} over the windows pcm[offset + i * hop : offset + i * hop + window]; the recording
+        goes up once and every pass runs the leader's frontend launches once"""
+        pcm = HipModel._pcm1(pcm)
+        window = int(self.clip_samples if window is None else window)
+        if offset < 0:
+            raise ValueError("offset must not be negative")
+        x = pcm[min(int(offset), len(pcm)):]
+        self.check(window)
+        nw = self.leader._rec_count(len(x), window, hop)
+        logits, probs = np.empty((self.k, nw), np.float32), np.empty((self.k, nw), np.float32)
+        if nw:
+            n_out = C.c_int32()
+            self._check(self.lib.nww_bank_forward_recording(self._members, self.k, x.ctypes.data_as(C.c_void_p), len(x), window, int(hop),
+                                                            int(max_batch), logits.ctypes.data_as(C.c_void_p),
+                                                            probs.ctypes.data_as(C.c_void_p), C.byref(n_out)))
+            assert n_out.value == nw
+        return self._split(logits, probs)
+
+    def forward_recording_dev(self, pcm_ptr: int, n_samples: int, window: int, hop: int, logits_ptr: int, probs_ptr: int = 0,
+                              max_batch: int = 4096, stream: int = 0) -> int:
+        """Raw device pointers, outputs [k][nW] member-major; enqueues on `stream`, does not synchronise.  Returns nW."""
+        nw = self.leader._rec_count(n_samples, window, hop)
+        self._check(self.lib.nww_bank_forward_recording_dev(self._members, self.k, C.c_void_p(pcm_ptr), int(n_samples), int(window), int(hop),
+                                                            int(max_batch), C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                            C.c_void_p(probs_ptr) if probs_ptr else None,
+                                                            C.c_void_p(stream) if stream else None))
+        return nw
+
+    # ------------------------------------------------------------------ streams: the batch, its rings and its state are the leader's
+    def stream_open(self, n_streams: int, window_samples: Optional[int] = None, hop_samples: int = 1280):
+        window = int(self.clip_samples if window_samples is None else window_samples)
+        self.check(window)
+        self.leader.stream_open(n_streams, window, hop_samples)
+
+    def stream_reset(self):
+        self.leader.stream_reset()
+
+    def stream_reset_some(self, ids):
+        self.leader.stream_reset_some(ids)
+
+    def stream_close(self):
+        self.leader.stream_close()
+
+    def stream_filled_of(self, i: int) -> int:
+        return self.leader.stream_filled_of(i)
+
+    def stream_pool_stats(self):
+        return self.leader.stream_pool_stats()
+
+    def stream_push_some(self, ids, chunk):
+        """ids: strictly ascending stream numbers [n]; chunk int16 [n, hop], row i for stream ids[i] -> {name: (logits [n], probs [n])},
+        0 / 0 for every model on a stream whose own ring does not hold a window yet"""
+        if not hasattr(self.leader, "_stream"):
+            raise NwwError("member 0: no open stream batch (nww_stream_open): the leader holds a bank's streams")
+        S, W, hop = self.leader._stream
+        ids = HipModel._stream_ids(ids)
+        n = len(ids)
+        chunk = HipModel._pcm(chunk) if n else np.zeros((0, hop), np.int16)
+        if chunk.shape != (n, hop):
+            raise ValueError(f"chunk must have shape ({n}, {hop}), got {chunk.shape}")
+        logits, probs = np.empty((self.k, n), np.float32), np.empty((self.k, n), np.float32)
+        self._check(self.lib.nww_bank_stream_push_some(self._members, self.k, ids.ctypes.data_as(C.c_void_p), n, chunk.ctypes.data_as(C.c_void_p),
+                                                       logits.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p)))
+        return self._split(logits, probs)
+
+    def stream_push_some_dev(self, ids, chunk_ptr: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0):
+        """Raw device pointers (ids stays on the host), outputs [k][n] member-major; enqueues on `stream`, does not synchronise."""
+        ids = HipModel._stream_ids(ids)
+        self._check(self.lib.nww_bank_stream_push_some_dev(self._members, self.k, ids.ctypes.data_as(C.c_void_p), len(ids), C.c_void_p(chunk_ptr),
+                                                           C.c_void_p(logits_ptr) if logits_ptr else None,
+                                                           C.c_void_p(probs_ptr) if probs_ptr else None,
+                                                           C.c_void_p(stream) if stream else None))
+
+    def describe(self) -> str:
+        """The launches of one bank call on a batch of clips, one per line: the leader's frontend, then every member's head plan under
+        its name (a recording's shared route and a pool call run the leader's own launches around the frontend instead)."""
+        lines = []
+        for j, (name, m) in enumerate(self.models.items()):
+            for l in m.describe_plan().strip().split("\n"):
+                if l.startswith("frontend:"):
+                    if j == 0:
+                        lines.append(l + " - once, by the leader '%s'" % name)
+                else:
+                    lines.append("%s/%s" % (name, l))
+        return "\n".join(lines) + "\n"
+
+
 class _Input:
     """Stand-in for onnxruntime NodeArg (cf. _FakeInput, remote_verifier.py:595-603)."""
 
@@ -857,6 +1004,38 @@ class HipSession:
                                                      gate_threshold=gate_threshold)
         self.last_cascade = (len(gp), n_open)
         return gp, probs
+
+    def bank_accepts(self, other_session) -> bool:
+        """Whether `other_session` can share this session's frontend pass (run_recording_bank, HipBank): both e2e HipSessions on two
+        models of one device, built for the same clip length, and the bank's rules hold for the pair led by this one (nww_bank_check)."""
+        if not (isinstance(other_session, HipSession) and other_session is not self and self.mode == "e2e" and other_session.mode == "e2e"
+                and other_session.model is not self.model and other_session.model.device == self.model.device
+                and other_session.clip_samples == self.clip_samples):
+            return False
+        pair = (C.c_void_p * 2)(self.model._h, other_session.model._h)
+        return self.model.lib.nww_bank_check(pair, 2, self.clip_samples) == 0
+
+    def _bank(self, sessions) -> "HipBank":
+        sessions = list(sessions)
+        if not sessions or sessions[0] is not self or not all(self.bank_accepts(s) for s in sessions[1:]):
+            raise ValueError("a bank needs e2e HipSessions on one device with the same clip_samples and identical frontends, led by this one")
+        key = tuple(id(s.model) for s in sessions)
+        bank = getattr(self, "_bank_cache", None)
+        if bank is None or bank[0] != key:
+            bank = self._bank_cache = (key, HipBank({str(j): s.model for j, s in enumerate(sessions)}))
+        return bank[1]
+
+    def run_bank(self, sessions, pcm: np.ndarray):
+        """int16 (B,N) / (B,1,N) or float PCM as run() takes it -> [probabilities (B,1,1)] per session of `sessions` (this one first),
+        scored on ONE upload and ONE frontend pass: HipInterpreter.predict's path for a bank."""
+        out = self._bank(sessions).forward_pcm(self._to_pcm(pcm))
+        return [out[str(j)][1].reshape(-1, 1, 1) for j in range(len(out))]
+
+    def run_recording_bank(self, sessions, pcm: np.ndarray, hop: int = 1280, offset: int = 0, max_batch: int = 4096):
+        """int16 [N] -> [probabilities [nW]] per session of `sessions` (this one first, the leader), over the windows of run_recording:
+        the recording uploaded once and each pass's frontend run once.  HipInterpreter.score_recording's batch path for a bank."""
+        out = self._bank(sessions).forward_recording(pcm, window=self.clip_samples, hop=hop, offset=offset, max_batch=max_batch)
+        return [out[str(j)][1] for j in range(len(out))]
 
     def run_logits(self, input_feed):
         logits, _ = self._forward(input_feed)

@@ -12,7 +12,9 @@ profiles/raw_recording_bench_configs.jsonl.
 --stream-pool [out]: 1024 streams per tick, lock-step against push_some (all streams, a random half) against whole-window re-scoring
 (stream_pool_main) -> profiles/stream_pool_bench_configs.jsonl.
 --cascade-pool [out]: 1024 streams per tick through a gate + verifier pair, nww_cascade_stream_push_some_dev against push_some on both
-models against the lock-step cascade (cascade_pool_main) -> profiles/cascade_pool_bench_configs.jsonl."""
+models against the lock-step cascade (cascade_pool_main) -> profiles/cascade_pool_bench_configs.jsonl.
+--bank [out]: several heads as one bank call (nww_bank_*: one frontend pass) against the same handles called one after the other, on
+batches, a stream pool and a recording (bank_main) -> profiles/bank_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -860,7 +862,171 @@ def cascade_pool_main(out_path):
     sys.stdout.write(text)
 
 
+BANK_B = 4096
+# (name, workload, [(head, seed)]): 1 s clips, 64 mel; the DNN heads are the reference's default model_type with weights of their own
+BANK_SETTINGS = [
+    ("batch 2 dnn", "batch", [("dnn", 1), ("dnn", 2)]),
+    ("batch 4 dnn", "batch", [("dnn", 1), ("dnn", 2), ("dnn", 3), ("dnn", 4)]),
+    ("batch cnn+gru+crnn", "batch", [("cnn", 1), ("gru", 1), ("crnn", 1)]),
+    ("stream pool 4 dnn, all listed", "pool_all", [("dnn", 1), ("dnn", 2), ("dnn", 3), ("dnn", 4)]),
+    ("stream pool 4 dnn, a random half", "pool_half", [("dnn", 1), ("dnn", 2), ("dnn", 3), ("dnn", 4)]),
+    ("recording cnn+dnn", "recording", [("cnn", 1), ("dnn", 1)]),
+]
+
+
+def bank_child():
+    """One process, every BANK_SETTINGS row: the members as ONE bank call (session.HipBank, PCM on the device) against the same handles
+    called one after the other through the single-handle entry points, ms per call as the median of RNN_STEPS device-event timings behind
+    RNN_WARMUP warm-up calls; and the leader's frontend entry of nww_get_profile on its single call (what a follower no longer runs).
+    Stream rows: POOL_STREAMS streams, 80 ms hops; the bank's batch is the leader's, the baseline opens one batch per handle."""
+    import torch
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipBank, HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    B, S, W, hop = BANK_B, POOL_STREAMS, REC_W, REC_HOP
+    ts = torch.cuda.Stream(dev)
+    stream = ts.cuda_stream
+    pcm = torch.from_numpy(synth_pcm("noise", B, W, seed=10)).to(dev)
+    rec_n = W + (B - 1) * hop
+    rec = torch.from_numpy(synth_pcm("speechlike", 1, rec_n, seed=3)[0]).to(dev)
+    parts = [torch.from_numpy(synth_pcm("speechlike", S, hop, seed=20 + i)).to(dev) for i in range(4)]
+    rng = np.random.default_rng(5)
+    every = np.arange(S, dtype=np.int32)
+    halves = [np.sort(rng.permutation(S)[:S // 2]).astype(np.int32) for _ in range(8)]
+    half_parts = [[p[torch.from_numpy(h.astype(np.int64)).to(dev)].contiguous() for p in parts] for h in halves]
+    fill = W // hop + 1
+    models = {}
+
+    def model(head, seed):
+        if (head, seed) not in models:
+            cfg = HeadConfig(head, (101, 64))
+            models[(head, seed)] = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg, seed=seed), window=window, mel_fb=fb)
+        return models[(head, seed)]
+
+    def timed(step):
+        for i in range(RNN_WARMUP):
+            step(i)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for i, (e0, e1) in enumerate(ev):
+            e0.record(ts); step(RNN_WARMUP + i); e1.record(ts)
+        torch.cuda.synchronize()
+        return round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+
+    def frontend_ms(lead, step):
+        lead.set_profiling(True)
+        for i in range(20):
+            step(i)
+        torch.cuda.synchronize()
+        name, ms, cnt = lead.get_profile()[0]
+        lead.set_profiling(False)
+        return round(ms / max(cnt, 1), 4)
+
+    for name, work, heads in BANK_SETTINGS:
+        ms = [model(h, s) for h, s in heads]
+        k = len(ms)
+        bank = HipBank({str(j): m for j, m in enumerate(ms)})
+        n = {"batch": B, "recording": B, "pool_all": S, "pool_half": S // 2}[work]
+        lg = torch.empty(k * n, dtype=torch.float32, device=dev)
+        rows = [lg[j * n:(j + 1) * n] for j in range(k)]
+        out = {"setting": name, "workload": work, "members": [h for h, _ in heads], "k": k, "items": n}
+        if work == "batch":
+            def one(m, row):
+                m.forward_pcm_dev(pcm.data_ptr(), B, W, row.data_ptr(), 0, stream)
+            sep = timed(lambda i: [one(m, r) for m, r in zip(ms, rows)])
+            want = lg.clone()
+            bnk = timed(lambda i: bank.forward_pcm_dev(pcm.data_ptr(), B, W, lg.data_ptr(), 0, stream))
+            fe_ms = frontend_ms(ms[0], lambda i: one(ms[0], rows[0]))
+        elif work == "recording":
+            def one(m, row):
+                m.forward_recording_dev(rec.data_ptr(), rec_n, W, hop, row.data_ptr(), 0, B, stream)
+            sep = timed(lambda i: [one(m, r) for m, r in zip(ms, rows)])
+            want = lg.clone()
+            bnk = timed(lambda i: bank.forward_recording_dev(rec.data_ptr(), rec_n, W, hop, lg.data_ptr(), 0, B, stream))
+            fe_ms = frontend_ms(ms[0], lambda i: one(ms[0], rows[0]))
+            out["route"] = ms[0].recording_route(W, hop)
+        else:
+            def args(i):
+                return (every, parts[i % 4]) if work == "pool_all" else (halves[i % 8], half_parts[i % 8][i % 4])
+
+            def one(m, row, i):
+                ids, chunk = args(i)
+                m.stream_push_some_dev(ids, chunk.data_ptr(), row.data_ptr(), 0, stream)
+            for m in ms:                                           # the baseline: a batch per handle, each filled
+                m.stream_open(S, W, hop)
+                for i in range(fill):
+                    m.stream_push_some_dev(every, parts[i % 4].data_ptr(), rows[0].data_ptr(), 0, stream)
+            sep = timed(lambda i: [one(m, r, i) for m, r in zip(ms, rows)])
+            fe_ms = frontend_ms(ms[0], lambda i: one(ms[0], rows[0], RNN_WARMUP + RNN_STEPS + i))
+            for m in ms:
+                m.stream_close()
+            bank.stream_open(S, W, hop)                            # the bank: the leader's batch alone, filled, then the same calls
+            for i in range(fill):
+                bank.stream_push_some_dev(every, parts[i % 4].data_ptr(), lg.data_ptr(), 0, stream)
+
+            def step(i):
+                ids, chunk = args(i)
+                bank.stream_push_some_dev(ids, chunk.data_ptr(), lg.data_ptr(), 0, stream)
+            bnk = timed(step)
+            out["route"] = bank.stream_pool_stats()[1]
+            bank.stream_close()
+            want = None
+        if want is not None:                                       # the timed bank call wrote what the separate calls wrote
+            torch.cuda.synchronize()
+            out["bit_identical"] = bool(torch.equal(want, lg))
+        out.update(bank_ms=bnk, separate_ms=sep, frontend_ms=fe_ms)
+        print(json.dumps(out), flush=True)
+    for m in models.values():
+        m.close()
+
+
+def bank_main(out_path):
+    """RNN_REPEATS fresh processes, one after another, every setting in each; per setting the medians of the repeats and their spread
+    (max - min, the larger of the two legs), the saving (separate - bank) against the expected (k - 1) x the leader's frontend entry, and
+    whether the bank is faster by more than the spread."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--bank-child"], env=dict(os.environ), cwd=ROOT,
+                           stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"child exited {r.returncode}")
+        print(r.stdout.strip(), file=sys.stderr, flush=True)
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")])
+    lines = []
+    for i, (name, work, heads) in enumerate(BANK_SETTINGS):
+        rep = {key: [r[i][key] for r in runs] for key in ("bank_ms", "separate_ms", "frontend_ms")}
+        med = {key: float(np.median(v)) for key, v in rep.items()}
+        spread = max(max(rep[key]) - min(rep[key]) for key in ("bank_ms", "separate_ms"))
+        k = len(heads)
+        saved, expected = med["separate_ms"] - med["bank_ms"], (k - 1) * med["frontend_ms"]
+        line = {"config": f"bank: {name}, 1 s clips, 64 mel, {runs[0][i]['items']} items, ms per call", "workload": work, "members": [h for h, _ in heads],
+                "k": k, "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS}
+        for key in rep:
+            line[key + "_repeats"] = rep[key]
+            line[key] = round(med[key], 4)
+        line.update(spread_ms=round(spread, 4), saved_ms=round(saved, 4), expected_saving_ms=round(expected, 4),
+                    saved_over_expected=round(saved / expected, 3) if expected > 0 else None, bank_wins=bool(saved > spread))
+        for key in ("route", "bit_identical"):
+            if key in runs[0][i]:
+                line[key] = runs[0][i][key] if key == "route" else all(r[i][key] for r in runs)
+        lines.append(line)
+    text = "".join(json.dumps(l) + "\n" for l in lines)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--bank-child" in sys.argv[1:]:
+        return bank_child()
+    if "--bank" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--bank"]
+        return bank_main(rest[0] if rest else os.path.join(ROOT, "profiles", "bank_bench_configs.jsonl"))
     if "--cascade-pool-child" in sys.argv[1:]:
         return cascade_pool_child()
     if "--cascade-pool" in sys.argv[1:]:
