@@ -411,6 +411,51 @@ extern int nww_bank_stream_push_some_dev(nww_handle* const* members, int32_t k, 
 extern int nww_bank_stream_push_some(nww_handle* const* members, int32_t k, const int32_t* idx, int32_t n, const int16_t* chunk,
                                      float* logits, float* probs);
 
+/* ---- clips mixed on the device: SNR mixing and level scaling (augment_clips.py:45-79,201-231,246-259) --------------------------------
+ * An ARENA is one int16 device buffer of arena_samples samples in which foregrounds and backgrounds lie back to back (2-byte alignment
+ * only).  A call takes a HOST table of B items and writes int16 out[B][N]; the table goes up through slots of the handle's own pinned
+ * and device buffers (an event per slot), the device gathers, measures and mixes.  What the reference draws at random - background,
+ * crop, position, SNR, gain, level - the host decides and writes into the item; the arithmetic is fixed so that it is the same bits on
+ * the host (csrc/mix_plan.h, tests/mix_oracle.py) and on the device.  With f[j] = fg[j] / 32768, b[i] = bg[(bg_start + i) % bg_len] / 32768:
+ *   Sf = sum fg[j]^2, Sb = sum of the background's squares under the foreground (at start + j), P = max |background| over the N
+ *   samples: exact integers.  The background is REAL iff bg_len > 0 and P >= 4 (the reference's peak > 1e-4).
+ *   real:      scale in float64 from Sf, Sb (eps = 2^-23, background floor 0.005, scaled-foreground floor 0.01: _mix_snr), rounded
+ *              to float32 once = s;  x[i] = b[i], and x[i] = b[i] + f[i - start] * s for start <= i < start + fg_len
+ *   not real:  x[i] = f[i] for i < fg_len, 0 elsewhere (`start` is ignored)
+ *   y = x * gain;  flags bit 0 (peak-normalise): pk = max |y| (1 if < 1e-8), z = y * (level / pk);  clear: z = y * level
+ *   out[i] = (int16) trunc(clamp(z, -1, 1) * 32767)
+ * Every float32 product and sum is rounded on its own (nothing contracted).  A clip depends on its own item alone: the same bits at
+ * any B, at any position in the table.  DESIGN.md 4.8g.
+ * Rules, checked on the host for EVERY item before anything is enqueued - a failing call launches nothing, takes no table slot and
+ * returns NWW_ERR_INVALID with the item's index and the field's name in nww_last_error:
+ *   1 <= fg_len <= N;  [fg_off, fg_off + fg_len) inside the arena;  bg_len >= 0, and for bg_len > 0 [bg_off, bg_off + bg_len)
+ *   inside the arena and 0 <= bg_start < bg_len (bg_off and bg_start are not read when bg_len == 0);  0 <= start <= N - fg_len;
+ *   snr_linear, gain and level finite and > 0;  no flag bit but bit 0.
+ * N >= 1.  B == 0 returns NWW_OK and does nothing.  The handle must be finalized.
+ * (Declared `extern` like the blocks above.)                                                                                        */
+typedef struct nww_mix_item {
+    int64_t fg_off, bg_off;            /* first sample of the foreground / background in the arena                       */
+    int32_t fg_len, bg_len;            /* samples; bg_len == 0: no background                                            */
+    int32_t bg_start;                  /* clip sample i reads background sample (bg_start + i) % bg_len                  */
+    int32_t start;                     /* clip sample the foreground's first sample is mixed into                        */
+    float snr_linear, gain, level;     /* 10^(snr_db / 20), 10^(gain_db / 20), target peak (bit 0 set) or volume factor */
+    uint32_t flags;                    /* NWW_MIX_PEAK_NORMALISE; 48 bytes, no implicit padding                          */
+} nww_mix_item;
+#define NWW_MIX_PEAK_NORMALISE 1u
+/* d_arena [arena_samples], items [B] (host) -> d_out [B][N]; asynchronous on `stream` (NULL: the handle's own); `items` may be reused
+   as soon as the call returns                                                                                                        */
+extern int nww_mix_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const nww_mix_item* items, int32_t B, int32_t N,
+                       int16_t* d_out, void* stream);
+/* host pointers: the arena is uploaded, the clips are mixed and downloaded; synchronises before it returns                         */
+extern int nww_mix(nww_handle* h, const int16_t* arena, int64_t arena_samples, const nww_mix_item* items, int32_t B, int32_t N, int16_t* out);
+/* the clips mixed into the handle's PCM staging, then nww_forward_pcm_dev's path on them: d_logits / d_probs [B] (d_probs may be
+   NULL), bit-identical to nww_forward_pcm on the output of nww_mix                                                                  */
+extern int nww_mix_forward_pcm_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const nww_mix_item* items, int32_t B, int32_t N,
+                                   float* d_logits, float* d_probs, void* stream);
+/* ... then nww_frontend_dev's path on them: d_logmel as nww_frontend_dev writes it                                                  */
+extern int nww_mix_frontend_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const nww_mix_item* items, int32_t B, int32_t N,
+                                float* d_logmel, int32_t frames_major, void* stream);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

@@ -53,6 +53,7 @@ SYMBOLS = [
     "nww_cascade_stream_push_some", "nww_cascade_stream_push_some_dev", "nww_cascade_stream_reset_some",
     "nww_bank_check", "nww_bank_forward_pcm_dev", "nww_bank_forward_pcm", "nww_bank_forward_recording_dev", "nww_bank_forward_recording",
     "nww_bank_stream_push_some_dev", "nww_bank_stream_push_some",
+    "nww_mix_dev", "nww_mix", "nww_mix_forward_pcm_dev", "nww_mix_frontend_dev",
 ]
 
 
@@ -180,6 +181,12 @@ def load_library():
     lib.nww_bank_forward_recording.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i32p]; lib.nww_bank_forward_recording.restype = C.c_int
     lib.nww_bank_stream_push_some_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]; lib.nww_bank_stream_push_some_dev.restype = C.c_int
     lib.nww_bank_stream_push_some.argtypes = [vp, i32, vp, i32, vp, vp, vp]; lib.nww_bank_stream_push_some.restype = C.c_int
+    # clips mixed on the device: `items` is a host table of nww_mix_item (augment.MIX_ITEM), passed as a pointer
+    i64 = C.c_int64
+    lib.nww_mix_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp]; lib.nww_mix_dev.restype = C.c_int
+    lib.nww_mix.argtypes = [vp, vp, i64, vp, i32, i32, vp]; lib.nww_mix.restype = C.c_int
+    lib.nww_mix_forward_pcm_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp]; lib.nww_mix_forward_pcm_dev.restype = C.c_int
+    lib.nww_mix_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, i32, vp]; lib.nww_mix_frontend_dev.restype = C.c_int
     _lib = lib
     return lib
 

@@ -171,6 +171,7 @@ extern "C" int nww_destroy(nww_handle* h) {
     nww_recording_free(h);
     nww_cascade_free(h);
     nww_bank_free(h);
+    nww_mix_free(h);
     nww_comm_destroy(h);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);

@@ -3,6 +3,7 @@
 // and weight preparation; nww_plan.hip: the per-head launch plans (nww_finalize); nww_stream.hip: batched streaming (nww_stream_*); nww_comm.hip: RCCL gather;
 // nww_emb.hip: embedding-mode state (nww_emb_*); nww_recording.hip: recording scoring (nww_recording_*, nww_forward_recording*);
 // nww_cascade.hip: gate + verifier cascades (nww_cascade_*); nww_bank.hip: model banks (nww_bank_*: K heads on one frontend pass);
+// nww_mix.hip: clips mixed on the device out of an arena (nww_mix_*; kernel in mix.hip, arithmetic in mix_plan.h);
 // stream_plan.h: what a (window, hop) pair shares between windows (host-only arithmetic, used by the last two); stream_pool.h: the
 // one ring state of a stream batch, moved by its lock-step calls and by the calls whose streams push and reset on their own (host-only
 // too, used by nww_stream.hip and read by nww_cascade.hip); plan_host.h: the
@@ -175,6 +176,7 @@ struct nww_handle {
     // bank scoring (nww_bank.hip), held by the LEADER's handle: the dense [2][k][n] logits / probabilities of the host-pointer entry
     // points, grown on demand
     float* d_bank_out = nullptr; size_t bank_out_bytes = 0;
+    struct MixState* mix = nullptr; // clip mixing (nww_mix.hip): the table slots and the host-pointer entry point's buffers, made by the first call
     void* comm = nullptr;          // ncclComm_t of this rank (nww_comm_init)
     unsigned char* pin_in = nullptr; unsigned char* pin_out = nullptr;   // pinned staging for small host-pointer calls
     bool pin_in_busy = false;                                            // an async copy out of pin_in may still be in flight
@@ -251,6 +253,7 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
                          const PoolEntry** tab_out = nullptr, int* m_out = nullptr, const BankRun* bank = nullptr);
 void nww_cascade_free(nww_handle* h);          // nww_cascade.hip
 void nww_bank_free(nww_handle* h);             // nww_bank.hip
+void nww_mix_free(nww_handle* h);              // nww_mix.hip
 void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next eight: what nww_finalize does to the loaded weights before it plans
 void balance_channel_gains(nww_handle* h);
 void fold_batchnorms(nww_handle* h);

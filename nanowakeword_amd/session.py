@@ -351,6 +351,61 @@ class HipModel:
                                                       C.c_void_p(probs_ptr) if probs_ptr else None,
                                                       C.c_void_p(stream) if stream else None))
 
+    # ------------------------------------------------------------------ clips mixed on the device (nww_mix_*, augment.py)
+    def mix_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, stream: int = 0):
+        """Raw device pointers; `items` is a host table of augment.MIX_ITEM.  int16 out [B, N]; enqueues on `stream`, does not synchronise."""
+        from .augment import as_items
+        items = as_items(items)
+        self._check(self.lib.nww_mix_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items), int(N),
+                                         C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def forward_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0):
+        """mix_dev into the handle's PCM staging, then forward_pcm_dev's path on it; does not synchronise."""
+        from .augment import as_items
+        items = as_items(items)
+        self._check(self.lib.nww_mix_forward_pcm_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
+                                                     int(N), C.c_void_p(logits_ptr), C.c_void_p(probs_ptr) if probs_ptr else None,
+                                                     C.c_void_p(stream) if stream else None))
+
+    def frontend_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, frames_major: bool = False, stream: int = 0):
+        """mix_dev into the handle's PCM staging, then frontend_dev's path on it; does not synchronise."""
+        from .augment import as_items
+        items = as_items(items)
+        self._check(self.lib.nww_mix_frontend_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
+                                                  int(N), C.c_void_p(out_ptr), int(frames_major), C.c_void_p(stream) if stream else None))
+
+    def mix(self, arena, items, N: int) -> np.ndarray:
+        """The clips of `items` (augment.mix_items / draw_mix_items) mixed out of `arena` -> int16 [B, N].  A device-resident
+        augment.ClipArena is read where it lies; a host arena (ClipArena(device=None) or an int16 array) is uploaded by the call."""
+        from .augment import as_items
+        items = as_items(items)
+        B, N = len(items), int(N)
+        host = arena if isinstance(arena, np.ndarray) else arena.host
+        if host is not None:
+            if host.dtype != np.int16 or host.ndim != 1:
+                raise ValueError("a host arena must be a one-dimensional int16 array")
+            host = np.ascontiguousarray(host)
+            out = np.empty((B, max(N, 0)), np.int16)
+            self._check(self.lib.nww_mix(self._h, host.ctypes.data_as(C.c_void_p), host.size, items.ctypes.data_as(C.c_void_p), B, N,
+                                         out.ctypes.data_as(C.c_void_p)))
+            return out
+        import torch
+        out = torch.empty((B, max(N, 0)), dtype=torch.int16, device=f"cuda:{self.device}")
+        self.mix_dev(arena.ptr, arena.samples, items, N, out.data_ptr())
+        torch.cuda.synchronize(self.device)
+        return out.cpu().numpy()
+
+    def forward_mixed(self, arena, items, N: int):
+        """(logits [B], probs [B]) of the clips mix() gives, bit-identical to forward_pcm(mix(arena, items, N)); the clips stay on the device."""
+        import torch
+        from .augment import as_items
+        items = as_items(items)
+        out = torch.zeros((2, len(items)), dtype=torch.float32, device=f"cuda:{self.device}")
+        self.forward_mixed_dev(arena.ptr, arena.samples, items, N, out[0].data_ptr(), out[1].data_ptr())
+        torch.cuda.synchronize(self.device)
+        res = out.cpu().numpy()
+        return res[0].copy(), res[1].copy()
+
     # ------------------------------------------------------------------ batched streaming (rings on the device)
     def stream_open(self, n_streams: int, window_samples: int = 16000, hop_samples: int = 1280):
         self._check(self.lib.nww_stream_open(self._h, int(n_streams), int(window_samples), int(hop_samples)))
@@ -1040,6 +1095,17 @@ class HipSession:
     def run_logits(self, input_feed):
         logits, _ = self._forward(input_feed)
         return logits.reshape(-1, 1)
+
+    # clips mixed on the device out of an augment.ClipArena (HipModel.mix / forward_mixed): clips of clip_samples
+    def mix(self, arena, items) -> np.ndarray:
+        """int16 [B, clip_samples]: the clips of `items` mixed out of `arena`"""
+        return self.model.mix(arena, items, self.clip_samples)
+
+    def forward_mixed(self, arena, items):
+        """[probabilities (B,1,1)] as run() returns them for mix(arena, items), the clips never leaving the device"""
+        if self.mode != "e2e":
+            raise ValueError("forward_mixed needs an e2e session (raw PCM in)")
+        return [self.model.forward_mixed(arena, items, self.clip_samples)[1].reshape(-1, 1, 1)]
 
     # a pool of streams on the session's model (interpreter.StreamPool takes a session as its backend): windows of clip_samples
     def stream_open(self, n_streams: int, window_samples: Optional[int] = None, hop_samples: int = 1280):

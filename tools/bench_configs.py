@@ -14,7 +14,9 @@ profiles/raw_recording_bench_configs.jsonl.
 --cascade-pool [out]: 1024 streams per tick through a gate + verifier pair, nww_cascade_stream_push_some_dev against push_some on both
 models against the lock-step cascade (cascade_pool_main) -> profiles/cascade_pool_bench_configs.jsonl.
 --bank [out]: several heads as one bank call (nww_bank_*: one frontend pass) against the same handles called one after the other, on
-batches, a stream pool and a recording (bank_main) -> profiles/bank_bench_configs.jsonl."""
+batches, a stream pool and a recording (bank_main) -> profiles/bank_bench_configs.jsonl.
+--mix [out]: clips mixed on the device (nww_mix_*) alone and in front of the CNN head, against uploading the pre-mixed batch and against
+the same chain in torch ops (mix_main) -> profiles/mix_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -1021,7 +1023,146 @@ def bank_main(out_path):
     sys.stdout.write(text)
 
 
+MIX_B, MIX_N, MIX_COPY_CEILING = 4096, 16000, 6.29e12          # the measured-copy ceiling in bytes / s
+
+
+def torch_mix(torch, arena, tab, N):
+    """The chain of nww_mix_dev in torch ops on the device, as augment_clips writes it for one clip (float32 means, its own op order):
+    arena int16 [samples], tab a dict of [B] device tensors -> int16 [B, N]"""
+    i = torch.arange(N, device=arena.device)[None, :]
+    j = i - tab["start"][:, None]
+    in_fg = (j >= 0) & (j < tab["fg_len"][:, None])
+    f = torch.where(in_fg, arena[(tab["fg_off"][:, None] + j.clamp(min=0)).clamp(max=arena.numel() - 1)], 0).to(torch.float32) / 32768.0
+    b = arena[tab["bg_off"][:, None] + (tab["bg_start"][:, None] + i) % tab["bg_len"][:, None]].to(torch.float32) / 32768.0
+    n = tab["fg_len"][:, None].to(torch.float32)
+    eps = torch.finfo(torch.float32).eps
+    fr = torch.sqrt((f * f).sum(1, keepdim=True) / n + eps)
+    br = torch.sqrt((torch.where(in_fg, b, 0.0) ** 2).sum(1, keepdim=True) / n + eps).clamp(min=0.005)
+    scale = tab["snr_linear"][:, None] * br / fr
+    srms = torch.sqrt(((f * scale) ** 2).sum(1, keepdim=True) / n + eps)
+    scale = torch.where(srms < 0.01, scale * (0.01 / srms), scale)
+    y = (b + f * scale) * tab["gain"][:, None]
+    pk = y.abs().amax(1, keepdim=True)
+    pk = torch.where(pk < 1e-8, torch.ones_like(pk), pk)
+    return (torch.clamp(y * (tab["level"][:, None] / pk), -1.0, 1.0) * 32767).to(torch.int16)
+
+
+def mix_child():
+    """One process: MIX_B clips of MIX_N samples out of a device-resident arena of 64 foregrounds of 0.5 - 1 s and 16 backgrounds of 1 - 10 s
+    (augment.draw_mix_items, every clip with a background), CNN head.  ms per call as the median of RNN_STEPS device-event timings behind
+    RNN_WARMUP warm-up calls, every leg on one stream: (a) mix_dev alone, (b) forward_mixed_dev, (r) forward_pcm_dev on the resident mixed
+    clips, (c) the pre-mixed batch copied up from pinned host memory + forward_pcm_dev, (d) the chain in torch ops; and whether (d)'s clips
+    are (a)'s to within 1 LSB."""
+    import torch
+    from nanowakeword_amd.augment import ClipArena, draw_mix_items
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    cfg = HeadConfig("cnn", (101, 64))
+    m = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+    rng = np.random.default_rng(7)
+    fg_len = rng.integers(MIX_N // 2, MIX_N + 1, 64)
+    bg_len = rng.integers(MIX_N, 10 * MIX_N + 1, 16)
+    clips = [synth_pcm("speechlike", 1, int(n), seed=100 + k)[0] for k, n in enumerate(fg_len)] + \
+            [synth_pcm("noise", 1, int(n), seed=200 + k)[0] for k, n in enumerate(bg_len)]
+    arena = ClipArena(clips, device=0)
+    items = draw_mix_items(rng, arena, rng.integers(0, 64, MIX_B), 64 + np.arange(16), MIX_N)
+    B, N = MIX_B, MIX_N
+    ts = torch.cuda.Stream(dev)
+    stream = ts.cuda_stream
+    m.reserve(B, N)
+    pcm = torch.empty((B, N), dtype=torch.int16, device=dev)
+    lg, pr = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(2))
+    m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream)
+    torch.cuda.synchronize()
+    pcm_host = pcm.cpu().pin_memory()
+    up = torch.empty_like(pcm)
+    tab = {k: torch.from_numpy(np.ascontiguousarray(items[k]).astype(np.float32 if items[k].dtype.kind == "f" else np.int64)).to(dev) for k in items.dtype.names}
+
+    def upload_forward():
+        with torch.cuda.stream(ts):
+            up.copy_(pcm_host, non_blocking=True)
+        m.forward_pcm_dev(up.data_ptr(), B, N, lg.data_ptr(), pr.data_ptr(), stream)
+
+    def torch_leg():
+        with torch.cuda.stream(ts), torch.no_grad():
+            return torch_mix(torch, arena._dev, tab, N)
+    legs = {"mix": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream),
+            "mix_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream),
+            "resident_forward": lambda: m.forward_pcm_dev(pcm.data_ptr(), B, N, lg.data_ptr(), pr.data_ptr(), stream),
+            "upload_forward": upload_forward, "torch_mix": torch_leg}
+    # what the passes of mix.hip cost: the same table without peak normalisation (no pass 2), and without backgrounds (no pass 1, half the reads)
+    no_peak, no_bg = items.copy(), items.copy()
+    no_peak["flags"] = 0
+    no_bg["bg_len"] = 0
+    legs["mix_no_peak"] = lambda: m.mix_dev(arena.ptr, arena.samples, no_peak, N, pcm.data_ptr(), stream)
+    legs["mix_no_background"] = lambda: m.mix_dev(arena.ptr, arena.samples, no_bg, N, pcm.data_ptr(), stream)
+    read = int((2 * (2 * items["fg_len"].astype(np.int64) + N)).sum())
+    out = {"B": B, "N": N, "arena_samples": arena.samples, "algorithmic_read_bytes": read, "algorithmic_written_bytes": 2 * B * N,
+           "batch_bytes": 2 * B * N}
+    for name, step in legs.items():
+        for _ in range(RNN_WARMUP):
+            got = step()
+        torch.cuda.synchronize()
+        if name == "torch_mix":
+            d = (got.to(torch.int32) - pcm.to(torch.int32)).abs()
+            out["torch_mix_max_lsb"], out["torch_mix_differing_share"] = int(d.max()), round(float((d > 0).float().mean()), 6)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for e0, e1 in ev:
+            e0.record(ts); step(); e1.record(ts)
+        torch.cuda.synchronize()
+        out[name + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+    print(json.dumps(out), flush=True)
+    m.close()
+
+
+def mix_main(out_path):
+    """RNN_REPEATS fresh child processes, one after another, each under its own time limit; the medians of the repeats, their spread (max -
+    min over the repeats, the largest of the legs compared), and the claim: mixing on the device in front of the head costs less over
+    the head on resident PCM than uploading the mixed batch does, by more than the spread."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--mix-child"], env=dict(os.environ), cwd=ROOT,
+                           stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"mix child exited {r.returncode}")
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][0])
+    names = ("mix", "mix_forward", "resident_forward", "upload_forward", "torch_mix", "mix_no_peak", "mix_no_background")
+    rep = {k: [r[k + "_ms"] for r in runs] for k in names}
+    med = {k: float(np.median(v)) for k, v in rep.items()}
+    spread = max(max(rep[k]) - min(rep[k]) for k in ("mix_forward", "resident_forward", "upload_forward"))
+    first = runs[0]
+    moved = first["algorithmic_read_bytes"] + first["algorithmic_written_bytes"]
+    line = {"config": f"mix B={MIX_B} N={MIX_N}, foregrounds of 0.5-1 s, device-resident arena, cnn 101x64", "B": MIX_B, "N": MIX_N,
+            "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS, "ms_repeats": rep,
+            "algorithmic_bytes": moved, "mix_ms": round(med["mix"], 4),
+            "mix_fraction_of_copy_ceiling": round(moved / (med["mix"] * 1e-3) / MIX_COPY_CEILING, 3),
+            "mix_forward_ms": round(med["mix_forward"], 4), "resident_forward_ms": round(med["resident_forward"], 4),
+            "upload_forward_ms": round(med["upload_forward"], 4), "torch_mix_ms": round(med["torch_mix"], 4), "spread_ms": round(spread, 4),
+            "mix_over_resident_ms": round(med["mix_forward"] - med["resident_forward"], 4),
+            "upload_over_resident_ms": round(med["upload_forward"] - med["resident_forward"], 4),
+            "mix_costs_less_than_upload": bool((med["upload_forward"] - med["mix_forward"]) > spread),
+            "clips_per_s": {k: round(MIX_B / (med[k] * 1e-3)) for k in ("mix_forward", "resident_forward", "upload_forward")},
+            "torch_mix_over_mix": round(med["torch_mix"] / med["mix"], 1),
+            "mix_without_peak_pass_ms": round(med["mix_no_peak"], 4), "mix_without_backgrounds_ms": round(med["mix_no_background"], 4),
+            "torch_mix_max_lsb": first["torch_mix_max_lsb"], "torch_mix_differing_share": first["torch_mix_differing_share"]}
+    text = json.dumps(line) + "\n"
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--mix-child" in sys.argv[1:]:
+        return mix_child()
+    if "--mix" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--mix"]
+        return mix_main(rest[0] if rest else os.path.join(ROOT, "profiles", "mix_bench_configs.jsonl"))
     if "--bank-child" in sys.argv[1:]:
         return bank_child()
     if "--bank" in sys.argv[1:]:
