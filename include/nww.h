@@ -456,6 +456,40 @@ extern int nww_mix_forward_pcm_dev(nww_handle* h, const int16_t* d_arena, int64_
 extern int nww_mix_frontend_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const nww_mix_item* items, int32_t B, int32_t N,
                                 float* d_logmel, int32_t frames_major, void* stream);
 
+/* ---- ... through a room impulse response (the reference's ApplyImpulseResponse, augment_clips.py:150-157) ----------------------------
+ * With y[i] the float32 clip above (after the gain, before the level) and h[0 .. L) a float32 impulse response:
+ *   w[i] = sum over k <= i, k < L of h[k] * y[i - k],  0 <= i < N        (convolve(mode = "full")[..., :N])
+ * and the tail runs on w: pk = max |w| under bit 0 (1 if < 1e-8), z = w * ratio, out as above.  Taps at k >= N never reach the first N
+ * outputs and are dropped.  The response's own scale is the caller's business (under bit 0 it cancels in level / pk).
+ * The convolution is a float32 FFT of M real points per clip held in LDS (csrc/rir.hip): M is the smallest of 2048,
+ * 8192 and 32768 with N + min(L_max, N) - 1 <= M - nww_rir_fft_size returns it, or 0 where none fits (every N <= 16384 fits with any
+ * response).  The arithmetic is fixed (csrc/rir_plan.h, restated in tests/rir_oracle.py): the same bits on the host and the device, at
+ * any B and any position in the table.  An item without a response (ir_id == -1) is the clip nww_mix gives, bit for bit.
+ * Response SPECTRA are prepared once: nww_rir_prepare_dev takes K responses lying back to back in a float32 device buffer
+ * (ir_off / ir_len: HOST arrays, samples) and writes float [K][M] (8-byte aligned) in the kernel's own order - opaque to callers, valid
+ * for this N and M only.  A response with N + min(ir_len, N) - 1 > 32768 is NWW_ERR_INVALID with its index ("overlap-save not built"),
+ * and so are ir_len < 1, one that does not fit M, and an M that is none of the three; nothing is truncated silently.  The call
+ * synchronises `stream` before it returns.
+ * The mixing calls take a second HOST table rir_items [B] next to `items` (NULL: no response anywhere, M / d_spectra / n_irs are not
+ * read and the call is nww_mix_*'s); both tables go up in ONE copy through the same slot.  Checked on the host for every item before
+ * anything is enqueued, after the rules above: ir_id in [-1, n_irs), reserved == 0, and M one of the three sizes with N <= M (the M the
+ * spectra were prepared at) - NWW_ERR_INVALID names the index and the field, nothing is launched and no slot is taken.                */
+typedef struct nww_rir_item { int32_t ir_id; uint32_t reserved; } nww_rir_item;   /* -1: none; reserved == 0 */
+extern int32_t nww_rir_fft_size(int32_t N, int32_t max_ir_len);
+extern int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int64_t* ir_off, const int32_t* ir_len, int32_t K, int32_t N, int32_t M,
+                               float* d_spectra, void* stream);
+extern int nww_mix_rir_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                           const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, int16_t* d_out, void* stream);
+/* arena and out are host pointers as in nww_mix; d_spectra stays a device pointer (nww_rir_prepare_dev wrote it)                     */
+extern int nww_mix_rir(nww_handle* h, const int16_t* arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                       const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, int16_t* out);
+extern int nww_mix_rir_forward_pcm_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                                       const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, float* d_logits,
+                                       float* d_probs, void* stream);
+extern int nww_mix_rir_frontend_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                                    const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, float* d_logmel,
+                                    int32_t frames_major, void* stream);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

@@ -54,6 +54,7 @@ SYMBOLS = [
     "nww_bank_check", "nww_bank_forward_pcm_dev", "nww_bank_forward_pcm", "nww_bank_forward_recording_dev", "nww_bank_forward_recording",
     "nww_bank_stream_push_some_dev", "nww_bank_stream_push_some",
     "nww_mix_dev", "nww_mix", "nww_mix_forward_pcm_dev", "nww_mix_frontend_dev",
+    "nww_rir_fft_size", "nww_rir_prepare_dev", "nww_mix_rir_dev", "nww_mix_rir", "nww_mix_rir_forward_pcm_dev", "nww_mix_rir_frontend_dev",
 ]
 
 
@@ -187,6 +188,15 @@ def load_library():
     lib.nww_mix.argtypes = [vp, vp, i64, vp, i32, i32, vp]; lib.nww_mix.restype = C.c_int
     lib.nww_mix_forward_pcm_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp]; lib.nww_mix_forward_pcm_dev.restype = C.c_int
     lib.nww_mix_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, i32, vp]; lib.nww_mix_frontend_dev.restype = C.c_int
+    # ... through room impulse responses: spectra prepared once (device), `rir_items` a second host table (augment.RIR_ITEM)
+    lib.nww_rir_fft_size.argtypes = [i32, i32]; lib.nww_rir_fft_size.restype = i32
+    lib.nww_rir_prepare_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]; lib.nww_rir_prepare_dev.restype = C.c_int
+    lib.nww_mix_rir_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp]; lib.nww_mix_rir_dev.restype = C.c_int
+    lib.nww_mix_rir.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp]; lib.nww_mix_rir.restype = C.c_int
+    lib.nww_mix_rir_forward_pcm_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.nww_mix_rir_forward_pcm_dev.restype = C.c_int
+    lib.nww_mix_rir_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp]
+    lib.nww_mix_rir_frontend_dev.restype = C.c_int
     _lib = lib
     return lib
 

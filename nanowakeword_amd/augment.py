@@ -7,8 +7,10 @@ device, and the recordings - uploaded once as a ``ClipArena`` - are gathered, me
 ``forward_mixed``, ``HipFeatures.embed_mixed``).  A robustness sweep of 1 000 positives x 20 noises x 6 SNRs is 120 000 table rows over
 1 020 recordings.
 
-Not restated: pitch shift and impulse responses (``torch_audiomentations``' PitchShift / ApplyImpulseResponse, augment_clips.py:150-157);
-``gain`` is the reference's Gain step, ``level`` its volume step (:246-255).
+Impulse responses (``ApplyImpulseResponse(p=rir_prob)``, augment_clips.py:150-157) ride on the same calls: the responses
+go up once as an ``IrArena``, whose spectra are prepared once, ``draw_rir_ids`` draws a response or none per clip, and every call above
+takes ``irs=..., ir_ids=...``.  Not restated: pitch shift (``torch_audiomentations``' PitchShift); ``gain`` is the reference's Gain step,
+``level`` its volume step (:246-255).
 """
 from __future__ import annotations
 
@@ -119,24 +121,140 @@ def draw_mix_items(rng: np.random.Generator, arena: ClipArena, fg_ids, bg_ids, N
     return mix_items(arena, fg, bg, N, snr_db=snr_db, gain_db=gain_db, level=level, start=start, bg_start=bg_start, fg_crop=fg_crop)
 
 
+# ---- room impulse responses (nww_rir_* / nww_mix_rir_*)
+RIR_FFT_SIZES = (2048, 8192, 32768)
+
+
+def rir_fft_size(N: int, max_ir_len: int) -> int:
+    """nww_rir_fft_size: the smallest transform size with N + min(L, N) - 1 <= M, or 0 where none fits"""
+    N, L = int(N), int(max_ir_len)
+    if N < 1 or L < 1:
+        return 0
+    need = N + min(L, N) - 1
+    return next((M for M in RIR_FFT_SIZES if need <= M), 0)
+
+
+class IrArena:
+    """Impulse responses for clips of N samples: float32 responses back to back (``offsets`` / ``lengths``, ``n`` of them), normalised
+    on the host in float64 - ``"energy"``: sum h^2 = 1, ``"peak"``: max |h| = 1, None: as given (under peak normalisation of the clip the
+    response's scale cancels) - and ``M``, the transform size that holds the longest.  With a device (the default, 0) the responses are
+    uploaded ONCE and their spectra prepared ONCE, by the first model that uses the arena (``prepare(model)``); ``spectra_ptr`` is their
+    device address.  ``device=None`` keeps the host side only."""
+
+    def __init__(self, irs: Sequence[np.ndarray], N: int, device: Optional[int] = 0, normalize: Optional[str] = None, M: Optional[int] = None):
+        """``M``: a transform size larger than the smallest that fits (the default), for a caller that wants one size for several arenas"""
+        if normalize not in (None, "energy", "peak"):
+            raise ValueError('normalize must be None, "energy" or "peak"')
+        self.N = int(N)
+        arrs = []
+        for i, h in enumerate(irs):
+            h = np.asarray(h)
+            if h.ndim != 1 or h.size == 0 or h.dtype.kind != "f" or not np.isfinite(h).all():
+                raise ValueError(f"response {i} must be a non-empty one-dimensional finite floating-point array")
+            h64 = h.astype(np.float64)
+            if normalize is not None:
+                norm = float(np.sqrt((h64 * h64).sum())) if normalize == "energy" else float(np.abs(h64).max())
+                if norm == 0.0:
+                    raise ValueError(f"response {i} is all zeros and cannot be normalised")
+                h64 = h64 / norm
+            if rir_fft_size(self.N, h.size) == 0:
+                raise ValueError(f"response {i}: {h.size} taps against clips of {self.N} samples need more than 32768 points: "
+                                 "overlap-save not built")
+            arrs.append(h64.astype(np.float32))
+        if not arrs:
+            raise ValueError("an IrArena needs at least one response")
+        self.lengths = np.array([a.size for a in arrs], np.int32)
+        self.offsets = np.concatenate(([0], np.cumsum(self.lengths.astype(np.int64))[:-1])).astype(np.int64)
+        self.n = len(arrs)
+        self.M = rir_fft_size(self.N, int(self.lengths.max()))
+        if M is not None:
+            if int(M) not in RIR_FFT_SIZES or int(M) < self.M:
+                raise ValueError(f"M must be one of {RIR_FFT_SIZES} and at least {self.M} for these responses")
+            self.M = int(M)
+        self.device = device
+        self.host = np.concatenate(arrs)
+        self._irs = self._spectra = None
+
+    def __len__(self) -> int:
+        return self.n
+
+    def prepare(self, model) -> "IrArena":
+        """upload and nww_rir_prepare_dev through `model` (a HipModel), once"""
+        if self._spectra is None:
+            if self.device is None:
+                raise ValueError("an IrArena with device=None holds the host side only")
+            import torch
+            dev = f"cuda:{int(self.device)}"
+            self._irs = torch.from_numpy(self.host).to(dev)
+            spectra = torch.empty((self.n, self.M), dtype=torch.float32, device=dev)
+            model.rir_prepare_dev(self._irs.data_ptr(), self.offsets, self.lengths, self.N, self.M, spectra.data_ptr())
+            self._spectra = spectra
+        return self
+
+    @property
+    def spectra_ptr(self) -> int:
+        if self._spectra is None:
+            raise ValueError("the spectra are prepared by the first model that uses the arena: call prepare(model)")
+        return int(self._spectra.data_ptr())
+
+
+# struct nww_rir_item (include/nww.h): 8 bytes
+RIR_ITEM = np.dtype([("ir_id", "<i4"), ("reserved", "<u4")])
+
+
+def as_rir_items(ir_ids, B: int) -> np.ndarray:
+    """a contiguous RIR_ITEM table of B rows from response ids (-1: none) or a RIR_ITEM table"""
+    if isinstance(ir_ids, np.ndarray) and ir_ids.dtype == RIR_ITEM:
+        t = np.ascontiguousarray(ir_ids)
+    else:
+        ids = np.asarray(ir_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("ir_ids must be a one-dimensional integer array (draw_rir_ids builds it) or a table of augment.RIR_ITEM")
+        if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+            raise ValueError("ir_ids out of the int32 range")
+        t = np.zeros(ids.size, RIR_ITEM)
+        t["ir_id"] = ids
+    if t.ndim != 1 or len(t) != B:
+        raise ValueError(f"ir_ids must have one entry per item ({B}), got {t.shape}")
+    return t
+
+
+def draw_rir_ids(rng: np.random.Generator, n_irs: int, B: int, rir_prob: float = 0.5) -> np.ndarray:
+    """What ApplyImpulseResponse(p=rir_prob) draws for B clips (augment_clips.py:150-157, rir_prob = 0.5): with that probability one of
+    n_irs responses, uniformly, otherwise -1 (none) -> int32 [B].  The stream of random numbers is this function's own."""
+    B = int(B)
+    if int(n_irs) < 1:
+        return np.full(B, -1, np.int32)
+    on = rng.random(B) < float(rir_prob)
+    return np.where(on, rng.integers(0, int(n_irs), B), -1).astype(np.int32)
+
+
 class MixedClips:
     """The extractor generate_features runs over the tables of mixed_feature_batches: ``embed_clips(items)`` is
-    ``features.embed_mixed(arena, items, N)`` - the mixed clips never exist on the host."""
+    ``features.embed_mixed(arena, items, N)`` - the mixed clips never exist on the host.  With ``irs`` (an IrArena) the batches are
+    (items, ir_ids) pairs, as mixed_feature_batches yields them when it is given ir_ids."""
 
-    def __init__(self, features, arena: ClipArena, N: int):
-        self.features, self.arena, self.N = features, arena, int(N)
+    def __init__(self, features, arena: ClipArena, N: int, irs: Optional[IrArena] = None):
+        self.features, self.arena, self.N, self.irs = features, arena, int(N), irs
 
     def get_embedding_shape(self, audio_length_sec: float, sr: int = 16000):
         return self.features.get_embedding_shape(audio_length_sec, sr)
 
-    def embed_clips(self, x: np.ndarray, batch_size: int = 128, ncpu: int = 1) -> np.ndarray:
-        return self.features.embed_mixed(self.arena, x, self.N)
+    def embed_clips(self, x, batch_size: int = 128, ncpu: int = 1) -> np.ndarray:
+        if self.irs is None:
+            return self.features.embed_mixed(self.arena, x, self.N)
+        items, ir_ids = x
+        return self.features.embed_mixed(self.arena, items, self.N, irs=self.irs, ir_ids=ir_ids)
 
 
-def mixed_feature_batches(items: np.ndarray, batch_size: int = 4096) -> Iterator[np.ndarray]:
+def mixed_feature_batches(items: np.ndarray, batch_size: int = 4096, irs: Optional[IrArena] = None, ir_ids=None) -> Iterator:
     """`items` in tables of batch_size rows: what features.generate_features takes as its audio_batches when its extractor is a
-    MixedClips - ``generate_features(mixed_feature_batches(items), len(items), path, MixedClips(feats, arena, N), N / 16000)``."""
+    MixedClips - ``generate_features(mixed_feature_batches(items), len(items), path, MixedClips(feats, arena, N), N / 16000)``.
+    With ``irs`` and ``ir_ids`` (one id per item) every batch is an (items, ir_ids) pair for ``MixedClips(..., irs=irs)``."""
     items = as_items(items)
+    if (irs is None) != (ir_ids is None):
+        raise ValueError("irs and ir_ids go together")
+    rt = None if ir_ids is None else as_rir_items(ir_ids, len(items))
     step = max(int(batch_size), 1)
     for i in range(0, len(items), step):
-        yield items[i:i + step]
+        yield items[i:i + step] if rt is None else (items[i:i + step], rt[i:i + step])

@@ -2,16 +2,25 @@
 // the table goes up through the next of MIX_TAB_SLOTS = POOL_TAB_SLOTS slots of the handle's own pinned and device buffers - a slot is
 // rewritten once the event behind its previous call has passed, as the pool tables' are (nww_stream.hip) - and mix.hip gathers, measures
 // and mixes.  The forward and frontend forms mix into the handle's PCM staging and run the existing paths on it.
+// nww_rir_* / nww_mix_rir_* (DESIGN.md 4.8h): the same calls with a second table naming a room impulse response per clip - it rides in
+// the same slot - and rir.hip in mix.hip's place; response spectra are prepared once by nww_rir_prepare_dev (rir_plan.h).
 #include "nww_internal.h"
 #include "mix.h"
 #include "mix_plan.h"
+#include "rir.h"
+#include "rir_plan.h"
+
+// a slot holds a call's nww_mix_item table and, right behind its B items, the nww_rir_item table of a call that has one: ONE copy
+constexpr size_t MIX_SLOT_ITEM_BYTES = sizeof(nww_mix_item) + sizeof(nww_rir_item);
 
 struct MixState {
-    nww_mix_item* d_tab = nullptr; nww_mix_item* pin_tab = nullptr;    // [POOL_TAB_SLOTS][slot_items]
+    unsigned char* d_tab = nullptr; unsigned char* pin_tab = nullptr;  // [POOL_TAB_SLOTS][slot_items * MIX_SLOT_ITEM_BYTES]
     hipEvent_t ev[POOL_TAB_SLOTS] = {};
     size_t slot_items = 0; unsigned seq = 0;
     // the host-pointer entry point's arena and clips, grown on demand
     int16_t* d_arena = nullptr; int16_t* d_out = nullptr; size_t arena_bytes = 0, out_bytes = 0;
+    // impulse responses (rir.hip): the twiddle table of each transform size, made by the first call that needs it
+    float* d_tw[3] = {nullptr, nullptr, nullptr};
 };
 
 void nww_mix_free(nww_handle* h) {
@@ -22,6 +31,7 @@ void nww_mix_free(nww_handle* h) {
     for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
     if (m->d_arena) (void)hipFree(m->d_arena);
     if (m->d_out) (void)hipFree(m->d_out);
+    for (float* t : m->d_tw) if (t) (void)hipFree(t);
     delete m;
     h->mix = nullptr;
 }
@@ -37,9 +47,27 @@ static int mix_slots(nww_handle* h, size_t B) {
     if (m->pin_tab) (void)hipHostFree(m->pin_tab);
     m->d_tab = nullptr; m->pin_tab = nullptr; m->slot_items = 0; m->seq = 0;
     const size_t items = (B + 255) & ~(size_t)255;
-    HIP_TRY(h, hipMalloc(&m->d_tab, POOL_TAB_SLOTS * items * sizeof(nww_mix_item)));
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&m->pin_tab), POOL_TAB_SLOTS * items * sizeof(nww_mix_item), hipHostMallocDefault));
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&m->d_tab), POOL_TAB_SLOTS * items * MIX_SLOT_ITEM_BYTES));
+    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&m->pin_tab), POOL_TAB_SLOTS * items * MIX_SLOT_ITEM_BYTES, hipHostMallocDefault));
     m->slot_items = items;
+    return NWW_OK;
+}
+
+// the twiddle table of transform size M on the device (rir_plan.h: float64, rounded once), made on first use
+static int rir_twiddles(nww_handle* h, int M, const float** d_tw) {
+    if (!h->mix) h->mix = new MixState();
+    MixState* m = h->mix;
+    const int k = M == 2048 ? 0 : M == 8192 ? 1 : 2;
+    if (!m->d_tw[k]) {
+        std::vector<RirC> T((size_t)rir_twiddle_count(M));
+        rir_twiddles_host(M, T.data());
+        float* d = nullptr;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d), T.size() * sizeof(RirC)));
+        const hipError_t e = hipMemcpy(d, T.data(), T.size() * sizeof(RirC), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(h, NWW_ERR_HIP, "twiddle upload failed: %s", hipGetErrorString(e)); }
+        m->d_tw[k] = d;
+    }
+    *d_tw = m->d_tw[k];
     return NWW_OK;
 }
 
@@ -60,21 +88,32 @@ static int mix_check(nww_handle* h, const void* d_arena, int64_t arena_samples, 
     return NWW_OK;
 }
 
-// the validated table through the next slot, then the kernel, on s
-static int mix_enqueue(nww_handle* h, const int16_t* d_arena, const nww_mix_item* items, int B, int N, int16_t* d_out, hipStream_t s) {
+// the validated tables through the next slot, then the kernel, on s.  rir_items == null: mix.hip; otherwise rir.hip at M.
+static int mix_enqueue(nww_handle* h, const int16_t* d_arena, const nww_mix_item* items, int B, int N, int16_t* d_out, hipStream_t s,
+                       const nww_rir_item* rir_items = nullptr, const float* d_spectra = nullptr, int M = 0) {
     int rc = mix_slots(h, (size_t)B);
     if (rc) return rc;
     MixState* m = h->mix;
+    const float* d_tw = nullptr;
+    if (rir_items) {
+        rc = rir_twiddles(h, M, &d_tw);
+        if (rc) return rc;
+    }
     const unsigned slot = m->seq % POOL_TAB_SLOTS;
     if (m->seq >= POOL_TAB_SLOTS) HIP_TRY(h, hipEventSynchronize(m->ev[slot]));      // the slot's previous call has passed
     ++m->seq;
-    nww_mix_item* pin = m->pin_tab + slot * m->slot_items;
-    nww_mix_item* dev = m->d_tab + slot * m->slot_items;
-    std::memcpy(pin, items, (size_t)B * sizeof(nww_mix_item));
-    HIP_TRY(h, hipMemcpyAsync(dev, pin, (size_t)B * sizeof(nww_mix_item), hipMemcpyHostToDevice, s));
-    const hipError_t e = mix_launch(d_arena, dev, B, N, d_out, h->cu_count, s);
+    unsigned char* pin = m->pin_tab + slot * m->slot_items * MIX_SLOT_ITEM_BYTES;
+    unsigned char* dev = m->d_tab + slot * m->slot_items * MIX_SLOT_ITEM_BYTES;
+    const size_t tab_bytes = (size_t)B * sizeof(nww_mix_item), rtab_bytes = rir_items ? (size_t)B * sizeof(nww_rir_item) : 0;
+    std::memcpy(pin, items, tab_bytes);
+    if (rir_items) std::memcpy(pin + tab_bytes, rir_items, rtab_bytes);
+    HIP_TRY(h, hipMemcpyAsync(dev, pin, tab_bytes + rtab_bytes, hipMemcpyHostToDevice, s));
+    const nww_mix_item* d_items = reinterpret_cast<const nww_mix_item*>(dev);
+    const hipError_t e = rir_items ? rir_mix_launch(d_arena, d_items, reinterpret_cast<const nww_rir_item*>(dev + tab_bytes), d_spectra, M, d_tw, B, N,
+                                                    d_out, s)
+                                   : mix_launch(d_arena, d_items, B, N, d_out, h->cu_count, s);
     (void)hipEventRecord(m->ev[slot], s);
-    if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'mix' failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch '%s' failed: %s", rir_items ? "mix_rir" : "mix", hipGetErrorString(e));
     return NWW_OK;
 }
 
@@ -142,6 +181,142 @@ extern "C" int nww_mix_frontend_dev(nww_handle* h, const int16_t* d_arena, int64
     if (rc) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
     rc = mix_enqueue(h, d_arena, items, B, N, h->d_pcm, s);
+    if (rc) return rc;
+    return nww_frontend_on_dev(h, h->d_pcm, B, N, d_logmel, nullptr, frames_major, s, nullptr);
+}
+
+// ---- ... through a room impulse response (rir.hip, rir_plan.h)
+extern "C" int32_t nww_rir_fft_size(int32_t N, int32_t max_ir_len) { return rir_fft_size(N, max_ir_len); }
+
+extern "C" int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int64_t* ir_off, const int32_t* ir_len, int32_t K, int32_t N, int32_t M,
+                                   float* d_spectra, void* stream) {
+    if (!h) return NWW_ERR_INVALID;
+    if (!h->finalized) return fail(h, NWW_ERR_STATE, "model not finalized: call nww_finalize after loading the state_dict");
+    if (K < 0) return fail(h, NWW_ERR_INVALID, "the number of responses must not be negative (got %d)", K);
+    if (K == 0) return NWW_OK;
+    if (N < 1) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
+    if (!d_irs || !ir_off || !ir_len || !d_spectra) return fail(h, NWW_ERR_INVALID, "null response buffer, table or spectra");
+    if (!rir_size_fits(M, N)) return fail(h, NWW_ERR_INVALID, "M = %d is not a transform size (2048, 8192, 32768) that holds clips of %d", M, N);
+    const char* why = "";
+    const int64_t bad = rir_first_bad_response(ir_len, K, N, M, &why);
+    if (bad >= 0) {
+        if (why[0] == 'o')
+            return fail(h, NWW_ERR_INVALID, "response %lld: %d taps against clips of %d need more than 32768 points: overlap-save not built",
+                        (long long)bad, ir_len[bad], N);
+        if (why[0] == 'M') return fail(h, NWW_ERR_INVALID, "response %lld: %d taps against clips of %d do not fit M = %d", (long long)bad, ir_len[bad], N, M);
+        return fail(h, NWW_ERR_INVALID, "response %lld: ir_len out of range (got %d)", (long long)bad, ir_len[bad]);
+    }
+    for (int32_t k = 0; k < K; ++k)
+        if (ir_off[k] < 0) return fail(h, NWW_ERR_INVALID, "response %d: ir_off out of range", k);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const float* d_tw = nullptr;
+    int rc = rir_twiddles(h, M, &d_tw);
+    if (rc) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
+    unsigned char* d_tab = nullptr;                                    // [K] offsets, then [K] lengths: freed once the stream has passed
+    const size_t off_bytes = (size_t)K * sizeof(int64_t), len_bytes = (size_t)K * sizeof(int32_t);
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_tab), off_bytes + len_bytes));
+    hipError_t e = hipMemcpyAsync(d_tab, ir_off, off_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab + off_bytes, ir_len, len_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = rir_prepare_launch(d_irs, reinterpret_cast<const int64_t*>(d_tab), reinterpret_cast<const int32_t*>(d_tab + off_bytes), K, N, M, d_tw,
+                               d_spectra, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(d_tab);
+    if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'rir_prepare' failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, NWW_ERR_HIP, "rir_prepare failed: %s", hipGetErrorString(e2));
+    return NWW_OK;
+}
+
+// what the rir calls check behind mix_check, before anything is enqueued (rir_items != null)
+static int rir_check(nww_handle* h, const float* d_spectra, int32_t n_irs, int32_t M, const nww_rir_item* rir_items, int32_t B, int32_t N) {
+    if (n_irs < 0) return fail(h, NWW_ERR_INVALID, "n_irs must not be negative (got %d)", n_irs);
+    if (n_irs > 0 && !d_spectra) return fail(h, NWW_ERR_INVALID, "null spectra");
+    if (!rir_size_fits(M, N)) return fail(h, NWW_ERR_INVALID, "M = %d is not a transform size (2048, 8192, 32768) that holds clips of %d", M, N);
+    const char* field = nullptr;
+    const int64_t bad = rir_first_bad_item(rir_items, B, n_irs, &field);
+    if (bad >= 0) return fail(h, NWW_ERR_INVALID, "rir item %lld: %s out of range (%d responses)", (long long)bad, field, n_irs);
+    return NWW_OK;
+}
+
+extern "C" int nww_mix_rir_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                               const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, int16_t* d_out, void* stream) {
+    if (!rir_items) return nww_mix_dev(h, d_arena, arena_samples, items, B, N, d_out, stream);
+    bool done = false;
+    int rc = mix_check(h, d_arena, arena_samples, items, B, N, &done);
+    if (rc || done) return rc;
+    rc = rir_check(h, d_spectra, n_irs, M, rir_items, B, N);
+    if (rc) return rc;
+    if (!d_out) return fail(h, NWW_ERR_INVALID, "null device pointer");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return mix_enqueue(h, d_arena, items, B, N, d_out, stream ? (hipStream_t)stream : h->own_stream, rir_items, d_spectra, M);
+}
+
+extern "C" int nww_mix_rir(nww_handle* h, const int16_t* arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                           const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, int16_t* out) {
+    if (!rir_items) return nww_mix(h, arena, arena_samples, items, B, N, out);
+    bool done = false;
+    int rc = mix_check(h, arena, arena_samples, items, B, N, &done);
+    if (rc || done) return rc;
+    rc = rir_check(h, d_spectra, n_irs, M, rir_items, B, N);
+    if (rc) return rc;
+    if (!out) return fail(h, NWW_ERR_INVALID, "null output pointer");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    rc = mix_slots(h, (size_t)B);
+    if (rc) return rc;
+    MixState* m = h->mix;
+    const size_t ab = (size_t)arena_samples * sizeof(int16_t), ob = (size_t)B * N * sizeof(int16_t);
+    rc = nww_grow(h, reinterpret_cast<void**>(&m->d_arena), &m->arena_bytes, ab);
+    if (!rc) rc = nww_grow(h, reinterpret_cast<void**>(&m->d_out), &m->out_bytes, ob);
+    if (rc) return rc;
+    hipStream_t s = h->own_stream;
+    HIP_TRY(h, hipMemcpyAsync(m->d_arena, arena, ab, hipMemcpyHostToDevice, s));
+    rc = mix_enqueue(h, m->d_arena, items, B, N, m->d_out, s, rir_items, d_spectra, M);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, m->d_out, ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return NWW_OK;
+}
+
+extern "C" int nww_mix_rir_forward_pcm_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                                           const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, float* d_logits,
+                                           float* d_probs, void* stream) {
+    if (!rir_items) return nww_mix_forward_pcm_dev(h, d_arena, arena_samples, items, B, N, d_logits, d_probs, stream);
+    bool done = false;
+    int rc = mix_check(h, d_arena, arena_samples, items, B, N, &done);
+    if (rc || done) return rc;
+    rc = rir_check(h, d_spectra, n_irs, M, rir_items, B, N);
+    if (rc) return rc;
+    const ClipRows cr = nww_clip_rows(h, N);
+    if (cr.T <= 0) return nww_fail_short_clip(h, N);
+    if (!cr.fits)
+        return fail(h, NWW_ERR_SHAPE, "frontend yields (%d,%d) features for %d samples but the head was built for input_shape=(%d,%d)", cr.rows,
+                    cr.cols, N, h->cfg.in_rows, h->cfg.in_cols);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    rc = nww_ensure_ws(h, B, N);
+    if (rc) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
+    rc = mix_enqueue(h, d_arena, items, B, N, h->d_pcm, s, rir_items, d_spectra, M);
+    if (rc) return rc;
+    return nww_forward_pcm_on_dev(h, h->d_pcm, B, N, d_logits, d_probs, s);
+}
+
+extern "C" int nww_mix_rir_frontend_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                                        const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, float* d_logmel,
+                                        int32_t frames_major, void* stream) {
+    if (!rir_items) return nww_mix_frontend_dev(h, d_arena, arena_samples, items, B, N, d_logmel, frames_major, stream);
+    bool done = false;
+    int rc = mix_check(h, d_arena, arena_samples, items, B, N, &done);
+    if (rc || done) return rc;
+    rc = rir_check(h, d_spectra, n_irs, M, rir_items, B, N);
+    if (rc) return rc;
+    if (!d_logmel) return fail(h, NWW_ERR_INVALID, "null device pointer");
+    if (nww_pcm_rows(h, N) <= 0) return nww_fail_short_clip(h, N);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    rc = nww_ensure_ws(h, B, N);
+    if (rc) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
+    rc = mix_enqueue(h, d_arena, items, B, N, h->d_pcm, s, rir_items, d_spectra, M);
     if (rc) return rc;
     return nww_frontend_on_dev(h, h->d_pcm, B, N, d_logmel, nullptr, frames_major, s, nullptr);
 }

@@ -1,0 +1,16 @@
+// rir.h - launchers of rir.hip: response spectra prepared once, and B clips mixed out of an int16 arena and convolved with them
+// (include/nww.h, nww_rir_* / nww_mix_rir_*)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "../../include/nww.h"
+
+// M must be one of rir_plan.h's sizes, d_tw its twiddle table (rir_twiddles_host), and the tables validated on the host: the kernels
+// check nothing.
+// K responses at d_irs + d_off[k] of d_len[k] taps (the first min(len, N) are read) -> d_spectra [K][M / 2] complex
+hipError_t rir_prepare_launch(const float* d_irs, const int64_t* d_off, const int32_t* d_len, int K, int N, int M, const float* d_tw,
+                              float* d_spectra, hipStream_t stream);
+// d_rtab [B]: a clip's response (-1: none, the clip mix.hip gives)
+hipError_t rir_mix_launch(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra, int M,
+                          const float* d_tw, int B, int N, int16_t* d_out, hipStream_t stream);

@@ -352,56 +352,108 @@ class HipModel:
                                                       C.c_void_p(stream) if stream else None))
 
     # ------------------------------------------------------------------ clips mixed on the device (nww_mix_*, augment.py)
-    def mix_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, stream: int = 0):
-        """Raw device pointers; `items` is a host table of augment.MIX_ITEM.  int16 out [B, N]; enqueues on `stream`, does not synchronise."""
+    def rir_prepare_dev(self, irs_ptr: int, ir_off, ir_len, N: int, M: int, spectra_ptr: int, stream: int = 0):
+        """nww_rir_prepare_dev: float32 responses back to back at irs_ptr (host tables ir_off int64 / ir_len int32, samples) -> their
+        spectra float32 [K, M] at spectra_ptr, for clips of N samples at transform size M.  Synchronises `stream`."""
+        off, ln = np.ascontiguousarray(ir_off, np.int64), np.ascontiguousarray(ir_len, np.int32)
+        if off.ndim != 1 or off.shape != ln.shape:
+            raise ValueError("ir_off and ir_len must be one-dimensional and of one length")
+        self._check(self.lib.nww_rir_prepare_dev(self._h, C.c_void_p(irs_ptr), off.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), len(off),
+                                                 int(N), int(M), C.c_void_p(spectra_ptr), C.c_void_p(stream) if stream else None))
+
+    def _rir_args(self, irs, ir_ids, B: int, N: int):
+        """(spectra pointer, n_irs, M, the RIR_ITEM table) of a call's irs / ir_ids, or None without them (augment.IrArena, prepared here)"""
+        if irs is None and ir_ids is None:
+            return None
+        if irs is None or ir_ids is None:
+            raise ValueError("irs (an augment.IrArena) and ir_ids (one response id per item, -1: none) go together")
+        from .augment import as_rir_items
+        if int(N) != irs.N:
+            raise ValueError(f"the IrArena was prepared for clips of {irs.N} samples, not {int(N)}")
+        rt = as_rir_items(ir_ids, B)
+        irs.prepare(self)
+        return C.c_void_p(irs.spectra_ptr), irs.n, irs.M, rt
+
+    def mix_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, stream: int = 0, irs=None, ir_ids=None):
+        """Raw device pointers; `items` is a host table of augment.MIX_ITEM.  int16 out [B, N]; enqueues on `stream`, does not synchronise.
+        With `irs` (an augment.IrArena) and `ir_ids` every clip with an id >= 0 is convolved with that response (nww_mix_rir_dev)."""
         from .augment import as_items
         items = as_items(items)
-        self._check(self.lib.nww_mix_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items), int(N),
-                                         C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+        st = C.c_void_p(stream) if stream else None
+        rir = self._rir_args(irs, ir_ids, len(items), N)
+        if rir is None:
+            self._check(self.lib.nww_mix_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items), int(N),
+                                             C.c_void_p(out_ptr), st))
+        else:
+            self._check(self.lib.nww_mix_rir_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), rir[0], rir[1], rir[2],
+                                                 items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), len(items), int(N),
+                                                 C.c_void_p(out_ptr), st))
 
-    def forward_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0):
+    def forward_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0, irs=None,
+                          ir_ids=None):
         """mix_dev into the handle's PCM staging, then forward_pcm_dev's path on it; does not synchronise."""
         from .augment import as_items
         items = as_items(items)
-        self._check(self.lib.nww_mix_forward_pcm_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
-                                                     int(N), C.c_void_p(logits_ptr), C.c_void_p(probs_ptr) if probs_ptr else None,
-                                                     C.c_void_p(stream) if stream else None))
+        st, pp = C.c_void_p(stream) if stream else None, C.c_void_p(probs_ptr) if probs_ptr else None
+        rir = self._rir_args(irs, ir_ids, len(items), N)
+        if rir is None:
+            self._check(self.lib.nww_mix_forward_pcm_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
+                                                         int(N), C.c_void_p(logits_ptr), pp, st))
+        else:
+            self._check(self.lib.nww_mix_rir_forward_pcm_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), rir[0], rir[1], rir[2],
+                                                             items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), len(items), int(N),
+                                                             C.c_void_p(logits_ptr), pp, st))
 
-    def frontend_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, frames_major: bool = False, stream: int = 0):
+    def frontend_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, frames_major: bool = False, stream: int = 0,
+                           irs=None, ir_ids=None):
         """mix_dev into the handle's PCM staging, then frontend_dev's path on it; does not synchronise."""
         from .augment import as_items
         items = as_items(items)
-        self._check(self.lib.nww_mix_frontend_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
-                                                  int(N), C.c_void_p(out_ptr), int(frames_major), C.c_void_p(stream) if stream else None))
+        st = C.c_void_p(stream) if stream else None
+        rir = self._rir_args(irs, ir_ids, len(items), N)
+        if rir is None:
+            self._check(self.lib.nww_mix_frontend_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
+                                                      int(N), C.c_void_p(out_ptr), int(frames_major), st))
+        else:
+            self._check(self.lib.nww_mix_rir_frontend_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), rir[0], rir[1], rir[2],
+                                                          items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), len(items), int(N),
+                                                          C.c_void_p(out_ptr), int(frames_major), st))
 
-    def mix(self, arena, items, N: int) -> np.ndarray:
+    def mix(self, arena, items, N: int, irs=None, ir_ids=None) -> np.ndarray:
         """The clips of `items` (augment.mix_items / draw_mix_items) mixed out of `arena` -> int16 [B, N].  A device-resident
-        augment.ClipArena is read where it lies; a host arena (ClipArena(device=None) or an int16 array) is uploaded by the call."""
+        augment.ClipArena is read where it lies; a host arena (ClipArena(device=None) or an int16 array) is uploaded by the call.
+        `irs` (an augment.IrArena) and `ir_ids` (augment.draw_rir_ids; -1: none) send clips through impulse responses."""
         from .augment import as_items
         items = as_items(items)
         B, N = len(items), int(N)
+        rir = self._rir_args(irs, ir_ids, B, N)
         host = arena if isinstance(arena, np.ndarray) else arena.host
         if host is not None:
             if host.dtype != np.int16 or host.ndim != 1:
                 raise ValueError("a host arena must be a one-dimensional int16 array")
             host = np.ascontiguousarray(host)
             out = np.empty((B, max(N, 0)), np.int16)
-            self._check(self.lib.nww_mix(self._h, host.ctypes.data_as(C.c_void_p), host.size, items.ctypes.data_as(C.c_void_p), B, N,
-                                         out.ctypes.data_as(C.c_void_p)))
+            if rir is None:
+                self._check(self.lib.nww_mix(self._h, host.ctypes.data_as(C.c_void_p), host.size, items.ctypes.data_as(C.c_void_p), B, N,
+                                             out.ctypes.data_as(C.c_void_p)))
+            else:
+                self._check(self.lib.nww_mix_rir(self._h, host.ctypes.data_as(C.c_void_p), host.size, rir[0], rir[1], rir[2],
+                                                 items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), B, N,
+                                                 out.ctypes.data_as(C.c_void_p)))
             return out
         import torch
         out = torch.empty((B, max(N, 0)), dtype=torch.int16, device=f"cuda:{self.device}")
-        self.mix_dev(arena.ptr, arena.samples, items, N, out.data_ptr())
+        self.mix_dev(arena.ptr, arena.samples, items, N, out.data_ptr(), irs=irs, ir_ids=ir_ids)
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy()
 
-    def forward_mixed(self, arena, items, N: int):
+    def forward_mixed(self, arena, items, N: int, irs=None, ir_ids=None):
         """(logits [B], probs [B]) of the clips mix() gives, bit-identical to forward_pcm(mix(arena, items, N)); the clips stay on the device."""
         import torch
         from .augment import as_items
         items = as_items(items)
         out = torch.zeros((2, len(items)), dtype=torch.float32, device=f"cuda:{self.device}")
-        self.forward_mixed_dev(arena.ptr, arena.samples, items, N, out[0].data_ptr(), out[1].data_ptr())
+        self.forward_mixed_dev(arena.ptr, arena.samples, items, N, out[0].data_ptr(), out[1].data_ptr(), irs=irs, ir_ids=ir_ids)
         torch.cuda.synchronize(self.device)
         res = out.cpu().numpy()
         return res[0].copy(), res[1].copy()
@@ -1097,15 +1149,15 @@ class HipSession:
         return logits.reshape(-1, 1)
 
     # clips mixed on the device out of an augment.ClipArena (HipModel.mix / forward_mixed): clips of clip_samples
-    def mix(self, arena, items) -> np.ndarray:
-        """int16 [B, clip_samples]: the clips of `items` mixed out of `arena`"""
-        return self.model.mix(arena, items, self.clip_samples)
+    def mix(self, arena, items, irs=None, ir_ids=None) -> np.ndarray:
+        """int16 [B, clip_samples]: the clips of `items` mixed out of `arena` (irs / ir_ids: through impulse responses, HipModel.mix)"""
+        return self.model.mix(arena, items, self.clip_samples, irs=irs, ir_ids=ir_ids)
 
-    def forward_mixed(self, arena, items):
+    def forward_mixed(self, arena, items, irs=None, ir_ids=None):
         """[probabilities (B,1,1)] as run() returns them for mix(arena, items), the clips never leaving the device"""
         if self.mode != "e2e":
             raise ValueError("forward_mixed needs an e2e session (raw PCM in)")
-        return [self.model.forward_mixed(arena, items, self.clip_samples)[1].reshape(-1, 1, 1)]
+        return [self.model.forward_mixed(arena, items, self.clip_samples, irs=irs, ir_ids=ir_ids)[1].reshape(-1, 1, 1)]
 
     # a pool of streams on the session's model (interpreter.StreamPool takes a session as its backend): windows of clip_samples
     def stream_open(self, n_streams: int, window_samples: Optional[int] = None, hop_samples: int = 1280):

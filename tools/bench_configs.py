@@ -16,7 +16,9 @@ models against the lock-step cascade (cascade_pool_main) -> profiles/cascade_poo
 --bank [out]: several heads as one bank call (nww_bank_*: one frontend pass) against the same handles called one after the other, on
 batches, a stream pool and a recording (bank_main) -> profiles/bank_bench_configs.jsonl.
 --mix [out]: clips mixed on the device (nww_mix_*) alone and in front of the CNN head, against uploading the pre-mixed batch and against
-the same chain in torch ops (mix_main) -> profiles/mix_bench_configs.jsonl."""
+the same chain in torch ops (mix_main) -> profiles/mix_bench_configs.jsonl.
+--mix-rir [out]: the same clips through room impulse responses (nww_mix_rir_*) alone and in front of the CNN head, against the calls
+without responses and against torch.fft.rfft / irfft plus the tail on the same card (mix_rir_main) -> profiles/mix_rir_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -1157,7 +1159,114 @@ def mix_main(out_path):
     sys.stdout.write(text)
 
 
+def mix_rir_child():
+    """One process: mix_child's arena and table, every clip with a response drawn from 64 of 0.25 - 1 s (exponentially decaying noise,
+    energy-normalised), M = 32768.  ms per call as the median of RNN_STEPS device-event timings behind RNN_WARMUP warm-up calls, every leg
+    on one stream: (a) mix_dev with responses alone, (b) forward_mixed_dev with them, (r) forward_mixed_dev without - the parent's
+    number -, (d) the reference's route in torch ops on the same card: rfft / irfft at n = N + L_max - 1 on a resident float32 batch of
+    the same shape against the 64 responses' spectra (prepared once, as ours are, and gathered per clip), cut to N, then the peak /
+    level / clamp / int16 tail."""
+    import torch
+    from nanowakeword_amd.augment import ClipArena, IrArena, draw_mix_items, draw_rir_ids
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    cfg = HeadConfig("cnn", (101, 64))
+    m = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+    rng = np.random.default_rng(7)
+    fg_len = rng.integers(MIX_N // 2, MIX_N + 1, 64)
+    bg_len = rng.integers(MIX_N, 10 * MIX_N + 1, 16)
+    clips = [synth_pcm("speechlike", 1, int(n), seed=100 + k)[0] for k, n in enumerate(fg_len)] + \
+            [synth_pcm("noise", 1, int(n), seed=200 + k)[0] for k, n in enumerate(bg_len)]
+    arena = ClipArena(clips, device=0)
+    items = draw_mix_items(rng, arena, rng.integers(0, 64, MIX_B), 64 + np.arange(16), MIX_N)
+    ir_len = rng.integers(MIX_N // 4, MIX_N + 1, 64)
+    responses = [(rng.standard_normal(int(L)) * np.exp(-6.0 * np.arange(int(L)) / int(L))).astype(np.float32) for L in ir_len]
+    irs = IrArena(responses, MIX_N, device=0, normalize="energy").prepare(m)
+    ids = draw_rir_ids(rng, 64, MIX_B, 1.0)
+    B, N = MIX_B, MIX_N
+    ts = torch.cuda.Stream(dev)
+    stream = ts.cuda_stream
+    m.reserve(B, N)
+    pcm = torch.empty((B, N), dtype=torch.int16, device=dev)
+    lg, pr = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(2))
+    # (d)'s inputs, resident: a float32 batch, the responses' spectra at n, the ids and levels
+    m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream)
+    torch.cuda.synchronize()
+    y = pcm.to(torch.float32) / 32768.0
+    Lmax = int(ir_len.max())
+    n = N + Lmax - 1
+    hp = np.zeros((64, Lmax), np.float32)
+    for k in range(64):
+        hp[k, :irs.lengths[k]] = irs.host[irs.offsets[k]:irs.offsets[k] + irs.lengths[k]]
+    Hs = torch.fft.rfft(torch.from_numpy(hp).to(dev), n=n)
+    tid = torch.from_numpy(ids.astype(np.int64)).to(dev)
+    level = torch.from_numpy(np.ascontiguousarray(items["level"])).to(dev)[:, None]
+
+    def torch_leg():
+        with torch.cuda.stream(ts), torch.no_grad():
+            w = torch.fft.irfft(torch.fft.rfft(y, n=n) * Hs[tid], n=n)[:, :N]
+            pk = w.abs().amax(1, keepdim=True)
+            pk = torch.where(pk < 1e-8, torch.ones_like(pk), pk)
+            return (torch.clamp(w * (level / pk), -1.0, 1.0) * 32767).to(torch.int16)
+    legs = {"mix_rir": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream, irs=irs, ir_ids=ids),
+            "mix_rir_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream, irs=irs, ir_ids=ids),
+            "mix_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream),
+            "mix": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream),
+            "torch_fft": torch_leg}
+    out = {"B": B, "N": N, "M": irs.M, "responses": 64, "ir_len_min": int(ir_len.min()), "ir_len_max": Lmax, "torch_fft_n": n}
+    for name, step in legs.items():
+        for _ in range(RNN_WARMUP):
+            step()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for e0, e1 in ev:
+            e0.record(ts); step(); e1.record(ts)
+        torch.cuda.synchronize()
+        out[name + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+    print(json.dumps(out), flush=True)
+    m.close()
+
+
+def mix_rir_main(out_path):
+    """RNN_REPEATS fresh child processes, one after another, each under its own time limit; the medians of the repeats with their spread
+    (max - min over the repeats).  No claim is asserted: (a) against (d) and (b) against (r) are written down as measured."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--mix-rir-child"], env=dict(os.environ), cwd=ROOT,
+                           stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"mix-rir child exited {r.returncode}")
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][0])
+    names = ("mix_rir", "mix_rir_forward", "mix_forward", "mix", "torch_fft")
+    rep = {k: [r[k + "_ms"] for r in runs] for k in names}
+    med = {k: float(np.median(v)) for k, v in rep.items()}
+    first = runs[0]
+    line = {"config": f"mix-rir B={MIX_B} N={MIX_N}, every clip through one of 64 responses of 0.25-1 s, M={first['M']}, cnn 101x64", "B": MIX_B,
+            "N": MIX_N, "M": first["M"], "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS, "ms_repeats": rep,
+            "spread_ms": {k: round(max(v) - min(v), 4) for k, v in rep.items()},
+            "mix_rir_ms": round(med["mix_rir"], 4), "torch_fft_ms": round(med["torch_fft"], 4), "torch_fft_n": first["torch_fft_n"],
+            "torch_fft_over_mix_rir": round(med["torch_fft"] / med["mix_rir"], 2),
+            "mix_rir_forward_ms": round(med["mix_rir_forward"], 4), "mix_forward_ms": round(med["mix_forward"], 4), "mix_ms": round(med["mix"], 4),
+            "rir_over_mix_forward_ms": round(med["mix_rir_forward"] - med["mix_forward"], 4),
+            "clips_per_s": {k: round(MIX_B / (med[k] * 1e-3)) for k in ("mix_rir", "mix_rir_forward", "mix_forward")}}
+    text = json.dumps(line) + "\n"
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--mix-rir-child" in sys.argv[1:]:
+        return mix_rir_child()
+    if "--mix-rir" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--mix-rir"]
+        return mix_rir_main(rest[0] if rest else os.path.join(ROOT, "profiles", "mix_rir_bench_configs.jsonl"))
     if "--mix-child" in sys.argv[1:]:
         return mix_child()
     if "--mix" in sys.argv[1:]:
