@@ -1114,6 +1114,40 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
     int hh = T / 2, ww = F / 2, cur = 0;
     bool mean_fused = false;
     const int ch[4] = {32, 64, 128, 256};
+    // float32 activations under NWW_ARITH_F16X3: a block's d and xs rows are scaled per pixel in the kernel and its weights per tensor, which
+    // needs no bound - but a channel (or its weight column) far off its neighbours loses bits (f16_pixel_rows_ok, plan_host.h).  ReLU models
+    // were balanced at load time (balance_channel_gains); what is still spread here - GELU / SiLU BatchNorm gains - sends the block to the
+    // three-term bf16 form, unchained.  Per-channel typical magnitudes as in add_trunk (f16_rows_typ), the two branches of a block by hypot
+    bool h2_ok[4] = {false, true, true, true};
+    if (p.h->f16 && !act_bf16) {
+        const std::vector<float> none;
+        const float *pa0 = p.W("model.init_conv.1.alpha"), *pb0 = p.W("model.init_conv.1.beta");
+        const auto hw0 = f16_fetch(p.h, p.W("model.init_conv.0.weight"), 32 * 9);
+        const auto ha0 = f16_fetch(p.h, pa0, 32), hb0 = f16_fetch(p.h, pb0, 32);
+        const F16Rows m0 = f16_rows_moments(32, 9, [&](int q, int co) { return hw0[(size_t)co * 9 + q]; }, [](int) { return 0; }, std::vector<double>(1, F16_FEATURES.typ));
+        std::vector<double> typ_h = f16_rows_typ(m0, none, false, ha0, hb0, pa0 != nullptr);
+        for (int i = 1; i <= 3; ++i) {
+            const std::string q = "model.block" + std::to_string(i);
+            const int ci = ch[i - 1], co = ch[i];
+            const auto dwt = f16_fetch(p.h, p.W(q + ".depthwise.weight_t"), (size_t)9 * ci);      // [9][ci] tap-major
+            std::vector<double> typ_d(ci, 0.0);
+            for (int cc = 0; cc < ci; ++cc) {
+                double l2 = 0;
+                for (int k = 0; k < 9; ++k) l2 += (double)dwt[(size_t)k * ci + cc] * (double)dwt[(size_t)k * ci + cc];
+                typ_d[cc] = std::sqrt(l2) * typ_h[cc];
+            }
+            const float *pa1 = p.W(q + ".bn1.alpha"), *pas = p.W(q + ".shortcut.1.alpha");
+            const auto wpw = f16_fetch(p.h, p.W(q + ".pointwise.weight"), (size_t)co * ci), wsc = f16_fetch(p.h, p.W(q + ".shortcut.0.weight"), (size_t)co * ci);
+            const auto ha1 = f16_fetch(p.h, pa1, co), hb1 = f16_fetch(p.h, p.W(q + ".bn1.beta"), co);
+            const auto has = f16_fetch(p.h, pas, co), hbs = f16_fetch(p.h, p.W(q + ".shortcut.1.beta"), co);
+            const F16Rows mpw = f16_rows_moments(co, ci, [&](int k, int o) { return wpw[(size_t)o * ci + k]; }, [](int k) { return k; }, typ_d);
+            const F16Rows msc = f16_rows_moments(co, ci, [&](int k, int o) { return wsc[(size_t)o * ci + k]; }, [](int k) { return k; }, typ_h);
+            h2_ok[i] = f16_pixel_rows_ok(mpw, typ_d) && f16_pixel_rows_ok(msc, typ_h);
+            const std::vector<double> tpw = f16_rows_typ(mpw, none, false, ha1, hb1, pa1 != nullptr), tsc = f16_rows_typ(msc, none, false, has, hbs, pas != nullptr);
+            typ_h.assign(co, 0.0);
+            for (int o = 0; o < co; ++o) typ_h[o] = std::hypot(tpw[o], tsc[o]);
+        }
+    }
     const int st[3][2] = {{2, 2}, {2, 2}, {2, 1}};
     // d_i / xs_i (depthwise output and strided block input) of the coming block live in buffers dwb / xsb; have_dx: they are
     // already there - written by the fused front kernel or by the previous block's chained kernel (bc_chain.hip)
@@ -1139,8 +1173,8 @@ int plan_bcresnet(PlanCtx& p) {                     // BcResNetModel: architectu
             p.need(outb, (size_t)rows * co);
             // both products from split operands on the bf16 matrix cores (dual_x3.hip) under the same arithmetic switch
             // float32 activations under NWW_ARITH_F16X3: two binary16 terms per operand, the activation rows scaled per pixel in
-            // the kernel (DualArgs::h2) - no tensor bound needed
-            const bool dual_h2 = p.h->f16 && !act_bf16;
+            // the kernel (DualArgs::h2) - no tensor bound needed, the spread of the channels held by h2_ok above
+            const bool dual_h2 = p.h->f16 && !act_bf16 && h2_ok[i];
             // blocks 1 and 2 chained with the next block's depthwise (bc_chain.hip; two-term weights in every storage mode)
             const bool will_chain = nww_knobs().bc_chain && i < 3 && have_dx && bc_chain_supported(ci, ho, wo) &&
                                     (act_f16 || dual_h2 || (act16 == NWW_ACT_DTYPE_BF16 && p.h->f16));

@@ -209,16 +209,61 @@ void nww_build_spec(nww_handle* h) {
 }
 
 // ------------------------------------------------------------------------------------------ weights and frontend tables
-// channel gains balanced at load time (balance_channels, plan_host.h), before the BatchNorms are folded: the conv trunks of the ReLU heads
+// channel gains balanced at load time (balance_channels, plan_host.h), before the BatchNorms are folded: the conv trunks of the ReLU heads, and
+// BcResNet's blocks
 void balance_channel_gains(nww_handle* h) {
     const nww_config& c = h->cfg;
-    if (!(h->f16 && h->conv_products == 6 && c.activation == ACT_RELU)) return;
+    if (!(h->f16 && h->conv_products == 6)) return;
+    if (c.head_type != NWW_HEAD_BCRESNET && c.activation != ACT_RELU) return;
     auto T = [&](const std::string& k) -> HostTensor* { auto it = h->tensors.find(k); return it == h->tensors.end() || !it->second.loaded ? nullptr : &it->second; };
     auto layer = [&](const std::string& conv, const std::string& bn) {
         BalanceLayer L; L.w = T(conv + ".weight"); L.b = T(conv + ".bias");
         if (!bn.empty()) { L.g = T(bn + ".weight"); L.beta = T(bn + ".bias"); L.mean = T(bn + ".running_mean"); L.var = T(bn + ".running_var"); }
         return L;
     };
+    if (c.head_type == NWW_HEAD_BCRESNET) {
+        // the operands of a block's two products are scaled per PIXEL ROW in the kernel (dual_x3, bc_chain) and their weights per tensor, so a
+        // channel 2^g off its neighbours costs them (and the weight columns that compensate it) g bits all the same.  Balanced here:
+        //   depthwise[c] against pointwise[:, c] of the same block - nothing nonlinear between them, so under every activation;
+        //   under ReLU, the init conv's BatchNorm, and each block's TWO BatchNorms as one channel (bn1 + shortcut.1: the sum of the bounds,
+        //   the same 2^e), against the next block's pointwise and shortcut.0 columns - the last block's against fc.weight
+        const bool relu = c.activation == ACT_RELU;
+        auto usable = [](const BalanceLayer& L, size_t C) {
+            return L.w && !L.w->shape.empty() && (size_t)L.w->shape[0] == C && C > 0 && L.w->data.size() % C == 0 &&
+                   (!L.g || (L.beta && L.mean && L.var && L.g->data.size() == C && L.beta->data.size() == C && L.mean->data.size() == C && L.var->data.size() == C));
+        };
+        auto reads = [](HostTensor* W, size_t C) { return W && !W->shape.empty() && W->shape[0] > 0 && (W->data.size() / (size_t)W->shape[0]) % C == 0 && W->data.size() % (size_t)W->shape[0] == 0; };
+        const size_t ch[4] = {32, 64, 128, 256};
+        double bound_h = NWW_F16_FEATURE_BOUND;
+        for (int i = 0; i <= 3; ++i) {
+            const std::string q = "model.block" + std::to_string(i), qn = "model.block" + std::to_string(i + 1);
+            if (relu) {                                   // the channels of h_i: the init conv (i = 0) or block i
+                std::vector<BalanceLayer> prod;
+                std::vector<double> in;
+                if (i == 0) { prod = {layer("model.init_conv.0", "model.init_conv.1")}; in = {bound_h}; }
+                else { prod = {layer(q + ".pointwise", q + ".bn1"), layer(q + ".shortcut.0", q + ".shortcut.1")}; in = {0.0, bound_h}; }
+                std::vector<HostTensor*> cons;
+                if (i < 3) cons = {T(qn + ".pointwise.weight"), T(qn + ".shortcut.0.weight")};
+                else cons = {T("model.fc.weight")};
+                for (const BalanceLayer& L : prod) if (!usable(L, ch[i]) || !L.g) return;
+                for (HostTensor* W : cons) if (!reads(W, ch[i])) return;
+                if (i > 0) {                              // d_i's bound: the depthwise rows as balanced in the pass before, on h_(i-1)'s bound
+                    const HostTensor* dw = T(q + ".depthwise.weight");
+                    double worst = 0.0;
+                    for (size_t cc = 0; cc < ch[i - 1]; ++cc) { double l1 = 0.0; for (int k = 0; k < 9; ++k) l1 += std::fabs((double)dw->data[cc * 9 + k]); worst = std::fmax(worst, l1); }
+                    in[0] = worst * bound_h;
+                }
+                bound_h = balance_channels(prod, in, cons);
+            }
+            if (i < 3) {
+                BalanceLayer dw; dw.w = T(qn + ".depthwise.weight");
+                HostTensor* pw = T(qn + ".pointwise.weight");
+                if (!usable(dw, ch[i]) || dw.w->data.size() != ch[i] * 9 || !reads(pw, ch[i])) return;
+                (void)balance_channels(dw, {pw}, 1.0);
+            }
+        }
+        return;
+    }
     std::vector<std::pair<BalanceLayer, HostTensor*>> links;      // a layer and the weight that reads its channels
     if (c.head_type == NWW_HEAD_CNN) {
         links = {{layer("model.conv1", ""), T("model.conv2.weight")}, {layer("model.conv2", ""), T("model.fc1.weight")}};

@@ -128,7 +128,8 @@ inline double f16_layer_typ(const std::vector<float>& w, int Cout, int K, const 
     return acc / (Cout > 0 ? Cout : 1) * typ_in;
 }
 
-// ---- channel gains balanced at load time (two-term arithmetic, ReLU heads with a plan-time-scaled conv trunk: cnn, crnn, e2e_dnn)
+// ---- channel gains balanced at load time (two-term arithmetic, ReLU heads with a plan-time-scaled conv trunk: cnn, crnn, e2e_dnn; and
+// BcResNet's blocks, whose operands are scaled per pixel row - a spread of channel gains costs the same bits there, see f16_pixel_rows_ok)
 // One power of two per TENSOR serves conv1's and conv2's outputs, so a channel whose gain is G times the others' pushes them log2 G bits
 // down the operand, and the range guard (F16Range, f16_rows_ok) then has to send the layer that reads it to three terms.  ReLU and the
 // pools are positively homogeneous: channel c of a layer x s_c and the next layer's weights on c / s_c, s_c a power of two, is the same
@@ -139,18 +140,25 @@ inline double f16_layer_typ(const std::vector<float>& w, int Cout, int K, const 
 // bounds within a few x of each other) are not touched; GELU / SiLU heads cannot be (the guard decides for them).  -> the layer's bound after
 // (the per-channel bound folds the BatchNorm in double from the raw statistics - not f16_layer_bound's float32 folded factors: the two differ in the last bits)
 struct BalanceLayer { HostTensor *w = nullptr, *b = nullptr, *g = nullptr, *beta = nullptr, *mean = nullptr, *var = nullptr; };
-inline double balance_channels(const BalanceLayer& L, const std::vector<HostTensor*>& consumers, double in_bound) {
-    const int Cout = (int)L.w->shape[0], K = (int)(L.w->data.size() / Cout);
+// A channel may have several PRODUCERS that are added behind their BatchNorms (BcResNet: bn1 and shortcut.1 of one block; the activation sits
+// on one branch only, so the channel is positively homogeneous in the pair).  Its bound is the sum of the producers' bounds (each on its own
+// input bound) and every producer takes the same 2^e.  One producer is the plain form above, to the bit.
+inline double balance_channels(const std::vector<BalanceLayer>& Ls, const std::vector<double>& in_bounds, const std::vector<HostTensor*>& consumers) {
+    const int Cout = (int)Ls[0].w->shape[0];
     std::vector<double> bound(Cout, 0.0);
-    for (int c = 0; c < Cout; ++c) {
-        double t = 0.0;
-        for (int k = 0; k < K; ++k) t += std::fabs((double)L.w->data[(size_t)c * K + k]);
-        t = t * in_bound + (L.b ? std::fabs((double)L.b->data[c]) : 0.0);
-        if (L.g) {
-            const double al = (double)L.g->data[c] / std::sqrt((double)L.var->data[c] + 1e-5), be = (double)L.beta->data[c] - (double)L.mean->data[c] * al;
-            t = t * std::fabs(al) + std::fabs(be);
+    for (size_t l = 0; l < Ls.size(); ++l) {
+        const BalanceLayer& L = Ls[l];
+        const int K = (int)(L.w->data.size() / Cout);
+        for (int c = 0; c < Cout; ++c) {
+            double t = 0.0;
+            for (int k = 0; k < K; ++k) t += std::fabs((double)L.w->data[(size_t)c * K + k]);
+            t = t * in_bounds[l] + (L.b ? std::fabs((double)L.b->data[c]) : 0.0);
+            if (L.g) {
+                const double al = (double)L.g->data[c] / std::sqrt((double)L.var->data[c] + 1e-5), be = (double)L.beta->data[c] - (double)L.mean->data[c] * al;
+                t = t * std::fabs(al) + std::fabs(be);
+            }
+            bound[c] = l == 0 ? t : bound[c] + t;
         }
-        bound[c] = t;
     }
     // what a channel is worth to the layer behind it: its bound times the 2-norm of the weights that read it.  A channel worth less than 2^-8
     // of the layer's best (a nearly dead BatchNorm channel, a pruned column) is neither moved nor counted: the median is taken over the rest
@@ -179,8 +187,11 @@ inline double balance_channels(const BalanceLayer& L, const std::vector<HostTens
         }
         if (e != 0) {
             const float s = std::ldexp(1.0f, e), r = std::ldexp(1.0f, -e);
-            if (L.g) { L.g->data[c] *= s; L.beta->data[c] *= s; }
-            else { for (int k = 0; k < K; ++k) L.w->data[(size_t)c * K + k] *= s; if (L.b) L.b->data[c] *= s; }
+            for (const BalanceLayer& L : Ls) {
+                const int K = (int)(L.w->data.size() / Cout);
+                if (L.g) { L.g->data[c] *= s; L.beta->data[c] *= s; }
+                else { for (int k = 0; k < K; ++k) L.w->data[(size_t)c * K + k] *= s; if (L.b) L.b->data[c] *= s; }
+            }
             for (HostTensor* W : consumers) {                   // [N][Cout * per]: channel c is columns c per .. c per + per - 1
                 const size_t N = (size_t)W->shape[0], Kc = W->data.size() / N, per = Kc / Cout;
                 for (size_t n = 0; n < N; ++n)
@@ -190,4 +201,28 @@ inline double balance_channels(const BalanceLayer& L, const std::vector<HostTens
         worst = std::fmax(worst, std::ldexp(bound[c], e));
     }
     return worst;
+}
+inline double balance_channels(const BalanceLayer& L, const std::vector<HostTensor*>& consumers, double in_bound) {
+    return balance_channels(std::vector<BalanceLayer>{L}, std::vector<double>{in_bound}, consumers);
+}
+
+// ---- operands scaled per pixel row in the kernel (dual_x3 / bc_chain under NWW_ARITH_F16X3): the row's largest element lands in
+// [2^14, 2^15) and W carries one power of two per tensor, so no tensor bound is needed - but an element 2^g below its row's (its tensor's)
+// largest keeps min(22, 38 - g) bits: the absolute error of a scaled value is 2^-25 once its `lo` term is subnormal, 2^-39 of the largest.
+// An activation channel's lost bits reach output row co through W's column on it, a weight's through the activations it multiplies, so
+// with typ[c] the per-channel typical magnitudes of the operand and (sig2, norm2, wmax) the moments of W on them (f16_rows_moments):
+//   activations: 2^-39 max_c typ[c] sqrt(norm2[co]) against the row's output sqrt(sig2[co])   ->  max typ <= window x f16_rows_seen
+//   weights:     2^-39 wmax sqrt(sum_c typ[c]^2)   against the same                           ->  wmax |typ| <= window x sqrt(sig2[co])
+// window = f16_range_factor() (2^16: 22 bits, as F16Range::ok; no 2^4 on top as in f16_rows_ok - nothing here is a worst-case bound).
+// Uniform channels pass with 2^12 to spare; a channel 2^g louder or quieter than its neighbours (compensated in W's column) fails from
+// g ~ 16 + log2 sqrt(K) at the latest.  A row or channel of exact zeros is exempt.  What fails stays on the three-term bf16 form
+inline bool f16_pixel_rows_ok(const F16Rows& m, const std::vector<double>& typ) {
+    double tmax = 0.0, t2 = 0.0;
+    for (double t : typ) { tmax = std::fmax(tmax, t); t2 += t * t; }
+    if (!(tmax > 0.0) || !std::isfinite(t2)) return false;
+    const double window = f16_range_factor(), seen = f16_rows_seen(m);
+    if (!(seen < INFINITY) || !(tmax <= seen * window)) return false;
+    for (size_t co = 0; co < m.norm2.size(); ++co)
+        if (m.norm2[co] > 0.0 && !(m.wmax * std::sqrt(t2) <= std::sqrt(m.sig2[co]) * window)) return false;
+    return true;
 }

@@ -1,7 +1,8 @@
 // plan_host_check.cpp - the planner's value arithmetic (csrc/plan_host.h) held to what its comments promise (tests/test_plan_host.py):
 // the power-of-two scales against the binary16 range, the layer bound against sampled and sign-aligned inputs, the range guards on a
 // model with uniform channel gains and on one whose gains spread, and the load-time channel balance against a float32 forward of a
-// tiny conv + ReLU + Linear net written out here.
+// tiny conv + ReLU + Linear net written out here - and, for a channel with two producers, of a tiny two-branch block; the guard of the
+// operands that are scaled per pixel row.
 #include <cstdio>
 #include <cstring>
 #include <random>
@@ -232,7 +233,132 @@ static void check_balance() {
     }
 }
 
+// ---- balance_channels with TWO producers of one channel (a BcResNet block): h[c] = ReLU(BN1(pw[c] . d)) + BN2(sc[c] . xs), 8 channels on
+// 6 inputs each, read by a [4][8] and a [3][8] layer (the next block's pointwise and shortcut)
+struct DualNet {
+    HostTensor pw, sc, g1, beta1, mean1, var1, g2, beta2, mean2, var2, n1, n2;
+    std::vector<BalanceLayer> layers() {
+        BalanceLayer a, b;
+        a.w = &pw; a.g = &g1; a.beta = &beta1; a.mean = &mean1; a.var = &var1;
+        b.w = &sc; b.g = &g2; b.beta = &beta2; b.mean = &mean2; b.var = &var2;
+        return {a, b};
+    }
+    std::vector<HostTensor*> all() { return {&pw, &sc, &g1, &beta1, &mean1, &var1, &g2, &beta2, &mean2, &var2, &n1, &n2}; }
+    static float bn(float acc, const HostTensor& g, const HostTensor& beta, const HostTensor& mean, const HostTensor& var, int c) {
+        const float invstd = 1.0f / std::sqrt(var.data[c] + 1e-5f), al = g.data[c] * invstd, be = beta.data[c] - mean.data[c] * al;
+        return acc * al + be;
+    }
+    void forward(const float* d, const float* xs, float* out) const {      // float32, one summation order, the library's fold
+        float h[8];
+        for (int c = 0; c < 8; ++c) {
+            float a = 0.0f, r = 0.0f;
+            for (int k = 0; k < 6; ++k) { a += pw.data[c * 6 + k] * d[k]; r += sc.data[c * 6 + k] * xs[k]; }
+            a = bn(a, g1, beta1, mean1, var1, c); r = bn(r, g2, beta2, mean2, var2, c);
+            h[c] = (a > 0.0f ? a : 0.0f) + r;
+        }
+        for (int n = 0; n < 4; ++n) { float acc = 0.0f; for (int c = 0; c < 8; ++c) acc += n1.data[n * 8 + c] * h[c]; out[n] = acc; }
+        for (int n = 0; n < 3; ++n) { float acc = 0.0f; for (int c = 0; c < 8; ++c) acc += n2.data[n * 8 + c] * h[c]; out[4 + n] = acc; }
+    }
+    double bound(double bd, double bx) const {                            // the largest channel's: the SUM of the two branches' bounds
+        double worst = 0.0;
+        for (int c = 0; c < 8; ++c) {
+            double t1 = 0.0, t2 = 0.0;
+            for (int k = 0; k < 6; ++k) { t1 += std::fabs((double)pw.data[c * 6 + k]); t2 += std::fabs((double)sc.data[c * 6 + k]); }
+            const double al1 = (double)g1.data[c] / std::sqrt((double)var1.data[c] + 1e-5), be1 = (double)beta1.data[c] - (double)mean1.data[c] * al1;
+            const double al2 = (double)g2.data[c] / std::sqrt((double)var2.data[c] + 1e-5), be2 = (double)beta2.data[c] - (double)mean2.data[c] * al2;
+            worst = std::fmax(worst, (t1 * bd * std::fabs(al1) + std::fabs(be1)) + (t2 * bx * std::fabs(al2) + std::fabs(be2)));
+        }
+        return worst;
+    }
+};
+static DualNet dual_net() {
+    DualNet t;
+    t.pw.shape = t.sc.shape = {8, 6, 1, 1}; t.pw.data = rand_vec(48, -1.0, 1.0); t.sc.data = rand_vec(48, -1.0, 1.0);
+    for (HostTensor* v : {&t.g1, &t.beta1, &t.mean1, &t.var1, &t.g2, &t.beta2, &t.mean2, &t.var2}) v->shape = {8};
+    t.g1.data = rand_vec(8, 0.8, 1.25); t.beta1.data = rand_vec(8, -0.5, 0.5); t.mean1.data = rand_vec(8, -0.5, 0.5); t.var1.data = rand_vec(8, 0.8, 1.25);
+    t.g2.data = rand_vec(8, 0.8, 1.25); t.beta2.data = rand_vec(8, -0.5, 0.5); t.mean2.data = rand_vec(8, -0.5, 0.5); t.var2.data = rand_vec(8, 0.8, 1.25);
+    t.n1.shape = {4, 8, 1, 1}; t.n1.data = rand_vec(32, -1.0, 1.0);
+    t.n2.shape = {3, 8, 1, 1}; t.n2.data = rand_vec(24, -1.0, 1.0);
+    return t;
+}
+static void set_dual_gain(DualNet& t, int c, int e) {                      // both BatchNorms of channel c x 2^e, both readers' columns x 2^-e
+    for (HostTensor* v : {&t.g1, &t.beta1, &t.g2, &t.beta2}) v->data[c] = std::ldexp(v->data[c], e);
+    for (int n = 0; n < 4; ++n) t.n1.data[n * 8 + c] = std::ldexp(t.n1.data[n * 8 + c], -e);
+    for (int n = 0; n < 3; ++n) t.n2.data[n * 8 + c] = std::ldexp(t.n2.data[n * 8 + c], -e);
+}
+static void check_balance_two_producers() {
+    const double bd = 6.0, bx = 4.0;
+    const std::vector<float> ds = rand_vec(100 * 6, -bd, bd), xs = rand_vec(100 * 6, -bx, bx);
+    for (int e : {10, -10}) {
+        DualNet before = dual_net();
+        set_dual_gain(before, 5, e);
+        DualNet after = before;
+        const double ret = balance_channels(after.layers(), {bd, bx}, {&after.n1, &after.n2});
+        int moved = 0;
+        const std::vector<HostTensor*> tb = before.all(), ta = after.all();
+        for (size_t i = 0; i < tb.size(); ++i)
+            for (size_t j = 0; j < tb[i]->data.size(); ++j) {
+                const float x = tb[i]->data[j], y = ta[i]->data[j];
+                if (x == 0.0f) { CHECK(y == 0.0f, "dual tensor %zu[%zu]: 0 -> %g", i, j, (double)y); continue; }
+                CHECK(is_pow2((double)y / (double)x), "dual tensor %zu[%zu]: factor %.9g", i, j, (double)y / (double)x);
+                moved += y != x;
+            }
+        CHECK(moved > 0, "dual 2^%d: nothing was balanced", e);
+        // the two BatchNorms of a channel take the SAME power of two, the convolutions and the statistics none
+        for (int c = 0; c < 8; ++c) {
+            const double f = (double)after.g1.data[c] / (double)before.g1.data[c];
+            CHECK(f == (double)after.g2.data[c] / (double)before.g2.data[c] && f == (double)after.beta1.data[c] / (double)before.beta1.data[c] &&
+                  f == (double)after.beta2.data[c] / (double)before.beta2.data[c], "dual 2^%d channel %d: unequal factors", e, c);
+            CHECK((c == 5) == (f != 1.0), "dual 2^%d channel %d: factor %g", e, c, f);
+        }
+        CHECK(after.pw.data == before.pw.data && after.sc.data == before.sc.data && after.var1.data == before.var1.data && after.mean2.data == before.mean2.data,
+              "dual 2^%d: a convolution or a statistic moved", e);
+        float o0[7], o1[7];
+        for (int i = 0; i < 100; ++i) {
+            before.forward(&ds[(size_t)i * 6], &xs[(size_t)i * 6], o0); after.forward(&ds[(size_t)i * 6], &xs[(size_t)i * 6], o1);
+            CHECK(std::memcmp(o0, o1, sizeof o0) == 0, "dual 2^%d input %d: %.9g .. -> %.9g ..", e, i, (double)o0[0], (double)o1[0]);
+        }
+        CHECK(ret == after.bound(bd, bx), "dual 2^%d: returned %.17g, the balanced tensors give %.17g", e, ret, after.bound(bd, bx));
+        if (e > 0) CHECK(after.bound(bd, bx) < before.bound(bd, bx) * 0.0625, "dual: bound %g -> %g", before.bound(bd, bx), after.bound(bd, bx));
+    }
+    DualNet mild = dual_net();
+    for (int c = 0; c < 8; ++c) set_dual_gain(mild, c, c % 4);
+    DualNet kept = mild;
+    const double ret2 = balance_channels(kept.layers(), {bd, bx}, {&kept.n1, &kept.n2});
+    const std::vector<HostTensor*> tm = mild.all(), tk = kept.all();
+    for (size_t i = 0; i < tm.size(); ++i)
+        CHECK(std::memcmp(tm[i]->data.data(), tk[i]->data.data(), tm[i]->data.size() * sizeof(float)) == 0, "dual mild: tensor %zu changed", i);
+    CHECK(ret2 == mild.bound(bd, bx), "dual mild: returned %.17g, the tensors give %.17g", ret2, mild.bound(bd, bx));
+}
+
+// ---- f16_pixel_rows_ok: operands scaled per pixel row, weights per tensor - a channel (and the column that compensates it) 2^g off the rest
+static void check_pixel_rows() {
+    const int N = 6, K = 8;
+    auto ok = [&](const std::vector<float>& w, const std::vector<double>& typ) {
+        return f16_pixel_rows_ok(f16_rows_moments(N, K, [&](int q, int co) { return w[(size_t)co * K + q]; }, [](int q) { return q; }, typ), typ);
+    };
+    const std::vector<float> w0 = rand_vec((size_t)N * K, 0.5, 1.0);
+    const std::vector<double> t0(K, 3.0);
+    CHECK(ok(w0, t0), "uniform channels");
+    for (int g : {-24, -20, -8, 8, 20, 24}) {                   // channel 2 x 2^g, its column x 2^-g: passes at 2^8, fails at 2^20 and beyond
+        std::vector<float> w = w0;
+        std::vector<double> t = t0;
+        t[2] = std::ldexp(t[2], g);
+        for (int n = 0; n < N; ++n) w[(size_t)n * K + 2] = std::ldexp(w[(size_t)n * K + 2], -g);
+        CHECK(ok(w, t) == (std::abs(g) == 8), "channel 2 x 2^%d compensated", g);
+    }
+    std::vector<double> t = t0;
+    t[2] = std::ldexp(t[2], -24);                               // a quiet channel nothing compensates loses bits nobody reads: fine
+    CHECK(ok(w0, t), "a quiet channel with ordinary weights");
+    std::vector<float> w = w0;
+    for (int k = 0; k < K; ++k) w[(size_t)3 * K + k] = 0.0f;    // a row of zeros is exempt
+    CHECK(ok(w, t0), "a row of zeros");
+    CHECK(!ok(w0, std::vector<double>(K, 0.0)), "no magnitude known");
+}
+
 int main() {
+    check_balance_two_producers();
+    check_pixel_rows();
     check_scale();
     check_wscale();
     check_layer_bound();

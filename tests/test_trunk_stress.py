@@ -8,8 +8,8 @@ the guard also holds the bound against the operand as its quietest consumer row 
 what it refuses stays on the three-term bf16 form.
 
 Heads: cnn, crnn, e2e_dnn with ReLU only - GELU and SiLU are not positively homogeneous, so a channel rescale is not the same function under
-them.  BcResNet stays out: its identity shortcuts add a block's input to its output, so no per-channel rescale of one layer can be undone in
-the next.
+them.  BcResNet has a file of its own, tests/test_bcresnet_stress.py: its shortcuts are 1x1 convolutions with a BatchNorm, so a per-channel
+rescale of a block's output is undone in the next block's pointwise and shortcut columns, and its operands are scaled per pixel row.
 
 The emulator's table at (37, 28) ((24, 16) tells the same; table() prints both) - max |logit - float64| / max(1, |logit|max) on 33 clips of
 synth_features(seed 9), every operand the device splits under the plan's scales split as split_h2.h does (hi = RN16(v), lo = RN16(v - hi),
