@@ -467,15 +467,27 @@ extern int nww_mix_frontend_dev(nww_handle* h, const int16_t* d_arena, int64_t a
  * any B and any position in the table.  An item without a response (ir_id == -1) is the clip nww_mix gives, bit for bit.
  * Response SPECTRA are prepared once: nww_rir_prepare_dev takes K responses lying back to back in a float32 device buffer
  * (ir_off / ir_len: HOST arrays, samples) and writes float [K][M] (8-byte aligned) in the kernel's own order - opaque to callers, valid
- * for this N and M only.  A response with N + min(ir_len, N) - 1 > 32768 is NWW_ERR_INVALID with its index ("overlap-save not built"),
- * and so are ir_len < 1, one that does not fit M, and an M that is none of the three; nothing is truncated silently.  The call
- * synchronises `stream` before it returns.
+ * for this N and M only.  A response with N + min(ir_len, N) - 1 > 32768 is NWW_ERR_INVALID with its index ("overlap-save not built"
+ * into this route; pass NWW_RIR_SEGMENTED), and so are ir_len < 1, one that does not fit M, and an M that is none of the three; nothing
+ * is truncated silently.  The call synchronises `stream` before it returns.
+ * M = NWW_RIR_SEGMENTED selects the second route, for clips and responses of ANY length (N >= 1, ir_len >= 1): uniformly partitioned
+ * overlap-save on the 32768-point transform.  The first min(ir_len, N) taps are cut into nww_rir_parts(N, ir_len) partitions of 16384
+ * taps, the clip into segments of 16384 outputs; a segment is the float32 sum, partition after partition, of its windows' transforms
+ * (csrc/rir_plan.h, restated in tests/rir_seg_oracle.py: again the same bits on the host and the device, at any B), and the peak is
+ * taken over the whole clip before the tail.  d_spectra then holds nww_rir_spectra_floats(K, N, max ir_len, NWW_RIR_SEGMENTED) floats
+ * (16-byte aligned; it carries every response's partition count) and is valid for this N, and for n_irs <= K, only; the mixing calls
+ * keep 4 B N + 4 B ceil(N / 16384) bytes of float32 scratch on the handle.  Every other rule and message is the same on both routes.
  * The mixing calls take a second HOST table rir_items [B] next to `items` (NULL: no response anywhere, M / d_spectra / n_irs are not
  * read and the call is nww_mix_*'s); both tables go up in ONE copy through the same slot.  Checked on the host for every item before
  * anything is enqueued, after the rules above: ir_id in [-1, n_irs), reserved == 0, and M one of the three sizes with N <= M (the M the
  * spectra were prepared at) - NWW_ERR_INVALID names the index and the field, nothing is launched and no slot is taken.                */
 typedef struct nww_rir_item { int32_t ir_id; uint32_t reserved; } nww_rir_item;   /* -1: none; reserved == 0 */
 extern int32_t nww_rir_fft_size(int32_t N, int32_t max_ir_len);
+#define NWW_RIR_SEGMENTED (-1)         /* as M: the segmented route */
+/* partitions of a response of max_ir_len taps against clips of N; 0 for arguments below 1                                           */
+extern int32_t nww_rir_parts(int32_t N, int32_t max_ir_len);
+/* floats of d_spectra for K responses at M (a transform size: K * M; NWW_RIR_SEGMENTED: see above); 0 for bad arguments             */
+extern int64_t nww_rir_spectra_floats(int32_t K, int32_t N, int32_t max_ir_len, int32_t M);
 extern int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int64_t* ir_off, const int32_t* ir_len, int32_t K, int32_t N, int32_t M,
                                float* d_spectra, void* stream);
 extern int nww_mix_rir_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,

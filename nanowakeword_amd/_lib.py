@@ -55,6 +55,7 @@ SYMBOLS = [
     "nww_bank_stream_push_some_dev", "nww_bank_stream_push_some",
     "nww_mix_dev", "nww_mix", "nww_mix_forward_pcm_dev", "nww_mix_frontend_dev",
     "nww_rir_fft_size", "nww_rir_prepare_dev", "nww_mix_rir_dev", "nww_mix_rir", "nww_mix_rir_forward_pcm_dev", "nww_mix_rir_frontend_dev",
+    "nww_rir_parts", "nww_rir_spectra_floats",
 ]
 
 
@@ -190,6 +191,8 @@ def load_library():
     lib.nww_mix_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, i32, vp]; lib.nww_mix_frontend_dev.restype = C.c_int
     # ... through room impulse responses: spectra prepared once (device), `rir_items` a second host table (augment.RIR_ITEM)
     lib.nww_rir_fft_size.argtypes = [i32, i32]; lib.nww_rir_fft_size.restype = i32
+    lib.nww_rir_parts.argtypes = [i32, i32]; lib.nww_rir_parts.restype = i32
+    lib.nww_rir_spectra_floats.argtypes = [i32, i32, i32, i32]; lib.nww_rir_spectra_floats.restype = i64
     lib.nww_rir_prepare_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]; lib.nww_rir_prepare_dev.restype = C.c_int
     lib.nww_mix_rir_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp]; lib.nww_mix_rir_dev.restype = C.c_int
     lib.nww_mix_rir.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp]; lib.nww_mix_rir.restype = C.c_int

@@ -134,18 +134,47 @@ def rir_fft_size(N: int, max_ir_len: int) -> int:
     return next((M for M in RIR_FFT_SIZES if need <= M), 0)
 
 
+RIR_SEGMENTED = -1            # NWW_RIR_SEGMENTED: as M, the segmented route (clips and responses of any length)
+RIR_SEG_TAPS = 16384          # taps of a partition, and outputs of a segment (csrc/rir_plan.h)
+
+
+def rir_parts(N: int, max_ir_len: int) -> int:
+    """nww_rir_parts: the partitions of a response of L taps against clips of N, ceil(min(L, N) / 16384); 0 for arguments below 1"""
+    N, L = int(N), int(max_ir_len)
+    if N < 1 or L < 1:
+        return 0
+    return -(-min(L, N) // RIR_SEG_TAPS)
+
+
+def rir_spectra_floats(K: int, N: int, max_ir_len: int, M: int) -> int:
+    """nww_rir_spectra_floats: the float32 values of a spectra buffer of K responses at M; 0 for bad arguments"""
+    K, N, L, M = int(K), int(N), int(max_ir_len), int(M)
+    if K < 1 or N < 1 or L < 1:
+        return 0
+    if M == RIR_SEGMENTED:
+        return ((K + 2 + 3) & ~3) + K * rir_parts(N, L) * 32768
+    return K * M if M in RIR_FFT_SIZES else 0
+
+
 class IrArena:
     """Impulse responses for clips of N samples: float32 responses back to back (``offsets`` / ``lengths``, ``n`` of them), normalised
     on the host in float64 - ``"energy"``: sum h^2 = 1, ``"peak"``: max |h| = 1, None: as given (under peak normalisation of the clip the
     response's scale cancels) - and ``M``, the transform size that holds the longest.  With a device (the default, 0) the responses are
     uploaded ONCE and their spectra prepared ONCE, by the first model that uses the arena (``prepare(model)``); ``spectra_ptr`` is their
-    device address.  ``device=None`` keeps the host side only."""
+    device address.  ``device=None`` keeps the host side only.
 
-    def __init__(self, irs: Sequence[np.ndarray], N: int, device: Optional[int] = 0, normalize: Optional[str] = None, M: Optional[int] = None):
+    ``segmented=True`` lifts the limit of N + min(L, N) - 1 <= 32768: where no transform size fits, ``M`` is ``RIR_SEGMENTED`` and
+    ``parts`` the partitions of the longest response (``rir_parts``); where one fits, ``M`` is that size, as without the argument
+    (short clips keep the one-workgroup route and its bits) - unless ``M=RIR_SEGMENTED`` asks for the segmented route all the same."""
+
+    def __init__(self, irs: Sequence[np.ndarray], N: int, device: Optional[int] = 0, normalize: Optional[str] = None, M: Optional[int] = None,
+                 segmented: bool = False):
         """``M``: a transform size larger than the smallest that fits (the default), for a caller that wants one size for several arenas"""
         if normalize not in (None, "energy", "peak"):
             raise ValueError('normalize must be None, "energy" or "peak"')
         self.N = int(N)
+        if segmented and self.N < 1:
+            raise ValueError("a clip needs at least one sample")
         arrs = []
         for i, h in enumerate(irs):
             h = np.asarray(h)
@@ -157,7 +186,7 @@ class IrArena:
                 if norm == 0.0:
                     raise ValueError(f"response {i} is all zeros and cannot be normalised")
                 h64 = h64 / norm
-            if rir_fft_size(self.N, h.size) == 0:
+            if not segmented and rir_fft_size(self.N, h.size) == 0:
                 raise ValueError(f"response {i}: {h.size} taps against clips of {self.N} samples need more than 32768 points: "
                                  "overlap-save not built")
             arrs.append(h64.astype(np.float32))
@@ -167,7 +196,13 @@ class IrArena:
         self.offsets = np.concatenate(([0], np.cumsum(self.lengths.astype(np.int64))[:-1])).astype(np.int64)
         self.n = len(arrs)
         self.M = rir_fft_size(self.N, int(self.lengths.max()))
-        if M is not None:
+        self.parts = 0
+        if segmented and (self.M == 0 or (M is not None and int(M) == RIR_SEGMENTED)):
+            # no transform size holds the longest response, or the caller wants this route for clips that one would hold
+            if M is not None and int(M) != RIR_SEGMENTED:
+                raise ValueError("these responses need the segmented route: M can only be RIR_SEGMENTED")
+            self.M, self.parts = RIR_SEGMENTED, rir_parts(self.N, int(self.lengths.max()))
+        elif M is not None:
             if int(M) not in RIR_FFT_SIZES or int(M) < self.M:
                 raise ValueError(f"M must be one of {RIR_FFT_SIZES} and at least {self.M} for these responses")
             self.M = int(M)
@@ -186,7 +221,13 @@ class IrArena:
             import torch
             dev = f"cuda:{int(self.device)}"
             self._irs = torch.from_numpy(self.host).to(dev)
-            spectra = torch.empty((self.n, self.M), dtype=torch.float32, device=dev)
+            if self.M == RIR_SEGMENTED:
+                floats = int(model.lib.nww_rir_spectra_floats(self.n, self.N, int(self.lengths.max()), self.M))
+                if floats != rir_spectra_floats(self.n, self.N, int(self.lengths.max()), self.M):
+                    raise RuntimeError("nww_rir_spectra_floats disagrees with augment.rir_spectra_floats")
+                spectra = torch.empty((floats,), dtype=torch.float32, device=dev)
+            else:
+                spectra = torch.empty((self.n, self.M), dtype=torch.float32, device=dev)
             model.rir_prepare_dev(self._irs.data_ptr(), self.offsets, self.lengths, self.N, self.M, spectra.data_ptr())
             self._spectra = spectra
         return self

@@ -21,6 +21,8 @@ struct MixState {
     int16_t* d_arena = nullptr; int16_t* d_out = nullptr; size_t arena_bytes = 0, out_bytes = 0;
     // impulse responses (rir.hip): the twiddle table of each transform size, made by the first call that needs it
     float* d_tw[3] = {nullptr, nullptr, nullptr};
+    // the segmented route's float32 clips before the tail [B][N] and, behind them, the segments' peaks [B][Q]
+    void* d_seg = nullptr; size_t seg_bytes = 0;
 };
 
 void nww_mix_free(nww_handle* h) {
@@ -32,6 +34,7 @@ void nww_mix_free(nww_handle* h) {
     if (m->d_arena) (void)hipFree(m->d_arena);
     if (m->d_out) (void)hipFree(m->d_out);
     for (float* t : m->d_tw) if (t) (void)hipFree(t);
+    if (m->d_seg) (void)hipFree(m->d_seg);
     delete m;
     h->mix = nullptr;
 }
@@ -57,6 +60,7 @@ static int mix_slots(nww_handle* h, size_t B) {
 static int rir_twiddles(nww_handle* h, int M, const float** d_tw) {
     if (!h->mix) h->mix = new MixState();
     MixState* m = h->mix;
+    if (M == NWW_RIR_SEGMENTED) M = RIR_M_MAX;
     const int k = M == 2048 ? 0 : M == 8192 ? 1 : 2;
     if (!m->d_tw[k]) {
         std::vector<RirC> T((size_t)rir_twiddle_count(M));
@@ -95,8 +99,11 @@ static int mix_enqueue(nww_handle* h, const int16_t* d_arena, const nww_mix_item
     if (rc) return rc;
     MixState* m = h->mix;
     const float* d_tw = nullptr;
+    const bool seg = rir_items && M == NWW_RIR_SEGMENTED;
+    const size_t w_bytes = (size_t)B * (size_t)N * sizeof(float);
     if (rir_items) {
         rc = rir_twiddles(h, M, &d_tw);
+        if (!rc && seg) rc = nww_grow(h, &m->d_seg, &m->seg_bytes, w_bytes + (size_t)B * (size_t)rir_segments(N) * sizeof(unsigned));
         if (rc) return rc;
     }
     const unsigned slot = m->seq % POOL_TAB_SLOTS;
@@ -109,9 +116,11 @@ static int mix_enqueue(nww_handle* h, const int16_t* d_arena, const nww_mix_item
     if (rir_items) std::memcpy(pin + tab_bytes, rir_items, rtab_bytes);
     HIP_TRY(h, hipMemcpyAsync(dev, pin, tab_bytes + rtab_bytes, hipMemcpyHostToDevice, s));
     const nww_mix_item* d_items = reinterpret_cast<const nww_mix_item*>(dev);
-    const hipError_t e = rir_items ? rir_mix_launch(d_arena, d_items, reinterpret_cast<const nww_rir_item*>(dev + tab_bytes), d_spectra, M, d_tw, B, N,
-                                                    d_out, s)
-                                   : mix_launch(d_arena, d_items, B, N, d_out, h->cu_count, s);
+    const nww_rir_item* d_ritems = reinterpret_cast<const nww_rir_item*>(dev + tab_bytes);
+    const hipError_t e = seg         ? rir_seg_mix_launch(d_arena, d_items, d_ritems, d_spectra, d_tw, B, N, static_cast<float*>(m->d_seg),
+                                                          reinterpret_cast<unsigned*>(static_cast<unsigned char*>(m->d_seg) + w_bytes), d_out, s)
+                         : rir_items ? rir_mix_launch(d_arena, d_items, d_ritems, d_spectra, M, d_tw, B, N, d_out, s)
+                                     : mix_launch(d_arena, d_items, B, N, d_out, h->cu_count, s);
     (void)hipEventRecord(m->ev[slot], s);
     if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch '%s' failed: %s", rir_items ? "mix_rir" : "mix", hipGetErrorString(e));
     return NWW_OK;
@@ -187,6 +196,8 @@ extern "C" int nww_mix_frontend_dev(nww_handle* h, const int16_t* d_arena, int64
 
 // ---- ... through a room impulse response (rir.hip, rir_plan.h)
 extern "C" int32_t nww_rir_fft_size(int32_t N, int32_t max_ir_len) { return rir_fft_size(N, max_ir_len); }
+extern "C" int32_t nww_rir_parts(int32_t N, int32_t max_ir_len) { return rir_parts(N, max_ir_len); }
+extern "C" int64_t nww_rir_spectra_floats(int32_t K, int32_t N, int32_t max_ir_len, int32_t M) { return rir_spectra_floats(K, N, max_ir_len, M); }
 
 extern "C" int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int64_t* ir_off, const int32_t* ir_len, int32_t K, int32_t N, int32_t M,
                                    float* d_spectra, void* stream) {
@@ -196,9 +207,10 @@ extern "C" int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int6
     if (K == 0) return NWW_OK;
     if (N < 1) return fail(h, NWW_ERR_INVALID, "a clip needs at least one sample (got %d)", N);
     if (!d_irs || !ir_off || !ir_len || !d_spectra) return fail(h, NWW_ERR_INVALID, "null response buffer, table or spectra");
-    if (!rir_size_fits(M, N)) return fail(h, NWW_ERR_INVALID, "M = %d is not a transform size (2048, 8192, 32768) that holds clips of %d", M, N);
+    const bool seg = M == NWW_RIR_SEGMENTED;
+    if (!seg && !rir_size_fits(M, N)) return fail(h, NWW_ERR_INVALID, "M = %d is not a transform size (2048, 8192, 32768) that holds clips of %d", M, N);
     const char* why = "";
-    const int64_t bad = rir_first_bad_response(ir_len, K, N, M, &why);
+    const int64_t bad = seg ? rir_seg_first_bad_response(ir_len, K) : rir_first_bad_response(ir_len, K, N, M, &why);
     if (bad >= 0) {
         if (why[0] == 'o')
             return fail(h, NWW_ERR_INVALID, "response %lld: %d taps against clips of %d need more than 32768 points: overlap-save not built",
@@ -218,9 +230,14 @@ extern "C" int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int6
     HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_tab), off_bytes + len_bytes));
     hipError_t e = hipMemcpyAsync(d_tab, ir_off, off_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab + off_bytes, ir_len, len_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = rir_prepare_launch(d_irs, reinterpret_cast<const int64_t*>(d_tab), reinterpret_cast<const int32_t*>(d_tab + off_bytes), K, N, M, d_tw,
-                               d_spectra, s);
+    if (e == hipSuccess) {
+        const int64_t* d_off = reinterpret_cast<const int64_t*>(d_tab);
+        const int32_t* d_len = reinterpret_cast<const int32_t*>(d_tab + off_bytes);
+        int32_t longest = 1;
+        for (int32_t k = 0; k < K; ++k) longest = ir_len[k] > longest ? ir_len[k] : longest;
+        e = seg ? rir_seg_prepare_launch(d_irs, d_off, d_len, K, N, rir_parts(N, longest), d_tw, d_spectra, s)
+                : rir_prepare_launch(d_irs, d_off, d_len, K, N, M, d_tw, d_spectra, s);
+    }
     const hipError_t e2 = hipStreamSynchronize(s);
     (void)hipFree(d_tab);
     if (e != hipSuccess) return fail(h, NWW_ERR_HIP, "launch 'rir_prepare' failed: %s", hipGetErrorString(e));
@@ -232,7 +249,8 @@ extern "C" int nww_rir_prepare_dev(nww_handle* h, const float* d_irs, const int6
 static int rir_check(nww_handle* h, const float* d_spectra, int32_t n_irs, int32_t M, const nww_rir_item* rir_items, int32_t B, int32_t N) {
     if (n_irs < 0) return fail(h, NWW_ERR_INVALID, "n_irs must not be negative (got %d)", n_irs);
     if (n_irs > 0 && !d_spectra) return fail(h, NWW_ERR_INVALID, "null spectra");
-    if (!rir_size_fits(M, N)) return fail(h, NWW_ERR_INVALID, "M = %d is not a transform size (2048, 8192, 32768) that holds clips of %d", M, N);
+    if (M != NWW_RIR_SEGMENTED && !rir_size_fits(M, N))
+        return fail(h, NWW_ERR_INVALID, "M = %d is not a transform size (2048, 8192, 32768) that holds clips of %d", M, N);
     const char* field = nullptr;
     const int64_t bad = rir_first_bad_item(rir_items, B, n_irs, &field);
     if (bad >= 0) return fail(h, NWW_ERR_INVALID, "rir item %lld: %s out of range (%d responses)", (long long)bad, field, n_irs);

@@ -208,6 +208,207 @@ __global__ __launch_bounds__(RirCfg<M>::THREADS) void rir_mix_kernel(const int16
     for (unsigned i = tid; i < (unsigned)N; i += THREADS) o[i] = mix_out(rir_lds[i], r);
 }
 
+// ---- the segmented route (rir_plan.h: RIR_SEG_*): partitions of RIR_SEG_LP taps, segments of RIR_SEG_V outputs, on the M = 32768 network
+constexpr int SEG_M = RIR_M_MAX, SEG_H = SEG_M / 2, SEG_V = RIR_SEG_V, SEG_THREADS = RirCfg<SEG_M>::THREADS, SEG_PER = SEG_V / SEG_THREADS;
+static_assert(SEG_V % SEG_THREADS == 0 && SEG_M == 2 * SEG_V && RIR_SEG_LP <= SEG_M - SEG_V + 1, "a window is two segments; its upper half is free of wrap-around");
+
+// One workgroup per (response, partition): blockIdx.x = k * P_max + p.  Partition 0's workgroup also writes the response's count, and
+// the first workgroup the header's two leading words.
+__global__ __launch_bounds__(SEG_THREADS) void rir_seg_prepare_kernel(const float* __restrict__ irs, const int64_t* __restrict__ off,
+                                                                      const int32_t* __restrict__ len, int K, int N, int P_max,
+                                                                      const RirC* __restrict__ T, float* __restrict__ spectra) {
+    extern __shared__ __attribute__((aligned(16))) float rir_lds[];
+    RirC* z = reinterpret_cast<RirC*>(rir_lds);
+    const int k = (int)(blockIdx.x / (unsigned)P_max), p = (int)(blockIdx.x % (unsigned)P_max);
+    const int P = rir_parts(N, len[k]);
+    int32_t* hdr = reinterpret_cast<int32_t*>(spectra);
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == 0) { hdr[0] = P_max; hdr[1] = K; }
+        if (p == 0) hdr[2 + k] = P;
+    }
+    if (p >= P) return;                                                // the same in every lane of the workgroup
+    const int L = len[k], Le = L < N ? L : N, lo = p * RIR_SEG_LP, n = Le - lo < RIR_SEG_LP ? Le - lo : RIR_SEG_LP;
+    const float* h = irs + off[k] + lo;
+    for (int i = threadIdx.x; i < SEG_M; i += SEG_THREADS) rir_lds[i] = i < n ? h[i] : 0.0f;
+    __syncthreads();
+    fft_forward<SEG_M>(z, T);
+    RirC* spec = reinterpret_cast<RirC*>(spectra + rir_seg_header_floats(K)) + (size_t)blockIdx.x * SEG_H;
+    const float scale = 1.0f / (float)(8 * SEG_H);
+    for (uint32_t u = threadIdx.x; u < (uint32_t)(SEG_H / 2); u += SEG_THREADS) {
+        uint32_t pk, pm, kk;
+        pair_task<SEG_M>(u, pk, pm, kk);
+        RirC sk, sm;
+        rir_spectrum_pair(z[pk], z[pm], T[kk], scale, sk, sm);
+        spec[pm] = sm; spec[pk] = sk;
+        if (u == 0) spec[0] = rir_spectrum0(z[0], scale);
+    }
+}
+
+// One workgroup per (clip, segment): blockIdx.x = clip * Q + q.  Pass 1 runs over the WHOLE clip in every one of a clip's workgroups
+// (N int16 reads out of L2 against fifteen LDS passes per transform), so that a segment's bits are a function of its item and response
+// alone.  A thread keeps its SEG_PER = 16 outputs r = tid + j THREADS of the segment in registers across the partitions.
+__global__ __launch_bounds__(SEG_THREADS) void rir_seg_kernel(const int16_t* __restrict__ arena, const nww_mix_item* __restrict__ tab,
+                                                              const nww_rir_item* __restrict__ rtab, const float* __restrict__ spectra,
+                                                              const RirC* __restrict__ T, int N, int Q, float* __restrict__ w_out,
+                                                              unsigned* __restrict__ peaks) {
+    constexpr int THREADS = SEG_THREADS, WAVES = THREADS / 64, M = SEG_M, H = SEG_H, V = SEG_V;
+    extern __shared__ __attribute__((aligned(16))) float rir_lds[];
+    __shared__ unsigned long long red_sum[2][WAVES];
+    __shared__ unsigned red_max[2][WAVES];
+    RirC* z = reinterpret_cast<RirC*>(rir_lds);
+    const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const size_t clip = blockIdx.x / (unsigned)Q;
+    const int q = (int)(blockIdx.x % (unsigned)Q);
+    const nww_mix_item it = tab[clip];
+    const int ir = rtab[clip].ir_id;
+    const int16_t* fg = arena + it.fg_off;
+    const int16_t* bg = it.bg_len > 0 ? arena + it.bg_off : nullptr;
+    const unsigned bg_len = (unsigned)it.bg_len;
+    const unsigned step = bg ? (unsigned)THREADS % bg_len : 0u;
+    bool real = false;
+    float s = 0.0f;
+    if (bg) {                                                          // pass 1, as rir_mix_kernel's
+        unsigned long long Sf = 0, Sb = 0;
+        unsigned P = 0, p = ((unsigned)it.bg_start + tid) % bg_len;
+#pragma unroll 4
+        for (unsigned i = tid; i < (unsigned)N; i += THREADS) {
+            const int b = bg[p];
+            p += step; if (p >= bg_len) p -= bg_len;
+            const unsigned a = (unsigned)(b < 0 ? -b : b);
+            P = a > P ? a : P;
+            const long long j = (long long)i - it.start;
+            if (j >= 0 && j < it.fg_len) { const int f = fg[j]; Sf += (unsigned)(f * f); Sb += (unsigned)(b * b); }
+        }
+        Sf = wave_sum(Sf); Sb = wave_sum(Sb); P = wave_max(P);
+        if (lane == 0) { red_sum[0][wave] = Sf; red_sum[1][wave] = Sb; red_max[0][wave] = P; }
+        __syncthreads();
+        Sf = Sb = 0; P = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) { Sf += red_sum[0][w]; Sb += red_sum[1][w]; P = red_max[0][w] > P ? red_max[0][w] : P; }
+        real = mix_real_background(it.bg_len, (int32_t)P);
+        if (real) s = mix_scale(Sf, Sb, it.fg_len, it.snr_linear);
+    }
+    const long long ws = real ? it.start : 0;
+    // y of clip samples a0 + tid + t THREADS, t in [t0, t1), into dst[tid + t THREADS]: zeros outside the clip; the background index is
+    // taken modulo its length once and stepped from there
+    auto stage = [&](long long a0, int t0, int t1, float* dst) {
+        const long long first = a0 + tid + (long long)t0 * THREADS;
+        unsigned p = real && first >= 0 ? (unsigned)(((unsigned long long)it.bg_start + (unsigned long long)first) % bg_len) : 0u;
+#pragma unroll 4
+        for (int t = t0; t < t1; ++t) {
+            const long long i = a0 + tid + (long long)t * THREADS;
+            float v = 0.0f;
+            if (i >= 0 && i < N) {
+                const long long j = i - ws;
+                const bool in_fg = j >= 0 && j < it.fg_len;
+                int b = 0;
+                if (real) b = bg[p];
+                v = mix_y(in_fg ? fg[j] : 0, b, in_fg, real, s, it.gain);
+            }
+            if (real) { p += step; if (p >= bg_len) p -= bg_len; }
+            dst[tid + t * THREADS] = v;
+        }
+    };
+    float acc[SEG_PER];
+    if (ir < 0) {                                                      // the same in every lane of the workgroup: mix.hip's clip
+        stage((long long)q * V, 0, SEG_PER, rir_lds);                  // a thread reads back what it wrote itself
+#pragma unroll
+        for (int j = 0; j < SEG_PER; ++j) acc[j] = rir_lds[tid + j * THREADS];
+    } else {
+        const int32_t* hdr = reinterpret_cast<const int32_t*>(spectra);
+        const int P_max = hdr[0], P = hdr[2 + ir];
+        const RirC* spec0 = reinterpret_cast<const RirC*>(spectra + rir_seg_header_floats(hdr[1])) + (size_t)ir * P_max * H;
+        const int last = P - 1 < q ? P - 1 : q;
+#pragma unroll 1
+        for (int p = 0; p <= last; ++p) {
+            const RirC* spec = spec0 + (size_t)p * H;
+            // the window [(q - p - 1) V, (q - p + 1) V): with p == q its lower half lies before the clip
+            if (p == q) {
+#pragma unroll
+                for (int t = 0; t < SEG_PER; ++t) rir_lds[tid + t * THREADS] = 0.0f;
+                stage(-(long long)V, SEG_PER, 2 * SEG_PER, rir_lds);
+            } else {
+                stage((long long)(q - p - 1) * V, 0, 2 * SEG_PER, rir_lds);
+            }
+            __syncthreads();
+            fft_forward<M>(z, T);
+            constexpr int PAIRS = H / 2 / THREADS, STEP = 4;
+#pragma unroll 1
+            for (int t0 = 0; t0 < PAIRS; t0 += STEP) {
+                uint32_t pk[STEP], pm[STEP];
+                RirC w[STEP], sk[STEP], sm[STEP], zk[STEP], zm[STEP];
+#pragma unroll
+                for (int i = 0; i < STEP; ++i) {
+                    uint32_t k;
+                    pair_task<M>(tid + (uint32_t)(t0 + i) * THREADS, pk[i], pm[i], k);
+                    w[i] = T[k]; sk[i] = spec[pk[i]]; sm[i] = spec[pm[i]];
+                    zk[i] = z[pk[i]]; zm[i] = z[pm[i]];
+                }
+#pragma unroll
+                for (int i = 0; i < STEP; ++i) {
+                    rir_pair(zk[i], zm[i], w[i], sk[i], sm[i]);
+                    z[pm[i]] = zm[i]; z[pk[i]] = zk[i];
+                }
+            }
+            if (tid == 0) z[0] = rir_pair0(z[0], spec[0]);
+            __syncthreads();
+            fft_inverse<M>(z, T);                                      // ends in a barrier
+#pragma unroll
+            for (int j = 0; j < SEG_PER; ++j) acc[j] = rir_seg_acc(p, acc[j], rir_lds[V + tid + j * THREADS]);
+            __syncthreads();                                           // the next window overwrites what was just read
+        }
+    }
+    float* wrow = w_out + clip * (size_t)N + (size_t)q * V;
+    const int n = N - q * V < V ? N - q * V : V;
+    unsigned m = 0;
+#pragma unroll
+    for (int j = 0; j < SEG_PER; ++j) {
+        const int r = (int)tid + j * THREADS;
+        if (r < n) {
+            wrow[r] = acc[j];
+            const unsigned a = __float_as_uint(acc[j]) & 0x7fffffffu;
+            m = a > m ? a : m;
+        }
+    }
+    m = wave_max(m);
+    if (lane == 0) red_max[1][wave] = m;
+    __syncthreads();
+    if (tid == 0) {
+        m = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) m = red_max[1][w] > m ? red_max[1][w] : m;
+        peaks[blockIdx.x] = m;
+    }
+}
+
+// One workgroup per (clip, segment) again: the clip's peak out of its Q segments', the ratio, mix_out
+__global__ __launch_bounds__(256) void rir_seg_tail_kernel(const nww_mix_item* __restrict__ tab, const float* __restrict__ w_in,
+                                                           const unsigned* __restrict__ peaks, int N, int Q, int16_t* __restrict__ out) {
+    __shared__ unsigned red_max[4];
+    const unsigned tid = threadIdx.x;
+    const size_t clip = blockIdx.x / (unsigned)Q;
+    const int q = (int)(blockIdx.x % (unsigned)Q);
+    const float level = tab[clip].level;
+    const uint32_t flags = tab[clip].flags;
+    float pk = 0.0f;
+    if (flags & NWW_MIX_PEAK_NORMALISE) {
+        unsigned m = 0;
+        for (int i = (int)tid; i < Q; i += 256) { const unsigned a = peaks[clip * (size_t)Q + i]; m = a > m ? a : m; }
+        m = wave_max(m);
+        if ((tid & 63) == 0) red_max[tid >> 6] = m;
+        __syncthreads();
+        m = red_max[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) m = red_max[w] > m ? red_max[w] : m;
+        pk = __uint_as_float(m);
+    }
+    const float r = mix_ratio(level, flags, pk);
+    const size_t base = clip * (size_t)N + (size_t)q * SEG_V;
+    const int n = N - q * SEG_V < SEG_V ? N - q * SEG_V : SEG_V;
+#pragma unroll 4
+    for (int i = (int)tid; i < n; i += 256) out[base + i] = mix_out(w_in[base + i], r);
+}
+
 template <int M>
 hipError_t prepare_m(const float* d_irs, const int64_t* d_off, const int32_t* d_len, int K, int N, const float* d_tw, float* d_spectra, hipStream_t stream) {
     const size_t lds = (size_t)M * sizeof(float);
@@ -240,6 +441,33 @@ hipError_t rir_prepare_launch(const float* d_irs, const int64_t* d_off, const in
     case 32768: return prepare_m<32768>(d_irs, d_off, d_len, K, N, d_tw, d_spectra, stream);
     }
     return hipErrorInvalidValue;
+}
+
+hipError_t rir_seg_prepare_launch(const float* d_irs, const int64_t* d_off, const int32_t* d_len, int K, int N, int P_max, const float* d_tw,
+                                  float* d_spectra, hipStream_t stream) {
+    if (K <= 0) return hipSuccess;
+    if (P_max < 1 || (int64_t)K * P_max > 0x7fffffff) return hipErrorInvalidValue;
+    const size_t lds = (size_t)SEG_M * sizeof(float);
+    const hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(&rir_seg_prepare_kernel), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rir_seg_prepare_kernel, dim3((unsigned)(K * P_max)), dim3(SEG_THREADS), lds, stream, d_irs, d_off, d_len, K, N, P_max,
+                       reinterpret_cast<const RirC*>(d_tw), d_spectra);
+    return hipGetLastError();
+}
+
+hipError_t rir_seg_mix_launch(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra,
+                              const float* d_tw, int B, int N, float* d_w, unsigned* d_peaks, int16_t* d_out, hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    const int Q = rir_segments(N);
+    if (Q < 1 || (int64_t)B * Q > 0x7fffffff) return hipErrorInvalidValue;
+    const size_t lds = (size_t)SEG_M * sizeof(float);
+    const hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(&rir_seg_kernel), lds);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)(B * Q));
+    hipLaunchKernelGGL(rir_seg_kernel, grid, dim3(SEG_THREADS), lds, stream, d_arena, d_tab, d_rtab, d_spectra, reinterpret_cast<const RirC*>(d_tw), N,
+                       Q, d_w, d_peaks);
+    hipLaunchKernelGGL(rir_seg_tail_kernel, grid, dim3(256), 0, stream, d_tab, d_w, d_peaks, N, Q, d_out);
+    return hipGetLastError();
 }
 
 hipError_t rir_mix_launch(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra, int M,

@@ -11,6 +11,7 @@
 // 2 X_h / (8H), and the unnormalised inverse then ends in w itself.
 // Every float32 product and sum is rounded on its own (MIX_NO_CONTRACT); a complex multiply is four products and two sums.
 #pragma once
+#include <cstring>
 #include <vector>
 
 #include "mix_plan.h"
@@ -210,6 +211,101 @@ inline void rir_clip_host(const int16_t* arena, const nww_mix_item& it, const Ri
         for (int32_t i = 0; i < N; ++i) pk = std::fmax(pk, std::fabs(w[i]));
     const float r = mix_ratio(it.level, it.flags, pk);
     for (int32_t i = 0; i < N; ++i) out[i] = mix_out(w[i], r);
+}
+
+// ---- the segmented route (NWW_RIR_SEGMENTED): uniformly partitioned overlap-save on the M = 32768 transform, for clips and responses
+// of any length.  A response's first Le = min(L, N) taps are cut into P = ceil(Le / RIR_SEG_LP) partitions, each prepared as a response
+// of a RIR_SEG_V-sample clip is; the clip into Q = ceil(N / RIR_SEG_V) segments.  Segment q is the sum over p <= min(P - 1, q), in that
+// order, of the upper half of the window y[(q - p - 1) V .. (q - p + 1) V) (zeros outside the clip) convolved with partition p.
+#define RIR_SEG_V 16384
+#define RIR_SEG_LP 16384
+MIX_HD int32_t rir_parts(int32_t N, int32_t L) {
+    if (N < 1 || L < 1) return 0;
+    const int32_t Le = L < N ? L : N;
+    return (int32_t)(((int64_t)Le + RIR_SEG_LP - 1) / RIR_SEG_LP);
+}
+// partition p's term c joins a segment's sum: ((c_0 + c_1) + c_2) + ..
+MIX_HD float rir_seg_acc(int p, float acc, float c) { MIX_NO_CONTRACT return p ? acc + c : c; }
+MIX_HD int32_t rir_segments(int32_t N) { return N < 1 ? 0 : (int32_t)(((int64_t)N + RIR_SEG_V - 1) / RIR_SEG_V); }
+// The segmented spectra buffer, in floats: a header of int32 bit patterns - [0] the partitions every response has room for (P of the
+// longest), [1] K, [2 + k] response k's own P - padded to four, then [K][P_max][M / 2] complex values.
+MIX_HD int64_t rir_seg_header_floats(int32_t K) { return ((int64_t)K + 2 + 3) & ~(int64_t)3; }
+// the size of d_spectra for either route (M a transform size: K * M), or 0 for bad arguments
+MIX_HD int64_t rir_spectra_floats(int32_t K, int32_t N, int32_t max_ir_len, int32_t M) {
+    if (K < 1 || N < 1 || max_ir_len < 1) return 0;
+    if (M == NWW_RIR_SEGMENTED) return rir_seg_header_floats(K) + (int64_t)K * rir_parts(N, max_ir_len) * RIR_M_MAX;
+    return rir_is_size(M) ? (int64_t)K * M : 0;
+}
+
+// a response's partitions [P][M / 2], each as rir_prepare_host leaves a response of at most RIR_SEG_LP taps (host only)
+inline void rir_seg_prepare_host(const float* h, int32_t L, int32_t N, const RirC* T, RirC* spec) {
+    const int32_t Le = L < N ? L : N, P = rir_parts(N, L);
+    for (int32_t p = 0; p < P; ++p) {
+        const int32_t lo = p * RIR_SEG_LP, n = Le - lo < RIR_SEG_LP ? Le - lo : RIR_SEG_LP;
+        rir_prepare_host(h + lo, n, RIR_SEG_V, RIR_M_MAX, T, spec + (size_t)p * (RIR_M_MAX / 2));
+    }
+}
+
+// One clip on the host as rir_seg_kernel and rir_seg_tail_kernel run it (the CPU check's reference; the library never calls it):
+// spec == null is the clip without a response.  w [N] holds the clip before the tail afterwards.
+inline void rir_seg_clip_host(const int16_t* arena, const nww_mix_item& it, const RirC* spec, int32_t P, int32_t N, const RirC* T, float* w,
+                              int16_t* out) {
+    const int32_t M = RIR_M_MAX, V = RIR_SEG_V;
+    const int16_t* fg = arena + it.fg_off;
+    const int16_t* bg = it.bg_len > 0 ? arena + it.bg_off : nullptr;
+    auto bgs = [&](int64_t i) -> int { return bg[(it.bg_start + i) % it.bg_len]; };
+    bool real = false;
+    float s = 0.0f;
+    if (bg) {
+        uint64_t Sf = 0, Sb = 0;
+        int32_t Pk = 0;
+        for (int32_t j = 0; j < it.fg_len; ++j) {
+            const int64_t f = fg[j], b = bgs((int64_t)it.start + j);
+            Sf += (uint64_t)(f * f); Sb += (uint64_t)(b * b);
+        }
+        for (int32_t i = 0; i < N; ++i) { const int32_t a = bgs(i) < 0 ? -bgs(i) : bgs(i); Pk = a > Pk ? a : Pk; }
+        real = mix_real_background(it.bg_len, Pk);
+        if (real) s = mix_scale(Sf, Sb, it.fg_len, it.snr_linear);
+    }
+    const int64_t ws = real ? it.start : 0;
+    auto y_at = [&](int64_t i) -> float {
+        if (i < 0 || i >= N) return 0.0f;
+        const bool in_fg = i >= ws && i < ws + it.fg_len;
+        return mix_y(in_fg ? fg[i - ws] : 0, real ? bgs(i) : 0, in_fg, real, s, it.gain);
+    };
+    if (!spec) {
+        for (int32_t i = 0; i < N; ++i) w[i] = y_at(i);
+    } else {
+        std::vector<float> x((size_t)M);
+        const int32_t Q = rir_segments(N);
+        for (int32_t q = 0; q < Q; ++q) {
+            const int32_t n = N - q * V < V ? N - q * V : V;
+            for (int32_t p = 0; p < P && p <= q; ++p) {
+                const int64_t a0 = (int64_t)(q - p - 1) * V;
+                for (int32_t t = 0; t < M; ++t) x[(size_t)t] = y_at(a0 + t);
+                rir_convolve_host(x.data(), M, T, spec + (size_t)p * (M / 2));
+                for (int32_t r = 0; r < n; ++r) w[(size_t)q * V + r] = rir_seg_acc(p, w[(size_t)q * V + r], x[(size_t)(V + r)]);
+            }
+        }
+    }
+    uint32_t m = 0;                                                    // the peak as the kernels take it: the max of the bit patterns
+    if (it.flags & NWW_MIX_PEAK_NORMALISE)
+        for (int32_t i = 0; i < N; ++i) {
+            uint32_t a;
+            std::memcpy(&a, &w[i], 4);
+            a &= 0x7fffffffu;
+            m = a > m ? a : m;
+        }
+    float pk;
+    std::memcpy(&pk, &m, 4);
+    const float r = mix_ratio(it.level, it.flags, pk);
+    for (int32_t i = 0; i < N; ++i) out[i] = mix_out(w[i], r);
+}
+// what nww_rir_prepare_dev refuses on the segmented route: a response without taps
+inline int64_t rir_seg_first_bad_response(const int32_t* ir_len, int64_t K) {
+    for (int64_t i = 0; i < K; ++i)
+        if (ir_len[i] < 1) return i;
+    return -1;
 }
 
 // what the calls check beyond mix_first_bad_item: every rir item against the number of responses, and M against N (rir_size_fits)

@@ -354,7 +354,8 @@ class HipModel:
     # ------------------------------------------------------------------ clips mixed on the device (nww_mix_*, augment.py)
     def rir_prepare_dev(self, irs_ptr: int, ir_off, ir_len, N: int, M: int, spectra_ptr: int, stream: int = 0):
         """nww_rir_prepare_dev: float32 responses back to back at irs_ptr (host tables ir_off int64 / ir_len int32, samples) -> their
-        spectra float32 [K, M] at spectra_ptr, for clips of N samples at transform size M.  Synchronises `stream`."""
+        spectra float32 [K, M] at spectra_ptr, for clips of N samples at transform size M - or, with M = augment.RIR_SEGMENTED, the
+        augment.rir_spectra_floats(...) values of the segmented route.  Synchronises `stream`."""
         off, ln = np.ascontiguousarray(ir_off, np.int64), np.ascontiguousarray(ir_len, np.int32)
         if off.ndim != 1 or off.shape != ln.shape:
             raise ValueError("ir_off and ir_len must be one-dimensional and of one length")

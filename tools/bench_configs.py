@@ -18,7 +18,9 @@ batches, a stream pool and a recording (bank_main) -> profiles/bank_bench_config
 --mix [out]: clips mixed on the device (nww_mix_*) alone and in front of the CNN head, against uploading the pre-mixed batch and against
 the same chain in torch ops (mix_main) -> profiles/mix_bench_configs.jsonl.
 --mix-rir [out]: the same clips through room impulse responses (nww_mix_rir_*) alone and in front of the CNN head, against the calls
-without responses and against torch.fft.rfft / irfft plus the tail on the same card (mix_rir_main) -> profiles/mix_rir_bench_configs.jsonl."""
+without responses and against torch.fft.rfft / irfft plus the tail on the same card (mix_rir_main) -> profiles/mix_rir_bench_configs.jsonl.
+--mix-rir-seg [out]: the same protocol at clips of 2 s on the segmented route (NWW_RIR_SEGMENTED), with --mix-rir's one-workgroup route in
+the same session as the per-transform yardstick (mix_rir_seg_main) -> profiles/mix_rir_seg_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -1261,7 +1263,144 @@ def mix_rir_main(out_path):
     sys.stdout.write(text)
 
 
+MIX_SEG_N = 32000             # the reference's shortest clip (transform_clips.py: min_allowable_length)
+
+
+def mix_rir_seg_child():
+    """One process: mix_rir_child's workload at clips of 2 s - the same 64 + 16 recordings, foregrounds cut to the clip, 64 responses of
+    0.25 - 1 s (4000 .. 16 000 taps: one partition, two segments, so two transforms per clip) on the segmented route.  Legs as there:
+    (a) mix_dev with responses alone, (b) forward_mixed_dev with them (cnn 201x64), (r) forward_mixed_dev without, (m) mix_dev without,
+    (d) torch.fft.rfft / irfft at n = N + L_max - 1 plus the tail on a resident float32 batch.  (d)'s batch is (m)'s int16 clips as
+    floats - levelled and quantised, where (a) convolves the float32 clip before the level - so its samples are not (a)'s:
+    torch_fft_max_lsb / torch_fft_differing_share only record that it computes the same convolution to within that quantisation."""
+    import torch
+    from nanowakeword_amd.augment import RIR_SEGMENTED, ClipArena, IrArena, draw_mix_items, draw_rir_ids, rir_parts
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    B, N = MIX_B, MIX_SEG_N
+    cfg = HeadConfig("cnn", (fe.n_frames(N), 64))
+    m = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+    rng = np.random.default_rng(7)
+    fg_len = rng.integers(N // 2, N + 1, 64)
+    bg_len = rng.integers(N, 10 * N + 1, 16)
+    clips = [synth_pcm("speechlike", 1, int(n), seed=100 + k)[0] for k, n in enumerate(fg_len)] + \
+            [synth_pcm("noise", 1, int(n), seed=200 + k)[0] for k, n in enumerate(bg_len)]
+    arena = ClipArena(clips, device=0)
+    items = draw_mix_items(rng, arena, rng.integers(0, 64, B), 64 + np.arange(16), N)
+    ir_len = rng.integers(4000, 16001, 64)
+    responses = [(rng.standard_normal(int(L)) * np.exp(-6.0 * np.arange(int(L)) / int(L))).astype(np.float32) for L in ir_len]
+    irs = IrArena(responses, N, device=0, normalize="energy", segmented=True).prepare(m)
+    assert irs.M == RIR_SEGMENTED
+    ids = draw_rir_ids(rng, 64, B, 1.0)
+    Q = -(-N // 16384)
+    pairs = int(sum(sum(1 for q in range(Q) for p in range(rir_parts(N, int(ir_len[k]))) if p <= q) for k in ids))
+    ts = torch.cuda.Stream(dev)
+    stream = ts.cuda_stream
+    m.reserve(B, N)
+    pcm = torch.empty((B, N), dtype=torch.int16, device=dev)
+    lg, pr = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(2))
+    m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream)
+    torch.cuda.synchronize()
+    y = pcm.to(torch.float32) / 32768.0
+    Lmax = int(ir_len.max())
+    n = N + Lmax - 1
+    hp = np.zeros((64, Lmax), np.float32)
+    for k in range(64):
+        hp[k, :irs.lengths[k]] = irs.host[irs.offsets[k]:irs.offsets[k] + irs.lengths[k]]
+    Hs = torch.fft.rfft(torch.from_numpy(hp).to(dev), n=n)
+    tid = torch.from_numpy(ids.astype(np.int64)).to(dev)
+    level = torch.from_numpy(np.ascontiguousarray(items["level"])).to(dev)[:, None]
+
+    def torch_leg():
+        with torch.cuda.stream(ts), torch.no_grad():
+            w = torch.fft.irfft(torch.fft.rfft(y, n=n) * Hs[tid], n=n)[:, :N]
+            pk = w.abs().amax(1, keepdim=True)
+            pk = torch.where(pk < 1e-8, torch.ones_like(pk), pk)
+            return (torch.clamp(w * (level / pk), -1.0, 1.0) * 32767).to(torch.int16)
+    legs = {"mix_rir_seg": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream, irs=irs, ir_ids=ids),
+            "mix_rir_seg_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream, irs=irs,
+                                                               ir_ids=ids),
+            "mix_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream),
+            "mix": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream),
+            "torch_fft": torch_leg}
+    out = {"B": B, "N": N, "M": irs.M, "responses": 64, "ir_len_min": int(ir_len.min()), "ir_len_max": Lmax, "torch_fft_n": n, "segments": Q,
+           "transforms": pairs, "scratch_bytes": 4 * B * N + 4 * B * Q}
+    for name, step in legs.items():
+        for _ in range(RNN_WARMUP):
+            got = step()
+        torch.cuda.synchronize()
+        if name == "torch_fft":                                              # pcm still holds (a)'s clips: legs (r) and (m) ran after it
+            m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream, irs=irs, ir_ids=ids)
+            torch.cuda.synchronize()
+            d = (got.to(torch.int32) - pcm.to(torch.int32)).abs()
+            out["torch_fft_max_lsb"], out["torch_fft_differing_share"] = int(d.max()), round(float((d > 0).float().mean()), 6)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+        for e0, e1 in ev:
+            e0.record(ts); step(); e1.record(ts)
+        torch.cuda.synchronize()
+        out[name + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+    print(json.dumps(out), flush=True)
+    m.close()
+
+
+def mix_rir_seg_main(out_path):
+    """RNN_REPEATS fresh child processes of the segmented route, then as many of --mix-rir's (the one-workgroup route at clips of 1 s: the
+    per-transform yardstick of this session), one after another, each under its own time limit; the medians of the repeats with their
+    spread (max - min over the repeats).  No claim is asserted; written down as measured: the segmented call against the torch route and
+    whether it beats it by more than the spread, the time per (segment, partition) transform against the one-workgroup route's per clip
+    (each of them less the mixing call without responses), and what the float32 scratch - written once and read once - costs at the
+    measured copy ceiling as a share of the call."""
+    import subprocess
+
+    def repeats(flag, names):
+        runs = []
+        for _ in range(RNN_REPEATS):
+            r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), flag], env=dict(os.environ), cwd=ROOT,
+                               stdout=subprocess.PIPE, text=True)
+            if r.returncode != 0:
+                raise SystemExit(f"{flag} exited {r.returncode}")
+            runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][0])
+        rep = {k: [r[k + "_ms"] for r in runs] for k in names}
+        return runs[0], rep, {k: float(np.median(v)) for k, v in rep.items()}
+    first, rep, med = repeats("--mix-rir-seg-child", ("mix_rir_seg", "mix_rir_seg_forward", "mix_forward", "mix", "torch_fft"))
+    one_first, one_rep, one_med = repeats("--mix-rir-child", ("mix_rir", "mix"))
+    spread = {k: round(max(v) - min(v), 4) for k, v in rep.items()}
+    per_transform_us = (med["mix_rir_seg"] - med["mix"]) / first["transforms"] * 1e3
+    one_per_clip_us = (one_med["mix_rir"] - one_med["mix"]) / one_first["B"] * 1e3
+    scratch_ms = 2 * first["scratch_bytes"] / MIX_COPY_CEILING * 1e3
+    line = {"config": f"mix-rir-seg B={MIX_B} N={MIX_SEG_N}, every clip through one of 64 responses of 0.25-1 s, segmented route, cnn 201x64", "B": MIX_B,
+            "N": MIX_SEG_N, "M": first["M"], "segments": first["segments"], "transforms": first["transforms"], "warmup": RNN_WARMUP,
+            "steps": RNN_STEPS, "repeats": RNN_REPEATS, "ms_repeats": rep, "spread_ms": spread,
+            "mix_rir_seg_ms": round(med["mix_rir_seg"], 4), "torch_fft_ms": round(med["torch_fft"], 4), "torch_fft_n": first["torch_fft_n"],
+            "torch_fft_over_mix_rir_seg": round(med["torch_fft"] / med["mix_rir_seg"], 2),
+            "beats_torch_fft_by_more_than_the_spread": bool(med["torch_fft"] - med["mix_rir_seg"] > max(spread["torch_fft"], spread["mix_rir_seg"])),
+            "torch_fft_max_lsb": first["torch_fft_max_lsb"], "torch_fft_differing_share": first["torch_fft_differing_share"],
+            "mix_rir_seg_forward_ms": round(med["mix_rir_seg_forward"], 4), "mix_forward_ms": round(med["mix_forward"], 4), "mix_ms": round(med["mix"], 4),
+            "rir_over_mix_forward_ms": round(med["mix_rir_seg_forward"] - med["mix_forward"], 4),
+            "clips_per_s": {k: round(MIX_B / (med[k] * 1e-3)) for k in ("mix_rir_seg", "mix_rir_seg_forward", "mix_forward")},
+            "one_workgroup_route": {"N": one_first["N"], "M": one_first["M"], "ms_repeats": one_rep, "mix_rir_ms": round(one_med["mix_rir"], 4),
+                                    "mix_ms": round(one_med["mix"], 4)},
+            "us_per_transform_segmented": round(per_transform_us, 4), "us_per_clip_one_workgroup": round(one_per_clip_us, 4),
+            "transform_cost_ratio": round(per_transform_us / one_per_clip_us, 3),
+            "scratch_bytes": first["scratch_bytes"], "scratch_ms_at_copy_ceiling": round(scratch_ms, 4),
+            "scratch_share_of_mix_rir_seg": round(scratch_ms / med["mix_rir_seg"], 4)}
+    text = json.dumps(line) + "\n"
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 def main():
+    if "--mix-rir-seg-child" in sys.argv[1:]:
+        return mix_rir_seg_child()
+    if "--mix-rir-seg" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--mix-rir-seg"]
+        return mix_rir_seg_main(rest[0] if rest else os.path.join(ROOT, "profiles", "mix_rir_seg_bench_configs.jsonl"))
     if "--mix-rir-child" in sys.argv[1:]:
         return mix_rir_child()
     if "--mix-rir" in sys.argv[1:]:

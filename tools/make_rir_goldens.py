@@ -36,7 +36,7 @@ def convolve(signal, ir):
     return torch.fft.irfft(torch.fft.rfft(signal, n=n) * torch.fft.rfft(ir, n=n), n=n)
 
 
-def reference_clip(mix_snr, arena, it, h):
+def reference_clip(mix_snr, arena, it, h, N=N):
     import torch
     fg = torch.from_numpy(arena[int(it["fg_off"]):int(it["fg_off"]) + int(it["fg_len"])].astype(np.float32) / np.float32(32768.0))
     L = int(it["bg_len"])
