@@ -502,6 +502,42 @@ extern int nww_mix_rir_frontend_dev(nww_handle* h, const int16_t* d_arena, int64
                                     const nww_mix_item* items, const nww_rir_item* rir_items, int32_t B, int32_t N, float* d_logmel,
                                     int32_t frames_major, void* stream);
 
+/* ---- pitch shift between the gain and the response (csrc/pitch.hip, csrc/pitch_plan.h) -------------------------
+ * The reference applies PitchShift(+-2 semitones, p = 0.5) between Gain and ApplyImpulseResponse (augment_clips.py:150-157).  What is
+ * restated is a DEFINITION of that construction, not the library's samples: a time stretch by a phase vocoder without phase scaling,
+ * then a windowed-sinc resampler back to N samples, at a rational ratio r = p / q (r > 1 raises the pitch):
+ *   STFT       n_fft 512, hop 128, periodic Hann, centred with reflect padding: T = 1 + N / 128 frames of 257 bins (N > 256)
+ *   vocoder    T_out = ceil(T p / q) frames; frame t reads X[i], X[i + 1] at i = (t q) div p, alpha = ((t q) mod p) / p (frames >= T are
+ *              zero); magnitude alpha |X1| + (1 - alpha) |X0|; phase of frame 0 that of X[0], then advanced by angle(X1) - angle(X0)
+ *   ISTFT      overlap-add over the summed squared window, centre trimmed: S = 128 (T_out - 1) samples
+ *   resample   y[n] = sum_k s[k] g(n p / q - k), n < ceil(S q / p), g a Hann-windowed sinc of six zero crossings a side at rolloff
+ *              0.99 (cutoff 0.99 min(1, q / p)); cropped or zero-padded to N
+ * The transform length, hop and window are this project's own.  y takes the place of the mixed clip after the gain in everything
+ * behind it: the response, the peak, the level and the int16 tail.  The float32 arithmetic is fixed in csrc/pitch_plan.h (restated in
+ * tests/pitch_oracle.py): the same bits on the host and the device, at any B and any place in the table.
+ * nww_pitch_set_ratios validates K <= 64 ratios (1 <= num, den <= 256, 2^(-4/12) <= num / den <= 2^(4/12)), builds their resampler
+ * tables on the host and uploads them onto the handle (it waits for the device); K = 0 clears them.
+ * The nww_mix_aug_* calls are the nww_mix_rir_* calls plus a third HOST table pitch_items [B] (NULL: the nww_mix_rir_* call; rir_items
+ * NULL as well: nww_mix_*'s); a clip with pitch_id == -1 comes out bit-identical to the same clip without the table.  Checked on the
+ * host before anything is enqueued, after the rules above: ratios set, 256 < N <= 2^28, pitch_id in [-1, K), reserved == 0 -
+ * NWW_ERR_INVALID names the index and the field, nothing is launched, no slot is taken and the ratios stay what they were.  The calls
+ * keep 4 (N + 128 ceil(T 162 / 128)) bytes of float32 scratch per shifted clip on the handle (about 9.1 N), grown on demand; calls on
+ * one handle share it, so they go on one stream or are ordered by the caller.                                                         */
+typedef struct nww_pitch_item { int32_t pitch_id; uint32_t reserved; } nww_pitch_item;   /* -1: none; reserved == 0 */
+extern int nww_pitch_set_ratios(nww_handle* h, const int32_t* num, const int32_t* den, int32_t K);
+extern int nww_mix_aug_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                           const nww_mix_item* items, const nww_rir_item* rir_items, const nww_pitch_item* pitch_items, int32_t B, int32_t N,
+                           int16_t* d_out, void* stream);
+extern int nww_mix_aug(nww_handle* h, const int16_t* arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs, int32_t M,
+                       const nww_mix_item* items, const nww_rir_item* rir_items, const nww_pitch_item* pitch_items, int32_t B, int32_t N,
+                       int16_t* out);
+extern int nww_mix_aug_forward_pcm_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs,
+                                       int32_t M, const nww_mix_item* items, const nww_rir_item* rir_items, const nww_pitch_item* pitch_items,
+                                       int32_t B, int32_t N, float* d_logits, float* d_probs, void* stream);
+extern int nww_mix_aug_frontend_dev(nww_handle* h, const int16_t* d_arena, int64_t arena_samples, const float* d_spectra, int32_t n_irs,
+                                    int32_t M, const nww_mix_item* items, const nww_rir_item* rir_items, const nww_pitch_item* pitch_items,
+                                    int32_t B, int32_t N, float* d_logmel, int32_t frames_major, void* stream);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

@@ -56,6 +56,7 @@ SYMBOLS = [
     "nww_mix_dev", "nww_mix", "nww_mix_forward_pcm_dev", "nww_mix_frontend_dev",
     "nww_rir_fft_size", "nww_rir_prepare_dev", "nww_mix_rir_dev", "nww_mix_rir", "nww_mix_rir_forward_pcm_dev", "nww_mix_rir_frontend_dev",
     "nww_rir_parts", "nww_rir_spectra_floats",
+    "nww_pitch_set_ratios", "nww_mix_aug_dev", "nww_mix_aug", "nww_mix_aug_forward_pcm_dev", "nww_mix_aug_frontend_dev",
 ]
 
 
@@ -200,6 +201,14 @@ def load_library():
     lib.nww_mix_rir_forward_pcm_dev.restype = C.c_int
     lib.nww_mix_rir_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp]
     lib.nww_mix_rir_frontend_dev.restype = C.c_int
+    # ... shifted in pitch first: ratios set once on the handle, `pitch_items` a third host table (augment.PITCH_ITEM)
+    lib.nww_pitch_set_ratios.argtypes = [vp, vp, vp, i32]; lib.nww_pitch_set_ratios.restype = C.c_int
+    lib.nww_mix_aug_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]; lib.nww_mix_aug_dev.restype = C.c_int
+    lib.nww_mix_aug.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, vp]; lib.nww_mix_aug.restype = C.c_int
+    lib.nww_mix_aug_forward_pcm_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.nww_mix_aug_forward_pcm_dev.restype = C.c_int
+    lib.nww_mix_aug_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp]
+    lib.nww_mix_aug_frontend_dev.restype = C.c_int
     _lib = lib
     return lib
 

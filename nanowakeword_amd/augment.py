@@ -9,8 +9,13 @@ device, and the recordings - uploaded once as a ``ClipArena`` - are gathered, me
 
 Impulse responses (``ApplyImpulseResponse(p=rir_prob)``, augment_clips.py:150-157) ride on the same calls: the responses
 go up once as an ``IrArena``, whose spectra are prepared once, ``draw_rir_ids`` draws a response or none per clip, and every call above
-takes ``irs=..., ir_ids=...``.  Not restated: pitch shift (``torch_audiomentations``' PitchShift); ``gain`` is the reference's Gain step,
-``level`` its volume step (:246-255).
+takes ``irs=..., ir_ids=...``.  ``gain`` is the reference's Gain step, ``level`` its volume step (:246-255).
+
+Pitch shift (``PitchShift(+-2 semitones, p=0.5)`` between Gain and ApplyImpulseResponse, :150-157) rides on them as well:
+``pitch_ratios`` lists rational ratios, a ``PitchBank`` sets them on a model, ``draw_pitch_ids`` draws a ratio or none per clip, and
+every call takes ``pitch=..., pitch_ids=...``.  What is restated is a DEFINITION of the library's construction - a phase vocoder without
+phase scaling, then a windowed-sinc resampler, at rational ratios - not ``torch_audiomentations``' samples: the transform length (512),
+hop (128) and window (periodic Hann) are this project's own (include/nww.h).
 """
 from __future__ import annotations
 
@@ -270,32 +275,123 @@ def draw_rir_ids(rng: np.random.Generator, n_irs: int, B: int, rir_prob: float =
     return np.where(on, rng.integers(0, int(n_irs), B), -1).astype(np.int32)
 
 
+# ---- pitch shift (nww_pitch_set_ratios / nww_mix_aug_*)
+PITCH_MAX_TERM = 256          # a ratio's numerator and denominator
+PITCH_MAX_RATIOS = 64         # the ratios a model holds at a time
+PITCH_MIN_SAMPLES = 257       # clips of at most 256 samples cannot be reflect-padded
+
+
+def pitch_ratio_ok(num: int, den: int) -> bool:
+    """what nww_pitch_set_ratios accepts: terms in [1, 256] and 2^(-4/12) <= num / den <= 2^(4/12), decided in integers"""
+    num, den = int(num), int(den)
+    return 1 <= num <= PITCH_MAX_TERM and 1 <= den <= PITCH_MAX_TERM and num ** 3 <= 2 * den ** 3 and den ** 3 <= 2 * num ** 3
+
+
+def pitch_ratios(min_semitones: float = -2.0, max_semitones: float = 2.0, max_den: int = 32):
+    """The reduced fractions num / den with den <= max_den and 2^(min_semitones / 12) <= num / den <= 2^(max_semitones / 12), without 1,
+    in ascending order -> [(num, den)].  The reference draws +-2 semitones (augment_clips.py:150-157); a call can name at most
+    PITCH_MAX_RATIOS of them (the defaults list far more: pick, or lower max_den)."""
+    from math import gcd
+    lo, hi = 2.0 ** (float(min_semitones) / 12.0), 2.0 ** (float(max_semitones) / 12.0)
+    out = []
+    for den in range(1, int(max_den) + 1):
+        for num in range(max(int(lo * den), 1), min(int(hi * den) + 1, PITCH_MAX_TERM) + 1):
+            if num != den and gcd(num, den) == 1 and lo <= num / den <= hi and pitch_ratio_ok(num, den):
+                out.append((num, den))
+    return sorted(out, key=lambda r: (r[0] / r[1], r[1]))
+
+
+class PitchBank:
+    """The ratios (num, den) a call's pitch ids name, at most 64.  ``prepare(model)`` sets them on the model (nww_pitch_set_ratios builds
+    the resampler tables and uploads them); a model holds one bank at a time, and a call with another bank sets that one."""
+
+    def __init__(self, ratios: Sequence):
+        r = [(int(a), int(b)) for a, b in ratios]
+        if not r or len(r) > PITCH_MAX_RATIOS:
+            raise ValueError(f"a PitchBank holds between 1 and {PITCH_MAX_RATIOS} ratios, got {len(r)}")
+        for k, (a, b) in enumerate(r):
+            if not pitch_ratio_ok(a, b):
+                raise ValueError(f"ratio {k}: {a} / {b} out of range (terms in [1, 256], within +-4 semitones)")
+        self.ratios = r
+        self.num, self.den = np.array([a for a, _ in r], np.int32), np.array([b for _, b in r], np.int32)
+        self.n = len(r)
+
+    def __len__(self) -> int:
+        return self.n
+
+    def prepare(self, model) -> "PitchBank":
+        if getattr(model, "_pitch_bank", None) is not self:
+            model.pitch_set_ratios(self.num, self.den)
+            model._pitch_bank = self
+        return self
+
+
+# struct nww_pitch_item (include/nww.h): 8 bytes
+PITCH_ITEM = np.dtype([("pitch_id", "<i4"), ("reserved", "<u4")])
+
+
+def as_pitch_items(pitch_ids, B: int) -> np.ndarray:
+    """a contiguous PITCH_ITEM table of B rows from ratio ids (-1: none) or a PITCH_ITEM table"""
+    if isinstance(pitch_ids, np.ndarray) and pitch_ids.dtype == PITCH_ITEM:
+        t = np.ascontiguousarray(pitch_ids)
+    else:
+        ids = np.asarray(pitch_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("pitch_ids must be a one-dimensional integer array (draw_pitch_ids builds it) or a table of augment.PITCH_ITEM")
+        if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+            raise ValueError("pitch_ids out of the int32 range")
+        t = np.zeros(ids.size, PITCH_ITEM)
+        t["pitch_id"] = ids
+    if t.ndim != 1 or len(t) != B:
+        raise ValueError(f"pitch_ids must have one entry per item ({B}), got {t.shape}")
+    return t
+
+
+def draw_pitch_ids(rng: np.random.Generator, n_ratios: int, B: int, pitch_prob: float = 0.5) -> np.ndarray:
+    """What PitchShift(p=pitch_prob) draws for B clips (augment_clips.py:150-157, p = 0.5): with that probability one of n_ratios ratios,
+    uniformly, otherwise -1 (none) -> int32 [B].  The stream of random numbers is this function's own."""
+    B = int(B)
+    if int(n_ratios) < 1:
+        return np.full(B, -1, np.int32)
+    on = rng.random(B) < float(pitch_prob)
+    return np.where(on, rng.integers(0, int(n_ratios), B), -1).astype(np.int32)
+
+
 class MixedClips:
     """The extractor generate_features runs over the tables of mixed_feature_batches: ``embed_clips(items)`` is
     ``features.embed_mixed(arena, items, N)`` - the mixed clips never exist on the host.  With ``irs`` (an IrArena) the batches are
-    (items, ir_ids) pairs, as mixed_feature_batches yields them when it is given ir_ids."""
+    (items, ir_ids) pairs, with ``pitch`` (a PitchBank) (items, pitch_ids) pairs, with both (items, ir_ids, pitch_ids) triples, as
+    mixed_feature_batches yields them when it is given the ids."""
 
-    def __init__(self, features, arena: ClipArena, N: int, irs: Optional[IrArena] = None):
-        self.features, self.arena, self.N, self.irs = features, arena, int(N), irs
+    def __init__(self, features, arena: ClipArena, N: int, irs: Optional[IrArena] = None, pitch: Optional[PitchBank] = None):
+        self.features, self.arena, self.N, self.irs, self.pitch = features, arena, int(N), irs, pitch
 
     def get_embedding_shape(self, audio_length_sec: float, sr: int = 16000):
         return self.features.get_embedding_shape(audio_length_sec, sr)
 
     def embed_clips(self, x, batch_size: int = 128, ncpu: int = 1) -> np.ndarray:
-        if self.irs is None:
+        if self.irs is None and self.pitch is None:
             return self.features.embed_mixed(self.arena, x, self.N)
-        items, ir_ids = x
-        return self.features.embed_mixed(self.arena, items, self.N, irs=self.irs, ir_ids=ir_ids)
+        rest = list(x[1:])
+        ir_ids = rest.pop(0) if self.irs is not None else None
+        pitch_ids = rest.pop(0) if self.pitch is not None else None
+        return self.features.embed_mixed(self.arena, x[0], self.N, irs=self.irs, ir_ids=ir_ids, pitch=self.pitch, pitch_ids=pitch_ids)
 
 
-def mixed_feature_batches(items: np.ndarray, batch_size: int = 4096, irs: Optional[IrArena] = None, ir_ids=None) -> Iterator:
+def mixed_feature_batches(items: np.ndarray, batch_size: int = 4096, irs: Optional[IrArena] = None, ir_ids=None,
+                          pitch: Optional[PitchBank] = None, pitch_ids=None) -> Iterator:
     """`items` in tables of batch_size rows: what features.generate_features takes as its audio_batches when its extractor is a
     MixedClips - ``generate_features(mixed_feature_batches(items), len(items), path, MixedClips(feats, arena, N), N / 16000)``.
-    With ``irs`` and ``ir_ids`` (one id per item) every batch is an (items, ir_ids) pair for ``MixedClips(..., irs=irs)``."""
+    With ``irs`` and ``ir_ids`` (one id per item) every batch is an (items, ir_ids) pair for ``MixedClips(..., irs=irs)``; with ``pitch``
+    and ``pitch_ids`` the pitch ids follow, for ``MixedClips(..., pitch=pitch)``."""
     items = as_items(items)
     if (irs is None) != (ir_ids is None):
         raise ValueError("irs and ir_ids go together")
+    if (pitch is None) != (pitch_ids is None):
+        raise ValueError("pitch and pitch_ids go together")
     rt = None if ir_ids is None else as_rir_items(ir_ids, len(items))
+    pt = None if pitch_ids is None else as_pitch_items(pitch_ids, len(items))
     step = max(int(batch_size), 1)
     for i in range(0, len(items), step):
-        yield items[i:i + step] if rt is None else (items[i:i + step], rt[i:i + step])
+        parts = [t[i:i + step] for t in (items, rt, pt) if t is not None]
+        yield parts[0] if len(parts) == 1 else tuple(parts)

@@ -16,7 +16,7 @@ LIB = os.path.join(PKG, "libnwwhip.so")
 EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
 EMU_LIB = os.path.join(EMU_DIR, "libfe_emu.so")
 
-HIP_SOURCES = ["nww_api.hip", "nww_weights.hip", "nww_plan.hip", "nww_stream.hip", "nww_comm.hip", "nww_emb.hip", "nww_recording.hip", "rec_windows.hip", "nww_cascade.hip", "cascade.hip", "nww_bank.hip", "nww_mix.hip", "mix.hip", "rir.hip", "frontend2.hip", "layers.hip", "gemm_x3.hip", "trunk.hip", "trunk_b.hip", "conv3_x3.hip", "ffn_x3.hip", "lin_x3.hip", "dual_x3.hip", "bc_chain.hip", "rnn_f32.hip", "rnn_x3.hip", "rnn_stream.hip", "mha_mfma.hip", "mha_h2.hip", "attn_x3.hip", "emb_stream.hip", "tcn_x3.hip", "merge_x3.hip", "qn_x3.hip", "raw_conv.hip", "raw_x3.hip", "conv2s_x3.hip", "fe_tables.cpp"]
+HIP_SOURCES = ["nww_api.hip", "nww_weights.hip", "nww_plan.hip", "nww_stream.hip", "nww_comm.hip", "nww_emb.hip", "nww_recording.hip", "rec_windows.hip", "nww_cascade.hip", "cascade.hip", "nww_bank.hip", "nww_mix.hip", "mix.hip", "rir.hip", "pitch.hip", "frontend2.hip", "layers.hip", "gemm_x3.hip", "trunk.hip", "trunk_b.hip", "conv3_x3.hip", "ffn_x3.hip", "lin_x3.hip", "dual_x3.hip", "bc_chain.hip", "rnn_f32.hip", "rnn_x3.hip", "rnn_stream.hip", "mha_mfma.hip", "mha_h2.hip", "attn_x3.hip", "emb_stream.hip", "tcn_x3.hip", "merge_x3.hip", "qn_x3.hip", "raw_conv.hip", "raw_x3.hip", "conv2s_x3.hip", "fe_tables.cpp"]
 
 
 def _hipcc() -> str:
@@ -41,8 +41,8 @@ def _newer(target: str, deps) -> bool:
 # (NWW_SLP=none against the default, tools/bench_configs.py): BcResNet front 0.534 -> 0.515, its depthwise kernels 0.118 /
 # 0.102 -> 0.114 / 0.094, dual_x3 0.172 / 0.242 -> 0.163 / 0.236, ffn_x3 -1 %; mha_mfma 0.318 -> 0.366 and conv3_x3 +1 % (they keep SLP).
 # rir.hip: its complex butterflies pair into 704 v_pk_* instructions; tools/bench_configs.py --mix-rir, mix + responses alone, B = 4096:
-# 1.534 ms with SLP, 1.508 without (spread of the repeats 0.004) - built without.
-NO_SLP = {"frontend2.hip", "trunk_b.hip", "dual_x3.hip", "bc_chain.hip", "layers.hip", "rnn_f32.hip", "ffn_x3.hip", "rir.hip"}
+# 1.534 ms with SLP, 1.508 without (spread of the repeats 0.004) - built without.  pitch.hip runs the same butterflies: built as rir.hip is.
+NO_SLP = {"frontend2.hip", "trunk_b.hip", "dual_x3.hip", "bc_chain.hip", "layers.hip", "rnn_f32.hip", "ffn_x3.hip", "rir.hip", "pitch.hip"}
 
 
 def build_hip(force: bool = False, verbose: bool = False, out: str = LIB) -> str:

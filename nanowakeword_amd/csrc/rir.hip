@@ -107,10 +107,13 @@ __device__ inline unsigned wave_max(unsigned v) {
     return v;
 }
 
-template <int M>
+// PITCH: the instance of nww_mix_aug_* - a clip whose pitch_id >= 0 is staged from yf32 (pitch.hip's shifted clip, its row in the item's
+// `reserved`) in place of steps 1 and 2; every other clip, and the instance without the flag, runs as it always has
+template <int M, bool PITCH>
 __global__ __launch_bounds__(RirCfg<M>::THREADS) void rir_mix_kernel(const int16_t* __restrict__ arena, const nww_mix_item* __restrict__ tab,
                                                                      const nww_rir_item* __restrict__ rtab, const RirC* __restrict__ spectra,
-                                                                     const RirC* __restrict__ T, int N, int16_t* __restrict__ out) {
+                                                                     const RirC* __restrict__ T, int N, int16_t* __restrict__ out,
+                                                                     const nww_pitch_item* __restrict__ ptab, const float* __restrict__ yf32) {
     constexpr int H = RirCfg<M>::H, THREADS = RirCfg<M>::THREADS, WAVES = THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) float rir_lds[];
     __shared__ unsigned long long red_sum[2][WAVES];
@@ -120,8 +123,9 @@ __global__ __launch_bounds__(RirCfg<M>::THREADS) void rir_mix_kernel(const int16
     const size_t clip = blockIdx.x;
     const nww_mix_item it = tab[clip];
     const int ir = rtab[clip].ir_id;
+    const bool shifted = PITCH && ptab[clip].pitch_id >= 0;            // the same in every lane of the workgroup
     const int16_t* fg = arena + it.fg_off;
-    const int16_t* bg = it.bg_len > 0 ? arena + it.bg_off : nullptr;
+    const int16_t* bg = it.bg_len > 0 && !shifted ? arena + it.bg_off : nullptr;
     const unsigned bg_len = (unsigned)it.bg_len;
     // this thread's background samples: clip sample i = tid + t THREADS reads bg[p], p stepping modulo bg_len
     const unsigned p0 = bg ? ((unsigned)it.bg_start + tid) % bg_len : 0u, step = bg ? (unsigned)THREADS % bg_len : 0u;
@@ -149,7 +153,11 @@ __global__ __launch_bounds__(RirCfg<M>::THREADS) void rir_mix_kernel(const int16
         if (real) s = mix_scale(Sf, Sb, it.fg_len, it.snr_linear);
     }
     const long long ws = real ? it.start : 0;                          // without a real background: the foreground alone, at the clip's start
-    {
+    if (shifted) {
+        const float* y = yf32 + (size_t)ptab[clip].reserved * (size_t)N;
+#pragma unroll 4
+        for (unsigned i = tid; i < (unsigned)M; i += THREADS) rir_lds[i] = i < (unsigned)N ? y[i] : 0.0f;
+    } else {
         unsigned p = p0;
 #pragma unroll 4
         for (unsigned i = tid; i < (unsigned)M; i += THREADS) {
@@ -247,10 +255,13 @@ __global__ __launch_bounds__(SEG_THREADS) void rir_seg_prepare_kernel(const floa
 // One workgroup per (clip, segment): blockIdx.x = clip * Q + q.  Pass 1 runs over the WHOLE clip in every one of a clip's workgroups
 // (N int16 reads out of L2 against fifteen LDS passes per transform), so that a segment's bits are a function of its item and response
 // alone.  A thread keeps its SEG_PER = 16 outputs r = tid + j THREADS of the segment in registers across the partitions.
+// PITCH: as rir_mix_kernel's flag - a window of a clip whose pitch_id >= 0 is read from yf32
+template <bool PITCH>
 __global__ __launch_bounds__(SEG_THREADS) void rir_seg_kernel(const int16_t* __restrict__ arena, const nww_mix_item* __restrict__ tab,
                                                               const nww_rir_item* __restrict__ rtab, const float* __restrict__ spectra,
                                                               const RirC* __restrict__ T, int N, int Q, float* __restrict__ w_out,
-                                                              unsigned* __restrict__ peaks) {
+                                                              unsigned* __restrict__ peaks, const nww_pitch_item* __restrict__ ptab,
+                                                              const float* __restrict__ yf32) {
     constexpr int THREADS = SEG_THREADS, WAVES = THREADS / 64, M = SEG_M, H = SEG_H, V = SEG_V;
     extern __shared__ __attribute__((aligned(16))) float rir_lds[];
     __shared__ unsigned long long red_sum[2][WAVES];
@@ -261,8 +272,10 @@ __global__ __launch_bounds__(SEG_THREADS) void rir_seg_kernel(const int16_t* __r
     const int q = (int)(blockIdx.x % (unsigned)Q);
     const nww_mix_item it = tab[clip];
     const int ir = rtab[clip].ir_id;
+    const bool shifted = PITCH && ptab[clip].pitch_id >= 0;            // the same in every lane of the workgroup
+    const float* ysh = shifted ? yf32 + (size_t)ptab[clip].reserved * (size_t)N : nullptr;
     const int16_t* fg = arena + it.fg_off;
-    const int16_t* bg = it.bg_len > 0 ? arena + it.bg_off : nullptr;
+    const int16_t* bg = it.bg_len > 0 && !shifted ? arena + it.bg_off : nullptr;
     const unsigned bg_len = (unsigned)it.bg_len;
     const unsigned step = bg ? (unsigned)THREADS % bg_len : 0u;
     bool real = false;
@@ -299,11 +312,15 @@ __global__ __launch_bounds__(SEG_THREADS) void rir_seg_kernel(const int16_t* __r
             const long long i = a0 + tid + (long long)t * THREADS;
             float v = 0.0f;
             if (i >= 0 && i < N) {
-                const long long j = i - ws;
-                const bool in_fg = j >= 0 && j < it.fg_len;
-                int b = 0;
-                if (real) b = bg[p];
-                v = mix_y(in_fg ? fg[j] : 0, b, in_fg, real, s, it.gain);
+                if (PITCH && shifted) {
+                    v = ysh[i];
+                } else {
+                    const long long j = i - ws;
+                    const bool in_fg = j >= 0 && j < it.fg_len;
+                    int b = 0;
+                    if (real) b = bg[p];
+                    v = mix_y(in_fg ? fg[j] : 0, b, in_fg, real, s, it.gain);
+                }
             }
             if (real) { p += step; if (p >= bg_len) p -= bg_len; }
             dst[tid + t * THREADS] = v;
@@ -419,15 +436,21 @@ hipError_t prepare_m(const float* d_irs, const int64_t* d_off, const int32_t* d_
     return hipGetLastError();
 }
 
+template <int M, bool PITCH>
+hipError_t mix_mp(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra, const float* d_tw, int B, int N,
+                  int16_t* d_out, const nww_pitch_item* d_ptab, const float* d_y, hipStream_t stream) {
+    const size_t lds = (size_t)M * sizeof(float);
+    const hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(&rir_mix_kernel<M, PITCH>), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((rir_mix_kernel<M, PITCH>), dim3((unsigned)B), dim3(RirCfg<M>::THREADS), lds, stream, d_arena, d_tab, d_rtab,
+                       reinterpret_cast<const RirC*>(d_spectra), reinterpret_cast<const RirC*>(d_tw), N, d_out, d_ptab, d_y);
+    return hipGetLastError();
+}
 template <int M>
 hipError_t mix_m(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra, const float* d_tw, int B, int N,
-                 int16_t* d_out, hipStream_t stream) {
-    const size_t lds = (size_t)M * sizeof(float);
-    const hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(&rir_mix_kernel<M>), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rir_mix_kernel<M>, dim3((unsigned)B), dim3(RirCfg<M>::THREADS), lds, stream, d_arena, d_tab, d_rtab,
-                       reinterpret_cast<const RirC*>(d_spectra), reinterpret_cast<const RirC*>(d_tw), N, d_out);
-    return hipGetLastError();
+                 int16_t* d_out, const nww_pitch_item* d_ptab, const float* d_y, hipStream_t stream) {
+    return d_ptab ? mix_mp<M, true>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, d_ptab, d_y, stream)
+                  : mix_mp<M, false>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, nullptr, nullptr, stream);
 }
 
 }  // namespace
@@ -456,27 +479,32 @@ hipError_t rir_seg_prepare_launch(const float* d_irs, const int64_t* d_off, cons
 }
 
 hipError_t rir_seg_mix_launch(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra,
-                              const float* d_tw, int B, int N, float* d_w, unsigned* d_peaks, int16_t* d_out, hipStream_t stream) {
+                              const float* d_tw, int B, int N, float* d_w, unsigned* d_peaks, int16_t* d_out, hipStream_t stream,
+                              const nww_pitch_item* d_ptab, const float* d_y) {
     if (B <= 0) return hipSuccess;
     const int Q = rir_segments(N);
     if (Q < 1 || (int64_t)B * Q > 0x7fffffff) return hipErrorInvalidValue;
     const size_t lds = (size_t)SEG_M * sizeof(float);
-    const hipError_t e = nww_allow_lds(reinterpret_cast<const void*>(&rir_seg_kernel), lds);
+    const hipError_t e = nww_allow_lds(d_ptab ? reinterpret_cast<const void*>(&rir_seg_kernel<true>) : reinterpret_cast<const void*>(&rir_seg_kernel<false>), lds);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)(B * Q));
-    hipLaunchKernelGGL(rir_seg_kernel, grid, dim3(SEG_THREADS), lds, stream, d_arena, d_tab, d_rtab, d_spectra, reinterpret_cast<const RirC*>(d_tw), N,
-                       Q, d_w, d_peaks);
+    if (d_ptab)
+        hipLaunchKernelGGL(rir_seg_kernel<true>, grid, dim3(SEG_THREADS), lds, stream, d_arena, d_tab, d_rtab, d_spectra,
+                           reinterpret_cast<const RirC*>(d_tw), N, Q, d_w, d_peaks, d_ptab, d_y);
+    else
+        hipLaunchKernelGGL(rir_seg_kernel<false>, grid, dim3(SEG_THREADS), lds, stream, d_arena, d_tab, d_rtab, d_spectra,
+                           reinterpret_cast<const RirC*>(d_tw), N, Q, d_w, d_peaks, nullptr, nullptr);
     hipLaunchKernelGGL(rir_seg_tail_kernel, grid, dim3(256), 0, stream, d_tab, d_w, d_peaks, N, Q, d_out);
     return hipGetLastError();
 }
 
 hipError_t rir_mix_launch(const int16_t* d_arena, const nww_mix_item* d_tab, const nww_rir_item* d_rtab, const float* d_spectra, int M,
-                          const float* d_tw, int B, int N, int16_t* d_out, hipStream_t stream) {
+                          const float* d_tw, int B, int N, int16_t* d_out, hipStream_t stream, const nww_pitch_item* d_ptab, const float* d_y) {
     if (B <= 0) return hipSuccess;
     switch (M) {
-    case 2048: return mix_m<2048>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, stream);
-    case 8192: return mix_m<8192>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, stream);
-    case 32768: return mix_m<32768>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, stream);
+    case 2048: return mix_m<2048>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, d_ptab, d_y, stream);
+    case 8192: return mix_m<8192>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, d_ptab, d_y, stream);
+    case 32768: return mix_m<32768>(d_arena, d_tab, d_rtab, d_spectra, d_tw, B, N, d_out, d_ptab, d_y, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -27,7 +27,8 @@ MIX_HD int32_t rir_fft_size(int32_t N, int32_t L) {
     return need <= 2048 ? 2048 : need <= 8192 ? 8192 : need <= RIR_M_MAX ? RIR_M_MAX : 0;
 }
 MIX_HD bool rir_is_size(int32_t M) { return M == 2048 || M == 8192 || M == RIR_M_MAX; }
-MIX_HD int rir_digits(int32_t M) { return M == 2048 ? 5 : M == 8192 ? 6 : 7; }           // H = M / 2 = 4^D
+// H = M / 2 = 4^D; 512 is the transform of pitch_plan.h's frames (no response is prepared at it: rir_is_size)
+MIX_HD int rir_digits(int32_t M) { return M == 512 ? 4 : M == 2048 ? 5 : M == 8192 ? 6 : 7; }
 
 // k's D base-4 digits reversed: its 2D bits reversed, then the two bits of every digit swapped back
 MIX_HD uint32_t rir_rev(uint32_t k, int D) {
@@ -92,22 +93,30 @@ MIX_HD void rir_spectrum_pair(RirC zk, RirC zm, RirC w, float scale, RirC& sk, R
 }
 MIX_HD RirC rir_spectrum0(RirC z0, float scale) { MIX_NO_CONTRACT const RirC x = rir_split0(z0); return {x.re * scale, x.im * scale}; }
 
+// the split's way back: the spectrum's pair (yk, ym) at bins k, H - k packed for the inverse network, which then ends in 2H times the
+// real sequence whose M-point transform the pairs are
+MIX_HD void rir_unsplit(RirC yk, RirC ym, RirC w, RirC& zk, RirC& zm) {
+    MIX_NO_CONTRACT
+    const RirC a = rir_add(yk, rir_conj(ym)), b = rir_sub(yk, rir_conj(ym));
+    const RirC o = rir_mul(b, w);
+    zk = {a.re - o.im, a.im + o.re};
+    zm = {a.re + o.im, o.re - a.im};
+}
+MIX_HD RirC rir_unsplit0(float y0, float yh) { MIX_NO_CONTRACT return {y0 + yh, y0 - yh}; }
+
 // a clip's pair: split, times the response's (sk, sm), packed again for the inverse - in place of zk, zm
 MIX_HD void rir_pair(RirC& zk, RirC& zm, RirC w, RirC sk, RirC sm) {
     MIX_NO_CONTRACT
     RirC xk, xm;
     rir_split(zk, zm, w, xk, xm);
     const RirC yk = rir_mul(xk, sk), ym = rir_mul(xm, sm);
-    const RirC a = rir_add(yk, rir_conj(ym)), b = rir_sub(yk, rir_conj(ym));
-    const RirC o = rir_mul(b, w);
-    zk = {a.re - o.im, a.im + o.re};
-    zm = {a.re + o.im, o.re - a.im};
+    rir_unsplit(yk, ym, w, zk, zm);
 }
 MIX_HD RirC rir_pair0(RirC z0, RirC s0) {
     MIX_NO_CONTRACT
     const RirC x = rir_split0(z0);
     const float y0 = x.re * s0.re, yh = x.im * s0.im;
-    return {y0 + yh, y0 - yh};
+    return rir_unsplit0(y0, yh);
 }
 
 // The pair tasks of a transform: task u < H / 2 works on positions p = 4 (u / 2) + (u & 1) - those whose k = rev(p) lies below H / 2 -

@@ -51,14 +51,15 @@ class HipFeatures:
             out.append(np.ascontiguousarray(lm.transpose(0, 2, 1)))
         return np.concatenate(out, axis=0) if out else np.zeros((0,) + self.get_embedding_shape(x.shape[1] / 16000), np.float32)
 
-    def mix(self, arena, items, N: int, irs=None, ir_ids=None) -> np.ndarray:
+    def mix(self, arena, items, N: int, irs=None, ir_ids=None, pitch=None, pitch_ids=None) -> np.ndarray:
         """int16 [B, N]: the clips of `items` mixed out of `arena` on the device (HipModel.mix)"""
-        return self._model.mix(arena, items, N, irs=irs, ir_ids=ir_ids)
+        return self._model.mix(arena, items, N, irs=irs, ir_ids=ir_ids, pitch=pitch, pitch_ids=pitch_ids)
 
-    def embed_mixed(self, arena, items, N: int, irs=None, ir_ids=None) -> np.ndarray:
+    def embed_mixed(self, arena, items, N: int, irs=None, ir_ids=None, pitch=None, pitch_ids=None) -> np.ndarray:
         """The features of the clips augment.mix_items / draw_mix_items describe, mixed out of a device-resident augment.ClipArena
         without the clips ever reaching the host -> float32 [B, frames, n_mels], equal to embed_clips(mix(arena, items, N)).  `irs` (an
-        augment.IrArena) and `ir_ids` send clips through impulse responses on the way."""
+        augment.IrArena) and `ir_ids` send clips through impulse responses on the way, `pitch` (an augment.PitchBank) and `pitch_ids`
+        shift them in pitch before that."""
         import torch
         from .augment import as_items
         items = as_items(items)
@@ -68,7 +69,7 @@ class HipFeatures:
         frames = self.fe.n_frames(N)
         dev = self._model.device
         out = torch.zeros((len(items), self.fe.n_mels, frames), dtype=torch.float32, device=f"cuda:{dev}")    # as frontend() lays it out
-        self._model.frontend_mixed_dev(arena.ptr, arena.samples, items, N, out.data_ptr(), irs=irs, ir_ids=ir_ids)
+        self._model.frontend_mixed_dev(arena.ptr, arena.samples, items, N, out.data_ptr(), irs=irs, ir_ids=ir_ids, pitch=pitch, pitch_ids=pitch_ids)
         torch.cuda.synchronize(dev)
         return np.ascontiguousarray(out.cpu().numpy().transpose(0, 2, 1))
 

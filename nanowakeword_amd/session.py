@@ -106,6 +106,7 @@ class HipModel:
             self._h = C.c_void_p()
             raise _EXC.get(rc, NwwError)(msg)
         self.finalized = False
+        self._pitch_bank = None            # the augment.PitchBank whose ratios the handle holds (PitchBank.prepare)
         if window is None and mel_fb is None and tables == "torchaudio":
             try:
                 window, mel_fb = torchaudio_tables(self.fe)
@@ -375,86 +376,98 @@ class HipModel:
         irs.prepare(self)
         return C.c_void_p(irs.spectra_ptr), irs.n, irs.M, rt
 
-    def mix_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, stream: int = 0, irs=None, ir_ids=None):
+    def pitch_set_ratios(self, num, den):
+        """nww_pitch_set_ratios: the ratios num[k] / den[k] a call's pitch ids name (augment.PitchBank does this); waits for the device"""
+        num, den = np.ascontiguousarray(num, np.int32), np.ascontiguousarray(den, np.int32)
+        if num.ndim != 1 or num.shape != den.shape:
+            raise ValueError("num and den must be one-dimensional and of one length")
+        self._check(self.lib.nww_pitch_set_ratios(self._h, num.ctypes.data_as(C.c_void_p), den.ctypes.data_as(C.c_void_p), len(num)))
+        self._pitch_bank = None
+
+    def _pitch_args(self, pitch, pitch_ids, B: int):
+        """the PITCH_ITEM table of a call's pitch / pitch_ids, or None without them (augment.PitchBank, set on this model here)"""
+        if pitch is None and pitch_ids is None:
+            return None
+        if pitch is None or pitch_ids is None:
+            raise ValueError("pitch (an augment.PitchBank) and pitch_ids (one ratio id per item, -1: none) go together")
+        from .augment import as_pitch_items
+        pt = as_pitch_items(pitch_ids, B)
+        pitch.prepare(self)
+        return pt
+
+    def _mix_call(self, form: str, arena, arena_samples: int, items, N: int, rest, rir, pt):
+        """nww_mix<form>, nww_mix_rir<form> or nww_mix_aug<form> - the first that takes the tables given; `rest` are the call's arguments
+        behind N"""
+        head = [self._h, arena, int(arena_samples)]
+        tabs = [items.ctypes.data_as(C.c_void_p)]
+        if rir is not None or pt is not None:
+            head += list(rir[:3]) if rir is not None else [None, 0, 0]
+            tabs.append(rir[3].ctypes.data_as(C.c_void_p) if rir is not None else None)
+        if pt is not None:
+            tabs.append(pt.ctypes.data_as(C.c_void_p))
+        fn = getattr(self.lib, "nww_mix" + ("_aug" if pt is not None else "_rir" if rir is not None else "") + form)
+        self._check(fn(*head, *tabs, len(items), int(N), *rest))
+
+    def mix_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, stream: int = 0, irs=None, ir_ids=None, pitch=None,
+                pitch_ids=None):
         """Raw device pointers; `items` is a host table of augment.MIX_ITEM.  int16 out [B, N]; enqueues on `stream`, does not synchronise.
-        With `irs` (an augment.IrArena) and `ir_ids` every clip with an id >= 0 is convolved with that response (nww_mix_rir_dev)."""
+        With `irs` (an augment.IrArena) and `ir_ids` every clip with an id >= 0 is convolved with that response (nww_mix_rir_dev); with
+        `pitch` (an augment.PitchBank) and `pitch_ids` every clip with an id >= 0 is shifted by that ratio first (nww_mix_aug_dev)."""
         from .augment import as_items
         items = as_items(items)
         st = C.c_void_p(stream) if stream else None
-        rir = self._rir_args(irs, ir_ids, len(items), N)
-        if rir is None:
-            self._check(self.lib.nww_mix_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items), int(N),
-                                             C.c_void_p(out_ptr), st))
-        else:
-            self._check(self.lib.nww_mix_rir_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), rir[0], rir[1], rir[2],
-                                                 items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), len(items), int(N),
-                                                 C.c_void_p(out_ptr), st))
+        rir, pt = self._rir_args(irs, ir_ids, len(items), N), self._pitch_args(pitch, pitch_ids, len(items))
+        self._mix_call("_dev", C.c_void_p(arena_ptr), arena_samples, items, N, [C.c_void_p(out_ptr), st], rir, pt)
 
     def forward_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, logits_ptr: int, probs_ptr: int = 0, stream: int = 0, irs=None,
-                          ir_ids=None):
+                          ir_ids=None, pitch=None, pitch_ids=None):
         """mix_dev into the handle's PCM staging, then forward_pcm_dev's path on it; does not synchronise."""
         from .augment import as_items
         items = as_items(items)
         st, pp = C.c_void_p(stream) if stream else None, C.c_void_p(probs_ptr) if probs_ptr else None
-        rir = self._rir_args(irs, ir_ids, len(items), N)
-        if rir is None:
-            self._check(self.lib.nww_mix_forward_pcm_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
-                                                         int(N), C.c_void_p(logits_ptr), pp, st))
-        else:
-            self._check(self.lib.nww_mix_rir_forward_pcm_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), rir[0], rir[1], rir[2],
-                                                             items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), len(items), int(N),
-                                                             C.c_void_p(logits_ptr), pp, st))
+        rir, pt = self._rir_args(irs, ir_ids, len(items), N), self._pitch_args(pitch, pitch_ids, len(items))
+        self._mix_call("_forward_pcm_dev", C.c_void_p(arena_ptr), arena_samples, items, N, [C.c_void_p(logits_ptr), pp, st], rir, pt)
 
     def frontend_mixed_dev(self, arena_ptr: int, arena_samples: int, items, N: int, out_ptr: int, frames_major: bool = False, stream: int = 0,
-                           irs=None, ir_ids=None):
+                           irs=None, ir_ids=None, pitch=None, pitch_ids=None):
         """mix_dev into the handle's PCM staging, then frontend_dev's path on it; does not synchronise."""
         from .augment import as_items
         items = as_items(items)
         st = C.c_void_p(stream) if stream else None
-        rir = self._rir_args(irs, ir_ids, len(items), N)
-        if rir is None:
-            self._check(self.lib.nww_mix_frontend_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), items.ctypes.data_as(C.c_void_p), len(items),
-                                                      int(N), C.c_void_p(out_ptr), int(frames_major), st))
-        else:
-            self._check(self.lib.nww_mix_rir_frontend_dev(self._h, C.c_void_p(arena_ptr), int(arena_samples), rir[0], rir[1], rir[2],
-                                                          items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), len(items), int(N),
-                                                          C.c_void_p(out_ptr), int(frames_major), st))
+        rir, pt = self._rir_args(irs, ir_ids, len(items), N), self._pitch_args(pitch, pitch_ids, len(items))
+        self._mix_call("_frontend_dev", C.c_void_p(arena_ptr), arena_samples, items, N, [C.c_void_p(out_ptr), int(frames_major), st], rir, pt)
 
-    def mix(self, arena, items, N: int, irs=None, ir_ids=None) -> np.ndarray:
+    def mix(self, arena, items, N: int, irs=None, ir_ids=None, pitch=None, pitch_ids=None) -> np.ndarray:
         """The clips of `items` (augment.mix_items / draw_mix_items) mixed out of `arena` -> int16 [B, N].  A device-resident
         augment.ClipArena is read where it lies; a host arena (ClipArena(device=None) or an int16 array) is uploaded by the call.
-        `irs` (an augment.IrArena) and `ir_ids` (augment.draw_rir_ids; -1: none) send clips through impulse responses."""
+        `irs` (an augment.IrArena) and `ir_ids` (augment.draw_rir_ids; -1: none) send clips through impulse responses; `pitch` (an
+        augment.PitchBank) and `pitch_ids` (augment.draw_pitch_ids; -1: none) shift them in pitch before that."""
         from .augment import as_items
         items = as_items(items)
         B, N = len(items), int(N)
-        rir = self._rir_args(irs, ir_ids, B, N)
+        rir, pt = self._rir_args(irs, ir_ids, B, N), self._pitch_args(pitch, pitch_ids, B)
         host = arena if isinstance(arena, np.ndarray) else arena.host
         if host is not None:
             if host.dtype != np.int16 or host.ndim != 1:
                 raise ValueError("a host arena must be a one-dimensional int16 array")
             host = np.ascontiguousarray(host)
             out = np.empty((B, max(N, 0)), np.int16)
-            if rir is None:
-                self._check(self.lib.nww_mix(self._h, host.ctypes.data_as(C.c_void_p), host.size, items.ctypes.data_as(C.c_void_p), B, N,
-                                             out.ctypes.data_as(C.c_void_p)))
-            else:
-                self._check(self.lib.nww_mix_rir(self._h, host.ctypes.data_as(C.c_void_p), host.size, rir[0], rir[1], rir[2],
-                                                 items.ctypes.data_as(C.c_void_p), rir[3].ctypes.data_as(C.c_void_p), B, N,
-                                                 out.ctypes.data_as(C.c_void_p)))
+            self._mix_call("", host.ctypes.data_as(C.c_void_p), host.size, items, N, [out.ctypes.data_as(C.c_void_p)], rir, pt)
             return out
         import torch
         out = torch.empty((B, max(N, 0)), dtype=torch.int16, device=f"cuda:{self.device}")
-        self.mix_dev(arena.ptr, arena.samples, items, N, out.data_ptr(), irs=irs, ir_ids=ir_ids)
+        self.mix_dev(arena.ptr, arena.samples, items, N, out.data_ptr(), irs=irs, ir_ids=ir_ids, pitch=pitch, pitch_ids=pitch_ids)
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy()
 
-    def forward_mixed(self, arena, items, N: int, irs=None, ir_ids=None):
+    def forward_mixed(self, arena, items, N: int, irs=None, ir_ids=None, pitch=None, pitch_ids=None):
         """(logits [B], probs [B]) of the clips mix() gives, bit-identical to forward_pcm(mix(arena, items, N)); the clips stay on the device."""
         import torch
         from .augment import as_items
         items = as_items(items)
         out = torch.zeros((2, len(items)), dtype=torch.float32, device=f"cuda:{self.device}")
-        self.forward_mixed_dev(arena.ptr, arena.samples, items, N, out[0].data_ptr(), out[1].data_ptr(), irs=irs, ir_ids=ir_ids)
+        self.forward_mixed_dev(arena.ptr, arena.samples, items, N, out[0].data_ptr(), out[1].data_ptr(), irs=irs, ir_ids=ir_ids, pitch=pitch,
+                               pitch_ids=pitch_ids)
         torch.cuda.synchronize(self.device)
         res = out.cpu().numpy()
         return res[0].copy(), res[1].copy()
@@ -1150,15 +1163,17 @@ class HipSession:
         return logits.reshape(-1, 1)
 
     # clips mixed on the device out of an augment.ClipArena (HipModel.mix / forward_mixed): clips of clip_samples
-    def mix(self, arena, items, irs=None, ir_ids=None) -> np.ndarray:
-        """int16 [B, clip_samples]: the clips of `items` mixed out of `arena` (irs / ir_ids: through impulse responses, HipModel.mix)"""
-        return self.model.mix(arena, items, self.clip_samples, irs=irs, ir_ids=ir_ids)
+    def mix(self, arena, items, irs=None, ir_ids=None, pitch=None, pitch_ids=None) -> np.ndarray:
+        """int16 [B, clip_samples]: the clips of `items` mixed out of `arena` (irs / ir_ids: through impulse responses, pitch / pitch_ids:
+        shifted in pitch; HipModel.mix)"""
+        return self.model.mix(arena, items, self.clip_samples, irs=irs, ir_ids=ir_ids, pitch=pitch, pitch_ids=pitch_ids)
 
-    def forward_mixed(self, arena, items, irs=None, ir_ids=None):
+    def forward_mixed(self, arena, items, irs=None, ir_ids=None, pitch=None, pitch_ids=None):
         """[probabilities (B,1,1)] as run() returns them for mix(arena, items), the clips never leaving the device"""
         if self.mode != "e2e":
             raise ValueError("forward_mixed needs an e2e session (raw PCM in)")
-        return [self.model.forward_mixed(arena, items, self.clip_samples, irs=irs, ir_ids=ir_ids)[1].reshape(-1, 1, 1)]
+        return [self.model.forward_mixed(arena, items, self.clip_samples, irs=irs, ir_ids=ir_ids, pitch=pitch,
+                                         pitch_ids=pitch_ids)[1].reshape(-1, 1, 1)]
 
     # a pool of streams on the session's model (interpreter.StreamPool takes a session as its backend): windows of clip_samples
     def stream_open(self, n_streams: int, window_samples: Optional[int] = None, hop_samples: int = 1280):

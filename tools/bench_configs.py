@@ -20,7 +20,9 @@ the same chain in torch ops (mix_main) -> profiles/mix_bench_configs.jsonl.
 --mix-rir [out]: the same clips through room impulse responses (nww_mix_rir_*) alone and in front of the CNN head, against the calls
 without responses and against torch.fft.rfft / irfft plus the tail on the same card (mix_rir_main) -> profiles/mix_rir_bench_configs.jsonl.
 --mix-rir-seg [out]: the same protocol at clips of 2 s on the segmented route (NWW_RIR_SEGMENTED), with --mix-rir's one-workgroup route in
-the same session as the per-transform yardstick (mix_rir_seg_main) -> profiles/mix_rir_seg_bench_configs.jsonl."""
+the same session as the per-transform yardstick (mix_rir_seg_main) -> profiles/mix_rir_seg_bench_configs.jsonl.
+--mix-pitch [out]: half of --mix's clips shifted in pitch (nww_mix_aug_*) alone and in front of the CNN head, against the calls without
+a shift and against the same definition in torch ops on the same card (mix_pitch_main) -> profiles/mix_pitch_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -1263,6 +1265,151 @@ def mix_rir_main(out_path):
     sys.stdout.write(text)
 
 
+def torch_pitch_shift(torch, y, p, q, win, taps):
+    """The definition of nww_mix_aug_*'s pitch shift (include/nww.h) in float32 torch ops on a batch y [b, N] at ONE ratio p / q:
+    torch.stft, the textbook vocoder (angle, wrap, cumsum, polar), torch.istft, and the resampler as one conv1d of q output channels -
+    channel phi holds phase phi's taps behind (phi p) div q zeros - at stride p, the channels interleaved.  taps: float32 [q, 16]."""
+    F = torch.nn.functional
+    b, N = y.shape
+    X = torch.stft(y, 512, 128, window=win, center=True, pad_mode="reflect", return_complex=True)       # [b, 257, T]
+    T = X.shape[2]
+    T_out = -(-T * p // q)
+    t = torch.arange(T_out, device=y.device)
+    i, alpha = (t * q) // p, ((t * q) % p).to(torch.float32) / p
+    Xz = F.pad(X, (0, 2))
+    X0, X1 = Xz[:, :, i], Xz[:, :, i + 1]
+    mag = alpha * X1.abs() + (1.0 - alpha) * X0.abs()
+    adv = torch.linspace(0, np.pi * 128, 257, device=y.device)[None, :, None]
+    d = X1.angle() - X0.angle() - adv
+    d = d - 2 * np.pi * torch.round(d / (2 * np.pi)) + adv
+    phase = torch.cumsum(torch.cat([X[:, :, :1].angle(), d[:, :, :-1]], dim=2), dim=2)
+    s = torch.istft(torch.polar(mag, phase), 512, 128, window=win, center=True)                       # [b, 128 (T_out - 1)]
+    S = s.shape[1]
+    a = (torch.arange(q) * p) // q
+    w = torch.zeros((q, 1, p + 16), dtype=torch.float32, device=y.device)
+    for phi in range(q):
+        w[phi, 0, int(a[phi]):int(a[phi]) + 16] = taps[phi]
+    m = -(-N // q)
+    need = (m - 1) * p + p + 16
+    sp = F.pad(s, (7, max(need - S - 7, 0)))[:, None, :]
+    out = F.conv1d(sp, w, stride=p)[:, :, :m].transpose(1, 2).reshape(b, -1)[:, :N]
+    Ly = -(-S * q // p)
+    if Ly < N:
+        out = torch.cat([out[:, :Ly], torch.zeros((b, N - Ly), dtype=out.dtype, device=out.device)], dim=1)
+    return out
+
+
+def mix_pitch_child():
+    """One process: mix_child's arena and table; half the clips draw one of 64 of augment.pitch_ratios() (the 64 nearest 1 of its 72: a
+    model holds at most 64), as the reference shifts half its clips.  ms per call as the median of RNN_STEPS device-event timings behind
+    RNN_WARMUP warm-up calls, every leg on one stream: (a) mix_dev with the ratios alone, (b) forward_mixed_dev with them, (r)
+    forward_mixed_dev and mix_dev without, (s) forward_pcm_dev on the resident clips, (d) the same definition in torch ops on the same
+    card on a resident float32 batch of the shifted clips, ratio by ratio (torch_pitch_shift), plus the peak / level / clamp / int16 tail
+    over the batch.  (d) starts from the int16 clips of (r) as floats, so its samples are not compared with (a)'s here: torch_pitch_shift is
+    the float32 yardstick of tests/pitch_oracle.py batched, and as far from the float64 definition as that yardstick is (1e-4 .. 2e-3 on
+    its clips, the float32 angle sums' error)."""
+    import torch
+    from nanowakeword_amd.augment import ClipArena, PitchBank, draw_mix_items, draw_pitch_ids, pitch_ratios
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel, torchaudio_tables
+    from nanowakeword_amd.synth import synth_pcm, synth_state_dict
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pitch_oracle
+    dev = torch.device("cuda", 0)
+    fe = FrontendConfig()
+    window, fb = torchaudio_tables(fe)
+    cfg = HeadConfig("cnn", (101, 64))
+    m = HipModel(cfg, fe, device=0, state_dict=synth_state_dict(cfg), window=window, mel_fb=fb)
+    rng = np.random.default_rng(7)
+    fg_len = rng.integers(MIX_N // 2, MIX_N + 1, 64)
+    bg_len = rng.integers(MIX_N, 10 * MIX_N + 1, 16)
+    clips = [synth_pcm("speechlike", 1, int(n), seed=100 + k)[0] for k, n in enumerate(fg_len)] + \
+            [synth_pcm("noise", 1, int(n), seed=200 + k)[0] for k, n in enumerate(bg_len)]
+    arena = ClipArena(clips, device=0)
+    items = draw_mix_items(rng, arena, rng.integers(0, 64, MIX_B), 64 + np.arange(16), MIX_N)
+    ratios = sorted(sorted(pitch_ratios(), key=lambda r: abs(np.log(r[0] / r[1])))[:64], key=lambda r: r[0] / r[1])
+    bank = PitchBank(ratios).prepare(m)
+    ids = draw_pitch_ids(rng, len(ratios), MIX_B, 0.5)
+    B, N = MIX_B, MIX_N
+    ts = torch.cuda.Stream(dev)
+    stream = ts.cuda_stream
+    m.reserve(B, N)
+    pcm, plain = (torch.empty((B, N), dtype=torch.int16, device=dev) for _ in range(2))
+    lg, pr = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(2))
+    m.mix_dev(arena.ptr, arena.samples, items, N, plain.data_ptr(), stream)
+    torch.cuda.synchronize()
+    # (d)'s inputs, resident: the float32 clips, the rows of every ratio, its taps, the levels
+    y = plain.to(torch.float32) / 32768.0
+    win = torch.hann_window(512, periodic=True, device=dev)
+    groups = [(p, q, torch.from_numpy(np.flatnonzero(ids == k)).to(dev), torch.from_numpy(pitch_oracle.resample_table(p, q)).to(dev))
+              for k, (p, q) in enumerate(ratios) if (ids == k).any()]
+    level = torch.from_numpy(np.ascontiguousarray(items["level"])).to(dev)[:, None]
+
+    def torch_leg():
+        with torch.cuda.stream(ts), torch.no_grad():
+            w = y.clone()
+            for p, q, rows, taps in groups:
+                w[rows] = torch_pitch_shift(torch, y[rows], p, q, win, taps)
+            pk = w.abs().amax(1, keepdim=True)
+            pk = torch.where(pk < 1e-8, torch.ones_like(pk), pk)
+            return (torch.clamp(w * (level / pk), -1.0, 1.0) * 32767).to(torch.int16)
+    legs = {"mix_aug": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, pcm.data_ptr(), stream, pitch=bank, pitch_ids=ids),
+            "mix_aug_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream, pitch=bank,
+                                                           pitch_ids=ids),
+            "mix_forward": lambda: m.forward_mixed_dev(arena.ptr, arena.samples, items, N, lg.data_ptr(), pr.data_ptr(), stream),
+            "resident_forward": lambda: m.forward_pcm_dev(plain.data_ptr(), B, N, lg.data_ptr(), pr.data_ptr(), stream),
+            "mix": lambda: m.mix_dev(arena.ptr, arena.samples, items, N, plain.data_ptr(), stream),
+            "torch_pitch": torch_leg}
+    out = {"B": B, "N": N, "ratios": len(ratios), "shifted": int((ids >= 0).sum()), "ratios_drawn": len(groups)}
+    steps = {"torch_pitch": max(RNN_STEPS // 10, 5)}                    # hundreds of launches a call: fewer timed calls say the same
+    for name, step in legs.items():
+        for _ in range(RNN_WARMUP if name != "torch_pitch" else 2):
+            step()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps.get(name, RNN_STEPS))]
+        for e0, e1 in ev:
+            e0.record(ts); step(); e1.record(ts)
+        torch.cuda.synchronize()
+        out[name + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+    print(json.dumps(out), flush=True)
+    m.close()
+
+
+def mix_pitch_main(out_path):
+    """RNN_REPEATS fresh child processes, one after another, each under its own time limit; the medians of the repeats with their spread
+    (max - min over the repeats).  No claim is asserted: every ratio is written down as measured."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "400", sys.executable, os.path.abspath(__file__), "--mix-pitch-child"], env=dict(os.environ),
+                           cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"mix-pitch child exited {r.returncode}")
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][0])
+    names = ("mix_aug", "mix_aug_forward", "mix_forward", "resident_forward", "mix", "torch_pitch")
+    rep = {k: [r[k + "_ms"] for r in runs] for k in names}
+    med = {k: float(np.median(v)) for k, v in rep.items()}
+    first = runs[0]
+    line = {"config": f"mix-pitch B={MIX_B} N={MIX_N}, half the clips shifted by one of {first['ratios']} ratios within +-2 semitones, cnn 101x64",
+            "B": MIX_B, "N": MIX_N, "shifted": first["shifted"], "ratios": first["ratios"], "ratios_drawn": first["ratios_drawn"],
+            "warmup": RNN_WARMUP, "steps": RNN_STEPS, "repeats": RNN_REPEATS, "ms_repeats": rep,
+            "spread_ms": {k: round(max(v) - min(v), 4) for k, v in rep.items()},
+            "mix_aug_ms": round(med["mix_aug"], 4), "mix_ms": round(med["mix"], 4), "mix_aug_over_mix": round(med["mix_aug"] / med["mix"], 1),
+            "pitch_us_per_shifted_clip": round((med["mix_aug"] - med["mix"]) / first["shifted"] * 1e3, 3),
+            "torch_pitch_ms": round(med["torch_pitch"], 4), "torch_pitch_over_mix_aug": round(med["torch_pitch"] / med["mix_aug"], 2),
+            "mix_aug_forward_ms": round(med["mix_aug_forward"], 4), "mix_forward_ms": round(med["mix_forward"], 4),
+            "resident_forward_ms": round(med["resident_forward"], 4),
+            "pitch_over_mix_forward_ms": round(med["mix_aug_forward"] - med["mix_forward"], 4),
+            "mix_aug_forward_over_resident_forward": round(med["mix_aug_forward"] / med["resident_forward"], 2),
+            "torch_pitch_steps": max(RNN_STEPS // 10, 5),
+            "clips_per_s": {k: round(MIX_B / (med[k] * 1e-3)) for k in ("mix_aug", "mix_aug_forward", "mix_forward", "resident_forward")}}
+    text = json.dumps(line) + "\n"
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 MIX_SEG_N = 32000             # the reference's shortest clip (transform_clips.py: min_allowable_length)
 
 
@@ -1396,6 +1543,11 @@ def mix_rir_seg_main(out_path):
 
 
 def main():
+    if "--mix-pitch-child" in sys.argv[1:]:
+        return mix_pitch_child()
+    if "--mix-pitch" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--mix-pitch"]
+        return mix_pitch_main(rest[0] if rest else os.path.join(ROOT, "profiles", "mix_pitch_bench_configs.jsonl"))
     if "--mix-rir-seg-child" in sys.argv[1:]:
         return mix_rir_seg_child()
     if "--mix-rir-seg" in sys.argv[1:]:
