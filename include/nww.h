@@ -538,6 +538,59 @@ extern int nww_mix_aug_frontend_dev(nww_handle* h, const int16_t* d_arena, int64
                                     int32_t M, const nww_mix_item* items, const nww_rir_item* rir_items, const nww_pitch_item* pitch_items,
                                     int32_t B, int32_t N, float* d_logmel, int32_t frames_major, void* stream);
 
+/* ---- recordings at their own sample rate brought to the target rate (csrc/resample.hip, csrc/resample_plan.h) ------
+ * The reference resamples and downmixes on every path into 16 kHz mono: torchaudio.transforms.Resample(clip_sr, 16000), then the mean
+ * over the channels (augment_clips.py:31-43, transform_clips.py:65-93, utils/audio_preprocess.py:55-90).  What is restated is a
+ * DEFINITION of that resampler's construction - sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99 - not the library's samples.
+ * A recording has L frames of C interleaved channels at rate fs; the target rate is ft; g = gcd(fs, ft), p = fs / g, q = ft / g
+ * (p / q > 1 lowers the rate).
+ *   downmix    m[k] = (0.0f + c_0[k] + .. + c_{C-1}[k]) / (float)C: channels in ascending order, one correctly rounded division; C = 1
+ *              is the sample itself.  The reference takes the mean after resampling: equal in exact arithmetic (both are linear).
+ *   resample   M = ceil(L q / p) outputs; output n sits at input position n p / q:
+ *              v[n] = 0.0f + sum over ascending j of m[k0 + j] g[phase][j],  phase = n mod q,  k0 = (n div q) p + (phase p) div q + j0,
+ *              taps with k0 + j outside [0, L) left out; every product and sum rounded on its own
+ *   taps       g[phase][j] = c sinc(c x) cos^2(pi c x / 12) where |c x| < 6 and an exact 0 elsewhere, x = frac - (j0 + j),
+ *              frac = ((phase p) mod q) / q, c = 0.99 min(1, q / p); float64, rounded once.  j0 = 1 - ceil(6 / c), 2 ceil(6 / c) taps a
+ *              phase (ceil(6 / c) in integers: ceil(200 p / (33 q)) where p > q, 7 otherwise): 38 at 3/1, 34 at 441/160, 18 at 441/320
+ *   formats    source NWW_PCM_S16 (the float of its value) or NWW_PCM_F32 (as given; a non-finite sample is the caller's business).
+ *              Destination F32: v 2^-15 from an S16 source (exact), v from an F32 source - the units torchaudio.load gives.
+ *              Destination S16: (int16) rint(clamp(u, -32768, 32767)), nearest even, u = v from an S16 source and v 32768 from an F32
+ *              source: a full-scale square wave overshoots to 37 708 at 48 k -> 16 k and comes out as 32 767, never wrapped
+ *   rate_id -1 the recording is already at the target rate: downmixed and converted only (the reference's `if clip_sr != sr`), no filter
+ * The float32 arithmetic is fixed in csrc/resample_plan.h (restated in tests/resample_oracle.py): the same bits on the host and the
+ * device, at any B and any place in the table.
+ * The ratios a table's rate_id names are set once on the handle: terms in [1, 1024], 1/4 <= num / den <= 12, K <= 16 (K = 0 clears
+ * them); the tables are built on the host and uploaded, the call waits for the device.  They are separate from the pitch ratios.
+ * A call takes a HOST table of B items (reusable once it returns) through a slot of the handle, as the mixing calls do.  Rules, checked
+ * on the host for EVERY item before anything is enqueued - a failing call launches nothing, takes no slot, leaves the ratios alone and
+ * returns NWW_ERR_INVALID with the item's index and the field's name in nww_last_error:
+ *   ratios set unless every rate_id is -1;  1 <= src_frames <= 2^30;  1 <= channels <= 8;  [src_off, src_off + src_frames channels)
+ *   inside src_values;  rate_id in [-1, K);  reserved == 0;  both formats known;  [dst_off, dst_off + len) inside dst_values, len the
+ *   item's outputs;  destination ranges ascending and disjoint across the table (dst_off[i] >= dst_off[i - 1] + len[i - 1]): no two
+ *   workgroups write one sample.
+ * B == 0 returns NWW_OK and does nothing.  The handle must be finalized.                                                             */
+#define NWW_PCM_S16 0
+#define NWW_PCM_F32 1
+typedef struct nww_resample_item {
+    int64_t src_off;                   /* first value of the recording in the source buffer (values, not frames)          */
+    int64_t dst_off;                   /* first output in the destination buffer                                         */
+    int32_t src_frames;                /* L                                                                              */
+    int32_t channels;                  /* C, interleaved                                                                 */
+    int32_t rate_id;                   /* the ratio, or -1: already at the target rate                                   */
+    uint32_t reserved;                 /* 0; 32 bytes, no implicit padding                                               */
+} nww_resample_item;
+extern int nww_resample_set_ratios(nww_handle* h, const int32_t* num, const int32_t* den, int32_t K);
+/* ceil(frames den / num); 0 for bad arguments (frames outside [1, 2^30], a ratio out of range)                                       */
+extern int64_t nww_resample_length(int64_t frames, int32_t num, int32_t den);
+/* d_src [src_values] of src_format, items [B] (host) -> d_dst [dst_values] of dst_format; asynchronous on `stream` (NULL: the
+   handle's own)                                                                                                                      */
+extern int nww_resample_dev(nww_handle* h, const void* d_src, int64_t src_values, int32_t src_format, const nww_resample_item* items, int32_t B,
+                            void* d_dst, int64_t dst_values, int32_t dst_format, void* stream);
+/* host pointers: the source is uploaded, the items' destination ranges are downloaded (what lies between them is left alone);
+   synchronises before it returns                                                                                                     */
+extern int nww_resample(nww_handle* h, const void* src, int64_t src_values, int32_t src_format, const nww_resample_item* items, int32_t B,
+                        void* dst, int64_t dst_values, int32_t dst_format);
+
 /* ---- embedding-mode preprocessor state on the device (S lock-step streams) -------------------------------
  * Replaces the buffers and windowing of nanowakeword/data/AudioFeatures.py around its two ONNX models
  * (melspectrogram.onnx / embedding_model.onnx: un-vendored release binaries, pluggable here - the caller runs

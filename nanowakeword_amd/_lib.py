@@ -57,6 +57,7 @@ SYMBOLS = [
     "nww_rir_fft_size", "nww_rir_prepare_dev", "nww_mix_rir_dev", "nww_mix_rir", "nww_mix_rir_forward_pcm_dev", "nww_mix_rir_frontend_dev",
     "nww_rir_parts", "nww_rir_spectra_floats",
     "nww_pitch_set_ratios", "nww_mix_aug_dev", "nww_mix_aug", "nww_mix_aug_forward_pcm_dev", "nww_mix_aug_frontend_dev",
+    "nww_resample_set_ratios", "nww_resample_length", "nww_resample_dev", "nww_resample",
 ]
 
 
@@ -209,6 +210,11 @@ def load_library():
     lib.nww_mix_aug_forward_pcm_dev.restype = C.c_int
     lib.nww_mix_aug_frontend_dev.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp]
     lib.nww_mix_aug_frontend_dev.restype = C.c_int
+    # recordings brought to the target rate: ratios set once on the handle, `items` a host table (augment.RESAMPLE_ITEM)
+    lib.nww_resample_set_ratios.argtypes = [vp, vp, vp, i32]; lib.nww_resample_set_ratios.restype = C.c_int
+    lib.nww_resample_length.argtypes = [i64, i32, i32]; lib.nww_resample_length.restype = i64
+    lib.nww_resample_dev.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, i32, vp]; lib.nww_resample_dev.restype = C.c_int
+    lib.nww_resample.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, i32]; lib.nww_resample.restype = C.c_int
     _lib = lib
     return lib
 

@@ -16,6 +16,11 @@ Pitch shift (``PitchShift(+-2 semitones, p=0.5)`` between Gain and ApplyImpulseR
 every call takes ``pitch=..., pitch_ids=...``.  What is restated is a DEFINITION of the library's construction - a phase vocoder without
 phase scaling, then a windowed-sinc resampler, at rational ratios - not ``torch_audiomentations``' samples: the transform length (512),
 hop (128) and window (periodic Hann) are this project's own (include/nww.h).
+
+Recordings that are not 16 kHz mono yet (``torchaudio.transforms.Resample(clip_sr, 16000)`` and the mean over the channels on every path
+into the reference's clips, augment_clips.py:31-43) are downmixed and resampled on the device as well:
+``ClipArena.from_recordings`` builds the arena out of arrays at their own rates, ``HipModel.resample`` returns them to the host -
+float32 for an ``IrArena`` - and ``resample_ratio`` / ``resampled_length`` say what a rate pair comes to.
 """
 from __future__ import annotations
 
@@ -61,6 +66,39 @@ class ClipArena:
 
     def __len__(self) -> int:
         return len(self.lengths)
+
+    @classmethod
+    def from_recordings(cls, model, recordings: Sequence[np.ndarray], rates: Sequence[int], dst_hz: int = 16000, device: int = 0,
+                        chunk_bytes: int = 64 << 20) -> "ClipArena":
+        """An arena on the device out of recordings at their own sample rates: arrays [frames] or [frames, channels], int16 or float32
+        (units of full scale), each with its rate in `rates`.  The sources go up in chunks of at most `chunk_bytes` and `model` (a
+        HipModel on `device`) downmixes and resamples them straight into the arena's buffer (nww_resample_dev): offsets
+        and lengths come from ``resampled_length``, and the host never sees the resampled audio.  A recording at `dst_hz` is downmixed
+        and converted only."""
+        import torch
+        if device is None or int(device) != int(model.device):
+            raise ValueError("from_recordings resamples on the device: `device` must be the model's")
+        recs, lengths, chunks = resample_plan(recordings, rates, dst_hz, chunk_bytes)
+        self = cls.__new__(cls)
+        self.lengths = lengths
+        self.offsets = np.concatenate(([0], np.cumsum(lengths)[:-1])).astype(np.int64)
+        self.samples = int(lengths.sum())
+        self.device, self.host = device, None
+        dev = f"cuda:{int(device)}"
+        self._dev = torch.empty((self.samples,), dtype=torch.int16, device=dev)
+        self.ptr = int(self._dev.data_ptr())
+        for ch in chunks:
+            src = np.concatenate([r.ravel() for r in recs[ch["lo"]:ch["hi"]]])
+            d_src = torch.from_numpy(src).to(dev)
+            items = ch["items"].copy()
+            items["dst_off"] = self.offsets[ch["lo"]:ch["hi"]]
+            if ch["ratios"]:
+                model.resample_set_ratios([a for a, _ in ch["ratios"]], [b for _, b in ch["ratios"]])
+            torch.cuda.synchronize(int(device))                     # the upload has landed: the call runs on the model's own stream
+            model.resample_dev(d_src.data_ptr(), src.size, ch["format"], items, self.ptr, self.samples, PCM_S16)
+            torch.cuda.synchronize(int(device))                     # the chunk's source is released below
+            del d_src
+        return self
 
 
 def as_items(items) -> np.ndarray:
@@ -355,6 +393,95 @@ def draw_pitch_ids(rng: np.random.Generator, n_ratios: int, B: int, pitch_prob: 
         return np.full(B, -1, np.int32)
     on = rng.random(B) < float(pitch_prob)
     return np.where(on, rng.integers(0, int(n_ratios), B), -1).astype(np.int32)
+
+
+# ---- recordings at their own sample rate (nww_resample_*)
+# struct nww_resample_item (include/nww.h), field for field: 32 bytes
+RESAMPLE_ITEM = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("src_frames", "<i4"), ("channels", "<i4"), ("rate_id", "<i4"), ("reserved", "<u4")])
+RESAMPLE_TILE = 1024          # outputs a workgroup produces per tile (csrc/resample_plan.h)
+RESAMPLE_MAX_TERM = 1024      # a ratio's numerator and denominator
+RESAMPLE_MAX_RATIOS = 16      # the ratios a model holds at a time
+RESAMPLE_MAX_FRAMES = 1 << 30
+RESAMPLE_MAX_CHANNELS = 8
+PCM_S16, PCM_F32 = 0, 1       # NWW_PCM_S16, NWW_PCM_F32
+
+
+def resample_ratio_ok(num: int, den: int) -> bool:
+    """what nww_resample_set_ratios accepts: terms in [1, 1024] and 1/4 <= num / den <= 12, decided in integers"""
+    num, den = int(num), int(den)
+    return 1 <= num <= RESAMPLE_MAX_TERM and 1 <= den <= RESAMPLE_MAX_TERM and den <= 4 * num and num <= 12 * den
+
+
+def resample_ratio(src_hz: int, dst_hz: int = 16000):
+    """(p, q) = (src_hz, dst_hz) / gcd - 48000 -> (3, 1), 44100 -> (441, 160), 22050 -> (441, 320) - or None when the rates are equal"""
+    from math import gcd
+    s, d = int(src_hz), int(dst_hz)
+    if s != src_hz or d != dst_hz or s < 1 or d < 1:
+        raise ValueError("sample rates must be positive integers")
+    if s == d:
+        return None
+    g = gcd(s, d)
+    p, q = s // g, d // g
+    if not resample_ratio_ok(p, q):
+        raise ValueError(f"{s} Hz -> {d} Hz is {p} / {q}: out of range (terms in [1, {RESAMPLE_MAX_TERM}], 1/4 <= ratio <= 12)")
+    return p, q
+
+
+def resampled_length(frames: int, src_hz: int, dst_hz: int = 16000) -> int:
+    """the frames a recording has at dst_hz: ceil(frames q / p), as nww_resample_length; `frames` itself when the rates are equal"""
+    r = resample_ratio(src_hz, dst_hz)
+    frames = int(frames)
+    if frames < 1 or frames > RESAMPLE_MAX_FRAMES:
+        raise ValueError(f"a recording has between 1 and 2^30 frames (got {frames})")
+    return frames if r is None else -(-frames * r[1] // r[0])
+
+
+def as_resample_items(items) -> np.ndarray:
+    """a contiguous one-dimensional RESAMPLE_ITEM table"""
+    if not isinstance(items, np.ndarray) or items.dtype != RESAMPLE_ITEM or items.ndim != 1:
+        raise ValueError("items must be a one-dimensional array of augment.RESAMPLE_ITEM")
+    return np.ascontiguousarray(items)
+
+
+def resample_plan(recordings: Sequence[np.ndarray], rates: Sequence[int], dst_hz: int = 16000, chunk_bytes: int = 64 << 20):
+    """What HipModel.resample and ClipArena.from_recordings send: (the recordings as contiguous [frames, channels] arrays, their lengths
+    at dst_hz as int64, the chunks).  A chunk is a run of consecutive recordings [lo, hi) of one sample format, of at most chunk_bytes
+    of source (a longer recording goes alone) and at most RESAMPLE_MAX_RATIOS different ratios: a dict of lo, hi, format, ratios
+    [(p, q)] and items - a RESAMPLE_ITEM table whose src_off count from the chunk's first value and whose dst_off pack the chunk's
+    outputs back to back from 0."""
+    if len(recordings) != len(rates):
+        raise ValueError("one rate per recording")
+    if len(recordings) == 0:
+        raise ValueError("at least one recording is needed")
+    recs, lens, ratios = [], [], []
+    for i, (x, hz) in enumerate(zip(recordings, rates)):
+        if not isinstance(x, np.ndarray) or x.dtype not in (np.int16, np.float32) or x.ndim not in (1, 2) or x.shape[0] == 0:
+            raise ValueError(f"recording {i} must be a non-empty int16 or float32 array of shape [frames] or [frames, channels]")
+        x = np.ascontiguousarray(x.reshape(x.shape[0], -1))
+        if not 1 <= x.shape[1] <= RESAMPLE_MAX_CHANNELS:
+            raise ValueError(f"recording {i} has {x.shape[1]} channels: between 1 and {RESAMPLE_MAX_CHANNELS} are taken")
+        recs.append(x)
+        lens.append(resampled_length(x.shape[0], hz, dst_hz))
+        ratios.append(resample_ratio(hz, dst_hz))
+    chunks, lo = [], 0
+    while lo < len(recs):
+        hi, size, rs = lo, 0, []
+        while hi < len(recs) and recs[hi].dtype == recs[lo].dtype and (hi == lo or size + recs[hi].nbytes <= int(chunk_bytes)):
+            if ratios[hi] is not None and ratios[hi] not in rs:
+                if len(rs) == RESAMPLE_MAX_RATIOS:
+                    break
+                rs.append(ratios[hi])
+            size += recs[hi].nbytes
+            hi += 1
+        t = np.zeros(hi - lo, RESAMPLE_ITEM)
+        t["src_frames"] = [r.shape[0] for r in recs[lo:hi]]
+        t["channels"] = [r.shape[1] for r in recs[lo:hi]]
+        t["src_off"] = np.concatenate(([0], np.cumsum([r.size for r in recs[lo:hi]])[:-1]))
+        t["dst_off"] = np.concatenate(([0], np.cumsum(lens[lo:hi])[:-1]))
+        t["rate_id"] = [-1 if r is None else rs.index(r) for r in ratios[lo:hi]]
+        chunks.append({"lo": lo, "hi": hi, "format": PCM_F32 if recs[lo].dtype == np.float32 else PCM_S16, "ratios": rs, "items": t})
+        lo = hi
+    return recs, np.array(lens, np.int64), chunks
 
 
 class MixedClips:

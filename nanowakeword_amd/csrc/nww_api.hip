@@ -172,6 +172,7 @@ extern "C" int nww_destroy(nww_handle* h) {
     nww_cascade_free(h);
     nww_bank_free(h);
     nww_mix_free(h);
+    nww_resample_free(h);
     nww_comm_destroy(h);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);

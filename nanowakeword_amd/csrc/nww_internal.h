@@ -177,6 +177,7 @@ struct nww_handle {
     // points, grown on demand
     float* d_bank_out = nullptr; size_t bank_out_bytes = 0;
     struct MixState* mix = nullptr; // clip mixing (nww_mix.hip): the table slots and the host-pointer entry point's buffers, made by the first call
+    struct ResampleState* resample = nullptr;   // recordings brought to the target rate (nww_resample.hip): ratios, table slots, the host form's buffers
     void* comm = nullptr;          // ncclComm_t of this rank (nww_comm_init)
     unsigned char* pin_in = nullptr; unsigned char* pin_out = nullptr;   // pinned staging for small host-pointer calls
     bool pin_in_busy = false;                                            // an async copy out of pin_in may still be in flight
@@ -254,6 +255,7 @@ int nww_pool_push_on_dev(nww_handle* h, const int32_t* idx, int n, const int16_t
 void nww_cascade_free(nww_handle* h);          // nww_cascade.hip
 void nww_bank_free(nww_handle* h);             // nww_bank.hip
 void nww_mix_free(nww_handle* h);              // nww_mix.hip
+void nww_resample_free(nww_handle* h);         // nww_resample.hip
 void nww_build_spec(nww_handle* h);            // nww_weights.hip, as the next eight: what nww_finalize does to the loaded weights before it plans
 void balance_channel_gains(nww_handle* h);
 void fold_batchnorms(nww_handle* h);

@@ -472,6 +472,43 @@ class HipModel:
         res = out.cpu().numpy()
         return res[0].copy(), res[1].copy()
 
+    # ------------------------------------------------------------------ recordings at their own sample rate (nww_resample_*, augment.py)
+    def resample_set_ratios(self, num, den):
+        """nww_resample_set_ratios: the ratios num[k] / den[k] (source rate over target rate) a table's rate_id names, at most 16;
+        waits for the device"""
+        num, den = np.ascontiguousarray(num, np.int32), np.ascontiguousarray(den, np.int32)
+        if num.ndim != 1 or num.shape != den.shape:
+            raise ValueError("num and den must be one-dimensional and of one length")
+        self._check(self.lib.nww_resample_set_ratios(self._h, num.ctypes.data_as(C.c_void_p), den.ctypes.data_as(C.c_void_p), len(num)))
+
+    def resample_dev(self, src_ptr: int, src_values: int, src_format: int, items, dst_ptr: int, dst_values: int, dst_format: int, stream: int = 0):
+        """Raw device pointers; `items` is a host table of augment.RESAMPLE_ITEM, the formats are augment.PCM_S16 / PCM_F32.  Enqueues on
+        `stream`, does not synchronise."""
+        from .augment import as_resample_items
+        items = as_resample_items(items)
+        self._check(self.lib.nww_resample_dev(self._h, C.c_void_p(src_ptr), int(src_values), int(src_format), items.ctypes.data_as(C.c_void_p),
+                                              len(items), C.c_void_p(dst_ptr), int(dst_values), int(dst_format), C.c_void_p(stream) if stream else None))
+
+    def resample(self, recordings, rates, dst_hz: int = 16000, dtype=np.int16, chunk_bytes: int = 64 << 20):
+        """Recordings - arrays [frames] or [frames, channels], int16 or float32 in units of full scale, each with its sample rate in
+        `rates` - downmixed and brought to dst_hz on the device -> one host array per recording, int16 or (dtype=np.float32, what an
+        augment.IrArena takes) float32 in units of full scale.  A recording at dst_hz is downmixed and converted only."""
+        from .augment import PCM_F32, PCM_S16, resample_plan
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.int16), np.dtype(np.float32)):
+            raise ValueError("dtype must be int16 or float32")
+        recs, lengths, chunks = resample_plan(recordings, rates, dst_hz, chunk_bytes)
+        out = []
+        for ch in chunks:
+            src = np.concatenate([r.ravel() for r in recs[ch["lo"]:ch["hi"]]])
+            dst = np.empty(int(lengths[ch["lo"]:ch["hi"]].sum()), dtype)
+            if ch["ratios"]:
+                self.resample_set_ratios([a for a, _ in ch["ratios"]], [b for _, b in ch["ratios"]])
+            self._check(self.lib.nww_resample(self._h, src.ctypes.data_as(C.c_void_p), src.size, ch["format"], ch["items"].ctypes.data_as(C.c_void_p),
+                                              len(ch["items"]), dst.ctypes.data_as(C.c_void_p), dst.size, PCM_F32 if dtype == np.float32 else PCM_S16))
+            out += [dst[o:o + n].copy() for o, n in zip(ch["items"]["dst_off"].tolist(), lengths[ch["lo"]:ch["hi"]].tolist())]
+        return out
+
     # ------------------------------------------------------------------ batched streaming (rings on the device)
     def stream_open(self, n_streams: int, window_samples: int = 16000, hop_samples: int = 1280):
         self._check(self.lib.nww_stream_open(self._h, int(n_streams), int(window_samples), int(hop_samples)))

@@ -22,7 +22,10 @@ without responses and against torch.fft.rfft / irfft plus the tail on the same c
 --mix-rir-seg [out]: the same protocol at clips of 2 s on the segmented route (NWW_RIR_SEGMENTED), with --mix-rir's one-workgroup route in
 the same session as the per-transform yardstick (mix_rir_seg_main) -> profiles/mix_rir_seg_bench_configs.jsonl.
 --mix-pitch [out]: half of --mix's clips shifted in pitch (nww_mix_aug_*) alone and in front of the CNN head, against the calls without
-a shift and against the same definition in torch ops on the same card (mix_pitch_main) -> profiles/mix_pitch_bench_configs.jsonl."""
+a shift and against the same definition in torch ops on the same card (mix_pitch_main) -> profiles/mix_pitch_bench_configs.jsonl.
+--resample [out]: recordings brought to 16 kHz mono int16 (nww_resample_dev) - 4 096 mono clips of 1 s at 22 050 Hz, and 16 stereo
+recordings of 60 s at 48 kHz - against a device-to-device copy that moves the same bytes in the same run (resample_main) ->
+profiles/resample_bench_configs.jsonl."""
 import json
 import os
 import re
@@ -1410,6 +1413,89 @@ def mix_pitch_main(out_path):
     sys.stdout.write(text)
 
 
+RESAMPLE_CORPORA = (("tts", 4096, 22050, 22050, 1), ("backgrounds", 16, 60 * 48000, 48000, 2))      # (name, recordings, frames, Hz, channels)
+
+
+def resample_child():
+    """One process, both corpora of RESAMPLE_CORPORA in turn, int16 noise resident in HBM -> 16 kHz mono int16 in one table per corpus.
+    ms per call as the median of RNN_STEPS device-event timings behind RNN_WARMUP warm-up calls, both legs on one stream: (r)
+    nww_resample_dev - the host's checks and the table's upload are inside the call - and (c) a device-to-device copy of half the bytes
+    (r) reads and writes together, which therefore moves the same bytes."""
+    import torch
+    from nanowakeword_amd.augment import PCM_S16, RESAMPLE_ITEM, resample_ratio, resampled_length
+    from nanowakeword_amd.config import FrontendConfig, HeadConfig
+    from nanowakeword_amd.session import HipModel
+    from nanowakeword_amd.synth import synth_state_dict
+    dev = torch.device("cuda", 0)
+    cfg = HeadConfig("cnn", (101, 64))
+    m = HipModel(cfg, FrontendConfig(), device=0, state_dict=synth_state_dict(cfg))
+    ts = torch.cuda.Stream(dev)
+    stream = ts.cuda_stream
+    out = {}
+    for name, n, frames, hz, ch in RESAMPLE_CORPORA:
+        p, q = resample_ratio(hz)
+        m.resample_set_ratios([p], [q])
+        length = resampled_length(frames, hz)
+        items = np.zeros(n, RESAMPLE_ITEM)
+        items["src_off"], items["dst_off"] = np.arange(n, dtype=np.int64) * frames * ch, np.arange(n, dtype=np.int64) * length
+        items["src_frames"], items["channels"], items["rate_id"] = frames, ch, 0
+        src_values, dst_values = n * frames * ch, n * length
+        src = torch.randint(-20000, 20000, (src_values,), dtype=torch.int16, device=dev)
+        dst = torch.empty((dst_values,), dtype=torch.int16, device=dev)
+        moved = 2 * (src_values + dst_values)
+        a, b = (torch.empty((moved // 2,), dtype=torch.uint8, device=dev) for _ in range(2))
+
+        def copy_leg():
+            with torch.cuda.stream(ts):
+                b.copy_(a)
+        legs = {"resample": lambda: m.resample_dev(src.data_ptr(), src_values, PCM_S16, items, dst.data_ptr(), dst_values, PCM_S16, stream),
+                "copy": copy_leg}
+        row = {"recordings": n, "frames": frames, "hz": hz, "channels": ch, "ratio": [p, q], "outputs": dst_values, "bytes_moved": moved}
+        for leg, step in legs.items():
+            for _ in range(RNN_WARMUP):
+                step()
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RNN_STEPS)]
+            for e0, e1 in ev:
+                e0.record(ts); step(); e1.record(ts)
+            torch.cuda.synchronize()
+            row[leg + "_ms"] = round(float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])), 4)
+        out[name] = row
+        del src, dst, a, b
+    print(json.dumps(out), flush=True)
+    m.close()
+
+
+def resample_main(out_path):
+    """RNN_REPEATS fresh child processes, one after another, each under its own time limit; the medians of the repeats with their spread
+    (max - min over the repeats).  No claim is asserted: bytes over time for both legs, and the resampler's as a share of the copy's."""
+    import subprocess
+    runs = []
+    for _ in range(RNN_REPEATS):
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--resample-child"], env=dict(os.environ),
+                           cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"resample child exited {r.returncode}")
+        runs.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][0])
+    line = {"config": "resample to 16 kHz mono int16: 4096 mono clips of 1 s at 22050 Hz; 16 stereo recordings of 60 s at 48 kHz", "warmup": RNN_WARMUP,
+            "steps": RNN_STEPS, "repeats": RNN_REPEATS}
+    for name, *_ in RESAMPLE_CORPORA:
+        first = runs[0][name]
+        rep = {k: [r[name][k + "_ms"] for r in runs] for k in ("resample", "copy")}
+        med = {k: float(np.median(v)) for k, v in rep.items()}
+        line[name] = dict(first, ms_repeats=rep, spread_ms={k: round(max(v) - min(v), 4) for k, v in rep.items()},
+                          resample_ms=round(med["resample"], 4), copy_ms=round(med["copy"], 4),
+                          resample_bytes_per_s=round(first["bytes_moved"] / (med["resample"] * 1e-3)),
+                          copy_bytes_per_s=round(first["bytes_moved"] / (med["copy"] * 1e-3)),
+                          share_of_copy=round(med["copy"] / med["resample"], 4),
+                          source_seconds_per_s=round(first["recordings"] * first["frames"] / first["hz"] / (med["resample"] * 1e-3)))
+    text = json.dumps(line) + "\n"
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text)
+    sys.stdout.write(text)
+
+
 MIX_SEG_N = 32000             # the reference's shortest clip (transform_clips.py: min_allowable_length)
 
 
@@ -1543,6 +1629,11 @@ def mix_rir_seg_main(out_path):
 
 
 def main():
+    if "--resample-child" in sys.argv[1:]:
+        return resample_child()
+    if "--resample" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--resample"]
+        return resample_main(rest[0] if rest else os.path.join(ROOT, "profiles", "resample_bench_configs.jsonl"))
     if "--mix-pitch-child" in sys.argv[1:]:
         return mix_pitch_child()
     if "--mix-pitch" in sys.argv[1:]:
